@@ -14,8 +14,10 @@ RCCL).  `--shape c1` runs configs[1] (MSLR-WEB10K-shape, 1.2 M documents).
   python bench.py --gpus N --steps K --warmup W      N > 1: the script starts its own N ranks (torch.distributed.run, one per GPU)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...    (the same, launched from outside)
   --scaling weak: N x the shape's documents (the same documents per rank at every N) instead of the same set sharded
+  --dump-outputs DIR: after the timed steps, what the last one computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)
+  --full: everything else the benchmark measures (below); without it a run sets up, warms up, times the steps and prints the line
 
-Prints ONE JSON line on rank 0.  `roofline` is for the time-dominant kernel (the child-node histogram passes, rl::k_hist<false>):
+Prints ONE JSON line on rank 0.  With --full: `roofline` is for the time-dominant kernel (the child-node histogram passes, rl::k_hist<false>):
 algorithmic bytes per launch / HIP-event time of that launch measured live on the library's own stream, with the counter traffic
 (`traffic`, `frac_traffic`) beside SURVEY.md 8d's figure; `roofline.root_pass` is the root histogram (rl::k_hist<true>) likewise,
 `roofline.lds_atomic_calibration` the measured LDS atomic rates both kernels' atomics are a fraction of.
@@ -40,6 +42,39 @@ HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6290 GB/s 
 # 32-byte row gathers; WRITE_SIZE is exact.  Both in KB.
 FETCH_FACTOR_WIDE = 2.0
 FETCH_FACTOR_GATHER32 = 2.0
+
+DUMP_LIMIT_BYTES = 64 << 20
+SCORE_SAMPLE = 1 << 22        # --dump-outputs: scores of up to this many documents are written whole, of more a fixed sample of this many positions
+
+
+def host_threads():
+    """Threads for the CPU baselines: the CPUs this process may run on, capped by OMP_NUM_THREADS where the host sets it (a shared host hands a job
+    fewer CPUs than os.cpu_count() shows; more threads than that only slow the baseline down)."""
+    n = len(os.sched_getaffinity(0))
+    cap = int(os.environ.get("OMP_NUM_THREADS") or 0)
+    return min(n, cap) if cap > 0 else n
+
+
+def score_positions(n):
+    """--dump-outputs: None (all n scores are written) or the sorted positions of a fixed, seeded sample, the same in every run of the same arguments:
+    one position drawn in each of SCORE_SAMPLE equal slices of the n."""
+    import numpy as np
+    if n <= SCORE_SAMPLE:
+        return None
+    edges = np.arange(SCORE_SAMPLE + 1, dtype=np.int64) * n // SCORE_SAMPLE
+    return edges[:-1] + (np.random.default_rng(20240601).random(SCORE_SAMPLE) * np.diff(edges)).astype(np.int64)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array; integer outputs (tree structure, counts) are written as float64, which holds them exactly."""
+    import numpy as np
+    arrays = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in ((k, np.ascontiguousarray(v)) for k, v in arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def live_pmc(shape, rounds=4):
@@ -193,6 +228,12 @@ def bench_infer(args):
         elapsed = float(tt.item())
     ms = e0.elapsed_time(e1) / args.steps
     docs_per_s = n * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        pos = score_positions(n)
+        if pos is None:
+            dump_outputs(args.dump_outputs, {"scores": dO.cpu().numpy()})
+        else:
+            dump_outputs(args.dump_outputs, {"scores": dO[torch.from_numpy(pos).to(dO.device)].cpu().numpy(), "score_positions": pos})
     # --infer-ab VAR=v1,v2,..: the same rows with an environment knob of the kernel set to each value (one warm-up + `--steps` timed passes each), and
     # whether every value left the same score bits (RLHIP_EVAL_COMPACT=1,0: rank-coded against float cells)
     variants = {}
@@ -244,7 +285,7 @@ def bench_infer(args):
     }
     if args.cpu_rounds > 0:
         import oracle_ffi as O
-        threads = args.cpu_threads or (os.cpu_count() or 1)
+        threads = args.cpu_threads or host_threads()
         all_trees = [trees[i % len(trees)] for i in range(nt)]
         # a short probe sizes the timed sample to ~3 s of wall time on all host threads (thread start-up dominates shorter runs)
         probe = min(n, threads * 64)
@@ -344,14 +385,17 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--shape", default="c2", help="c0 | c1 | c1ns | c2 | c2ns | c3 (ranklib_amd.synth.SHAPES)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: CPU baseline, sustained run, node timing, membench, PMC passes, "
+                    "the c1 / c2 whole runs, the sharded leg and c2ns (the options below size them); without --full only the timed steps run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     ap.add_argument("--cpu-rounds", type=int, default=8, help="rounds timed for the CPU baseline (0 = skip)")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = all host cores (RankLib's default -thread)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use (RankLib's default -thread: all host cores)")
     ap.add_argument("--no-timing", action="store_true", help="do not record HIP events around the dominant kernel")
     ap.add_argument("--sustain", type=int, default=300, help="extra rounds after the timed region for config.sustained_rounds_per_s (0 = skip)")
     ap.add_argument("--node-rounds", type=int, default=10, help="extra rounds with HIP events around every child-node histogram launch (0 = skip)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes behind roofline.traffic")
     ap.add_argument("--sharded-one-rank", action="store_true", help="N = 1 only: run the sharded (multi-GPU) code path on a one-rank RCCL communicator")
-    ap.add_argument("--plain", action="store_true", help="timed region only: no CPU baseline, sustained run, node timing, membench or PMC passes")
+    ap.add_argument("--plain", action="store_true", help="timed region only, what a run without --full does (overrides --full)")
     ap.add_argument("--metric", default="NDCG", help="train metric: NDCG (the BASELINE.json metric) | DCG | ERR | MAP (RankLib's own default is ERR@10)")
     ap.add_argument("--first-tie", action="store_true", help="RL_FLAG_FIRST_TIE: exact ties keep the first candidate (no lazy Java-order tie-break)")
     ap.add_argument("--java-order", action="store_true", help="RL_FLAG_JAVA_ORDER: the strict mode (split gains from the Java's own f64 summation order)")
@@ -368,7 +412,10 @@ def main():
     ap.add_argument("--infer-train-rounds", type=int, default=100)
     ap.add_argument("--infer-ab", default="", help="infer: time the same rows with an environment knob at several values, e.g. RLHIP_EVAL_COMPACT=1,0")
     args = ap.parse_args()
-    if args.plain:
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.plain or not args.full:
+        args.plain = True
         args.cpu_rounds, args.sustain, args.node_rounds, args.no_pmc, args.no_timing, args.c1_trees, args.ns_rounds, args.c2_trees, args.shard1_rounds = 0, 0, 0, True, True, 0, 0, 0, 0
     if args.workload == "infer":
         if not any(a.startswith("--steps") for a in sys.argv):
@@ -464,6 +511,17 @@ def main():
     gs = g.array("GROW_STATS")
     gd = (g.array("GROW_DOCS").astype(np.float64) - gd0) / max(args.steps, 1)      # documents per round: built, partitioned, Java-left, Java-split
     ds = (g.dist_stats().astype(np.float64) - ds0) / max(args.steps, 1)             # exchange of this rank per round: all-reduce calls / bytes, all-gather calls / bytes
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed rounds receives for the last one: its tree, its train metric and the scores after it (rank 0's documents)
+        tree = g.get_tree(total_rounds - 1).trimmed()
+        scores = g.array("SCORE")
+        pos = score_positions(len(scores))
+        out_arrays = {"tree_" + k: v for k, v in tree.items()}
+        out_arrays["train_metric"] = np.array([ndcg_t], np.float32)
+        out_arrays["scores"] = scores if pos is None else scores[pos]
+        if pos is not None:
+            out_arrays["score_positions"] = pos
+        dump_outputs(args.dump_outputs, out_arrays)
 
     # ---- after the headline region: sustained rate over a long run, then a few rounds with events around every node-histogram launch
     sustained = None
@@ -771,7 +829,7 @@ def main():
 
     if args.cpu_rounds > 0 and world == 1:
         import oracle_ffi as O
-        threads = args.cpu_threads or (os.cpu_count() or 1)
+        threads = args.cpu_threads or host_threads()
         o = O.Oracle(X, lab, qoff, n_trees=args.cpu_rounds, n_leaves=n_leaves, n_threads=threads)
         tc = time.perf_counter()
         o.init()

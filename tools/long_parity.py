@@ -12,7 +12,7 @@ own and the final train and held-out NDCG@10 of both are printed (MetricScorer.s
 usage (GPU box; ~0.7 s a round at c1 and ~2.2 s at c2 on the box's host threads, i.e. 12 + 11 minutes):
     python tools/long_parity.py c1 1000
     python tools/long_parity.py c2 300
-The last line is one JSON object; the c1 x 1000 one is committed as profiles/r05_long_parity_c1.json and read by bench.py (config.c1_heldout_run)."""
+The last line is one JSON object; the c1 x 1000 one is committed as profiles/r05_long_parity_c1.json and read by bench.py --full (config.c1_heldout_run)."""
 import json
 import os
 import sys

@@ -3,7 +3,7 @@
 var=$1; vals=$2; shift 2
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for v in $vals; do
-  env $var=$v python $R/bench.py --no-pmc --cpu-rounds 0 --sustain 0 "$@" 2>/dev/null | python -c "
+  env $var=$v python $R/bench.py --full --no-pmc --cpu-rounds 0 --sustain 0 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d.get('kernel_ms_per_round',{})
