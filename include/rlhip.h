@@ -343,6 +343,65 @@ int rl_set_timing_flags(rl_trainer *t, int32_t flags);
 int rl_debug_membench(int32_t device, int32_t mode, int64_t bytes, int32_t stride, int32_t iters, double *avg_ms, double *alg_bytes);
 int rl_reset_timing(rl_trainer *t);
 
+/* ---- Coordinate Ascent (-ranker 4, learning/CoorAscent.java) ------------------------------------------------------------
+ * A linear ranker trained by rl_ca_learn: the whole learn() loop of CoorAscent.java:67-202 with the Java's double arithmetic kept
+ * bit for bit.  The trials of one search direction are evaluated in one pass on the GPU (rl_ca.hip); the keep / restore
+ * decisions, the weights and the feature shuffle (java.util.Random(seed), Collections.shuffle) live on the host.
+ * Train metrics: RL_METRIC_NDCG / DCG / MAP / ERR and, for this ranker only, P@k and RR@k. */
+enum { RL_METRIC_P = 4, RL_METRIC_RR = 5 };
+
+typedef struct rl_ca rl_ca;             /* opaque */
+
+typedef struct {
+    int32_t  n_restart;         /* CoorAscent.nRestart      default 5     (< 1: RL_ERR_INVALID; the Java ends in a NullPointerException) */
+    int32_t  n_max_iteration;   /* CoorAscent.nMaxIteration default 25 */
+    double   step_base;         /* CoorAscent.stepBase      default 0.05 */
+    double   step_scale;        /* CoorAscent.stepScale     default 2.0 */
+    double   tolerance;         /* CoorAscent.tolerance     default 0.001 */
+    int32_t  regularized;       /* CoorAscent.regularized   default 0 */
+    double   slack;             /* CoorAscent.slack         default 0.001 */
+    int32_t  metric;            /* RL_METRIC_*: NDCG, DCG, MAP, ERR, P, RR */
+    int32_t  metric_k;          /* the scorer's k (10; 0 for MAP) */
+    int32_t  device;            /* HIP device ordinal */
+    int64_t  seed;              /* the shuffles of one rl_ca_learn are drawn from ONE java.util.Random(seed) (the Java's is unseeded) */
+    double   err_max;           /* ERRScorer.MAX (-gmax): default 16 */
+} rl_ca_params;
+
+/* One record of rl_ca_learn's trace, in the order the Java does the work. */
+enum { RL_CA_RESTART = 0, RL_CA_PASS = 1, RL_CA_TRIAL = 2, RL_CA_SUCCESS = 3, RL_CA_VALID = 4 };
+typedef struct {
+    int32_t kind;               /* RL_CA_* */
+    int32_t restart;            /* 0-based restart */
+    int32_t feature;            /* index into the feature list (TRIAL / SUCCESS), else -1 */
+    int32_t dir;                /* 1, -1 or 0 (TRIAL), else 0 */
+    int32_t j;                  /* trial of the direction (TRIAL); pass number (PASS); else 0 */
+    int32_t improved;           /* TRIAL: the score beat the restart's best (the Java prints a log line) */
+    double  weight;             /* TRIAL: the feature's trial weight; SUCCESS: its weight after the L1 normalisation */
+    double  score;              /* RESTART: startScore; TRIAL: the score after any -reg penalty; SUCCESS: bestScore; VALID: the restart's
+                                   validation score */
+} rl_ca_trace_rec;
+
+void rl_ca_params_default(rl_ca_params *p);         /* CoorAscent.java:37-43, NDCG@10, device 0, seed 0, err_max 16 */
+int  rl_ca_create(const rl_ca_params *p, rl_ca **out);
+void rl_ca_destroy(rl_ca *c);
+/* X: [n_docs][n_features] row-major, column f = DataPoint.getFeatureValue(features[f]), as rl_set_train.  A +-Infinity cell is
+ * RL_ERR_UNSUPPORTED (the Java's cached scores turn NaN through 0 * Infinity). */
+int  rl_ca_set_train(rl_ca *c, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
+                     int32_t n_queries, const int32_t *qkey);
+int  rl_ca_set_validation(rl_ca *c, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
+                          const int32_t *qkey);
+int  rl_ca_set_external_judgments(rl_ca *c, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count);
+int  rl_ca_learn(rl_ca *c);
+int  rl_ca_get_weights(const rl_ca *c, double *w, int32_t cap);
+/* train: scorer.score(rank(samples)) of the final weights (not rounded); valid: the same on the validation set (0 without one) */
+int  rl_ca_scores(const rl_ca *c, double *train, double *valid);
+/* out may be NULL (only *n is set); at most cap records are written */
+int  rl_ca_trace(const rl_ca *c, rl_ca_trace_rec *out, int64_t cap, int64_t *n);
+/* CoorAscent.eval on the GPU: out[i] = 0.0 + w[0] * x[fid[0]] + w[1] * x[fid[1]] + ... in f64, feature order (CoorAscent.java:229-235).
+ * X rows as rl_model_predict's (column f holds feature ID f); an ID at or beyond row_stride reads 0. */
+int  rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weights, int32_t n_weights, const float *X, int64_t n_docs,
+                   int32_t row_stride, double *out);
+
 #ifdef __cplusplus
 }
 #endif

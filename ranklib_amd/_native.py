@@ -25,6 +25,23 @@ class RlParams(C.Structure):
 
 
 RL_METRIC = dict(NDCG=0, DCG=1, MAP=2, ERR=3)
+RL_CA_METRIC = dict(RL_METRIC, P=4, RR=5)      # Coordinate Ascent also trains on P@k and RR@k
+
+
+class RlCaParams(C.Structure):
+    _fields_ = [("n_restart", C.c_int32), ("n_max_iteration", C.c_int32), ("step_base", C.c_double), ("step_scale", C.c_double),
+                ("tolerance", C.c_double), ("regularized", C.c_int32), ("slack", C.c_double), ("metric", C.c_int32),
+                ("metric_k", C.c_int32), ("device", C.c_int32), ("seed", C.c_int64), ("err_max", C.c_double)]
+
+
+class RlCaTraceRec(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("restart", C.c_int32), ("feature", C.c_int32), ("dir", C.c_int32), ("j", C.c_int32),
+                ("improved", C.c_int32), ("weight", C.c_double), ("score", C.c_double)]
+
+
+CA_TRACE_DTYPE = np.dtype([("kind", np.int32), ("restart", np.int32), ("feature", np.int32), ("dir", np.int32), ("j", np.int32),
+                           ("improved", np.int32), ("weight", np.float64), ("score", np.float64)])
+CA_RESTART, CA_PASS, CA_TRIAL, CA_SUCCESS, CA_VALID = 0, 1, 2, 3, 4
 RL_RANKER = dict(MART=0, LAMBDAMART=6)
 
 
@@ -50,6 +67,8 @@ ABI_SYMBOLS = [
     "rl_model_predict", "rl_model_predict_device", "rl_dist_unique_id", "rl_dist_init", "rl_dist_init_callback", "rl_dist_stats", "rl_bin_stride", "rl_hist_features", "rl_quant_exponent", "rl_get_array", "rl_debug_exp", "rl_debug_rho", "rl_debug_float_chain",
     "rl_letor_parse", "rl_letor_info", "rl_letor_arrays", "rl_letor_rows", "rl_letor_destroy",
     "rl_get_timing", "rl_reset_timing", "rl_set_timing_flags", "rl_debug_membench", "rl_set_err_max", "rl_tree_capacity",
+    "rl_ca_params_default", "rl_ca_create", "rl_ca_destroy", "rl_ca_set_train", "rl_ca_set_validation", "rl_ca_set_external_judgments",
+    "rl_ca_learn", "rl_ca_get_weights", "rl_ca_scores", "rl_ca_trace", "rl_ca_predict",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -124,6 +143,20 @@ def lib():
     L.rl_set_err_max.argtypes = [C.c_double]
     L.rl_set_timing_flags.argtypes = [vp, i32]
     L.rl_debug_membench.argtypes = [i32, i32, i64, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_ca_create"):      # (A/B builds of older sources lack Coordinate Ascent)
+        L.rl_ca_params_default.argtypes = [C.POINTER(RlCaParams)]
+        L.rl_ca_params_default.restype = None
+        L.rl_ca_create.argtypes = [C.POINTER(RlCaParams), C.POINTER(vp)]
+        L.rl_ca_destroy.argtypes = [vp]
+        L.rl_ca_destroy.restype = None
+        L.rl_ca_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
+        L.rl_ca_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
+        L.rl_ca_set_external_judgments.argtypes = [vp, i32, vp, vp]
+        L.rl_ca_learn.argtypes = [vp]
+        L.rl_ca_get_weights.argtypes = [vp, vp, i32]
+        L.rl_ca_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.rl_ca_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.rl_ca_predict.argtypes = [i32, vp, vp, i32, vp, i64, i32, vp]
     _lib = L
     return L
 
@@ -515,3 +548,90 @@ class Model:
             self.close()
         except Exception:
             pass
+
+
+class CoorAscentTrainer:
+    """Thin object wrapper over the rl_ca handle: CoorAscent.learn() on one GPU (rl_ca.hip)."""
+
+    def __init__(self, n_restart=5, n_max_iteration=25, step_base=0.05, step_scale=2.0, tolerance=0.001, regularized=False, slack=0.001,
+                 metric="NDCG", metric_k=10, device=0, seed=0, err_max=16.0):
+        L = lib()
+        self.p = RlCaParams()
+        L.rl_ca_params_default(C.byref(self.p))
+        self.p.n_restart, self.p.n_max_iteration = int(n_restart), int(n_max_iteration)
+        self.p.step_base, self.p.step_scale, self.p.tolerance = float(step_base), float(step_scale), float(tolerance)
+        self.p.regularized, self.p.slack = 1 if regularized else 0, float(slack)
+        m = metric.upper()
+        if m not in RL_CA_METRIC:
+            raise RankLibError("rlhip: the Coordinate Ascent train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
+        self.p.metric, self.p.metric_k, self.p.device = RL_CA_METRIC[m], int(metric_k), int(device)
+        self.p.seed = ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)      # a Java long
+        self.p.err_max = float(err_max)
+        self.h = C.c_void_p()
+        check(L.rl_ca_create(C.byref(self.p), C.byref(self.h)))
+        self.F = 0
+        self.has_valid = False
+
+    def set_train(self, X, labels, qoff, qkey=None):
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        self.F = X.shape[1]
+        check(lib().rl_ca_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                    None if qk is None else qk.ctypes.data))
+
+    def set_validation(self, X, labels, qoff, qkey=None):
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        if X.shape[1] != self.F:
+            raise RankLibError("validation set must have the training set's feature columns")
+        check(lib().rl_ca_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                         None if qk is None else qk.ctypes.data))
+        self.has_valid = True
+
+    def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
+        idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
+        rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
+        check(lib().rl_ca_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
+                                                 None if rdc is None else rdc.ctypes.data))
+
+    def learn(self):
+        check(lib().rl_ca_learn(self.h))
+
+    def weights(self):
+        w = np.zeros(max(1, self.F), np.float64)
+        check(lib().rl_ca_get_weights(self.h, w.ctypes.data, len(w)))
+        return w[:self.F]
+
+    def scores(self):
+        ts, vs = C.c_double(0), C.c_double(0)
+        check(lib().rl_ca_scores(self.h, C.byref(ts), C.byref(vs)))
+        return ts.value, (vs.value if self.has_valid else None)
+
+    def trace(self):
+        """structured array (CA_TRACE_DTYPE): one record per restart, pass, trial, success and validation score, in the Java's order"""
+        n = C.c_int64(0)
+        check(lib().rl_ca_trace(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, CA_TRACE_DTYPE)
+        if n.value:
+            check(lib().rl_ca_trace(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().rl_ca_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ca_predict(feature_ids, weights, rows, device=0):
+    """CoorAscent.eval on the GPU: rows[:, f] holds feature ID f (column 0 unused, like DataPoint.fVals); f64 scores"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    fid = np.ascontiguousarray(feature_ids, dtype=np.int32)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    out = np.zeros(rows.shape[0], np.float64)
+    check(lib().rl_ca_predict(int(device), fid.ctypes.data, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0], rows.shape[1],
+                              out.ctypes.data))
+    return out

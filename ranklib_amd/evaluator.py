@@ -1,5 +1,5 @@
-"""Command line of the `-ranker 6` path: mirrors the flags of eval/Evaluator.java that reach LambdaMART
-(:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
+"""Command line of the `-ranker 6 / 0 / 8 / 4` paths: mirrors the flags of eval/Evaluator.java that reach LambdaMART, MART, Random
+Forests and Coordinate Ascent (:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
 
     python -m ranklib_amd.evaluator -train f -ranker 6 -metric2t NDCG@10 -tree 1000 -leaf 31 -save model.txt
     python -m ranklib_amd.evaluator -load model.txt -rank f -score out.txt
@@ -11,7 +11,7 @@ import sys
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
+from .learning import (CoorAscent, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
                        stable_desc_order)
 from .metric import ERRScorer, MetricScorerFactory
 
@@ -196,7 +196,7 @@ def main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 6|0|8 [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|6|0|8 [-r n -i n -tolerance t -reg slack] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f] [-rank f -indri out] [-score out]")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
@@ -248,7 +248,7 @@ def main(argv=None):
             if rt not in (0, 6):
                 raise RankLibError("%s cannot be bagged. Random Forests only supports MART/LambdaMART." % rt)
             RFRanker.rType = RankerType(rt)
-        elif a == "-seed": RFRanker.seed = FeatureHistogram.seed = int(nxt())               # rlhip extension: the Java draws are unseeded
+        elif a == "-seed": RFRanker.seed = FeatureHistogram.seed = CoorAscent.seed = int(nxt())     # rlhip extension: the Java draws are unseeded
         elif a == "-thread": nxt()                          # CPU thread pool of the reference: irrelevant here
         elif a == "-tts": ttSplit = float(nxt())            # :245-250
         elif a == "-tvs": tvSplit = float(nxt())
@@ -261,21 +261,27 @@ def main(argv=None):
         elif a == "-norm":                                   # :256-267
             Evaluator.nml = normalizer.create(nxt())
             Evaluator.normalize = True
-        elif a in ("-round", "-epoch", "-tolerance", "-reg", "-r", "-i",
+        elif a == "-r": CoorAscent.nRestart = int(nxt())                                     # :310-323
+        elif a == "-i": CoorAscent.nMaxIteration = int(nxt())
+        elif a == "-reg":
+            CoorAscent.slack = float(nxt())
+            CoorAscent.regularized = True
+        elif a == "-tolerance": CoorAscent.tolerance = float(nxt())                         # (also AdaRank.tolerance: out of scope)
+        elif a in ("-round", "-epoch",
                    "-layer", "-node", "-lr", "-noeq", "-max", "-l2"):
             # parameters of the other rankers / of flows that are out of scope: parsed (the reference's own test passes
             # -round -epoch to every ranker, test:eval/EvaluatorTest.java:207-220) and ignored
             if a != "-noeq":
                 nxt()
-        elif a == "-device": LambdaMART.device = int(nxt())
+        elif a == "-device": LambdaMART.device = CoorAscent.device = int(nxt())
         else:
             raise RankLibError("Unknown command-line parameter: " + args[i])     # :369-371 (incl. the documented -silent)
         i += 1
     if not testMetric:
         testMetric = trainMetric                            # :379-381
-    if trainFile and rankerType not in (0, 6, 8):
-        raise RankLibError("rlhip builds -ranker 6 (LambdaMART), -ranker 0 (MART) and -ranker 8 (Random Forests) only")
-    e = Evaluator(RankerType(rankerType) if rankerType in (0, 6, 8) else RankerType.LAMBDAMART, trainMetric, testMetric)
+    if trainFile and rankerType not in (0, 4, 6, 8):
+        raise RankLibError("rlhip builds -ranker 6 (LambdaMART), -ranker 0 (MART), -ranker 8 (Random Forests) and -ranker 4 (Coordinate Ascent) only")
+    e = Evaluator(RankerType(rankerType) if rankerType in (0, 4, 6, 8) else RankerType.LAMBDAMART, trainMetric, testMetric)
     if trainFile:
         if foldCV != -1:                                    # :469-482
             if kcvModelDir and not kcvModelFile:

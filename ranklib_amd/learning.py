@@ -7,6 +7,7 @@ RankLib's API read the same here:
     RankList                     learning/RankList.java:21-114
     Ranker (abstract)            learning/Ranker.java:36-186
     LambdaMART                   learning/tree/LambdaMART.java:33-329   (init/learn run on the GPU through librlhip.so)
+    CoorAscent                   learning/CoorAscent.java:33-396        (learn and eval run on the GPU through librlhip.so)
     RankerType / RankerFactory   learning/RankerType.java, learning/RankerFactory.java:36-118
     RankerTrainer                learning/RankerTrainer.java:23-56
 
@@ -632,6 +633,194 @@ class RFRanker(Ranker):
         logger.info("Learning rate: %s", java_float_str(cls.learningRate))
 
 
+class CoorAscent(Ranker):
+    """learning/CoorAscent.java: the linear ranker, learn() executed on an MI355X (librlhip.so rl_ca_*, every trial of a search direction
+    in one pass), eval() as the GPU's f64 dot product in feature order."""
+    # process-global parameters, like the Java statics (:37-43)
+    nRestart = 5
+    nMaxIteration = 25
+    stepBase = 0.05
+    stepScale = 2.0
+    tolerance = 0.001
+    regularized = False
+    slack = 0.001
+    seed = 0                          # not in the Java (Collections.shuffle on an unseeded Random): one java.util.Random(seed) per learn()
+    device = 0
+
+    def __init__(self, samples=None, features=None, scorer=None):
+        super().__init__(samples, features, scorer)
+        self.weight = None
+        self.trace = None             # structured array of the last learn() (_native.CA_TRACE_DTYPE)
+        self._trainer = None
+
+    def init(self):                   # :60-64
+        logger.info("Initializing... ")
+        self.weight = [1.0 / len(self.features)] * len(self.features)
+        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        if metric not in N.RL_CA_METRIC:
+            raise RankLibError("rlhip: the Coordinate Ascent train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
+                               % (self.scorer.name() if self.scorer else None))
+        cls = type(self)
+        X, lab, qoff, qkey = flatten(self.samples, self.features)
+        nk = int(qkey.max()) + 1 if len(qkey) else 0
+        t = N.CoorAscentTrainer(n_restart=cls.nRestart, n_max_iteration=cls.nMaxIteration, step_base=cls.stepBase, step_scale=cls.stepScale,
+                                tolerance=cls.tolerance, regularized=cls.regularized, slack=cls.slack, metric=metric,
+                                metric_k=self.scorer.getK(), device=cls.device, seed=cls.seed, err_max=ERRScorer.MAX)
+        t.set_train(X, lab, qoff, qkey=qkey)
+        if self.validationSamples is not None:
+            Xv, lv, qv, _ = flatten(self.validationSamples, self.features)
+            ids = {}
+            for q, rl in enumerate(self.samples):
+                ids.setdefault(rl.getID(), int(qkey[q]))
+            vkey = np.array([ids.setdefault(rl.getID(), nk + i) for i, rl in enumerate(self.validationSamples)], np.int32)
+            t.set_validation(Xv, lv, qv, qkey=vkey)
+        for validation, lists in ((False, self.samples), (True, self.validationSamples)):      # what the scorer object holds (see LambdaMART.init)
+            if lists is None:
+                continue
+            ideal = rdc = None
+            gains = getattr(self.scorer, "idealGains", None)
+            if metric == "NDCG" and gains:
+                ideal = np.array([gains.get(rl.getID(), np.nan) for rl in lists], np.float64)
+            counts = getattr(self.scorer, "relDocCount", None)
+            if metric == "MAP" and counts is not None:
+                rdc = np.array([counts.get(rl.getID(), 0) for rl in lists], np.int32)
+            if ideal is not None or rdc is not None:
+                t.set_external_judgments(validation, ideal, rdc)
+        self._trainer = t
+
+    def learn(self):                  # :67-202
+        cls = type(self)
+        t = self._trainer
+        logger.info("Training starts...")
+        t.learn()
+        nm = self.scorer.name()
+        self.trace = tr = t.trace()
+        best = None
+        for rec in tr:                # the Java's log, replayed from the trace
+            kind = int(rec["kind"])
+            if kind == N.CA_RESTART:
+                logger.info("[+] Random restart #%d/%d...", int(rec["restart"]) + 1, cls.nRestart)
+                best = float(rec["score"])
+            elif kind == N.CA_PASS:
+                logger.info("Shuffling features' order...")
+                logger.info("Optimizing weight vector... ")
+                self.printLogLn([7, 8, 7], ["Feature", "weight", nm])
+            elif kind == N.CA_TRIAL and rec["improved"]:
+                best = float(rec["score"])
+                w = float(rec["weight"])
+                bw = ("+" if w > 0 else "") + java_double_str(java_round(w, 4))
+                self.printLogLn([7, 8, 7], [str(self.features[int(rec["feature"])]), bw, java_double_str(java_round(best, 4))])
+        self.weight = [float(v) for v in t.weights()]
+        ts, vs = t.scores()
+        self.scoreOnTrainingData = java_round(ts, 4)
+        logger.info("Finished sucessfully.")
+        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
+        if vs is not None:
+            self.bestScoreOnValidationData = vs
+            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
+        t.close()
+        self._trainer = None
+
+    # --- scoring: 0.0 + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_ca_predict) -----------------
+    def _rows(self, dps):
+        fmax = max([int(f) for f in self.features] + [0])
+        width = max([fmax + 1] + [len(dp.fVals) for dp in dps])
+        rows = np.zeros((len(dps), width), np.float32)
+        for i, dp in enumerate(dps):
+            fv = dp.fVals
+            rows[i, :len(fv)] = np.where(np.isnan(fv), np.float32(0), fv)
+        if not DataPoint.missingZero:
+            for dp in dps:
+                for f in self.features:
+                    if f <= 0 or f >= len(dp.fVals):
+                        raise RankLibError("Error in DenseDataPoint::getFeatureValue(): requesting unspecified feature, fid=%d" % f)
+        return rows
+
+    def evalList(self, rl):
+        if rl.size() == 0:
+            return []
+        return [float(v) for v in N.ca_predict(self.features, self.weight, self._rows(rl.rl), type(self).device)]
+
+    def eval(self, dp):               # noqa: A003  :229-235
+        return self.evalList(RankList([dp]))[0]
+
+    def createNew(self):
+        return CoorAscent()
+
+    def toString(self):               # :243-249
+        return " ".join("%d:%s" % (f, java_double_str(w)) for f, w in zip(self.features, self.weight))
+
+    def model(self):                  # :252-264
+        cls = type(self)
+        out = "## " + self.name() + "\n"
+        out += "## Restart = %d\n" % cls.nRestart
+        out += "## MaxIteration = %d\n" % cls.nMaxIteration
+        out += "## StepBase = %s\n" % java_double_str(cls.stepBase)
+        out += "## StepScale = %s\n" % java_double_str(cls.stepScale)
+        out += "## Tolerance = %s\n" % java_double_str(cls.tolerance)
+        out += "## Regularized = %s\n" % ("true" if cls.regularized else "false")
+        out += "## Slack = %s\n" % java_double_str(cls.slack)
+        return out + self.toString()
+
+    def loadFromString(self, fullText):   # :267-296: the first non-empty line that is not "##", read by utilities/KeyValuePair.java
+        try:
+            line = None
+            for content in fullText.splitlines():
+                content = content.strip()
+                if not content or content.startswith("##"):
+                    continue
+                line = content
+                break
+            idx = line.rfind("#")
+            if idx != -1:
+                line = line[:idx].strip()
+            keys, values = [], []
+            for tok in line.split(" "):
+                tok = tok.strip()
+                if not tok:
+                    continue
+                keys.append(tok[:tok.index(":")])
+                values.append(tok[tok.rfind(":") + 1:])
+            self.features = [int(k) for k in keys]
+            self.weight = [float(v) for v in values]
+        except Exception as ex:       # noqa: BLE001 -- the reference wraps everything
+            raise RankLibError("Error in CoorAscent::load(): %s" % ex)
+
+    def printParameters(self):        # :298-308
+        cls = type(self)
+        logger.info("No. of random restarts: %d", cls.nRestart)
+        logger.info("No. of iterations to search in each direction: %d", cls.nMaxIteration)
+        logger.info("Tolerance: %s", java_double_str(cls.tolerance))
+        if cls.regularized:
+            logger.info("Reg. param: %s", java_double_str(cls.slack))
+        else:
+            logger.info("Regularization: No")
+
+    def name(self):
+        return "Coordinate Ascent"
+
+    @staticmethod
+    def getDistance(w1, w2):          # :350-364
+        s1 = s2 = 0.0
+        for a, b in zip(w1, w2):
+            s1 += abs(a)
+            s2 += abs(b)
+        dist = 0.0
+        for a, b in zip(w1, w2):
+            t = a / s1 - b / s2
+            dist += t * t
+        return math.sqrt(dist)
+
+    def copyModel(self, ranker):      # :384-391
+        if len(ranker.weight) != len(self.features):
+            raise RankLibError("These two models use different feature set!!")
+        self.weight = list(ranker.weight)
+        logger.info("Model loaded.")
+
+    def distance(self, ca):           # :393-395
+        return self.getDistance(self.weight, ca.weight)
+
+
 # ---------------------------------------------------------------------------------------------------------
 class RankerType(enum.Enum):          # learning/RankerType.java
     MART = 0
@@ -651,8 +840,9 @@ RFRanker.rType = RankerType.MART
 
 class RankerFactory:                  # learning/RankerFactory.java:36-118
     def __init__(self):
-        self.map = {"LAMBDAMART": LambdaMART, "MART": MART, "RANDOM_FOREST": RFRanker}
-        self.names = {"LAMBDAMART": "LAMBDAMART", "MART": "MART", "RANDOM FORESTS": "RANDOM_FOREST"}     # name().toUpperCase() -> type (:44-53)
+        self.map = {"LAMBDAMART": LambdaMART, "MART": MART, "RANDOM_FOREST": RFRanker, "COOR_ASCENT": CoorAscent}
+        self.names = {"LAMBDAMART": "LAMBDAMART", "MART": "MART", "RANDOM FORESTS": "RANDOM_FOREST",
+                      "COORDINATE ASCENT": "COOR_ASCENT"}     # name().toUpperCase() -> type (:44-53)
 
     def createRanker(self, rtype, samples=None, features=None, scorer=None):
         if isinstance(rtype, str):
@@ -661,7 +851,7 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
             except KeyError:
                 raise RankLibError("Could find the class \"%s\" you specified. Make sure the jar library is in your classpath." % rtype)
         if rtype.name not in self.map:
-            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART) and 8 (Random Forests) only; %s is out of scope (SURVEY.md 8)" % rtype.name)
+            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests) and 4 (Coordinate Ascent) only; %s is out of scope (SURVEY.md 8)" % rtype.name)
         r = self.map[rtype.name]()
         if samples is not None:
             r.setTrainingSet(samples)
@@ -673,7 +863,7 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
         first = fullText.split("\n", 1)[0]
         name = first.replace("## ", "").strip()
         if name.upper() not in self.names:
-            raise RankLibError("Model file does not start with '## LambdaMART', '## MART' or '## Random Forests' (got %r)" % first)
+            raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests' or '## Coordinate Ascent' (got %r)" % first)
         r = self.createRanker(RankerType[self.names[name.upper()]])
         r.loadFromString(fullText)
         return r
