@@ -402,6 +402,59 @@ int  rl_ca_trace(const rl_ca *c, rl_ca_trace_rec *out, int64_t cap, int64_t *n);
 int  rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weights, int32_t n_weights, const float *X, int64_t n_docs,
                    int32_t row_stride, double *out);
 
+/* ---- AdaRank (-ranker 3, learning/boosting/AdaRank.java) ---------------------------------------------------------------
+ * A linear ensemble of single-feature weak rankers trained by rl_ada_learn: the whole learn() loop of AdaRank.java:97-262 (both phases,
+ * rollbacks, "F. REM." removals, the best model on validation data) with the Java's double arithmetic kept bit for bit.
+ * The GPU builds the weak rankers' metric table once (each feature's metric on each list, the list ranked by utilities/Sorter's selection
+ * sort), evaluates the candidate sums of every round and ranks / scores the ensemble after each new term (rl_ca.hip's trial kernel);
+ * the selection, alpha (log), the sample weights (exp) and every decision live on the host.  Train metrics as rl_ca: NDCG, DCG, MAP, ERR,
+ * P, RR (BEST is RL_ERR_UNSUPPORTED).  A round whose alpha is not finite is RL_ERR_UNSUPPORTED (the Java goes on with Infinity / NaN). */
+typedef struct rl_ada rl_ada;           /* opaque */
+
+typedef struct {
+    int32_t  n_iteration;       /* AdaRank.nIteration       default 500 (-round) */
+    double   tolerance;         /* AdaRank.tolerance        default 0.002 (-tolerance) */
+    int32_t  train_with_enqueue;/* AdaRank.trainWithEnqueue default 1 (-noeq clears it) */
+    int32_t  max_sel_count;     /* AdaRank.maxSelCount      default 5 (-max) */
+    int32_t  metric;            /* RL_METRIC_*: NDCG, DCG, MAP, ERR, P, RR */
+    int32_t  metric_k;          /* the scorer's k (10; 0 for MAP) */
+    int32_t  device;            /* HIP device ordinal */
+    double   err_max;           /* ERRScorer.MAX (-gmax): default 16 */
+} rl_ada_params;
+
+/* One record of rl_ada_learn's trace, in the order the Java does the work. */
+enum { RL_ADA_ROUND = 0, RL_ADA_ROLLBACK = 1, RL_ADA_PHASE = 2 };
+enum { RL_ADA_OK = 0, RL_ADA_DAMN = 1, RL_ADA_FREM = 2 };
+typedef struct {
+    int32_t iteration;          /* the Java's t */
+    int32_t kind;               /* RL_ADA_* */
+    int32_t feature;            /* index into the feature list: ROUND / ROLLBACK the selected feature; PHASE the feature taken off the
+                                   queue (-1 for the first call of learn(t, withEnqueue)) */
+    int32_t status;             /* ROUND: RL_ADA_OK / DAMN / FREM; PHASE: withEnqueue (1 / 0); ROLLBACK: 0 */
+    double  alpha;              /* ROUND: alpha_t */
+    double  train_score;        /* ROUND: trainedScore (the ensemble's metric on the training data, not rounded) */
+    double  valid_score;        /* ROUND: scorer.score(rank(validationSamples)) (0 without a validation set) */
+} rl_ada_trace_rec;
+
+void rl_ada_params_default(rl_ada_params *p);       /* AdaRank.java:37-40, NDCG@10, device 0, err_max 16 */
+int  rl_ada_create(const rl_ada_params *p, rl_ada **out);
+void rl_ada_destroy(rl_ada *a);
+/* X as rl_ca_set_train (column f = DataPoint.getFeatureValue(features[f])); NaN and +-Infinity cells are refused as there */
+int  rl_ada_set_train(rl_ada *a, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
+                      int32_t n_queries, const int32_t *qkey);
+int  rl_ada_set_validation(rl_ada *a, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
+                           const int32_t *qkey);
+int  rl_ada_set_external_judgments(rl_ada *a, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count);
+int  rl_ada_learn(rl_ada *a);
+/* the final model: n_rankers (fid = feature index, repeats allowed) and weights in ensemble order; fid / weight may be NULL (only
+ * *n is set); at most cap entries are written */
+int  rl_ada_get_model(const rl_ada *a, int32_t *fid, double *weight, int32_t cap, int32_t *n);
+/* train: scorer.score(rank(samples)) of the final model (not rounded); valid: the same on the validation set (0 without one) */
+int  rl_ada_scores(const rl_ada *a, double *train, double *valid);
+int  rl_ada_trace(const rl_ada *a, rl_ada_trace_rec *out, int64_t cap, int64_t *n);
+/* debug: the weak-ranker table, out[f * n_queries + q] = scorer.score(WeakRanker(f).rank(list q)) (cap >= n_features * n_queries) */
+int  rl_ada_debug_weak_table(const rl_ada *a, double *out, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

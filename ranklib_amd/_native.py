@@ -42,6 +42,18 @@ class RlCaTraceRec(C.Structure):
 CA_TRACE_DTYPE = np.dtype([("kind", np.int32), ("restart", np.int32), ("feature", np.int32), ("dir", np.int32), ("j", np.int32),
                            ("improved", np.int32), ("weight", np.float64), ("score", np.float64)])
 CA_RESTART, CA_PASS, CA_TRIAL, CA_SUCCESS, CA_VALID = 0, 1, 2, 3, 4
+
+
+class RlAdaParams(C.Structure):
+    _fields_ = [("n_iteration", C.c_int32), ("tolerance", C.c_double), ("train_with_enqueue", C.c_int32), ("max_sel_count", C.c_int32),
+                ("metric", C.c_int32), ("metric_k", C.c_int32), ("device", C.c_int32), ("err_max", C.c_double)]
+
+
+ADA_TRACE_DTYPE = np.dtype([("iteration", np.int32), ("kind", np.int32), ("feature", np.int32), ("status", np.int32),
+                            ("alpha", np.float64), ("train_score", np.float64), ("valid_score", np.float64)])
+ADA_ROUND, ADA_ROLLBACK, ADA_PHASE = 0, 1, 2
+ADA_OK, ADA_DAMN, ADA_FREM = 0, 1, 2
+ADA_STATUS = {ADA_OK: "OK", ADA_DAMN: "DAMN", ADA_FREM: "F. REM."}
 RL_RANKER = dict(MART=0, LAMBDAMART=6)
 
 
@@ -69,6 +81,8 @@ ABI_SYMBOLS = [
     "rl_get_timing", "rl_reset_timing", "rl_set_timing_flags", "rl_debug_membench", "rl_set_err_max", "rl_tree_capacity",
     "rl_ca_params_default", "rl_ca_create", "rl_ca_destroy", "rl_ca_set_train", "rl_ca_set_validation", "rl_ca_set_external_judgments",
     "rl_ca_learn", "rl_ca_get_weights", "rl_ca_scores", "rl_ca_trace", "rl_ca_predict",
+    "rl_ada_params_default", "rl_ada_create", "rl_ada_destroy", "rl_ada_set_train", "rl_ada_set_validation", "rl_ada_set_external_judgments",
+    "rl_ada_learn", "rl_ada_get_model", "rl_ada_scores", "rl_ada_trace", "rl_ada_debug_weak_table",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -157,6 +171,20 @@ def lib():
         L.rl_ca_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_ca_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_ca_predict.argtypes = [i32, vp, vp, i32, vp, i64, i32, vp]
+    if hasattr(L, "rl_ada_create"):     # (A/B builds of older sources lack AdaRank)
+        L.rl_ada_params_default.argtypes = [C.POINTER(RlAdaParams)]
+        L.rl_ada_params_default.restype = None
+        L.rl_ada_create.argtypes = [C.POINTER(RlAdaParams), C.POINTER(vp)]
+        L.rl_ada_destroy.argtypes = [vp]
+        L.rl_ada_destroy.restype = None
+        L.rl_ada_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
+        L.rl_ada_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
+        L.rl_ada_set_external_judgments.argtypes = [vp, i32, vp, vp]
+        L.rl_ada_learn.argtypes = [vp]
+        L.rl_ada_get_model.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
+        L.rl_ada_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.rl_ada_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.rl_ada_debug_weak_table.argtypes = [vp, vp, i64]
     _lib = L
     return L
 
@@ -617,6 +645,88 @@ class CoorAscentTrainer:
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             lib().rl_ca_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AdaRankTrainer:
+    """Thin object wrapper over the rl_ada handle: AdaRank.learn() on one GPU (rl_ada.inc in rl_ca.hip)."""
+
+    def __init__(self, n_iteration=500, tolerance=0.002, train_with_enqueue=True, max_sel_count=5, metric="NDCG", metric_k=10, device=0,
+                 err_max=16.0):
+        L = lib()
+        self.p = RlAdaParams()
+        L.rl_ada_params_default(C.byref(self.p))
+        self.p.n_iteration, self.p.tolerance = int(n_iteration), float(tolerance)
+        self.p.train_with_enqueue, self.p.max_sel_count = 1 if train_with_enqueue else 0, int(max_sel_count)
+        m = metric.upper()
+        if m not in RL_CA_METRIC:
+            raise RankLibError("rlhip: the AdaRank train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
+        self.p.metric, self.p.metric_k, self.p.device, self.p.err_max = RL_CA_METRIC[m], int(metric_k), int(device), float(err_max)
+        self.h = C.c_void_p()
+        check(L.rl_ada_create(C.byref(self.p), C.byref(self.h)))
+        self.F = self.Q = 0
+        self.has_valid = False
+
+    def set_train(self, X, labels, qoff, qkey=None):
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        self.F, self.Q = X.shape[1], len(qoff) - 1
+        check(lib().rl_ada_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                     None if qk is None else qk.ctypes.data))
+
+    def set_validation(self, X, labels, qoff, qkey=None):
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        if X.shape[1] != self.F:
+            raise RankLibError("validation set must have the training set's feature columns")
+        check(lib().rl_ada_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                          None if qk is None else qk.ctypes.data))
+        self.has_valid = True
+
+    def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
+        idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
+        rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
+        check(lib().rl_ada_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
+                                                  None if rdc is None else rdc.ctypes.data))
+
+    def learn(self):
+        check(lib().rl_ada_learn(self.h))
+
+    def model(self):
+        """(feature indices, weights) of the final ensemble, in ensemble order (an index may repeat)"""
+        n = C.c_int32(0)
+        check(lib().rl_ada_get_model(self.h, None, None, 0, C.byref(n)))
+        fid, w = np.zeros(max(1, n.value), np.int32), np.zeros(max(1, n.value), np.float64)
+        check(lib().rl_ada_get_model(self.h, fid.ctypes.data, w.ctypes.data, n.value, C.byref(n)))
+        return fid[:n.value], w[:n.value]
+
+    def scores(self):
+        ts, vs = C.c_double(0), C.c_double(0)
+        check(lib().rl_ada_scores(self.h, C.byref(ts), C.byref(vs)))
+        return ts.value, (vs.value if self.has_valid else None)
+
+    def trace(self):
+        """structured array (ADA_TRACE_DTYPE): one record per phase start, round and rollback, in the Java's order"""
+        n = C.c_int64(0)
+        check(lib().rl_ada_trace(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, ADA_TRACE_DTYPE)
+        if n.value:
+            check(lib().rl_ada_trace(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def weak_table(self):
+        """[F, Q] f64: scorer.score(WeakRanker(f).rank(list q)) as the GPU built it"""
+        out = np.zeros((self.F, self.Q), np.float64)
+        check(lib().rl_ada_debug_weak_table(self.h, out.ctypes.data, out.size))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().rl_ada_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

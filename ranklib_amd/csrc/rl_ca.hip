@@ -798,3 +798,5 @@ int rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weig
 }
 
 }  // extern "C"
+
+#include "rl_ada.inc"      // AdaRank (-ranker 3): the same translation unit, so its kernels share ca_metric and k_ca_trials

@@ -11,7 +11,7 @@ import sys
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (CoorAscent, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
                        stable_desc_order)
 from .metric import ERRScorer, MetricScorerFactory
 
@@ -196,7 +196,7 @@ def main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|6|0|8 [-r n -i n -tolerance t -reg slack] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f] [-rank f -indri out] [-score out]")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
@@ -266,22 +266,23 @@ def main(argv=None):
         elif a == "-reg":
             CoorAscent.slack = float(nxt())
             CoorAscent.regularized = True
-        elif a == "-tolerance": CoorAscent.tolerance = float(nxt())                         # (also AdaRank.tolerance: out of scope)
-        elif a in ("-round", "-epoch",
-                   "-layer", "-node", "-lr", "-noeq", "-max", "-l2"):
+        elif a == "-tolerance": AdaRank.tolerance = CoorAscent.tolerance = float(nxt())
+        elif a == "-round": AdaRank.nIteration = int(nxt())                                 # :305-318
+        elif a == "-noeq": AdaRank.trainWithEnqueue = False
+        elif a == "-max": AdaRank.maxSelCount = int(nxt())
+        elif a in ("-epoch", "-layer", "-node", "-lr", "-l2"):
             # parameters of the other rankers / of flows that are out of scope: parsed (the reference's own test passes
             # -round -epoch to every ranker, test:eval/EvaluatorTest.java:207-220) and ignored
-            if a != "-noeq":
-                nxt()
-        elif a == "-device": LambdaMART.device = CoorAscent.device = int(nxt())
+            nxt()
+        elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = int(nxt())
         else:
             raise RankLibError("Unknown command-line parameter: " + args[i])     # :369-371 (incl. the documented -silent)
         i += 1
     if not testMetric:
         testMetric = trainMetric                            # :379-381
-    if trainFile and rankerType not in (0, 4, 6, 8):
-        raise RankLibError("rlhip builds -ranker 6 (LambdaMART), -ranker 0 (MART), -ranker 8 (Random Forests) and -ranker 4 (Coordinate Ascent) only")
-    e = Evaluator(RankerType(rankerType) if rankerType in (0, 4, 6, 8) else RankerType.LAMBDAMART, trainMetric, testMetric)
+    if trainFile and rankerType not in (0, 3, 4, 6, 8):
+        raise RankLibError("rlhip builds -ranker 6 (LambdaMART), -ranker 0 (MART), -ranker 8 (Random Forests), -ranker 4 (Coordinate Ascent) and -ranker 3 (AdaRank) only")
+    e = Evaluator(RankerType(rankerType) if rankerType in (0, 3, 4, 6, 8) else RankerType.LAMBDAMART, trainMetric, testMetric)
     if trainFile:
         if foldCV != -1:                                    # :469-482
             if kcvModelDir and not kcvModelFile:

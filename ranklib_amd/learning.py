@@ -8,6 +8,7 @@ RankLib's API read the same here:
     Ranker (abstract)            learning/Ranker.java:36-186
     LambdaMART                   learning/tree/LambdaMART.java:33-329   (init/learn run on the GPU through librlhip.so)
     CoorAscent                   learning/CoorAscent.java:33-396        (learn and eval run on the GPU through librlhip.so)
+    AdaRank                      learning/boosting/AdaRank.java:33-346  (learn and eval run on the GPU through librlhip.so)
     RankerType / RankerFactory   learning/RankerType.java, learning/RankerFactory.java:36-118
     RankerTrainer                learning/RankerTrainer.java:23-56
 
@@ -633,6 +634,71 @@ class RFRanker(Ranker):
         logger.info("Learning rate: %s", java_float_str(cls.learningRate))
 
 
+def _feed_linear_trainer(ranker, t, metric):
+    """The training / validation lists of a CoorAscent or AdaRank ranker into its rl_ca / rl_ada trainer t, with the NDCG ideal-DCG keys
+    shared across the two sets and the external judgments the scorer holds (see LambdaMART.init)."""
+    X, lab, qoff, qkey = flatten(ranker.samples, ranker.features)
+    nk = int(qkey.max()) + 1 if len(qkey) else 0
+    t.set_train(X, lab, qoff, qkey=qkey)
+    if ranker.validationSamples is not None:
+        Xv, lv, qv, _ = flatten(ranker.validationSamples, ranker.features)
+        ids = {}
+        for q, rl in enumerate(ranker.samples):
+            ids.setdefault(rl.getID(), int(qkey[q]))
+        vkey = np.array([ids.setdefault(rl.getID(), nk + i) for i, rl in enumerate(ranker.validationSamples)], np.int32)
+        t.set_validation(Xv, lv, qv, qkey=vkey)
+    for validation, lists in ((False, ranker.samples), (True, ranker.validationSamples)):      # what the scorer object holds
+        if lists is None:
+            continue
+        ideal = rdc = None
+        gains = getattr(ranker.scorer, "idealGains", None)
+        if metric == "NDCG" and gains:
+            ideal = np.array([gains.get(rl.getID(), np.nan) for rl in lists], np.float64)
+        counts = getattr(ranker.scorer, "relDocCount", None)
+        if metric == "MAP" and counts is not None:
+            rdc = np.array([counts.get(rl.getID(), 0) for rl in lists], np.int32)
+        if ideal is not None or rdc is not None:
+            t.set_external_judgments(validation, ideal, rdc)
+
+
+def _linear_rows(dps, fids):
+    """DataPoint rows for rl_ca_predict: column f = feature ID f (NaN read as 0), wide enough for every fid in fids"""
+    fmax = max([int(f) for f in fids] + [0])
+    width = max([fmax + 1] + [len(dp.fVals) for dp in dps])
+    rows = np.zeros((len(dps), width), np.float32)
+    for i, dp in enumerate(dps):
+        fv = dp.fVals
+        rows[i, :len(fv)] = np.where(np.isnan(fv), np.float32(0), fv)
+    if not DataPoint.missingZero:
+        for dp in dps:
+            for f in fids:
+                if f <= 0 or f >= len(dp.fVals):
+                    raise RankLibError("Error in DenseDataPoint::getFeatureValue(): requesting unspecified feature, fid=%d" % f)
+    return rows
+
+
+def _key_value_line(fullText):
+    """The first non-empty line that is not "##", split by utilities/KeyValuePair.java into (keys, values)"""
+    line = None
+    for content in fullText.splitlines():
+        content = content.strip()
+        if not content or content.startswith("##"):
+            continue
+        line = content
+        break
+    idx = line.rfind("#")
+    if idx != -1:
+        line = line[:idx].strip()
+    keys, values = [], []
+    for tok in line.split(" "):
+        tok = tok.strip()
+        if not tok:
+            continue
+        keys.append(tok[:tok.index(":")])
+        values.append(tok[tok.rfind(":") + 1:])
+    return keys, values
+
+
 class CoorAscent(Ranker):
     """learning/CoorAscent.java: the linear ranker, learn() executed on an MI355X (librlhip.so rl_ca_*, every trial of a search direction
     in one pass), eval() as the GPU's f64 dot product in feature order."""
@@ -661,31 +727,10 @@ class CoorAscent(Ranker):
             raise RankLibError("rlhip: the Coordinate Ascent train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
                                % (self.scorer.name() if self.scorer else None))
         cls = type(self)
-        X, lab, qoff, qkey = flatten(self.samples, self.features)
-        nk = int(qkey.max()) + 1 if len(qkey) else 0
         t = N.CoorAscentTrainer(n_restart=cls.nRestart, n_max_iteration=cls.nMaxIteration, step_base=cls.stepBase, step_scale=cls.stepScale,
                                 tolerance=cls.tolerance, regularized=cls.regularized, slack=cls.slack, metric=metric,
                                 metric_k=self.scorer.getK(), device=cls.device, seed=cls.seed, err_max=ERRScorer.MAX)
-        t.set_train(X, lab, qoff, qkey=qkey)
-        if self.validationSamples is not None:
-            Xv, lv, qv, _ = flatten(self.validationSamples, self.features)
-            ids = {}
-            for q, rl in enumerate(self.samples):
-                ids.setdefault(rl.getID(), int(qkey[q]))
-            vkey = np.array([ids.setdefault(rl.getID(), nk + i) for i, rl in enumerate(self.validationSamples)], np.int32)
-            t.set_validation(Xv, lv, qv, qkey=vkey)
-        for validation, lists in ((False, self.samples), (True, self.validationSamples)):      # what the scorer object holds (see LambdaMART.init)
-            if lists is None:
-                continue
-            ideal = rdc = None
-            gains = getattr(self.scorer, "idealGains", None)
-            if metric == "NDCG" and gains:
-                ideal = np.array([gains.get(rl.getID(), np.nan) for rl in lists], np.float64)
-            counts = getattr(self.scorer, "relDocCount", None)
-            if metric == "MAP" and counts is not None:
-                rdc = np.array([counts.get(rl.getID(), 0) for rl in lists], np.int32)
-            if ideal is not None or rdc is not None:
-                t.set_external_judgments(validation, ideal, rdc)
+        _feed_linear_trainer(self, t, metric)
         self._trainer = t
 
     def learn(self):                  # :67-202
@@ -723,18 +768,7 @@ class CoorAscent(Ranker):
 
     # --- scoring: 0.0 + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_ca_predict) -----------------
     def _rows(self, dps):
-        fmax = max([int(f) for f in self.features] + [0])
-        width = max([fmax + 1] + [len(dp.fVals) for dp in dps])
-        rows = np.zeros((len(dps), width), np.float32)
-        for i, dp in enumerate(dps):
-            fv = dp.fVals
-            rows[i, :len(fv)] = np.where(np.isnan(fv), np.float32(0), fv)
-        if not DataPoint.missingZero:
-            for dp in dps:
-                for f in self.features:
-                    if f <= 0 or f >= len(dp.fVals):
-                        raise RankLibError("Error in DenseDataPoint::getFeatureValue(): requesting unspecified feature, fid=%d" % f)
-        return rows
+        return _linear_rows(dps, self.features)
 
     def evalList(self, rl):
         if rl.size() == 0:
@@ -764,23 +798,7 @@ class CoorAscent(Ranker):
 
     def loadFromString(self, fullText):   # :267-296: the first non-empty line that is not "##", read by utilities/KeyValuePair.java
         try:
-            line = None
-            for content in fullText.splitlines():
-                content = content.strip()
-                if not content or content.startswith("##"):
-                    continue
-                line = content
-                break
-            idx = line.rfind("#")
-            if idx != -1:
-                line = line[:idx].strip()
-            keys, values = [], []
-            for tok in line.split(" "):
-                tok = tok.strip()
-                if not tok:
-                    continue
-                keys.append(tok[:tok.index(":")])
-                values.append(tok[tok.rfind(":") + 1:])
+            keys, values = _key_value_line(fullText)
             self.features = [int(k) for k in keys]
             self.weight = [float(v) for v in values]
         except Exception as ex:       # noqa: BLE001 -- the reference wraps everything
@@ -821,6 +839,114 @@ class CoorAscent(Ranker):
         return self.getDistance(self.weight, ca.weight)
 
 
+class AdaRank(Ranker):
+    """learning/boosting/AdaRank.java: a linear ensemble of single-feature weak rankers, learn() executed on an MI355X (librlhip.so
+    rl_ada_*: the weak rankers' metric table once, then a candidate pass and one ranking of the ensemble per round), eval() as the GPU's
+    f64 sum in ensemble order."""
+    # process-global parameters, like the Java statics (:37-40)
+    nIteration = 500
+    tolerance = 0.002
+    trainWithEnqueue = True
+    maxSelCount = 5
+    device = 0
+
+    def __init__(self, samples=None, features=None, scorer=None):
+        super().__init__(samples, features, scorer)
+        self.rankers = []             # the weak rankers' feature IDs (WeakRanker.getFID), in ensemble order; may repeat
+        self.rweight = []
+        self.trace = None             # structured array of the last learn() (_native.ADA_TRACE_DTYPE)
+        self._trainer = None
+
+    def init(self):                   # :205-227
+        logger.info("Initializing... ")
+        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        if metric not in N.RL_CA_METRIC:
+            raise RankLibError("rlhip: the AdaRank train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
+                               % (self.scorer.name() if self.scorer else None))
+        cls = type(self)
+        t = N.AdaRankTrainer(n_iteration=cls.nIteration, tolerance=cls.tolerance, train_with_enqueue=cls.trainWithEnqueue,
+                             max_sel_count=cls.maxSelCount, metric=metric, metric_k=self.scorer.getK(), device=cls.device,
+                             err_max=ERRScorer.MAX)
+        _feed_linear_trainer(self, t, metric)
+        self.rankers, self.rweight = [], []
+        self._trainer = t
+
+    def learn(self):                  # :230-262
+        t = self._trainer
+        logger.info("Training starts...")
+        nm = self.scorer.name()
+        self.printLogLn([7, 8, 9, 9, 9], ["#iter", "Sel. F.", nm + "-T", nm + "-V", "Status"])
+        try:
+            t.learn()
+        finally:
+            self.trace = tr = t.trace()
+            for rec in tr:            # the Java's log, replayed from the trace
+                kind, fid = int(rec["kind"]), (self.features[int(rec["feature"])] if rec["feature"] >= 0 else -1)
+                if kind == N.ADA_ROLLBACK:
+                    self.printLog([7], [str(int(rec["iteration"]))])
+                    self.printLogLn([8, 9, 9, 9], [str(fid), "", "", "ROLLBACK"])
+                elif kind == N.ADA_ROUND:
+                    self.printLog([7], [str(int(rec["iteration"]))])
+                    self.printLog([8, 9], [str(fid), java_double_str(java_round(float(rec["train_score"]), 4))])
+                    vs = java_double_str(java_round(float(rec["valid_score"]), 4)) if t.has_valid else ""
+                    self.printLogLn([9, 9], [vs, N.ADA_STATUS[int(rec["status"])]])
+        cols, w = t.model()
+        self.rankers = [int(self.features[int(c)]) for c in cols]
+        self.rweight = [float(v) for v in w]
+        ts, vs = t.scores()
+        self.scoreOnTrainingData = java_round(ts, 4)
+        logger.info("Finished sucessfully.")
+        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
+        if vs is not None:
+            self.bestScoreOnValidationData = vs
+            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
+        t.close()
+        self._trainer = None
+
+    # --- scoring: 0.0 + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_ca_predict, repeated fids) -----------------
+    def evalList(self, rl):
+        if rl.size() == 0:
+            return []
+        return [float(v) for v in N.ca_predict(self.rankers, self.rweight, _linear_rows(rl.rl, self.rankers), type(self).device)]
+
+    def eval(self, dp):               # noqa: A003  :265-271
+        return self.evalList(RankList([dp]))[0]
+
+    def createNew(self):
+        return AdaRank()
+
+    def toString(self):               # :279-285
+        return " ".join("%d:%s" % (f, java_double_str(w)) for f, w in zip(self.rankers, self.rweight))
+
+    def model(self):                  # :288-297
+        cls = type(self)
+        out = "## " + self.name() + "\n"
+        out += "## Iteration = %d\n" % cls.nIteration
+        out += "## Train with enqueue: %s\n" % ("Yes" if cls.trainWithEnqueue else "No")
+        out += "## Tolerance = %s\n" % java_double_str(cls.tolerance)
+        out += "## Max consecutive selection count = %d\n" % cls.maxSelCount
+        return out + self.toString()
+
+    def loadFromString(self, fullText):   # :300-332
+        try:
+            keys, values = _key_value_line(fullText)
+            self.features = [int(k) for k in keys]
+            self.rankers = list(self.features)
+            self.rweight = [float(v) for v in values]
+        except Exception as ex:       # noqa: BLE001 -- the reference wraps everything
+            raise RankLibError("Error in AdaRank::load(): %s" % ex)
+
+    def printParameters(self):        # :335-340
+        cls = type(self)
+        logger.info("No. of rounds: %d", cls.nIteration)
+        logger.info("Train with 'enequeue': %s", "Yes" if cls.trainWithEnqueue else "No")
+        logger.info("Tolerance: %s", java_double_str(cls.tolerance))
+        logger.info("Max Sel. Count: %d", cls.maxSelCount)
+
+    def name(self):
+        return "AdaRank"
+
+
 # ---------------------------------------------------------------------------------------------------------
 class RankerType(enum.Enum):          # learning/RankerType.java
     MART = 0
@@ -840,9 +966,9 @@ RFRanker.rType = RankerType.MART
 
 class RankerFactory:                  # learning/RankerFactory.java:36-118
     def __init__(self):
-        self.map = {"LAMBDAMART": LambdaMART, "MART": MART, "RANDOM_FOREST": RFRanker, "COOR_ASCENT": CoorAscent}
+        self.map = {"LAMBDAMART": LambdaMART, "MART": MART, "RANDOM_FOREST": RFRanker, "COOR_ASCENT": CoorAscent, "ADARANK": AdaRank}
         self.names = {"LAMBDAMART": "LAMBDAMART", "MART": "MART", "RANDOM FORESTS": "RANDOM_FOREST",
-                      "COORDINATE ASCENT": "COOR_ASCENT"}     # name().toUpperCase() -> type (:44-53)
+                      "COORDINATE ASCENT": "COOR_ASCENT", "ADARANK": "ADARANK"}     # name().toUpperCase() -> type (:44-53)
 
     def createRanker(self, rtype, samples=None, features=None, scorer=None):
         if isinstance(rtype, str):
@@ -851,7 +977,7 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
             except KeyError:
                 raise RankLibError("Could find the class \"%s\" you specified. Make sure the jar library is in your classpath." % rtype)
         if rtype.name not in self.map:
-            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests) and 4 (Coordinate Ascent) only; %s is out of scope (SURVEY.md 8)" % rtype.name)
+            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent) and 3 (AdaRank) only; %s is out of scope (SURVEY.md 8)" % rtype.name)
         r = self.map[rtype.name]()
         if samples is not None:
             r.setTrainingSet(samples)
@@ -863,7 +989,7 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
         first = fullText.split("\n", 1)[0]
         name = first.replace("## ", "").strip()
         if name.upper() not in self.names:
-            raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests' or '## Coordinate Ascent' (got %r)" % first)
+            raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests', '## Coordinate Ascent' or '## AdaRank' (got %r)" % first)
         r = self.createRanker(RankerType[self.names[name.upper()]])
         r.loadFromString(fullText)
         return r
