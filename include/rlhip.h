@@ -455,6 +455,64 @@ int  rl_ada_trace(const rl_ada *a, rl_ada_trace_rec *out, int64_t cap, int64_t *
 /* debug: the weak-ranker table, out[f * n_queries + q] = scorer.score(WeakRanker(f).rank(list q)) (cap >= n_features * n_queries) */
 int  rl_ada_debug_weak_table(const rl_ada *a, double *out, int64_t cap);
 
+/* ---- RankBoost (-ranker 2, learning/boosting/RankBoost.java) -----------------------------------------------------------
+ * An ensemble of threshold weak rankers h(x) = [x[fid] > threshold] trained by rl_rb_learn: all of RankBoost.init() and learn()
+ * (:143-346) with the Java's double arithmetic kept bit for bit.  The training lists are put into getCorrectRanking()'s
+ * order (utilities/Sorter's unstable selection sort on the labels) by rl_rb_set_train; pair indices, the train metric's tie order and
+ * rl_rb_debug_potentials refer to that order.  The GPU keeps one weight per crucial pair (label_j > label_k), computes the potentials,
+ * the candidates' serial r chains (one per feature, staged through LDS), the pair update with the Z_t chain and both metrics of every
+ * round; the arg-max over (feature, threshold), alpha_t (log) and exp(+-alpha_t) live on the host.  Train metrics as rl_ca.  A training
+ * set without a crucial pair, a round whose alpha_t, Z_t or exp(alpha_t) is not finite (or Z_t == 0) and a pair table that does not
+ * fit are RL_ERR_UNSUPPORTED. */
+typedef struct rl_rb rl_rb;             /* opaque */
+
+typedef struct {
+    int32_t  n_iteration;       /* RankBoost.nIteration default 300 (-round) */
+    int32_t  n_threshold;       /* RankBoost.nThreshold default 10 (-tc); <= 0: every feature value is a candidate */
+    int32_t  metric;            /* RL_METRIC_*: NDCG, DCG, MAP, ERR, P, RR */
+    int32_t  metric_k;          /* the scorer's k (10; 0 for MAP) */
+    int32_t  device;            /* HIP device ordinal */
+    int32_t  keep_potentials;   /* debug: the potentials of rounds 1 .. keep_potentials stay readable (default 0) */
+    double   err_max;           /* ERRScorer.MAX (-gmax): default 16 */
+} rl_rb_params;
+
+/* One record per round of rl_rb_learn. */
+typedef struct {
+    int32_t iteration;          /* the Java's t */
+    int32_t feature;            /* index into the feature list of the selected weak ranker */
+    double  threshold;          /* its threshold */
+    double  max_r;              /* maxR of learnWeakRanker (:96-141) */
+    double  r_t;                /* R_t = Z_{t-1} * maxR */
+    double  alpha;              /* alpha_t */
+    double  z_t;                /* Z_t: the serial sum of the updated pair weights */
+    double  train_score;        /* scorer.score(rank(samples)) after the round (not rounded) */
+    double  valid_score;        /* the same on the validation set (0 without one) */
+} rl_rb_trace_rec;
+
+void rl_rb_params_default(rl_rb_params *p);         /* RankBoost.java:38-39, NDCG@10, device 0, err_max 16 */
+int  rl_rb_create(const rl_rb_params *p, rl_rb **out);
+void rl_rb_destroy(rl_rb *r);
+/* X as rl_ca_set_train (column f = DataPoint.getFeatureValue(features[f])); NaN and +-Infinity cells are refused as there */
+int  rl_rb_set_train(rl_rb *r, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
+                     int32_t n_queries, const int32_t *qkey);
+int  rl_rb_set_validation(rl_rb *r, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
+                          const int32_t *qkey);
+int  rl_rb_set_external_judgments(rl_rb *r, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count);
+int  rl_rb_learn(rl_rb *r);
+/* the final model: n weak rankers (fid = feature index, repeats allowed), thresholds and weights in ensemble order; the arrays may be
+ * NULL (only *n is set); at most cap entries are written */
+int  rl_rb_get_model(const rl_rb *r, int32_t *fid, double *threshold, double *weight, int32_t cap, int32_t *n);
+/* train: scorer.score(rank(samples)) of the final model (not rounded); valid: the same on the validation set (0 without one) */
+int  rl_rb_scores(const rl_rb *r, double *train, double *valid);
+int  rl_rb_trace(const rl_rb *r, rl_rb_trace_rec *out, int64_t cap, int64_t *n);
+/* debug: potential[list][doc] as updatePotential (:75-89) left it in round `round` (1 .. keep_potentials), n_docs doubles, the
+ * documents of each list in getCorrectRanking()'s order */
+int  rl_rb_debug_potentials(const rl_rb *r, int32_t round, double *out, int64_t cap);
+/* RankBoost.eval on the GPU: out[i] = 0.0 + w[0] * [x[fid[0]] > thr[0]] + w[1] * [x[fid[1]] > thr[1]] + ... in f64, ensemble order
+ * (RankBoost.java:348-355).  X rows as rl_ca_predict's; an ID at or beyond row_stride reads 0. */
+int  rl_rb_predict(int32_t device, const int32_t *feature_ids, const double *thresholds, const double *weights, int32_t n_rankers,
+                   const float *X, int64_t n_docs, int32_t row_stride, double *out);
+
 #ifdef __cplusplus
 }
 #endif

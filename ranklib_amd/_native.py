@@ -54,6 +54,16 @@ ADA_TRACE_DTYPE = np.dtype([("iteration", np.int32), ("kind", np.int32), ("featu
 ADA_ROUND, ADA_ROLLBACK, ADA_PHASE = 0, 1, 2
 ADA_OK, ADA_DAMN, ADA_FREM = 0, 1, 2
 ADA_STATUS = {ADA_OK: "OK", ADA_DAMN: "DAMN", ADA_FREM: "F. REM."}
+
+
+class RlRbParams(C.Structure):
+    _fields_ = [("n_iteration", C.c_int32), ("n_threshold", C.c_int32), ("metric", C.c_int32), ("metric_k", C.c_int32),
+                ("device", C.c_int32), ("keep_potentials", C.c_int32), ("err_max", C.c_double)]
+
+
+RB_TRACE_DTYPE = np.dtype([("iteration", np.int32), ("feature", np.int32), ("threshold", np.float64), ("max_r", np.float64),
+                           ("r_t", np.float64), ("alpha", np.float64), ("z_t", np.float64), ("train_score", np.float64),
+                           ("valid_score", np.float64)])
 RL_RANKER = dict(MART=0, LAMBDAMART=6)
 
 
@@ -83,6 +93,8 @@ ABI_SYMBOLS = [
     "rl_ca_learn", "rl_ca_get_weights", "rl_ca_scores", "rl_ca_trace", "rl_ca_predict",
     "rl_ada_params_default", "rl_ada_create", "rl_ada_destroy", "rl_ada_set_train", "rl_ada_set_validation", "rl_ada_set_external_judgments",
     "rl_ada_learn", "rl_ada_get_model", "rl_ada_scores", "rl_ada_trace", "rl_ada_debug_weak_table",
+    "rl_rb_params_default", "rl_rb_create", "rl_rb_destroy", "rl_rb_set_train", "rl_rb_set_validation", "rl_rb_set_external_judgments",
+    "rl_rb_learn", "rl_rb_get_model", "rl_rb_scores", "rl_rb_trace", "rl_rb_debug_potentials", "rl_rb_predict",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -185,6 +197,21 @@ def lib():
         L.rl_ada_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_ada_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_ada_debug_weak_table.argtypes = [vp, vp, i64]
+    if hasattr(L, "rl_rb_create"):      # (A/B builds of older sources lack RankBoost)
+        L.rl_rb_params_default.argtypes = [C.POINTER(RlRbParams)]
+        L.rl_rb_params_default.restype = None
+        L.rl_rb_create.argtypes = [C.POINTER(RlRbParams), C.POINTER(vp)]
+        L.rl_rb_destroy.argtypes = [vp]
+        L.rl_rb_destroy.restype = None
+        L.rl_rb_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
+        L.rl_rb_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
+        L.rl_rb_set_external_judgments.argtypes = [vp, i32, vp, vp]
+        L.rl_rb_learn.argtypes = [vp]
+        L.rl_rb_get_model.argtypes = [vp, vp, vp, vp, i32, C.POINTER(i32)]
+        L.rl_rb_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.rl_rb_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.rl_rb_debug_potentials.argtypes = [vp, i32, vp, i64]
+        L.rl_rb_predict.argtypes = [i32, vp, vp, vp, i32, vp, i64, i32, vp]
     _lib = L
     return L
 
@@ -734,6 +761,99 @@ class AdaRankTrainer:
             self.close()
         except Exception:
             pass
+
+
+class RankBoostTrainer:
+    """Thin object wrapper over the rl_rb handle: RankBoost.init() and learn() on one GPU (rl_rb.inc in rl_ca.hip)."""
+
+    def __init__(self, n_iteration=300, n_threshold=10, metric="NDCG", metric_k=10, device=0, err_max=16.0, keep_potentials=0):
+        L = lib()
+        self.p = RlRbParams()
+        L.rl_rb_params_default(C.byref(self.p))
+        self.p.n_iteration, self.p.n_threshold, self.p.keep_potentials = int(n_iteration), int(n_threshold), int(keep_potentials)
+        m = metric.upper()
+        if m not in RL_CA_METRIC:
+            raise RankLibError("rlhip: the RankBoost train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
+        self.p.metric, self.p.metric_k, self.p.device, self.p.err_max = RL_CA_METRIC[m], int(metric_k), int(device), float(err_max)
+        self.h = C.c_void_p()
+        check(L.rl_rb_create(C.byref(self.p), C.byref(self.h)))
+        self.F = self.Q = self.N = 0
+        self.has_valid = False
+
+    def set_train(self, X, labels, qoff, qkey=None):
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        self.F, self.Q, self.N = X.shape[1], len(qoff) - 1, X.shape[0]
+        check(lib().rl_rb_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                    None if qk is None else qk.ctypes.data))
+
+    def set_validation(self, X, labels, qoff, qkey=None):
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        if X.shape[1] != self.F:
+            raise RankLibError("validation set must have the training set's feature columns")
+        check(lib().rl_rb_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                         None if qk is None else qk.ctypes.data))
+        self.has_valid = True
+
+    def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
+        idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
+        rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
+        check(lib().rl_rb_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
+                                                 None if rdc is None else rdc.ctypes.data))
+
+    def learn(self):
+        check(lib().rl_rb_learn(self.h))
+
+    def model(self):
+        """(feature indices, thresholds, weights) of the final ensemble, in ensemble order (an index may repeat)"""
+        n = C.c_int32(0)
+        check(lib().rl_rb_get_model(self.h, None, None, None, 0, C.byref(n)))
+        m = max(1, n.value)
+        fid, thr, w = np.zeros(m, np.int32), np.zeros(m, np.float64), np.zeros(m, np.float64)
+        check(lib().rl_rb_get_model(self.h, fid.ctypes.data, thr.ctypes.data, w.ctypes.data, n.value, C.byref(n)))
+        return fid[:n.value], thr[:n.value], w[:n.value]
+
+    def scores(self):
+        ts, vs = C.c_double(0), C.c_double(0)
+        check(lib().rl_rb_scores(self.h, C.byref(ts), C.byref(vs)))
+        return ts.value, (vs.value if self.has_valid else None)
+
+    def trace(self):
+        """structured array (RB_TRACE_DTYPE): one record per round"""
+        n = C.c_int64(0)
+        check(lib().rl_rb_trace(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, RB_TRACE_DTYPE)
+        if n.value:
+            check(lib().rl_rb_trace(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def potentials(self, round):       # noqa: A002
+        """[N] f64: the potentials of round `round` (1 .. keep_potentials), every list in getCorrectRanking()'s order"""
+        out = np.zeros(self.N, np.float64)
+        check(lib().rl_rb_debug_potentials(self.h, int(round), out.ctypes.data, out.size))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().rl_rb_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rb_predict(feature_ids, thresholds, weights, rows, device=0):
+    """RankBoost.eval on the GPU: rows[:, f] holds feature ID f (column 0 unused, like DataPoint.fVals); f64 scores"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    fid = np.ascontiguousarray(feature_ids, dtype=np.int32)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    out = np.zeros(rows.shape[0], np.float64)
+    check(lib().rl_rb_predict(int(device), fid.ctypes.data, thr.ctypes.data, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0],
+                              rows.shape[1], out.ctypes.data))
+    return out
 
 
 def ca_predict(feature_ids, weights, rows, device=0):

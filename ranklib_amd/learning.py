@@ -947,6 +947,124 @@ class AdaRank(Ranker):
         return "AdaRank"
 
 
+class RankBoost(Ranker):
+    """learning/boosting/RankBoost.java: an ensemble of threshold weak rankers (RBWeakRanker: 1 if x[fid] > threshold else 0), init() and
+    learn() executed on an MI355X (librlhip.so rl_rb_*: the crucial pairs' weights, the potentials, the candidate chains, the Z_t chain
+    and the metrics of every round), eval() as the GPU's f64 sum in ensemble order."""
+    # process-global parameters, like the Java statics (:38-39)
+    nIteration = 300
+    nThreshold = 10
+    device = 0
+
+    def __init__(self, samples=None, features=None, scorer=None):
+        super().__init__(samples, features, scorer)
+        self.wRankers = []            # (fid, threshold) of the weak rankers, in ensemble order; a fid may repeat
+        self.rWeight = []
+        self.trace = None             # structured array of the last learn() (_native.RB_TRACE_DTYPE)
+        self._trainer = None
+
+    def init(self):                   # :143-263
+        logger.info("Initializing... ")
+        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        if metric not in N.RL_CA_METRIC:
+            raise RankLibError("rlhip: the RankBoost train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
+                               % (self.scorer.name() if self.scorer else None))
+        cls = type(self)
+        t = N.RankBoostTrainer(n_iteration=cls.nIteration, n_threshold=cls.nThreshold, metric=metric, metric_k=self.scorer.getK(),
+                               device=cls.device, err_max=ERRScorer.MAX)
+        _feed_linear_trainer(self, t, metric)
+        self.wRankers, self.rWeight = [], []
+        self._trainer = t
+
+    def learn(self):                  # :265-346
+        t = self._trainer
+        logger.info("Training starts...")
+        nm = self.scorer.name()
+        self.printLogLn([7, 8, 9, 9, 9, 9], ["#iter", "Sel. F.", "Threshold", "Error", nm + "-T", nm + "-V"])
+        try:
+            t.learn()
+        finally:
+            self.trace = tr = t.trace()
+            for rec in tr:            # the Java's log, replayed from the trace
+                self.printLog([7, 8, 9, 9], [str(int(rec["iteration"])), str(self.features[int(rec["feature"])]),
+                                             java_double_str(java_round(float(rec["threshold"]), 4)),
+                                             java_double_str(java_round(float(rec["r_t"]), 4))])
+                self.printLog([9], [java_double_str(java_round(float(rec["train_score"]), 4))])
+                if t.has_valid:
+                    self.printLog([9], [java_double_str(java_round(float(rec["valid_score"]), 4))])
+                self.flushLog()
+        cols, thr, w = t.model()
+        self.wRankers = [(int(self.features[int(c)]), float(v)) for c, v in zip(cols, thr)]
+        self.rWeight = [float(v) for v in w]
+        ts, vs = t.scores()
+        self.scoreOnTrainingData = java_round(ts, 4)
+        logger.info("Finished sucessfully.")
+        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
+        if vs is not None:
+            self.bestScoreOnValidationData = vs
+            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
+        t.close()
+        self._trainer = None
+
+    # --- scoring: 0.0 + w[0] h_0(x) + w[1] h_1(x) + ... in f64 on the GPU (rl_rb_predict, repeated fids) ---------------
+    def evalList(self, rl):
+        if rl.size() == 0:
+            return []
+        fids = [f for f, _ in self.wRankers]
+        return [float(v) for v in N.rb_predict(fids, [t for _, t in self.wRankers], self.rWeight, _linear_rows(rl.rl, fids),
+                                               type(self).device)]
+
+    def eval(self, dp):               # noqa: A003  :348-355
+        return self.evalList(RankList([dp]))[0]
+
+    def createNew(self):
+        return RankBoost()
+
+    def toString(self):               # :362-369
+        return " ".join("%d:%s:%s" % (f, java_double_str(t), java_double_str(w)) for (f, t), w in zip(self.wRankers, self.rWeight))
+
+    def model(self):                  # :371-379
+        cls = type(self)
+        out = "## " + self.name() + "\n"
+        out += "## Iteration = %d\n" % cls.nIteration
+        out += "## No. of threshold candidates = %d\n" % cls.nThreshold
+        return out + self.toString()
+
+    def loadFromString(self, fullText):   # :381-427
+        try:
+            content = None
+            for line in fullText.split("\n"):
+                line = line.strip()
+                if not line or line.startswith("##"):
+                    continue
+                content = line
+                break
+            if content is None:
+                raise RankLibError("Model name is not found.")
+            idx = content.rfind("#")
+            if idx != -1:
+                content = content[:idx].strip()       # the comment at the end of the line
+            self.wRankers, self.rWeight = [], []
+            for tok in content.split(" "):
+                tok = tok.strip()
+                if not tok:
+                    continue
+                strs = tok.split(":")
+                self.wRankers.append((int(strs[0]), float(strs[1])))
+                self.rWeight.append(float(strs[2]))
+            self.features = [f for f, _ in self.wRankers]
+        except Exception as ex:       # noqa: BLE001 -- the reference wraps everything
+            raise RankLibError("Error in RankBoost::load(): %s" % ex)
+
+    def printParameters(self):        # :430-433
+        cls = type(self)
+        logger.info("No. of rounds: %d", cls.nIteration)
+        logger.info("No. of threshold candidates: %d", cls.nThreshold)
+
+    def name(self):
+        return "RankBoost"
+
+
 # ---------------------------------------------------------------------------------------------------------
 class RankerType(enum.Enum):          # learning/RankerType.java
     MART = 0
@@ -966,9 +1084,10 @@ RFRanker.rType = RankerType.MART
 
 class RankerFactory:                  # learning/RankerFactory.java:36-118
     def __init__(self):
-        self.map = {"LAMBDAMART": LambdaMART, "MART": MART, "RANDOM_FOREST": RFRanker, "COOR_ASCENT": CoorAscent, "ADARANK": AdaRank}
+        self.map = {"LAMBDAMART": LambdaMART, "MART": MART, "RANDOM_FOREST": RFRanker, "COOR_ASCENT": CoorAscent, "ADARANK": AdaRank,
+                    "RANKBOOST": RankBoost}
         self.names = {"LAMBDAMART": "LAMBDAMART", "MART": "MART", "RANDOM FORESTS": "RANDOM_FOREST",
-                      "COORDINATE ASCENT": "COOR_ASCENT", "ADARANK": "ADARANK"}     # name().toUpperCase() -> type (:44-53)
+                      "COORDINATE ASCENT": "COOR_ASCENT", "ADARANK": "ADARANK", "RANKBOOST": "RANKBOOST"}     # name().toUpperCase() -> type (:44-53)
 
     def createRanker(self, rtype, samples=None, features=None, scorer=None):
         if isinstance(rtype, str):
@@ -977,7 +1096,7 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
             except KeyError:
                 raise RankLibError("Could find the class \"%s\" you specified. Make sure the jar library is in your classpath." % rtype)
         if rtype.name not in self.map:
-            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent) and 3 (AdaRank) only; %s is out of scope (SURVEY.md 8)" % rtype.name)
+            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank) and 2 (RankBoost) only; %s is out of scope (SURVEY.md 8)" % rtype.name)
         r = self.map[rtype.name]()
         if samples is not None:
             r.setTrainingSet(samples)
@@ -989,7 +1108,7 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
         first = fullText.split("\n", 1)[0]
         name = first.replace("## ", "").strip()
         if name.upper() not in self.names:
-            raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests', '## Coordinate Ascent' or '## AdaRank' (got %r)" % first)
+            raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests', '## Coordinate Ascent', '## AdaRank' or '## RankBoost' (got %r)" % first)
         r = self.createRanker(RankerType[self.names[name.upper()]])
         r.loadFromString(fullText)
         return r
