@@ -513,6 +513,54 @@ int  rl_rb_debug_potentials(const rl_rb *r, int32_t round, double *out, int64_t 
 int  rl_rb_predict(int32_t device, const int32_t *feature_ids, const double *thresholds, const double *weights, int32_t n_rankers,
                    const float *X, int64_t n_docs, int32_t row_stride, double *out);
 
+/* ---- Linear Regression (-ranker 9, learning/LinearRegRank.java) ---------------------------------------------------------
+ * The least-squares ranker trained by rl_lr_learn: all of LinearRegRank.learn() (:44-100) and solve() (:188-239) with the Java's double
+ * arithmetic kept bit for bit.  With nVar = the training set's column count, the regressors are columns 0 .. nVar - 2 plus
+ * a constant: the LAST of the nVar columns is not fitted (the Java's nVar is the largest feature id, not one more), and weight[nVar - 1]
+ * is the constant's.  The GPU accumulates xTx (its upper triangle: the matrix is bitwise symmetric) and xTy, every cell its own serial
+ * f64 sum over the documents in order, and scores / ranks both sets; the ridge term and the elimination without pivoting run on the
+ * host.  Train metrics as rl_ca.  A pivot that is 0 or not finite and weights that are not all finite are RL_ERR_UNSUPPORTED. */
+typedef struct rl_lr rl_lr;             /* opaque */
+
+typedef struct {
+    double   lambda;            /* LinearRegRank.lambda default 1E-10 (-L2); added to the diagonal unless it is 0.0 */
+    int32_t  metric;            /* RL_METRIC_*: NDCG, DCG, MAP, ERR, P, RR */
+    int32_t  metric_k;          /* the scorer's k (10; 0 for MAP) */
+    int32_t  device;            /* HIP device ordinal */
+    double   err_max;           /* ERRScorer.MAX (-gmax): default 16 */
+} rl_lr_params;
+
+void rl_lr_params_default(rl_lr_params *p);         /* LinearRegRank.java:26, NDCG@10, device 0, err_max 16 */
+int  rl_lr_create(const rl_lr_params *p, rl_lr **out);
+void rl_lr_destroy(rl_lr *r);
+/* X: [n_docs][n_features] row-major, column f = DataPoint.getFeatureValue(f + 1) (NOT the feature list: the fit ignores it); NaN and
+ * +-Infinity cells are refused as in rl_ca_set_train */
+int  rl_lr_set_train(rl_lr *r, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
+                     int32_t n_queries, const int32_t *qkey);
+int  rl_lr_set_validation(rl_lr *r, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
+                          const int32_t *qkey);
+int  rl_lr_set_external_judgments(rl_lr *r, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count);
+/* optional, after rl_lr_set_train.  n_var: the Java's nVar when the sets carry more columns than that (1 .. n_features; 0 = n_features).
+ * eval_cols: the columns eval() reads, features[i] - 1 in feature-list order (-1 reads 0: an id no row has, under -missingZero);
+ * NULL = columns 0 .. n_features - 1.  More eval columns than n_var is RL_ERR_UNSUPPORTED in rl_lr_learn (the Java ends in an
+ * ArrayIndexOutOfBoundsException). */
+int  rl_lr_set_features(rl_lr *r, int32_t n_var, const int32_t *eval_cols, int32_t n_eval);
+int  rl_lr_learn(rl_lr *r);
+/* weight[0 .. nVar): w may be NULL (only *n is set); at most cap entries are written */
+int  rl_lr_get_weights(const rl_lr *r, double *w, int32_t cap, int32_t *n);
+/* train: scorer.score(rank(samples)) of the weights (not rounded); valid: the same on the validation set (0 without one) */
+int  rl_lr_scores(const rl_lr *r, double *train, double *valid);
+/* debug: xTx [nVar][nVar] and xTy [nVar] as accumulated, BEFORE the ridge term (readable also after a refused solve); both may be NULL
+ * (only *n_var is set); cap = the nVar the buffers were sized for */
+int  rl_lr_debug_gram(const rl_lr *r, double *xtx, double *xty, int32_t cap, int32_t *n_var);
+/* debug: ms of the accumulation kernel (device events), of the host solve and of scoring + ranking both sets; the register block used */
+int  rl_lr_debug_times(const rl_lr *r, double *gram_ms, double *solve_ms, double *score_ms, int32_t *register_block);
+/* LinearRegRank.eval on the GPU: out[i] = weights[n_weights - 1], then += weights[t] * x[feature_ids[t]] for t < n_features, in f64
+ * (LinearRegRank.java:103-109: it starts from the bias).  X rows as rl_ca_predict's; an ID at or beyond row_stride reads 0;
+ * n_features > n_weights is RL_ERR_UNSUPPORTED. */
+int  rl_lr_predict(int32_t device, const int32_t *feature_ids, int32_t n_features, const double *weights, int32_t n_weights, const float *X,
+                   int64_t n_docs, int32_t row_stride, double *out);
+
 #ifdef __cplusplus
 }
 #endif

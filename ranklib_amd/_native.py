@@ -64,6 +64,12 @@ class RlRbParams(C.Structure):
 RB_TRACE_DTYPE = np.dtype([("iteration", np.int32), ("feature", np.int32), ("threshold", np.float64), ("max_r", np.float64),
                            ("r_t", np.float64), ("alpha", np.float64), ("z_t", np.float64), ("train_score", np.float64),
                            ("valid_score", np.float64)])
+
+
+class RlLrParams(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("metric", C.c_int32), ("metric_k", C.c_int32), ("device", C.c_int32), ("err_max", C.c_double)]
+
+
 RL_RANKER = dict(MART=0, LAMBDAMART=6)
 
 
@@ -95,6 +101,8 @@ ABI_SYMBOLS = [
     "rl_ada_learn", "rl_ada_get_model", "rl_ada_scores", "rl_ada_trace", "rl_ada_debug_weak_table",
     "rl_rb_params_default", "rl_rb_create", "rl_rb_destroy", "rl_rb_set_train", "rl_rb_set_validation", "rl_rb_set_external_judgments",
     "rl_rb_learn", "rl_rb_get_model", "rl_rb_scores", "rl_rb_trace", "rl_rb_debug_potentials", "rl_rb_predict",
+    "rl_lr_params_default", "rl_lr_create", "rl_lr_destroy", "rl_lr_set_train", "rl_lr_set_validation", "rl_lr_set_external_judgments",
+    "rl_lr_set_features", "rl_lr_learn", "rl_lr_get_weights", "rl_lr_scores", "rl_lr_debug_gram", "rl_lr_debug_times", "rl_lr_predict",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -212,6 +220,22 @@ def lib():
         L.rl_rb_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_rb_debug_potentials.argtypes = [vp, i32, vp, i64]
         L.rl_rb_predict.argtypes = [i32, vp, vp, vp, i32, vp, i64, i32, vp]
+    if hasattr(L, "rl_lr_create"):      # (A/B builds of older sources lack Linear Regression)
+        L.rl_lr_params_default.argtypes = [C.POINTER(RlLrParams)]
+        L.rl_lr_params_default.restype = None
+        L.rl_lr_create.argtypes = [C.POINTER(RlLrParams), C.POINTER(vp)]
+        L.rl_lr_destroy.argtypes = [vp]
+        L.rl_lr_destroy.restype = None
+        L.rl_lr_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
+        L.rl_lr_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
+        L.rl_lr_set_external_judgments.argtypes = [vp, i32, vp, vp]
+        L.rl_lr_set_features.argtypes = [vp, i32, vp, i32]
+        L.rl_lr_learn.argtypes = [vp]
+        L.rl_lr_get_weights.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        L.rl_lr_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.rl_lr_debug_gram.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
+        L.rl_lr_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
+        L.rl_lr_predict.argtypes = [i32, vp, i32, vp, i32, vp, i64, i32, vp]
     _lib = L
     return L
 
@@ -853,6 +877,108 @@ def rb_predict(feature_ids, thresholds, weights, rows, device=0):
     out = np.zeros(rows.shape[0], np.float64)
     check(lib().rl_rb_predict(int(device), fid.ctypes.data, thr.ctypes.data, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0],
                               rows.shape[1], out.ctypes.data))
+    return out
+
+
+class LinearRegTrainer:
+    """Thin object wrapper over the rl_lr handle: LinearRegRank.learn() on one GPU (rl_lr.inc in rl_ca.hip)."""
+
+    def __init__(self, lambda_=1E-10, metric="NDCG", metric_k=10, device=0, err_max=16.0):
+        L = lib()
+        if not hasattr(L, "rl_lr_create"):
+            raise RankLibError("rlhip: this librlhip.so has no Linear Regression (rl_lr_*)")
+        self.p = RlLrParams()
+        L.rl_lr_params_default(C.byref(self.p))
+        m = metric.upper()
+        if m not in RL_CA_METRIC:
+            raise RankLibError("rlhip: the Linear Regression train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
+        self.p.lambda_, self.p.metric, self.p.metric_k, self.p.device, self.p.err_max = (float(lambda_), RL_CA_METRIC[m], int(metric_k),
+                                                                                          int(device), float(err_max))
+        self.h = C.c_void_p()
+        check(L.rl_lr_create(C.byref(self.p), C.byref(self.h)))
+        self.F = self.Q = self.N = 0
+        self.has_valid = False
+
+    def set_train(self, X, labels, qoff, qkey=None):
+        """X[:, f] = getFeatureValue(f + 1): the fit reads columns 0 .. nVar - 2, whatever the feature list says"""
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        self.F, self.Q, self.N = X.shape[1], len(qoff) - 1, X.shape[0]
+        check(lib().rl_lr_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                    None if qk is None else qk.ctypes.data))
+
+    def set_validation(self, X, labels, qoff, qkey=None):
+        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
+        if X.shape[1] != self.F:
+            raise RankLibError("validation set must have the training set's feature columns")
+        check(lib().rl_lr_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+                                         None if qk is None else qk.ctypes.data))
+        self.has_valid = True
+
+    def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
+        idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
+        rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
+        check(lib().rl_lr_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
+                                                 None if rdc is None else rdc.ctypes.data))
+
+    def set_features(self, n_var=0, eval_cols=None):
+        """n_var: the Java's nVar (0 = every column); eval_cols: the columns eval() reads (features[i] - 1; -1 reads 0), None = all"""
+        cols = None if eval_cols is None else np.ascontiguousarray(eval_cols, dtype=np.int32)
+        keep = np.zeros(1, np.int32) if cols is not None and cols.size == 0 else cols      # an empty list is still a list: a real pointer
+        check(lib().rl_lr_set_features(self.h, int(n_var), None if keep is None else keep.ctypes.data, 0 if cols is None else cols.size))
+
+    def learn(self):
+        check(lib().rl_lr_learn(self.h))
+
+    def weights(self):
+        n = C.c_int32(0)
+        check(lib().rl_lr_get_weights(self.h, None, 0, C.byref(n)))
+        w = np.zeros(max(1, n.value), np.float64)
+        check(lib().rl_lr_get_weights(self.h, w.ctypes.data, n.value, C.byref(n)))
+        return w[:n.value]
+
+    def scores(self):
+        ts, vs = C.c_double(0), C.c_double(0)
+        check(lib().rl_lr_scores(self.h, C.byref(ts), C.byref(vs)))
+        return ts.value, (vs.value if self.has_valid else None)
+
+    def gram(self):
+        """(xTx [nVar, nVar], xTy [nVar]) as accumulated, before the ridge term"""
+        n = C.c_int32(0)
+        check(lib().rl_lr_debug_gram(self.h, None, None, 0, C.byref(n)))
+        xtx, xty = np.zeros((n.value, n.value), np.float64), np.zeros(n.value, np.float64)
+        check(lib().rl_lr_debug_gram(self.h, xtx.ctypes.data, xty.ctypes.data, n.value, C.byref(n)))
+        return xtx, xty
+
+    def times(self):
+        """dict: gram_ms (device events), solve_ms, score_ms (host clocks) and the register block of the last learn()"""
+        g, s, e, rb = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int32(0)
+        check(lib().rl_lr_debug_times(self.h, C.byref(g), C.byref(s), C.byref(e), C.byref(rb)))
+        return dict(gram_ms=g.value, solve_ms=s.value, score_ms=e.value, register_block=rb.value)
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().rl_lr_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lr_predict(feature_ids, weights, rows, device=0):
+    """LinearRegRank.eval on the GPU: weights[-1] first, then weights[t] * rows[:, feature_ids[t]]; rows as ca_predict's; f64 scores"""
+    L = lib()
+    if not hasattr(L, "rl_lr_predict"):
+        raise RankLibError("rlhip: this librlhip.so has no Linear Regression (rl_lr_*)")
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    fid = np.ascontiguousarray(feature_ids, dtype=np.int32)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    out = np.zeros(rows.shape[0], np.float64)
+    keep = fid if fid.size else np.zeros(1, np.int32)
+    check(L.rl_lr_predict(int(device), keep.ctypes.data, fid.size, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0], rows.shape[1],
+                          out.ctypes.data))
     return out
 
 

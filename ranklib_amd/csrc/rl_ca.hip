@@ -801,3 +801,4 @@ int rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weig
 
 #include "rl_ada.inc"      // AdaRank (-ranker 3): the same translation unit, so its kernels share ca_metric and k_ca_trials
 #include "rl_rb.inc"       // RankBoost (-ranker 2): the device sets, ca_metric and the ranking kernel again
+#include "rl_lr.inc"       // Linear Regression (-ranker 9): the same

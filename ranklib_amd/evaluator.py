@@ -1,5 +1,5 @@
-"""Command line of the `-ranker 6 / 0 / 8 / 4 / 3 / 2` paths: mirrors the flags of eval/Evaluator.java that reach LambdaMART, MART, Random
-Forests, Coordinate Ascent, AdaRank and RankBoost (:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
+"""Command line of the `-ranker 6 / 0 / 8 / 4 / 3 / 2 / 9` paths: mirrors the flags of eval/Evaluator.java that reach LambdaMART, MART, Random
+Forests, Coordinate Ascent, AdaRank, RankBoost and Linear Regression (:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
 
     python -m ranklib_amd.evaluator -train f -ranker 6 -metric2t NDCG@10 -tree 1000 -leaf 31 -save model.txt
     python -m ranklib_amd.evaluator -load model.txt -rank f -score out.txt
@@ -11,7 +11,7 @@ import sys
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
                        stable_desc_order)
 from .metric import ERRScorer, MetricScorerFactory
 
@@ -194,14 +194,14 @@ def _read_input(inputFile):
 
 # the command line's numbering (eval/Evaluator.java:69-73 rType2), not the enum's ordinals: 1 is RankNet and 2 is RankBoost there
 _RANKER_TYPES = {0: RankerType.MART, 2: RankerType.RANKBOOST, 3: RankerType.ADARANK, 4: RankerType.COOR_ASCENT, 6: RankerType.LAMBDAMART,
-                 8: RankerType.RANDOM_FOREST}
+                 8: RankerType.RANDOM_FOREST, 9: RankerType.LINEAR_REGRESSION}
 
 
 def main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|3|2|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f] [-rank f -indri out] [-score out]")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
@@ -275,11 +275,12 @@ def main(argv=None):
         elif a == "-round": RankBoost.nIteration = AdaRank.nIteration = int(nxt())          # :305-318
         elif a == "-noeq": AdaRank.trainWithEnqueue = False
         elif a == "-max": AdaRank.maxSelCount = int(nxt())
-        elif a in ("-epoch", "-layer", "-node", "-lr", "-l2"):
+        elif a == "-l2": LinearRegRank.lambda_ = float(nxt())                               # :355-356, whatever -ranker says
+        elif a in ("-epoch", "-layer", "-node", "-lr"):
             # parameters of the other rankers / of flows that are out of scope: parsed (the reference's own test passes
             # -round -epoch to every ranker, test:eval/EvaluatorTest.java:207-220) and ignored
             nxt()
-        elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = int(nxt())
+        elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = int(nxt())
         else:
             raise RankLibError("Unknown command-line parameter: " + args[i])     # :369-371 (incl. the documented -silent)
         i += 1
@@ -287,7 +288,8 @@ def main(argv=None):
         testMetric = trainMetric                            # :379-381
     if trainFile and rankerType not in _RANKER_TYPES:
         raise RankLibError("rlhip builds -ranker 6 (LambdaMART), -ranker 0 (MART), -ranker 8 (Random Forests), -ranker 4 (Coordinate Ascent), "
-                           "-ranker 3 (AdaRank) and -ranker 2 (RankBoost) only")
+                           "-ranker 3 (AdaRank), -ranker 2 (RankBoost) and -ranker 9 (Linear Regression) only: the neural-net rankers "
+                           "(-ranker 1 RankNet, 5 LambdaRank, 7 ListNet) are out of scope")
     e = Evaluator(_RANKER_TYPES.get(rankerType, RankerType.LAMBDAMART), trainMetric, testMetric)
     if trainFile:
         if foldCV != -1:                                    # :469-482

@@ -9,6 +9,7 @@ RankLib's API read the same here:
     LambdaMART                   learning/tree/LambdaMART.java:33-329   (init/learn run on the GPU through librlhip.so)
     CoorAscent                   learning/CoorAscent.java:33-396        (learn and eval run on the GPU through librlhip.so)
     AdaRank                      learning/boosting/AdaRank.java:33-346  (learn and eval run on the GPU through librlhip.so)
+    LinearRegRank                learning/LinearRegRank.java:23-240     (learn and eval run on the GPU through librlhip.so)
     RankerType / RankerFactory   learning/RankerType.java, learning/RankerFactory.java:36-118
     RankerTrainer                learning/RankerTrainer.java:23-56
 
@@ -634,14 +635,17 @@ class RFRanker(Ranker):
         logger.info("Learning rate: %s", java_float_str(cls.learningRate))
 
 
-def _feed_linear_trainer(ranker, t, metric):
+def _feed_linear_trainer(ranker, t, metric, flat=None):
     """The training / validation lists of a CoorAscent or AdaRank ranker into its rl_ca / rl_ada trainer t, with the NDCG ideal-DCG keys
-    shared across the two sets and the external judgments the scorer holds (see LambdaMART.init)."""
-    X, lab, qoff, qkey = flatten(ranker.samples, ranker.features)
+    shared across the two sets and the external judgments the scorer holds (see LambdaMART.init).  flat: the ranker's own flatten(samples)
+    where the columns are not the feature list's (LinearRegRank)."""
+    if flat is None:
+        flat = lambda lists: flatten(lists, ranker.features)      # noqa: E731
+    X, lab, qoff, qkey = flat(ranker.samples)
     nk = int(qkey.max()) + 1 if len(qkey) else 0
     t.set_train(X, lab, qoff, qkey=qkey)
     if ranker.validationSamples is not None:
-        Xv, lv, qv, _ = flatten(ranker.validationSamples, ranker.features)
+        Xv, lv, qv, _ = flat(ranker.validationSamples)
         ids = {}
         for q, rl in enumerate(ranker.samples):
             ids.setdefault(rl.getID(), int(qkey[q]))
@@ -1065,6 +1069,124 @@ class RankBoost(Ranker):
         return "RankBoost"
 
 
+class LinearRegRank(Ranker):
+    """learning/LinearRegRank.java: the least-squares ranker.  learn() runs on an MI355X (librlhip.so rl_lr_*: xTx and xTy accumulated cell
+    by cell in the Java's document order, then the Java's elimination without pivoting on the host), eval() as the GPU's f64 sum that
+    starts from weight[last].  nVar is the largest feature id of the training lists: features 1 .. nVar - 1 and a constant are fitted,
+    feature nVar is not, and eval() pairs weight[i] with features[i] whatever was fitted there."""
+    lambda_ = 1E-10                   # LinearRegRank.lambda (:26), -L2
+    device = 0
+
+    def __init__(self, samples=None, features=None, scorer=None):
+        super().__init__(samples, features, scorer)
+        self.weight = None
+        self.gram = None              # (xTx, xTy) of the last learn(), before the ridge term
+        self.times = None
+        self._trainer = None
+
+    def init(self):                   # :39-41
+        logger.info("Initializing...")
+        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        if metric not in N.RL_CA_METRIC:
+            raise RankLibError("rlhip: the Linear Regression train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
+                               % (self.scorer.name() if self.scorer else None))
+        cls = type(self)
+        nVar = max((rl.getFeatureCount() for rl in self.samples), default=0)      # :50-56
+        if nVar < 1:
+            raise RankLibError("Error: some of the input arrays is empty.")       # solve() :189-191
+        feats = [int(f) for f in self.features]
+        if len(feats) > nVar:
+            raise RankLibError("rlhip: Linear Regression has %d features to score with but only nVar = %d weights (the largest feature id "
+                               "of the training lists); the Java ends in an ArrayIndexOutOfBoundsException in eval" % (len(feats), nVar))
+        # the columns: feature ids 1 .. W.  The fit reads 1 .. nVar - 1 and eval reads the feature list; nothing else is asked of a row
+        width = max([nVar] + feats)
+        need = sorted(set(range(1, nVar)) | set(feats))
+
+        def flat(lists):
+            Xn, lab, qoff, qkey = flatten(lists, need)
+            X = np.zeros((Xn.shape[0], width), np.float32)
+            for j, f in enumerate(need):
+                if 1 <= f <= width:
+                    X[:, f - 1] = Xn[:, j]
+            return X, lab, qoff, qkey
+
+        t = N.LinearRegTrainer(lambda_=cls.lambda_, metric=metric, metric_k=self.scorer.getK(), device=cls.device, err_max=ERRScorer.MAX)
+        _feed_linear_trainer(self, t, metric, flat)
+        t.set_features(nVar, [f - 1 if 1 <= f <= width else -1 for f in feats])
+        self._trainer = t
+
+    def learn(self):                  # :44-100
+        t = self._trainer
+        logger.info("Training starts...")
+        logger.info("Learning the least square model... ")
+        try:
+            t.learn()
+        finally:
+            try:
+                self.gram, self.times = t.gram(), t.times()
+            except RankLibError:
+                self.gram = self.times = None
+        self.weight = [float(v) for v in t.weights()]
+        ts, vs = t.scores()
+        nm = self.scorer.name()
+        self.scoreOnTrainingData = java_round(ts, 4)
+        logger.info("Finished sucessfully.")
+        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
+        if vs is not None:
+            self.bestScoreOnValidationData = vs
+            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
+        t.close()
+        self._trainer = None
+
+    # --- scoring: weight[last] + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_lr_predict) -------------------------
+    def evalList(self, rl):
+        if rl.size() == 0:
+            return []
+        if len(self.features) > len(self.weight):
+            raise RankLibError("rlhip: Linear Regression has %d features to score with but only %d weights; the Java ends in an "
+                               "ArrayIndexOutOfBoundsException in eval" % (len(self.features), len(self.weight)))
+        return [float(v) for v in N.lr_predict(self.features, self.weight, _linear_rows(rl.rl, self.features), type(self).device)]
+
+    def eval(self, dp):               # noqa: A003  :103-109
+        return self.evalList(RankList([dp]))[0]
+
+    def createNew(self):
+        return LinearRegRank()
+
+    def toString(self):               # :117-123: the "0:" entry carries weight[0], and every pair ends in a space: `i == weight.length - 1`
+        out = "0:" + java_double_str(self.weight[0]) + " "      # never holds inside a loop that runs to features.length <= weight.length
+        for i, f in enumerate(self.features):
+            out += "%d:%s" % (f, java_double_str(self.weight[i])) + ("" if i == len(self.weight) - 1 else " ")
+        return out
+
+    def model(self):                  # :126-131
+        return "## " + self.name() + "\n## Lambda = " + java_double_str(type(self).lambda_) + "\n" + self.toString()
+
+    def loadFromString(self, fullText):   # :134-170: keys > 0 fill features / weight in order, the key 0 value goes to weight[last]
+        try:
+            keys, values = _key_value_line(fullText)
+            weight = [0.0] * len(keys)
+            features = [0] * (len(keys) - 1)
+            idx = 0
+            for k, v in zip(keys, values):
+                fid = int(k)
+                if fid > 0:
+                    features[idx] = fid
+                    weight[idx] = float(v)
+                    idx += 1
+                else:
+                    weight[len(weight) - 1] = float(v)
+            self.features, self.weight = features, weight
+        except Exception as ex:       # noqa: BLE001 -- the reference wraps everything
+            raise RankLibError("Error in LinearRegRank::load(): %s" % ex)
+
+    def printParameters(self):        # :173-175
+        logger.info("L2-norm regularization: lambda = %s", java_double_str(type(self).lambda_))
+
+    def name(self):
+        return "Linear Regression"
+
+
 # ---------------------------------------------------------------------------------------------------------
 class RankerType(enum.Enum):          # learning/RankerType.java
     MART = 0
@@ -1085,9 +1207,10 @@ RFRanker.rType = RankerType.MART
 class RankerFactory:                  # learning/RankerFactory.java:36-118
     def __init__(self):
         self.map = {"LAMBDAMART": LambdaMART, "MART": MART, "RANDOM_FOREST": RFRanker, "COOR_ASCENT": CoorAscent, "ADARANK": AdaRank,
-                    "RANKBOOST": RankBoost}
+                    "RANKBOOST": RankBoost, "LINEAR_REGRESSION": LinearRegRank}
         self.names = {"LAMBDAMART": "LAMBDAMART", "MART": "MART", "RANDOM FORESTS": "RANDOM_FOREST",
-                      "COORDINATE ASCENT": "COOR_ASCENT", "ADARANK": "ADARANK", "RANKBOOST": "RANKBOOST"}     # name().toUpperCase() -> type (:44-53)
+                      "COORDINATE ASCENT": "COOR_ASCENT", "ADARANK": "ADARANK", "RANKBOOST": "RANKBOOST",
+                      "LINEAR REGRESSION": "LINEAR_REGRESSION"}     # name().toUpperCase() -> type (:44-53)
 
     def createRanker(self, rtype, samples=None, features=None, scorer=None):
         if isinstance(rtype, str):
@@ -1096,7 +1219,8 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
             except KeyError:
                 raise RankLibError("Could find the class \"%s\" you specified. Make sure the jar library is in your classpath." % rtype)
         if rtype.name not in self.map:
-            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank) and 2 (RankBoost) only; %s is out of scope (SURVEY.md 8)" % rtype.name)
+            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank), 2 (RankBoost) and "
+                               "9 (Linear Regression); %s, one of the neural-net rankers, is out of scope (SURVEY.md 8)" % rtype.name)
         r = self.map[rtype.name]()
         if samples is not None:
             r.setTrainingSet(samples)
@@ -1108,7 +1232,8 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
         first = fullText.split("\n", 1)[0]
         name = first.replace("## ", "").strip()
         if name.upper() not in self.names:
-            raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests', '## Coordinate Ascent', '## AdaRank' or '## RankBoost' (got %r)" % first)
+            raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests', '## Coordinate Ascent', '## AdaRank', "
+                               "'## RankBoost' or '## Linear Regression' (got %r)" % first)
         r = self.createRanker(RankerType[self.names[name.upper()]])
         r.loadFromString(fullText)
         return r
