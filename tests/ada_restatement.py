@@ -84,10 +84,11 @@ def _per_list(sc, cache, lab, qoff, qid):
     return m
 
 
-def learn(train, valid=None, metric="NDCG", k=10, nIteration=500, tolerance=0.002, trainWithEnqueue=True, maxSelCount=5, err_max=16.0):
+def learn(train, valid=None, metric="NDCG", k=10, nIteration=500, tolerance=0.002, trainWithEnqueue=True, maxSelCount=5, err_max=16.0,
+          ideal=None, rel_doc_count=None, valid_rel_doc_count=CR.SAME):
     """train / valid: (X [n, F] float32, labels, qoff, qid list).  Returns dict(fid, weight, train, valid, trace, M, restored):
     restored = the best model on validation data replaced a different final ensemble."""
-    sc = CR.LiteralScorer(metric, k, err_max)
+    sc = CR.LiteralScorer(metric, k, err_max, ideal, rel_doc_count, valid_rel_doc_count)      # -qrel: see ca_restatement
     X, lab, qoff, qid = train
     F, Q = X.shape[1], len(qoff) - 1
     M = weak_table(X, lab, qoff, qid, sc, metric, k)
@@ -160,7 +161,7 @@ def learn(train, valid=None, metric="NDCG", k=10, nIteration=500, tolerance=0.00
                 st["lastFeature"] = best
             vs = 0.0
             if valid is not None:                                           # :177-183
-                vs = sc.score(_eval(valid[0], rankers, rweight), valid[1], valid[2], valid[3])
+                vs = sc.score(_eval(valid[0], rankers, rweight), valid[1], valid[2], valid[3], valid=True)
                 if vs > st["bestValid"]:
                     st["bestValid"] = vs
                     bestRankers, bestWeights = list(rankers), list(rweight)
@@ -190,5 +191,5 @@ def learn(train, valid=None, metric="NDCG", k=10, nIteration=500, tolerance=0.00
         restored = (bestRankers, bestWeights) != (rankers, rweight)
         rankers, rweight = list(bestRankers), list(bestWeights)
     ts = sc.score(_eval(X, rankers, rweight), lab, qoff, qid)
-    vs = sc.score(_eval(valid[0], rankers, rweight), valid[1], valid[2], valid[3]) if valid is not None else None
+    vs = sc.score(_eval(valid[0], rankers, rweight), valid[1], valid[2], valid[3], valid=True) if valid is not None else None
     return dict(fid=rankers, weight=rweight, train=ts, valid=vs, trace=trace, M=M, restored=restored)

@@ -9,6 +9,12 @@ on the cached scores, and the cache updates themselves -- comes from one of two 
     VectorScorer   numpy: one np.lexsort per evaluation, the metrics evaluated position by position over all lists at once, the
                    list-order serial sum as np.cumsum(...)[-1]; the cached scores are an f64 array
 
+Both take the two things -qrel puts into a scorer before any list is scored, keyed by qid: `ideal` (NDCGScorer.loadExternalRelevanceJudgment,
+:50-96: idealGains entries, so score() never computes that qid's own) and `rel_doc_count` (APScorer :45-66 and :86-94: a qid the map lacks
+counts 0 relevant documents and its list scores 0.0; no map at all = every list's own count).  The Java holds ONE map for every list it
+scores; rlhip's rl_*_set_external_judgments takes the counts per set, so `valid_rel_doc_count` restates a validation set fed differently
+(SAME = the one map, None = the validation lists' own counts); score(..., valid=True) scores with it.
+
 Both produce the trace rlhip's rl_ca_trace returns: (kind, restart, feature index, dir, j, improved, weight, score) per restart, pass,
 trial, success and validation score (kinds as _native.CA_*).
 """
@@ -144,13 +150,25 @@ class _RR:                              # metric/ReciprocalRankScorer.java:24-35
         return 0.0
 
 
+SAME = "same"                           # valid_rel_doc_count: the validation lists are scored with rel_doc_count, as the Java's one scorer does
+
+_GAIN = np.array([R.gain(i) for i in range(32)], np.float64)       # (1 << rel) - 1 on Java ints, by rel & 31
+
+
 class LiteralScorer:
-    def __init__(self, metric, k, err_max=16.0):
+    def __init__(self, metric, k, err_max=16.0, ideal=None, rel_doc_count=None, valid_rel_doc_count=SAME):
         if metric == "ERR":
             self.m = R.ERR(k)
             self.m.MAX = err_max
+        elif metric == "NDCG":
+            self.m = R.NDCG(k, ideal)
+        elif metric == "MAP":
+            self.m = R.MAP(k, rel_doc_count)
         else:
-            self.m = {"NDCG": R.NDCG, "DCG": R.DCG, "MAP": R.MAP, "P": _P, "RR": _RR}[metric](k)
+            self.m = {"DCG": R.DCG, "P": _P, "RR": _RR}[metric](k)
+        self.mv = self.m                # the validation lists' scorer: the same object (one idealGains cache), unless their counts differ
+        if metric == "MAP" and valid_rel_doc_count is not SAME:
+            self.mv = R.MAP(k, valid_rel_doc_count)
 
     def new_cache(self, n):
         return [0.0] * n
@@ -170,19 +188,22 @@ class LiteralScorer:
             out = [c / div for c in out]
         return out
 
-    def score(self, cache, labels, qoff, qid):
+    def score(self, cache, labels, qoff, qid, valid=False):
+        m = self.mv if valid else self.m
         s = 0.0
         for q in range(len(qoff) - 1):
             a, b = int(qoff[q]), int(qoff[q + 1])
             order = merge_sort_desc(cache[a:b])
-            s += self.m.score([float(labels[a + i]) for i in order], qid[q])
+            s += m.score([float(labels[a + i]) for i in order], qid[q])
         return s / (len(qoff) - 1)
 
 
 class VectorScorer:
-    def __init__(self, metric, k, err_max=16.0):
+    def __init__(self, metric, k, err_max=16.0, ideal=None, rel_doc_count=None, valid_rel_doc_count=SAME):
         self.metric, self.k, self.err_max = metric, k, err_max
-        self.ideal = {}                 # NDCGScorer.idealGains: keyed by qid, filled in the order lists are first scored
+        self.ideal = dict(ideal) if ideal else {}     # NDCGScorer.idealGains: keyed by qid, -qrel entries first, then filled in the order lists are first scored
+        self.rdc = rel_doc_count
+        self.vrdc = rel_doc_count if valid_rel_doc_count is SAME else valid_rel_doc_count
 
     def new_cache(self, n):
         return np.zeros(n, np.float64)
@@ -197,7 +218,7 @@ class VectorScorer:
         out = cache + wc * x.astype(np.float64)
         return out if div is None else out / div
 
-    def score(self, cache, labels, qoff, qid):
+    def score(self, cache, labels, qoff, qid, valid=False):
         qoff = np.asarray(qoff, np.int64)
         Q = len(qoff) - 1
         n = np.diff(qoff)
@@ -219,22 +240,31 @@ class VectorScorer:
             for p in range(int(size.max())):
                 on = size > p
                 rel = lab[qoff[:-1][on] + p].astype(np.int64)
-                dcg[on] = dcg[on] + ((2.0 ** rel) - 1.0) * R.discount(p)
+                dcg[on] = dcg[on] + _GAIN[rel & 31] * R.discount(p)
             res = dcg if self.metric == "DCG" else np.where(ideal > 0.0, dcg / np.where(ideal > 0.0, ideal, 1.0), 0.0)
         elif self.metric == "MAP":
             ap, cnt = np.zeros(Q), np.zeros(Q, np.int64)
-            for p in range(int(n.max())):
-                on = n > p
-                rel = lab[qoff[:-1][on] + p] > 0.0
-                c = cnt[on] + rel
-                cnt[on] = c
-                ap[on] = np.where(rel, ap[on] + c / float(p + 1), ap[on])
-            res = np.where(cnt > 0, ap / np.maximum(cnt, 1), 0.0)
+            if int(n.max()) > 4 * Q:      # a speed path for few long lists: list by list, the serial sum as np.cumsum (a non-relevant document adds 0.0: no change)
+                for q in range(Q):
+                    rel = lab[qoff[q]:qoff[q + 1]] > 0.0
+                    c = np.cumsum(rel)
+                    ap[q] = np.cumsum(np.where(rel, c / np.arange(1, len(c) + 1, dtype=np.float64), 0.0))[-1]
+                    cnt[q] = c[-1]
+            else:
+                for p in range(int(n.max())):
+                    on = n > p
+                    rel = lab[qoff[:-1][on] + p] > 0.0
+                    c = cnt[on] + rel
+                    cnt[on] = c
+                    ap[on] = np.where(rel, ap[on] + c / float(p + 1), ap[on])
+            rdc = self.vrdc if valid else self.rdc
+            rd = cnt if rdc is None else np.array([rdc.get(qid[q], 0) for q in range(Q)], np.int64)
+            res = np.where(rd > 0, ap / np.maximum(rd, 1), 0.0)
         elif self.metric == "ERR":
             sc, pp = np.zeros(Q), np.ones(Q)
             for p in range(int(size.max())):
                 on = size > p
-                Rr = ((2.0 ** lab[qoff[:-1][on] + p].astype(np.int64)) - 1.0) / self.err_max
+                Rr = _GAIN[lab[qoff[:-1][on] + p].astype(np.int64) & 31] / self.err_max
                 sc[on] = sc[on] + pp[on] * Rr / (p + 1)
                 pp[on] = pp[on] * (1.0 - Rr)
             res = sc
@@ -284,9 +314,9 @@ def _normalize(w):                      # :366-382
 
 
 def learn(train, valid=None, metric="NDCG", k=10, nRestart=5, nMaxIteration=25, stepBase=0.05, stepScale=2.0, tolerance=0.001,
-          regularized=False, slack=0.001, seed=0, err_max=16.0, literal=False):
+          regularized=False, slack=0.001, seed=0, err_max=16.0, literal=False, ideal=None, rel_doc_count=None, valid_rel_doc_count=SAME):
     """train / valid: (X [n, F] float32, labels, qoff, qid list).  Returns dict(weight, train, valid, trace)."""
-    sc = (LiteralScorer if literal else VectorScorer)(metric, k, err_max)
+    sc = (LiteralScorer if literal else VectorScorer)(metric, k, err_max, ideal, rel_doc_count, valid_rel_doc_count)
     X, lab, qoff, qid = train
     F = X.shape[1]
     cols = [X[:, f] for f in range(F)]
@@ -354,13 +384,13 @@ def learn(train, valid=None, metric="NDCG", k=10, nRestart=5, nMaxIteration=25, 
             if bestScore - startScore < tolerance:
                 break
         if valid is not None:
-            bestScore = sc.score(sc.dot(valid[0], weight), valid[1], valid[2], valid[3])
+            bestScore = sc.score(sc.dot(valid[0], weight), valid[1], valid[2], valid[3], valid=True)
             trace.append((VALID, r, -1, 0, 0, 0, 0.0, bestScore))
         if bestModel is None or bestScore > bestModelScore:
             bestModelScore, bestModel = bestScore, bestWeight
     weight = list(bestModel)
     ts = sc.score(sc.dot(X, weight), lab, qoff, qid)
-    vs = sc.score(sc.dot(valid[0], weight), valid[1], valid[2], valid[3]) if valid is not None else None
+    vs = sc.score(sc.dot(valid[0], weight), valid[1], valid[2], valid[3], valid=True) if valid is not None else None
     return dict(weight=weight, train=ts, valid=vs, trace=trace)
 
 

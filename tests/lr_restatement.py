@@ -110,7 +110,8 @@ def eval_scores(X, features, weight, missing_zero=True):
     return s
 
 
-def learn(train, valid=None, metric="NDCG", k=10, lam=1E-10, features=None, err_max=16.0):
+def learn(train, valid=None, metric="NDCG", k=10, lam=1E-10, features=None, err_max=16.0, ideal=None, rel_doc_count=None,
+          valid_rel_doc_count=CR.SAME):
     """train / valid: (X [N, F] float32 with column f - 1 = feature f, labels, qoff, qids).  Returns xtx / xty (before the ridge term), the
     weights, both sets' document scores and the two metric values (not rounded)."""
     X, lab, qoff, qid = train
@@ -122,14 +123,14 @@ def learn(train, valid=None, metric="NDCG", k=10, lam=1E-10, features=None, err_
         for i in range(nVar):
             a[i, i] += lam
     weight = solve(a, xty)
-    sc = (CR.VectorScorer if X.shape[0] > 1500 else CR.LiteralScorer)(metric, k, err_max)
+    sc = (CR.VectorScorer if X.shape[0] > 1500 else CR.LiteralScorer)(metric, k, err_max, ideal, rel_doc_count, valid_rel_doc_count)
     out = dict(xtx=xtx, xty=xty, weight=weight, features=features)
     out["train_scores"] = eval_scores(X, features, weight)
     out["train"] = sc.score(_cache(sc, out["train_scores"]), lab, qoff, qid)
     if valid is not None:
         Xv, lv, qv, qidv = valid
         out["valid_scores"] = eval_scores(Xv, features, weight)
-        out["valid"] = sc.score(_cache(sc, out["valid_scores"]), lv, qv, qidv)
+        out["valid"] = sc.score(_cache(sc, out["valid_scores"]), lv, qv, qidv, valid=True)
     return out
 
 

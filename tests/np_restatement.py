@@ -82,8 +82,9 @@ def discount(i):  # DCGScorer.java:26 ; SimpleMath.java:24-26
     return 1.0 / (math.log(i + 2) / math.log(2))
 
 
-def gain(rel):  # DCGScorer.java:28-31
-    return float((1 << rel) - 1)
+def gain(rel):  # DCGScorer.java:28-31,137-139: (1 << rel) - 1 on Java ints -- the shift count is rel & 31, the result wraps to 32 bits
+    v = ((1 << (int(rel) & 31)) - 1) & 0xFFFFFFFF
+    return float(v - (1 << 32) if v >= (1 << 31) else v)
 
 
 def stable_desc(scores):
@@ -100,9 +101,9 @@ def ideal_dcg(rel, topk):  # NDCGScorer.java:167-174
 
 
 class NDCG:
-    def __init__(self, k=10):
+    def __init__(self, k=10, ideal=None):
         self.k = k
-        self.ideal_gains = {}  # NDCGScorer.java:32
+        self.ideal_gains = dict(ideal) if ideal else {}  # NDCGScorer.java:32; loadExternalRelevanceJudgment (:50-96) fills it before any list is scored
 
     def score(self, lab_ranked, qid):  # NDCGScorer.java:103-129
         rel_ranked = [int(l) for l in lab_ranked]  # MetricScorer.getRelevanceLabels :54-60
@@ -168,8 +169,9 @@ class DCG:  # metric/DCGScorer.java
 
 
 class MAP:  # metric/APScorer.java  (k = 0 unless "MAP@k"; the score ignores k)
-    def __init__(self, k=0):
+    def __init__(self, k=0, rel_doc_count=None):
         self.k = k
+        self.rel_doc_count = rel_doc_count  # APScorer.java:33: null unless loadExternalRelevanceJudgment (:45-66) ran
 
     def score(self, lab_ranked, qid):  # :73-100
         ap, count = 0.0, 0
@@ -177,7 +179,8 @@ class MAP:  # metric/APScorer.java  (k = 0 unless "MAP@k"; the score ignores k)
             if l > 0.0:
                 count += 1
                 ap += count / (i + 1)
-        return 0.0 if count == 0 else ap / count
+        rd = count if self.rel_doc_count is None else self.rel_doc_count.get(qid, 0)  # :86-94 (a qid the map lacks: 0)
+        return 0.0 if rd == 0 else ap / rd
 
     def swap_change(self, lab_ranked, qid):  # :108-162
         n = len(lab_ranked)
@@ -210,7 +213,7 @@ class ERR:  # metric/ERRScorer.java
         self.k = k
 
     def R(self, rel):  # :71-73
-        return ((1 << rel) - 1) / self.MAX
+        return gain(rel) / self.MAX  # an int expression divided by the double MAX
 
     def score(self, lab_ranked, qid):  # :45-64
         n = len(lab_ranked)

@@ -87,11 +87,12 @@ def _eval_np(X, rankers, weights):
     return [float(v) for v in s]
 
 
-def learn(train, valid=None, metric="NDCG", k=10, nIteration=300, nThreshold=10, err_max=16.0, vector=False, keep_potentials=0):
+def learn(train, valid=None, metric="NDCG", k=10, nIteration=300, nThreshold=10, err_max=16.0, vector=False, keep_potentials=0,
+          ideal=None, rel_doc_count=None, valid_rel_doc_count=CR.SAME):
     """train / valid: (X [n, F] float32, labels, qoff, qid list).  Returns dict(fid, thr, weight, train, valid, trace, restored,
     pots): restored = the best prefix on validation data is shorter than the full model; pots[t - 1] = the potentials of round t in
     the corrected order (keep_potentials rounds); a non-finite round raises NonFiniteRound."""
-    sc = CR.LiteralScorer(metric, k, err_max)
+    sc = CR.LiteralScorer(metric, k, err_max, ideal, rel_doc_count, valid_rel_doc_count)      # -qrel: see ca_restatement
     X0, lab0, qoff, qid = train
     X, lab, _ = correct_ranking(X0, lab0, qoff)                               # init() :152
     F, Q = X.shape[1], len(qoff) - 1
@@ -198,7 +199,7 @@ def learn(train, valid=None, metric="NDCG", k=10, nIteration=300, nThreshold=10,
         ts = sc.score(ev(X, wRankers, rWeight), lab, qoff, qid)
         vs = 0.0
         if valid is not None:
-            vs = sc.score(ev(valid[0], wRankers, rWeight), valid[1], valid[2], valid[3])
+            vs = sc.score(ev(valid[0], wRankers, rWeight), valid[1], valid[2], valid[3], valid=True)
             if vs > bestValid:
                 bestValid, best_len = vs, len(wRankers)
         trace.append((t, bestFid, bestThreshold, maxR, R_t, alpha_t, Z_t, ts, vs))
@@ -215,6 +216,6 @@ def learn(train, valid=None, metric="NDCG", k=10, nIteration=300, nThreshold=10,
         restored = best_len < len(wRankers)
         wRankers, rWeight = wRankers[:best_len], rWeight[:best_len]
     ts = sc.score(ev(X, wRankers, rWeight), lab, qoff, qid)
-    vs = sc.score(ev(valid[0], wRankers, rWeight), valid[1], valid[2], valid[3]) if valid is not None else None
+    vs = sc.score(ev(valid[0], wRankers, rWeight), valid[1], valid[2], valid[3], valid=True) if valid is not None else None
     return dict(fid=[f for f, _ in wRankers], thr=[v for _, v in wRankers], weight=rWeight, train=ts, valid=vs, trace=trace,
                 restored=restored, pots=pots)

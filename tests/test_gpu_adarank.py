@@ -1,14 +1,21 @@
 """AdaRank (-ranker 3) on the MI355X: every round's feature, alpha, train and validation score, every rollback, the model and the final
 scores bit-identical to the literal restatement of AdaRank.learn (tests/ada_restatement.py); the weak-ranker table bit-identical to the
-restatement's Sorter order; the refusals; and the reference's testAdaRank flow through the command line."""
+restatement's Sorter order; the refusals; and the reference's testAdaRank flow through the command line.
+
+-qrel judgments are covered by test_external_judgments_match_the_restatement (per set), test_weak_table_external_judgments_across_the_
+length_classes, test_cli_qrel_reaches_the_trainer and test_external_judgment_refusals; labels of 31 and above (gains that wrap as Java
+ints) by test_weak_table_wrapped_labels and test_learn_wrapped_labels; fractional labels by test_fractional_labels."""
+import functools
+
 import numpy as np
 import pytest
 
 import ada_restatement as AR
+import linear_ext as E
 from ranklib_amd import _native as N
 from ranklib_amd import evaluator, learning
 from ranklib_amd.learning import AdaRank, CoorAscent, DataPoint, RankList, java_double_str
-from ranklib_amd.metric import ERRScorer
+from ranklib_amd.metric import ERRScorer, MetricScorerFactory
 
 pytestmark = pytest.mark.gpu
 
@@ -33,15 +40,9 @@ def _data(rng, lengths, F, levels=3, labels=3):
     return X, lab, qoff, ["q%d" % i for i in range(len(lengths))]
 
 
-def _trainer(train, valid=None, metric="NDCG", k=10, err_max=16.0, **p):
-    t = N.AdaRankTrainer(metric=metric, metric_k=k, err_max=err_max, **p)
-    X, lab, qoff, qid = train
-    keys = {}
-    t.set_train(X, lab, qoff, qkey=np.array([keys.setdefault(q, len(keys)) for q in qid], np.int32))
-    if valid is not None:
-        Xv, lv, qv, qidv = valid
-        t.set_validation(Xv, lv, qv, qkey=np.array([keys.setdefault(q, len(keys)) for q in qidv], np.int32))
-    return t
+def _trainer(train, valid=None, metric="NDCG", k=10, err_max=16.0, ext=None, **p):
+    """ext: the per-list external judgments of linear_ext.feed (ideal_tr / ideal_va / rdc_tr / rdc_va)"""
+    return E.feed(N.AdaRankTrainer(metric=metric, metric_k=k, err_max=err_max, **p), train, valid, **(ext or {}))
 
 
 def _bits(v):
@@ -262,3 +263,163 @@ def test_feature_subset_in_any_order_and_splits(tmp_path):
     rows = [line.rstrip("\n").split("\t") for line in open(scores)]
     assert [x[2] for x in rows] == [java_double_str(v) for v in want]
     evaluator.main(["-train", data, "-ranker", "3", "-kcv", "3", "-tvs", "0.8", "-metric2t", "MAP", "-round", "15"])
+
+
+# ---- -qrel judgments, labels of 31 and above, fractional labels ---------------------------------------------------------------------
+def _learn_or_refuse(tr, va, metric, k, rounds, arrays=None, ext=None):
+    """The restatement says what must happen.  Its alpha_t is not finite (a list scoring above 1 can turn sum w (1 - m) negative): rlhip
+    refuses with RL_ERR_UNSUPPORTED at that round and feature.  Otherwise: table, trace, model and scores are equal.  Returns the
+    restatement's run, or None after a refusal."""
+    t = _trainer(tr, va, metric, k, ext=arrays, n_iteration=rounds)
+    try:
+        r = AR.learn(tr, va, metric=metric, k=k, nIteration=rounds, **(ext or {}))
+    except AR.NonFiniteAlpha as want:
+        rnd, feat = str(want).split(",")[:2]
+        with pytest.raises(N.RankLibError) as e:
+            t.learn()
+        assert "status -4" in str(e.value) and "AdaRank %s:" % rnd in str(e.value) and "feature index %s " % feat.split()[1] in str(e.value)
+        return None
+    t.learn()
+    assert np.array_equal(t.weak_table().view(np.int64), r["M"].view(np.int64))
+    g = [tuple(x.item()) for x in t.trace()]
+    assert len(g) == len(r["trace"])
+    for a, b in zip(g, r["trace"]):
+        assert a[:4] == b[:4] and all(_bits(a[i]) == _bits(b[i]) for i in (4, 5, 6)), (a, b)
+    fid, w = t.model()
+    assert list(fid) == r["fid"] and [_bits(x) for x in w] == [_bits(x) for x in r["weight"]]
+    ts, vs = t.scores()
+    assert _bits(ts) == _bits(r["train"])
+    if va is not None:
+        assert _bits(vs) == _bits(r["valid"])
+    return r
+
+
+def _ext_case(metric):
+    rng = np.random.default_rng(71)
+    tr, va = E.shared_sets(rng, n_train=40)
+    # ideals of at least every list's own: a smaller one scores a list above 1, where only the weak table is compared
+    m = E.ideal_map([tr, va], 10, rng, (1.0, 2.0)) if metric == "NDCG" else E.count_map([tr, va], rng)
+    return tr, va, m
+
+
+@functools.lru_cache(maxsize=None)
+def _plain(metric, k):
+    """the restatement's run without judgments: computed once per metric, never changed"""
+    tr, va, _ = _ext_case(metric)
+    return AR.learn(tr, va, metric=metric, k=k, nIteration=18)
+
+
+@pytest.mark.parametrize("where", ["train", "valid", "both"])
+@pytest.mark.parametrize("metric,k", [("NDCG", 10), ("MAP", 0)])
+def test_external_judgments_match_the_restatement(metric, k, where):
+    """external ideal DCGs (NaN for the qids without one) and relevant-document counts (0, own, larger) given to the training set, the
+    validation set or both; a qid of both sets given through the validation set alone reaches the training list's score"""
+    tr, va, m = _ext_case(metric)
+    assert any(q in m for q in set(tr[3]) & set(va[3])) and any(q not in m for q in set(tr[3])) and any(q not in m for q in set(va[3]))
+    arrays, ext = E.judgments(metric, m, tr, va, where)
+    r = _learn_or_refuse(tr, va, metric, k, 18, arrays, ext)
+    assert r is not None and sum(1 for x in r["trace"] if x[1] == AR.ROUND) >= 10
+    plain = _plain(metric, k)
+    assert r["trace"] != plain["trace"]
+    if where != "valid" or metric == "NDCG":
+        assert not np.array_equal(r["M"], plain["M"])
+
+
+@pytest.mark.parametrize("metric,k", [("NDCG", 10), ("MAP", 0)])
+def test_weak_table_external_judgments_across_the_length_classes(metric, k):
+    """an external entry (ideals below, at and above the lists' own) on lists of every length class of k_ada_weak"""
+    rng = np.random.default_rng(72)
+    tr = E.data(rng, E.LENGTH_CLASSES, 3, levels=3, prefix="L")
+    m = E.ideal_map([tr], 10, rng, missing=0.2) if metric == "NDCG" else E.count_map([tr], rng)
+    n = np.diff(tr[2])
+    for lo, hi in ((0, 16), (16, 384), (384, 5000), (5000, 1 << 30)):
+        cls = [q for q in range(len(n)) if lo < n[q] <= hi]
+        assert any(tr[3][q] in m and q != cls.index(q) for q in cls), (lo, hi)
+    arrays, ext = E.judgments(metric, m, tr, None, "train")
+    M = AR.weak_table(tr[0], tr[1], tr[2], tr[3], AR.CR.LiteralScorer(metric, k, **ext), metric, k)
+    assert not np.array_equal(M, AR.weak_table(tr[0], tr[1], tr[2], tr[3], AR.CR.LiteralScorer(metric, k), metric, k))
+    t = _trainer(tr, None, metric, k, ext=arrays, n_iteration=0)
+    t.learn()
+    assert np.array_equal(t.weak_table().view(np.int64), M.view(np.int64))
+
+
+def _wrapped_sets(seed, sparse):
+    """labels from {0, 1, 2, 31, 32, 33}; sparse: four documents of the training set hold one of 31, 32, 33"""
+    rng = np.random.default_rng(seed)
+    tr, va = E.shared_sets(rng, labels=(0, 1, 2) if sparse else E.WRAPPED, n_train=40)
+    if sparse:
+        idx = rng.choice(len(tr[1]), 4, replace=False)
+        tr[1][idx] = rng.choice(np.array([31, 32, 33], np.float32), 4)
+    return tr, va
+
+
+@pytest.mark.parametrize("metric,k", [("NDCG", 10), ("DCG", 5), ("ERR", 10)])
+def test_weak_table_wrapped_labels(metric, k):
+    """gains 2147483647, 0 and 1 for labels 31, 32 and 33 (metric/DCGScorer.java:28-31,137-139; ERRScorer.java:71-73)"""
+    tr, _ = _wrapped_sets(0, False)
+    assert {31.0, 32.0, 33.0} <= set(tr[1].tolist())
+    M = AR.weak_table(tr[0], tr[1], tr[2], tr[3], AR.CR.LiteralScorer(metric, k), metric, k)
+    assert np.abs(M).max() > 1e6
+    assert np.array_equal(_weak_gpu(tr, metric, k).view(np.int64), M.view(np.int64))
+
+
+@pytest.mark.parametrize("metric,k,seed,sparse,refused", [
+    ("NDCG", 10, 11, True, False),       # lists score up to 2.49 and every alpha stays finite: 14 rounds
+    ("NDCG", 10, 0, False, True),        # sum w (1 - m) is negative on round 1
+    ("ERR", 10, 7, True, False),
+    ("ERR", 10, 0, False, True),
+    ("DCG", 5, 0, False, True),
+])
+def test_learn_wrapped_labels(metric, k, seed, sparse, refused):
+    tr, va = _wrapped_sets(seed, sparse)
+    r = _learn_or_refuse(tr, va, metric, k, 15)
+    assert (r is None) == refused
+    if r is not None:
+        assert sum(1 for x in r["trace"] if x[1] == AR.ROUND) >= 10 and (metric != "NDCG" or r["M"].max() > 1.0)
+
+
+@pytest.mark.parametrize("metric,k", [("MAP", 0), ("P", 3), ("RR", 10), ("NDCG", 10)])
+def test_fractional_labels(metric, k):
+    """labels of 0.5, 1.5 and 2.99: relevant (label > 0) for MAP / P / RR, (int) label for NDCG"""
+    rng = np.random.default_rng(74)
+    tr, va = E.shared_sets(rng, labels=E.FRACTIONAL, n_train=40)
+    assert {0.5, 1.5} <= set(tr[1].tolist())
+    assert _learn_or_refuse(tr, va, metric, k, 18) is not None
+
+
+def test_external_judgment_refusals():
+    """rl_ada_set_external_judgments forwards to rl_ca_set_external_judgments; a later set_train discards the judgments"""
+    rng = np.random.default_rng(75)
+    tr = E.data(rng, [4, 5, 6, 3], 3)
+    t, t2 = E.forwarded_refusals(lambda: N.AdaRankTrainer(metric="MAP", metric_k=0, n_iteration=2), tr, N.RankLibError)
+    judged = AR.weak_table(tr[0], tr[1], tr[2], tr[3], AR.CR.LiteralScorer("MAP", 0, rel_doc_count=E.REFUSAL_MAP), "MAP", 0)
+    plain = AR.weak_table(tr[0], tr[1], tr[2], tr[3], AR.CR.LiteralScorer("MAP", 0), "MAP", 0)
+    assert not np.array_equal(judged, plain)
+    assert np.array_equal(t.weak_table().view(np.int64), judged.view(np.int64))
+    assert np.array_equal(t2.weak_table().view(np.int64), plain.view(np.int64))
+
+
+@pytest.mark.parametrize("m2t", ["NDCG@10", "MAP"])
+def test_cli_qrel_reaches_the_trainer(tmp_path, m2t):
+    """-qrel <file> with -ranker 3: the saved model is the restatement's, fed the maps the host scorer loaded from the same file, and
+    differs from the model trained without the judgments"""
+    rng = np.random.default_rng(76)
+    X, lab, qoff, _ = _data(rng, rng.integers(2, 25, 30), 4, labels=4)
+    data, qrel, m_q, m_raw = (str(tmp_path / n) for n in ("d.txt", "qrel.txt", "q.txt", "raw.txt"))
+    E.write_letor(data, X, lab, qoff)
+    E.write_qrel(qrel, rng, np.diff(qoff))
+    sc = MetricScorerFactory().createScorer(m2t)
+    sc.loadExternalRelevanceJudgment(qrel)
+    ext = dict(ideal=dict(sc.idealGains)) if m2t != "MAP" else dict(rel_doc_count=dict(sc.relDocCount))
+    metric, k = ("MAP", 0) if m2t == "MAP" else ("NDCG", 10)
+    train = (X, lab, qoff, [str(q) for q in range(len(qoff) - 1)])
+    r, plain = AR.learn(train, None, metric, k, nIteration=15, **ext), AR.learn(train, None, metric, k, nIteration=15)
+    assert r["fid"] and (r["fid"], r["weight"]) != (plain["fid"], plain["weight"])
+    args = ["-train", data, "-ranker", "3", "-metric2t", m2t, "-round", "15"]
+    evaluator.main(args + ["-qrel", qrel, "-save", m_q])
+    evaluator.main(args + ["-save", m_raw])
+    assert evaluator.Evaluator.qrelFile == ""
+    head = "## AdaRank\n## Iteration = 15\n## Train with enqueue: Yes\n## Tolerance = 0.002\n## Max consecutive selection count = 5\n"
+    body = lambda m: " ".join("%d:%s" % (f + 1, java_double_str(w)) for f, w in zip(m["fid"], m["weight"]))      # noqa: E731
+    assert open(m_q).read() == head + body(r)
+    assert open(m_raw).read() == head + body(plain)

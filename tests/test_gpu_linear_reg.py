@@ -1,12 +1,17 @@
 """Linear Regression (-ranker 9) on the MI355X: xTx and xTy as accumulated (rl_lr_debug_gram), the weights, both metric values, evalList and
 the model text bit-identical to the literal restatement of LinearRegRank.learn / solve / eval (tests/lr_restatement.py); ragged cell tiles
 and document slabs for every register block; unknown cells and short rows through the Python class; the refusals; and the command-line
-flow on the LETOR fixtures.  Every comparison is float64.tobytes() equality."""
+flow on the LETOR fixtures.  Every comparison is float64.tobytes() equality.
+
+-qrel judgments are covered by test_external_judgments_match_the_restatement (per set), test_cli_qrel_reaches_the_trainer and
+test_external_judgment_refusals; labels of 31 and above (gains that wrap as Java ints) by test_wrapped_labels; fractional labels, which
+xTy takes as they are, by test_fractional_labels."""
 import os
 
 import numpy as np
 import pytest
 
+import linear_ext as E
 import lr_restatement as LR
 from ranklib_amd import _native as N
 from ranklib_amd import evaluator, learning
@@ -46,14 +51,10 @@ def _data(rng, lengths, F, zero_col=None, tiny=True):
     return X, lab, qoff, ["q%d" % i for i in range(len(lengths))]
 
 
-def _trainer(train, valid=None, metric="NDCG", k=10, err_max=16.0, lam=1E-10, features=None):
-    t = N.LinearRegTrainer(lambda_=lam, metric=metric, metric_k=k, err_max=err_max)
-    X, lab, qoff, qid = train
-    keys = {}
-    t.set_train(X, lab, qoff, qkey=np.array([keys.setdefault(q, len(keys)) for q in qid], np.int32))
-    if valid is not None:
-        Xv, lv, qv, qidv = valid
-        t.set_validation(Xv, lv, qv, qkey=np.array([keys.setdefault(q, len(keys)) for q in qidv], np.int32))
+def _trainer(train, valid=None, metric="NDCG", k=10, err_max=16.0, lam=1E-10, features=None, ext=None):
+    """ext: the per-list external judgments of linear_ext.feed (ideal_tr / ideal_va / rdc_tr / rdc_va)"""
+    t = E.feed(N.LinearRegTrainer(lambda_=lam, metric=metric, metric_k=k, err_max=err_max), train, valid, **(ext or {}))
+    X = train[0]
     if features is not None:
         t.set_features(0, [f - 1 if 1 <= f <= X.shape[1] else -1 for f in features])
     return t
@@ -333,3 +334,91 @@ def test_command_line_flow(tmp_path):
     assert ranker.getScoreOnTrainingData() == java_round(r["train"], 4) and _bits(ranker.getScoreOnValidationData()) == _bits(r["valid"])
     evaluator.main(["-load", model, "-rank", vv, "-score", scores2])
     assert len(open(scores2).readlines()) == b[0].shape[0]
+
+
+# ---- -qrel judgments, labels of 31 and above, fractional labels ---------------------------------------------------------------------
+def _sets(seed, labels=(0, 1, 2)):
+    """linear_ext.shared_sets (repeated qids, a validation set that shares some) with normal feature values: a well-conditioned fit"""
+    rng = np.random.default_rng(seed)
+    tr, va = E.shared_sets(rng, labels=labels)
+    return ((rng.standard_normal(tr[0].shape).astype(np.float32),) + tr[1:], (rng.standard_normal(va[0].shape).astype(np.float32),) + va[1:], rng)
+
+
+@pytest.mark.parametrize("where", ["train", "valid", "both"])
+@pytest.mark.parametrize("metric,k", [("NDCG", 10), ("MAP", 0)])
+def test_external_judgments_match_the_restatement(metric, k, where):
+    """external ideal DCGs (NaN for the qids without one; below, at and above the lists' own) and relevant-document counts (0, own, larger)
+    given to the training set, the validation set or both: the weights stay, the two metric values are the restatement's"""
+    tr, va, rng = _sets(91)
+    m = E.ideal_map([tr, va], 10, rng) if metric == "NDCG" else E.count_map([tr, va], rng)
+    assert any(q in m for q in set(tr[3]) & set(va[3])) and any(q not in m for q in set(tr[3])) and any(q not in m for q in set(va[3]))
+    arrays, ext = E.judgments(metric, m, tr, va, where)
+    r, plain = LR.learn(tr, va, metric, k, **ext), LR.learn(tr, va, metric, k)
+    assert (r["valid"] != plain["valid"]) == (where != "train" or metric == "NDCG")      # counts stay with their set; an ideal DCG is cached for both
+    assert (r["train"] != plain["train"]) == (where != "valid" or metric == "NDCG")
+    t = _trainer(tr, va, metric, k, ext=arrays)
+    t.learn()
+    _assert_same_run(t, r, True)
+
+
+@pytest.mark.parametrize("metric,k", [("NDCG", 10), ("DCG", 5), ("ERR", 10)])
+def test_wrapped_labels(metric, k):
+    """labels of 31, 32 and 33: gains 2147483647, 0 and 1 (metric/DCGScorer.java:28-31,137-139; ERRScorer.java:71-73); the regression
+    fits the labels themselves"""
+    tr, va, _ = _sets(93, E.WRAPPED)
+    assert {31.0, 32.0, 33.0} <= set(tr[1].tolist())
+    _, r = _run(tr, va, metric, k, 16.0, 1E-10)
+    assert abs(r["train"]) > (1e6 if metric != "NDCG" else 0.0)
+
+
+@pytest.mark.parametrize("metric,k", [("MAP", 0), ("P", 3), ("RR", 10), ("NDCG", 10)])
+def test_fractional_labels(metric, k):
+    """labels of 0.5, 1.5 and 2.99 enter xTy as they are (LinearRegRank.java:70-72), count as relevant for MAP / P / RR and as (int) label
+    for NDCG"""
+    tr, va, _ = _sets(94, E.FRACTIONAL)
+    assert {0.5, 1.5} <= set(tr[1].tolist())
+    t, r = _run(tr, va, metric, k, 16.0, 1E-10)
+    assert not np.array_equal(r["xty"], LR.accumulate(tr[0], np.floor(tr[1]), tr[0].shape[1])[1])
+    assert _bits(t.gram()[1]) == _bits(r["xty"])
+
+
+def test_external_judgment_refusals():
+    """rl_lr_set_external_judgments forwards to rl_ca_set_external_judgments; a later set_train discards the judgments"""
+    rng = np.random.default_rng(95)
+    tr = _data(rng, [4, 5, 6, 3], 3, tiny=False)
+    t, t2 = E.forwarded_refusals(lambda: N.LinearRegTrainer(metric="MAP", metric_k=0), tr, N.RankLibError)
+    judged, plain = LR.learn(tr, None, "MAP", 0, rel_doc_count=E.REFUSAL_MAP), LR.learn(tr, None, "MAP", 0)
+    assert judged["train"] != plain["train"]
+    _assert_same_run(t, judged, False)
+    _assert_same_run(t2, plain, False)
+
+
+@pytest.mark.parametrize("m2t", ["NDCG@10", "MAP"])
+def test_cli_qrel_reaches_the_trainer(tmp_path, m2t):
+    """-qrel <file> with -ranker 9.  The weights are a least-squares fit and know no metric, so the saved model is the restatement's with
+    and without the judgments; what the judgments change is the score of the training data the ranker reports, and that is the
+    restatement's fed the maps the host scorer loaded from the same file."""
+    rng = np.random.default_rng(96)
+    X, lab, qoff, _ = _data(rng, rng.integers(2, 25, 30), 4, tiny=False)
+    data, qrel, m_q, m_raw = (str(tmp_path / n) for n in ("d.txt", "qrel.txt", "q.txt", "raw.txt"))
+    E.write_letor(data, X, lab, qoff)
+    E.write_qrel(qrel, rng, np.diff(qoff))
+    sc = MetricScorerFactory().createScorer(m2t)
+    sc.loadExternalRelevanceJudgment(qrel)
+    ext = dict(ideal=dict(sc.idealGains)) if m2t != "MAP" else dict(rel_doc_count=dict(sc.relDocCount))
+    metric, k = ("MAP", 0) if m2t == "MAP" else ("NDCG", 10)
+    train = (X, lab, qoff, [str(q) for q in range(len(qoff) - 1)])
+    r, plain = LR.learn(train, None, metric, k, **ext), LR.learn(train, None, metric, k)
+    assert java_round(r["train"], 4) != java_round(plain["train"], 4)
+    args = ["-train", data, "-ranker", "9", "-metric2t", m2t]
+    try:
+        evaluator.main(args + ["-qrel", qrel, "-save", m_q])
+        assert evaluator.Evaluator.qrelFile == qrel           # the Evaluator built now loads the file, as main() just did
+        judged = evaluator.Evaluator(learning.RankerType.LINEAR_REGRESSION, m2t, m2t).evaluate(data)
+    finally:
+        evaluator.Evaluator.qrelFile = ""                     # whatever fails above, no later test inherits the file
+    evaluator.main(args + ["-save", m_raw])
+    assert evaluator.Evaluator.qrelFile == ""
+    raw = evaluator.Evaluator(learning.RankerType.LINEAR_REGRESSION, m2t, m2t).evaluate(data)
+    assert open(m_q).read() == open(m_raw).read() == LR.model_text(r["weight"], [1, 2, 3, 4], 1E-10)
+    assert judged.getScoreOnTrainingData() == java_round(r["train"], 4) and raw.getScoreOnTrainingData() == java_round(plain["train"], 4)

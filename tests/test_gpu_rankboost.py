@@ -1,14 +1,21 @@
 """RankBoost (-ranker 2) on the MI355X: every round's feature, threshold, maxR, R_t, alpha_t, Z_t, train and validation score, the model and
 the final scores bit-identical to the literal restatement of RankBoost.init / learn (tests/rb_restatement.py); the potentials (device-only
-state) bit-identical too; the length classes; the refusals; and the reference's testRanker flow for ranker 2 through the command line."""
+state) bit-identical too; the length classes; the refusals; and the reference's testRanker flow for ranker 2 through the command line.
+
+-qrel judgments are covered by test_external_judgments_match_the_restatement (per set), test_cli_qrel_reaches_the_trainer and
+test_external_judgment_refusals; labels of 31 and above (gains that wrap as Java ints) by test_wrapped_labels; fractional labels, which
+the crucial pairs and getCorrectRanking() compare as floats (RankBoost.java:157,173; RankList.java:84-90), by test_fractional_labels."""
+import functools
+
 import numpy as np
 import pytest
 
+import linear_ext as E
 import rb_restatement as RB
 from ranklib_amd import _native as N
 from ranklib_amd import evaluator, learning
 from ranklib_amd.learning import AdaRank, DataPoint, LambdaMART, RankBoost, RankList, java_double_str
-from ranklib_amd.metric import ERRScorer
+from ranklib_amd.metric import ERRScorer, MetricScorerFactory
 
 pytestmark = pytest.mark.gpu
 
@@ -31,15 +38,9 @@ def _data(rng, lengths, F, levels=3, labels=3):
     return X, lab, qoff, ["q%d" % i for i in range(len(lengths))]
 
 
-def _trainer(train, valid=None, metric="NDCG", k=10, err_max=16.0, **p):
-    t = N.RankBoostTrainer(metric=metric, metric_k=k, err_max=err_max, **p)
-    X, lab, qoff, qid = train
-    keys = {}
-    t.set_train(X, lab, qoff, qkey=np.array([keys.setdefault(q, len(keys)) for q in qid], np.int32))
-    if valid is not None:
-        Xv, lv, qv, qidv = valid
-        t.set_validation(Xv, lv, qv, qkey=np.array([keys.setdefault(q, len(keys)) for q in qidv], np.int32))
-    return t
+def _trainer(train, valid=None, metric="NDCG", k=10, err_max=16.0, ext=None, **p):
+    """ext: the per-list external judgments of linear_ext.feed (ideal_tr / ideal_va / rdc_tr / rdc_va)"""
+    return E.feed(N.RankBoostTrainer(metric=metric, metric_k=k, err_max=err_max, **p), train, valid, **(ext or {}))
 
 
 def _bits(v):
@@ -278,3 +279,109 @@ def test_feature_subset_in_any_order_and_splits(tmp_path):
     assert [x[2] for x in rows] == [java_double_str(v) for v in want]
     evaluator.main(["-train", data, "-ranker", "2", "-kcv", "3", "-tvs", "0.8", "-metric2t", "MAP", "-round", "15"])
     evaluator.main(["-train", data, "-ranker", "2", "-tvs", "0.8", "-metric2t", "NDCG@10", "-round", "15", "-tc", "-1"])
+
+
+# ---- -qrel judgments, labels of 31 and above, fractional labels ---------------------------------------------------------------------
+def _ext_case(metric):
+    rng = np.random.default_rng(81)
+    tr, va = E.shared_sets(rng)
+    m = E.ideal_map([tr, va], 10, rng) if metric == "NDCG" else E.count_map([tr, va], rng)
+    return tr, va, m
+
+
+@functools.lru_cache(maxsize=None)
+def _plain(metric, k):
+    """the restatement's run without judgments: computed once per metric, never changed"""
+    tr, va, _ = _ext_case(metric)
+    return RB.learn(tr, va, metric=metric, k=k, nIteration=15)
+
+
+@pytest.mark.parametrize("where", ["train", "valid", "both"])
+@pytest.mark.parametrize("metric,k", [("NDCG", 10), ("MAP", 0)])
+def test_external_judgments_match_the_restatement(metric, k, where):
+    """external ideal DCGs (NaN for the qids without one; below, at and above the lists' own) and relevant-document counts (0, own, larger)
+    given to the training set, the validation set or both: every round's train and validation score, and the best prefix on validation data"""
+    tr, va, m = _ext_case(metric)
+    assert any(q in m for q in set(tr[3]) & set(va[3])) and any(q not in m for q in set(tr[3])) and any(q not in m for q in set(va[3]))
+    arrays, ext = E.judgments(metric, m, tr, va, where)
+    r = RB.learn(tr, va, metric=metric, k=k, nIteration=15, **ext)
+    plain = _plain(metric, k)
+    assert len(r["trace"]) == 15
+    if where != "train" or metric == "NDCG":                 # counts stay with their set; an ideal DCG is cached for both
+        assert [x[8] for x in r["trace"]] != [x[8] for x in plain["trace"]]
+    if where != "valid" or metric == "NDCG":                 # (valid, NDCG): a qid of both sets, given through the validation set alone
+        assert [x[7] for x in r["trace"]] != [x[7] for x in plain["trace"]]
+    t = _trainer(tr, va, metric, k, ext=arrays, n_iteration=15)
+    t.learn()
+    _assert_same_run(t, r, True)
+
+
+@pytest.mark.parametrize("metric,k", [("NDCG", 10), ("DCG", 5), ("ERR", 10)])
+def test_wrapped_labels(metric, k):
+    """labels of 31, 32 and 33: gains 2147483647, 0 and 1 (metric/DCGScorer.java:28-31,137-139; ERRScorer.java:71-73), while the pairs
+    compare the labels themselves"""
+    rng = np.random.default_rng(83)
+    tr, va = E.shared_sets(rng, labels=E.WRAPPED)
+    assert {31.0, 32.0, 33.0} <= set(tr[1].tolist())
+    r = RB.learn(tr, va, metric=metric, k=k, nIteration=15)
+    assert len(r["trace"]) == 15 and max(abs(x[7]) for x in r["trace"]) > (1e6 if metric != "NDCG" else 1.0)
+    t = _trainer(tr, va, metric, k, n_iteration=15)
+    t.learn()
+    _assert_same_run(t, r, True)
+
+
+@pytest.mark.parametrize("metric,k", [("MAP", 0), ("P", 3), ("RR", 10), ("NDCG", 10)])
+def test_fractional_labels(metric, k):
+    """labels of 0.5, 1.5 and 2.99: (0.5, 0) and (2.99, 2) are crucial pairs -- the potentials of round 1 say so directly -- and a 0.5 is
+    relevant for MAP / P / RR, gain 0 for NDCG"""
+    rng = np.random.default_rng(84)
+    tr, va = E.shared_sets(rng, labels=E.FRACTIONAL)
+    assert {0.5, 1.5} <= set(tr[1].tolist())
+    r = RB.learn(tr, va, metric=metric, k=k, nIteration=15, keep_potentials=1)
+    trunc = (tr[0], np.floor(tr[1]), tr[2], tr[3])           # the same lists with (int) labels hold fewer crucial pairs
+    assert not np.array_equal(RB.learn(trunc, None, metric=metric, k=k, nIteration=1, keep_potentials=1)["pots"][0], r["pots"][0])
+    t = _trainer(tr, va, metric, k, n_iteration=15, keep_potentials=1)
+    t.learn()
+    assert np.array_equal(t.potentials(1).view(np.int64), r["pots"][0].view(np.int64))
+    _assert_same_run(t, r, True)
+
+
+def test_external_judgment_refusals():
+    """rl_rb_set_external_judgments forwards to rl_ca_set_external_judgments; a later set_train discards the judgments"""
+    rng = np.random.default_rng(85)
+    tr = E.data(rng, [4, 5, 6, 3], 3)
+    t, t2 = E.forwarded_refusals(lambda: N.RankBoostTrainer(metric="MAP", metric_k=0, n_iteration=2), tr, N.RankLibError)
+    judged, plain = RB.learn(tr, None, "MAP", 0, nIteration=2, rel_doc_count=E.REFUSAL_MAP), RB.learn(tr, None, "MAP", 0, nIteration=2)
+    assert judged["train"] != plain["train"]
+    _assert_same_run(t, judged, False)
+    _assert_same_run(t2, plain, False)
+
+
+@pytest.mark.parametrize("m2t", ["NDCG@10", "MAP"])
+def test_cli_qrel_reaches_the_trainer(tmp_path, m2t):
+    """-qrel <file> with -ranker 2 and -validate (the judgments reach a RankBoost model through the best prefix on validation data only):
+    the saved model is the restatement's, fed the maps the host scorer loaded from the same file, and differs from the model trained
+    without the judgments"""
+    rng = np.random.default_rng(86)
+    tr = E.data(rng, rng.integers(2, 25, 30), 4, (0, 1, 2, 3), levels=7)
+    va = E.data(rng, rng.integers(2, 25, 12), 4, (0, 1, 2, 3), levels=7)
+    data, vdata, qrel, m_q, m_raw = (str(tmp_path / n) for n in ("d.txt", "v.txt", "qrel.txt", "q.txt", "raw.txt"))
+    E.write_letor(data, *tr[:3])
+    E.write_letor(vdata, *va[:3], qid0=30)                   # the validation qids go on from the training file's: 30 .. 41
+    E.write_qrel(qrel, rng, np.concatenate([np.diff(tr[2]), np.diff(va[2])]))
+    sc = MetricScorerFactory().createScorer(m2t)
+    sc.loadExternalRelevanceJudgment(qrel)
+    ext = dict(ideal=dict(sc.idealGains)) if m2t != "MAP" else dict(rel_doc_count=dict(sc.relDocCount))
+    metric, k = ("MAP", 0) if m2t == "MAP" else ("NDCG", 10)
+    train, valid = tr[:3] + ([str(q) for q in range(30)],), va[:3] + ([str(q + 30) for q in range(12)],)
+    r, plain = RB.learn(train, valid, metric, k, nIteration=15, **ext), RB.learn(train, valid, metric, k, nIteration=15)
+    assert r["fid"] and len(r["fid"]) != len(plain["fid"])
+    args = ["-train", data, "-validate", vdata, "-ranker", "2", "-metric2t", m2t, "-round", "15"]
+    evaluator.main(args + ["-qrel", qrel, "-save", m_q])
+    evaluator.main(args + ["-save", m_raw])
+    assert evaluator.Evaluator.qrelFile == ""
+    head = "## RankBoost\n## Iteration = 15\n## No. of threshold candidates = 10\n"
+    body = lambda m: " ".join("%d:%s:%s" % (f + 1, java_double_str(t), java_double_str(w))      # noqa: E731
+                              for f, t, w in zip(m["fid"], m["thr"], m["weight"]))
+    assert open(m_q).read() == head + body(r)
+    assert open(m_raw).read() == head + body(plain)
