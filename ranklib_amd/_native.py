@@ -177,62 +177,36 @@ def lib():
     L.rl_set_err_max.argtypes = [C.c_double]
     L.rl_set_timing_flags.argtypes = [vp, i32]
     L.rl_debug_membench.argtypes = [i32, i32, i64, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    if hasattr(L, "rl_ca_create"):      # (A/B builds of older sources lack Coordinate Ascent)
-        L.rl_ca_params_default.argtypes = [C.POINTER(RlCaParams)]
-        L.rl_ca_params_default.restype = None
-        L.rl_ca_create.argtypes = [C.POINTER(RlCaParams), C.POINTER(vp)]
-        L.rl_ca_destroy.argtypes = [vp]
-        L.rl_ca_destroy.restype = None
-        L.rl_ca_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
-        L.rl_ca_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
-        L.rl_ca_set_external_judgments.argtypes = [vp, i32, vp, vp]
-        L.rl_ca_learn.argtypes = [vp]
+    for pre, params in (("rl_ca_", RlCaParams), ("rl_ada_", RlAdaParams), ("rl_rb_", RlRbParams), ("rl_lr_", RlLrParams)):
+        if not hasattr(L, pre + "create"):      # (A/B builds of older sources lack the later linear rankers)
+            continue
+        fn = lambda name: getattr(L, pre + name)      # noqa: E731
+        fn("params_default").argtypes = [C.POINTER(params)]
+        fn("params_default").restype = None
+        fn("create").argtypes = [C.POINTER(params), C.POINTER(vp)]
+        fn("destroy").argtypes = [vp]
+        fn("destroy").restype = None
+        fn("set_train").argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
+        fn("set_validation").argtypes = [vp, vp, i64, vp, vp, i32, vp]
+        fn("set_external_judgments").argtypes = [vp, i32, vp, vp]
+        fn("learn").argtypes = [vp]
+        fn("scores").argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_ca_create"):
         L.rl_ca_get_weights.argtypes = [vp, vp, i32]
-        L.rl_ca_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_ca_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_ca_predict.argtypes = [i32, vp, vp, i32, vp, i64, i32, vp]
-    if hasattr(L, "rl_ada_create"):     # (A/B builds of older sources lack AdaRank)
-        L.rl_ada_params_default.argtypes = [C.POINTER(RlAdaParams)]
-        L.rl_ada_params_default.restype = None
-        L.rl_ada_create.argtypes = [C.POINTER(RlAdaParams), C.POINTER(vp)]
-        L.rl_ada_destroy.argtypes = [vp]
-        L.rl_ada_destroy.restype = None
-        L.rl_ada_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
-        L.rl_ada_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
-        L.rl_ada_set_external_judgments.argtypes = [vp, i32, vp, vp]
-        L.rl_ada_learn.argtypes = [vp]
+    if hasattr(L, "rl_ada_create"):
         L.rl_ada_get_model.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
-        L.rl_ada_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_ada_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_ada_debug_weak_table.argtypes = [vp, vp, i64]
-    if hasattr(L, "rl_rb_create"):      # (A/B builds of older sources lack RankBoost)
-        L.rl_rb_params_default.argtypes = [C.POINTER(RlRbParams)]
-        L.rl_rb_params_default.restype = None
-        L.rl_rb_create.argtypes = [C.POINTER(RlRbParams), C.POINTER(vp)]
-        L.rl_rb_destroy.argtypes = [vp]
-        L.rl_rb_destroy.restype = None
-        L.rl_rb_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
-        L.rl_rb_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
-        L.rl_rb_set_external_judgments.argtypes = [vp, i32, vp, vp]
-        L.rl_rb_learn.argtypes = [vp]
+    if hasattr(L, "rl_rb_create"):
         L.rl_rb_get_model.argtypes = [vp, vp, vp, vp, i32, C.POINTER(i32)]
-        L.rl_rb_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_rb_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_rb_debug_potentials.argtypes = [vp, i32, vp, i64]
         L.rl_rb_predict.argtypes = [i32, vp, vp, vp, i32, vp, i64, i32, vp]
-    if hasattr(L, "rl_lr_create"):      # (A/B builds of older sources lack Linear Regression)
-        L.rl_lr_params_default.argtypes = [C.POINTER(RlLrParams)]
-        L.rl_lr_params_default.restype = None
-        L.rl_lr_create.argtypes = [C.POINTER(RlLrParams), C.POINTER(vp)]
-        L.rl_lr_destroy.argtypes = [vp]
-        L.rl_lr_destroy.restype = None
-        L.rl_lr_set_train.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp]
-        L.rl_lr_set_validation.argtypes = [vp, vp, i64, vp, vp, i32, vp]
-        L.rl_lr_set_external_judgments.argtypes = [vp, i32, vp, vp]
+    if hasattr(L, "rl_lr_create"):
         L.rl_lr_set_features.argtypes = [vp, i32, vp, i32]
-        L.rl_lr_learn.argtypes = [vp]
         L.rl_lr_get_weights.argtypes = [vp, vp, i32, C.POINTER(i32)]
-        L.rl_lr_scores.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_lr_debug_gram.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
         L.rl_lr_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
         L.rl_lr_predict.argtypes = [i32, vp, i32, vp, i32, vp, i64, i32, vp]
@@ -629,73 +603,69 @@ class Model:
             pass
 
 
-class CoorAscentTrainer:
-    """Thin object wrapper over the rl_ca handle: CoorAscent.learn() on one GPU (rl_ca.hip)."""
+class _LinearTrainer:
+    """What the handles of the four linear rankers share (rl_linear.inc): a subclass names its C prefix, the ranker as the messages call
+    it and its trace records, and fills its own parameters."""
+    _prefix = _name = _trace_dtype = None
 
-    def __init__(self, n_restart=5, n_max_iteration=25, step_base=0.05, step_scale=2.0, tolerance=0.001, regularized=False, slack=0.001,
-                 metric="NDCG", metric_k=10, device=0, seed=0, err_max=16.0):
-        L = lib()
-        self.p = RlCaParams()
-        L.rl_ca_params_default(C.byref(self.p))
-        self.p.n_restart, self.p.n_max_iteration = int(n_restart), int(n_max_iteration)
-        self.p.step_base, self.p.step_scale, self.p.tolerance = float(step_base), float(step_scale), float(tolerance)
-        self.p.regularized, self.p.slack = 1 if regularized else 0, float(slack)
+    def _fn(self, name):
+        return getattr(lib(), self._prefix + name)
+
+    def _open(self, params, metric, metric_k, device, err_max, **own):
+        """creates the handle: the ranker's defaults, the common parameters, then its own"""
+        self.p = params()
+        self._fn("params_default")(C.byref(self.p))
         m = metric.upper()
         if m not in RL_CA_METRIC:
-            raise RankLibError("rlhip: the Coordinate Ascent train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
-        self.p.metric, self.p.metric_k, self.p.device = RL_CA_METRIC[m], int(metric_k), int(device)
-        self.p.seed = ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)      # a Java long
-        self.p.err_max = float(err_max)
+            raise RankLibError("rlhip: the %s train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % (self._name, metric))
+        self.p.metric, self.p.metric_k, self.p.device, self.p.err_max = RL_CA_METRIC[m], int(metric_k), int(device), float(err_max)
+        for k, v in own.items():
+            setattr(self.p, k, v)
         self.h = C.c_void_p()
-        check(L.rl_ca_create(C.byref(self.p), C.byref(self.h)))
-        self.F = 0
+        check(self._fn("create")(C.byref(self.p), C.byref(self.h)))
+        self.F = self.Q = self.N = 0
         self.has_valid = False
 
     def set_train(self, X, labels, qoff, qkey=None):
         X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
-        self.F = X.shape[1]
-        check(lib().rl_ca_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+        self.F, self.Q, self.N = X.shape[1], len(qoff) - 1, X.shape[0]
+        check(self._fn("set_train")(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
                                     None if qk is None else qk.ctypes.data))
 
     def set_validation(self, X, labels, qoff, qkey=None):
         X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
         if X.shape[1] != self.F:
             raise RankLibError("validation set must have the training set's feature columns")
-        check(lib().rl_ca_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
+        check(self._fn("set_validation")(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
                                          None if qk is None else qk.ctypes.data))
         self.has_valid = True
 
     def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
         idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
         rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
-        check(lib().rl_ca_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
+        check(self._fn("set_external_judgments")(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
                                                  None if rdc is None else rdc.ctypes.data))
 
     def learn(self):
-        check(lib().rl_ca_learn(self.h))
-
-    def weights(self):
-        w = np.zeros(max(1, self.F), np.float64)
-        check(lib().rl_ca_get_weights(self.h, w.ctypes.data, len(w)))
-        return w[:self.F]
+        check(self._fn("learn")(self.h))
 
     def scores(self):
         ts, vs = C.c_double(0), C.c_double(0)
-        check(lib().rl_ca_scores(self.h, C.byref(ts), C.byref(vs)))
+        check(self._fn("scores")(self.h, C.byref(ts), C.byref(vs)))
         return ts.value, (vs.value if self.has_valid else None)
 
     def trace(self):
-        """structured array (CA_TRACE_DTYPE): one record per restart, pass, trial, success and validation score, in the Java's order"""
+        """structured array (the class's trace dtype) of what learn() did, in the Java's order"""
         n = C.c_int64(0)
-        check(lib().rl_ca_trace(self.h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, CA_TRACE_DTYPE)
+        check(self._fn("trace")(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, self._trace_dtype)
         if n.value:
-            check(lib().rl_ca_trace(self.h, out.ctypes.data, n.value, C.byref(n)))
+            check(self._fn("trace")(self.h, out.ctypes.data, n.value, C.byref(n)))
         return out
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:
-            lib().rl_ca_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -705,47 +675,33 @@ class CoorAscentTrainer:
             pass
 
 
-class AdaRankTrainer:
-    """Thin object wrapper over the rl_ada handle: AdaRank.learn() on one GPU (rl_ada.inc in rl_ca.hip)."""
+class CoorAscentTrainer(_LinearTrainer):
+    """Thin object wrapper over the rl_ca handle: CoorAscent.learn() on one GPU (rl_ca.hip).
+    trace(): CA_TRACE_DTYPE, one record per restart, pass, trial, success and validation score."""
+    _prefix, _name, _trace_dtype = "rl_ca_", "Coordinate Ascent", CA_TRACE_DTYPE
+
+    def __init__(self, n_restart=5, n_max_iteration=25, step_base=0.05, step_scale=2.0, tolerance=0.001, regularized=False, slack=0.001,
+                 metric="NDCG", metric_k=10, device=0, seed=0, err_max=16.0):
+        self._open(RlCaParams, metric, metric_k, device, err_max, n_restart=int(n_restart), n_max_iteration=int(n_max_iteration),
+                   step_base=float(step_base), step_scale=float(step_scale), tolerance=float(tolerance),
+                   regularized=1 if regularized else 0, slack=float(slack),
+                   seed=((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63))      # a Java long
+
+    def weights(self):
+        w = np.zeros(max(1, self.F), np.float64)
+        check(lib().rl_ca_get_weights(self.h, w.ctypes.data, len(w)))
+        return w[:self.F]
+
+
+class AdaRankTrainer(_LinearTrainer):
+    """Thin object wrapper over the rl_ada handle: AdaRank.learn() on one GPU (rl_ada.inc in rl_ca.hip).
+    trace(): ADA_TRACE_DTYPE, one record per phase start, round and rollback."""
+    _prefix, _name, _trace_dtype = "rl_ada_", "AdaRank", ADA_TRACE_DTYPE
 
     def __init__(self, n_iteration=500, tolerance=0.002, train_with_enqueue=True, max_sel_count=5, metric="NDCG", metric_k=10, device=0,
                  err_max=16.0):
-        L = lib()
-        self.p = RlAdaParams()
-        L.rl_ada_params_default(C.byref(self.p))
-        self.p.n_iteration, self.p.tolerance = int(n_iteration), float(tolerance)
-        self.p.train_with_enqueue, self.p.max_sel_count = 1 if train_with_enqueue else 0, int(max_sel_count)
-        m = metric.upper()
-        if m not in RL_CA_METRIC:
-            raise RankLibError("rlhip: the AdaRank train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
-        self.p.metric, self.p.metric_k, self.p.device, self.p.err_max = RL_CA_METRIC[m], int(metric_k), int(device), float(err_max)
-        self.h = C.c_void_p()
-        check(L.rl_ada_create(C.byref(self.p), C.byref(self.h)))
-        self.F = self.Q = 0
-        self.has_valid = False
-
-    def set_train(self, X, labels, qoff, qkey=None):
-        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
-        self.F, self.Q = X.shape[1], len(qoff) - 1
-        check(lib().rl_ada_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
-                                     None if qk is None else qk.ctypes.data))
-
-    def set_validation(self, X, labels, qoff, qkey=None):
-        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
-        if X.shape[1] != self.F:
-            raise RankLibError("validation set must have the training set's feature columns")
-        check(lib().rl_ada_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
-                                          None if qk is None else qk.ctypes.data))
-        self.has_valid = True
-
-    def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
-        idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
-        rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
-        check(lib().rl_ada_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
-                                                  None if rdc is None else rdc.ctypes.data))
-
-    def learn(self):
-        check(lib().rl_ada_learn(self.h))
+        self._open(RlAdaParams, metric, metric_k, device, err_max, n_iteration=int(n_iteration), tolerance=float(tolerance),
+                   train_with_enqueue=1 if train_with_enqueue else 0, max_sel_count=int(max_sel_count))
 
     def model(self):
         """(feature indices, weights) of the final ensemble, in ensemble order (an index may repeat)"""
@@ -755,77 +711,21 @@ class AdaRankTrainer:
         check(lib().rl_ada_get_model(self.h, fid.ctypes.data, w.ctypes.data, n.value, C.byref(n)))
         return fid[:n.value], w[:n.value]
 
-    def scores(self):
-        ts, vs = C.c_double(0), C.c_double(0)
-        check(lib().rl_ada_scores(self.h, C.byref(ts), C.byref(vs)))
-        return ts.value, (vs.value if self.has_valid else None)
-
-    def trace(self):
-        """structured array (ADA_TRACE_DTYPE): one record per phase start, round and rollback, in the Java's order"""
-        n = C.c_int64(0)
-        check(lib().rl_ada_trace(self.h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, ADA_TRACE_DTYPE)
-        if n.value:
-            check(lib().rl_ada_trace(self.h, out.ctypes.data, n.value, C.byref(n)))
-        return out
-
     def weak_table(self):
         """[F, Q] f64: scorer.score(WeakRanker(f).rank(list q)) as the GPU built it"""
         out = np.zeros((self.F, self.Q), np.float64)
         check(lib().rl_ada_debug_weak_table(self.h, out.ctypes.data, out.size))
         return out
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().rl_ada_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RankBoostTrainer:
-    """Thin object wrapper over the rl_rb handle: RankBoost.init() and learn() on one GPU (rl_rb.inc in rl_ca.hip)."""
+class RankBoostTrainer(_LinearTrainer):
+    """Thin object wrapper over the rl_rb handle: RankBoost.init() and learn() on one GPU (rl_rb.inc in rl_ca.hip).
+    trace(): RB_TRACE_DTYPE, one record per round."""
+    _prefix, _name, _trace_dtype = "rl_rb_", "RankBoost", RB_TRACE_DTYPE
 
     def __init__(self, n_iteration=300, n_threshold=10, metric="NDCG", metric_k=10, device=0, err_max=16.0, keep_potentials=0):
-        L = lib()
-        self.p = RlRbParams()
-        L.rl_rb_params_default(C.byref(self.p))
-        self.p.n_iteration, self.p.n_threshold, self.p.keep_potentials = int(n_iteration), int(n_threshold), int(keep_potentials)
-        m = metric.upper()
-        if m not in RL_CA_METRIC:
-            raise RankLibError("rlhip: the RankBoost train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
-        self.p.metric, self.p.metric_k, self.p.device, self.p.err_max = RL_CA_METRIC[m], int(metric_k), int(device), float(err_max)
-        self.h = C.c_void_p()
-        check(L.rl_rb_create(C.byref(self.p), C.byref(self.h)))
-        self.F = self.Q = self.N = 0
-        self.has_valid = False
-
-    def set_train(self, X, labels, qoff, qkey=None):
-        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
-        self.F, self.Q, self.N = X.shape[1], len(qoff) - 1, X.shape[0]
-        check(lib().rl_rb_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
-                                    None if qk is None else qk.ctypes.data))
-
-    def set_validation(self, X, labels, qoff, qkey=None):
-        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
-        if X.shape[1] != self.F:
-            raise RankLibError("validation set must have the training set's feature columns")
-        check(lib().rl_rb_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
-                                         None if qk is None else qk.ctypes.data))
-        self.has_valid = True
-
-    def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
-        idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
-        rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
-        check(lib().rl_rb_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
-                                                 None if rdc is None else rdc.ctypes.data))
-
-    def learn(self):
-        check(lib().rl_rb_learn(self.h))
+        self._open(RlRbParams, metric, metric_k, device, err_max, n_iteration=int(n_iteration), n_threshold=int(n_threshold),
+                   keep_potentials=int(keep_potentials))
 
     def model(self):
         """(feature indices, thresholds, weights) of the final ensemble, in ensemble order (an index may repeat)"""
@@ -836,89 +736,25 @@ class RankBoostTrainer:
         check(lib().rl_rb_get_model(self.h, fid.ctypes.data, thr.ctypes.data, w.ctypes.data, n.value, C.byref(n)))
         return fid[:n.value], thr[:n.value], w[:n.value]
 
-    def scores(self):
-        ts, vs = C.c_double(0), C.c_double(0)
-        check(lib().rl_rb_scores(self.h, C.byref(ts), C.byref(vs)))
-        return ts.value, (vs.value if self.has_valid else None)
-
-    def trace(self):
-        """structured array (RB_TRACE_DTYPE): one record per round"""
-        n = C.c_int64(0)
-        check(lib().rl_rb_trace(self.h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, RB_TRACE_DTYPE)
-        if n.value:
-            check(lib().rl_rb_trace(self.h, out.ctypes.data, n.value, C.byref(n)))
-        return out
-
     def potentials(self, round):       # noqa: A002
         """[N] f64: the potentials of round `round` (1 .. keep_potentials), every list in getCorrectRanking()'s order"""
         out = np.zeros(self.N, np.float64)
         check(lib().rl_rb_debug_potentials(self.h, int(round), out.ctypes.data, out.size))
         return out
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().rl_rb_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def rb_predict(feature_ids, thresholds, weights, rows, device=0):
-    """RankBoost.eval on the GPU: rows[:, f] holds feature ID f (column 0 unused, like DataPoint.fVals); f64 scores"""
-    rows = np.ascontiguousarray(rows, dtype=np.float32)
-    fid = np.ascontiguousarray(feature_ids, dtype=np.int32)
-    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
-    w = np.ascontiguousarray(weights, dtype=np.float64)
-    out = np.zeros(rows.shape[0], np.float64)
-    check(lib().rl_rb_predict(int(device), fid.ctypes.data, thr.ctypes.data, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0],
-                              rows.shape[1], out.ctypes.data))
-    return out
-
-
-class LinearRegTrainer:
-    """Thin object wrapper over the rl_lr handle: LinearRegRank.learn() on one GPU (rl_lr.inc in rl_ca.hip)."""
+class LinearRegTrainer(_LinearTrainer):
+    """Thin object wrapper over the rl_lr handle: LinearRegRank.learn() on one GPU (rl_lr.inc in rl_ca.hip).  It keeps no trace."""
+    _prefix, _name = "rl_lr_", "Linear Regression"
 
     def __init__(self, lambda_=1E-10, metric="NDCG", metric_k=10, device=0, err_max=16.0):
-        L = lib()
-        if not hasattr(L, "rl_lr_create"):
+        if not hasattr(lib(), "rl_lr_create"):
             raise RankLibError("rlhip: this librlhip.so has no Linear Regression (rl_lr_*)")
-        self.p = RlLrParams()
-        L.rl_lr_params_default(C.byref(self.p))
-        m = metric.upper()
-        if m not in RL_CA_METRIC:
-            raise RankLibError("rlhip: the Linear Regression train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % metric)
-        self.p.lambda_, self.p.metric, self.p.metric_k, self.p.device, self.p.err_max = (float(lambda_), RL_CA_METRIC[m], int(metric_k),
-                                                                                          int(device), float(err_max))
-        self.h = C.c_void_p()
-        check(L.rl_lr_create(C.byref(self.p), C.byref(self.h)))
-        self.F = self.Q = self.N = 0
-        self.has_valid = False
+        self._open(RlLrParams, metric, metric_k, device, err_max, lambda_=float(lambda_))
 
     def set_train(self, X, labels, qoff, qkey=None):
         """X[:, f] = getFeatureValue(f + 1): the fit reads columns 0 .. nVar - 2, whatever the feature list says"""
-        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
-        self.F, self.Q, self.N = X.shape[1], len(qoff) - 1, X.shape[0]
-        check(lib().rl_lr_set_train(self.h, X.ctypes.data, X.shape[0], self.F, labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
-                                    None if qk is None else qk.ctypes.data))
-
-    def set_validation(self, X, labels, qoff, qkey=None):
-        X, labels, qoff, qk = Trainer._prep(X, labels, qoff, qkey)
-        if X.shape[1] != self.F:
-            raise RankLibError("validation set must have the training set's feature columns")
-        check(lib().rl_lr_set_validation(self.h, X.ctypes.data, X.shape[0], labels.ctypes.data, qoff.ctypes.data, len(qoff) - 1,
-                                         None if qk is None else qk.ctypes.data))
-        self.has_valid = True
-
-    def set_external_judgments(self, validation, ideal_dcg=None, rel_doc_count=None):
-        idl = None if ideal_dcg is None else np.ascontiguousarray(ideal_dcg, dtype=np.float64)
-        rdc = None if rel_doc_count is None else np.ascontiguousarray(rel_doc_count, dtype=np.int32)
-        check(lib().rl_lr_set_external_judgments(self.h, 1 if validation else 0, None if idl is None else idl.ctypes.data,
-                                                 None if rdc is None else rdc.ctypes.data))
+        super().set_train(X, labels, qoff, qkey)
 
     def set_features(self, n_var=0, eval_cols=None):
         """n_var: the Java's nVar (0 = every column); eval_cols: the columns eval() reads (features[i] - 1; -1 reads 0), None = all"""
@@ -926,20 +762,12 @@ class LinearRegTrainer:
         keep = np.zeros(1, np.int32) if cols is not None and cols.size == 0 else cols      # an empty list is still a list: a real pointer
         check(lib().rl_lr_set_features(self.h, int(n_var), None if keep is None else keep.ctypes.data, 0 if cols is None else cols.size))
 
-    def learn(self):
-        check(lib().rl_lr_learn(self.h))
-
     def weights(self):
         n = C.c_int32(0)
         check(lib().rl_lr_get_weights(self.h, None, 0, C.byref(n)))
         w = np.zeros(max(1, n.value), np.float64)
         check(lib().rl_lr_get_weights(self.h, w.ctypes.data, n.value, C.byref(n)))
         return w[:n.value]
-
-    def scores(self):
-        ts, vs = C.c_double(0), C.c_double(0)
-        check(lib().rl_lr_scores(self.h, C.byref(ts), C.byref(vs)))
-        return ts.value, (vs.value if self.has_valid else None)
 
     def gram(self):
         """(xTx [nVar, nVar], xTy [nVar]) as accumulated, before the ridge term"""
@@ -955,16 +783,29 @@ class LinearRegTrainer:
         check(lib().rl_lr_debug_times(self.h, C.byref(g), C.byref(s), C.byref(e), C.byref(rb)))
         return dict(gram_ms=g.value, solve_ms=s.value, score_ms=e.value, register_block=rb.value)
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            lib().rl_lr_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _predict_arrays(feature_ids, weights, rows):
+    """the predict functions' arguments as the library takes them, and the f64 scores to fill"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    return (rows, np.ascontiguousarray(feature_ids, dtype=np.int32), np.ascontiguousarray(weights, dtype=np.float64),
+            np.zeros(rows.shape[0], np.float64))
+
+
+def ca_predict(feature_ids, weights, rows, device=0):
+    """CoorAscent.eval on the GPU: rows[:, f] holds feature ID f (column 0 unused, like DataPoint.fVals); f64 scores"""
+    rows, fid, w, out = _predict_arrays(feature_ids, weights, rows)
+    check(lib().rl_ca_predict(int(device), fid.ctypes.data, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0], rows.shape[1],
+                              out.ctypes.data))
+    return out
+
+
+def rb_predict(feature_ids, thresholds, weights, rows, device=0):
+    """RankBoost.eval on the GPU: rows as ca_predict's; f64 scores"""
+    rows, fid, w, out = _predict_arrays(feature_ids, weights, rows)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    check(lib().rl_rb_predict(int(device), fid.ctypes.data, thr.ctypes.data, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0],
+                              rows.shape[1], out.ctypes.data))
+    return out
 
 
 def lr_predict(feature_ids, weights, rows, device=0):
@@ -972,22 +813,8 @@ def lr_predict(feature_ids, weights, rows, device=0):
     L = lib()
     if not hasattr(L, "rl_lr_predict"):
         raise RankLibError("rlhip: this librlhip.so has no Linear Regression (rl_lr_*)")
-    rows = np.ascontiguousarray(rows, dtype=np.float32)
-    fid = np.ascontiguousarray(feature_ids, dtype=np.int32)
-    w = np.ascontiguousarray(weights, dtype=np.float64)
-    out = np.zeros(rows.shape[0], np.float64)
+    rows, fid, w, out = _predict_arrays(feature_ids, weights, rows)
     keep = fid if fid.size else np.zeros(1, np.int32)
     check(L.rl_lr_predict(int(device), keep.ctypes.data, fid.size, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0], rows.shape[1],
                           out.ctypes.data))
-    return out
-
-
-def ca_predict(feature_ids, weights, rows, device=0):
-    """CoorAscent.eval on the GPU: rows[:, f] holds feature ID f (column 0 unused, like DataPoint.fVals); f64 scores"""
-    rows = np.ascontiguousarray(rows, dtype=np.float32)
-    fid = np.ascontiguousarray(feature_ids, dtype=np.int32)
-    w = np.ascontiguousarray(weights, dtype=np.float64)
-    out = np.zeros(rows.shape[0], np.float64)
-    check(lib().rl_ca_predict(int(device), fid.ctypes.data, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0], rows.shape[1],
-                              out.ctypes.data))
     return out

@@ -1,5 +1,6 @@
-// rl_ada.inc -- AdaRank (-ranker 3, learning/boosting/AdaRank.java) on gfx950; included at the end of rl_ca.hip, whose scorer
-// (ca_metric), trial kernel (k_ca_trials) and device sets it reuses.
+// rl_ada.inc -- AdaRank (-ranker 3, learning/boosting/AdaRank.java) on gfx950; included at the end of rl_ca.hip.  The handle holds a
+// ranking context (LinCtx, rl_linear.inc: the device sets, the stream, the common entry-point bodies) and uses rl_ca.hip's scorer
+// (ca_metric) and trial kernel (k_ca_trials).
 //
 // Every number an AdaRank round needs is a list metric:
 //   * the weak rankers' table M[q][f] = scorer.score(WeakRanker(f).rank(list q)): constant over the run (the list ranked by feature f
@@ -17,7 +18,7 @@
 //                        k_ca_trials': <= 16 documents (16 lanes), <= 384 (one wavefront), <= 5000 (one block, LDS), longer (one block,
 //                        global scratch, features in chunks).
 //   k_ada_select         lane f: the three list-order f64 chains of feature f; M is [Q][F] so a row load is contiguous across lanes.
-//   k_ada_recompute      the final model from scratch: 0.0 + w[0] x[c0] + w[1] x[c1] + ... (AdaRank.eval :265-271, repeated columns).
+// The final model is scored from scratch by k_lin_score: 0.0 + w[0] x[c0] + w[1] x[c1] + ... (AdaRank.eval :265-271, repeated columns).
 //
 // log / exp are the host C library's (SimpleMath.ln = log(x) / log(e), Math.exp), the functions Python's math module calls too.
 
@@ -94,24 +95,13 @@ __global__ void k_ada_select(const double *M, const double *sw, int32_t Q, int32
     out[2 * F + f] = denom;
 }
 
-__global__ void k_ada_recompute(double *out, const float *xc, int64_t n, const int32_t *col, const double *w, int32_t T)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0.0;
-    for (int t = 0; t < T; t++) s += w[t] * (double)xc[(int64_t)col[t] * n + i];
-    out[i] = s;
-}
-
 }  // namespace rl
 
 struct rl_ada {
     rl_ada_params p;
-    rl_ca ca;                          // the data sets on the device, the scorer's tables, the trial kernel's buffers and the stream
-    bool learned = false;
+    LinCtx ctx;
     double *d_M = nullptr, *d_sw = nullptr, *d_sel = nullptr;
     std::vector<int32_t> fid; std::vector<double> weight;
-    double train_score = 0, valid_score = 0;
     std::vector<rl_ada_trace_rec> trace;
 };
 
@@ -120,14 +110,14 @@ namespace rl {
 // M[q][f] for every list of set d (the training set): one launch per length class (the longest class in feature chunks of its scratch)
 static int ada_weak_table(rl_ada *A)
 {
-    rl_ca *c = &A->ca;
+    LinCtx *c = &A->ctx;
     CaSet &d = c->tr;
     const int F = c->F;
     RL_HIP(c->buf.alloc(&A->d_M, (size_t)d.Q * F));
     CaArgs a;
     memset(&a, 0, sizeof(a));
     a.labels = d.d_labels; a.qoff = d.d_qoff; a.ideal = d.d_ideal; a.rd_ext = d.d_rd; a.disc = c->d_disc;
-    a.Q = d.Q; a.metric = c->p.metric; a.k = c->p.metric_k; a.err_max = c->err_max;
+    a.Q = d.Q; a.metric = c->metric; a.k = c->metric_k; a.err_max = c->err_max;
     float *hv = nullptr; int32_t *hr = nullptr; int fchunk = F;
     if (d.cls[3].nq) {
         fchunk = (int)std::max<int64_t>(1, std::min<int64_t>(F, ((int64_t)64 << 20) / std::max<int64_t>(1, d.cls[3].nh)));   // <= 512 MiB
@@ -158,7 +148,7 @@ static int ada_weak_table(rl_ada *A)
 // s_f, num_f, denom_f of every feature under the sample weights sw (3 F doubles)
 static int ada_select(rl_ada *A, const std::vector<double> &sw, std::vector<double> &sel)
 {
-    rl_ca *c = &A->ca;
+    LinCtx *c = &A->ctx;
     const int F = c->F;
     RL_HIP(hipMemcpyAsync(A->d_sw, sw.data(), sw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_ada_select, dim3((unsigned)((F + kWave - 1) / kWave)), dim3(kWave), 0, c->stream, (const double *)A->d_M,
@@ -173,7 +163,7 @@ static int ada_select(rl_ada *A, const std::vector<double> &sw, std::vector<doub
 // the ensemble + alpha * x_f on set d: its per-list metrics into m (when given) and scorer.score(rank(d)) into *score
 static int ada_step(rl_ada *A, CaSet &d, int f, double alpha, std::vector<double> *m, double *score)
 {
-    rl_ca *c = &A->ca;
+    LinCtx *c = &A->ctx;
     int rc = ca_trials(c, d, d.d_xc + (size_t)f * d.N, &alpha, 1, 1, score);
     if (rc) return rc;
     if (m) {
@@ -186,29 +176,9 @@ static int ada_step(rl_ada *A, CaSet &d, int f, double alpha, std::vector<double
 // the most recent term off the ensemble: the caches before it are still in the second buffers
 static void ada_undo(rl_ada *A)
 {
-    rl_ca *c = &A->ca;
+    LinCtx *c = &A->ctx;
     std::swap(c->tr.d_cache, c->tr.d_cache2);
     if (c->has_valid) std::swap(c->va.d_cache, c->va.d_cache2);
-}
-
-// scorer.score(rank(d)) of the model (fid, w), the cache recomputed from scratch
-static int ada_score_model(rl_ada *A, CaSet &d, const std::vector<int32_t> &fid, const std::vector<double> &w, double *score)
-{
-    rl_ca *c = &A->ca;
-    CaBuf tmp;
-    int32_t *dc = nullptr; double *dw = nullptr;
-    RL_HIP(tmp.alloc(&dc, fid.size()));
-    RL_HIP(tmp.alloc(&dw, w.size()));
-    if (!fid.empty()) {
-        RL_HIP(hipMemcpyAsync(dc, fid.data(), fid.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        RL_HIP(hipMemcpyAsync(dw, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    hipLaunchKernelGGL(k_ada_recompute, dim3((unsigned)((d.N + 255) / 256)), dim3(256), 0, c->stream, d.d_cache, (const float *)d.d_xc, d.N,
-                       (const int32_t *)dc, (const double *)dw, (int32_t)fid.size());
-    RL_HIP(hipGetLastError());
-    int rc = ca_trials(c, d, nullptr, nullptr, 1, 0, score);
-    RL_HIP(hipStreamSynchronize(c->stream));           // before tmp is freed
-    return rc;
 }
 
 static double ada_ln(double v)
@@ -229,7 +199,7 @@ struct AdaState {                      // the Java object's fields (AdaRank.java
 // AdaRank.learn(startIteration, withEnqueue) :97-202
 static int ada_learn_phase(rl_ada *A, AdaState &S, int start, bool withEnqueue, int *t_out)
 {
-    rl_ca *c = &A->ca;
+    LinCtx *c = &A->ctx;
     const rl_ada_params &P = A->p;
     const int F = c->F, Q = c->tr.Q;
     std::vector<double> sel, m;
@@ -322,7 +292,7 @@ static int ada_learn_phase(rl_ada *A, AdaState &S, int start, bool withEnqueue, 
 
 static int ada_learn(rl_ada *A)
 {
-    rl_ca *c = &A->ca;
+    LinCtx *c = &A->ctx;
     const int F = c->F, Q = c->tr.Q;
     A->trace.clear();
     int rc = ada_weak_table(A);
@@ -356,11 +326,9 @@ static int ada_learn(rl_ada *A)
     }
     if (c->has_valid && !S.bestRankers.empty()) { S.rankers = S.bestRankers; S.rweight = S.bestWeights; }    // :247-252
     A->fid = S.rankers; A->weight = S.rweight;
-    if ((rc = ada_score_model(A, c->tr, A->fid, A->weight, &A->train_score))) return rc;
-    A->valid_score = 0;
-    if (c->has_valid && (rc = ada_score_model(A, c->va, A->fid, A->weight, &A->valid_score))) return rc;
-    A->learned = true;
-    return RL_OK;
+    LinModel m;
+    m.col = A->fid.data(); m.w = A->weight.data(); m.nt = m.nw = (int32_t)A->fid.size();
+    return lin_finish(c, m);
 }
 
 }  // namespace rl
@@ -378,67 +346,46 @@ int rl_ada_create(const rl_ada_params *p, rl_ada **out)
 {
     if (!p || !out) return fail(RL_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (p->metric < RL_METRIC_NDCG || p->metric > RL_METRIC_RR)
-        return fail(RL_ERR_UNSUPPORTED, "AdaRank train metric must be NDCG, DCG, MAP, ERR, P or RR (BEST is not built for training)");
-    rl_ca_params cp;
-    rl_ca_params_default(&cp);
-    cp.metric = p->metric; cp.metric_k = p->metric_k; cp.device = p->device; cp.err_max = p->err_max;
-    rl_ca *c = nullptr;
-    int rc = rl_ca_create(&cp, &c);                           // device checks, the stream
-    if (rc) return rc;
     std::unique_ptr<rl_ada> A(new rl_ada());
     A->p = *p;
-    A->ca.p = c->p; A->ca.err_max = c->err_max;
-    std::swap(A->ca.stream, c->stream);
-    rl_ca_destroy(c);
+    int rc = lin_create(&A->ctx, "AdaRank", p->metric, p->metric_k, p->device, p->err_max);
+    if (rc) return rc;
     *out = A.release();
     return RL_OK;
 }
 
-void rl_ada_destroy(rl_ada *a)
-{
-    if (!a) return;
-    (void)hipSetDevice(a->p.device);
-    if (a->ca.stream) (void)hipStreamSynchronize(a->ca.stream);
-    delete a;
-}
+void rl_ada_destroy(rl_ada *a) { lin_destroy(a); }
 
 int rl_ada_set_train(rl_ada *a, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
                      int32_t n_queries, const int32_t *qkey)
 {
-    if (!a) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_train(&a->ca, X, n_docs, n_features, labels, qoff, n_queries, qkey);
+    return lin_set_train(lin_ctx(a), "rl_ada_", X, n_docs, n_features, labels, qoff, n_queries, qkey);
 }
 
 int rl_ada_set_validation(rl_ada *a, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
                           const int32_t *qkey)
 {
-    if (!a) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_validation(&a->ca, X, n_docs, labels, qoff, n_queries, qkey);
+    return lin_set_validation(lin_ctx(a), "rl_ada_", X, n_docs, labels, qoff, n_queries, qkey);
 }
 
 int rl_ada_set_external_judgments(rl_ada *a, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count)
 {
-    if (!a) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_external_judgments(&a->ca, validation, ideal_dcg, rel_doc_count);
+    return lin_set_external_judgments(lin_ctx(a), "rl_ada_", validation, ideal_dcg, rel_doc_count);
 }
 
 int rl_ada_learn(rl_ada *a)
 {
-    if (!a) return fail(RL_ERR_INVALID, "null handle");
-    if (!a->ca.has_train) return fail(RL_ERR_STATE, "set the training data first");
-    if (a->ca.uploaded) return fail(RL_ERR_STATE, "rl_ada_learn runs once per handle");
-    if (a->p.max_sel_count < 0) return fail(RL_ERR_INVALID, "max_sel_count must be >= 0");
-    RL_HIP(hipSetDevice(a->p.device));
-    int rc = ca_prepare(&a->ca);
+    int rc = lin_begin_learn(lin_ctx(a), "rl_ada_");
     if (rc) return rc;
+    if (a->p.max_sel_count < 0) return fail(RL_ERR_INVALID, "max_sel_count must be >= 0");
+    if ((rc = ca_prepare(&a->ctx))) return rc;
     return ada_learn(a);
 }
 
 int rl_ada_get_model(const rl_ada *a, int32_t *fid, double *weight, int32_t cap, int32_t *n)
 {
     if (!a || !n) return fail(RL_ERR_INVALID, "null argument");
-    if (!a->learned) return fail(RL_ERR_STATE, "rl_ada_learn has not run");
+    if (!a->ctx.learned) return fail(RL_ERR_STATE, "rl_ada_learn has not run");
     *n = (int32_t)a->fid.size();
     const size_t m = std::min<size_t>(a->fid.size(), (size_t)std::max(0, cap));
     if (fid) std::copy(a->fid.begin(), a->fid.begin() + m, fid);
@@ -446,30 +393,17 @@ int rl_ada_get_model(const rl_ada *a, int32_t *fid, double *weight, int32_t cap,
     return RL_OK;
 }
 
-int rl_ada_scores(const rl_ada *a, double *train, double *valid)
-{
-    if (!a) return fail(RL_ERR_INVALID, "null handle");
-    if (!a->learned) return fail(RL_ERR_STATE, "rl_ada_learn has not run");
-    if (train) *train = a->train_score;
-    if (valid) *valid = a->valid_score;
-    return RL_OK;
-}
+int rl_ada_scores(const rl_ada *a, double *train, double *valid) { return lin_scores(lin_ctx(a), "rl_ada_", train, valid); }
 
-int rl_ada_trace(const rl_ada *a, rl_ada_trace_rec *out, int64_t cap, int64_t *n)
-{
-    if (!a || !n) return fail(RL_ERR_INVALID, "null argument");
-    *n = (int64_t)a->trace.size();
-    if (out) std::copy(a->trace.begin(), a->trace.begin() + std::max<int64_t>(0, std::min<int64_t>(cap, *n)), out);
-    return RL_OK;
-}
+int rl_ada_trace(const rl_ada *a, rl_ada_trace_rec *out, int64_t cap, int64_t *n) { return lin_trace(a ? &a->trace : nullptr, out, cap, n); }
 
 int rl_ada_debug_weak_table(const rl_ada *a, double *out, int64_t cap)
 {
     if (!a || !out) return fail(RL_ERR_INVALID, "null argument");
     if (!a->d_M) return fail(RL_ERR_STATE, "rl_ada_learn has not built the weak-ranker table");
-    const int64_t F = a->ca.F, Q = a->ca.tr.Q;
+    const int64_t F = a->ctx.F, Q = a->ctx.tr.Q;
     if (cap < F * Q) return fail(RL_ERR_INVALID, "weak-table buffer too small");
-    RL_HIP(hipSetDevice(a->p.device));
+    RL_HIP(hipSetDevice(a->ctx.device));
     std::vector<double> m((size_t)(F * Q));
     RL_HIP(hipMemcpy(m.data(), a->d_M, m.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int64_t q = 0; q < Q; q++)

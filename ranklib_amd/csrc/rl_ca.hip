@@ -12,10 +12,14 @@
 //                        Length classes: <= 16 documents (G = 16, 16 lists per block), <= 384 (one wavefront), <= 5000 (one block,
 //                        LDS), longer (one block, global scratch).
 //   k_ca_apply           cached = cached + wc * x, then optionally cached = cached / sum (updateCached / scaleCached :315-335)
-//   k_ca_recompute       cached = 0.0 + w[0] x0 + w[1] x1 + ...  (rank() with current_feature == -1, :207-213; also CoorAscent.eval)
+//   k_lin_score          cached = 0.0 + w[0] x0 + w[1] x1 + ...  (rank() with current_feature == -1, :207-213; also CoorAscent.eval): the
+//                        scoring kernel of all four linear rankers (rl_linear.inc)
 //
 // The host side runs CoorAscent.learn() (:67-202) literally: weights, the keep / restore decisions, the -reg penalty and the shuffle.
 // Built with -ffp-contract=off like the rest of the library: no fused multiply-adds, plain IEEE divisions.  There is no CPU fallback.
+//
+// The sets on the device, the scorer's tables, the stream and the entry points' common bodies are the ranking context's (LinCtx,
+// rl_linear.inc), which AdaRank, RankBoost and Linear Regression (included at the end of this file) use as well; k_ca_trials ranks for all.
 #include "rl_internal.h"
 
 #include <algorithm>
@@ -24,10 +28,10 @@
 #include <map>
 #include <memory>
 
+#include "rl_linear.inc"   // LinCtx and everything the four linear rankers share
+
 namespace rl {
 
-constexpr int kCaSteps = 64;          // trials per launch (a direction of more trials is evaluated in pieces of 64: same chain)
-constexpr int kCaTiny = 16, kCaWave = 384, kCaBlock = 5000;
 constexpr int kCaStage = 2048;        // doubles of LDS the last block stages the per-list metrics through (32 rows of kCaSteps trials)
 
 struct CaArgs {
@@ -222,88 +226,22 @@ __global__ void k_ca_apply(double *cache, const float *x, int64_t n, double wc, 
     cache[i] = v;
 }
 
-// column-major X (xc[f * n + i]) or rows (x[i * stride + fid[f]], fid >= stride reads 0)
-__global__ void k_ca_recompute(double *out, const float *xc, const float *rows, int64_t stride, const int32_t *fid, const double *w, int32_t F,
-                               int64_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0.0;
-    for (int f = 0; f < F; f++) {
-        float v;
-        if (xc) v = xc[(int64_t)f * n + i];
-        else v = (fid[f] >= 0 && fid[f] < stride) ? rows[i * stride + fid[f]] : 0.f;
-        s += w[f] * (double)v;
-    }
-    out[i] = s;
-}
+}  // namespace rl
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------------------------------------------
-struct CaBuf {                         // device allocations of one handle, freed together
-    std::vector<void *> ptrs;
-    template <class T> hipError_t alloc(T **p, size_t count)
-    {
-        hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    ~CaBuf() { for (void *p : ptrs) (void)hipFree(p); }
-};
-
-struct CaClass {
-    int32_t nq = 0; int32_t *d_qlist = nullptr;
-    int64_t nh = 0; int64_t *d_hoff = nullptr;        // longest class only
-};
-
-struct CaSet {
-    int64_t N = 0; int32_t Q = 0, maxq = 0;
-    std::vector<float> X;              // [N][F] as given
-    std::vector<float> labels; std::vector<int32_t> qoff, qkey; bool has_key = false;
-    std::vector<double> ext_ideal; std::vector<int32_t> ext_rd;
-    float *d_xc = nullptr, *d_labels = nullptr; int32_t *d_qoff = nullptr, *d_rd = nullptr;
-    double *d_ideal = nullptr, *d_cache = nullptr, *d_cache2 = nullptr;
-    CaClass cls[4];
-    double *d_hsc = nullptr; int32_t *d_hrel = nullptr; int32_t hchunks = 0;
-};
-
-}  // namespace rl
 
 using namespace rl;
 
 struct rl_ca {
     rl_ca_params p;
-    int32_t F = 0;
-    bool has_train = false, has_valid = false, learned = false, uploaded = false;
-    CaSet tr, va;
-    double err_max = 16.0;
-    hipStream_t stream = nullptr;
-    CaBuf buf;
-    double *d_disc = nullptr, *d_m = nullptr, *d_sums = nullptr, *d_w = nullptr; uint32_t *d_done = nullptr;
-    double *h_sums = nullptr;
-    std::vector<double> weight; double train_score = 0, valid_score = 0;
+    LinCtx ctx;
+    std::vector<double> weight;
     std::vector<rl_ca_trace_rec> trace;
-    ~rl_ca()
-    {
-        if (h_sums) (void)hipHostFree(h_sums);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace rl {
-
-static double ca_discount(int i) { return 1.0 / (std::log((double)(i + 2)) / std::log(2.0)); }   // DCGScorer.java:26
-
-static double ca_ideal_dcg(const float *labels, int n, int topk, const std::vector<double> &disc)
-{   // NDCGScorer.getIdealDCG (:167-174)
-    std::vector<int> rel(n);
-    for (int i = 0; i < n; i++) rel[i] = (int)labels[i];
-    std::sort(rel.begin(), rel.end(), [](int a, int b) { return a > b; });
-    double dcg = 0;
-    for (int i = 0; i < topk; i++) dcg += (double)(int32_t)(((uint32_t)1 << (rel[i] & 31)) - 1u) * disc[i];
-    return dcg;
-}
 
 // java.util.Random (the javadoc's LCG) and Collections.shuffle (java/util/Collections.java: for i = size; i > 1; i--: swap(i-1, nextInt(i)))
 struct JavaRandom {
@@ -324,144 +262,16 @@ struct JavaRandom {
     }
 };
 
-static int ca_check_set(const float *X, int64_t n, int32_t F, const float *labels, const int32_t *qoff, int32_t Q)
-{
-    if (!X || !labels || !qoff) return fail(RL_ERR_INVALID, "null data pointer");
-    if (n <= 0 || Q <= 0 || F <= 0) return fail(RL_ERR_INVALID, "There are no training samples / features");
-    if (n >= (int64_t)2147483647 - 4096) return fail(RL_ERR_UNSUPPORTED, "more than 2^31 documents per GPU");
-    if (qoff[0] != 0 || (int64_t)qoff[Q] != n) return fail(RL_ERR_INVALID, "qoff must start at 0 and end at n_docs");
-    for (int32_t q = 0; q < Q; q++)
-        if (qoff[q + 1] <= qoff[q]) return fail(RL_ERR_INVALID, "qoff must be strictly increasing (empty ranked list)");
-    for (int64_t i = 0; i < n; i++) {
-        if (!(labels[i] >= 0)) return fail(RL_ERR_INVALID, "Relevance label cannot be negative. System will now exit.");
-        if (labels[i] >= 16777216.f) return fail(RL_ERR_UNSUPPORTED, "relevance label of 2^24 or more");
-    }
-    for (int64_t i = 0; i < n * F; i++) {
-        if (std::isnan(X[i])) return fail(RL_ERR_INVALID, "NaN in X (a missing feature must be passed as 0)");
-        if (std::isinf(X[i])) return fail(RL_ERR_UNSUPPORTED, "+-Infinity feature value: the Java's cached scores turn NaN (0 * Infinity), not reproduced (DESIGN.md 7)");
-    }
-    return RL_OK;
-}
-
-static void ca_store(CaSet &d, const float *X, int64_t n, int32_t F, const float *labels, const int32_t *qoff, int32_t Q, const int32_t *qkey)
-{
-    d.N = n; d.Q = Q;
-    d.X.assign(X, X + n * F);
-    d.labels.assign(labels, labels + n);
-    d.qoff.assign(qoff, qoff + Q + 1);
-    d.has_key = qkey != nullptr;
-    if (qkey) d.qkey.assign(qkey, qkey + Q); else d.qkey.clear();
-    d.maxq = 0;
-    for (int32_t q = 0; q < Q; q++) d.maxq = std::max(d.maxq, qoff[q + 1] - qoff[q]);
-    d.ext_ideal.clear(); d.ext_rd.clear();
-}
-
-static int ca_upload(rl_ca *c, CaSet &d, const std::vector<double> &ideal)
-{
-    const int64_t N = d.N; const int32_t F = c->F;
-    std::vector<float> xc((size_t)N * F);
-    for (int64_t i = 0; i < N; i++)
-        for (int32_t f = 0; f < F; f++) xc[(size_t)f * N + i] = d.X[(size_t)i * F + f];
-    std::vector<float>().swap(d.X);                  // the rows are not needed on the host any more
-    RL_HIP(c->buf.alloc(&d.d_xc, xc.size()));
-    RL_HIP(hipMemcpy(d.d_xc, xc.data(), xc.size() * sizeof(float), hipMemcpyHostToDevice));
-    RL_HIP(c->buf.alloc(&d.d_labels, (size_t)N));
-    RL_HIP(hipMemcpy(d.d_labels, d.labels.data(), N * sizeof(float), hipMemcpyHostToDevice));
-    RL_HIP(c->buf.alloc(&d.d_qoff, (size_t)d.Q + 1));
-    RL_HIP(hipMemcpy(d.d_qoff, d.qoff.data(), ((size_t)d.Q + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    RL_HIP(c->buf.alloc(&d.d_ideal, (size_t)d.Q));
-    RL_HIP(hipMemcpy(d.d_ideal, ideal.data(), d.Q * sizeof(double), hipMemcpyHostToDevice));
-    if (!d.ext_rd.empty()) {
-        RL_HIP(c->buf.alloc(&d.d_rd, (size_t)d.Q));
-        RL_HIP(hipMemcpy(d.d_rd, d.ext_rd.data(), d.Q * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    RL_HIP(c->buf.alloc(&d.d_cache, (size_t)N));
-    RL_HIP(c->buf.alloc(&d.d_cache2, (size_t)N));
-    std::vector<int32_t> lists[4];
-    std::vector<int64_t> hoff;
-    int64_t nh = 0;
-    for (int32_t q = 0; q < d.Q; q++) {
-        const int n = d.qoff[q + 1] - d.qoff[q];
-        const int k = n <= kCaTiny ? 0 : n <= kCaWave ? 1 : n <= kCaBlock ? 2 : 3;
-        lists[k].push_back(q);
-        if (k == 3) { hoff.push_back(nh); nh += n; }
-    }
-    for (int k = 0; k < 4; k++) {
-        CaClass &cl = d.cls[k];
-        cl.nq = (int32_t)lists[k].size();
-        if (!cl.nq) continue;
-        RL_HIP(c->buf.alloc(&cl.d_qlist, lists[k].size()));
-        RL_HIP(hipMemcpy(cl.d_qlist, lists[k].data(), lists[k].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    if (d.cls[3].nq) {
-        CaClass &cl = d.cls[3];
-        cl.nh = nh;
-        RL_HIP(c->buf.alloc(&cl.d_hoff, hoff.size()));
-        RL_HIP(hipMemcpy(cl.d_hoff, hoff.data(), hoff.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        d.hchunks = std::max(1, std::min(kCaSteps, 1024 / cl.nq));     // chunks of the trials of one launch (sizes the scratch)
-        RL_HIP(c->buf.alloc(&d.d_hsc, (size_t)d.hchunks * nh));
-        RL_HIP(c->buf.alloc(&d.d_hrel, (size_t)d.hchunks * nh));
-    }
-    return RL_OK;
-}
-
-// ideal DCGs with the qid-keyed cache quirk (NDCGScorer.java:114-122,134-143), -qrel entries first: as rl_trainer.hip builds them
-static int ca_prepare(rl_ca *c)
-{
-    const int maxq = std::max(c->tr.maxq, c->has_valid ? c->va.maxq : 0);
-    std::vector<double> disc((size_t)maxq + 2);
-    for (size_t i = 0; i < disc.size(); i++) disc[i] = ca_discount((int)i);
-    RL_HIP(c->buf.alloc(&c->d_disc, disc.size()));
-    RL_HIP(hipMemcpy(c->d_disc, disc.data(), disc.size() * sizeof(double), hipMemcpyHostToDevice));
-    std::map<int64_t, double> cache;
-    auto preload = [&](CaSet &d, int64_t anon_base) {
-        for (int q = 0; q < d.Q && !d.ext_ideal.empty(); q++)
-            if (d.ext_ideal[q] == d.ext_ideal[q]) cache[d.has_key ? (int64_t)d.qkey[q] : anon_base + q] = d.ext_ideal[q];
-    };
-    preload(c->tr, (int64_t)1 << 40);
-    if (c->has_valid) preload(c->va, (int64_t)1 << 41);
-    const std::map<int64_t, double> external = cache;
-    auto run = [&](CaSet &d, int64_t anon_base, std::vector<double> &cached) {
-        cached.resize(d.Q);
-        for (int q = 0; q < d.Q; q++) {
-            const int n = d.qoff[q + 1] - d.qoff[q];
-            const int size = (c->p.metric_k > n || c->p.metric_k <= 0) ? n : c->p.metric_k;
-            const int64_t key = d.has_key ? (int64_t)d.qkey[q] : anon_base + q;
-            { auto pre = external.find(key); if (pre != external.end()) { cached[q] = pre->second; continue; } }
-            auto it = cache.find(key);
-            if (it == cache.end()) it = cache.emplace(key, ca_ideal_dcg(d.labels.data() + d.qoff[q], n, size, disc)).first;
-            cached[q] = it->second;
-        }
-    };
-    std::vector<double> ideal;
-    run(c->tr, (int64_t)1 << 40, ideal);
-    int rc = ca_upload(c, c->tr, ideal);
-    if (rc) return rc;
-    if (c->has_valid) {
-        run(c->va, (int64_t)1 << 41, ideal);
-        rc = ca_upload(c, c->va, ideal);
-        if (rc) return rc;
-    }
-    RL_HIP(c->buf.alloc(&c->d_m, (size_t)std::max(c->tr.Q, c->has_valid ? c->va.Q : 0) * kCaSteps));
-    RL_HIP(c->buf.alloc(&c->d_sums, (size_t)kCaSteps));
-    RL_HIP(c->buf.alloc(&c->d_done, 1));
-    RL_HIP(hipMemset(c->d_done, 0, sizeof(uint32_t)));
-    RL_HIP(c->buf.alloc(&c->d_w, (size_t)c->F));
-    RL_HIP(hipHostMalloc((void **)&c->h_sums, kCaSteps * sizeof(double), hipHostMallocDefault));
-    c->uploaded = true;
-    return RL_OK;
-}
-
 // Evaluates trials [0, T) of one direction on set d (steps[t] = the weight change of trial t; first = 0: T == 1, the cache as it is) and
 // copies sums[0..T) (= scorer.score(rank(samples)) after each trial) into out.  first = 1 leaves the chain's final value in d.d_cache.
-static int ca_trials(rl_ca *c, CaSet &d, const float *xcol, const double *steps, int T, int first, double *out)
+static int ca_trials(LinCtx *c, CaSet &d, const float *xcol, const double *steps, int T, int first, double *out)
 {
     CaArgs a;
     memset(&a, 0, sizeof(a));
     a.cache = d.d_cache; a.cache_out = d.d_cache2; a.x = xcol;
     a.labels = d.d_labels; a.qoff = d.d_qoff; a.ideal = d.d_ideal; a.rd_ext = d.d_rd; a.disc = c->d_disc;
     a.m = c->d_m; a.sums = c->d_sums; a.done = c->d_done;
-    a.Q = d.Q; a.T = T; a.first = first; a.metric = c->p.metric; a.k = c->p.metric_k; a.err_max = c->err_max;
+    a.Q = d.Q; a.T = T; a.first = first; a.metric = c->metric; a.k = c->metric_k; a.err_max = c->err_max;
     for (int t = 0; t < T; t++) a.steps[t] = steps ? steps[t] : 0.0;
     static const int G[4] = {kCaTiny, kWave, kThreads, kThreads};
     // a group per (list, chunk of trials): few lists get the trial dimension spread over more groups (~2048 wavefronts of work)
@@ -498,7 +308,7 @@ static int ca_trials(rl_ca *c, CaSet &d, const float *xcol, const double *steps,
 }
 
 // all trials of one direction (in launches of up to kCaSteps trials: each continues the previous one's chain)
-static int ca_direction(rl_ca *c, int f, const std::vector<double> &steps, std::vector<double> &scores)
+static int ca_direction(LinCtx *c, int f, const std::vector<double> &steps, std::vector<double> &scores)
 {
     const int T = (int)steps.size();
     scores.resize(T);
@@ -511,7 +321,7 @@ static int ca_direction(rl_ca *c, int f, const std::vector<double> &steps, std::
     return RL_OK;
 }
 
-static int ca_apply(rl_ca *c, int f, double wc, bool scale, double sum)
+static int ca_apply(LinCtx *c, int f, double wc, bool scale, double sum)
 {
     CaSet &d = c->tr;
     const int64_t n = d.N;
@@ -519,16 +329,6 @@ static int ca_apply(rl_ca *c, int f, double wc, bool scale, double sum)
                        scale ? 1 : 0, sum);
     RL_HIP(hipGetLastError());
     return RL_OK;
-}
-
-// scorer.score(rank(set)) with current_feature == -1: the cache recomputed from the weights
-static int ca_score_weights(rl_ca *c, CaSet &d, const std::vector<double> &w, double *score)
-{
-    RL_HIP(hipMemcpyAsync(c->d_w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_ca_recompute, dim3((unsigned)((d.N + 255) / 256)), dim3(256), 0, c->stream, d.d_cache, d.d_xc, (const float *)nullptr,
-                       (int64_t)0, (const int32_t *)nullptr, c->d_w, c->F, d.N);
-    RL_HIP(hipGetLastError());
-    return ca_trials(c, d, nullptr, nullptr, 1, 0, score);
 }
 
 static double ca_distance(const std::vector<double> &w1, const std::vector<double> &w2)
@@ -549,15 +349,17 @@ static double ca_normalize(std::vector<double> &w)
     return sum;
 }
 
-static int ca_learn(rl_ca *c)
+static int ca_learn(rl_ca *h)
 {
-    const rl_ca_params &P = c->p;
+    LinCtx *c = &h->ctx;
+    const rl_ca_params &P = h->p;
     const int F = c->F;
     auto rec = [&](int kind, int r, int f, int dir, int j, int imp, double w, double s) {
         rl_ca_trace_rec t; t.kind = kind; t.restart = r; t.feature = f; t.dir = dir; t.j = j; t.improved = imp; t.weight = w; t.score = s;
-        c->trace.push_back(t);
+        h->trace.push_back(t);
     };
-    c->trace.clear();
+    auto model = [&](const std::vector<double> &w) { LinModel m; m.w = w.data(); m.nt = m.nw = F; return m; };      // column t, weight w[t]
+    h->trace.clear();
     std::vector<double> weight((size_t)F), regVector((size_t)F, 1.0 / F);      // init() :62-63, copied at :68-69
     std::vector<double> bestModel; double bestModelScore = 0.0;
     const int sign[3] = {1, -1, 0};
@@ -567,7 +369,7 @@ static int ca_learn(rl_ca *c)
         int consecutive_fails = 0;
         for (int i = 0; i < F; i++) weight[i] = (double)(1.0f / (float)F);       // :87-89, a float division
         double startScore;
-        int rc = ca_score_weights(c, c->tr, weight, &startScore);
+        int rc = lin_score_model(c, c->tr, model(weight), &startScore);
         if (rc) return rc;
         rec(RL_CA_RESTART, r, -1, 0, 0, 0, 0.0, startScore);
         double bestScore = startScore;
@@ -630,19 +432,14 @@ static int ca_learn(rl_ca *c)
             if (bestScore - startScore < P.tolerance) break;
         }
         if (c->has_valid) {
-            int rc2 = ca_score_weights(c, c->va, weight, &bestScore);
+            int rc2 = lin_score_model(c, c->va, model(weight), &bestScore);
             if (rc2) return rc2;
             rec(RL_CA_VALID, r, -1, 0, 0, 0, 0.0, bestScore);
         }
         if (bestModel.empty() || bestScore > bestModelScore) { bestModelScore = bestScore; bestModel = bestWeight; }
     }
-    c->weight = bestModel;
-    int rc = ca_score_weights(c, c->tr, c->weight, &c->train_score);
-    if (rc) return rc;
-    c->valid_score = 0;
-    if (c->has_valid && (rc = ca_score_weights(c, c->va, c->weight, &c->valid_score))) return rc;
-    c->learned = true;
-    return RL_OK;
+    h->weight = bestModel;
+    return lin_finish(c, model(h->weight));
 }
 
 }  // namespace rl
@@ -661,144 +458,68 @@ int rl_ca_create(const rl_ca_params *p, rl_ca **out)
 {
     if (!p || !out) return fail(RL_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (p->metric < RL_METRIC_NDCG || p->metric > RL_METRIC_RR)
-        return fail(RL_ERR_UNSUPPORTED, "Coordinate Ascent train metric must be NDCG, DCG, MAP, ERR, P or RR (BEST is not built for training)");
     if (p->n_restart < 1) return fail(RL_ERR_INVALID, "n_restart must be >= 1 (the Java ends in a NullPointerException)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (p->device < 0 || p->device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    RL_HIP(hipSetDevice(p->device));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, p->device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(RL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", librlhip is built for gfx950 only");
     std::unique_ptr<rl_ca> c(new rl_ca());
     c->p = *p;
-    if (!(p->err_max > 0.0) || !std::isfinite(p->err_max)) return fail(RL_ERR_INVALID, "err_max (ERRScorer.MAX) must be positive and finite");
-    c->err_max = p->err_max;
-    RL_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    int rc = lin_create(&c->ctx, "Coordinate Ascent", p->metric, p->metric_k, p->device, p->err_max);
+    if (rc) return rc;
     *out = c.release();
     return RL_OK;
 }
 
-void rl_ca_destroy(rl_ca *c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->p.device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    delete c;
-}
+void rl_ca_destroy(rl_ca *c) { lin_destroy(c); }
 
 int rl_ca_set_train(rl_ca *c, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
                     int32_t n_queries, const int32_t *qkey)
 {
-    if (!c) return fail(RL_ERR_INVALID, "null handle");
-    if (c->uploaded) return fail(RL_ERR_STATE, "rl_ca_set_train after rl_ca_learn");
-    int rc = ca_check_set(X, n_docs, n_features, labels, qoff, n_queries);
-    if (rc) return rc;
-    c->F = n_features;
-    ca_store(c->tr, X, n_docs, n_features, labels, qoff, n_queries, qkey);
-    c->has_train = true;
-    return RL_OK;
+    return lin_set_train(lin_ctx(c), "rl_ca_", X, n_docs, n_features, labels, qoff, n_queries, qkey);
 }
 
 int rl_ca_set_validation(rl_ca *c, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
                          const int32_t *qkey)
 {
-    if (!c) return fail(RL_ERR_INVALID, "null handle");
-    if (!c->has_train) return fail(RL_ERR_STATE, "set the training data first");
-    if (c->uploaded) return fail(RL_ERR_STATE, "rl_ca_set_validation after rl_ca_learn");
-    int rc = ca_check_set(X, n_docs, c->F, labels, qoff, n_queries);
-    if (rc) return rc;
-    ca_store(c->va, X, n_docs, c->F, labels, qoff, n_queries, qkey);
-    c->has_valid = true;
-    return RL_OK;
+    return lin_set_validation(lin_ctx(c), "rl_ca_", X, n_docs, labels, qoff, n_queries, qkey);
 }
 
 int rl_ca_set_external_judgments(rl_ca *c, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count)
 {
-    if (!c) return fail(RL_ERR_INVALID, "null handle");
-    if (c->uploaded) return fail(RL_ERR_STATE, "rl_ca_set_external_judgments after rl_ca_learn");
-    if (validation ? !c->has_valid : !c->has_train) return fail(RL_ERR_STATE, "set the data first");
-    CaSet &d = validation ? c->va : c->tr;
-    d.ext_ideal.clear(); d.ext_rd.clear();
-    if (ideal_dcg) d.ext_ideal.assign(ideal_dcg, ideal_dcg + d.Q);
-    if (rel_doc_count) {
-        for (int q = 0; q < d.Q; q++) if (rel_doc_count[q] < 0) return fail(RL_ERR_INVALID, "negative relevant-document count");
-        d.ext_rd.assign(rel_doc_count, rel_doc_count + d.Q);
-    }
-    return RL_OK;
+    return lin_set_external_judgments(lin_ctx(c), "rl_ca_", validation, ideal_dcg, rel_doc_count);
 }
 
 int rl_ca_learn(rl_ca *c)
 {
-    if (!c) return fail(RL_ERR_INVALID, "null handle");
-    if (!c->has_train) return fail(RL_ERR_STATE, "set the training data first");
-    if (c->uploaded) return fail(RL_ERR_STATE, "rl_ca_learn runs once per handle");
-    RL_HIP(hipSetDevice(c->p.device));
-    int rc = ca_prepare(c);
+    int rc = lin_begin_learn(lin_ctx(c), "rl_ca_");
     if (rc) return rc;
+    if ((rc = ca_prepare(&c->ctx))) return rc;
     return ca_learn(c);
 }
 
 int rl_ca_get_weights(const rl_ca *c, double *w, int32_t cap)
 {
     if (!c || !w) return fail(RL_ERR_INVALID, "null argument");
-    if (!c->learned) return fail(RL_ERR_STATE, "rl_ca_learn has not run");
-    if (cap < c->F) return fail(RL_ERR_INVALID, "weight buffer too small");
+    if (!c->ctx.learned) return fail(RL_ERR_STATE, "rl_ca_learn has not run");
+    if (cap < c->ctx.F) return fail(RL_ERR_INVALID, "weight buffer too small");
     std::copy(c->weight.begin(), c->weight.end(), w);
     return RL_OK;
 }
 
-int rl_ca_scores(const rl_ca *c, double *train, double *valid)
-{
-    if (!c) return fail(RL_ERR_INVALID, "null handle");
-    if (!c->learned) return fail(RL_ERR_STATE, "rl_ca_learn has not run");
-    if (train) *train = c->train_score;
-    if (valid) *valid = c->valid_score;
-    return RL_OK;
-}
+int rl_ca_scores(const rl_ca *c, double *train, double *valid) { return lin_scores(lin_ctx(c), "rl_ca_", train, valid); }
 
-int rl_ca_trace(const rl_ca *c, rl_ca_trace_rec *out, int64_t cap, int64_t *n)
-{
-    if (!c || !n) return fail(RL_ERR_INVALID, "null argument");
-    *n = (int64_t)c->trace.size();
-    if (out) std::copy(c->trace.begin(), c->trace.begin() + std::min<int64_t>(cap, *n), out);
-    return RL_OK;
-}
+int rl_ca_trace(const rl_ca *c, rl_ca_trace_rec *out, int64_t cap, int64_t *n) { return lin_trace(c ? &c->trace : nullptr, out, cap, n); }
 
 int rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weights, int32_t n_weights, const float *X, int64_t n_docs,
                   int32_t row_stride, double *out)
 {
     if (!feature_ids || !weights || !out || (n_docs > 0 && !X)) return fail(RL_ERR_INVALID, "null argument");
     if (n_weights < 0 || n_docs < 0 || row_stride < 1) return fail(RL_ERR_INVALID, "bad sizes");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    if (n_docs == 0) return RL_OK;
-    RL_HIP(hipSetDevice(device));
-    CaBuf buf;
-    float *dX = nullptr; int32_t *dF = nullptr; double *dW = nullptr, *dO = nullptr;
-    RL_HIP(buf.alloc(&dX, (size_t)n_docs * row_stride));
-    RL_HIP(buf.alloc(&dF, (size_t)n_weights));
-    RL_HIP(buf.alloc(&dW, (size_t)n_weights));
-    RL_HIP(buf.alloc(&dO, (size_t)n_docs));
-    RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
-    if (n_weights) {
-        RL_HIP(hipMemcpy(dF, feature_ids, n_weights * sizeof(int32_t), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(dW, weights, n_weights * sizeof(double), hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_ca_recompute, dim3((unsigned)((n_docs + 255) / 256)), dim3(256), 0, 0, dO, (const float *)nullptr, dX, (int64_t)row_stride,
-                       dF, dW, n_weights, n_docs);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipMemcpy(out, dO, n_docs * sizeof(double), hipMemcpyDeviceToHost));
-    return RL_OK;
+    LinModel m;
+    m.col = feature_ids; m.w = weights; m.nt = m.nw = n_weights;
+    return lin_predict(device, m, X, n_docs, row_stride, out);
 }
 
 }  // extern "C"
 
-#include "rl_ada.inc"      // AdaRank (-ranker 3): the same translation unit, so its kernels share ca_metric and k_ca_trials
-#include "rl_rb.inc"       // RankBoost (-ranker 2): the device sets, ca_metric and the ranking kernel again
-#include "rl_lr.inc"       // Linear Regression (-ranker 9): the same
+// The other three linear rankers: the same translation unit, so each handle's LinCtx is ranked by k_ca_trials and scored by ca_metric
+#include "rl_ada.inc"      // AdaRank (-ranker 3): k_ada_weak shares ca_metric and the sets' length classes
+#include "rl_rb.inc"       // RankBoost (-ranker 2): its training lists sorted into getCorrectRanking() order in the context's set
+#include "rl_lr.inc"       // Linear Regression (-ranker 9): k_lr_gram reads the context's column-major training set

@@ -1,5 +1,6 @@
-// rl_lr.inc -- Linear Regression (-ranker 9, learning/LinearRegRank.java) on gfx950; included at the end of rl_ca.hip, whose device sets,
-// scorer (ca_metric) and ranking kernel (k_ca_trials with T = 1 on the cache as it is) it reuses.
+// rl_lr.inc -- Linear Regression (-ranker 9, learning/LinearRegRank.java) on gfx950; included at the end of rl_ca.hip.  The handle holds a
+// ranking context (LinCtx, rl_linear.inc: the device sets, the stream, the common entry-point bodies) and ranks with rl_ca.hip's scorer
+// (ca_metric) and ranking kernel (k_ca_trials with T = 1 on the cache as it is).
 //
 // learn() (:44-100) is one accumulation and one solve.  With t = (x_1, ..., x_{nVar-1}, 1) per document, in (list, document) order:
 //     xTx[j][k] += t_j * t_k   the product of two widened floats, exact in f64 (24 + 24 significand bits)
@@ -16,8 +17,8 @@
 //                   The add is fma(t_j, t_k, acc): the product is exact, so the one rounding of the fma IS the rounding of the Java's
 //                   multiply-then-add.  It is the only explicit fma in the library (-ffp-contract=off stays); v_mul_f64 + v_add_f64
 //                   would double the f64 issue slots of the chain for the same bits.
-//   k_lr_score      one document per thread: score = w[last], then += w[i] * x[features[i]] (LinearRegRank.eval :103-109: bias first)
 //
+// Scoring is k_lin_score with the bias: score = w[last], then += w[i] * x[features[i]] (LinearRegRank.eval :103-109: bias first).
 // The ridge term, solve() (:188-239: Gaussian elimination without pivoting) and the refusals are host code, built with the same flags.
 
 #include <chrono>
@@ -195,37 +196,16 @@ __global__ __launch_bounds__(kThreads) void k_lr_gram(const float *xc, const flo
     }
 }
 
-// column-major X (xc[col * n + i]) or rows (x[i * stride + col]); col < 0 or (rows) col >= stride reads 0.  w has nw entries, w[nw - 1] is
-// where eval starts from; nf <= nw
-__global__ void k_lr_score(double *out, const float *xc, const float *rows, int64_t stride, int64_t n, const int32_t *col, int32_t nf,
-                           const double *w, int32_t nw)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = w[nw - 1];
-    for (int t = 0; t < nf; t++) {
-        const int32_t c = col[t];
-        float v = 0.f;
-        if (c >= 0) {
-            if (xc) v = xc[(int64_t)c * n + i];
-            else if (c < stride) v = rows[i * stride + c];
-        }
-        s += w[t] * (double)v;
-    }
-    out[i] = s;
-}
-
 }  // namespace rl
 
 struct rl_lr {
     rl_lr_params p;
-    rl_ca ca;                          // the data sets on the device, the scorer's tables, the ranking kernel's buffers and the stream
-    bool learned = false, gram_done = false;
+    LinCtx ctx;
+    bool gram_done = false;
     int32_t n_var = 0;                 // the Java's nVar (0: the training set's column count)
     bool has_cols = false;
     std::vector<int32_t> cols;         // eval's columns (features[i] - 1; -1 reads 0)
     std::vector<double> xtx, xty, weight;
-    double train_score = 0, valid_score = 0;
     double gram_ms = 0, solve_ms = 0, score_ms = 0;
     int32_t rb = 0;
 };
@@ -294,7 +274,7 @@ static int lr_solve(std::vector<double> &a, std::vector<double> &b, int n, std::
 
 static int lr_gram(rl_lr *R)
 {
-    rl_ca *c = &R->ca;
+    LinCtx *c = &R->ctx;
     CaSet &d = c->tr;
     const int C = R->n_var;
     const int rb = R->rb = lr_pick_rb(C);
@@ -324,20 +304,10 @@ static int lr_gram(rl_lr *R)
     return RL_OK;
 }
 
-// scorer.score(rank(d)) of the weights: the cache filled by eval
-static int lr_score_set(rl_lr *R, CaSet &d, const int32_t *dcol, const double *dw, double *score)
-{
-    rl_ca *c = &R->ca;
-    hipLaunchKernelGGL(k_lr_score, dim3((unsigned)((d.N + 255) / 256)), dim3(256), 0, c->stream, d.d_cache, (const float *)d.d_xc,
-                       (const float *)nullptr, (int64_t)0, d.N, dcol, (int32_t)R->cols.size(), dw, (int32_t)R->weight.size());
-    RL_HIP(hipGetLastError());
-    return ca_trials(c, d, nullptr, nullptr, 1, 0, score);
-}
-
 // LinearRegRank.learn() :44-100
 static int lr_learn(rl_lr *R)
 {
-    rl_ca *c = &R->ca;
+    LinCtx *c = &R->ctx;
     const int W = c->F;
     if (R->n_var == 0) R->n_var = W;
     const int n = R->n_var;
@@ -356,16 +326,10 @@ static int lr_learn(rl_lr *R)
     if ((rc = lr_solve(a, b, n, R->weight))) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     R->solve_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    int32_t *dcol = nullptr; double *dw = nullptr;
-    RL_HIP(c->buf.alloc(&dcol, R->cols.size()));
-    RL_HIP(c->buf.alloc(&dw, R->weight.size()));
-    if (!R->cols.empty()) RL_HIP(hipMemcpy(dcol, R->cols.data(), R->cols.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(dw, R->weight.data(), R->weight.size() * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = lr_score_set(R, c->tr, dcol, dw, &R->train_score))) return rc;
-    R->valid_score = 0;
-    if (c->has_valid && (rc = lr_score_set(R, c->va, dcol, dw, &R->valid_score))) return rc;
+    LinModel m;                                               // eval :103-109: the bias w[n - 1], then the columns
+    m.col = R->cols.data(); m.nt = (int32_t)R->cols.size(); m.w = R->weight.data(); m.nw = (int32_t)R->weight.size(); m.bias = true;
+    if ((rc = lin_finish(c, m))) return rc;
     R->score_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    R->learned = true;
     return RL_OK;
 }
 
@@ -383,61 +347,43 @@ int rl_lr_create(const rl_lr_params *p, rl_lr **out)
 {
     if (!p || !out) return fail(RL_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (p->metric < RL_METRIC_NDCG || p->metric > RL_METRIC_RR)
-        return fail(RL_ERR_UNSUPPORTED, "Linear Regression train metric must be NDCG, DCG, MAP, ERR, P or RR (BEST is not built for training)");
     if (!std::isfinite(p->lambda)) return fail(RL_ERR_INVALID, "lambda (-L2) must be finite");
-    rl_ca_params cp;
-    rl_ca_params_default(&cp);
-    cp.metric = p->metric; cp.metric_k = p->metric_k; cp.device = p->device; cp.err_max = p->err_max;
-    rl_ca *c = nullptr;
-    int rc = rl_ca_create(&cp, &c);                           // device checks, the stream
-    if (rc) return rc;
     std::unique_ptr<rl_lr> R(new rl_lr());
     R->p = *p;
-    R->ca.p = c->p; R->ca.err_max = c->err_max;
-    std::swap(R->ca.stream, c->stream);
-    rl_ca_destroy(c);
+    int rc = lin_create(&R->ctx, "Linear Regression", p->metric, p->metric_k, p->device, p->err_max);
+    if (rc) return rc;
     *out = R.release();
     return RL_OK;
 }
 
-void rl_lr_destroy(rl_lr *r)
-{
-    if (!r) return;
-    (void)hipSetDevice(r->p.device);
-    if (r->ca.stream) (void)hipStreamSynchronize(r->ca.stream);
-    delete r;
-}
+void rl_lr_destroy(rl_lr *r) { lin_destroy(r); }
 
 int rl_lr_set_train(rl_lr *r, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
                     int32_t n_queries, const int32_t *qkey)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_train(&r->ca, X, n_docs, n_features, labels, qoff, n_queries, qkey);
+    return lin_set_train(lin_ctx(r), "rl_lr_", X, n_docs, n_features, labels, qoff, n_queries, qkey);
 }
 
 int rl_lr_set_validation(rl_lr *r, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
                          const int32_t *qkey)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_validation(&r->ca, X, n_docs, labels, qoff, n_queries, qkey);
+    return lin_set_validation(lin_ctx(r), "rl_lr_", X, n_docs, labels, qoff, n_queries, qkey);
 }
 
 int rl_lr_set_external_judgments(rl_lr *r, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_external_judgments(&r->ca, validation, ideal_dcg, rel_doc_count);
+    return lin_set_external_judgments(lin_ctx(r), "rl_lr_", validation, ideal_dcg, rel_doc_count);
 }
 
 int rl_lr_set_features(rl_lr *r, int32_t n_var, const int32_t *eval_cols, int32_t n_eval)
 {
     if (!r) return fail(RL_ERR_INVALID, "null handle");
-    if (!r->ca.has_train) return fail(RL_ERR_STATE, "set the training data first");
-    if (r->ca.uploaded) return fail(RL_ERR_STATE, "rl_lr_set_features after rl_lr_learn");
-    if (n_var < 0 || n_var > r->ca.F) return fail(RL_ERR_INVALID, "n_var must be 0 (all columns) or 1 .. n_features");
+    if (!r->ctx.has_train) return fail(RL_ERR_STATE, "set the training data first");
+    if (r->ctx.uploaded) return fail(RL_ERR_STATE, "rl_lr_set_features after rl_lr_learn");
+    if (n_var < 0 || n_var > r->ctx.F) return fail(RL_ERR_INVALID, "n_var must be 0 (all columns) or 1 .. n_features");
     if (n_eval < 0 || (n_eval > 0 && !eval_cols)) return fail(RL_ERR_INVALID, "bad eval columns");
     for (int32_t i = 0; i < n_eval; i++)
-        if (eval_cols[i] < -1 || eval_cols[i] >= r->ca.F) return fail(RL_ERR_INVALID, "eval column out of range (-1 .. n_features - 1)");
+        if (eval_cols[i] < -1 || eval_cols[i] >= r->ctx.F) return fail(RL_ERR_INVALID, "eval column out of range (-1 .. n_features - 1)");
     r->n_var = n_var;
     r->has_cols = eval_cols != nullptr;                      // NULL: columns 0 .. n_features - 1
     r->cols.clear();
@@ -447,30 +393,21 @@ int rl_lr_set_features(rl_lr *r, int32_t n_var, const int32_t *eval_cols, int32_
 
 int rl_lr_learn(rl_lr *r)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    if (!r->ca.has_train) return fail(RL_ERR_STATE, "set the training data first");
-    if (r->ca.uploaded) return fail(RL_ERR_STATE, "rl_lr_learn runs once per handle");
-    RL_HIP(hipSetDevice(r->p.device));
+    int rc = lin_begin_learn(lin_ctx(r), "rl_lr_");
+    if (rc) return rc;
     return lr_learn(r);
 }
 
 int rl_lr_get_weights(const rl_lr *r, double *w, int32_t cap, int32_t *n)
 {
     if (!r || !n) return fail(RL_ERR_INVALID, "null argument");
-    if (!r->learned) return fail(RL_ERR_STATE, "rl_lr_learn has not run");
+    if (!r->ctx.learned) return fail(RL_ERR_STATE, "rl_lr_learn has not run");
     *n = (int32_t)r->weight.size();
     if (w) std::copy(r->weight.begin(), r->weight.begin() + std::min<size_t>(r->weight.size(), (size_t)std::max(0, cap)), w);
     return RL_OK;
 }
 
-int rl_lr_scores(const rl_lr *r, double *train, double *valid)
-{
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    if (!r->learned) return fail(RL_ERR_STATE, "rl_lr_learn has not run");
-    if (train) *train = r->train_score;
-    if (valid) *valid = r->valid_score;
-    return RL_OK;
-}
+int rl_lr_scores(const rl_lr *r, double *train, double *valid) { return lin_scores(lin_ctx(r), "rl_lr_", train, valid); }
 
 int rl_lr_debug_gram(const rl_lr *r, double *xtx, double *xty, int32_t cap, int32_t *n_var)
 {
@@ -504,26 +441,9 @@ int rl_lr_predict(int32_t device, const int32_t *feature_ids, int32_t n_features
         return fail(RL_ERR_UNSUPPORTED, "Linear Regression: " + std::to_string(n_features) + " features to score with, but only " +
                                         std::to_string(n_weights) + " weights; the Java ends in an ArrayIndexOutOfBoundsException in eval "
                                         "(DESIGN.md 11)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    if (n_docs == 0) return RL_OK;
-    RL_HIP(hipSetDevice(device));
-    CaBuf buf;
-    float *dX = nullptr; int32_t *dF = nullptr; double *dW = nullptr, *dO = nullptr;
-    RL_HIP(buf.alloc(&dX, (size_t)n_docs * row_stride));
-    RL_HIP(buf.alloc(&dF, (size_t)n_features));
-    RL_HIP(buf.alloc(&dW, (size_t)n_weights));
-    RL_HIP(buf.alloc(&dO, (size_t)n_docs));
-    RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
-    if (n_features) RL_HIP(hipMemcpy(dF, feature_ids, n_features * sizeof(int32_t), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(dW, weights, n_weights * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_lr_score, dim3((unsigned)((n_docs + 255) / 256)), dim3(256), 0, 0, dO, (const float *)nullptr, (const float *)dX,
-                       (int64_t)row_stride, n_docs, (const int32_t *)dF, n_features, (const double *)dW, n_weights);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipMemcpy(out, dO, n_docs * sizeof(double), hipMemcpyDeviceToHost));
-    return RL_OK;
+    LinModel m;
+    m.col = feature_ids; m.nt = n_features; m.w = weights; m.nw = n_weights; m.bias = true;
+    return lin_predict(device, m, X, n_docs, row_stride, out);
 }
 
 }  // extern "C"

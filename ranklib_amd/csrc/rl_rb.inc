@@ -1,5 +1,6 @@
-// rl_rb.inc -- RankBoost (-ranker 2, learning/boosting/RankBoost.java) on gfx950; included at the end of rl_ca.hip, whose device sets,
-// scorer (ca_metric) and ranking kernel (k_ca_trials with T = 1 on the cache as it is) it reuses.
+// rl_rb.inc -- RankBoost (-ranker 2, learning/boosting/RankBoost.java) on gfx950; included at the end of rl_ca.hip.  The handle holds a
+// ranking context (LinCtx, rl_linear.inc: the device sets, the stream, the common entry-point bodies) and ranks with rl_ca.hip's scorer
+// (ca_metric) and ranking kernel (k_ca_trials with T = 1 on the cache as it is).
 //
 // The Java keeps sweight[list][j][k] for every pair of a list.  Only crucial pairs (label_j > label_k) ever hold anything but +0.0, and
 // adding or subtracting +0.0 changes neither a potential nor Z_t, so the device stores the crucial pairs alone, in (list, j, k) order:
@@ -17,8 +18,8 @@
 //   k_rb_update      16 lanes per row: w = w * exp(alpha_t * (h(k) - h(j))), the factor one of exp(alpha_t), exp(-alpha_t), 1.0 (the host's)
 //   k_rb_zsum        ONE block: Z_t, the serial f64 sum over all pairs; tiles staged in LDS as in k_rb_cand
 //   k_rb_normalize   w = w / Z_t, an IEEE division
-//   k_rb_recompute   a model's scores from scratch: 0.0 + w[0] h_0(x) + w[1] h_1(x) + ... (RankBoost.eval :348-355)
 //
+// A model's scores from scratch, 0.0 + w[0] h_0(x) + w[1] h_1(x) + ... (RankBoost.eval :348-355), are k_lin_score's with thresholds.
 // log / exp are the host C library's, as in rl_ada.inc.
 
 #include <thread>
@@ -184,30 +185,12 @@ __global__ void k_rb_normalize(double *w, int64_t P, double z)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride) w[i] = w[i] / z;
 }
 
-// column-major X (xc[col * n + i]) or rows (x[i * stride + col], col >= stride reads 0)
-__global__ void k_rb_recompute(double *out, const float *xc, const float *rows, int64_t stride, int64_t n, const int32_t *col, const double *thr,
-                               const double *w, int32_t T)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0.0;
-    for (int t = 0; t < T; t++) {
-        float v;
-        if (xc) v = xc[(int64_t)col[t] * n + i];
-        else v = (col[t] >= 0 && col[t] < stride) ? rows[i * stride + col[t]] : 0.f;
-        s += w[t] * (double)(((double)v > thr[t]) ? 1 : 0);
-    }
-    out[i] = s;
-}
-
 }  // namespace rl
 
 struct rl_rb {
     rl_rb_params p;
-    rl_ca ca;                          // the data sets on the device, the scorer's tables, the ranking kernel's buffers and the stream
-    bool learned = false;
+    LinCtx ctx;
     std::vector<int32_t> fid; std::vector<double> thr, weight;
-    double train_score = 0, valid_score = 0;
     std::vector<rl_rb_trace_rec> trace;
     std::vector<std::vector<double>> pots;       // keep_potentials
 };
@@ -312,7 +295,7 @@ static std::string rb_gb(double bytes)
 // the crucial-pair layout of the training set (labels descending within a list) and RankBoost.init()'s tables, then the upload
 static int rb_init(rl_rb *R, RbDev &D, std::vector<RbFeature> &feat)
 {
-    rl_ca *c = &R->ca;
+    LinCtx *c = &R->ctx;
     CaSet &d = c->tr;
     const int64_t N = d.N; const int F = c->F;
     std::vector<int64_t> rowoff((size_t)N + 1);
@@ -388,32 +371,10 @@ static int rb_init(rl_rb *R, RbDev &D, std::vector<RbFeature> &feat)
     return RL_OK;
 }
 
-// scorer.score(rank(d)) of the model's first T terms, the cache recomputed from scratch
-static int rb_score_model(rl_rb *R, CaSet &d, int T, double *score)
-{
-    rl_ca *c = &R->ca;
-    CaBuf tmp;
-    int32_t *dc = nullptr; double *dt = nullptr, *dw = nullptr;
-    RL_HIP(tmp.alloc(&dc, (size_t)T));
-    RL_HIP(tmp.alloc(&dt, (size_t)T));
-    RL_HIP(tmp.alloc(&dw, (size_t)T));
-    if (T) {
-        RL_HIP(hipMemcpyAsync(dc, R->fid.data(), T * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        RL_HIP(hipMemcpyAsync(dt, R->thr.data(), T * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        RL_HIP(hipMemcpyAsync(dw, R->weight.data(), T * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    hipLaunchKernelGGL(k_rb_recompute, dim3((unsigned)((d.N + 255) / 256)), dim3(256), 0, c->stream, d.d_cache, (const float *)d.d_xc,
-                       (const float *)nullptr, (int64_t)0, d.N, (const int32_t *)dc, (const double *)dt, (const double *)dw, (int32_t)T);
-    RL_HIP(hipGetLastError());
-    int rc = ca_trials(c, d, nullptr, nullptr, 1, 0, score);
-    RL_HIP(hipStreamSynchronize(c->stream));           // before tmp is freed
-    return rc;
-}
-
 // RankBoost.learn() :265-346
 static int rb_learn(rl_rb *R)
 {
-    rl_ca *c = &R->ca;
+    LinCtx *c = &R->ctx;
     const int F = c->F;
     RbDev D;
     std::vector<RbFeature> feat;
@@ -493,11 +454,9 @@ static int rb_learn(rl_rb *R)
     }
     RL_HIP(hipStreamSynchronize(c->stream));
     if (c->has_valid && bestLen > 0) { R->fid.resize(bestLen); R->thr.resize(bestLen); R->weight.resize(bestLen); }      // :333-338
-    if ((rc = rb_score_model(R, tr, (int)R->fid.size(), &R->train_score))) return rc;
-    R->valid_score = 0;
-    if (c->has_valid && (rc = rb_score_model(R, va, (int)R->fid.size(), &R->valid_score))) return rc;
-    R->learned = true;
-    return RL_OK;
+    LinModel m;
+    m.col = R->fid.data(); m.thr = R->thr.data(); m.w = R->weight.data(); m.nt = m.nw = (int32_t)R->fid.size();
+    return lin_finish(c, m);
 }
 
 }  // namespace rl
@@ -515,78 +474,57 @@ int rl_rb_create(const rl_rb_params *p, rl_rb **out)
 {
     if (!p || !out) return fail(RL_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (p->metric < RL_METRIC_NDCG || p->metric > RL_METRIC_RR)
-        return fail(RL_ERR_UNSUPPORTED, "RankBoost train metric must be NDCG, DCG, MAP, ERR, P or RR (BEST is not built for training)");
-    rl_ca_params cp;
-    rl_ca_params_default(&cp);
-    cp.metric = p->metric; cp.metric_k = p->metric_k; cp.device = p->device; cp.err_max = p->err_max;
-    rl_ca *c = nullptr;
-    int rc = rl_ca_create(&cp, &c);                           // device checks, the stream
-    if (rc) return rc;
     std::unique_ptr<rl_rb> R(new rl_rb());
     R->p = *p;
-    R->ca.p = c->p; R->ca.err_max = c->err_max;
-    std::swap(R->ca.stream, c->stream);
-    rl_ca_destroy(c);
+    int rc = lin_create(&R->ctx, "RankBoost", p->metric, p->metric_k, p->device, p->err_max);
+    if (rc) return rc;
     *out = R.release();
     return RL_OK;
 }
 
-void rl_rb_destroy(rl_rb *r)
-{
-    if (!r) return;
-    (void)hipSetDevice(r->p.device);
-    if (r->ca.stream) (void)hipStreamSynchronize(r->ca.stream);
-    delete r;
-}
+void rl_rb_destroy(rl_rb *r) { lin_destroy(r); }
 
 int rl_rb_set_train(rl_rb *r, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
                     int32_t n_queries, const int32_t *qkey)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    if (r->ca.uploaded) return fail(RL_ERR_STATE, "rl_rb_set_train after rl_rb_learn");
-    int rc = ca_check_set(X, n_docs, n_features, labels, qoff, n_queries);
+    int rc = lin_set_train(lin_ctx(r), "rl_rb_", X, n_docs, n_features, labels, qoff, n_queries, qkey);
     if (rc) return rc;
     // init() :152: samples.set(i, samples.get(i).getCorrectRanking()) -- every list in Sorter's order of its labels from here on
-    std::vector<float> Xs((size_t)n_docs * n_features), ls((size_t)n_docs);
+    CaSet &d = r->ctx.tr;
     std::vector<int32_t> idx;
     for (int32_t q = 0; q < n_queries; q++) {
         const int a = qoff[q], n = qoff[q + 1] - a;
         rb_sorter(labels + a, n, idx);
         for (int i = 0; i < n; i++) {
-            ls[(size_t)a + i] = labels[a + idx[i]];
-            std::copy(X + (size_t)(a + idx[i]) * n_features, X + (size_t)(a + idx[i] + 1) * n_features, Xs.begin() + (size_t)(a + i) * n_features);
+            d.labels[(size_t)a + i] = labels[a + idx[i]];
+            std::copy(X + (size_t)(a + idx[i]) * n_features, X + (size_t)(a + idx[i] + 1) * n_features, d.X.begin() + (size_t)(a + i) * n_features);
         }
     }
-    return rl_ca_set_train(&r->ca, Xs.data(), n_docs, n_features, ls.data(), qoff, n_queries, qkey);
+    return RL_OK;
 }
 
 int rl_rb_set_validation(rl_rb *r, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
                          const int32_t *qkey)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_validation(&r->ca, X, n_docs, labels, qoff, n_queries, qkey);
+    return lin_set_validation(lin_ctx(r), "rl_rb_", X, n_docs, labels, qoff, n_queries, qkey);
 }
 
 int rl_rb_set_external_judgments(rl_rb *r, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    return rl_ca_set_external_judgments(&r->ca, validation, ideal_dcg, rel_doc_count);
+    return lin_set_external_judgments(lin_ctx(r), "rl_rb_", validation, ideal_dcg, rel_doc_count);
 }
 
 int rl_rb_learn(rl_rb *r)
 {
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    if (!r->ca.has_train) return fail(RL_ERR_STATE, "set the training data first");
-    if (r->ca.uploaded) return fail(RL_ERR_STATE, "rl_rb_learn runs once per handle");
-    RL_HIP(hipSetDevice(r->p.device));
+    int rc = lin_begin_learn(lin_ctx(r), "rl_rb_");
+    if (rc) return rc;
     return rb_learn(r);
 }
 
 int rl_rb_get_model(const rl_rb *r, int32_t *fid, double *threshold, double *weight, int32_t cap, int32_t *n)
 {
     if (!r || !n) return fail(RL_ERR_INVALID, "null argument");
-    if (!r->learned) return fail(RL_ERR_STATE, "rl_rb_learn has not run");
+    if (!r->ctx.learned) return fail(RL_ERR_STATE, "rl_rb_learn has not run");
     *n = (int32_t)r->fid.size();
     const size_t m = std::min<size_t>(r->fid.size(), (size_t)std::max(0, cap));
     if (fid) std::copy(r->fid.begin(), r->fid.begin() + m, fid);
@@ -595,22 +533,9 @@ int rl_rb_get_model(const rl_rb *r, int32_t *fid, double *threshold, double *wei
     return RL_OK;
 }
 
-int rl_rb_scores(const rl_rb *r, double *train, double *valid)
-{
-    if (!r) return fail(RL_ERR_INVALID, "null handle");
-    if (!r->learned) return fail(RL_ERR_STATE, "rl_rb_learn has not run");
-    if (train) *train = r->train_score;
-    if (valid) *valid = r->valid_score;
-    return RL_OK;
-}
+int rl_rb_scores(const rl_rb *r, double *train, double *valid) { return lin_scores(lin_ctx(r), "rl_rb_", train, valid); }
 
-int rl_rb_trace(const rl_rb *r, rl_rb_trace_rec *out, int64_t cap, int64_t *n)
-{
-    if (!r || !n) return fail(RL_ERR_INVALID, "null argument");
-    *n = (int64_t)r->trace.size();
-    if (out) std::copy(r->trace.begin(), r->trace.begin() + std::max<int64_t>(0, std::min<int64_t>(cap, *n)), out);
-    return RL_OK;
-}
+int rl_rb_trace(const rl_rb *r, rl_rb_trace_rec *out, int64_t cap, int64_t *n) { return lin_trace(r ? &r->trace : nullptr, out, cap, n); }
 
 int rl_rb_debug_potentials(const rl_rb *r, int32_t round, double *out, int64_t cap)
 {
@@ -628,30 +553,9 @@ int rl_rb_predict(int32_t device, const int32_t *feature_ids, const double *thre
 {
     if (!feature_ids || !thresholds || !weights || !out || (n_docs > 0 && !X)) return fail(RL_ERR_INVALID, "null argument");
     if (n_rankers < 0 || n_docs < 0 || row_stride < 1) return fail(RL_ERR_INVALID, "bad sizes");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    if (n_docs == 0) return RL_OK;
-    RL_HIP(hipSetDevice(device));
-    CaBuf buf;
-    float *dX = nullptr; int32_t *dF = nullptr; double *dT = nullptr, *dW = nullptr, *dO = nullptr;
-    RL_HIP(buf.alloc(&dX, (size_t)n_docs * row_stride));
-    RL_HIP(buf.alloc(&dF, (size_t)n_rankers));
-    RL_HIP(buf.alloc(&dT, (size_t)n_rankers));
-    RL_HIP(buf.alloc(&dW, (size_t)n_rankers));
-    RL_HIP(buf.alloc(&dO, (size_t)n_docs));
-    RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
-    if (n_rankers) {
-        RL_HIP(hipMemcpy(dF, feature_ids, n_rankers * sizeof(int32_t), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(dT, thresholds, n_rankers * sizeof(double), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(dW, weights, n_rankers * sizeof(double), hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_rb_recompute, dim3((unsigned)((n_docs + 255) / 256)), dim3(256), 0, 0, dO, (const float *)nullptr, (const float *)dX,
-                       (int64_t)row_stride, n_docs, (const int32_t *)dF, (const double *)dT, (const double *)dW, n_rankers);
-    RL_HIP(hipGetLastError());
-    RL_HIP(hipMemcpy(out, dO, n_docs * sizeof(double), hipMemcpyDeviceToHost));
-    return RL_OK;
+    LinModel m;
+    m.col = feature_ids; m.thr = thresholds; m.w = weights; m.nt = m.nw = n_rankers;
+    return lin_predict(device, m, X, n_docs, row_stride, out);
 }
 
 }  // extern "C"

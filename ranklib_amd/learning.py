@@ -703,7 +703,41 @@ def _key_value_line(fullText):
     return keys, values
 
 
-class CoorAscent(Ranker):
+class _LinearRanker(Ranker):
+    """What CoorAscent, AdaRank, RankBoost and LinearRegRank share: each trains through a _native trainer of its own (self._trainer, made
+    by init()) and scores rows with one of the library's predict functions (_predict)."""
+
+    def _train_metric(self):
+        """the scorer's metric as the trainers name it; the linear rankers train on all six"""
+        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        if metric not in N.RL_CA_METRIC:
+            raise RankLibError("rlhip: the %s train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
+                               % (self.name(), self.scorer.name() if self.scorer else None))
+        return metric
+
+    def _finish_learn(self):
+        """the end of every learn(): the final scores, their log lines, and the trainer closed"""
+        t, nm = self._trainer, self.scorer.name()
+        ts, vs = t.scores()
+        self.scoreOnTrainingData = java_round(ts, 4)
+        logger.info("Finished sucessfully.")
+        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
+        if vs is not None:
+            self.bestScoreOnValidationData = vs
+            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
+        t.close()
+        self._trainer = None
+
+    def evalList(self, rl):
+        if rl.size() == 0:
+            return []
+        return [float(v) for v in self._predict(rl.rl)]
+
+    def eval(self, dp):               # noqa: A003  the Java's eval(DataPoint): the same f64 sum, one row
+        return self.evalList(RankList([dp]))[0]
+
+
+class CoorAscent(_LinearRanker):
     """learning/CoorAscent.java: the linear ranker, learn() executed on an MI355X (librlhip.so rl_ca_*, every trial of a search direction
     in one pass), eval() as the GPU's f64 dot product in feature order."""
     # process-global parameters, like the Java statics (:37-43)
@@ -726,10 +760,7 @@ class CoorAscent(Ranker):
     def init(self):                   # :60-64
         logger.info("Initializing... ")
         self.weight = [1.0 / len(self.features)] * len(self.features)
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
-        if metric not in N.RL_CA_METRIC:
-            raise RankLibError("rlhip: the Coordinate Ascent train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
-                               % (self.scorer.name() if self.scorer else None))
+        metric = self._train_metric()
         cls = type(self)
         t = N.CoorAscentTrainer(n_restart=cls.nRestart, n_max_iteration=cls.nMaxIteration, step_base=cls.stepBase, step_scale=cls.stepScale,
                                 tolerance=cls.tolerance, regularized=cls.regularized, slack=cls.slack, metric=metric,
@@ -760,27 +791,11 @@ class CoorAscent(Ranker):
                 bw = ("+" if w > 0 else "") + java_double_str(java_round(w, 4))
                 self.printLogLn([7, 8, 7], [str(self.features[int(rec["feature"])]), bw, java_double_str(java_round(best, 4))])
         self.weight = [float(v) for v in t.weights()]
-        ts, vs = t.scores()
-        self.scoreOnTrainingData = java_round(ts, 4)
-        logger.info("Finished sucessfully.")
-        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
-        if vs is not None:
-            self.bestScoreOnValidationData = vs
-            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
-        t.close()
-        self._trainer = None
+        self._finish_learn()
 
     # --- scoring: 0.0 + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_ca_predict) -----------------
-    def _rows(self, dps):
-        return _linear_rows(dps, self.features)
-
-    def evalList(self, rl):
-        if rl.size() == 0:
-            return []
-        return [float(v) for v in N.ca_predict(self.features, self.weight, self._rows(rl.rl), type(self).device)]
-
-    def eval(self, dp):               # noqa: A003  :229-235
-        return self.evalList(RankList([dp]))[0]
+    def _predict(self, dps):          # eval :229-235
+        return N.ca_predict(self.features, self.weight, _linear_rows(dps, self.features), type(self).device)
 
     def createNew(self):
         return CoorAscent()
@@ -843,7 +858,7 @@ class CoorAscent(Ranker):
         return self.getDistance(self.weight, ca.weight)
 
 
-class AdaRank(Ranker):
+class AdaRank(_LinearRanker):
     """learning/boosting/AdaRank.java: a linear ensemble of single-feature weak rankers, learn() executed on an MI355X (librlhip.so
     rl_ada_*: the weak rankers' metric table once, then a candidate pass and one ranking of the ensemble per round), eval() as the GPU's
     f64 sum in ensemble order."""
@@ -863,10 +878,7 @@ class AdaRank(Ranker):
 
     def init(self):                   # :205-227
         logger.info("Initializing... ")
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
-        if metric not in N.RL_CA_METRIC:
-            raise RankLibError("rlhip: the AdaRank train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
-                               % (self.scorer.name() if self.scorer else None))
+        metric = self._train_metric()
         cls = type(self)
         t = N.AdaRankTrainer(n_iteration=cls.nIteration, tolerance=cls.tolerance, train_with_enqueue=cls.trainWithEnqueue,
                              max_sel_count=cls.maxSelCount, metric=metric, metric_k=self.scorer.getK(), device=cls.device,
@@ -897,24 +909,11 @@ class AdaRank(Ranker):
         cols, w = t.model()
         self.rankers = [int(self.features[int(c)]) for c in cols]
         self.rweight = [float(v) for v in w]
-        ts, vs = t.scores()
-        self.scoreOnTrainingData = java_round(ts, 4)
-        logger.info("Finished sucessfully.")
-        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
-        if vs is not None:
-            self.bestScoreOnValidationData = vs
-            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
-        t.close()
-        self._trainer = None
+        self._finish_learn()
 
     # --- scoring: 0.0 + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_ca_predict, repeated fids) -----------------
-    def evalList(self, rl):
-        if rl.size() == 0:
-            return []
-        return [float(v) for v in N.ca_predict(self.rankers, self.rweight, _linear_rows(rl.rl, self.rankers), type(self).device)]
-
-    def eval(self, dp):               # noqa: A003  :265-271
-        return self.evalList(RankList([dp]))[0]
+    def _predict(self, dps):          # eval :265-271
+        return N.ca_predict(self.rankers, self.rweight, _linear_rows(dps, self.rankers), type(self).device)
 
     def createNew(self):
         return AdaRank()
@@ -951,7 +950,7 @@ class AdaRank(Ranker):
         return "AdaRank"
 
 
-class RankBoost(Ranker):
+class RankBoost(_LinearRanker):
     """learning/boosting/RankBoost.java: an ensemble of threshold weak rankers (RBWeakRanker: 1 if x[fid] > threshold else 0), init() and
     learn() executed on an MI355X (librlhip.so rl_rb_*: the crucial pairs' weights, the potentials, the candidate chains, the Z_t chain
     and the metrics of every round), eval() as the GPU's f64 sum in ensemble order."""
@@ -969,10 +968,7 @@ class RankBoost(Ranker):
 
     def init(self):                   # :143-263
         logger.info("Initializing... ")
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
-        if metric not in N.RL_CA_METRIC:
-            raise RankLibError("rlhip: the RankBoost train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
-                               % (self.scorer.name() if self.scorer else None))
+        metric = self._train_metric()
         cls = type(self)
         t = N.RankBoostTrainer(n_iteration=cls.nIteration, n_threshold=cls.nThreshold, metric=metric, metric_k=self.scorer.getK(),
                                device=cls.device, err_max=ERRScorer.MAX)
@@ -1000,26 +996,12 @@ class RankBoost(Ranker):
         cols, thr, w = t.model()
         self.wRankers = [(int(self.features[int(c)]), float(v)) for c, v in zip(cols, thr)]
         self.rWeight = [float(v) for v in w]
-        ts, vs = t.scores()
-        self.scoreOnTrainingData = java_round(ts, 4)
-        logger.info("Finished sucessfully.")
-        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
-        if vs is not None:
-            self.bestScoreOnValidationData = vs
-            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
-        t.close()
-        self._trainer = None
+        self._finish_learn()
 
     # --- scoring: 0.0 + w[0] h_0(x) + w[1] h_1(x) + ... in f64 on the GPU (rl_rb_predict, repeated fids) ---------------
-    def evalList(self, rl):
-        if rl.size() == 0:
-            return []
+    def _predict(self, dps):          # eval :348-355
         fids = [f for f, _ in self.wRankers]
-        return [float(v) for v in N.rb_predict(fids, [t for _, t in self.wRankers], self.rWeight, _linear_rows(rl.rl, fids),
-                                               type(self).device)]
-
-    def eval(self, dp):               # noqa: A003  :348-355
-        return self.evalList(RankList([dp]))[0]
+        return N.rb_predict(fids, [t for _, t in self.wRankers], self.rWeight, _linear_rows(dps, fids), type(self).device)
 
     def createNew(self):
         return RankBoost()
@@ -1069,7 +1051,7 @@ class RankBoost(Ranker):
         return "RankBoost"
 
 
-class LinearRegRank(Ranker):
+class LinearRegRank(_LinearRanker):
     """learning/LinearRegRank.java: the least-squares ranker.  learn() runs on an MI355X (librlhip.so rl_lr_*: xTx and xTy accumulated cell
     by cell in the Java's document order, then the Java's elimination without pivoting on the host), eval() as the GPU's f64 sum that
     starts from weight[last].  nVar is the largest feature id of the training lists: features 1 .. nVar - 1 and a constant are fitted,
@@ -1086,10 +1068,7 @@ class LinearRegRank(Ranker):
 
     def init(self):                   # :39-41
         logger.info("Initializing...")
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
-        if metric not in N.RL_CA_METRIC:
-            raise RankLibError("rlhip: the Linear Regression train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
-                               % (self.scorer.name() if self.scorer else None))
+        metric = self._train_metric()
         cls = type(self)
         nVar = max((rl.getFeatureCount() for rl in self.samples), default=0)      # :50-56
         if nVar < 1:
@@ -1127,28 +1106,14 @@ class LinearRegRank(Ranker):
             except RankLibError:
                 self.gram = self.times = None
         self.weight = [float(v) for v in t.weights()]
-        ts, vs = t.scores()
-        nm = self.scorer.name()
-        self.scoreOnTrainingData = java_round(ts, 4)
-        logger.info("Finished sucessfully.")
-        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
-        if vs is not None:
-            self.bestScoreOnValidationData = vs
-            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
-        t.close()
-        self._trainer = None
+        self._finish_learn()
 
     # --- scoring: weight[last] + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_lr_predict) -------------------------
-    def evalList(self, rl):
-        if rl.size() == 0:
-            return []
+    def _predict(self, dps):          # eval :103-109
         if len(self.features) > len(self.weight):
             raise RankLibError("rlhip: Linear Regression has %d features to score with but only %d weights; the Java ends in an "
                                "ArrayIndexOutOfBoundsException in eval" % (len(self.features), len(self.weight)))
-        return [float(v) for v in N.lr_predict(self.features, self.weight, _linear_rows(rl.rl, self.features), type(self).device)]
-
-    def eval(self, dp):               # noqa: A003  :103-109
-        return self.evalList(RankList([dp]))[0]
+        return N.lr_predict(self.features, self.weight, _linear_rows(dps, self.features), type(self).device)
 
     def createNew(self):
         return LinearRegRank()

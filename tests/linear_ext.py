@@ -105,8 +105,9 @@ REFUSAL_MAP = {"q0": 9, "q2": 9, "q3": 9}                # the same as a restate
 
 
 def forwarded_refusals(new_trainer, tr, error):
-    """rl_{ada,rb,lr}_set_external_judgments forward to rl_ca_set_external_judgments: RL_ERR_STATE (-3) before set_train, for a validation
-    set that was never given and after learn(); RL_ERR_INVALID (-1) for a negative count; a later set_train discards the judgments (ca_store).
+    """rl_{ca,ada,rb,lr}_set_external_judgments are one function on the handles' shared ranking context (lin_set_external_judgments,
+    rl_linear.inc): RL_ERR_STATE (-3) before set_train, for a validation set that was never given and after learn(); RL_ERR_INVALID (-1)
+    for a negative count; a later set_train discards the judgments (ca_store).
     tr holds four lists q0 .. q3.  Returns (the trainer that learned with REFUSAL_COUNTS, the one whose judgments were discarded)."""
     t = new_trainer()
     with pytest.raises(error) as e:
