@@ -23,6 +23,8 @@
 
 #include <chrono>
 
+#include "rl_knobs.h"
+
 namespace rl {
 
 constexpr int kLrSlab = 3584;          // values staged per slab: 14 per thread
@@ -208,6 +210,7 @@ struct rl_lr {
     std::vector<double> xtx, xty, weight;
     double gram_ms = 0, solve_ms = 0, score_ms = 0;
     int32_t rb = 0;
+    int32_t rb_knob = 0;               // RLHIP_LR_RB when it names a register block (1 / 2 / 4), else 0: lr_pick_rb chooses
 };
 
 namespace rl {
@@ -217,10 +220,10 @@ static int lr_blocks(int C, int rb) { const int nt = (C + 16 * rb - 1) / (16 * r
 // The register block, by a model: a lane's RB^2 chains cost max(13, 4 RB^2) cycles a document (the latency of one dependent f64 add against
 // the issue of RB^2 wave64 f64 operations), and the chip runs about 512 blocks at a time (two 59.5 KB blocks per CU).  The measured costs
 // are higher (the LDS reads set them), but the sweeps at 46, 136 and 700 columns agree with every choice it makes (DESIGN.md 11).
-// RLHIP_LR_RB overrides.
-static int lr_pick_rb(int C)
+// rl_lr::rb_knob overrides.
+static int lr_pick_rb(int C, int rb_knob)
 {
-    if (const char *e = getenv("RLHIP_LR_RB")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) return v; }
+    if (rb_knob) return rb_knob;
     int best = 1; int64_t bc = 0;
     for (int rb = 1; rb <= 4; rb *= 2) {
         const int64_t cost = (int64_t)((lr_blocks(C, rb) + 511) / 512) * std::max(13, 4 * rb * rb);
@@ -277,7 +280,7 @@ static int lr_gram(rl_lr *R)
     LinCtx *c = &R->ctx;
     CaSet &d = c->tr;
     const int C = R->n_var;
-    const int rb = R->rb = lr_pick_rb(C);
+    const int rb = R->rb = lr_pick_rb(C, R->rb_knob);
     const int nt = (C + 16 * rb - 1) / (16 * rb), ntri = nt * (nt + 1) / 2;
     const unsigned grid = (unsigned)lr_blocks(C, rb);
     double *dxtx = nullptr, *dxty = nullptr;
@@ -350,6 +353,7 @@ int rl_lr_create(const rl_lr_params *p, rl_lr **out)
     if (!std::isfinite(p->lambda)) return fail(RL_ERR_INVALID, "lambda (-L2) must be finite");
     std::unique_ptr<rl_lr> R(new rl_lr());
     R->p = *p;
+    R->rb_knob = read_lr_rb_knob();
     int rc = lin_create(&R->ctx, "Linear Regression", p->metric, p->metric_k, p->device, p->err_max);
     if (rc) return rc;
     *out = R.release();

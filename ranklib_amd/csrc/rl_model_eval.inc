@@ -1,0 +1,394 @@
+// rl_model_eval.inc -- the scoring-only model: an ensemble loaded from RankLib model text, its two evaluation kernels and the rl_model_* ABI.
+// Included at the end of rl_trainer.hip (it uses DevPool, EnsTree and HostTree).
+struct rl_model {
+    int32_t device = 0;
+    std::vector<HostTree> trees;
+    std::vector<int32_t> features;
+    int32_t maxn = 1;
+    bool uniform_weight = true;
+    DevPool pool;
+    EnsTree ens;
+    float *d_w = nullptr;
+    unsigned long long *d_pack = nullptr;   // packed nodes for k_model_eval_tiled (null when the model does not fit the packing)
+    unsigned char *d_perm = nullptr;        // [tiles][kEvalTreeTile] trees of a tile by descending depth (255 = none): walker wavefront p takes ranks 8 p .. 8 p + 7
+    unsigned char *d_gdepth = nullptr;      // [tiles][kEvalParts] deepest leaf among a walker's trees = its lockstep walk length
+    int32_t maxcol = 0;                     // largest column any node reads
+    EvalKnobs knobs;                        // RLHIP_EVAL_*, read by rl_model_from_text
+};
+
+namespace rl {
+// like k_ensemble_eval but with a weight per tree (Ensemble.weights)
+__global__ __launch_bounds__(kThreads) void k_model_eval(const EnsTree e, const float *w, int MAXN, int nt, const float *X, int64_t n,
+                                                          int stride, float *out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+        const float *row = X + (size_t)i * stride;
+        float s = 0.f;
+        for (int t = 0; t < nt; t++) {
+            const size_t o = (size_t)t * MAXN;
+            int nd = 0;
+            while (e.feat_idx[o + nd] != -1) {
+                const int fc = e.feat_idx[o + nd];
+                const float v = (fc < stride) ? row[fc] : 0.f;                 // -missingZero  DenseDataPoint.java:22-25
+                nd = (v <= e.thr[o + nd]) ? e.left[o + nd] : e.right[o + nd];
+            }
+            s = (float)((double)s + (double)e.out[o + nd] * (double)w[t]);     // Ensemble.java:113
+        }
+        out[i] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K10 (SURVEY.md 8f-1, config c4): Ensemble.eval for many trees.  One block scores a tile of kEvalDocs documents against
+// the whole ensemble:
+//   * the tile's feature rows are transposed into LDS once, sX[column][doc] (columns the rows do not have are zero:
+//     -missingZero): a lane reads sX[c * kEvalDocs + doc], so the bank is doc % 32 whatever column the lane's path asks
+//     for -- conflict-free;
+//   * trees stream through LDS in tiles of kEvalTreeTile as packed 8-byte nodes, children adjacent (right = left + 1):
+//       bits 0..31 threshold (or leaf output) float bits | 32..47 byte offset of the column in sX (0xFFFF = leaf)
+//       | 48..63 byte offset of the left child in the tree
+//     so a step is: load node, load value, compare, add -- 7 VALU + 2 LDS instructions;
+//   * walker wavefront p (of kEvalParts) owns trees [p*kEvalPer, (p+1)*kEvalPer) of the tile for all documents: kEvalPer
+//     chains per lane in lockstep (a leaf is a fixed point of the step, so finished trees idle in place).  The walk is
+//     bound by instruction issue (13 per chain step), not by LDS latency.  Measured and dropped: refilling a finished chain
+//     with the lane's next tree (fewer steps, but a leaf branch that some lane takes at almost every step: 8.2 M docs/s
+//     against 14.8), and a branch-free step with all value loads issued first (22 instructions per step: 9.7 M docs/s);
+//   * one more wavefront does nothing but Ensemble.eval's accumulation  s = (float)(s + out * weight)  in tree order
+//     (learning/tree/Ensemble.java:110-116) for the PREVIOUS tile (leaf outputs double-buffered in LDS), so the serial
+//     float chain of a document overlaps the walk of the next tile instead of stalling the walkers;
+//   * the next tile of trees is fetched into registers while the current one is walked.
+// Needs: column offsets and child offsets that fit 16 bits, and the LDS budget; otherwise k_model_eval runs.
+// ------------------------------------------------------------------------------------------------
+#ifndef RL_EVAL_PARTS
+#define RL_EVAL_PARTS 4
+#endif
+#ifndef RL_EVAL_PER
+#define RL_EVAL_PER 8
+#endif
+constexpr int kEvalDocs = 64, kEvalParts = RL_EVAL_PARTS, kEvalPer = RL_EVAL_PER, kEvalTreeTile = kEvalParts * kEvalPer;
+constexpr int kEvalThreads = kEvalDocs * (kEvalParts + 1), kEvalPrefetch = 8;     // 8-byte words each thread prefetches per tile
+// Phases of a walker's walk (round 6; see the loop): chains still walking after the first phase, the second, .. and in the last one.  Same box,
+// alternating libraries, 30 M rows x 10 000 trees (profiles/r06w_ab_infer_phased_walk.txt): one loop of eight chains 26.8 M docs/s | 8 -> 4: 27.9 |
+// 8 -> 4 -> 2: 27.5 | 8 -> 6 -> 4 -> 2: 28.3 - 28.5 | a staircase 8 -> 7 -> .. -> 1: 23.3.
+#ifndef RL_EVAL_PHASES
+#define RL_EVAL_PHASES 3
+#endif
+#if RL_EVAL_PHASES == 1
+constexpr int kEvalPhases = 1, kEvalPh1 = 4, kEvalPh2 = 2, kEvalPhLast = 4;
+#elif RL_EVAL_PHASES == 2
+constexpr int kEvalPhases = 2, kEvalPh1 = 4, kEvalPh2 = 2, kEvalPhLast = 2;
+#else
+constexpr int kEvalPhases = 3, kEvalPh1 = 6, kEvalPh2 = 4, kEvalPhLast = 2;
+#endif
+static_assert(kEvalPer >= kEvalPh1 && kEvalPh1 >= kEvalPh2 && kEvalPh2 >= kEvalPhLast && kEvalPhLast >= 1, "a phase walks the deepest chains of the phase before it");
+constexpr int kEvalMetaDepths = kEvalParts * (1 + kEvalPhases);      // per tile: every walker's steps, then the steps at which its phases end
+
+static inline size_t eval_tiled_lds(int cols, int maxn)
+{
+    return (size_t)cols * kEvalDocs * 4 + (size_t)kEvalTreeTile * maxn * 8 + (size_t)2 * kEvalTreeTile * kEvalDocs * 4 + 2 * kEvalTreeTile * 4 + 2 * (kEvalTreeTile + kEvalMetaDepths);
+}
+
+// cols = max(row_stride, largest column any node reads + 1)
+//
+// The walk (round 4).  A leaf is packed as a node that loops onto itself: it "reads" column 0 -- no RankLib feature has id 0; the staged tile holds
+// -infinity there -- so `x <= value` is always true and its left-child offset is its own.  A chain step is then the same eight instructions for
+// every node (and, add, ds_read_b32, shift, compare, select, add3, ds_read_b64) with no leaf test and no branch, so the compiler issues the eight
+// chains' feature loads back to back and their node loads back to back: the wavefront waits for LDS twice per step of EIGHT chains instead of
+// twice per chain (the branchy version spent half of its time in those waits: 2.5 walker wavefronts per SIMD cannot hide them).  The trees of a
+// tile, sorted by depth, are dealt round the walkers (perm / gdepth, built with the packing), deepest first inside a walker; a walker's deepest tree sets its
+// number of steps, and since round 6 its chains drop out in phases as their trees end -- eight chains to the 7th tree's depth, six to the 5th's, four to the
+// 3rd's, two to the deepest's (see kEvalPhases) -- instead of all eight idling on their leaves to the last step: 26.8 -> 28.4 M docs/s.  The accumulator
+// adds the outputs in the ensemble's own order whatever walker produced them.
+__global__ __launch_bounds__(kEvalThreads) void k_model_eval_tiled(const unsigned long long *nodes, const float *w, int MAXN, int nt,
+                                                                   const float *X, int64_t n, int stride, int cols, float *out,
+                                                                   const unsigned char *perm, const unsigned char *gdepth)
+{
+    extern __shared__ unsigned char ev_raw[];
+    float *sX = (float *)ev_raw;                                               // [cols][kEvalDocs]
+    unsigned long long *sT = (unsigned long long *)(sX + (size_t)cols * kEvalDocs);   // [kEvalTreeTile][MAXN]
+    float *sO = (float *)(sT + (size_t)kEvalTreeTile * MAXN);                  // [2][kEvalTreeTile][kEvalDocs] leaf outputs (double buffer)
+    float *sW = sO + 2 * kEvalTreeTile * kEvalDocs;                            // [2][kEvalTreeTile] tree weights
+    unsigned char *sP = (unsigned char *)(sW + 2 * kEvalTreeTile);             // [2][kEvalTreeTile + kEvalMetaDepths] the tile's walker assignment and walk lengths
+    const int tid = threadIdx.x, doc = tid & (kEvalDocs - 1), part = tid / kEvalDocs;
+    const bool walker = part < kEvalParts;
+    const int tile_words = kEvalTreeTile * MAXN;                               // <= kEvalThreads * kEvalPrefetch (checked by the host)
+    const unsigned char *sXb = (const unsigned char *)sX + doc * 4;
+    for (int64_t tile = blockIdx.x; tile * kEvalDocs < n; tile += gridDim.x) {
+        const int64_t d0 = tile * kEvalDocs;
+        const int nd = (int)min((int64_t)kEvalDocs, n - d0);
+        __syncthreads();
+        const float *src = X + (size_t)d0 * stride;                            // the tile is one contiguous range of X
+        for (int e = tid; e < nd * stride; e += kEvalThreads) { const int dd = e / stride, c = e - dd * stride; sX[c * kEvalDocs + dd] = src[e]; }
+        for (int e = tid; e < (cols - stride) * kEvalDocs; e += kEvalThreads) sX[stride * kEvalDocs + e] = 0.f;
+        float s = 0.f;                                                         // the accumulator wavefront's running Ensemble.eval sum
+        unsigned long long pre[kEvalPrefetch];
+#pragma unroll
+        for (int u = 0; u < kEvalPrefetch; u++) { const int e = tid + u * kEvalThreads; pre[u] = (e < min(tile_words, nt * MAXN)) ? nodes[e] : 0ull; }
+        __syncthreads();
+        if (tid < kEvalDocs) sX[tid] = -__builtin_inff();                      // column 0: what a leaf "reads" (after the staging pass wrote the rows' column 0)
+        int k = 0, tt_prev = 0;
+        for (int t0 = 0; t0 < nt; t0 += kEvalTreeTile, k++) {
+            const int tt = min(kEvalTreeTile, nt - t0);
+            const int cb = k & 1;
+            __syncthreads();                                                   // tile k-1 walked (its outputs complete), sT free
+#pragma unroll
+            for (int u = 0; u < kEvalPrefetch; u++) { const int e = tid + u * kEvalThreads; if (e < tile_words) sT[e] = pre[u]; }
+            if (tid < tt) sW[cb * kEvalTreeTile + tid] = w[t0 + tid];
+            if (tid < kEvalTreeTile) sP[cb * (kEvalTreeTile + kEvalMetaDepths) + tid] = perm[(size_t)k * kEvalTreeTile + tid];
+            else if (tid < kEvalTreeTile + kEvalMetaDepths) sP[cb * (kEvalTreeTile + kEvalMetaDepths) + tid] = gdepth[(size_t)k * kEvalMetaDepths + (tid - kEvalTreeTile)];
+            __syncthreads();
+            {   // next tile -> registers (in flight during the walk)
+                const size_t nb = (size_t)(t0 + kEvalTreeTile) * MAXN;
+                const long long left = (long long)nt * MAXN - (long long)nb;
+#pragma unroll
+                for (int u = 0; u < kEvalPrefetch; u++) { const int e = tid + u * kEvalThreads; pre[u] = (e < tile_words && e < left) ? nodes[nb + e] : 0ull; }
+            }
+            if (walker) {
+                const unsigned char *pp = sP + cb * (kEvalTreeTile + kEvalMetaDepths);
+                const int depth = __builtin_amdgcn_readfirstlane((int)pp[kEvalTreeTile + part]);      // wave-uniform: a scalar loop bound
+                if (depth > 0) {
+                    float *so = sO + (size_t)cb * kEvalTreeTile * kEvalDocs + doc;
+                    const unsigned char *tb[kEvalPer];
+                    unsigned long long v[kEvalPer];
+                    int li[kEvalPer];
+#pragma unroll
+                    for (int u = 0; u < kEvalPer; u++) {
+                        li[u] = __builtin_amdgcn_readfirstlane((int)pp[part * kEvalPer + u]);         // 255: no such tree in this (last) tile -- the chain walks tree 0 again, unstored
+                        tb[u] = (const unsigned char *)(sT + (size_t)(li[u] < tt ? li[u] : 0) * MAXN);
+                        v[u] = *(const unsigned long long *)tb[u];
+                    }
+                    // The walker's trees come deepest first.  All eight chains walk for as many steps as the walker's (kEvalPh1 + 1)-th tree has levels, then the
+                    // kEvalPh1 deepest for as many as the (kEvalPh2 + 1)-th has, ... : a chain that has reached its leaf in every lane stops costing instructions
+                    // (in ONE loop to the deepest tree's depth the shallow chains idled on their leaves, at the cost of their instructions).
+                    int step = 0;
+#define RL_EVAL_PHASE(NCH, UNTIL)                                                                                                          \
+                    for (; step < (UNTIL); step++) {                                                                                       \
+                        float x[NCH];                                                                                                      \
+                        _Pragma("unroll") for (int u = 0; u < NCH; u++) x[u] = *(const float *)(sXb + ((unsigned)(v[u] >> 32) & 0xffffu)); \
+                        _Pragma("unroll") for (int u = 0; u < NCH; u++) {       /* Split.eval: value <= threshold goes left (Split.java:118); a leaf stays where it is */ \
+                            const unsigned off = (unsigned)(v[u] >> 48) + ((x[u] <= __uint_as_float((unsigned)v[u])) ? 0u : 8u);           \
+                            v[u] = *(const unsigned long long *)(tb[u] + off);                                                             \
+                        }                                                                                                                  \
+                    }
+                    const unsigned char *pd = pp + kEvalTreeTile + kEvalParts + part * kEvalPhases;
+                    const int end0 = __builtin_amdgcn_readfirstlane((int)pd[0]);           // (scalar loop bounds, read once)
+                    [[maybe_unused]] const int end1 = __builtin_amdgcn_readfirstlane((int)pd[kEvalPhases >= 2 ? 1 : 0]);
+                    [[maybe_unused]] const int end2 = __builtin_amdgcn_readfirstlane((int)pd[kEvalPhases >= 3 ? 2 : 0]);
+                    RL_EVAL_PHASE(kEvalPer, end0)
+#if RL_EVAL_PHASES >= 2
+                    RL_EVAL_PHASE(kEvalPh1, end1)
+#endif
+#if RL_EVAL_PHASES >= 3
+                    RL_EVAL_PHASE(kEvalPh2, end2)
+#endif
+                    RL_EVAL_PHASE(kEvalPhLast, depth)
+#undef RL_EVAL_PHASE
+                    if (doc < nd) {
+#pragma unroll
+                        for (int u = 0; u < kEvalPer; u++) if (li[u] < tt) so[li[u] * kEvalDocs] = __uint_as_float((unsigned)v[u]);
+                    }
+                }
+            } else if (k > 0 && doc < nd) {                                    // accumulate the previous tile while this one is walked
+                const float *po = sO + (size_t)(cb ^ 1) * kEvalTreeTile * kEvalDocs + doc, *pw = sW + (cb ^ 1) * kEvalTreeTile;
+                for (int t = 0; t < tt_prev; t++) s = (float)((double)s + (double)po[t * kEvalDocs] * (double)pw[t]);   // Ensemble.java:113
+            }
+            tt_prev = tt;
+        }
+        __syncthreads();
+        if (!walker && doc < nd) {
+            if (k > 0) {
+                const int cb = (k - 1) & 1;
+                const float *po = sO + (size_t)cb * kEvalTreeTile * kEvalDocs + doc, *pw = sW + cb * kEvalTreeTile;
+                for (int t = 0; t < tt_prev; t++) s = (float)((double)s + (double)po[t * kEvalDocs] * (double)pw[t]);
+            }
+            out[d0 + doc] = s;
+        }
+    }
+}
+}  // namespace rl
+
+extern "C" {
+
+int rl_model_from_text(const char *text, int32_t device, rl_model **out)
+{
+    if (!text || !out) return fail(RL_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<rl_model> m(new rl_model());
+    std::string err;
+    if (!model_from_text(text, m->trees, err)) return fail(RL_ERR_INVALID, "Error in Emsemble(xmlRepresentation): " + err);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
+    m->device = device;
+    m->knobs.read();
+    RL_HIP(hipSetDevice(device));
+    std::map<int32_t, int> fids;
+    for (auto &t : m->trees) { m->maxn = std::max(m->maxn, t.n_nodes); for (int f : t.feature) if (f != -1) fids[f] = 0; }
+    for (auto &kv : fids) m->features.push_back(kv.first);
+    const size_t nt = m->trees.size(), en = std::max<size_t>(1, nt * m->maxn);
+    std::vector<int32_t> fi(en, -1), le(en, -1), ri(en, -1);
+    std::vector<float> th(en, 0.f), ou(en, 0.f), w(std::max<size_t>(1, nt), 0.f);
+    for (size_t i = 0; i < nt; i++) {
+        const HostTree &t = m->trees[i];
+        w[i] = t.weight;
+        for (int j = 0; j < t.n_nodes; j++) {
+            const size_t o = i * m->maxn + j;
+            fi[o] = t.feature[j]; le[o] = t.left[j]; ri[o] = t.right[j]; th[o] = t.threshold[j]; ou[o] = t.output[j];
+        }
+    }
+    memset(&m->ens, 0, sizeof(m->ens));
+    RL_HIP(m->pool.alloc(&m->ens.feat_idx, en)); RL_HIP(m->pool.alloc(&m->ens.left, en)); RL_HIP(m->pool.alloc(&m->ens.right, en));
+    RL_HIP(m->pool.alloc(&m->ens.thr, en)); RL_HIP(m->pool.alloc(&m->ens.out, en)); RL_HIP(m->pool.alloc(&m->d_w, w.size()));
+    RL_HIP(hipMemcpy(m->ens.feat_idx, fi.data(), en * 4, hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(m->ens.left, le.data(), en * 4, hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(m->ens.right, ri.data(), en * 4, hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(m->ens.thr, th.data(), en * 4, hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(m->ens.out, ou.data(), en * 4, hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(m->d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    {   // packed nodes (see k_model_eval_tiled): breadth-first renumbering puts siblings next to each other
+        int maxcol = 0;
+        for (int32_t f : m->features) maxcol = std::max(maxcol, f);
+        m->maxcol = maxcol;
+        bool ok = nt > 0 && (size_t)m->maxn * 8 < 0x10000 && (size_t)(maxcol + 1) * kEvalDocs * 4 < 0xffff &&
+                  (size_t)kEvalTreeTile * m->maxn <= (size_t)kEvalThreads * kEvalPrefetch;
+        for (int32_t f : m->features) ok = ok && f >= 1;        // column 0 is what a packed leaf reads (no RankLib feature has id 0: learning/DataPoint.java:33)
+        if (ok) {
+            std::vector<unsigned long long> pk(en, 0ull);           // (padding: a leaf at offset 0 with value +0.0)
+            std::vector<int> order, newid, lvl;
+            std::vector<int> tdepth(nt, 0);
+            for (size_t i = 0; i < nt && ok; i++) {
+                const HostTree &t = m->trees[i];
+                order.assign(1, 0); newid.assign(t.n_nodes, -1); newid[0] = 0; lvl.assign(1, 0);
+                for (size_t h = 0; h < order.size(); h++) {
+                    const int j = order[h];
+                    if (t.feature[j] == -1) continue;
+                    if (t.left[j] < 0 || t.right[j] < 0 || t.left[j] >= t.n_nodes || t.right[j] >= t.n_nodes || (int)order.size() + 2 > t.n_nodes) { ok = false; break; }
+                    newid[t.left[j]] = (int)order.size(); order.push_back(t.left[j]); lvl.push_back(lvl[h] + 1);
+                    newid[t.right[j]] = (int)order.size(); order.push_back(t.right[j]); lvl.push_back(lvl[h] + 1);
+                    tdepth[i] = std::max(tdepth[i], lvl[h] + 1);
+                }
+                for (size_t h = 0; h < order.size() && ok; h++) {
+                    const int j = order[h];
+                    const bool leaf = t.feature[j] == -1;
+                    uint32_t bits; const float fv = leaf ? t.output[j] : t.threshold[j];
+                    memcpy(&bits, &fv, 4);
+                    if (leaf && std::isnan(fv)) { ok = false; break; }       // a leaf loops through `-inf <= value`: NaN outputs take the generic kernel
+                    // leaf: reads column 0 (-infinity in the staged tile) and its left child is itself
+                    const unsigned long long co = leaf ? 0ull : (unsigned long long)t.feature[j] * kEvalDocs * 4;
+                    const unsigned long long lo = leaf ? (unsigned long long)h * 8 : (unsigned long long)newid[t.left[j]] * 8;
+                    pk[i * m->maxn + h] = (unsigned long long)bits | (co << 32) | (lo << 48);
+                }
+                if (tdepth[i] > 250) ok = false;
+            }
+            if (ok) {
+                // the trees of a tile go to the walker wavefronts by descending depth (stable), eight each
+                const size_t ntl = (nt + kEvalTreeTile - 1) / kEvalTreeTile;
+                std::vector<unsigned char> pm(ntl * kEvalTreeTile, 255), gd(ntl * kEvalMetaDepths, 0);       // gd: per tile the walkers' steps, then per walker the steps at which its phases end
+                std::vector<int> idx;
+                for (size_t tl = 0; tl < ntl; tl++) {
+                    const size_t t0 = tl * kEvalTreeTile, tt = std::min<size_t>(kEvalTreeTile, nt - t0);
+                    idx.resize(tt);
+                    for (size_t q = 0; q < tt; q++) idx[q] = (int)q;
+                    std::stable_sort(idx.begin(), idx.end(), [&](int a2, int b2) { return tdepth[t0 + a2] > tdepth[t0 + b2]; });
+                    // The sorted trees are dealt ROUND the walkers (walker p: ranks p, p + 4, p + 8, ..; deepest first inside a walker as the phases need it): every
+                    // walker spans the tile's whole range of depths, so its chains drop out early and the four walkers reach the tile's barrier together.
+                    // With eight consecutive ranks each (rounds 4 - 5, RLHIP_EVAL_DEAL=0) walker 0 held the eight deepest trees -- little to drop, and the others
+                    // waited for it: 28.2 against 28.8 M docs/s (profiles/r06w_ab_infer_phased_walk.txt).
+                    if (m->knobs.deal && tt == (size_t)kEvalTreeTile) {
+                        std::vector<int> rr(tt);
+                        for (size_t q = 0; q < tt; q++) rr[(q % kEvalParts) * kEvalPer + q / kEvalParts] = idx[q];
+                        idx = rr;
+                    }
+                    for (size_t q = 0; q < tt; q++) {
+                        pm[tl * kEvalTreeTile + q] = (unsigned char)idx[q];
+                        unsigned char &g = gd[tl * kEvalMetaDepths + q / kEvalPer];
+                        g = std::max<unsigned char>(g, (unsigned char)std::max(tdepth[t0 + idx[q]], 1));      // (a single-leaf tree still stores its output: one step)
+                    }
+                    // a phase of n chains ends when the walker's (n' + 1)-th tree (n' = the next phase's chains) is done: that tree's depth.  A walker with fewer
+                    // trees: 0 (the phase is skipped).  RLHIP_EVAL_PHASED=0: every phase runs to the walker's full depth (one loop, rounds 4 - 5).
+                    const int next_ch[3] = {kEvalPhases >= 2 ? kEvalPh1 : kEvalPhLast, kEvalPhases >= 3 ? kEvalPh2 : kEvalPhLast, kEvalPhLast};
+                    for (int p = 0; p < kEvalParts; p++)
+                        for (int ph = 0; ph < kEvalPhases; ph++) {
+                            const size_t q = (size_t)p * kEvalPer + next_ch[ph];
+                            unsigned char &e = gd[tl * kEvalMetaDepths + kEvalParts + p * kEvalPhases + ph];
+                            e = !m->knobs.phased ? gd[tl * kEvalMetaDepths + p] : (q < tt ? (unsigned char)std::max(tdepth[t0 + idx[q]], 1) : 0);
+                        }
+                }
+                RL_HIP(m->pool.alloc(&m->d_perm, pm.size())); RL_HIP(m->pool.alloc(&m->d_gdepth, gd.size()));
+                RL_HIP(hipMemcpy(m->d_perm, pm.data(), pm.size(), hipMemcpyHostToDevice));
+                RL_HIP(hipMemcpy(m->d_gdepth, gd.data(), gd.size(), hipMemcpyHostToDevice));
+                RL_HIP(m->pool.alloc(&m->d_pack, en));
+                RL_HIP(hipMemcpy(m->d_pack, pk.data(), en * 8, hipMemcpyHostToDevice));
+                RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            }
+        }
+    }
+    *out = m.release();
+    return RL_OK;
+}
+
+void rl_model_destroy(rl_model *m)
+{
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    delete m;
+}
+
+int rl_model_num_trees(const rl_model *m, int32_t *n)
+{
+    if (!m) return fail(RL_ERR_INVALID, "null model");
+    if (n) *n = (int32_t)m->trees.size();
+    return RL_OK;
+}
+
+int rl_model_features(const rl_model *m, int32_t *ids, int32_t cap, int32_t *n)
+{
+    if (!m) return fail(RL_ERR_INVALID, "null model");
+    if (n) *n = (int32_t)m->features.size();
+    if (ids) for (int i = 0; i < cap && i < (int)m->features.size(); i++) ids[i] = m->features[i];
+    return RL_OK;
+}
+
+static int model_eval_launch(rl_model *m, const float *dX, int64_t n_docs, int32_t row_stride, float *dO, hipStream_t s)
+{
+    const int cols = std::max(row_stride, m->maxcol + 1);
+    const size_t lds = eval_tiled_lds(cols, m->maxn);
+    if (m->d_pack && lds <= (size_t)160 * 1024 && !m->knobs.generic) {
+        const int64_t tiles = (n_docs + kEvalDocs - 1) / kEvalDocs;
+        hipLaunchKernelGGL(k_model_eval_tiled, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256)), dim3(kEvalThreads), lds, s,
+                           (const unsigned long long *)m->d_pack, (const float *)m->d_w, m->maxn, (int)m->trees.size(), dX, n_docs, row_stride, cols, dO,
+                           (const unsigned char *)m->d_perm, (const unsigned char *)m->d_gdepth);
+    } else {
+        hipLaunchKernelGGL(k_model_eval, dim3((unsigned)std::min<int64_t>(8192, (n_docs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, m->ens,
+                           (const float *)m->d_w, m->maxn, (int)m->trees.size(), dX, n_docs, row_stride, dO);
+    }
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+int rl_model_predict(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, float *out)
+{
+    if (!m) return fail(RL_ERR_INVALID, "null model");
+    if (!X || !out || n_docs < 0 || row_stride < 1) return fail(RL_ERR_INVALID, "bad argument");
+    if (n_docs == 0) return RL_OK;
+    RL_HIP(hipSetDevice(m->device));
+    float *dX = nullptr, *dO = nullptr;
+    RL_HIP(hipMalloc((void **)&dX, (size_t)n_docs * row_stride * sizeof(float)));
+    RL_HIP(hipMalloc((void **)&dO, (size_t)n_docs * sizeof(float)));
+    RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
+    int rc = model_eval_launch(m, dX, n_docs, row_stride, dO, 0);
+    if (rc == RL_OK) { RL_HIP(hipDeviceSynchronize()); RL_HIP(hipMemcpy(out, dO, (size_t)n_docs * sizeof(float), hipMemcpyDeviceToHost)); }
+    (void)hipFree(dX); (void)hipFree(dO);
+    return rc;
+}
+
+int rl_model_predict_device(rl_model *m, const float *dX, int64_t n_docs, int32_t row_stride, float *dOut, void *stream)
+{
+    if (!m) return fail(RL_ERR_INVALID, "null model");
+    if (!dX || !dOut || n_docs < 0 || row_stride < 1) return fail(RL_ERR_INVALID, "bad argument");
+    if (n_docs == 0) return RL_OK;
+    RL_HIP(hipSetDevice(m->device));
+    return model_eval_launch(m, dX, n_docs, row_stride, dOut, (hipStream_t)stream);
+}
+
+}  // extern "C"
