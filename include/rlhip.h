@@ -561,6 +561,35 @@ int  rl_lr_debug_times(const rl_lr *r, double *gram_ms, double *solve_ms, double
 int  rl_lr_predict(int32_t device, const int32_t *feature_ids, int32_t n_features, const double *weights, int32_t n_weights, const float *X,
                    int64_t n_docs, int32_t row_stride, double *out);
 
+/* ---- Neural-net models (RankNet -ranker 1, LambdaRank 5, ListNet 7: learning/neuralnet/) ---------------------------------
+ * Scoring only: the forward pass RankNet.eval (RankNet.java:336-349), which LambdaRank and ListNet inherit, with the Java's double
+ * arithmetic kept bit for bit.  Training these rankers is not built.  The network is the one RankNet.wire() (:87-110)
+ * makes: layer 0 holds the n_features inputs and a bias neuron of output 1.0, then come the hidden layers, then one output neuron;
+ * every neuron past layer 0 computes 1.0 / (1.0 + exp(-wsum)) (LogiFunction.java:18-20) of wsum = 0.0, += source.output * weight over
+ * its inLinks in order (Neuron.computeOutput, Neuron.java:68-76): the previous layer's neurons in order, the bias LAST. */
+typedef struct rl_net rl_net;           /* opaque */
+
+/* which kernel the last rl_net_predict / rl_net_predict_device of a handle took (rl_net_debug_path) */
+enum { RL_NET_PATH_NONE = 0, RL_NET_PATH_LDS = 1, RL_NET_PATH_GLOBAL = 2 };
+
+/* feature_ids[k] = the feature ID input neuron k reads (RankNet.java:339-341: p.getFeatureValue(features[k])).  hidden_sizes: the
+ * n_hidden layer sizes (NULL when n_hidden is 0).  weights, in INPUT order: for each layer l = 1 .. n_hidden + 1 a row-major matrix
+ * [n_l][n_{l-1} + 1], row j = the weights of neuron j's inLinks (sources in order, the bias last), n_0 = n_features and the last
+ * n_l = 1 -- not the order of a model file, whose lines follow the outLinks (RankNet.toString :356-372).  The weights are uploaded
+ * once.  A wrong n_weights, n_features < 1 or a layer size < 1 is RL_ERR_INVALID; no gfx950 device is RL_ERR_NO_DEVICE. */
+int  rl_net_create(int32_t device, const int32_t *feature_ids, int32_t n_features, const int32_t *hidden_sizes, int32_t n_hidden,
+                   const double *weights, int32_t n_weights, rl_net **out);
+void rl_net_destroy(rl_net *net);
+/* RankNet.eval (:336-349) of every row: out[i] = the output neuron's output, a double in [0, 1].  X rows as rl_lr_predict's and
+ * rl_model_predict's (column f holds feature ID f); an ID at or beyond row_stride reads 0. */
+int  rl_net_predict(rl_net *net, const float *X, int64_t n_docs, int32_t row_stride, double *out);
+/* The same on device pointers (dX: n_docs * row_stride floats, dOut: n_docs doubles), enqueued on `stream` (a hipStream_t, NULL = the
+ * default stream) without any synchronisation.  Calls on one handle must be ordered by the caller (a network too large for the
+ * LDS kernel keeps its hidden outputs in a scratch of the handle). */
+int  rl_net_predict_device(rl_net *net, const float *dX, int64_t n_docs, int32_t row_stride, double *dOut, void *stream);
+/* debug: RL_NET_PATH_* of the last predict call (Neuron.computeOutput :68-76 is the same arithmetic in both kernels) */
+int  rl_net_debug_path(const rl_net *net, int32_t *path);
+
 #ifdef __cplusplus
 }
 #endif

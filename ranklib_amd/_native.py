@@ -103,6 +103,7 @@ ABI_SYMBOLS = [
     "rl_rb_learn", "rl_rb_get_model", "rl_rb_scores", "rl_rb_trace", "rl_rb_debug_potentials", "rl_rb_predict",
     "rl_lr_params_default", "rl_lr_create", "rl_lr_destroy", "rl_lr_set_train", "rl_lr_set_validation", "rl_lr_set_external_judgments",
     "rl_lr_set_features", "rl_lr_learn", "rl_lr_get_weights", "rl_lr_scores", "rl_lr_debug_gram", "rl_lr_debug_times", "rl_lr_predict",
+    "rl_net_create", "rl_net_destroy", "rl_net_predict", "rl_net_predict_device", "rl_net_debug_path",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -210,6 +211,13 @@ def lib():
         L.rl_lr_debug_gram.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
         L.rl_lr_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
         L.rl_lr_predict.argtypes = [i32, vp, i32, vp, i32, vp, i64, i32, vp]
+    if hasattr(L, "rl_net_create"):
+        L.rl_net_create.argtypes = [i32, vp, i32, vp, i32, vp, i32, C.POINTER(vp)]
+        L.rl_net_destroy.argtypes = [vp]
+        L.rl_net_destroy.restype = None
+        L.rl_net_predict.argtypes = [vp, vp, i64, i32, vp]
+        L.rl_net_predict_device.argtypes = [vp, vp, i64, i32, vp, vp]
+        L.rl_net_debug_path.argtypes = [vp, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -594,6 +602,56 @@ class Model:
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             lib().rl_model_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+NET_PATH_NONE, NET_PATH_LDS, NET_PATH_GLOBAL = 0, 1, 2
+
+
+class NetModel:
+    """A scoring-only neural network on the device (rl_net_*): the forward pass of RankNet, LambdaRank and ListNet models.
+    weights: per layer l = 1 .. len(hidden_sizes) + 1 a row-major [n_l][n_{l-1} + 1] matrix, row j = neuron j's inLinks with the
+    bias last (the input order of include/rlhip.h, not a model file's)."""
+
+    def __init__(self, feature_ids, hidden_sizes, weights, device=0):
+        L = lib()
+        if not hasattr(L, "rl_net_create"):
+            raise RankLibError("rlhip: this librlhip.so has no neural-net scoring (rl_net_*)")
+        fid = np.ascontiguousarray(feature_ids, dtype=np.int32)
+        hid = np.ascontiguousarray(hidden_sizes, dtype=np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        keep = hid if hid.size else np.zeros(1, np.int32)
+        self.h = C.c_void_p()
+        check(L.rl_net_create(int(device), fid.ctypes.data if fid.size else None, fid.size, keep.ctypes.data, hid.size,
+                              w.ctypes.data if w.size else None, w.size, C.byref(self.h)))
+
+    def predict_rows(self, rows):
+        """rows[:, f] holds feature ID f (column 0 unused, like DataPoint.fVals); f64 scores"""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        out = np.zeros(rows.shape[0], np.float64)
+        check(lib().rl_net_predict(self.h, rows.ctypes.data, rows.shape[0], rows.shape[1], out.ctypes.data))
+        return out
+
+    def predict_device(self, dX_ptr, n_docs, row_stride, dOut_ptr, stream=None):
+        """rows (f32) / scores (f64) are device pointers (e.g. torch tensors' data_ptr()); enqueued, not synchronised"""
+        check(lib().rl_net_predict_device(self.h, C.c_void_p(dX_ptr), n_docs, row_stride, C.c_void_p(dOut_ptr),
+                                          C.c_void_p(stream) if stream else None))
+
+    def path(self):
+        """NET_PATH_* of the last predict call: which kernel variant it took"""
+        p = C.c_int32(0)
+        check(lib().rl_net_debug_path(self.h, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            lib().rl_net_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

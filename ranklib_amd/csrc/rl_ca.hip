@@ -523,3 +523,5 @@ int rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weig
 #include "rl_ada.inc"      // AdaRank (-ranker 3): k_ada_weak shares ca_metric and the sets' length classes
 #include "rl_rb.inc"       // RankBoost (-ranker 2): its training lists sorted into getCorrectRanking() order in the context's set
 #include "rl_lr.inc"       // Linear Regression (-ranker 9): k_lr_gram reads the context's column-major training set
+// not a linear ranker, but it shares this unit's device buffers (CaBuf) and build
+#include "rl_net.inc"      // RankNet / LambdaRank / ListNet models (-ranker 1 / 5 / 7): the forward pass, scoring only

@@ -3,6 +3,9 @@ Forests, Coordinate Ascent, AdaRank, RankBoost and Linear Regression (:230-377) 
 
     python -m ranklib_amd.evaluator -train f -ranker 6 -metric2t NDCG@10 -tree 1000 -leaf 31 -save model.txt
     python -m ranklib_amd.evaluator -load model.txt -rank f -score out.txt
+
+-load also takes the model files of the neural-net rankers (## RankNet, ## LambdaRank, ## ListNet: learning/neuralnet/) for -test, -rank
+-score / -indri, -idv, -norm and -qrel; they are scored on the GPU, -train with -ranker 1 / 5 / 7 stays refused.
 """
 import logging
 import math
@@ -11,7 +14,7 @@ import sys
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
                        stable_desc_order)
 from .metric import ERRScorer, MetricScorerFactory
 
@@ -202,7 +205,8 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
         print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
-              "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f] [-rank f -indri out] [-score out]")
+              "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
+              "(-load also reads RankNet, LambdaRank and ListNet models; they are scored, not trained)")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
     Evaluator.mustHaveRelDoc = False
@@ -280,7 +284,7 @@ def main(argv=None):
             # parameters of the other rankers / of flows that are out of scope: parsed (the reference's own test passes
             # -round -epoch to every ranker, test:eval/EvaluatorTest.java:207-220) and ignored
             nxt()
-        elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = int(nxt())
+        elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = RankNet.device = int(nxt())
         else:
             raise RankLibError("Unknown command-line parameter: " + args[i])     # :369-371 (incl. the documented -silent)
         i += 1

@@ -10,6 +10,8 @@ RankLib's API read the same here:
     CoorAscent                   learning/CoorAscent.java:33-396        (learn and eval run on the GPU through librlhip.so)
     AdaRank                      learning/boosting/AdaRank.java:33-346  (learn and eval run on the GPU through librlhip.so)
     LinearRegRank                learning/LinearRegRank.java:23-240     (learn and eval run on the GPU through librlhip.so)
+    RankNet / LambdaRank / ListNet   learning/neuralnet/RankNet.java:33-490, LambdaRank.java, ListNet.java:24-236
+                                 (model text in and out, eval on the GPU through librlhip.so; training is not built)
     RankerType / RankerFactory   learning/RankerType.java, learning/RankerFactory.java:36-118
     RankerTrainer                learning/RankerTrainer.java:23-56
 
@@ -1152,6 +1154,196 @@ class LinearRegRank(_LinearRanker):
         return "Linear Regression"
 
 
+def _neural_refusal(type_name):
+    """what createRanker, init() and learn() say about RANKNET, LAMBDARANK and LISTNET: they load and score, they do not train"""
+    return ("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank), 2 (RankBoost) and "
+            "9 (Linear Regression); %s, one of the neural-net rankers, is out of scope (SURVEY.md 8)" % type_name)
+
+
+def _java_int(tok):
+    """Integer.parseInt: an optional sign and decimal digits, nothing else, within 32 bits"""
+    body = tok[1:] if tok[:1] in ("+", "-") else tok
+    if not body or not body.isascii() or not body.isdigit():
+        raise ValueError('For input string: "%s"' % tok)
+    v = int(tok)
+    if not -(1 << 31) <= v < (1 << 31):
+        raise ValueError('For input string: "%s"' % tok)
+    return v
+
+
+class RankNet(Ranker):
+    """learning/neuralnet/RankNet.java as a scoring-only ranker: loadFromString (:400-448), eval (:336-349) on an MI355X (librlhip.so
+    rl_net_*) and model() / toString() (:356-398).  The network is the one wire() (:87-110) makes: layer 0 = the inputs and a bias neuron,
+    then the hidden layers, then one output neuron.  self.weights[l - 1] is layer l's matrix [n_l][n_{l-1} + 1]: row j = the weights of
+    neuron j's inLinks (the previous layer's neurons in order, the bias last), the order eval() sums in.  A model file lists the weights by
+    outLinks instead: input and hidden neurons feed the next layer's neurons in order, the bias neuron (line "0 F") every neuron of layer
+    1, then of layer 2, ..., then the output neuron.  init() and learn() are refused: training is not built."""
+    # process-global parameters, like the Java statics (:37-40); only nIteration is used here (the "## Epochs" line of model())
+    nIteration = 100
+    nHiddenLayer = 1
+    nHiddenNodePerLayer = 10
+    learningRate = 0.00005
+    device = 0
+    _TYPE = "RANKNET"
+    _LOAD = "RankNet"                 # the class whose loadFromString runs: LambdaRank inherits RankNet's, ListNet has its own copy
+
+    def __init__(self, samples=None, features=None, scorer=None):
+        super().__init__(samples, features, scorer)
+        self.hidden = []              # sizes of the hidden layers
+        self.weights = []             # per layer past the input: np.float64 [n_l][n_{l-1} + 1]
+        self._net = None
+
+    def init(self):
+        raise RankLibError(_neural_refusal(self._TYPE))
+
+    def learn(self):
+        raise RankLibError(_neural_refusal(self._TYPE))
+
+    # --- the network's shape --------------------------------------------------------------------------------
+    def _sizes(self):
+        """neurons per layer as eval() sees them: the inputs (without the bias), the hidden layers, the output neuron"""
+        return [len(self.features)] + list(self.hidden) + [1]
+
+    @staticmethod
+    def _out_links(n, layer, neuron):
+        """[(target layer, target neuron)] of a neuron's outLinks in wire()'s order, n = _sizes(); layer 0 has the bias at index n[0]"""
+        if layer == 0 and neuron == n[0]:
+            return [(l, j) for l in range(1, len(n)) for j in range(n[l])]
+        return [(layer + 1, j) for j in range(n[layer + 1])]
+
+    @staticmethod
+    def _in_index(n, layer, neuron, target_layer):
+        """where the synapse from (layer, neuron) sits among its target's inLinks: the bias is every neuron's last source"""
+        return n[target_layer - 1] if (layer == 0 and neuron == n[0]) else neuron
+
+    # --- scoring: the forward pass in f64 on the GPU (rl_net_predict) ---------------------------------------
+    def _model(self):
+        if self._net is None:
+            flat = np.concatenate([w.ravel() for w in self.weights])
+            self._net = N.NetModel(self.features, self.hidden, flat, type(self).device)
+        return self._net
+
+    def evalList(self, rl):
+        if rl.size() == 0:
+            return []
+        net = self._model()
+        return [float(v) for v in net.predict_rows(_linear_rows(rl.rl, self.features))]
+
+    def eval(self, dp):               # noqa: A003  :336-349
+        return self.evalList(RankList([dp]))[0]
+
+    def createNew(self):
+        return type(self)()
+
+    # --- model text -----------------------------------------------------------------------------------------
+    def toString(self):               # :356-372: "layer neuron w0 w1 ..." per neuron of every layer but the last, by outLinks
+        n = self._sizes()
+        out = []
+        for i in range(len(n) - 1):
+            for j in range(n[i] + (1 if i == 0 else 0)):
+                ws = " ".join(java_double_str(self.weights[tl - 1][tj, self._in_index(n, i, j, tl)]) for tl, tj in self._out_links(n, i, j))
+                out.append("%d %d %s\n" % (i, j, ws))
+        return "".join(out)
+
+    def model(self):                  # :374-398
+        out = "## " + self.name() + "\n"
+        out += "## Epochs = %d\n" % type(self).nIteration
+        out += "## No. of features = %d\n" % len(self.features)
+        out += "## No. of hidden layers = %d\n" % len(self.hidden)
+        for i, sz in enumerate(self.hidden):
+            out += "## Layer %d: %d neurons\n" % (i + 1, sz)
+        out += " ".join(str(f) for f in self.features) + "\n"
+        out += "%d\n" % len(self.hidden)
+        for sz in self.hidden:
+            out += "%d\n" % sz
+        return out + self.toString()
+
+    def loadFromString(self, fullText):   # :400-448 (ListNet.java:176-224 is the same text with another message)
+        try:
+            lines = []
+            for content in fullText.splitlines():
+                content = content.strip()
+                if not content or content.startswith("##"):
+                    continue
+                lines.append(content)
+            features = [_java_int(t) for t in lines[0].split(" ")]
+            nhl = _java_int(lines[1])
+            if nhl < 0:
+                raise ValueError("NegativeArraySizeException: %d" % nhl)
+            hidden = [_java_int(lines[2 + k]) for k in range(nhl)]
+            for k, sz in enumerate(hidden):
+                if sz < 1:
+                    raise ValueError("hidden layer %d has %d neurons: a layer without a neuron is not reproduced" % (k + 1, sz))
+            n = [len(features)] + hidden + [1]
+            weights = [np.zeros((n[l], n[l - 1] + 1), np.float64) for l in range(1, len(n))]
+            seen = set()
+            for line in lines[2 + nhl:]:
+                s = line.split(" ")
+                iLayer, iNeuron = _java_int(s[0]), _java_int(s[1])
+                count = n[iLayer] + (1 if iLayer == 0 else 0) if 0 <= iLayer < len(n) else -1
+                if not 0 <= iNeuron < count:
+                    raise IndexError("no neuron %d in layer %d" % (iNeuron, iLayer))
+                if iLayer == len(n) - 1:
+                    continue          # the output neuron has no outLinks: nothing is read from its line
+                for k, (tl, tj) in enumerate(self._out_links(n, iLayer, iNeuron)):      # tokens beyond the outLinks are ignored
+                    if k + 2 >= len(s):
+                        raise IndexError("Index %d out of bounds for length %d" % (k + 2, len(s)))
+                    weights[tl - 1][tj, self._in_index(n, iLayer, iNeuron, tl)] = float(s[k + 2])      # a later line of the same neuron wins
+                seen.add((iLayer, iNeuron))
+            for i in range(len(n) - 1):
+                for j in range(n[i] + (1 if i == 0 else 0)):
+                    if (i, j) not in seen:
+                        raise ValueError("no weight line for neuron %d of layer %d: the Java would keep its random initial weights, "
+                                         "not reproduced" % (j, i))
+            self.features, self.hidden, self.weights, self._net = features, hidden, weights, None
+        except Exception as ex:       # noqa: BLE001 -- the reference wraps everything
+            raise RankLibError("Error in %s::load(): %s" % (self._LOAD, ex))
+
+    def printParameters(self):        # :450-456
+        cls = type(self)
+        logger.info("No. of epochs: %d", cls.nIteration)
+        logger.info("No. of hidden layers: %d", cls.nHiddenLayer)
+        logger.info("No. of hidden nodes per layer: %d", cls.nHiddenNodePerLayer)
+        logger.info("Learning rate: %s", java_double_str(cls.learningRate))
+
+    def name(self):
+        return "RankNet"
+
+
+class LambdaRank(RankNet):
+    """learning/neuralnet/LambdaRank.java: RankNet's network, model text and eval; only training differs, and that is not built."""
+    _TYPE = "LAMBDARANK"
+
+    def name(self):                   # :136-138
+        return "LambdaRank"
+
+
+class ListNet(RankNet):
+    """learning/neuralnet/ListNet.java: RankNet's eval (:143-145) and toString; its own statics, a shorter model() header (:157-174) and
+    its own message in loadFromString (:176-224), which reads hidden layers although ListNet.learn never makes any."""
+    nIteration = 1500                 # :29-31
+    learningRate = 0.00001
+    nHiddenLayer = 0
+    _TYPE = "LISTNET"
+    _LOAD = "ListNet"
+
+    def model(self):                  # :157-174: no "hidden layers" lines, and a literal 0 whatever the network is
+        out = "## " + self.name() + "\n"
+        out += "## Epochs = %d\n" % type(self).nIteration
+        out += "## No. of features = %d\n" % len(self.features)
+        out += " ".join(str(f) for f in self.features) + "\n"
+        out += "0\n"
+        return out + self.toString()
+
+    def printParameters(self):        # :226-230
+        cls = type(self)
+        logger.info("No. of epochs: %d", cls.nIteration)
+        logger.info("Learning rate: %s", java_double_str(cls.learningRate))
+
+    def name(self):
+        return "ListNet"
+
+
 # ---------------------------------------------------------------------------------------------------------
 class RankerType(enum.Enum):          # learning/RankerType.java
     MART = 0
@@ -1175,7 +1367,9 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
                     "RANKBOOST": RankBoost, "LINEAR_REGRESSION": LinearRegRank}
         self.names = {"LAMBDAMART": "LAMBDAMART", "MART": "MART", "RANDOM FORESTS": "RANDOM_FOREST",
                       "COORDINATE ASCENT": "COOR_ASCENT", "ADARANK": "ADARANK", "RANKBOOST": "RANKBOOST",
-                      "LINEAR REGRESSION": "LINEAR_REGRESSION"}     # name().toUpperCase() -> type (:44-53)
+                      "LINEAR REGRESSION": "LINEAR_REGRESSION",
+                      "RANKNET": "RANKNET", "LAMBDARANK": "LAMBDARANK", "LISTNET": "LISTNET"}     # name().toUpperCase() -> type (:44-53)
+        self.loadOnly = {"RANKNET": RankNet, "LAMBDARANK": LambdaRank, "LISTNET": ListNet}       # loaded and scored, not trained
 
     def createRanker(self, rtype, samples=None, features=None, scorer=None):
         if isinstance(rtype, str):
@@ -1184,8 +1378,7 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
             except KeyError:
                 raise RankLibError("Could find the class \"%s\" you specified. Make sure the jar library is in your classpath." % rtype)
         if rtype.name not in self.map:
-            raise RankLibError("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank), 2 (RankBoost) and "
-                               "9 (Linear Regression); %s, one of the neural-net rankers, is out of scope (SURVEY.md 8)" % rtype.name)
+            raise RankLibError(_neural_refusal(rtype.name))
         r = self.map[rtype.name]()
         if samples is not None:
             r.setTrainingSet(samples)
@@ -1198,8 +1391,9 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
         name = first.replace("## ", "").strip()
         if name.upper() not in self.names:
             raise RankLibError("Model file does not start with '## LambdaMART', '## MART', '## Random Forests', '## Coordinate Ascent', '## AdaRank', "
-                               "'## RankBoost' or '## Linear Regression' (got %r)" % first)
-        r = self.createRanker(RankerType[self.names[name.upper()]])
+                               "'## RankBoost', '## Linear Regression', '## RankNet', '## LambdaRank' or '## ListNet' (got %r)" % first)
+        tname = self.names[name.upper()]
+        r = self.loadOnly[tname]() if tname in self.loadOnly else self.createRanker(RankerType[tname])      # createRanker refuses the three
         r.loadFromString(fullText)
         return r
 
