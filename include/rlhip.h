@@ -195,6 +195,9 @@ int rl_predict(rl_trainer *t, const float *X, int64_t n_docs, float *out);
 /* Writes LambdaMART.model() into buf (NUL-terminated).  Returns RL_OK and *needed = bytes required
  * incl. NUL; if cap < *needed nothing is written. */
 int  rl_model_to_text(const rl_trainer *t, char *buf, int64_t cap, int64_t *needed);
+/* Text that Ensemble's constructor would refuse is RL_ERR_INVALID ("Error in Emsemble(xmlRepresentation): ..."), and so is a split whose
+ * feature id is below -1 or does not fit an int: Integer.parseInt refuses the second, and the first indexes before the row when the
+ * Java scores.  A feature id of -1 is a leaf (Split.eval, Split.java:116). */
 int  rl_model_from_text(const char *text, int32_t device, rl_model **out);
 void rl_model_destroy(rl_model *m);
 int  rl_model_num_trees(const rl_model *m, int32_t *n);
@@ -208,6 +211,10 @@ int  rl_model_predict(rl_model *m, const float *X, int64_t n_docs, int32_t row_s
  * loop uses: Ensemble.eval for a batch of rows without the PCIe round trip (eval/Evaluator.java:1076-1094 does the
  * same per DataPoint on the CPU). */
 int  rl_model_predict_device(rl_model *m, const float *dX, int64_t n_docs, int32_t row_stride, float *dOut, void *stream);
+/* which kernel the last rl_model_predict / rl_model_predict_device of a handle took (rl_model_debug_path) */
+enum { RL_MODEL_PATH_NONE = 0, RL_MODEL_PATH_TILED = 1, RL_MODEL_PATH_GENERIC = 2 };
+/* debug: RL_MODEL_PATH_* of the last predict call (Split.eval :115-125 and Ensemble.eval :110-116 are the same arithmetic in both kernels) */
+int  rl_model_debug_path(const rl_model *m, int32_t *path);
 
 /* ---- LETOR text (host only) ---------------------------------------------------
  * `label qid:ID fid:val ... # description` lines as learning/DataPoint.java:58-110 and features/FeatureManager.java:199-235 read

@@ -92,7 +92,7 @@ ABI_SYMBOLS = [
     "rl_set_train", "rl_set_validation", "rl_set_rows", "rl_set_external_judgments", "rl_init", "rl_boost_round", "rl_boost_rounds_async", "rl_sync",
     "rl_finish", "rl_num_trees", "rl_get_tree", "rl_get_round_metrics", "rl_best_validation", "rl_predict",
     "rl_model_to_text", "rl_model_from_text", "rl_model_destroy", "rl_model_num_trees", "rl_model_features",
-    "rl_model_predict", "rl_model_predict_device", "rl_dist_unique_id", "rl_dist_init", "rl_dist_init_callback", "rl_dist_stats", "rl_bin_stride", "rl_hist_features", "rl_quant_exponent", "rl_get_array", "rl_debug_exp", "rl_debug_rho", "rl_debug_float_chain",
+    "rl_model_predict", "rl_model_predict_device", "rl_model_debug_path", "rl_dist_unique_id", "rl_dist_init", "rl_dist_init_callback", "rl_dist_stats", "rl_bin_stride", "rl_hist_features", "rl_quant_exponent", "rl_get_array", "rl_debug_exp", "rl_debug_rho", "rl_debug_float_chain",
     "rl_letor_parse", "rl_letor_info", "rl_letor_arrays", "rl_letor_rows", "rl_letor_destroy",
     "rl_get_timing", "rl_reset_timing", "rl_set_timing_flags", "rl_debug_membench", "rl_set_err_max", "rl_tree_capacity",
     "rl_ca_params_default", "rl_ca_create", "rl_ca_destroy", "rl_ca_set_train", "rl_ca_set_validation", "rl_ca_set_external_judgments",
@@ -155,6 +155,8 @@ def lib():
     L.rl_model_features.argtypes = [vp, vp, i32, C.POINTER(i32)]
     L.rl_model_predict.argtypes = [vp, vp, i64, i32, vp]
     L.rl_model_predict_device.argtypes = [vp, vp, i64, i32, vp, vp]
+    if hasattr(L, "rl_model_debug_path"):   # (A/B builds of older sources lack it)
+        L.rl_model_debug_path.argtypes = [vp, C.POINTER(i32)]
     L.rl_dist_unique_id.argtypes = [vp]
     L.rl_dist_init.argtypes = [vp, vp, i32, i32]
     L.rl_dist_stats.argtypes = [vp, vp]
@@ -568,6 +570,9 @@ class Trainer:
             pass
 
 
+MODEL_PATH_NONE, MODEL_PATH_TILED, MODEL_PATH_GENERIC = 0, 1, 2
+
+
 class Model:
     """A scoring-only ensemble loaded from RankLib model text (rl_model_*)."""
 
@@ -598,6 +603,12 @@ class Model:
         """rows / scores are device pointers (e.g. torch tensors' data_ptr()); enqueued, not synchronised"""
         check(lib().rl_model_predict_device(self.h, C.c_void_p(dX_ptr), n_docs, row_stride, C.c_void_p(dOut_ptr),
                                             C.c_void_p(stream) if stream else None))
+
+    def path(self):
+        """MODEL_PATH_* of the last predict call: which kernel it took"""
+        p = C.c_int32(0)
+        check(lib().rl_model_debug_path(self.h, C.byref(p)))
+        return p.value
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

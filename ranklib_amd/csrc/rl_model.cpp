@@ -1,7 +1,9 @@
 // rl_model.cpp -- RankLib <ensemble> model text, written and parsed without a JVM.
 #include "rl_model.h"
 
+#include <cerrno>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -158,8 +160,11 @@ bool parse_split_body(Parser &ps, HostTree &t, int &me)
         std::string v;
         if (!ps.open("feature") || !ps.text_until_close("feature", v)) return false;
         char *end = nullptr;
-        const long fid = strtol(v.c_str(), &end, 10);
-        if (!end || *end != 0 || v.empty()) { ps.err = "bad feature id '" + v + "'"; return false; }
+        errno = 0;
+        const long long fid = strtoll(v.c_str(), &end, 10);
+        // Integer.parseInt refuses what does not fit an int; an id below -1 (-1 is a leaf to Split.eval :116) is an ArrayIndexOutOfBoundsException
+        // in DenseDataPoint.getFeatureValue when the model scores, and would index before the row here
+        if (!end || *end != 0 || v.empty() || errno == ERANGE || fid < -1 || fid > INT32_MAX) { ps.err = "bad feature id '" + v + "'"; return false; }
         t.feature[me] = (int32_t)fid;
         if (!ps.open("threshold") || !ps.text_until_close("threshold", v)) return false;
         float th;

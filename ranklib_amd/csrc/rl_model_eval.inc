@@ -14,6 +14,7 @@ struct rl_model {
     unsigned char *d_gdepth = nullptr;      // [tiles][kEvalParts] deepest leaf among a walker's trees = its lockstep walk length
     int32_t maxcol = 0;                     // largest column any node reads
     EvalKnobs knobs;                        // RLHIP_EVAL_*, read by rl_model_from_text
+    int32_t last_path = RL_MODEL_PATH_NONE; // the kernel the last predict call took (rl_model_debug_path)
 };
 
 namespace rl {
@@ -249,7 +250,7 @@ int rl_model_from_text(const char *text, int32_t device, rl_model **out)
         int maxcol = 0;
         for (int32_t f : m->features) maxcol = std::max(maxcol, f);
         m->maxcol = maxcol;
-        bool ok = nt > 0 && (size_t)m->maxn * 8 < 0x10000 && (size_t)(maxcol + 1) * kEvalDocs * 4 < 0xffff &&
+        bool ok = nt > 0 && (size_t)m->maxn * 8 < 0x10000 && ((size_t)maxcol + 1) * kEvalDocs * 4 < 0xffff &&
                   (size_t)kEvalTreeTile * m->maxn <= (size_t)kEvalThreads * kEvalPrefetch;
         for (int32_t f : m->features) ok = ok && f >= 1;        // column 0 is what a packed leaf reads (no RankLib feature has id 0: learning/DataPoint.java:33)
         if (ok) {
@@ -351,16 +352,18 @@ int rl_model_features(const rl_model *m, int32_t *ids, int32_t cap, int32_t *n)
 
 static int model_eval_launch(rl_model *m, const float *dX, int64_t n_docs, int32_t row_stride, float *dO, hipStream_t s)
 {
-    const int cols = std::max(row_stride, m->maxcol + 1);
+    const int cols = (int)std::min<int64_t>(INT32_MAX, std::max<int64_t>(row_stride, (int64_t)m->maxcol + 1));     // (a feature id may be INT32_MAX)
     const size_t lds = eval_tiled_lds(cols, m->maxn);
     if (m->d_pack && lds <= (size_t)160 * 1024 && !m->knobs.generic) {
         const int64_t tiles = (n_docs + kEvalDocs - 1) / kEvalDocs;
         hipLaunchKernelGGL(k_model_eval_tiled, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256)), dim3(kEvalThreads), lds, s,
                            (const unsigned long long *)m->d_pack, (const float *)m->d_w, m->maxn, (int)m->trees.size(), dX, n_docs, row_stride, cols, dO,
                            (const unsigned char *)m->d_perm, (const unsigned char *)m->d_gdepth);
+        m->last_path = RL_MODEL_PATH_TILED;
     } else {
         hipLaunchKernelGGL(k_model_eval, dim3((unsigned)std::min<int64_t>(8192, (n_docs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, m->ens,
                            (const float *)m->d_w, m->maxn, (int)m->trees.size(), dX, n_docs, row_stride, dO);
+        m->last_path = RL_MODEL_PATH_GENERIC;
     }
     RL_HIP(hipGetLastError());
     return RL_OK;
@@ -389,6 +392,13 @@ int rl_model_predict_device(rl_model *m, const float *dX, int64_t n_docs, int32_
     if (n_docs == 0) return RL_OK;
     RL_HIP(hipSetDevice(m->device));
     return model_eval_launch(m, dX, n_docs, row_stride, dOut, (hipStream_t)stream);
+}
+
+int rl_model_debug_path(const rl_model *m, int32_t *path)
+{
+    if (!m || !path) return fail(RL_ERR_INVALID, "null argument");
+    *path = m->last_path;
+    return RL_OK;
 }
 
 }  // extern "C"

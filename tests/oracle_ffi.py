@@ -313,8 +313,9 @@ def float_chain(x, idx=None):
     return np.float32(lib().ro_float_chain(x.ctypes.data, idx.ctypes.data, len(idx)))
 
 
-def eval_flat_model(trees, rows, n_threads=1, weight=0.1):
-    """trees: list of dicts (feature ids, threshold, left, right, output) in any node order with root 0; rows[:, f] = feature f"""
+def eval_flat_model(trees, rows, n_threads=1, weight=0.1, weights=None):
+    """trees: list of dicts (feature ids, threshold, left, right, output) in any node order with root 0; rows[:, f] = feature f;
+    weights: one per tree (default: `weight` for every tree)"""
     nt = len(trees)
     maxn = max(len(t["feature"]) for t in trees)
     feat = np.full((nt, maxn), -1, np.int32); left = np.zeros((nt, maxn), np.int32); right = np.zeros((nt, maxn), np.int32)
@@ -322,7 +323,8 @@ def eval_flat_model(trees, rows, n_threads=1, weight=0.1):
     for i, t in enumerate(trees):
         n = len(t["feature"])
         feat[i, :n] = t["feature"]; left[i, :n] = t["left"]; right[i, :n] = t["right"]; thr[i, :n] = t["threshold"]; outv[i, :n] = t["output"]
-    w = np.full(nt, weight, np.float32)
+    w = np.full(nt, weight, np.float32) if weights is None else np.ascontiguousarray(weights, np.float32)
+    assert w.shape == (nt,)
     rows = np.ascontiguousarray(rows, np.float32)
     res = np.zeros(rows.shape[0], np.float32)
     lib().ro_eval_flat_model(nt, maxn, feat.ctypes.data, thr.ctypes.data, left.ctypes.data, right.ctypes.data, outv.ctypes.data,
