@@ -678,7 +678,7 @@ static int init_round_state(rl_trainer *t, InitWork &w)
     }
     if (t->dist) {
         // Sharded runs: every rank must enqueue the same collectives, so the way a tree's end is detected has to be the same on
-        // all of them: the progress word (deterministic rule in enqueue_round) only if every rank has one, else the stream
+        // all of them: the progress word (deterministic rule in growth_gate, rl_round.inc) only if every rank has one, else the stream
         // synchronisation at fixed steps.
         int32_t have = c.progress != nullptr ? 1 : 0, *d_have = nullptr;
         RL_HIP(t->pool.alloc(&d_have, (size_t)1));

@@ -2584,7 +2584,7 @@ __device__ __forceinline__ void hist_finish_body(const Ctx &c, int nodes_in_lds,
     __syncthreads();
     if (!sh_last) return;
     // the growth steps' fused kernel carries ONE instantiation of the bookkeeping (node records in LDS: the host takes the two-launch path when
-    // they do not fit, enqueue_round) -- its speed depends on its size: a second inlined copy costs scalar spills and scratch in every block
+    // they do not fit, enqueue_growth_step) -- its speed depends on its size: a second inlined copy costs scalar spills and scratch in every block
     if (!ROOT && !DIST && !JAVA) select_step_t<true>(c, false, (unsigned char *)sh_raw, false);
     else select_step(c, ROOT, (unsigned char *)sh_raw, nodes_in_lds != 0, DIST);
 }

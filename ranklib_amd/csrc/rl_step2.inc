@@ -303,7 +303,7 @@ __global__ __launch_bounds__(kFinThreads) void k_select_root(const Ctx c, int no
 // deviances (:348-350), RegressionTree.fit's loop (:58-87, insert :147-157) as far as prepared nodes allow, the next step's slots -- but
 // laid out for latency: every global load is issued in the first instructions (the per-feature records, ALL node records, the queue, the
 // tree state: nothing depends on anything), three block barriers, cross-lane traffic on the DPP path, the serial part on one wavefront
-// without barriers.  Conditions (enqueue_round): one GPU, default mode (no strict order, no feature sampling), at most 160 histogram
+// without barriers.  Conditions (enqueue_growth_step): one GPU, default mode (no strict order, no feature sampling), at most 160 histogram
 // features (five records per lane of a half wavefront), node records and queue in LDS (<= 62 leaves).
 // ------------------------------------------------------------------------------------------------------------------------------------
 constexpr int kSel2Threads = 64 * kSpec > 256 ? 64 * kSpec : 256;      // one wavefront per slot

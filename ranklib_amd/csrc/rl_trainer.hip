@@ -508,6 +508,90 @@ static int enqueue_leaf_chains_pieces(rl_trainer *t, const ChainSource &src)
     return RL_OK;
 }
 
+// Sharded runs, the leaf-owner exchange (rl_dist.inc): lambda / weight of a leaf's documents go to the leaf's owner rank only, which evaluates the
+// chains over the whole leaf (t->gchain); the 2 L float sums come back to every rank.
+static int enqueue_leaf_chains_owner(rl_trainer *t, const ChainSource &src)
+{
+    Ctx &c = t->ctx;
+    hipStream_t s = t->stream;
+    const ChainBufs &lb = t->leaf_chain;
+    const int R = t->n_ranks, me = t->dist->rank, nseg = std::max(c.L, 2), MS = t->gchain.maxseg;      // -leaf 1 still has two leaves (the root always splits)
+    hipLaunchKernelGGL(k_chain_prefix, dim3((unsigned)((lb.cap_tiles + 3) / 4)), dim3(kThreads), 0, s, lb, src);      // local values in leaf order -> lb.xs
+    int rcd = t->dist->allgather(c.leaf_start, t->d_gls, (size_t)t->lsstride * sizeof(int32_t), s);
+    if (rcd) return rcd;
+    std::vector<int64_t> scount(R), sdispl(R), rcount(R), rdispl(R);
+    const bool dev_plan = t->d_xmail != nullptr && !t->knobs.dist_host_plan && nseg <= kPlanMaxSeg && R <= 64;       // (knobs.dist_host_plan: the host plan behind a stream synchronisation, as until round 5)
+    if (dev_plan) {
+        // the plan on the device; the host only needs the byte counts of the transfers and reads them from a pinned mailbox below, after it has
+        // enqueued the pack kernel (k_plan_exchange)
+        hipLaunchKernelGGL(k_plan_exchange, dim3(1), dim3(64), 0, s, (const int32_t *)t->d_gls, R, t->lsstride, nseg, MS, me, t->d_own, t->d_xtab, t->d_xmail, ++t->xmail_tag);
+    } else {
+        // the send / receive counts of the exchange have to be known to the host: one small copy per round (sharded runs are host-paced anyway)
+        std::vector<int32_t> &gls = t->h_gls;
+        gls.resize((size_t)R * t->lsstride);
+        RL_HIP(hipMemcpyAsync(gls.data(), t->d_gls, gls.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        RL_HIP(hipStreamSynchronize(s));
+        auto len_of = [&](int r, int l) { return (long long)gls[(size_t)r * t->lsstride + l + 1] - gls[(size_t)r * t->lsstride + l]; };
+        std::vector<int32_t> &own = t->h_own; own.assign((size_t)MS, 0);
+        {   // owners: largest leaf first onto the least loaded rank (every rank computes the same map from the same table)
+            std::vector<long long> glen((size_t)nseg, 0), load((size_t)R, 0);
+            std::vector<int32_t> order((size_t)nseg);
+            for (int l = 0; l < nseg; l++) { order[l] = l; for (int r = 0; r < R; r++) glen[l] += len_of(r, l); }
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return glen[a] > glen[b]; });
+            for (int l : order) {
+                if (glen[l] == 0) { own[l] = l % R; continue; }
+                int o = 0;
+                for (int r = 1; r < R; r++) if (load[r] < load[o]) o = r;
+                own[l] = o; load[o] += glen[l];
+            }
+        }
+        std::vector<long long> &tab = t->h_xtab; tab.assign((size_t)MS * (R + 1), 0);       // pack_off [MS] | asm_off [R][MS]
+        long long cur = 0;
+        for (int d = 0; d < R; d++) {
+            sdispl[d] = cur * 8;
+            if (d != me) for (int l = 0; l < nseg; l++) if (own[l] == d) { tab[l] = cur; cur += 2 * len_of(me, l); }       // (own leaves: not packed, k_chain_assemble)
+            scount[d] = cur * 8 - sdispl[d];
+        }
+        cur = 0;
+        for (int r = 0; r < R; r++) {
+            rdispl[r] = cur * 8;
+            if (r != me) for (int l = 0; l < nseg; l++) if (own[l] == me) { tab[(size_t)MS * (1 + r) + l] = cur; cur += 2 * len_of(r, l); }
+            rcount[r] = cur * 8 - rdispl[r];
+        }
+        RL_HIP(hipMemcpyAsync(t->d_own, own.data(), (size_t)MS * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RL_HIP(hipMemcpyAsync(t->d_xtab, tab.data(), tab.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    }
+    const LeafExchange lx{t->d_own, t->d_xtab, t->d_xtab + MS};
+    hipLaunchKernelGGL(k_chain_pack, dim3(nseg, 2, kLeafXferZ), dim3(kThreads), 0, s, (const double *)lb.xs, lb.cap_n, (const int32_t *)c.leaf_start, nseg, lx, t->d_send, me);
+    if (dev_plan) {       // the mailbox: the tag is stored last (release); a device error or a dead peer must end the wait
+        const auto t0w = std::chrono::steady_clock::now();
+        unsigned spins = 0;
+        while (__atomic_load_n(&t->h_xmail[4 * R], __ATOMIC_ACQUIRE) != t->xmail_tag) {
+            if ((++spins & 0xffff) == 0) {
+                const hipError_t q = hipStreamQuery(s);
+                if (q != hipSuccess && q != hipErrorNotReady) return fail(RL_ERR_HIP, std::string("device error before the leaf-owner exchange: ") + hipGetErrorString(q));
+                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0w).count() > t->knobs.dist_timeout_s)
+                    return fail(RL_ERR_COMM, "timed out waiting for the plan of the leaf-owner exchange (a rank of the job is missing from a collective?)");
+            }
+        }
+        for (int r = 0; r < R; r++) { scount[r] = t->h_xmail[r]; sdispl[r] = t->h_xmail[R + r]; rcount[r] = t->h_xmail[2 * R + r]; rdispl[r] = t->h_xmail[3 * R + r]; }
+    }
+    rcd = t->dist->alltoallv(t->d_send, scount.data(), sdispl.data(), t->d_gx, rcount.data(), rdispl.data(), s);
+    if (rcd) return rcd;
+    hipLaunchKernelGGL(k_plan_global, dim3(1), dim3(64), 0, s, (const int32_t *)t->d_gls, R, t->lsstride, nseg, t->gchain, (const int32_t *)t->d_own, me);
+    hipLaunchKernelGGL(k_chain_assemble, dim3(nseg, 2, kLeafXferZ), dim3(kThreads), 0, s, (const double *)t->d_gx, (const int32_t *)t->d_gls, R, t->lsstride, nseg, lx,
+                       t->gchain, me, (const double *)lb.xs, lb.cap_n, (const int32_t *)c.leaf_start);
+    ChainSource gsrc{t->gchain.xs, t->gchain.xs + t->gchain.cap_n, nullptr, nullptr, nullptr, nullptr};
+    enqueue_chain(t, t->gchain, gsrc);
+    if (R > 1) {       // every rank evaluated its own leaves: exchange the 2 L float sums
+        rcd = t->dist->allgather(t->gchain.result, t->d_gres, (size_t)2 * MS * sizeof(float), s);
+        if (rcd) return rcd;
+        hipLaunchKernelGGL(k_chain_pick, dim3((2 * nseg + kThreads - 1) / kThreads), dim3(kThreads), 0, s, (const float *)t->d_gres, R, 2,
+                           MS, nseg, (const int32_t *)t->d_own, t->gchain.result);
+    }
+    return RL_OK;
+}
+
 static void enqueue_metric_mean(rl_trainer *t, const double *ndcg_q, int Q, float *out, hipStream_t s = nullptr)
 {
     if (!s) s = t->stream;
@@ -1015,445 +1099,11 @@ static int resolve_ties(rl_trainer *t, size_t fin_lds, int nodes_in_lds, bool de
     return RL_OK;
 }
 
-static int enqueue_round(rl_trainer *t)
-{
-    Ctx &c = t->ctx;
-    hipStream_t s = t->stream;
-    const int m = t->round;
-    // round scalars
-    RL_HIP(hipMemsetAsync(&c.st->maxabs_bits, 0, sizeof(unsigned long long) + sizeof(long long), s));
-    int n_max = 0;       // blocks that reported their max |lambda| (folded by k_max_reduce)
-    if (c.mart) {    // MART: residuals instead of lambdas (weights stay 0)
-        ScopedTiming tm(t, RL_KERNEL_LAMBDA, (double)c.N * 20.0);
-        n_max = std::min(2048, (c.N + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL(k_mart_residual, dim3(n_max), dim3(kThreads), 0, s, c.labels, (const double *)c.scores, c.lw, c.N, t->d_wmax);
-    } else {   // K1 lambdas: pair terms in parallel, then ordered accumulation (ranked order comes from the previous
-        // round's k_rank_* / from rl_init for round 0)
-        ScopedTiming tm(t, RL_KERNEL_LAMBDA, (double)c.N * 28.0);
-        const double *ideal = (c.metric == RL_METRIC_NDCG) ? (m == 0 ? c.ideal0 : c.ideal1) : nullptr;
-        LamArgs g{t->tr.d_ss, t->tr.d_sl, t->tr.d_srel, t->tr.d_sidx, c.qoff, t->tr.d_docq, ideal, c.disc,
-                  t->d_T, c.lw, &c.st->maxabs_bits, c.N, c.k, c.k, c.metric, t->p.metric_k,
-                  t->tr.d_aux_i, t->tr.d_aux_a, t->tr.d_aux_b, t->d_wmax, t->tr.d_ext_rd};
-        if (t->d_T == nullptr) {
-            const int mode = (c.metric == RL_METRIC_ERR) ? 1 : (c.metric == RL_METRIC_MAP) ? 2 : 0;
-            // knobs.lam_compact: NDCG / DCG pair terms from per-wavefront lists of the active pairs (k_lambda_fused<., 0, true>) instead of column by row.
-            // Built and measured slower at NDCG@10 (profiles/r05i_ab_lambda_c2.txt: a wavefront's ~390 active pairs are 3.05 steps of 128, i.e. 4 against the 5 of
-            // ten rows in pairs, and the lists cost LDS, registers and six ds_bpermute per pair); it is the shorter way from about NDCG@16 on.  Off by default.
-            const bool cp = t->knobs.lam_compact && mode == 0;
-            auto lds_of = [&](int bt) { return (size_t)c.k * (bt + 8) * 16 + (size_t)c.k * 24 + lambda_fused_extra_bytes(mode, c.k, bt) + (cp ? lambda_fused_cp_bytes(c.k, bt) : 0); };
-            n_max = 0;
-            const DataSet &d = t->tr;
-            // (ls: the stream of this class -- the main one, or one of the three side streams forked below)
-            int lam_used = 0;
-            RL_HIP(hipEventRecord(t->ev_lam_fork, s));       // (sharded runs too, round 6: the classes only touch this rank's lists; the collectives follow on the main stream behind the join)
-            auto lam_stream = [&]() -> hipStream_t {
-                const int lam_side = t->knobs.lam_side;      // side streams used (the rest of the classes: the main stream).  One: the widest class beside the
-                // three others in a row on the main stream -- c2 423.1 -> 426.5 rounds/s against three side streams, c1 / c3 / c1ns within their noise
-                // (profiles/r05q_ab_lambda_side_*): the classes fill the chip either way, and a kernel that ends on a side stream is a cross-stream wait
-                if (lam_used >= lam_side) return s;
-                hipStream_t ls = t->lam_s[lam_used++];
-                (void)hipStreamWaitEvent(ls, t->ev_lam_fork, 0);
-                return ls;
-            };
-#define RL_LAUNCH_FUSED(BT, cls)                                                                                                             \
-            if (d.n_qcls[cls] > 0) {                                                                                                         \
-                hipStream_t ls = lam_stream();                                                                                               \
-                if (cp) hipLaunchKernelGGL((k_lambda_fused<BT, 0, true>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
-                else if (mode == 0) hipLaunchKernelGGL((k_lambda_fused<BT, 0>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
-                else if (mode == 1) hipLaunchKernelGGL((k_lambda_fused<BT, 1>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
-                else hipLaunchKernelGGL((k_lambda_fused<BT, 2>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
-                n_max += d.n_qcls[cls]; g.blockmax = t->d_wmax + n_max;                                                                      \
-            }
-            if (d.n_qcls[4] > 0 && mode == 0) {
-                const int nb = (d.n_qcls[4] + kLambdaTinyGroups - 1) / kLambdaTinyGroups;
-                hipLaunchKernelGGL(k_lambda_tiny, dim3(nb), dim3(kLambdaTinyDocs * kLambdaTinyGroups),
-                                   (size_t)kLambdaTinyGroups * lambda_tiny_group_bytes(c.k), s, g, (const int *)d.d_qcls[4], d.n_qcls[4]);
-                n_max += nb; g.blockmax = t->d_wmax + n_max;
-            } else {
-                // ERR / MAP: the lists of at most 16 documents take the block-per-query kernel too -- on the main stream: the side stream is for the
-                // widest class below (the first class launched used to take it)
-                const int keep = lam_used; lam_used = 1 << 20;
-                RL_LAUNCH_FUSED(64, 4)
-                lam_used = keep;
-            }
-            // longest lists first on the side streams (they take longest per block), the shortest class last on the main stream
-            RL_LAUNCH_FUSED(256, 3)
-            RL_LAUNCH_FUSED(192, 2)
-            RL_LAUNCH_FUSED(128, 1)
-            RL_LAUNCH_FUSED(64, 0)
-#undef RL_LAUNCH_FUSED
-            for (int i = 0; i < lam_used; i++) { RL_HIP(hipEventRecord(t->ev_lam_join[i], t->lam_s[i])); RL_HIP(hipStreamWaitEvent(s, t->ev_lam_join[i], 0)); }
-        } else {
-            const unsigned nb = (unsigned)((c.N + kThreads - 1) / kThreads);
-            hipLaunchKernelGGL(k_pair_terms, dim3(nb), dim3(kThreads), 0, s, g);
-            hipLaunchKernelGGL(k_lambda_acc, dim3(nb), dim3(kThreads), 0, s, g);
-            n_max = (int)nb;
-        }
-    }
-    hipLaunchKernelGGL(k_max_reduce, dim3((unsigned)std::max(1, std::min(16, (n_max + 4095) / 4096))), dim3(1024), 0, s, (const double *)t->d_wmax, n_max, &c.st->maxabs_bits);
-    if (t->dist) { int rcd = t->dist->allreduce(&c.st->maxabs_bits, 1, DT_U64, OP_MAX, s); if (rcd) return rcd; }
-    // The plain one-GPU root pass makes the fixed-point lambdas itself (k_hist<.., FQ>): one pass over the documents and one launch less a round.
-    // Sharded, strict-order and sparse-column runs (their kernels between here and the root pass read q) and a regrown tree (q exists) keep k_quantize.
-    bool root_quant_fused = t->knobs.fused_quant && !c.java && !c.sp_on && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs;       // (sharded runs too, round 6: max |lambda| is all-reduced before this point, nothing between here and the root pass reads q)
-    if (!root_quant_fused) hipLaunchKernelGGL(k_quantize, dim3(std::min(2048, (c.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, c);
-    const size_t hist_lds = (size_t)c.sub * ((c.sub == 16 && c.TS <= kHistLdsStride) ? kHistLdsStride : c.TS) * 12;    // int64 sums + int32 counts
-    const int hist_gx = c.numFG * (kHistFG / c.sub);
-    const size_t red_lds = (size_t)c.TS * 20;
-    const int rootCs = std::min(kChunk, std::max(kMinChunk, (((c.N + 63) / 64 + 255) & ~255)));   // == chunk_docs<true>(N)
-    const int rootChunks = (c.N + rootCs - 1) / rootCs;
-    // (a tree is grown a second time, from its root histogram, when the deferred tie-break finds that a tie over several features it took for one
-    // cut is not one -- rl_tie.inc, k_tie_verify; nothing a round keeps has been written by then)
-    const int tie_mode = c.tie_on;
-    struct TieModeRestore { Ctx &c; int v; ~TieModeRestore() { c.tie_on = v; } } tie_mode_restore{c, tie_mode};
-  regrow:
-    {   // K2 root histogram: dense groups from their 32-byte rows, groups of sparse columns from their entry lists (rl_csc.inc)
-        const double root_bytes = c.sp_on ? (double)c.N * ((double)(c.numFG - c.sp_ngroups) * kHistFG * 2.0 + 8.0) + (double)t->sp_entries * 4.0
-                                          : (double)c.N * ((double)c.F * 2.0 + 8.0);
-        ScopedTiming tm(t, RL_KERNEL_HIST_ROOT, root_bytes);
-        launch_hist<true>(c, t->knobs, hist_gx, rootChunks, hist_lds, s, root_quant_fused);
-        root_quant_fused = false;        // (a regrown tree reads the q / r this pass has stored)
-        if (c.sp_on) {
-            hipLaunchKernelGGL(k_hist_sp<kHistLdsStride>, dim3(c.sp_ngroups, rootChunks), dim3(kSpThreads), (size_t)kHistFG * kHistLdsStride * 8, s, c, rootCs);
-        }
-    }
-    // the last block of k_hist_finish runs the growth bookkeeping (select_step); node records live in LDS when they fit
-    const int nodes_in_lds = (select_lds_bytes(c.L, c.NC, true, c.F, c.fs_on != 0) <= 60 * 1024) ? 1 : 0;
-    const size_t par_lds = (c.TS <= kParCacheTS) ? (size_t)c.TS * 20 + 8 : 0;       // the parent's entries next to the bins (hist_finish_body)
-    const size_t fin_lds = std::max((size_t)c.TS * (c.java ? 28 : 20) + 8 + par_lds, select_lds_bytes(c.L, c.NC, nodes_in_lds != 0, c.F, c.fs_on != 0));      // bins + the parent's entries (hist_finish_body)
-    const int jbg = (c.TS + 63) / 64;        // RL_FLAG_JAVA_ORDER: 64-bin groups of k_jhist (+ 1 block for the node totals)
-    if (fin_lds > 128 * 1024) return fail(RL_ERR_UNSUPPORTED, "too many features / leaves for the growth bookkeeping in LDS (feature sampling needs 64 bytes per feature)");
-    if (t->dist) {
-        hipLaunchKernelGGL(k_hist_reduce, dim3(c.F), dim3(kFinThreads), red_lds, s, c, 1);
-        int rcd = t->dist->allreduce(c.dist_buf, (size_t)c.F * c.TS * c.limb_words + 4, DT_I64, OP_SUM, s);
-        if (rcd) return rcd;
-        hipLaunchKernelGGL((k_hist_finish<true, true>), dim3(c.F), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-    } else if (c.java) {
-        hipLaunchKernelGGL(k_jgather, dim3((c.N + kPartTile - 1) / kPartTile), dim3(kThreads), 0, s, c, 1);
-        if (c.jmap) hipLaunchKernelGGL(k_jhist2, dim3(c.n_live + 1, 1), dim3(kJ2Threads), 0, s, c, 1, c.jmap, c.jinv, c.jone);
-        else hipLaunchKernelGGL(k_jhist, dim3(c.n_live, jbg + 2, 1), dim3(64), 0, s, c, 1, jbg);
-        hipLaunchKernelGGL((k_hist_finish<true, false, true>), dim3(c.n_live), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-    } else if (t->knobs.step2 && c.TS <= kFin2MaxT) {       // rl_step2.inc
-        hipLaunchKernelGGL(k_fin2_root, dim3(c.n_live), dim3(kFin2RootThreads), 0, s, c, rootChunks);
-        hipLaunchKernelGGL(k_select_root, dim3(1), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-    } else hipLaunchKernelGGL((k_hist_finish<true, false>), dim3(c.n_live), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-    // Growth steps: each prepares up to kSpec queue nodes and commits as many splits as the fit loop allows; L-1 steps
-    // always suffice (every step commits at least the head of the queue); finished trees make the rest no-ops.
-    const int steps = std::max(c.L - 1, 1);
-    const size_t slot_words = (size_t)c.F * c.TS * c.limb_words + 4;
-    t->tree_seq++;
-    bool throttle = c.progress != nullptr;
-    // lazy tie-break (rl_tie.inc): the device may STALL the tree (no slots, progress word bit 31) until resolve_ties has run.  Growth kernels
-    // enqueued meanwhile are no-ops; afterwards the host carries on from the device's own step count.  `extra`: the stalled select_step call and
-    // its resumption count as steps of the device without committing a split.
-    const auto stalled = [&](unsigned long long w) { return c.tie_on && (w >> 32) == t->tree_seq && ((w >> 31) & 1ull); };
-    bool defer_seen = false;       // the finished tree holds nodes whose stored threshold awaits the batched tie-break (progress word bit 30)
-    int extra = 0, it = 0;
-    bool saw_end = false;
-    auto after_stall = [&](bool &ended) -> int {        // stream idle, tree stalled: resolve, then continue at the device's step
-        int rcs = resolve_ties(t, fin_lds, nodes_in_lds);
-        if (rcs) return rcs;
-        extra += 2;
-        if (c.progress) {       // resolve_ties waited for k_tie_finish, whose select_step left (step, done, deferred ties) in the pinned progress word
-            const unsigned long long w = __atomic_load_n(t->h_progress, __ATOMIC_ACQUIRE);
-            if ((w >> 32) != t->tree_seq) return fail(RL_ERR_STATE, "tie-break: the progress word is not this tree's (internal error)");
-            ended = (w & 1ull) != 0;
-            if (ended) defer_seen = ((w >> 30) & 1ull) != 0;
-            it = (int)((unsigned)(w & 0x3fffffffull) >> 1);
-            return RL_OK;
-        }
-        TreeState sth;
-        RL_HIP(hipMemcpy(&sth, c.st, sizeof(sth), hipMemcpyDeviceToHost));
-        ended = sth.done != 0;
-        if (ended) defer_seen = sth.defer_any != 0;
-        it = sth.step;
-        return RL_OK;
-    };
-  grow:
-    for (; it < steps + extra; it++) {
-        if (throttle && c.tie_on && !t->dist) {
-            const unsigned long long w0 = __atomic_load_n(t->h_progress, __ATOMIC_ACQUIRE);
-            if (stalled(w0)) {       // (resolve_ties reads the tree state through the stream: no drain of its own needed here)
-                bool ended = false;
-                int rcs = after_stall(ended);
-                if (rcs) return rcs;
-                if (ended) { saw_end = true; break; }
-                it--;
-                continue;
-            }
-        }
-        const int ahead = t->dist ? t->knobs.dist_ahead : t->knobs.step_ahead;
-        if (throttle && it >= ahead) {
-            // wait (bounded) until growth step it - step_ahead has been selected, then look at the tree's done flag.  Purely a
-            // scheduling hint: on a timeout the remaining steps are enqueued blindly, which is always correct.
-            const unsigned long long want = ((unsigned long long)t->tree_seq << 32) | ((unsigned long long)(unsigned)(it - ahead) << 1);
-            const auto finished = [&](unsigned long long w) { return (w >> 32) == t->tree_seq && (w & 1); };
-            unsigned long long w = __atomic_load_n(t->h_progress, __ATOMIC_ACQUIRE);
-            if (t->dist) {
-                // Deterministic over the ranks (they grow the same tree): wait -- without a timeout -- until growth step
-                // it - step_ahead has been selected or the tree is finished, and stop only if the tree was finished by a step
-                // <= it - step_ahead.  The word keeps (step at which `done` was set, done) once the tree is finished, so a rank
-                // that looks early and one that looks late take the same decision at the same `it`.
-                unsigned spins = 0;
-                const auto t0w = std::chrono::steady_clock::now();
-                while ((w & ~(3ull << 30)) < want && !finished(w) && !stalled(w)) {       // (bits 30 / 31 of the low word are flags)
-                    w = __atomic_load_n(t->h_progress, __ATOMIC_ACQUIRE);
-                    if ((++spins & 0xfffff) == 0) {
-                        const hipError_t q = hipStreamQuery(s);
-                        if (q != hipSuccess && q != hipErrorNotReady) return fail(RL_ERR_HIP, std::string("device error while growing a tree: ") + hipGetErrorString(q));
-                        // the wait ends when THIS rank's device finishes a growth step, which needs every other rank's share of the step's
-                        // collective: a rank that died or fell behind for good must surface as an error here, not as a hang
-                        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0w).count() > t->knobs.dist_timeout_s)
-                            return fail(RL_ERR_COMM, "timed out after " + std::to_string((int)t->knobs.dist_timeout_s) + " s waiting for growth step " + std::to_string(it - ahead) +
-                                                     " of tree " + std::to_string(t->tree_seq) + " (a rank of the job is missing from a collective?)");
-                    }
-                }
-                const int step_w = (int)((unsigned)(w & 0x3fffffffull) >> 1);
-                if (finished(w) && step_w <= it - ahead) { saw_end = true; defer_seen = ((w >> 30) & 1ull) != 0; break; }
-                // a stalled tree (rl_tie.inc): the word keeps the step at which it stalled, so -- as for the end of the tree -- every rank acts on
-                // it at the same `it`, after the same number of (empty) steps and their collectives
-                if (stalled(w) && step_w <= it - ahead) {
-                    bool ended = false;
-                    int rcs = after_stall(ended);
-                    if (rcs) return rcs;
-                    if (ended) { saw_end = true; break; }
-                    it--;
-                    continue;
-                }
-            } else {
-                // (bits 30 / 31 of the low word are flags: the step is compared field by field)
-                const auto behind = [&](unsigned long long v) {
-                    if ((v >> 32) != t->tree_seq) return true;                   // still the previous tree's word
-                    return (unsigned)((v & 0x3fffffffull) >> 1) < (unsigned)(it - ahead) && !(v & 1) && !((v >> 31) & 1);
-                };
-                if (behind(w)) {
-                    const auto t0 = std::chrono::steady_clock::now();
-                    unsigned spins = 0;
-                    while (behind(w = __atomic_load_n(t->h_progress, __ATOMIC_ACQUIRE))) {
-                        if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) { throttle = false; break; }
-                    }
-                }
-            }
-            if (!t->dist && stalled(w)) { it--; continue; }       // handled at the top of the loop
-            if (!t->dist && finished(w)) { saw_end = true; defer_seen = ((w >> 30) & 1ull) != 0; break; }
-        }
-        if (t->dist && !c.cum_cnt_loc) {      // local child sizes unknown in advance: count pass, then scatter (round 5; RLHIP_DIST_COUNT_PASS=1)
-            hipLaunchKernelGGL(k_part_count, dim3(c.nTiles), dim3(kThreads), 0, s, c);
-            hipLaunchKernelGGL(k_part_scatter<false>, dim3(c.nTiles), dim3(kThreads), 0, s, c);
-        } else hipLaunchKernelGGL(k_part_scatter<true>, dim3(c.nTiles), dim3(kThreads), 0, s, c);
-        {
-            ScopedTiming tm(t, RL_KERNEL_HIST_NODE, 0.0);
-            launch_hist<false>(c, t->knobs, hist_gx, c.maxChunks, hist_lds, s);
-        }
-        if (t->dist) {
-            hipLaunchKernelGGL(k_hist_reduce, dim3(c.F, kSpec), dim3(kFinThreads), red_lds, s, c, 0);
-            // growth step `it` works on at most min(kSpec, 2^it) nodes (1 after the root, then at most twice the commits of the step
-            // before): the first steps -- the ones with the largest histograms to wait for -- reduce one or two slots, not kSpec
-            const int max_slots = std::min(kSpec, 1 << std::min(it, 8));
-            int rcd = t->dist->allreduce(c.dist_buf, slot_words * max_slots, DT_I64, OP_SUM, s);
-            if (rcd) return rcd;
-            // round 6: the finish and the bookkeeping of the plain path's step (rl_step2.inc) on the all-reduced limbs; the round-4 fused kernel for what
-            // k_select2 does not cover (feature sampling, more than 160 features, more than 62 leaves)
-            const size_t sel2_lds_d = select2_lds_bytes(c.L, c.NC);
-            if (t->knobs.step2 && c.TS <= kFin2MaxT && !c.fs_on && c.F <= kSel2MaxF && c.L > 0 && c.L + 2 <= 64 && sel2_lds_d <= 60 * 1024) {
-                hipLaunchKernelGGL(k_fin2<true>, dim3(c.F, kSpec), dim3(kFin2Threads), 0, s, c);
-                hipLaunchKernelGGL(k_select2<false>, dim3(1), dim3(kSel2Threads), sel2_lds_d, s, c);
-            } else hipLaunchKernelGGL((k_hist_finish<false, true>), dim3(c.F, kSpec), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-            // Sharded runs pay a collective per step even when the tree is already finished, so the host looks at the
-            // (rank-invariant) `done` flag now and then and stops enqueuing: a stream sync costs far less than the
-            // all-reduces of ~20 empty steps.  One GPU keeps the fully asynchronous schedule (an empty step is 3 tiny launches).
-            if (!c.progress && it + 1 < steps + extra && ((it >= 7 && (it - 7) % 3 == 0) || c.tie_on)) {
-                TreeState sth;
-                RL_HIP(hipStreamSynchronize(s));
-                RL_HIP(hipMemcpy(&sth, c.st, sizeof(sth), hipMemcpyDeviceToHost));
-                if (sth.stall_n > 0) {       // (without a progress word every step of a tie-breaking sharded run is looked at: rank-invariant by construction)
-                    bool ended = false;
-                    int rcs = after_stall(ended);
-                    if (rcs) return rcs;
-                    if (ended) { saw_end = true; break; }
-                    it--;
-                    continue;
-                }
-                if (sth.done) { saw_end = true; defer_seen = sth.defer_any != 0; break; }
-            }
-        } else if (c.java) {
-            hipLaunchKernelGGL(k_jgather, dim3(c.nTiles), dim3(kThreads), 0, s, c, 0);
-            if (c.jmap) hipLaunchKernelGGL(k_jhist2, dim3(c.n_live + 1, kSpec), dim3(kJ2Threads), 0, s, c, 0, c.jmap, c.jinv, c.jone);
-            else hipLaunchKernelGGL(k_jhist, dim3(c.n_live, jbg + 2, kSpec), dim3(64), 0, s, c, 0, jbg);
-            hipLaunchKernelGGL((k_hist_finish<false, false, true>), dim3(c.n_live, kSpec), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-        } else if (t->knobs.step2 && c.TS <= kFin2MaxT) {
-            // rl_step2.inc: one bin per thread, DPP scans, plain stores -- then the bookkeeping as a launch of its own
-            hipLaunchKernelGGL(k_fin2<false>, dim3(c.n_live, kSpec), dim3(kFin2Threads), 0, s, c);
-            const size_t sel2_lds = select2_lds_bytes(c.L, c.NC);
-            if (!c.fs_on && c.F <= kSel2MaxF && c.L > 0 && c.L + 2 <= 64 && sel2_lds <= 60 * 1024)
-                hipLaunchKernelGGL(k_select2<false>, dim3(1), dim3(kSel2Threads), sel2_lds, s, c);
-            else if (t->knobs.sel2_wide && !c.fs_on && c.F <= 32 * kWideS && c.L > 0 && c.L + 2 <= 64 && sel2_lds <= 60 * 1024)
-                hipLaunchKernelGGL(k_select2<true>, dim3(1), dim3(kSel2Threads), sel2_lds, s, c);       // (hundreds of features: the Yahoo-set1 shape)
-            else hipLaunchKernelGGL(k_select, dim3(1), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-        } else if (t->fin_split || !nodes_in_lds) {       // (wide data; or node records that do not fit the LDS: the fused kernel has no path for them)
-            hipLaunchKernelGGL(k_hist_finish_wide, dim3(c.n_live, kSpec), dim3(kFinWideThreads), (size_t)c.TS * 20 + 8 + par_lds, s, c);
-            hipLaunchKernelGGL(k_select, dim3(1), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-        } else hipLaunchKernelGGL((k_hist_finish<false, false>), dim3(c.n_live, kSpec), dim3(kFinThreads), fin_lds, s, c, nodes_in_lds);
-    }
-    if (c.tie_on && !saw_end) {
-        // every step was enqueued without the host ever seeing the end of the tree (no progress word, a spin timeout, or a tree of fewer steps
-        // than the host keeps in flight): a stall may have gone unnoticed -- look, once per round
-        RL_HIP(hipStreamSynchronize(s));
-        TreeState sth;
-        RL_HIP(hipMemcpy(&sth, c.st, sizeof(sth), hipMemcpyDeviceToHost));
-        if (sth.stall_n > 0) {
-            bool ended = false;
-            int rcs = after_stall(ended);
-            if (rcs) return rcs;
-            if (!ended) goto grow;
-        } else defer_seen = sth.defer_any != 0;
-    }
-    // the score update streams over the documents when the leaf sums' gather can leave every document's leaf behind (one GPU, parallel chains, <= 1024 leaves)
-    const bool stream_scores = t->knobs.score_stream && !(t->p.flags & RL_FLAG_SERIAL_CHAIN) && c.leaf_of != nullptr && c.L > 0 && c.L <= 1024;       // (sharded runs too, round 6: the local gather in leaf order leaves every document's leaf behind)
-    hipLaunchKernelGGL(k_leaf_table, dim3(1), dim3(kThreads), 0, s, c, t->leaf_chain, t->d_seg_buf);
-    if (t->p.flags & RL_FLAG_SERIAL_CHAIN) {
-        hipLaunchKernelGGL(k_leaf_chain, dim3(c.L), dim3(64), 0, s, c);
-    } else if (t->dist) {
-        // multi-GPU: gather lambda / weight in leaf order from every rank and evaluate the chains over the whole leaf
-        // multi-GPU, the leaf-owner exchange (rl_dist.inc): lambda / weight of a leaf's documents go to the leaf's owner rank only
-        ChainSource src{nullptr, nullptr, c.lw, c.idx[0], c.idx[1], t->d_seg_buf, stream_scores ? c.leaf_of : nullptr};
-        if (t->piece_chains) {      // round 6: every rank evaluates its own pieces of every leaf, only tables travel (rl_dist.inc)
-            int rcp = enqueue_leaf_chains_pieces(t, src);
-            if (rcp) return rcp;
-            hipLaunchKernelGGL(k_leaf_output, dim3((c.L + kThreads - 1) / kThreads), dim3(kThreads), 0, s, c, t->leaf_chain);
-        } else {
-        const ChainBufs &lb = t->leaf_chain;
-        const int R = t->n_ranks, me = t->dist->rank, nseg = std::max(c.L, 2), MS = t->gchain.maxseg;      // -leaf 1 still has two leaves (the root always splits)
-        hipLaunchKernelGGL(k_chain_prefix, dim3((unsigned)((lb.cap_tiles + 3) / 4)), dim3(kThreads), 0, s, lb, src);      // local values in leaf order -> lb.xs
-        int rcd = t->dist->allgather(c.leaf_start, t->d_gls, (size_t)t->lsstride * sizeof(int32_t), s);
-        if (rcd) return rcd;
-        std::vector<int64_t> scount(R), sdispl(R), rcount(R), rdispl(R);
-        const bool dev_plan = t->d_xmail != nullptr && !t->knobs.dist_host_plan && nseg <= kPlanMaxSeg && R <= 64;       // (knobs.dist_host_plan: the host plan behind a stream synchronisation, as until round 5)
-        if (dev_plan) {
-            // the plan on the device; the host only needs the byte counts of the transfers and reads them from a pinned mailbox below, after it has
-            // enqueued the pack kernel (k_plan_exchange)
-            hipLaunchKernelGGL(k_plan_exchange, dim3(1), dim3(64), 0, s, (const int32_t *)t->d_gls, R, t->lsstride, nseg, MS, me, t->d_own, t->d_xtab, t->d_xmail, ++t->xmail_tag);
-        } else {
-            // the send / receive counts of the exchange have to be known to the host: one small copy per round (sharded runs are host-paced anyway)
-            std::vector<int32_t> &gls = t->h_gls;
-            gls.resize((size_t)R * t->lsstride);
-            RL_HIP(hipMemcpyAsync(gls.data(), t->d_gls, gls.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            RL_HIP(hipStreamSynchronize(s));
-            auto len_of = [&](int r, int l) { return (long long)gls[(size_t)r * t->lsstride + l + 1] - gls[(size_t)r * t->lsstride + l]; };
-            std::vector<int32_t> &own = t->h_own; own.assign((size_t)MS, 0);
-            {   // owners: largest leaf first onto the least loaded rank (every rank computes the same map from the same table)
-                std::vector<long long> glen((size_t)nseg, 0), load((size_t)R, 0);
-                std::vector<int32_t> order((size_t)nseg);
-                for (int l = 0; l < nseg; l++) { order[l] = l; for (int r = 0; r < R; r++) glen[l] += len_of(r, l); }
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return glen[a] > glen[b]; });
-                for (int l : order) {
-                    if (glen[l] == 0) { own[l] = l % R; continue; }
-                    int o = 0;
-                    for (int r = 1; r < R; r++) if (load[r] < load[o]) o = r;
-                    own[l] = o; load[o] += glen[l];
-                }
-            }
-            std::vector<long long> &tab = t->h_xtab; tab.assign((size_t)MS * (R + 1), 0);       // pack_off [MS] | asm_off [R][MS]
-            long long cur = 0;
-            for (int d = 0; d < R; d++) {
-                sdispl[d] = cur * 8;
-                if (d != me) for (int l = 0; l < nseg; l++) if (own[l] == d) { tab[l] = cur; cur += 2 * len_of(me, l); }       // (own leaves: not packed, k_chain_assemble)
-                scount[d] = cur * 8 - sdispl[d];
-            }
-            cur = 0;
-            for (int r = 0; r < R; r++) {
-                rdispl[r] = cur * 8;
-                if (r != me) for (int l = 0; l < nseg; l++) if (own[l] == me) { tab[(size_t)MS * (1 + r) + l] = cur; cur += 2 * len_of(r, l); }
-                rcount[r] = cur * 8 - rdispl[r];
-            }
-            RL_HIP(hipMemcpyAsync(t->d_own, own.data(), (size_t)MS * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            RL_HIP(hipMemcpyAsync(t->d_xtab, tab.data(), tab.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-        }
-        const LeafExchange lx{t->d_own, t->d_xtab, t->d_xtab + MS};
-        hipLaunchKernelGGL(k_chain_pack, dim3(nseg, 2, kLeafXferZ), dim3(kThreads), 0, s, (const double *)lb.xs, lb.cap_n, (const int32_t *)c.leaf_start, nseg, lx, t->d_send, me);
-        if (dev_plan) {       // the mailbox: the tag is stored last (release); a device error or a dead peer must end the wait
-            const auto t0w = std::chrono::steady_clock::now();
-            unsigned spins = 0;
-            while (__atomic_load_n(&t->h_xmail[4 * R], __ATOMIC_ACQUIRE) != t->xmail_tag) {
-                if ((++spins & 0xffff) == 0) {
-                    const hipError_t q = hipStreamQuery(s);
-                    if (q != hipSuccess && q != hipErrorNotReady) return fail(RL_ERR_HIP, std::string("device error before the leaf-owner exchange: ") + hipGetErrorString(q));
-                    if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0w).count() > t->knobs.dist_timeout_s)
-                        return fail(RL_ERR_COMM, "timed out waiting for the plan of the leaf-owner exchange (a rank of the job is missing from a collective?)");
-                }
-            }
-            for (int r = 0; r < R; r++) { scount[r] = t->h_xmail[r]; sdispl[r] = t->h_xmail[R + r]; rcount[r] = t->h_xmail[2 * R + r]; rdispl[r] = t->h_xmail[3 * R + r]; }
-        }
-        rcd = t->dist->alltoallv(t->d_send, scount.data(), sdispl.data(), t->d_gx, rcount.data(), rdispl.data(), s);
-        if (rcd) return rcd;
-        hipLaunchKernelGGL(k_plan_global, dim3(1), dim3(64), 0, s, (const int32_t *)t->d_gls, R, t->lsstride, nseg, t->gchain, (const int32_t *)t->d_own, me);
-        hipLaunchKernelGGL(k_chain_assemble, dim3(nseg, 2, kLeafXferZ), dim3(kThreads), 0, s, (const double *)t->d_gx, (const int32_t *)t->d_gls, R, t->lsstride, nseg, lx,
-                           t->gchain, me, (const double *)lb.xs, lb.cap_n, (const int32_t *)c.leaf_start);
-        ChainSource gsrc{t->gchain.xs, t->gchain.xs + t->gchain.cap_n, nullptr, nullptr, nullptr, nullptr};
-        enqueue_chain(t, t->gchain, gsrc);
-        if (R > 1) {       // every rank evaluated its own leaves: exchange the 2 L float sums
-            rcd = t->dist->allgather(t->gchain.result, t->d_gres, (size_t)2 * MS * sizeof(float), s);
-            if (rcd) return rcd;
-            hipLaunchKernelGGL(k_chain_pick, dim3((2 * nseg + kThreads - 1) / kThreads), dim3(kThreads), 0, s, (const float *)t->d_gres, R, 2,
-                               MS, nseg, (const int32_t *)t->d_own, t->gchain.result);
-        }
-        hipLaunchKernelGGL(k_leaf_output, dim3((c.L + kThreads - 1) / kThreads), dim3(kThreads), 0, s, c, t->gchain);
-        }
-    } else {   // K7: the two Java float running sums of every leaf, exactly, in parallel (rl_chain.inc)
-        ChainSource src{nullptr, nullptr, c.lw, c.idx[0], c.idx[1], t->d_seg_buf, stream_scores ? c.leaf_of : nullptr};
-        enqueue_chain(t, t->leaf_chain, src);
-        hipLaunchKernelGGL(k_leaf_output, dim3((c.L + kThreads - 1) / kThreads), dim3(kThreads), 0, s, c, t->leaf_chain);
-    }
-    if (c.tie_on && defer_seen) {
-        // deferred ties (plateaus of right children, several features over one cut): the tree was grown with the partition the tied candidates
-        // share; the (feature, threshold) the Java's rounding noise would store is decided now, in one batch (the leaf sums above are already
-        // enqueued and run meanwhile; the score update waits, because a tie that turns out to hide two different cuts restarts the tree)
-        bool other_cut = false;
-        int rcs = resolve_ties(t, fin_lds, nodes_in_lds, true, &other_cut);
-        if (rcs) return rcs;
-        if (other_cut && (c.tie_on & 2)) { c.tie_on = 1; t->tie_regrown++; goto regrow; }
-    }
-    if (stream_scores) hipLaunchKernelGGL(k_score_stream, dim3(std::max(1, std::min(2048, (c.N + kScoreBatch * kThreads - 1) / (kScoreBatch * kThreads)))), dim3(kThreads), 0, s, c);
-    else hipLaunchKernelGGL(k_score_update, dim3(std::max(1, std::min(4096, (c.N + kScoreBatch * kThreads - 1) / (kScoreBatch * kThreads)))), dim3(kThreads), 0, s, c);
-    hipLaunchKernelGGL(k_export_tree, dim3(1), dim3(kThreads), 0, s, c, t->ens, m);
-    RL_HIP(hipGetLastError());
-    // per-round training metric (LambdaMART.java:216)
-    // (sharded runs, round 6: the per-query values are gathered on the main stream -- one communicator, one stream -- and the float mean over the
-    // gathered lists runs on the side stream beside the next round's lambdas, as the one-GPU mean does)
-    const bool use_side = !t->has_valid;
-    if (use_side && t->side_pending) RL_HIP(hipStreamWaitEvent(s, t->ev_metric, 0));     // the previous round's metric still reads d_ndcg (sharded: the gathered copy)
-    int rc = launch_rank(t, t->tr, c.scores, t->tr.d_ndcg, true);      // also the ranking of round m+1's lambdas
-    if (rc != RL_OK) return rc;
-    if (use_side) {
-        const double *mq = t->tr.d_ndcg; int mQ = t->tr.Q;
-        if (t->dist) { rc = gather_queries(t, t->tr.d_ndcg, &mq); if (rc != RL_OK) return rc; mQ = t->Qglobal; }
-        RL_HIP(hipEventRecord(t->ev_ranked, s));
-        RL_HIP(hipStreamWaitEvent(t->side, t->ev_ranked, 0));
-        enqueue_metric_mean(t, mq, mQ, c.round_metric + 2 * (size_t)m, t->side);
-        RL_HIP(hipEventRecord(t->ev_metric, t->side));
-        t->side_pending = true;
-    } else if (t->dist) {
-        const double *gq = nullptr;
-        rc = gather_queries(t, t->tr.d_ndcg, &gq);
-        if (rc != RL_OK) return rc;
-        enqueue_metric_mean(t, gq, t->Qglobal, c.round_metric + 2 * (size_t)m);
-    } else enqueue_metric_mean(t, t->tr.d_ndcg, t->tr.Q, c.round_metric + 2 * (size_t)m);
-    if (t->has_valid) {   // :228-237
-        hipLaunchKernelGGL(k_valid_update, dim3(std::min<int64_t>(4096, (t->va.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                           t->ens, c.MAXN, m, (const float *)t->va.d_X, (int)t->va.N, t->F, c.lr, t->va.d_scores);
-        rc = launch_rank(t, t->va, t->va.d_scores, t->va.d_ndcg, false);
-        if (rc != RL_OK) return rc;
-        if (t->dist) {      // every rank holds a shard of the validation lists: the float mean runs over all of them in list order
-            const double *gq = nullptr;
-            rc = gather_queries(t, t->va.d_ndcg, &gq, true);
-            if (rc != RL_OK) return rc;
-            enqueue_metric_mean(t, gq, t->vQglobal, c.round_metric + 2 * (size_t)m + 1);
-        } else enqueue_metric_mean(t, t->va.d_ndcg, t->va.Q, c.round_metric + 2 * (size_t)m + 1);
-    }
-    RL_HIP(hipGetLastError());
-    t->round = m + 1;
-    t->n_kept = t->round;
-    return RL_OK;
-}
+}  // namespace rl
+
+#include "rl_round.inc"      // the stages of a boosting round and enqueue_round itself (resolve_ties above is theirs to call)
+
+namespace rl {
 
 static int sync_rounds(rl_trainer *t)
 {

@@ -93,6 +93,14 @@ CFG31 = (9000, 24, "mslr", 4, 31, 4)      # 30 growth steps allowed, trees finis
 CFG_BIG = (150000, 24, "mslr", 5, 31, 3)  # shards of 50-75 k documents: steps of many balanced chunks per rank, local left sizes from the ranks' own cumulative counts (round 6)
 
 
+def test_one_rank_sharded_path_without_a_progress_word_equals_plain_path(monkeypatch):
+    """RLHIP_STEP_AHEAD=0: no progress word, so the sharded growth loop looks at the tree state itself -- after every step of a tie-breaking run
+    (else at step 7, 10, 13, ...) -- to see the stalls and the end of the tree.  Host-callback transport, 1 rank: the plain path's trees"""
+    ref = single(*CFG_TIES)
+    monkeypatch.setenv("RLHIP_STEP_AHEAD", "0")
+    same(ref, single(*CFG_TIES, dist_mode="cb1"))
+
+
 @pytest.mark.parametrize("world,ranker,metric,k,cfg", [(2, "LAMBDAMART", "NDCG", 10, CFG), (3, "LAMBDAMART", "NDCG", 10, CFG),
                                                         (2, "MART", "NDCG", 10, CFG), (2, "LAMBDAMART", "MAP", 0, CFG),
                                                         (3, "LAMBDAMART", "ERR", 10, CFG), (2, "LAMBDAMART", "NDCG", 10, CFG31),

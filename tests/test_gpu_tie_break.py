@@ -136,6 +136,35 @@ def test_a_tree_whose_deferred_tie_fails_the_check_is_grown_again(monkeypatch):
     assert np.array_equal(sc.view(np.int64), sc_r.view(np.int64))
 
 
+def test_a_stall_seen_only_at_the_end_of_the_tree_resumes_the_growth(monkeypatch):
+    """RLHIP_STEP_AHEAD=0: the handle has no progress word, every growth step is enqueued blindly and a stalled tree is noticed only by the look
+    behind the last step -- which resolves the ties and carries on growing from the device's own step, as often as the tree stalls.  With the
+    deferral off every tie over several features stalls: the same trees and scores as the default run, and the oracle's"""
+    X, lab, qoff = duplicate_columns(31)
+    trees, ties, st, sc = run(X, lab, qoff, 5, 31)
+    assert ties == 0
+    monkeypatch.setenv("RLHIP_STEP_AHEAD", "0")
+    monkeypatch.setenv("RLHIP_TIE_NO_XDEFER", "1")
+    trees_b, ties_b, st_b, sc_b = run(X, lab, qoff, 5, 31)
+    assert ties_b == 0 and st_b[0] > 0, st_b
+    same_trees(trees, trees_b)
+    assert np.array_equal(sc.view(np.int64), sc_b.view(np.int64))
+
+
+def test_a_tree_is_grown_again_without_a_progress_word(monkeypatch):
+    """the forced miss of the deferred check under RLHIP_STEP_AHEAD=0: the second pass over the tree (stalls instead of deferrals) has no progress
+    word to follow either -- same trees, same scores"""
+    X, lab, qoff = duplicate_columns(32)
+    trees, ties, st, sc = run(X, lab, qoff, 4, 24)
+    assert ties == 0
+    monkeypatch.setenv("RLHIP_STEP_AHEAD", "0")
+    monkeypatch.setenv("RLHIP_TIE_FORCE_REGROW", "1")
+    trees_r, ties_r, st_r, sc_r = run(X, lab, qoff, 4, 24)
+    assert ties_r == 0 and st_r[9] > 0, st_r
+    same_trees(trees, trees_r)
+    assert np.array_equal(sc.view(np.int64), sc_r.view(np.int64))
+
+
 def test_equal_lambdas_on_opposite_sides_are_caught_by_the_check():
     """two candidates of two features with equal (left count, exact left sum) that are NOT the same documents: lists whose documents all carry one label
     have lambda = 0, and two such documents swapped between the sides leave count and sum unchanged.  Built on purpose: feature 0 takes two values and
