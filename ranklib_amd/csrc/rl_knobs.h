@@ -37,7 +37,7 @@ struct Knobs {
     Opt node_div, balance_target, balance_min, balance_cap, fin_split, hist_nt, hist_grid, trace_tree;
     // (the initialisers are the defaults of read(): a trainer that rl_create did not make -- rl_debug_float_chain's -- runs the default paths)
     int node_min = 256, sub_child = 16, p8 = 1, dm_div = 1, csc_dens = 3, crows = -1, step_ahead = 1, dist_ahead = 1, piece_force = 0, lam_side = 1, tiny_min = 4096;
-    size_t hist_ldspad = 0, tie_walk_max = 24576;
+    size_t hist_ldspad = 0, tie_walk_max = 24576, tie_slack = (size_t)64 << 20;
     double dist_timeout_s = 300.0;
     bool balance = true, skip_last = true, step2 = true, sel2_wide = true, fused_quant = true, score_stream = true, dm_root = false, lam_compact = false;
     bool rank_split = false, runs_off = false, jhist_v1 = false, lambda_unfused = false, tie_off = false, tie_no_xdefer = false, tie_walk = false, tie_force_regrow = false;
@@ -77,12 +77,13 @@ struct Knobs {
         lambda_unfused = present("RLHIP_LAMBDA_UNFUSED");                                       // pair-term matrix instead of the LDS-resident fused lambda kernel
         lam_side = std::max(0, std::min(3, value("RLHIP_LAMBDA_SIDE", 1)));                     // side streams the lambda kernels of the length classes use
         lam_compact = nonzero("RLHIP_LAMBDA_COMPACT");                                          // NDCG / DCG pair terms from per-wavefront lists of the active pairs
-        // -- lazy Java-order tie-break (rl_tie.inc)
+        // -- lazy Java-order tie-break (rl_tie.inc, rl_tie_host.inc)
         tie_off = present("RLHIP_TIE_OFF");                                                     // keep the first candidate of an exact tie
         tie_no_xdefer = present("RLHIP_TIE_NO_XDEFER");                                         // stall on ties over several features instead of deferring them
         tie_walk = present("RLHIP_TIE_WALK");                                                   // always the literal walk (the cross-check of the speculative chains)
         tie_walk_max = (size_t)(getenv("RLHIP_TIE_WALK_MAX") ? atoll(getenv("RLHIP_TIE_WALK_MAX")) : 24576ll);   // chains up to this many documents take the literal walk
-        tie_force_regrow = present("RLHIP_TIE_FORCE_REGROW");                                   // test aid: every verified batch reports a miss, the tree is grown again
+        tie_slack = (size_t)std::max(0ll, getenv("RLHIP_TIE_SLACK") ? atoll(getenv("RLHIP_TIE_SLACK")) : 64ll << 20);   // test aid: bytes the scratch arena's first reservation adds to its fixed part; 0: a speculative resolution grows the arena
+        tie_force_regrow = present("RLHIP_TIE_FORCE_REGROW");                                  // test aid: every verified batch reports a miss, the tree is grown again
         // -- sharded runs (rl_dist.inc)
         dist_ahead = std::max(0, value("RLHIP_DIST_STEP_AHEAD", 1));                            // growth steps enqueued beyond the last one the host has seen
         dist_timeout_s = getenv("RLHIP_DIST_TIMEOUT_S") ? std::max(1.0, atof(getenv("RLHIP_DIST_TIMEOUT_S"))) : 300.0;   // operational: a rank gives up waiting for its own device

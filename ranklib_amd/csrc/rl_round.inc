@@ -1,5 +1,5 @@
 // rl_round.inc -- the stages of one boosting round, in the order enqueue_round (at the end of this file) calls them.  Included by rl_trainer.hip behind
-// resolve_ties, which the growth stages call.
+// rl_tie_host.inc, whose resolve_ties the growth stages call.
 //
 // Every trainer path runs these stages: one GPU, MART, the strict Java order, sharded.  A stage enqueues on the trainer's stream and returns; where
 // the modes differ, the branches sit side by side inside the stage.  Sharded runs: every rank enqueues the same collectives in the same order, so

@@ -710,398 +710,10 @@ static int gather_queries(rl_trainer *t, const double *local, const double **out
     return RL_OK;
 }
 
-// Lazy Java-order tie-break (rl_tie.inc): the device stalled the tree on nodes whose exactly tied best split the Java's rounding noise decides.
-// The stream is idle when this runs (the caller synchronised it).  Reads the node records, lays out the derivation chains -- a node the Java
-// accumulates (root / left child) is summed from its members; a right child is parent - left sibling, recursively -- and runs the kernels that
-// put the Java's choice into the node records and resume the growth bookkeeping.  Device scratch comes from one arena that only ever grows.
-struct TieArena {
-    char *base = nullptr; size_t cap = 0, used = 0;
-    template <class T> T *take(size_t n) { used = (used + 255) & ~(size_t)255; T *p = (T *)(base + used); used += n * sizeof(T); return p; }
-};
-static int tie_arena_reserve(rl_trainer *t, size_t bytes)
-{
-    if (bytes <= t->tie_cap) return RL_OK;
-    if (t->tie_buf) { (void)hipFree(t->tie_buf); t->tie_buf = nullptr; t->tie_cap = 0; }
-    const size_t want = bytes + bytes / 4 + (1 << 20);
-    if (hipMalloc(&t->tie_buf, want) != hipSuccess) { (void)hipGetLastError(); t->tie_buf = nullptr; return RL_ERR_HIP; }
-    t->tie_cap = want;
-    return RL_OK;
-}
-
-// deferred = false: the tree is stalled on TreeState::stall_node (ties whose candidates may cut the node differently); afterwards the growth resumes.
-// deferred = true: the tree is grown; the committed nodes flagged 0x40 (plateau ties of right children: the partition was known, the stored
-// threshold was not) get the Java's threshold, all of them in one batch, before the tree is exported.
-static int resolve_ties(rl_trainer *t, size_t fin_lds, int nodes_in_lds, bool deferred = false, bool *other_cut = nullptr)
-{
-    Ctx &c = t->ctx;
-    hipStream_t s = t->stream;
-    const auto t_begin = std::chrono::steady_clock::now();
-    struct TieScope { DistBackend *d; TieScope(DistBackend *d_) : d(d_) { if (d) d->tie_scope = true; } ~TieScope() { if (d) d->tie_scope = false; } } tie_scope(t->dist.get());
-    // small reads come back through one pinned buffer (a pageable copy costs tens of microseconds each)
-    // The pinned buffer grows with what a resolution needs (nothing in flight reads it when it is asked to: every use is copy, synchronise, memcpy):
-    // a batch of deferred nodes of a tree with hundreds of leaves, or of wide data with many tied features, is not a reason to stop training
-    auto ensure_pin = [&](size_t bytes) -> int {
-        if (t->tie_pin_cap >= bytes) return RL_OK;
-        if (t->tie_pin) (void)hipHostFree(t->tie_pin);
-        t->tie_pin = nullptr; t->tie_pin_cap = 0;
-        const size_t want = bytes + bytes / 4;
-        if (hipHostMalloc(&t->tie_pin, want, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(RL_ERR_HIP, "tie-break: no pinned host memory"); }
-        t->tie_pin_cap = want;
-        return RL_OK;
-    };
-    { int rcp = ensure_pin(sizeof(TreeState) + (size_t)(c.NC + 2) * sizeof(NodeRec) + (size_t)kTieMaxChain * c.F * 4 + ((size_t)1 << 20)); if (rcp) return rcp; }
-    char *pin = (char *)t->tie_pin;
-    RL_HIP(hipMemcpyAsync(pin, c.st, sizeof(TreeState), hipMemcpyDeviceToHost, s));
-    RL_HIP(hipMemcpyAsync(pin + sizeof(TreeState), c.nodes, (size_t)c.NC * sizeof(NodeRec), hipMemcpyDeviceToHost, s));
-    RL_HIP(hipStreamSynchronize(s));
-    const bool tie_prof = t->knobs.tie_prof;
-    auto t_last = t_begin;
-    auto mark = [&](int ph) { if (!tie_prof) return; const auto now = std::chrono::steady_clock::now(); t->tie_phase_us[ph] += (long long)std::chrono::duration_cast<std::chrono::microseconds>(now - t_last).count(); t_last = now; };
-    mark(0);
-    TreeState st;
-    memcpy(&st, pin, sizeof(st));
-    if (!deferred && (st.stall_n <= 0 || st.stall_n > kSpec)) return fail(RL_ERR_STATE, "resolve_ties without a stalled tree (internal error)");
-    std::vector<NodeRec> nodes((size_t)st.n_nodes);
-    memcpy(nodes.data(), pin + sizeof(TreeState), nodes.size() * sizeof(NodeRec));
-    std::vector<int> todo;
-    if (deferred) { for (int x = 0; x < st.n_nodes; x++) if (nodes[x].left >= 0 && (nodes[x].tie & 0xc0) == 0x40) todo.push_back(x); }
-    else for (int x = 0; x < st.stall_n; x++) todo.push_back(st.stall_node[x]);
-    if (todo.empty()) return RL_OK;
-    std::vector<TieNode> an; std::vector<TiePred> preds; std::map<int, int> a_of;
-    auto is_right = [&](int x) { return nodes[x].parent >= 0 && nodes[nodes[x].parent].pr == x; };
-    auto direct = [&](int x) -> int {        // chain node of a directly accumulated node, with the split predicates of its path from the root
-        auto it = a_of.find(x);
-        if (it != a_of.end()) return it->second;
-        TieNode A; A.node = x; A.pred0 = (int)preds.size(); A.npred = 0; A.is_root = (x == 0) ? 1 : 0; A.list0 = 0; A.count = nodes[x].gcount;
-        A.gcount = nodes[x].gcount; A.pad = 0;             // count: this rank's members (the device sets it; == gcount on one GPU)
-        for (int ch = x; nodes[ch].parent >= 0; ch = nodes[ch].parent) {
-            const NodeRec &P = nodes[nodes[ch].parent];
-            preds.push_back(TiePred{P.best_f, P.best_t, P.pl == ch ? 1 : 0});
-            A.npred++;
-        }
-        an.push_back(A);
-        a_of[x] = (int)an.size() - 1;
-        return (int)an.size() - 1;
-    };
-    const int nx = (int)todo.size();
-    // deferred ties over several features: the node was cut by its first candidate; that every tied candidate cuts it the same way is verified
-    // document by document (k_tie_verify) -- these are the nodes, with the split predicates of their paths
-    std::vector<TieNode> vn; std::vector<int32_t> vx;
-    if (deferred)
-        for (int x = 0; x < nx; x++) {
-            if ((nodes[todo[x]].tie & 3) != 2) continue;
-            TieNode V; memset(&V, 0, sizeof(V));
-            V.node = todo[x]; V.pred0 = (int)preds.size(); V.is_root = (todo[x] == 0) ? 1 : 0; V.gcount = nodes[todo[x]].gcount;
-            for (int ch = todo[x]; nodes[ch].parent >= 0; ch = nodes[ch].parent) {
-                const NodeRec &P = nodes[nodes[ch].parent];
-                preds.push_back(TiePred{P.best_f, P.best_t, P.pl == ch ? 1 : 0});
-                V.npred++;
-            }
-            vn.push_back(V); vx.push_back(x);
-        }
-    const int nv = (int)vn.size();
-    int32_t *d_vflag = nullptr;
-    std::vector<std::vector<int>> chains((size_t)nx);
-    size_t chain_cap = 1;
-    for (int x = 0; x < nx; x++) {
-        // J(X): X itself when the Java accumulates it; else J(parent) - J(left sibling), the parent first (top-down)
-        std::vector<int> subs;               // left siblings, bottom-up
-        int cur = todo[x];
-        while (is_right(cur)) { subs.push_back(nodes[nodes[cur].parent].pl); cur = nodes[cur].parent; }
-        chains[x].push_back(direct(cur));
-        for (auto it = subs.rbegin(); it != subs.rend(); ++it) chains[x].push_back(direct(*it));
-        chain_cap = std::max(chain_cap, chains[x].size());
-    }
-    const int nA = (int)an.size();
-    const bool sharded = t->dist && t->n_ranks > 1;       // the members of a chain node are spread over the ranks: their values are gathered (below)
-    const int R = sharded ? t->n_ranks : 1;
-    // (the host tables above are complete: the pinned buffer may move now.  need[] and the chain nodes come back through it in stage 1)
-    { int rcp = ensure_pin((size_t)nA * c.F * sizeof(int32_t) + (size_t)nA * sizeof(TieNode) + (size_t)std::max(R, 1) * nA * sizeof(int32_t) + ((size_t)1 << 20)); if (rcp) return rcp; pin = (char *)t->tie_pin; }
-    size_t list_total = 0, u_total = 0;
-    std::vector<long long> u0((size_t)nA);
-    int maxcnt = 1;
-    for (int i = 0; i < nA; i++) {
-        TieNode &A = an[i];
-        if (!A.is_root) { A.list0 = (int32_t)list_total; list_total += (size_t)std::min(A.gcount, c.N); }
-        u0[i] = (long long)u_total; u_total += (size_t)A.gcount;
-        maxcnt = std::max(maxcnt, std::min(A.gcount, c.N));
-    }
-    if (list_total > ((size_t)1 << 31) - 1) return fail(RL_ERR_UNSUPPORTED, "tie-break: member lists beyond 2^31 entries");
-    std::vector<int32_t> xlen((size_t)nx), xchain((size_t)nx * chain_cap, 0), xnode((size_t)nx);
-    for (int x = 0; x < nx; x++) {
-        xnode[x] = todo[x]; xlen[x] = (int32_t)chains[x].size();
-        for (size_t i = 0; i < chains[x].size(); i++) xchain[(size_t)x * chain_cap + i] = chains[x][i];
-    }
-    const int tiles = (c.N + kTieTile - 1) / kTieTile, nbg = (c.TS + 63) / 64;
-    // short chains: the literal walk (one kernel, ~6 ns a document) beats the dozen launches and two more host round trips of the contiguous-chain path;
-    // known before anything ran on the device, so stage 1 does not have to report back either
-    const bool walk_early = !sharded && (t->knobs.tie_walk || u_total <= t->knobs.tie_walk_max || (size_t)kTsWaves * c.TS * 4 > (size_t)60 * 1024);
-    // ---- stage 1: fixed-size scratch, the tied candidates, the member lists
-    const size_t fixed_bytes = (size_t)nx * c.F * c.TS + ((size_t)nA * c.F + (size_t)nx * c.F + (size_t)nA * tiles + list_total + 64) * 4 + ((size_t)nA * c.F * c.TS + nA) * 8 +
-                               (xchain.size() + 2 * (size_t)nx + 16) * 4 + (size_t)nA * sizeof(TieNode) + (preds.size() + 1) * sizeof(TiePred) + (size_t)nA * 8 + 64 * 256 +
-                               (nv > 0 ? (size_t)nx * c.F * 12 + (size_t)nx * 4 + (size_t)nv * (sizeof(TieNode) + 4) + 1024 : 0) + (size_t)nx * c.F * 12 + 1024;
-    if (tie_arena_reserve(t, std::max(fixed_bytes + ((size_t)64 << 20), t->tie_hint))) return fail(RL_ERR_HIP, "tie-break: out of device memory");
-    TieArena ar;
-    TieArgs a;
-    long long *d_u0 = nullptr;
-    std::vector<int32_t> need((size_t)nA * c.F), lcnt((size_t)nA, 0);
-    // (a lambda: when stage 2 turns out to need a larger arena, the arena moves and stage 1 is simply run again)
-    auto stage1 = [&]() -> int {
-        ar = TieArena(); ar.base = (char *)t->tie_buf; ar.cap = t->tie_cap;
-        memset(&a, 0, sizeof(a));
-        a.nx = nx; a.nA = nA; a.chain_cap = (int32_t)chain_cap;
-        // the small host tables travel as ONE copy
-        std::vector<char> &blob = t->tie_blob; blob.clear();
-        auto put = [&](const void *src, size_t bytes) { const size_t o = (blob.size() + 15) & ~(size_t)15; blob.resize(o + bytes); if (bytes) memcpy(blob.data() + o, src, bytes); return o; };
-        const size_t o_xnode = put(xnode.data(), nx * sizeof(int32_t)), o_xlen = put(xlen.data(), nx * sizeof(int32_t)), o_xchain = put(xchain.data(), xchain.size() * sizeof(int32_t));
-        const size_t o_an = put(an.data(), nA * sizeof(TieNode)), o_preds = put(preds.data(), preds.size() * sizeof(TiePred)), o_u0 = put(u0.data(), nA * sizeof(long long));
-        const size_t o_vn = put(vn.data(), nv * sizeof(TieNode)), o_vx = put(vx.data(), nv * sizeof(int32_t));
-        char *d_blob = ar.take<char>(blob.size() + 16);
-        RL_HIP(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-        int32_t *d_xnode = (int32_t *)(d_blob + o_xnode), *d_xlen = (int32_t *)(d_blob + o_xlen), *d_xchain = (int32_t *)(d_blob + o_xchain);
-        a.an = (TieNode *)(d_blob + o_an); TiePred *d_preds = (TiePred *)(d_blob + o_preds);
-        d_u0 = (long long *)(d_blob + o_u0);
-        a.tmask = ar.take<uint8_t>((size_t)nx * c.F * c.TS); a.need = ar.take<int32_t>((size_t)nA * c.F); a.xf = ar.take<int32_t>((size_t)nx * c.F);
-        a.tile_cnt = ar.take<int32_t>((size_t)nA * tiles); a.list = ar.take<int32_t>(list_total + 1);
-        a.jbin = ar.take<double>((size_t)nA * c.F * c.TS); a.jtot = ar.take<double>(nA);
-        a.fS = ar.take<double>((size_t)nx * c.F); a.ft = ar.take<int32_t>((size_t)nx * c.F);
-        RL_HIP(hipMemsetAsync(a.need, 0, (size_t)nA * c.F * sizeof(int32_t), s));
-        a.xnode = d_xnode; a.xlen = d_xlen; a.xchain = d_xchain; a.preds = d_preds;
-        if (nv > 0) {
-            a.vcnt = ar.take<int32_t>((size_t)nx + 1); a.vlist = ar.take<int32_t>((size_t)nx * c.F * 3);
-            d_vflag = a.vcnt + nx;
-            RL_HIP(hipMemsetAsync(a.vcnt, 0, ((size_t)nx + 1) * sizeof(int32_t), s));
-        }
-        hipLaunchKernelGGL(k_tie_cand, dim3(c.F, nx), dim3(kFinThreads), 0, s, c, a);
-        if (nv > 0) hipLaunchKernelGGL(k_tie_verify, dim3(tiles, nv), dim3(kThreads), 0, s, c, a, (const TieNode *)(d_blob + o_vn), (const int32_t *)(d_blob + o_vx), d_vflag);
-        bool any_list = false;
-        for (auto &A : an) any_list |= !A.is_root;
-        if (any_list) {
-            hipLaunchKernelGGL(k_tie_count, dim3(tiles, nA), dim3(kThreads), 0, s, c, a, tiles);
-            hipLaunchKernelGGL(k_tie_scan, dim3(nA), dim3(kThreads), 0, s, a, tiles);
-            hipLaunchKernelGGL(k_tie_scatter, dim3(tiles, nA), dim3(kThreads), 0, s, c, a, tiles);
-        }
-        if (walk_early) return RL_OK;       // (need / lcnt stay zero: no pairs, the walk below)
-        RL_HIP(hipMemcpyAsync(pin, a.need, need.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        RL_HIP(hipMemcpyAsync(pin + need.size() * sizeof(int32_t), a.an, (size_t)nA * sizeof(TieNode), hipMemcpyDeviceToHost, s));
-        RL_HIP(hipStreamSynchronize(s));
-        memcpy(need.data(), pin, need.size() * sizeof(int32_t));
-        for (int i = 0; i < nA; i++) {      // this rank's member counts (k_tie_scan)
-            TieNode A; memcpy(&A, pin + need.size() * sizeof(int32_t) + (size_t)i * sizeof(TieNode), sizeof(A));
-            lcnt[i] = an[i].is_root ? c.N : (any_list ? A.count : an[i].gcount);
-        }
-        return RL_OK;
-    };
-    mark(1);
-    { int rc1 = stage1(); if (rc1) return rc1; }
-    mark(2);
-    // ---- stage 2: the needed (chain node, feature) pairs, their bins' sizes, the chains and their segments
-    std::vector<TiePair> pairs;
-    size_t v_total = u_total, m_total = 0;
-    int tiles_max = 1;
-    for (int i = 0; i < nA; i++)
-        for (int f = 0; f < c.F; f++)
-            if (need[(size_t)i * c.F + f]) {
-                TiePair P; P.a = i; P.f = f; P.tiles = (an[i].gcount + kTsTile - 1) / kTsTile; P.pad = 0; P.v0 = (long long)v_total; P.m0 = (long long)m_total;
-                v_total += (size_t)an[i].gcount; m_total += (size_t)an[i].gcount; tiles_max = std::max(tiles_max, P.tiles);
-                pairs.push_back(P);
-            }
-    const int npairs = (int)pairs.size();
-    bool walk = walk_early || npairs == 0 || (size_t)kTsWaves * c.TS * 4 > (size_t)60 * 1024;      // (huge threshold tables: the sort's cursors would not fit the LDS)
-    if (sharded) walk = false;                // the walk reads this rank's documents only; rl_init keeps the tie-break off for sharded runs with huge tables
-    std::vector<int32_t> cnts((size_t)npairs * c.TS);
-    if (!walk) {       // cumulative bin counts of the pairs (exact): where every bin's run starts in the sorted values
-        { int rcp = ensure_pin(cnts.size() * sizeof(int32_t) + 4096); if (rcp) return rcp; pin = (char *)t->tie_pin; }
-        for (int p = 0; p < npairs; p++)
-            RL_HIP(hipMemcpyAsync(pin + (size_t)p * c.TS * sizeof(int32_t), c.cum_cnt + ((size_t)an[pairs[p].a].node * c.F + pairs[p].f) * c.TS, (size_t)c.TS * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, s));
-        RL_HIP(hipStreamSynchronize(s));
-        memcpy(cnts.data(), pin, cnts.size() * sizeof(int32_t));
-    }
-    std::vector<TieChain> chs; std::vector<int32_t> win_chain, chunk_chain;
-    auto add_chain = [&](long long off, int len, int out) {
-        TieChain C; C.off = off; C.len = len; C.out = out; C.win0 = (int32_t)win_chain.size();
-        C.win = std::min(16384, std::max(2048, ((len / 256 + 2047) / 2048) * 2048));
-        const int nw = (len + C.win - 1) / C.win;
-        for (int j = 0; j < nw; j++) win_chain.push_back((int32_t)chs.size());
-        for (int j = 0; j <= nw; j++) chunk_chain.push_back((int32_t)chs.size());       // chunk ids: win0 + chain index + local chunk
-        chs.push_back(C);
-    };
-    std::vector<int32_t> &h_nthr = t->h_nthr;
-    if (!walk) {
-        if ((int)h_nthr.size() != c.F) { h_nthr.resize(c.F); RL_HIP(hipMemcpy(h_nthr.data(), c.nthr, c.F * sizeof(int32_t), hipMemcpyDeviceToHost)); }
-        for (int i = 0; i < nA; i++) add_chain(u0[i], an[i].gcount, -(i + 1));
-        for (int p = 0; p < npairs; p++) {
-            const int32_t *cc = cnts.data() + (size_t)p * c.TS;
-            for (int b = 0; b < h_nthr[pairs[p].f]; b++) {
-                const int start = b > 0 ? cc[b - 1] : 0;
-                add_chain(pairs[p].v0 + start, cc[b] - start, (int)(((size_t)pairs[p].a * c.F + pairs[p].f) * c.TS + b));
-            }
-        }
-    }
-    const int nch = (int)chs.size(), nwin = (int)win_chain.size(), nchunks = (int)chunk_chain.size();
-    size_t l_u = 0, l_m = 0;                 // this rank's members of the chain nodes / of the pairs' chain nodes
-    for (int i = 0; i < nA; i++) l_u += (size_t)lcnt[i];
-    for (int p = 0; p < npairs; p++) l_m += (size_t)lcnt[pairs[p].a];
-    const size_t spec_bytes = (m_total + 64) * 2 + (sharded ? (l_u + u_total + 64) * 8 + (l_m + m_total + 64) * 2 + (size_t)(R + 1) * nA * 4 : 0) + (size_t)(nA + 2 * npairs + 8) * 8 + v_total * 8 + (size_t)npairs * tiles_max * c.TS * 4 + (size_t)nwin * (16 + 16 + 4) + (size_t)nchunks * (4 + 16 + 8 + 8 * kSpW + 4) +
-                              (size_t)nch * (16 + 8 + 8 + sizeof(TieChain)) + (size_t)npairs * sizeof(TiePair) + (size_t)(nwin + nchunks) * 4 + 64 * 256;
-    {
-        // the arena has to grow: it moves, so stage 1 runs again in the new one (and later calls ask for this much up front)
-        const bool grow = !walk && fixed_bytes + spec_bytes + ((size_t)1 << 20) > t->tie_cap;
-        int oom = 0;
-        if (grow) {
-            t->tie_hint = fixed_bytes + spec_bytes + ((size_t)1 << 20);
-            if (tie_arena_reserve(t, t->tie_hint)) oom = 1;
-        }
-        if (sharded) {
-            // spec_bytes and the free memory differ from rank to rank, the exchange below does not: the out-of-memory decision is taken by ALL ranks
-            // (a rank that fell back to the walk on its own would leave the others waiting in the all-to-all -- and the walk sums its own documents
-            // only).  One 4-byte all-reduce per resolution of a sharded run.
-            if (!t->d_tie_flag) RL_HIP(t->pool.alloc(&t->d_tie_flag, (size_t)4));
-            int32_t *d_oom = t->d_tie_flag;
-            RL_HIP(hipMemcpyAsync(d_oom, &oom, sizeof(oom), hipMemcpyHostToDevice, s));
-            int rcd = t->dist->allreduce(d_oom, 1, DT_I32, OP_MAX, s);
-            if (rcd) return rcd;
-            int32_t any = 0;
-            RL_HIP(hipMemcpyAsync(&any, d_oom, sizeof(any), hipMemcpyDeviceToHost, s));
-            RL_HIP(hipStreamSynchronize(s));
-            if (any) return fail(RL_ERR_HIP, "tie-break: out of device memory on a rank of the job (the sharded tie-break needs the gathered chains on every rank)");
-            if (grow) { int rc1 = stage1(); if (rc1) return rc1; }
-        } else if (grow) {
-            if (oom) {      // no room for the contiguous chains: the literal walk in a minimal arena
-                walk = true;
-                if (tie_arena_reserve(t, fixed_bytes + ((size_t)1 << 20))) return fail(RL_ERR_HIP, "tie-break: out of device memory");
-            }
-            int rc1 = stage1(); if (rc1) return rc1;
-        }
-    }
-    if (walk) {
-        RL_HIP(hipMemsetAsync(a.jbin, 0, (size_t)nA * c.F * c.TS * sizeof(double), s));
-        hipLaunchKernelGGL(k_tie_jsum, dim3(c.F, nbg + 1, nA), dim3(64), 0, s, c, a, nbg);
-    } else {
-        SpArgs sp; memset(&sp, 0, sizeof(sp));
-        sp.nchains = nch; sp.nwin = nwin; sp.nchunks = nchunks; sp.npairs = npairs; sp.tiles_max = tiles_max;
-        std::vector<char> &blob = t->tie_blob; blob.clear();
-        auto put = [&](const void *src, size_t bytes) { const size_t o = (blob.size() + 15) & ~(size_t)15; blob.resize(o + bytes); if (bytes) memcpy(blob.data() + o, src, bytes); return o; };
-        const size_t o_pairs = put(pairs.data(), npairs * sizeof(TiePair)), o_chs = put(chs.data(), nch * sizeof(TieChain));
-        const size_t o_winc = put(win_chain.data(), nwin * sizeof(int32_t)), o_chunkc = put(chunk_chain.data(), nchunks * sizeof(int32_t));
-        std::vector<long long> m0s((size_t)npairs); std::vector<int32_t> pair_a((size_t)npairs);
-        for (int p2 = 0; p2 < npairs; p2++) { m0s[p2] = pairs[p2].m0; pair_a[p2] = pairs[p2].a; }
-        const size_t o_m0 = put(m0s.data(), npairs * sizeof(long long)), o_paira = put(pair_a.data(), npairs * sizeof(int32_t));
-        char *d_blob = ar.take<char>(blob.size() + 16);
-        RL_HIP(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-        TiePair *d_pairs = (TiePair *)(d_blob + o_pairs); TieChain *d_chs = (TieChain *)(d_blob + o_chs);
-        int32_t *d_winc = (int32_t *)(d_blob + o_winc), *d_chunkc = (int32_t *)(d_blob + o_chunkc);
-        long long *d_m0 = (long long *)(d_blob + o_m0); int32_t *d_paira = (int32_t *)(d_blob + o_paira);
-        (void)d_paira;
-        sp.vals = ar.take<double>(v_total + 1); sp.tbin = ar.take<int32_t>((size_t)npairs * tiles_max * c.TS);
-        sp.wsum = ar.take<double2>(nwin + 1); sp.wpre = ar.take<double2>(nwin + 1);
-        sp.cstart = ar.take<int32_t>(nchunks + 1); sp.cpre = ar.take<double2>(nchunks + 1);
-        sp.centre = ar.take<unsigned long long>(nchunks + 1); sp.table = ar.take<unsigned long long>((size_t)nchunks * kSpW + 1);
-        sp.cstate = ar.take<int32_t>((size_t)nch * 4); sp.ckey = ar.take<unsigned long long>(nch); sp.cshift = ar.take<double>(nch);
-        sp.open = ar.take<int32_t>(4);
-        if (ar.used > t->tie_cap) return fail(RL_ERR_HIP, "tie-break: scratch arena too small (internal error)");
-        sp.pairs = d_pairs; sp.chains = d_chs; sp.win_chain = d_winc; sp.chunk_chain = d_chunkc; sp.u0 = d_u0;
-        sp.mb = ar.take<uint16_t>(m_total + 64);
-        const dim3 ggrid_u(std::min(4096, (maxcnt + kThreads - 1) / kThreads), nA), ggrid_m(std::min(4096, (maxcnt + kThreads - 1) / kThreads), std::max(npairs, 1));
-        if (!sharded) {
-            // one GPU: this rank's members ARE the members -- lambda and bins go straight to their global places
-            hipLaunchKernelGGL(k_tie_gather, ggrid_u, dim3(kThreads), 0, s, c, a, sp.vals, (const long long *)d_u0);
-            if (npairs > 0) hipLaunchKernelGGL(k_tie_gather_bins, ggrid_m, dim3(kThreads), 0, s, c, a, (const TiePair *)d_pairs, sp.mb, (const long long *)d_m0);
-        } else {
-            // sharded: rank order is global document order, so the global arrays are the ranks' pieces behind each other.  Every rank gathers its
-            // own pieces, all ranks exchange them (an all-gather of variable pieces through the all-to-all primitive), and every rank then runs the
-            // SAME evaluation on the same global arrays -- the decision is rank-invariant by construction.
-            std::vector<long long> lu0((size_t)nA), lm0((size_t)std::max(npairs, 1));
-            { long long o = 0; for (int i = 0; i < nA; i++) { lu0[i] = o; o += lcnt[i]; } }
-            { long long o = 0; for (int p2 = 0; p2 < npairs; p2++) { lm0[p2] = o; o += lcnt[pairs[p2].a]; } }
-            long long *d_lu0 = ar.take<long long>(nA), *d_lm0 = ar.take<long long>(std::max(npairs, 1));
-            int32_t *d_lcnt = ar.take<int32_t>(nA), *d_cntR = ar.take<int32_t>((size_t)R * nA);
-            double *d_ul = ar.take<double>(l_u + 8), *d_urecv = ar.take<double>(u_total + 8);
-            uint16_t *d_mbl = ar.take<uint16_t>(l_m + 8), *d_mbrecv = ar.take<uint16_t>(m_total + 8);
-            if (ar.used > t->tie_cap) return fail(RL_ERR_HIP, "tie-break: scratch arena too small (internal error)");
-            RL_HIP(hipMemcpyAsync(d_lu0, lu0.data(), nA * sizeof(long long), hipMemcpyHostToDevice, s));
-            if (npairs > 0) RL_HIP(hipMemcpyAsync(d_lm0, lm0.data(), npairs * sizeof(long long), hipMemcpyHostToDevice, s));
-            RL_HIP(hipMemcpyAsync(d_lcnt, lcnt.data(), nA * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_tie_gather, ggrid_u, dim3(kThreads), 0, s, c, a, d_ul, (const long long *)d_lu0);
-            if (npairs > 0) hipLaunchKernelGGL(k_tie_gather_bins, ggrid_m, dim3(kThreads), 0, s, c, a, (const TiePair *)d_pairs, d_mbl, (const long long *)d_lm0);
-            int rcd = t->dist->allgather(d_lcnt, d_cntR, (size_t)nA * sizeof(int32_t), s);
-            if (rcd) return rcd;
-            std::vector<int32_t> cntR((size_t)R * nA);
-            RL_HIP(hipMemcpyAsync(pin, d_cntR, cntR.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            RL_HIP(hipStreamSynchronize(s));
-            memcpy(cntR.data(), pin, cntR.size() * sizeof(int32_t));
-            std::vector<int64_t> scount(R), sdispl(R, 0), rcount(R), rdispl(R);
-            {   // lambda pieces
-                int64_t o = 0;
-                for (int r = 0; r < R; r++) { int64_t n = 0; for (int i = 0; i < nA; i++) n += cntR[(size_t)r * nA + i]; rcount[r] = n * 8; rdispl[r] = o; o += n * 8; scount[r] = (int64_t)l_u * 8; }
-                if ((size_t)o != u_total * 8) return fail(RL_ERR_COMM, "tie-break: the ranks' member counts do not add up to the nodes' document counts");
-                rcd = t->dist->alltoallv(d_ul, scount.data(), sdispl.data(), d_urecv, rcount.data(), rdispl.data(), s);
-                if (rcd) return rcd;
-                hipLaunchKernelGGL(k_tie_place<double>, dim3(nA, R), dim3(kThreads), 0, s, (const double *)d_urecv, sp.vals, (const int32_t *)d_cntR, (const int32_t *)nullptr,
-                                   (const long long *)d_u0, nA, nA, R);
-            }
-            if (npairs > 0) {   // bins of the pairs
-                int64_t o = 0;
-                for (int r = 0; r < R; r++) { int64_t n = 0; for (int p2 = 0; p2 < npairs; p2++) n += cntR[(size_t)r * nA + pairs[p2].a]; rcount[r] = n * 2; rdispl[r] = o; o += n * 2; scount[r] = (int64_t)l_m * 2; }
-                rcd = t->dist->alltoallv(d_mbl, scount.data(), sdispl.data(), d_mbrecv, rcount.data(), rdispl.data(), s);
-                if (rcd) return rcd;
-                hipLaunchKernelGGL(k_tie_place<uint16_t>, dim3(npairs, R), dim3(kThreads), 0, s, (const uint16_t *)d_mbrecv, sp.mb, (const int32_t *)d_cntR, (const int32_t *)d_paira,
-                                   (const long long *)d_m0, npairs, nA, R);
-            }
-        }
-        hipLaunchKernelGGL(k_ts_count, dim3(tiles_max, npairs), dim3(kThreads), (size_t)c.TS * 4, s, c, a, sp);
-        hipLaunchKernelGGL(k_ts_scan, dim3(npairs, nbg), dim3(64), 0, s, c, a, sp);
-        hipLaunchKernelGGL(k_ts_scatter, dim3(tiles_max, npairs), dim3(kTsWaves * 64), (size_t)kTsWaves * c.TS * 4, s, c, a, sp);
-        const int cb = (nch + kThreads - 1) / kThreads;
-        if (nwin > 0) hipLaunchKernelGGL(k_sp_sum, dim3(nwin), dim3(64), 0, s, sp);
-        hipLaunchKernelGGL(k_sp_scan, dim3(cb), dim3(kThreads), 0, s, sp);
-        if (nwin > 0) hipLaunchKernelGGL(k_sp_bounds, dim3(nwin), dim3(64), 0, s, sp);
-        hipLaunchKernelGGL(k_sp_run<false>, dim3(nchunks), dim3(kSpW), 0, s, sp);
-        hipLaunchKernelGGL(k_sp_drift, dim3(cb), dim3(kThreads), 0, s, sp);
-        hipLaunchKernelGGL(k_sp_run<false>, dim3(nchunks), dim3(kSpW), 0, s, sp);
-        int32_t open = 0;
-        for (int rep = 0; rep <= kSpRepairs; rep++) {
-            RL_HIP(hipMemsetAsync(sp.open, 0, sizeof(int32_t), s));
-            hipLaunchKernelGGL(k_sp_stitch, dim3(cb), dim3(kThreads), 0, s, sp, a, rep == kSpRepairs ? 1 : 0);
-            RL_HIP(hipMemcpyAsync(pin, sp.open, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            RL_HIP(hipStreamSynchronize(s));
-            memcpy(&open, pin, sizeof(open));
-            if (open == 0) break;
-            t->tie_spec_repairs++;
-            hipLaunchKernelGGL(k_sp_run<true>, dim3(nchunks), dim3(kSpW), 0, s, sp);
-        }
-        if (c.steplog) {       // debug statistics (RLHIP_STEPLOG): window misses / serial chunks of this resolution
-            std::vector<int32_t> cst((size_t)nch * 4);
-            RL_HIP(hipMemcpyAsync(cst.data(), sp.cstate, cst.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            RL_HIP(hipStreamSynchronize(s));
-            for (int i = 0; i < nch; i++) { t->tie_spec_miss += cst[4 * (size_t)i + 1]; t->tie_spec_serial += cst[4 * (size_t)i + 2]; }
-        }
-        t->tie_spec_segs += nchunks;
-    }
-    mark(3);
-    // prefixes of all needed rows at once, the tied candidates of all (feature, node) pairs at once, then one block: arg-max, node records, select_step
-    hipLaunchKernelGGL(k_tie_prefix, dim3(c.F, nA), dim3(64), (size_t)c.TS * 8, s, c, a);
-    hipLaunchKernelGGL(k_tie_eval, dim3(c.F, nx), dim3(kFinThreads), 0, s, c, a);
-    hipLaunchKernelGGL(k_tie_finish, dim3(1), dim3(kFinThreads), fin_lds, s, c, a, nodes_in_lds, deferred ? 1 : 0);
-    RL_HIP(hipGetLastError());
-    if (nv > 0 && sharded) {      // every rank checked its own documents: a cut that differs anywhere makes every rank grow the tree again
-        int rcd = t->dist->allreduce(d_vflag, 1, DT_I32, OP_MAX, s);
-        if (rcd) return rcd;
-    }
-    if (nv > 0) RL_HIP(hipMemcpyAsync(pin, d_vflag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    RL_HIP(hipStreamSynchronize(s));
-    mark(4);
-    if (nv > 0 && other_cut) { int32_t fl = 0; memcpy(&fl, pin, sizeof(fl)); *other_cut = (fl != 0) || t->knobs.tie_force_regrow; }
-    t->tie_stalls++; t->tie_nodes += nx; t->tie_chain_nodes += nA; if (deferred) t->tie_batches++;
-    for (auto &A : an) t->tie_chain_docs += A.count;
-    t->tie_us += (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_begin).count();
-    return RL_OK;
-}
-
 }  // namespace rl
 
-#include "rl_round.inc"      // the stages of a boosting round and enqueue_round itself (resolve_ties above is theirs to call)
+#include "rl_tie_host.inc"   // the lazy tie-break's host side: the stages of a resolution and resolve_ties itself (their kernels: rl_tie.inc)
+#include "rl_round.inc"      // the stages of a boosting round and enqueue_round itself (resolve_ties is theirs to call)
 
 namespace rl {
 

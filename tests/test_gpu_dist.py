@@ -101,17 +101,11 @@ def test_one_rank_sharded_path_without_a_progress_word_equals_plain_path(monkeyp
     same(ref, single(*CFG_TIES, dist_mode="cb1"))
 
 
-@pytest.mark.parametrize("world,ranker,metric,k,cfg", [(2, "LAMBDAMART", "NDCG", 10, CFG), (3, "LAMBDAMART", "NDCG", 10, CFG),
-                                                        (2, "MART", "NDCG", 10, CFG), (2, "LAMBDAMART", "MAP", 0, CFG),
-                                                        (3, "LAMBDAMART", "ERR", 10, CFG), (2, "LAMBDAMART", "NDCG", 10, CFG31),
-                                                        (3, "MART", "NDCG", 10, CFG31), (2, "LAMBDAMART", "NDCG", 10, CFG2K),
-                                                        (2, "LAMBDAMART", "NDCG", 10, CFG_TIES), (3, "LAMBDAMART", "NDCG", 10, CFG_TIES),
-                                                        (2, "LAMBDAMART", "NDCG", 10, CFG_BIG), (3, "LAMBDAMART", "NDCG", 10, CFG_BIG)])
-def test_k_shards_equal_one_shard(world, ranker, metric, k, cfg, tmp_path):
+def k_shards_against_one_shard(world, ranker, metric, k, cfg, tmp_path, worker_env=None):
     CFG = cfg
     ref = single(*CFG, ranker=ranker, metric=metric, k=k)
     out = str(tmp_path / "dist.npz")
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", **(worker_env or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(29511 + world), os.path.join(ROOT, "tests", "dist_worker.py"), out] + [str(v) for v in CFG] + [ranker, metric, str(k)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -131,6 +125,22 @@ def test_k_shards_equal_one_shard(world, ranker, metric, k, cfg, tmp_path):
         assert st[3] / rounds <= 0.25 * 16.0 * CFG[0] * (world - 1) / world, st
     # (st[3], the all-gather bytes, also holds rl_init's one-off exchange of the distinct-value sets; the per-round figure is checked through
     # bench.py's counters in test_bench_entry_starts_its_own_ranks)
+
+
+@pytest.mark.parametrize("world,ranker,metric,k,cfg", [(2, "LAMBDAMART", "NDCG", 10, CFG), (3, "LAMBDAMART", "NDCG", 10, CFG),
+                                                        (2, "MART", "NDCG", 10, CFG), (2, "LAMBDAMART", "MAP", 0, CFG),
+                                                        (3, "LAMBDAMART", "ERR", 10, CFG), (2, "LAMBDAMART", "NDCG", 10, CFG31),
+                                                        (3, "MART", "NDCG", 10, CFG31), (2, "LAMBDAMART", "NDCG", 10, CFG2K),
+                                                        (2, "LAMBDAMART", "NDCG", 10, CFG_TIES), (3, "LAMBDAMART", "NDCG", 10, CFG_TIES),
+                                                        (2, "LAMBDAMART", "NDCG", 10, CFG_BIG), (3, "LAMBDAMART", "NDCG", 10, CFG_BIG)])
+def test_k_shards_equal_one_shard(world, ranker, metric, k, cfg, tmp_path):
+    k_shards_against_one_shard(world, ranker, metric, k, cfg, tmp_path)
+
+
+def test_sharded_tie_break_with_a_rank_that_grows_its_arena(tmp_path):
+    """RLHIP_TIE_SLACK=0 in the workers: the first reservation has no room for the gathered chains, so ranks grow their arenas and run stage 1 again
+    between the collectives of a resolution -- the out-of-memory vote is still one all-reduce on every rank, and two shards equal one"""
+    k_shards_against_one_shard(2, "LAMBDAMART", "NDCG", 10, CFG_TIES, tmp_path, worker_env={"RLHIP_TIE_SLACK": "0"})
 
 
 @pytest.mark.parametrize("world,metric,k,opt", [(2, "NDCG", 10, "noa2a"), (3, "NDCG", 10, "piecemiss"), (2, "NDCG", 10, "countpass,ownerx"), (3, "NDCG", 10, "ownerx"), (2, "NDCG", 10, "ownerx,noa2a"), (3, "NDCG", 10, "leafm1"), (2, "NDCG", 10, "qrel"), (3, "MAP", 0, "qrel"),

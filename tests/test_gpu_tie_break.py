@@ -40,6 +40,46 @@ def same_trees(a, b):
         assert np.array_equal(x["output"].view(np.uint32), y["output"].view(np.uint32))
 
 
+def run_env(env, *args, **kw):
+    """run() under the environment knobs of `env` (a handle reads its knobs when it is created)"""
+    with pytest.MonkeyPatch.context() as mp:
+        for name, value in env.items():
+            mp.setenv(name, value)
+        return run(*args, **kw)
+
+
+@pytest.fixture(scope="module")
+def small_chains():
+    """2 500 documents, five features, 31 leaves: exact ties in every round, every chain far below RLHIP_TIE_WALK_MAX.  The default run (against the
+    oracle: every resolution walks) and the run that sends the same resolutions through the speculative chains, computed once"""
+    data = synth.make_dataset(2500, 5, "mslr", seed_offset=4)
+    walked = run(*data, 4, 31)
+    spec = run_env({"RLHIP_TIE_WALK_MAX": "0"}, *data, 4, 31, oracle=False)
+    return data, walked, spec
+
+
+def test_small_chains_through_the_speculative_path_equal_the_walk(small_chains):
+    """RLHIP_TIE_WALK_MAX=0 on nodes of a few hundred documents: chains shorter than one window, empty bins as chains of no value, the k_ts_* sort on
+    a fraction of a tile -- the same resolutions, the walk's trees and scores"""
+    _, (trees, ties, st, sc), (trees_s, _, st_s, sc_s) = small_chains
+    assert ties == 0
+    assert st[0] > 0 and st[5] == 0, st                                # resolutions ran, every one of them walked
+    assert st_s[0] == st[0] and st_s[5] > 0, (st, st_s)                # the same resolutions, through speculative chunks
+    same_trees(trees, trees_s)
+    assert np.array_equal(sc.view(np.int64), sc_s.view(np.int64))
+
+
+def test_scratch_arena_that_has_to_grow_runs_stage_one_again(small_chains):
+    """RLHIP_TIE_SLACK=0: the first reservation holds stage 1's arrays and a quarter more, the chunk tables of hundreds of per-bin chains (2 KB a chunk)
+    do not fit -- the arena grows, moves, and stage 1 runs again in the new one.  The same trees, scores, resolutions and chunks"""
+    data, (trees, _, st, sc), (trees_s, _, st_s, sc_s) = small_chains
+    trees_g, _, st_g, sc_g = run_env({"RLHIP_TIE_WALK_MAX": "0", "RLHIP_TIE_SLACK": "0"}, *data, 4, 31, oracle=False)
+    for ref_trees, ref_sc in ((trees, sc), (trees_s, sc_s)):
+        same_trees(ref_trees, trees_g)
+        assert np.array_equal(ref_sc.view(np.int64), sc_g.view(np.int64))
+    assert st_g[0] == st[0] == st_s[0] and st_g[5] == st_s[5], (st, st_s, st_g)
+
+
 def test_long_chains_speculative_evaluation_equals_the_literal_walk_and_the_oracle(monkeypatch):
     """150 k documents, deep trees with a large minimum leaf support removed: derivation chains of 10^5 documents are cut into many chunks
     (windows of 2048 values), run from 256 candidate states, stitched -- and must give what the literal walk and the oracle give"""
@@ -121,6 +161,18 @@ def test_ties_over_several_features_that_share_one_cut_are_deferred_not_stalled(
     assert ties_s == 0 and st_s[0] > 3 * st[0], (st, st_s)
     same_trees(trees, trees_s)
     assert np.array_equal(sc.view(np.int64), sc_s.view(np.int64))
+
+
+def test_deferred_batch_with_verified_nodes_through_the_speculative_path_in_a_grown_arena():
+    """the per-tree batch of the duplicated columns (k_tie_verify's nodes among it) with RLHIP_TIE_WALK_MAX=0 and RLHIP_TIE_SLACK=0: the verification's
+    lists and flag are taken again in the arena that moved -- the default run's trees and scores"""
+    X, lab, qoff = duplicate_columns(31)
+    trees, _, st, sc = run(X, lab, qoff, 5, 31, oracle=False)
+    trees_g, _, st_g, sc_g = run_env({"RLHIP_TIE_WALK_MAX": "0", "RLHIP_TIE_SLACK": "0"}, X, lab, qoff, 5, 31, oracle=False)
+    assert st[8] > 0 and st_g[8] > 0, (st, st_g)                       # batches at the end of trees, in both runs
+    assert st_g[5] > 0, st_g                                           # ... through speculative chunks
+    same_trees(trees, trees_g)
+    assert np.array_equal(sc.view(np.int64), sc_g.view(np.int64))
 
 
 def test_a_tree_whose_deferred_tie_fails_the_check_is_grown_again(monkeypatch):
