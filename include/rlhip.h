@@ -61,8 +61,15 @@ enum { RL_METRIC_NDCG = 0, RL_METRIC_DCG = 1, RL_METRIC_MAP = 2, RL_METRIC_ERR =
 enum { RL_RANKER_MART = 0, RL_RANKER_LAMBDAMART = 6 };
 
 enum {                                  /* rl_params.flags */
-                                        /* bit 0 is reserved (rl_create rejects it): leaf outputs are always the Java's float running sums
-                                           (learning/tree/LambdaMART.java:401-408); there is no non-parity shortcut */
+    RL_FLAG_FAST_LEAF = 1,              /* opt-in, off by default: the two sums behind every leaf output are a fixed f64 reduction -- tiles of 256 samples in
+                                           ascending sample order, each folded in halves (a[i] += a[i + s], s = 128 .. 1), the tile results folded the same way until
+                                           one value is left, then rounded to float -- instead of the Java's float running sums (learning/tree/
+                                           LambdaMART.java:401-408), which stay the default and bit-exact.  Deterministic and independent of any launch shape; two
+                                           launches instead of about ten a round.  Leaf values differ from the reference's in their last bits (measured: DESIGN.md
+                                           14), so later rounds may grow other trees; the per-round metric stays the exact float chain.  One GPU
+                                           only: rl_dist_init* is RL_ERR_UNSUPPORTED (an f64 sum over ranks is not rank-count-invariant).  Not with
+                                           RL_FLAG_JAVA_ORDER (the strict mode is a parity instrument) nor RL_FLAG_SERIAL_CHAIN: RL_ERR_INVALID at rl_create.
+                                           Independent of RL_FLAG_FIRST_TIE; the two together are the speed-first setting. */
     RL_FLAG_TIMING = 2,                 /* record HIP events around the root histogram and the lambda kernels (rl_get_timing) */
     RL_FLAG_TIMING_NODES = 8,           /* ... and around every growth step's node-histogram launch (30 event pairs per round) */
     RL_FLAG_SERIAL_CHAIN = 4,           /* evaluate the float running sums with the literal serial kernel instead of
@@ -322,6 +329,10 @@ int rl_debug_rho(const double *x, const double *den, int32_t n, double *out_fast
  * :474-483) on arbitrary data: n doubles cut into n_seg segments (seg_start[0] = 0 ... seg_start[n_seg] = n), out[s] = the float
  * sum of segment s.  stats (may be null): int32[4] = segments evaluated, window misses repaired, segments finished serially, 0. */
 int rl_debug_float_chain(int32_t device, const double *x, int64_t n, const int64_t *seg_start, int32_t n_seg, float *out, int32_t *stats);
+/* RL_FLAG_FAST_LEAF's reduction on arbitrary data, by the trainer's own two kernels over the identity sample list: n doubles cut into n_seg
+ * segments as above, out_f64[s] = R of segment s (0.0 for an empty one), out_f32[s] = (float) out_f64[s], the value a leaf
+ * output is computed from.  Either output may be NULL. */
+int rl_debug_fast_sum(int32_t device, const double *x, int64_t n, const int64_t *seg_start, int32_t n_seg, double *out_f64, float *out_f32);
 int rl_bin_stride(const rl_trainer *t, int32_t *stride);
 /* Histogram features of an initialised trainer and the column (0-based position in feature_ids) behind each.  Equal to the data set's features
  * unless a threshold table has more than 4095 entries (-tc -1 on a column with that many distinct values, or -tc N > 4095: learning/tree/

@@ -81,6 +81,7 @@ class RlTree(C.Structure):
 
 
 RL_FLAG_TIMING, RL_FLAG_SERIAL_CHAIN, RL_FLAG_TIMING_NODES, RL_FLAG_JAVA_ORDER, RL_FLAG_FIRST_TIE = 2, 4, 8, 16, 32
+RL_FLAG_FAST_LEAF = 1      # leaf sums as the fixed f64 reduction of DESIGN.md 14 instead of the Java's float running sums (opt-in, one GPU)
 ARR = dict(LAMBDA=1, WEIGHT=2, SCORE=3, VALID_SCORE=4, NBINS=5, THRESHOLDS=6, BINS=7, ROOT_COUNT=8, ROOT_SUM=9,
            QUANT=10, ROOT_SUM_FIXED=11, NDCG_PER_QUERY=12, CHAIN_STATS=13, CHAIN_MISS=14, GROW_STATS=15, PHASE_CLOCKS=16,
            ROOT_SUM_JAVA=17, GROW_DOCS=18, SPARSE_INFO=19, STEP_LOG=20, TIE_STATS=21, BLOCK_TRACE=22, BUBBLES=23, PIECE_STATS=24)
@@ -92,7 +93,7 @@ ABI_SYMBOLS = [
     "rl_set_train", "rl_set_validation", "rl_set_rows", "rl_set_external_judgments", "rl_init", "rl_boost_round", "rl_boost_rounds_async", "rl_sync",
     "rl_finish", "rl_num_trees", "rl_get_tree", "rl_get_round_metrics", "rl_best_validation", "rl_predict",
     "rl_model_to_text", "rl_model_from_text", "rl_model_destroy", "rl_model_num_trees", "rl_model_features",
-    "rl_model_predict", "rl_model_predict_device", "rl_model_debug_path", "rl_dist_unique_id", "rl_dist_init", "rl_dist_init_callback", "rl_dist_stats", "rl_bin_stride", "rl_hist_features", "rl_quant_exponent", "rl_get_array", "rl_debug_exp", "rl_debug_rho", "rl_debug_float_chain",
+    "rl_model_predict", "rl_model_predict_device", "rl_model_debug_path", "rl_dist_unique_id", "rl_dist_init", "rl_dist_init_callback", "rl_dist_stats", "rl_bin_stride", "rl_hist_features", "rl_quant_exponent", "rl_get_array", "rl_debug_exp", "rl_debug_rho", "rl_debug_float_chain", "rl_debug_fast_sum",
     "rl_letor_parse", "rl_letor_info", "rl_letor_arrays", "rl_letor_rows", "rl_letor_destroy",
     "rl_get_timing", "rl_reset_timing", "rl_set_timing_flags", "rl_debug_membench", "rl_set_err_max", "rl_tree_capacity",
     "rl_ca_params_default", "rl_ca_create", "rl_ca_destroy", "rl_ca_set_train", "rl_ca_set_validation", "rl_ca_set_external_judgments",
@@ -169,6 +170,8 @@ def lib():
     if hasattr(L, "rl_debug_rho"):      # (A/B builds of older sources selected with RLHIP_LIB lack the probe; tests/test_abi.py checks the in-tree library's exports)
         L.rl_debug_rho.argtypes = [vp, vp, i32, vp, vp]
     L.rl_debug_float_chain.argtypes = [i32, vp, i64, vp, i32, vp, vp]
+    if hasattr(L, "rl_debug_fast_sum"):      # (A/B builds of older sources lack it)
+        L.rl_debug_fast_sum.argtypes = [i32, vp, i64, vp, i32, vp, vp]
     L.rl_letor_parse.argtypes = [vp, i64, C.POINTER(vp)]
     L.rl_letor_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)]
     L.rl_letor_arrays.argtypes = [vp] * 10
@@ -313,6 +316,17 @@ def debug_float_chain(x, seg_start=None, device=0):
     stats = np.zeros(4, np.int32)
     check(lib().rl_debug_float_chain(device, x.ctypes.data, len(x), seg.ctypes.data, len(seg) - 1, out.ctypes.data, stats.ctypes.data))
     return out, stats
+
+
+def debug_fast_sum(x, seg_start=None, device=0):
+    """RL_FLAG_FAST_LEAF's fixed f64 reduction R of the segments of x on the GPU (rl_fast_leaf.inc, the trainer's two kernels over the
+    identity list); returns (float64 R per segment, its float32 rounding)."""
+    x = np.ascontiguousarray(x, np.float64)
+    seg = np.ascontiguousarray([0, len(x)] if seg_start is None else seg_start, np.int64)
+    out64 = np.zeros(len(seg) - 1, np.float64)
+    out32 = np.zeros(len(seg) - 1, np.float32)
+    check(lib().rl_debug_fast_sum(device, x.ctypes.data, len(x), seg.ctypes.data, len(seg) - 1, out64.ctypes.data, out32.ctypes.data))
+    return out64, out32
 
 
 def set_err_max(max_gain):

@@ -74,6 +74,38 @@ int rl_debug_float_chain(int32_t device, const double *x, int64_t n, const int64
     return RL_OK;
 }
 
+int rl_debug_fast_sum(int32_t device, const double *x, int64_t n, const int64_t *seg_start, int32_t n_seg, double *out_f64, float *out_f32)
+{
+    if ((!x && n > 0) || !seg_start || n < 0 || n_seg < 1 || n > 2147483647 / 2) return fail(RL_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n_seg; i++) if (seg_start[i] > seg_start[i + 1]) return fail(RL_ERR_INVALID, "segments must be ascending");
+    if (seg_start[0] != 0 || seg_start[n_seg] != n) return fail(RL_ERR_INVALID, "segments must cover [0, n)");
+    RL_HIP(hipSetDevice(device));
+    DevPool pool;
+    // both value arrays carry x: the two sums of a leaf go through the same instructions side by side, and must come out equal
+    std::vector<double2> pair((size_t)n);
+    for (int64_t i = 0; i < n; i++) pair[(size_t)i] = make_double2(x[i], x[i]);
+    std::vector<int32_t> ss((size_t)n_seg + 1);
+    for (int i = 0; i <= n_seg; i++) ss[i] = (int32_t)seg_start[i];
+    double2 *d_pair = nullptr, *d_part = nullptr, *d_sums = nullptr; int32_t *d_ss = nullptr;
+    const int64_t slots = fast_leaf_slots(n, n_seg);
+    RL_HIP(pool.alloc(&d_pair, (size_t)n)); RL_HIP(pool.alloc(&d_part, (size_t)slots)); RL_HIP(pool.alloc(&d_sums, (size_t)n_seg)); RL_HIP(pool.alloc(&d_ss, ss.size()));
+    if (n > 0) RL_HIP(hipMemcpy(d_pair, pair.data(), (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(d_ss, ss.data(), ss.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    const FastLeafArgs fa{d_pair, nullptr, nullptr, nullptr, d_ss, nullptr, n_seg, nullptr, d_part, (int32_t)slots, d_sums, nullptr, nullptr, 0};
+    hipLaunchKernelGGL(k_fast_leaf_tiles, dim3((unsigned)slots), dim3(kFastTile), 0, 0, fa);
+    hipLaunchKernelGGL(k_fast_leaf_finish, dim3((unsigned)n_seg), dim3(kFastTile), 0, 0, fa);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipDeviceSynchronize());
+    std::vector<double2> sums((size_t)n_seg);
+    RL_HIP(hipMemcpy(sums.data(), d_sums, (size_t)n_seg * sizeof(double2), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_seg; i++) {
+        if (memcmp(&sums[i].x, &sums[i].y, sizeof(double)) != 0) return fail(RL_ERR_HIP, "rl_debug_fast_sum: the two sums of segment " + std::to_string(i) + " differ (internal error)");
+        if (out_f64) out_f64[i] = sums[i].x;
+        if (out_f32) out_f32[i] = (float)sums[i].x;
+    }
+    return RL_OK;
+}
+
 int rl_debug_membench(int32_t device, int32_t mode, int64_t bytes, int32_t stride, int32_t iters, double *avg_ms, double *alg_bytes)
 {
     if (!avg_ms || bytes < 4096 || iters < 1 || mode < 0 || mode > 9 || (mode == 3 && stride < 1)) return fail(RL_ERR_INVALID, "bad argument");

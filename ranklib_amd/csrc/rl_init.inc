@@ -770,6 +770,10 @@ static int init_dist_state(rl_trainer *t, InitWork &w)
     rc = alloc_chain(t, t->metric_chain, 1, 1, std::max(t->Qglobal, t->has_valid ? std::max(t->va.Q, t->vQglobal) : 0));
     if (rc) return rc;
     RL_HIP(t->pool.alloc(&t->d_seg_buf, (size_t)c.MAXN + 2));
+    if (t->p.flags & RL_FLAG_FAST_LEAF) {       // rl_fast_leaf.inc: one partial per tile slot, one pair of sums per leaf (one GPU: rl_dist_init* refuses the flag)
+        t->fast_slots = fast_leaf_slots(N, c.MAXN + 1);
+        RL_HIP(t->pool.alloc(&t->d_fast_part, (size_t)t->fast_slots)); RL_HIP(t->pool.alloc(&t->d_fast_sums, (size_t)c.MAXN + 1));
+    }
     if (t->dist) {
         t->lsstride = c.MAXN + 2;
         // piece mode (rl_dist.inc): the leaves' float chains from every rank's own pieces; the leaf-owner exchange for what it does not cover

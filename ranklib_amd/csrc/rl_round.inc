@@ -363,6 +363,15 @@ static int enqueue_leaf_outputs(rl_trainer *t, bool stream_scores)
         hipLaunchKernelGGL(k_leaf_chain, dim3(c.L), dim3(64), 0, s, c);
         return RL_OK;
     }
+    if (t->p.flags & RL_FLAG_FAST_LEAF) {
+        // rl_fast_leaf.inc: the fixed f64 reduction over the leaf table k_leaf_table has just written; level 0 leaves every document's leaf behind
+        // exactly as the float chains' gather does, so the score update takes the same kernel as in the default mode (the same bits either way)
+        const FastLeafArgs fa{c.lw, c.idx[0], c.idx[1], t->d_seg_buf, c.leaf_start, &c.st->n_leaves, c.MAXN + 1, stream_scores ? c.leaf_of : nullptr,
+                              t->d_fast_part, (int32_t)t->fast_slots, t->d_fast_sums, c.nodes, c.leaf_node, c.mart};
+        hipLaunchKernelGGL(k_fast_leaf_tiles, dim3((unsigned)t->fast_slots), dim3(kFastTile), 0, s, fa);
+        hipLaunchKernelGGL(k_fast_leaf_finish, dim3((unsigned)(c.MAXN + 1)), dim3(kFastTile), 0, s, fa);
+        return RL_OK;
+    }
     const ChainSource src{nullptr, nullptr, c.lw, c.idx[0], c.idx[1], t->d_seg_buf, stream_scores ? c.leaf_of : nullptr};
     const ChainBufs *sums = &t->leaf_chain;
     if (t->dist && t->piece_chains) {      // round 6: every rank evaluates its own pieces of every leaf, only tables travel (rl_dist.inc)

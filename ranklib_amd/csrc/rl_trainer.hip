@@ -22,6 +22,7 @@
 #include "rl_kernels_init.inc"
 #include "rl_chain.inc"
 #include "rl_kernels_round.inc"
+#include "rl_fast_leaf.inc"
 #include "rl_step2.inc"
 #include "rl_java_order.inc"
 #include "rl_csc.inc"
@@ -128,6 +129,7 @@ struct rl_trainer {
     float *d_final_f = nullptr; double *d_final_d = nullptr, *d_mean = nullptr;
     ChainBufs leaf_chain, metric_chain;      // exact parallel float chains (rl_chain.inc)
     int32_t *d_seg_buf = nullptr;
+    double2 *d_fast_part = nullptr, *d_fast_sums = nullptr; int64_t fast_slots = 0;      // RL_FLAG_FAST_LEAF (rl_fast_leaf.inc): tile partials [fast_slots], R of every leaf [MAXN + 1]
     double2 *d_T = nullptr;                  // pair terms of the lambda computation [N][k]
     double *d_wmax = nullptr;                // per-block max |lambda| of the lambda launches
     float *d_vmetric = nullptr;
@@ -855,7 +857,11 @@ int rl_create(const rl_params *p, rl_trainer **out)
     if (p->min_leaf_support < 1) return fail(RL_ERR_INVALID, "min_leaf_support must be >= 1");
     if (p->n_threshold != -1 && (p->n_threshold < 1 || p->n_threshold > (1 << 24)))
         return fail(RL_ERR_UNSUPPORTED, "n_threshold must be -1 or in [1, 2^24]");
-    if (p->flags & ~(RL_FLAG_TIMING | RL_FLAG_TIMING_NODES | RL_FLAG_SERIAL_CHAIN | RL_FLAG_JAVA_ORDER | RL_FLAG_FIRST_TIE)) return fail(RL_ERR_INVALID, "unknown bit in rl_params.flags");
+    if (p->flags & ~(RL_FLAG_FAST_LEAF | RL_FLAG_TIMING | RL_FLAG_TIMING_NODES | RL_FLAG_SERIAL_CHAIN | RL_FLAG_JAVA_ORDER | RL_FLAG_FIRST_TIE)) return fail(RL_ERR_INVALID, "unknown bit in rl_params.flags");
+    if ((p->flags & RL_FLAG_FAST_LEAF) && (p->flags & RL_FLAG_JAVA_ORDER))
+        return fail(RL_ERR_INVALID, "RL_FLAG_FAST_LEAF with RL_FLAG_JAVA_ORDER: the strict mode is a parity instrument, its leaves are the Java's float running sums");
+    if ((p->flags & RL_FLAG_FAST_LEAF) && (p->flags & RL_FLAG_SERIAL_CHAIN))
+        return fail(RL_ERR_INVALID, "RL_FLAG_FAST_LEAF with RL_FLAG_SERIAL_CHAIN: the serial kernel evaluates the float running sums that the fast mode replaces");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
@@ -1222,6 +1228,9 @@ static int dist_precheck(rl_trainer *t, int32_t rank, int32_t n_ranks)
     if (check_trainer(t)) return RL_ERR_INVALID;
     if (t->inited) return fail(RL_ERR_STATE, "rl_dist_init must be called before rl_init");
     if (n_ranks < 1 || n_ranks > 64 || rank < 0 || rank >= n_ranks) return fail(RL_ERR_INVALID, "bad rank / n_ranks (1..64 ranks)");
+    if (t->p.flags & RL_FLAG_FAST_LEAF)
+        return fail(RL_ERR_UNSUPPORTED, "RL_FLAG_FAST_LEAF with sharded training: an f64 sum over ranks is not rank-count-invariant (the leaf values would depend on "
+                                        "how the queries are sharded); train on one GPU, or without the flag");
     return RL_OK;
 }
 

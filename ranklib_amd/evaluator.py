@@ -204,7 +204,7 @@ def main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
               "(-load also reads RankNet, LambdaRank and ListNet models; they are scored, not trained)")
         return 0
@@ -212,6 +212,7 @@ def main(argv=None):
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False                             # :86
     Evaluator.qrelFile = ""
+    LambdaMART.fastLeaf = False                             # -fastleaf (rlhip extension)
     rankerType = 4                                          # the reference's default is Coordinate Ascent (:83)
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)
     ttSplit = tvSplit = 0.0
@@ -258,6 +259,7 @@ def main(argv=None):
                 raise RankLibError("%s cannot be bagged. Random Forests only supports MART/LambdaMART." % rt)
             RFRanker.rType = RankerType(rt)
         elif a == "-seed": RFRanker.seed = FeatureHistogram.seed = CoorAscent.seed = int(nxt())     # rlhip extension: the Java draws are unseeded
+        elif a == "-fastleaf": LambdaMART.fastLeaf = True   # rlhip extension: RL_FLAG_FAST_LEAF for -ranker 6 / 0 / 8 (leaf values within tolerance, not bit for bit)
         elif a == "-thread": nxt()                          # CPU thread pool of the reference: irrelevant here
         elif a == "-tts": ttSplit = float(nxt())            # :245-250
         elif a == "-tvs": tvSplit = float(nxt())

@@ -278,6 +278,8 @@ class LambdaMART(Ranker):
     nTreeLeaves = 10
     minLeafSupport = 1
     device = 0
+    fastLeaf = False          # not in the Java (-fastleaf): leaf sums as the fixed f64 reduction of RL_FLAG_FAST_LEAF instead of the float running
+                              # sums of :401-408; inherited by MART and, through these classes, by the bags of Random Forests
     _RANKER = "LAMBDAMART"
 
     def __init__(self, samples=None, features=None, scorer=None):
@@ -300,7 +302,7 @@ class LambdaMART(Ranker):
         N.set_err_max(ERRScorer.MAX)              # the reference's static ERRScorer.MAX (-gmax) reaches the kernels through the library's static
         t = N.Trainer(n_trees=cls.nTrees, n_leaves=cls.nTreeLeaves, learning_rate=cls.learningRate, n_threshold=cls.nThreshold,
                       min_leaf_support=cls.minLeafSupport, early_stop_rounds=cls.nRoundToStopEarly, metric_k=self.scorer.getK(),
-                      device=cls.device, metric=metric, ranker=self._RANKER,
+                      device=cls.device, metric=metric, ranker=self._RANKER, flags=N.RL_FLAG_FAST_LEAF if cls.fastLeaf else 0,
                       feature_sampling_rate=FeatureHistogram.samplingRate, seed=FeatureHistogram.seed)
         t.set_train(X, lab, qoff, feature_ids=self.features, qkey=qkey)
         if self.validationSamples is not None:
