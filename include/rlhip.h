@@ -51,7 +51,8 @@ enum {
     RL_ERR_STATE = -3,       /* call out of order (e.g. rl_boost_round before rl_init) */
     RL_ERR_UNSUPPORTED = -4, /* valid for RankLib but not built yet (documented in DESIGN.md) */
     RL_ERR_NO_DEVICE = -5,   /* no gfx950 device visible: there is NO CPU fallback */
-    RL_ERR_COMM = -6         /* RCCL failure */
+    RL_ERR_COMM = -6,        /* RCCL failure */
+    RL_ERR_NO_BEST = -7      /* rl_ln_learn with a validation set: no epoch scored above 0.0, no model was saved (the Java throws) */
 };
 
 /* train / validation metric (-metric2t): metric/{NDCG,DCG,AP,ERR}Scorer.java.  P, RR and BEST are not built for
@@ -581,7 +582,7 @@ int  rl_lr_predict(int32_t device, const int32_t *feature_ids, int32_t n_feature
 
 /* ---- Neural-net models (RankNet -ranker 1, LambdaRank 5, ListNet 7: learning/neuralnet/) ---------------------------------
  * Scoring only: the forward pass RankNet.eval (RankNet.java:336-349), which LambdaRank and ListNet inherit, with the Java's double
- * arithmetic kept bit for bit.  Training these rankers is not built.  The network is the one RankNet.wire() (:87-110)
+ * arithmetic kept bit for bit.  Training is built for ListNet only (below).  The network is the one RankNet.wire() (:87-110)
  * makes: layer 0 holds the n_features inputs and a bias neuron of output 1.0, then come the hidden layers, then one output neuron;
  * every neuron past layer 0 computes 1.0 / (1.0 + exp(-wsum)) (LogiFunction.java:18-20) of wsum = 0.0, += source.output * weight over
  * its inLinks in order (Neuron.computeOutput, Neuron.java:68-76): the previous layer's neurons in order, the bias LAST. */
@@ -607,6 +608,56 @@ int  rl_net_predict(rl_net *net, const float *X, int64_t n_docs, int32_t row_str
 int  rl_net_predict_device(rl_net *net, const float *dX, int64_t n_docs, int32_t row_stride, double *dOut, void *stream);
 /* debug: RL_NET_PATH_* of the last predict call (Neuron.computeOutput :68-76 is the same arithmetic in both kernels) */
 int  rl_net_debug_path(const rl_net *net, int32_t *path);
+
+/* ---- ListNet training (-ranker 7, learning/neuralnet/ListNet.java, ListNeuron.java) --------------------------------------
+ * ListNet.learn() (:101-140) with the Java's double arithmetic kept bit for bit: n_features inputs and a bias neuron feed
+ * one logistic output neuron, and the n_features + 1 weights are updated once per ranked list, list after list, for n_epochs epochs.
+ * After every epoch both sets are scored and ranked; with a validation set the weights of the epoch whose score is strictly above every
+ * earlier one (and above 0.0) are kept and restored after the last epoch.  The Java draws the start weights from an unseeded Random:
+ * here the caller gives them (rl_ln_set_weights), the library never sees a seed.  Train metrics as rl_ca.  Weights that are not all
+ * finite after an epoch are RL_ERR_UNSUPPORTED (the message names the epoch); a validation set on which no epoch scores above 0.0 is
+ * RL_ERR_NO_BEST (the Java's restoreBestModelOnValidation throws). */
+typedef struct rl_ln rl_ln;             /* opaque */
+
+typedef struct {
+    int32_t  n_epochs;          /* ListNet.nIteration       default 1500 (-epoch); < 0: RL_ERR_INVALID */
+    double   learning_rate;     /* Neuron.learningRate as ListNet.init() sets it, default 0.00001; not finite: RL_ERR_INVALID */
+    int32_t  metric;            /* RL_METRIC_*: NDCG, DCG, MAP, ERR, P, RR */
+    int32_t  metric_k;          /* the scorer's k (10; 0 for MAP) */
+    int32_t  device;            /* HIP device ordinal */
+    double   err_max;           /* ERRScorer.MAX (-gmax): default 16 */
+} rl_ln_params;
+
+typedef struct {
+    int32_t epoch;              /* 1 .. n_epochs */
+    int32_t saved;              /* 1 if this epoch became the best on validation */
+    double  train;              /* scorer.score(rank(samples)) after the epoch, not rounded */
+    double  valid;              /* the same on the validation set (0 without one) */
+} rl_ln_trace_rec;
+
+void rl_ln_params_default(rl_ln_params *p);         /* 1500, 0.00001, NDCG@10, device 0, err_max 16 */
+int  rl_ln_create(const rl_ln_params *p, rl_ln **out);
+void rl_ln_destroy(rl_ln *h);
+/* X: [n_docs][n_features] row-major, column k = the value input neuron k reads (getFeatureValue(features[k])); cells as rl_ca_set_train */
+int  rl_ln_set_train(rl_ln *h, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
+                     int32_t n_queries, const int32_t *qkey);
+int  rl_ln_set_validation(rl_ln *h, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
+                          const int32_t *qkey);
+int  rl_ln_set_external_judgments(rl_ln *h, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count);
+/* the start weights in inLinks order: inputs 0 .. n_features - 1, the bias last.  n != n_features + 1 is RL_ERR_INVALID.  Required
+ * before the handle learns (without them, or without a training set, learning is RL_ERR_INVALID); a later set_train discards them */
+int  rl_ln_set_weights(rl_ln *h, const double *w, int32_t n);
+int  rl_ln_learn(rl_ln *h);
+/* after learning: the restored best on validation, or the last epoch's.  w may be NULL (only *n is set); at most cap entries are written */
+int  rl_ln_get_weights(const rl_ln *h, double *w, int32_t cap, int32_t *n);
+/* train / valid: scorer.score(rank(.)) of those weights (not rounded; valid is 0 without a validation set) */
+int  rl_ln_scores(const rl_ln *h, double *train, double *valid);
+/* one record per epoch; out may be NULL (only *n is set); at most cap records are written */
+int  rl_ln_trace(const rl_ln *h, rl_ln_trace_rec *out, int64_t cap, int64_t *n);
+/* debug: the final weights' output for every document of the training (validation != 0: validation) set, as the scoring kernel wrote it */
+int  rl_ln_debug_doc_scores(const rl_ln *h, int32_t validation, double *out, int64_t cap);
+/* debug: ms of all epoch kernels together (device events) and of scoring + ranking both sets after every epoch (host clock) */
+int  rl_ln_debug_times(const rl_ln *h, double *epoch_ms, double *score_ms);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,18 @@ class RlLrParams(C.Structure):
     _fields_ = [("lambda_", C.c_double), ("metric", C.c_int32), ("metric_k", C.c_int32), ("device", C.c_int32), ("err_max", C.c_double)]
 
 
+class RlLnParams(C.Structure):
+    _fields_ = [("n_epochs", C.c_int32), ("learning_rate", C.c_double), ("metric", C.c_int32), ("metric_k", C.c_int32),
+                ("device", C.c_int32), ("err_max", C.c_double)]
+
+
+class RlLnTraceRec(C.Structure):
+    _fields_ = [("epoch", C.c_int32), ("saved", C.c_int32), ("train", C.c_double), ("valid", C.c_double)]
+
+
+LN_TRACE_DTYPE = np.dtype([("epoch", np.int32), ("saved", np.int32), ("train", np.float64), ("valid", np.float64)])
+RL_ERR_NO_BEST = -7                    # rl_ln_learn: no epoch scored above 0.0 on the validation set
+
 RL_RANKER = dict(MART=0, LAMBDAMART=6)
 
 
@@ -105,6 +117,8 @@ ABI_SYMBOLS = [
     "rl_lr_params_default", "rl_lr_create", "rl_lr_destroy", "rl_lr_set_train", "rl_lr_set_validation", "rl_lr_set_external_judgments",
     "rl_lr_set_features", "rl_lr_learn", "rl_lr_get_weights", "rl_lr_scores", "rl_lr_debug_gram", "rl_lr_debug_times", "rl_lr_predict",
     "rl_net_create", "rl_net_destroy", "rl_net_predict", "rl_net_predict_device", "rl_net_debug_path",
+    "rl_ln_params_default", "rl_ln_create", "rl_ln_destroy", "rl_ln_set_train", "rl_ln_set_validation", "rl_ln_set_external_judgments",
+    "rl_ln_set_weights", "rl_ln_learn", "rl_ln_get_weights", "rl_ln_scores", "rl_ln_trace", "rl_ln_debug_doc_scores", "rl_ln_debug_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -183,7 +197,8 @@ def lib():
     L.rl_set_err_max.argtypes = [C.c_double]
     L.rl_set_timing_flags.argtypes = [vp, i32]
     L.rl_debug_membench.argtypes = [i32, i32, i64, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    for pre, params in (("rl_ca_", RlCaParams), ("rl_ada_", RlAdaParams), ("rl_rb_", RlRbParams), ("rl_lr_", RlLrParams)):
+    for pre, params in (("rl_ca_", RlCaParams), ("rl_ada_", RlAdaParams), ("rl_rb_", RlRbParams), ("rl_lr_", RlLrParams),
+                        ("rl_ln_", RlLnParams)):
         if not hasattr(L, pre + "create"):      # (A/B builds of older sources lack the later linear rankers)
             continue
         fn = lambda name: getattr(L, pre + name)      # noqa: E731
@@ -216,6 +231,12 @@ def lib():
         L.rl_lr_debug_gram.argtypes = [vp, vp, vp, i32, C.POINTER(i32)]
         L.rl_lr_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
         L.rl_lr_predict.argtypes = [i32, vp, i32, vp, i32, vp, i64, i32, vp]
+    if hasattr(L, "rl_ln_create"):
+        L.rl_ln_set_weights.argtypes = [vp, vp, i32]
+        L.rl_ln_get_weights.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        L.rl_ln_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.rl_ln_debug_doc_scores.argtypes = [vp, i32, vp, i64]
+        L.rl_ln_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(L, "rl_net_create"):
         L.rl_net_create.argtypes = [i32, vp, i32, vp, i32, vp, i32, C.POINTER(vp)]
         L.rl_net_destroy.argtypes = [vp]
@@ -687,7 +708,7 @@ class NetModel:
 
 
 class _LinearTrainer:
-    """What the handles of the four linear rankers share (rl_linear.inc): a subclass names its C prefix, the ranker as the messages call
+    """What the handles of the four linear rankers and of ListNet training share (rl_linear.inc): a subclass names its C prefix, the ranker as the messages call
     it and its trace records, and fills its own parameters."""
     _prefix = _name = _trace_dtype = None
 
@@ -865,6 +886,55 @@ class LinearRegTrainer(_LinearTrainer):
         g, s, e, rb = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int32(0)
         check(lib().rl_lr_debug_times(self.h, C.byref(g), C.byref(s), C.byref(e), C.byref(rb)))
         return dict(gram_ms=g.value, solve_ms=s.value, score_ms=e.value, register_block=rb.value)
+
+
+class NoBestModelError(RankLibError):
+    """rl_ln_learn returned RL_ERR_NO_BEST: with a validation set, no epoch scored above 0.0 (learning.ListNet turns it into the Java's
+    message)"""
+
+
+class ListNetTrainer(_LinearTrainer):
+    """Thin object wrapper over the rl_ln handle: ListNet.learn() on one GPU (rl_ln.inc in rl_ca.hip).  The start weights are the
+    caller's (set_weights: inputs in order, the bias last).  trace(): LN_TRACE_DTYPE, one record per epoch."""
+    _prefix, _name, _trace_dtype = "rl_ln_", "ListNet", LN_TRACE_DTYPE
+
+    def __init__(self, n_epochs=1500, learning_rate=0.00001, metric="NDCG", metric_k=10, device=0, err_max=16.0):
+        if not hasattr(lib(), "rl_ln_create"):
+            raise RankLibError("rlhip: this librlhip.so has no ListNet training (rl_ln_*)")
+        self._open(RlLnParams, metric, metric_k, device, err_max, n_epochs=int(n_epochs), learning_rate=float(learning_rate))
+
+    def set_weights(self, w):
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        check(lib().rl_ln_set_weights(self.h, w.ctypes.data, w.size))
+
+    def learn(self):
+        rc = lib().rl_ln_learn(self.h)
+        if rc == RL_ERR_NO_BEST:
+            raise NoBestModelError("%s (rlhip status %d)" % (lib().rl_last_error().decode("utf-8", "replace"), rc))
+        check(rc)
+
+    def weights(self):
+        n = C.c_int32(0)
+        check(lib().rl_ln_get_weights(self.h, None, 0, C.byref(n)))
+        w = np.zeros(max(1, n.value), np.float64)
+        check(lib().rl_ln_get_weights(self.h, w.ctypes.data, n.value, C.byref(n)))
+        return w[:n.value]
+
+    def doc_scores(self, validation=False):
+        """[N] f64: the final weights' output for every document of the set, as k_ln_score wrote it"""
+        out = np.zeros(max(1, self.Nv if validation else self.N), np.float64)
+        check(lib().rl_ln_debug_doc_scores(self.h, 1 if validation else 0, out.ctypes.data, out.size))
+        return out[:self.Nv if validation else self.N]
+
+    def set_validation(self, X, labels, qoff, qkey=None):
+        super().set_validation(X, labels, qoff, qkey)
+        self.Nv = np.asarray(X).shape[0]
+
+    def times(self):
+        """dict: epoch_ms (all k_ln_epoch launches, device events), score_ms (scoring + ranking after every epoch, host clock)"""
+        e, s = C.c_double(0), C.c_double(0)
+        check(lib().rl_ln_debug_times(self.h, C.byref(e), C.byref(s)))
+        return dict(epoch_ms=e.value, score_ms=s.value)
 
 
 def _predict_arrays(feature_ids, weights, rows):

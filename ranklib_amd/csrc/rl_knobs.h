@@ -114,4 +114,8 @@ struct EvalKnobs {
 // Linear Regression (rl_lr::rb_knob, read by rl_lr_create): the register block of k_lr_gram, 1 / 2 / 4; anything else: chosen by lr_pick_rb's model
 inline int read_lr_rb_knob() { const int v = knob::value("RLHIP_LR_RB", 0); return (v == 1 || v == 2 || v == 4) ? v : 0; }
 
+// ListNet training (rl_ln::skip, read by rl_ln_create): a measuring aid of tools/ln_bench.py -- k_ln_epoch without its forward pass (1), its
+// sum chain (2) or its update (4); the weights such a run leaves are meaningless.  Anything else: the whole kernel
+inline int read_ln_skip_knob() { const int v = knob::value("RLHIP_LN_SKIP", 0); return (v == 1 || v == 2 || v == 4) ? v : 0; }
+
 }  // namespace rl

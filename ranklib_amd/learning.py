@@ -11,7 +11,8 @@ RankLib's API read the same here:
     AdaRank                      learning/boosting/AdaRank.java:33-346  (learn and eval run on the GPU through librlhip.so)
     LinearRegRank                learning/LinearRegRank.java:23-240     (learn and eval run on the GPU through librlhip.so)
     RankNet / LambdaRank / ListNet   learning/neuralnet/RankNet.java:33-490, LambdaRank.java, ListNet.java:24-236
-                                 (model text in and out, eval on the GPU through librlhip.so; training is not built)
+                                 (model text in and out, eval on the GPU through librlhip.so; ListNet also trains there,
+                                 behind a seed; RankNet and LambdaRank training is not built)
     RankerType / RankerFactory   learning/RankerType.java, learning/RankerFactory.java:36-118
     RankerTrainer                learning/RankerTrainer.java:23-56
 
@@ -1157,9 +1158,47 @@ class LinearRegRank(_LinearRanker):
 
 
 def _neural_refusal(type_name):
-    """what createRanker, init() and learn() say about RANKNET, LAMBDARANK and LISTNET: they load and score, they do not train"""
+    """what createRanker, init() and learn() say about RANKNET, LAMBDARANK and (without a seed) LISTNET: they load and score, they do not
+    train"""
     return ("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank), 2 (RankBoost) and "
-            "9 (Linear Regression); %s, one of the neural-net rankers, is out of scope (SURVEY.md 8)" % type_name)
+            "9 (Linear Regression); %s, one of the neural-net rankers, is out of scope (SURVEY.md 8)%s"
+            % (type_name, "; ListNet trains only with a seed for its initial weights (-netseed n / ListNet.seed)" if type_name == "LISTNET" else ""))
+
+
+class JavaRandom:
+    """java.util.Random as its javadoc specifies it: the 48-bit LCG, nextInt(bound) with its rejection loop and nextFloat()"""
+    _MASK = (1 << 48) - 1
+
+    def __init__(self, seed):
+        self.seed = (int(seed) ^ 0x5DEECE66D) & self._MASK
+
+    def next(self, bits):
+        self.seed = (self.seed * 0x5DEECE66D + 0xB) & self._MASK
+        v = (self.seed >> (48 - bits)) & 0xFFFFFFFF
+        return v - (1 << 32) if v >= (1 << 31) else v
+
+    def nextInt(self, bound=None):
+        if bound is None:
+            return self.next(32)
+        if bound <= 0:
+            raise ValueError("bound must be positive")
+        r = self.next(31)
+        m = bound - 1
+        if (bound & m) == 0:
+            return (bound * r) >> 31
+        u = r
+        while u - (u % bound) + m >= (1 << 31):       # the Java's int overflow test
+            u = self.next(31)
+        return u % bound
+
+    def nextFloat(self):
+        return np.float32(self.next(24)) / np.float32(1 << 24)
+
+
+class Neuron:
+    """the one static of learning/neuralnet/Neuron.java that reaches ListNet: ListNet.init() copies ListNet.learningRate into it, and
+    `-lr x` copies it (0.001 unless an earlier init() changed it) into ListNet.learningRate (eval/Evaluator.java:294-296)"""
+    learningRate = 0.001              # Neuron.java:22
 
 
 def _java_int(tok):
@@ -1179,7 +1218,8 @@ class RankNet(Ranker):
     then the hidden layers, then one output neuron.  self.weights[l - 1] is layer l's matrix [n_l][n_{l-1} + 1]: row j = the weights of
     neuron j's inLinks (the previous layer's neurons in order, the bias last), the order eval() sums in.  A model file lists the weights by
     outLinks instead: input and hidden neurons feed the next layer's neurons in order, the bias neuron (line "0 F") every neuron of layer
-    1, then of layer 2, ..., then the output neuron.  init() and learn() are refused: training is not built."""
+    1, then of layer 2, ..., then the output neuron.  init() and learn() are refused: training is not built (ListNet, a
+    subclass, trains behind a seed: DESIGN.md 15)."""
     # process-global parameters, like the Java statics (:37-40); only nIteration is used here (the "## Epochs" line of model())
     nIteration = 100
     nHiddenLayer = 1
@@ -1322,12 +1362,85 @@ class LambdaRank(RankNet):
 
 class ListNet(RankNet):
     """learning/neuralnet/ListNet.java: RankNet's eval (:143-145) and toString; its own statics, a shorter model() header (:157-174) and
-    its own message in loadFromString (:176-224), which reads hidden layers although ListNet.learn never makes any."""
+    its own message in loadFromString (:176-224), which reads hidden layers although ListNet.learn never makes any.
+
+    init() and learn() (:84-140) run on an MI355X (librlhip.so rl_ln_*: one pass over the ranked lists per epoch, the weights updated
+    after every list, bit for bit the Java's doubles) -- but only with ListNet.seed set (-netseed n, an rlhip extension): the Java draws
+    the initial weights from an unseeded static Random (Synapse.java:18,29), so no two of its runs agree.  Here every init() draws them
+    from a fresh java.util.Random(seed), two draws per synapse in wire() order.  With seed = None both stay refused."""
     nIteration = 1500                 # :29-31
     learningRate = 0.00001
     nHiddenLayer = 0
+    seed = None                       # rlhip extension (-netseed): None = training refused
     _TYPE = "LISTNET"
     _LOAD = "ListNet"
+
+    def __init__(self, samples=None, features=None, scorer=None):
+        super().__init__(samples, features, scorer)
+        self._trainer = None
+
+    @staticmethod
+    def initial_weights(seed, n):
+        """n synapses as Synapse.java:29 draws them: (nextInt(2) == 0 ? 1 : -1) * nextFloat() / 10 -- an int times a float, a FLOAT division
+        by 10, widened to double"""
+        rnd = JavaRandom(seed)
+        out = np.zeros(n, np.float64)
+        for k in range(n):
+            sign = np.float32(1 if rnd.nextInt(2) == 0 else -1)
+            out[k] = float(np.float32(np.float32(sign * rnd.nextFloat()) / np.float32(10)))
+        return out
+
+    def init(self):                   # :84-98
+        cls = type(self)
+        if cls.seed is None:
+            raise RankLibError(_neural_refusal(self._TYPE))
+        logger.info("Initializing... ")
+        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        if metric not in N.RL_CA_METRIC:
+            raise RankLibError("rlhip: the %s train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
+                               % (self.name(), self.scorer.name() if self.scorer else None))
+        F = len(self.features)
+        start = self.initial_weights(cls.seed, F + 1)      # wire(): inputs 0 .. F - 1 to the output neuron, then the bias
+        Neuron.learningRate = cls.learningRate              # :97
+        t = N.ListNetTrainer(n_epochs=cls.nIteration, learning_rate=Neuron.learningRate, metric=metric, metric_k=self.scorer.getK(),
+                             device=cls.device, err_max=ERRScorer.MAX)
+        _feed_linear_trainer(self, t, metric)
+        t.set_weights(start)
+        self.hidden, self.weights, self._net = [], [start.reshape(1, F + 1)], None
+        self._trainer = t
+
+    def learn(self):                  # :101-140
+        t = self._trainer
+        if type(self).seed is None or t is None:
+            raise RankLibError(_neural_refusal(self._TYPE))
+        nm, valid = self.scorer.name(), self.validationSamples is not None
+        logger.info("Training starts...")
+        self.printLogLn([7, 14, 9, 9], ["#epoch", "C.E. Loss", nm + "-T", nm + "-V"])
+        try:
+            try:
+                t.learn()
+            except N.NoBestModelError:
+                # bestModelOnValidation still holds its empty lists: l.get(0) throws (RankNet.java:206-223)
+                raise RankLibError("Error in NeuralNetwork.restoreBestModelOnValidation(): java.lang.IndexOutOfBoundsException: "
+                                   "Index 0 out of bounds for length 0") from None
+            for r in t.trace():           # estimateLoss() is never called: the loss column is the initial 0.0 in every epoch (:111)
+                self.printLog([7, 14], [str(int(r["epoch"])), java_double_str(java_round(0.0, 6))])
+                self.printLog([9], [java_double_str(java_round(float(r["train"]), 4))])
+                if valid:
+                    self.printLog([9], [java_double_str(java_round(float(r["valid"]), 4))])
+                self.flushLog()
+            F = len(self.features)
+            self.hidden, self.weights, self._net = [], [np.array(t.weights(), np.float64).reshape(1, F + 1)], None
+            ts, vs = t.scores()
+        finally:
+            t.close()
+            self._trainer = None
+        self.scoreOnTrainingData = java_round(ts, 4)
+        logger.info("Finished sucessfully.")
+        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
+        if valid:
+            self.bestScoreOnValidationData = vs
+            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
 
     def model(self):                  # :157-174: no "hidden layers" lines, and a literal 0 whatever the network is
         out = "## " + self.name() + "\n"
@@ -1379,9 +1492,12 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
                 rtype = RankerType[rtype]
             except KeyError:
                 raise RankLibError("Could find the class \"%s\" you specified. Make sure the jar library is in your classpath." % rtype)
-        if rtype.name not in self.map:
+        if rtype.name == "LISTNET" and ListNet.seed is not None:      # trains behind a seed only
+            r = ListNet()
+        elif rtype.name not in self.map:
             raise RankLibError(_neural_refusal(rtype.name))
-        r = self.map[rtype.name]()
+        else:
+            r = self.map[rtype.name]()
         if samples is not None:
             r.setTrainingSet(samples)
             r.setFeatures(features)
