@@ -315,8 +315,54 @@ enum {
                                    tools/step_trace.py); RL_ERR_STATE when no trace was requested */
     RL_ARR_PIECE_STATS = 24,    /* int64[2] cumulative, sharded runs with distributed float chains (rl_dist.inc): rounds of the repair loop, pieces re-evaluated from an
                                    exact start state after a detected window miss */
-    RL_ARR_BUBBLES = 23         /* int64[4] cumulative device wall-clock time (10 ns units) the main stream idled behind host decisions: [0] from the bookkeeping that ended a
+    RL_ARR_BUBBLES = 23,        /* int64[4] cumulative device wall-clock time (10 ns units) the main stream idled behind host decisions: [0] from the bookkeeping that ended a
                                    tree to the leaf table's first instruction, [1] trees, [2] from a leaf chain's last stitch to the leaf outputs, [3] rounds (round 6) */
+    RL_ARR_LAUNCH_ARMS = 25     /* int64[RL_ARM_COUNT_], read-only: which kernel variant the host launched, counted on the host (one increment per launch, cumulative
+                                   since rl_create), and the layout settings in force.  Indexed by the RL_ARM_* values below */
+};
+/* RL_ARR_LAUNCH_ARMS.  The histogram kernel's arms are counted apart for the root pass (RL_ARM_HIST_ROOT + arm) and the child passes (RL_ARM_HIST_CHILD + arm):
+ * an arm names the k_hist instantiation launch_hist chose (rl_trainer.hip), in the order it looks for one. */
+enum {
+    RL_HARM_COMPACT = 0,        /* child passes from compact rows (sparse data, RLHIP_CROWS) */
+    RL_HARM_SUB8 = 1,           /* child passes, 8 features and 256 threads a block (RLHIP_SUB_CHILD=8) */
+    RL_HARM_SUB4 = 2,           /* child passes, 4 features and 256 threads a block (RLHIP_SUB_CHILD=4) */
+    RL_HARM_NT1024 = 3,         /* child passes, 1024 threads a block (RLHIP_HIST_NT >= 1024) */
+    RL_HARM_NT512 = 4,          /* child passes, 512 threads a block (RLHIP_HIST_NT in 257 .. 1023) */
+    RL_HARM_FQ_PACKED = 5,      /* root pass that quantises the lambdas itself, packed rows (the default root pass) */
+    RL_HARM_FQ_ROWS16 = 6,      /* root pass that quantises the lambdas itself, 16-bit rows (RLHIP_P8=0) */
+    RL_HARM_PACKED_RUNS = 7,    /* packed rows, columns that come in runs folded by quads */
+    RL_HARM_PACKED = 8,         /* packed rows (root: RLHIP_FUSED_QUANT=0; children: RLHIP_P8=2) */
+    RL_HARM_ROWS16_RUNS = 9,    /* 16-bit rows, columns that come in runs folded by quads */
+    RL_HARM_ROWS16 = 10,        /* 16-bit rows (the default child pass) */
+    RL_HARM_STRIDE = 11,        /* LDS row stride known at run time only: more than 264 bins a feature, or fewer than 16 features a block */
+    RL_HARM_COUNT_ = 12,
+    RL_ARM_HIST_ROOT = 0, RL_ARM_HIST_CHILD = 12,      /* + RL_HARM_* */
+    /* launch_rank (training and validation lists alike) */
+    RL_ARM_RANK_TINY = 24, RL_ARM_RANK_MIXED = 25, RL_ARM_RANK_WAVE_LONG = 26, RL_ARM_RANK_WAVE_SHORT = 27, RL_ARM_RANK_BLOCK = 28, RL_ARM_RANK_HUGE = 29,
+    /* the lambda kernels of a round (enqueue_lambdas) */
+    RL_ARM_LAM_MART = 30,       /* k_mart_residual */
+    RL_ARM_LAM_TINY = 31,       /* k_lambda_tiny */
+    RL_ARM_LAM_FUSED = 32,      /* k_lambda_fused<., 0>: NDCG / DCG, column by row */
+    RL_ARM_LAM_COMPACT = 33,    /* k_lambda_fused<., 0, true>: NDCG / DCG from the lists of active pairs (RLHIP_LAMBDA_COMPACT) */
+    RL_ARM_LAM_ERR = 34,        /* k_lambda_fused<., 1> */
+    RL_ARM_LAM_MAP = 35,        /* k_lambda_fused<., 2> */
+    RL_ARM_LAM_UNFUSED = 36,    /* k_pair_terms + k_lambda_acc (counted once a round) */
+    RL_ARM_LAM_ON_SIDE = 37,    /* of the fused launches, those enqueued on a side stream (RLHIP_LAMBDA_SIDE) */
+    RL_ARM_LAM_ON_MAIN = 38,    /* ... and on the main stream (k_lambda_tiny included) */
+    RL_ARM_QUANTIZE = 39,       /* k_quantize launches: rounds whose root pass did not quantise the lambdas itself */
+    RL_ARM_XPLAN_HOST = 40,     /* sharded, leaf-owner exchange: plans made on the host (RLHIP_DIST_HOST_PLAN) */
+    RL_ARM_XPLAN_DEVICE = 41,   /* ... and on the device (k_plan_exchange) */
+    RL_ARM_STEPS_ENQUEUED = 42, /* growth steps the host enqueued (empty ones behind a finished tree included) */
+    /* growth steps the host keeps in flight beyond the progress word: one GPU (RLHIP_STEP_AHEAD), sharded (RLHIP_DIST_STEP_AHEAD); settings, not counters */
+    RL_ARM_SET_STEP_AHEAD = 43, RL_ARM_SET_DIST_AHEAD = 44,
+    /* the last child-pass launch: grid columns, grid rows, dynamic LDS bytes */
+    RL_ARM_CHILD_GRID_X = 45, RL_ARM_CHILD_GRID_Y = 46, RL_ARM_CHILD_LDS = 47,
+    /* settings in force once rl_init has run, not counters: packed rows 0 / 1 / 2, document-major root rows, RLHIP_DM_DIV, features per child block asked for, threads per
+     * child block asked for, any column in runs, compact rows built, lazy tie-break mode (0 = off), then chunk_docs' and balance_slots' parameters */
+    RL_ARM_SET_P8 = 48, RL_ARM_SET_DM_ROOT = 49, RL_ARM_SET_DM_DIV = 50, RL_ARM_SET_SUB_CHILD = 51, RL_ARM_SET_HIST_NT = 52, RL_ARM_SET_ANY_RUNS = 53,
+    RL_ARM_SET_CROWS = 54, RL_ARM_SET_TIE_ON = 55, RL_ARM_SET_NODE_DIV = 56, RL_ARM_SET_NODE_MIN = 57, RL_ARM_SET_BALANCE = 58, RL_ARM_SET_BALANCE_TARGET = 59,
+    RL_ARM_SET_BALANCE_MIN = 60, RL_ARM_SET_BALANCE_CAP = 61, RL_ARM_SET_NODE_CHUNK = 62, RL_ARM_SET_MAX_CHUNKS = 63,
+    RL_ARM_COUNT_ = 64
 };
 /* The device's two exp implementations (rho of learning/tree/LambdaMART.java:383) on n arguments: the branch-free one the
  * lambda kernels use and the literal fdlibm e_exp transcription; both must equal StrictMath.exp bit for bit. */

@@ -96,7 +96,15 @@ RL_FLAG_TIMING, RL_FLAG_SERIAL_CHAIN, RL_FLAG_TIMING_NODES, RL_FLAG_JAVA_ORDER, 
 RL_FLAG_FAST_LEAF = 1      # leaf sums as the fixed f64 reduction of DESIGN.md 14 instead of the Java's float running sums (opt-in, one GPU)
 ARR = dict(LAMBDA=1, WEIGHT=2, SCORE=3, VALID_SCORE=4, NBINS=5, THRESHOLDS=6, BINS=7, ROOT_COUNT=8, ROOT_SUM=9,
            QUANT=10, ROOT_SUM_FIXED=11, NDCG_PER_QUERY=12, CHAIN_STATS=13, CHAIN_MISS=14, GROW_STATS=15, PHASE_CLOCKS=16,
-           ROOT_SUM_JAVA=17, GROW_DOCS=18, SPARSE_INFO=19, STEP_LOG=20, TIE_STATS=21, BLOCK_TRACE=22, BUBBLES=23, PIECE_STATS=24)
+           ROOT_SUM_JAVA=17, GROW_DOCS=18, SPARSE_INFO=19, STEP_LOG=20, TIE_STATS=21, BLOCK_TRACE=22, BUBBLES=23, PIECE_STATS=24, LAUNCH_ARMS=25)
+# indices into array("LAUNCH_ARMS") (include/rlhip.h RL_ARM_* / RL_HARM_*; tests/test_abi.py holds the two lists together): which kernel variant the
+# host launched.  A k_hist arm is ARM["HIST_ROOT"] + HARM[..] for the root pass, ARM["HIST_CHILD"] + HARM[..] for the child passes
+HARM = dict(COMPACT=0, SUB8=1, SUB4=2, NT1024=3, NT512=4, FQ_PACKED=5, FQ_ROWS16=6, PACKED_RUNS=7, PACKED=8, ROWS16_RUNS=9, ROWS16=10, STRIDE=11, COUNT_=12)
+ARM = dict(HIST_ROOT=0, HIST_CHILD=12, RANK_TINY=24, RANK_MIXED=25, RANK_WAVE_LONG=26, RANK_WAVE_SHORT=27, RANK_BLOCK=28, RANK_HUGE=29,
+           LAM_MART=30, LAM_TINY=31, LAM_FUSED=32, LAM_COMPACT=33, LAM_ERR=34, LAM_MAP=35, LAM_UNFUSED=36, LAM_ON_SIDE=37, LAM_ON_MAIN=38,
+           QUANTIZE=39, XPLAN_HOST=40, XPLAN_DEVICE=41, STEPS_ENQUEUED=42, SET_STEP_AHEAD=43, SET_DIST_AHEAD=44, CHILD_GRID_X=45, CHILD_GRID_Y=46, CHILD_LDS=47,
+           SET_P8=48, SET_DM_ROOT=49, SET_DM_DIV=50, SET_SUB_CHILD=51, SET_HIST_NT=52, SET_ANY_RUNS=53, SET_CROWS=54, SET_TIE_ON=55, SET_NODE_DIV=56,
+           SET_NODE_MIN=57, SET_BALANCE=58, SET_BALANCE_TARGET=59, SET_BALANCE_MIN=60, SET_BALANCE_CAP=61, SET_NODE_CHUNK=62, SET_MAX_CHUNKS=63, COUNT_=64)
 KERNEL = dict(HIST_ROOT=0, HIST_NODE=1, LAMBDA=2)
 
 # every symbol include/rlhip.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -575,7 +583,7 @@ class Trainer:
             "THRESHOLDS": ((F_hist, TS), np.float32), "BINS": ((F_hist, self.N), np.uint16),
             "ROOT_COUNT": ((F_hist, TS), np.int32), "ROOT_SUM": ((F_hist, TS), np.float64), "ROOT_SUM_JAVA": ((F_hist, TS), np.float64),
             "QUANT": ((self.N,), np.int64), "ROOT_SUM_FIXED": ((F_hist, TS, 2), np.int64),
-            "NDCG_PER_QUERY": ((self.Q,), np.float64), "CHAIN_STATS": ((6,), np.int32), "GROW_STATS": ((4,), np.int32), "GROW_DOCS": ((4,), np.int64), "BUBBLES": ((4,), np.int64), "PIECE_STATS": ((2,), np.int64), "SPARSE_INFO": ((8,), np.int64), "PHASE_CLOCKS": ((64, 32), np.int64), "BLOCK_TRACE": ((64, 3, 2048, 8), np.int64), "STEP_LOG": ((8 + 8 * 8192,), np.int32), "TIE_STATS": ((10,), np.int64), "CHAIN_MISS": ((2, self.cap + 1), np.int32),
+            "NDCG_PER_QUERY": ((self.Q,), np.float64), "CHAIN_STATS": ((6,), np.int32), "GROW_STATS": ((4,), np.int32), "GROW_DOCS": ((4,), np.int64), "BUBBLES": ((4,), np.int64), "PIECE_STATS": ((2,), np.int64), "SPARSE_INFO": ((8,), np.int64), "PHASE_CLOCKS": ((64, 32), np.int64), "BLOCK_TRACE": ((64, 3, 2048, 8), np.int64), "STEP_LOG": ((8 + 8 * 8192,), np.int32), "TIE_STATS": ((10,), np.int64), "LAUNCH_ARMS": ((ARM["COUNT_"],), np.int64), "CHAIN_MISS": ((2, self.cap + 1), np.int32),
         }
         shape, dt = shapes[name]
         out = np.zeros(shape, dt)

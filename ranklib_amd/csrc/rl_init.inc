@@ -389,7 +389,9 @@ static int init_bins(rl_trainer *t, InitWork &w)
             unsigned char *d_pb = nullptr, *d_pd = nullptr; uint16_t *d_ph = nullptr;
             c.pd_stride = (c.numFG * 18 + 63) & ~63;
             RL_HIP(t->pool.alloc(&d_pb, (size_t)c.numFG * Npad * 16)); RL_HIP(t->pool.alloc(&d_ph, (size_t)c.numFG * Npad));
-            if (p8_mode > 1) {
+            // (document-major packed rows: for the child passes, and for a root pass that reads document-major rows -- RLHIP_DM_ROOT with the default
+            // packed root pass used to read them through a null pointer)
+            if (p8_mode > 1 || kn.dm_root) {
                 RL_HIP(t->pool.alloc(&d_pd, (size_t)Npad * c.pd_stride));
                 RL_HIP(hipMemsetAsync(d_pd, 0, (size_t)Npad * c.pd_stride, s));
             }

@@ -49,6 +49,7 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
     if (c.mart) {    // MART: residuals instead of lambdas (weights stay 0)
         ScopedTiming tm(t, RL_KERNEL_LAMBDA, (double)c.N * 20.0);
         n_max = std::min(2048, (c.N + kThreads - 1) / kThreads);
+        t->arms[RL_ARM_LAM_MART]++;
         hipLaunchKernelGGL(k_mart_residual, dim3(n_max), dim3(kThreads), 0, s, c.labels, (const double *)c.scores, c.lw, c.N, t->d_wmax);
     } else {   // K1 lambdas: pair terms in parallel, then ordered accumulation (ranked order comes from the previous
         // round's k_rank_* / from rl_init for round 0)
@@ -81,6 +82,8 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
 #define RL_LAUNCH_FUSED(BT, cls)                                                                                                             \
             if (d.n_qcls[cls] > 0) {                                                                                                         \
                 hipStream_t ls = lam_stream();                                                                                               \
+                t->arms[cp ? RL_ARM_LAM_COMPACT : mode == 0 ? RL_ARM_LAM_FUSED : mode == 1 ? RL_ARM_LAM_ERR : RL_ARM_LAM_MAP]++;                  \
+                t->arms[ls == s ? RL_ARM_LAM_ON_MAIN : RL_ARM_LAM_ON_SIDE]++;                                                                \
                 if (cp) hipLaunchKernelGGL((k_lambda_fused<BT, 0, true>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
                 else if (mode == 0) hipLaunchKernelGGL((k_lambda_fused<BT, 0>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
                 else if (mode == 1) hipLaunchKernelGGL((k_lambda_fused<BT, 1>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
@@ -89,6 +92,7 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
             }
             if (d.n_qcls[4] > 0 && mode == 0) {
                 const int nb = (d.n_qcls[4] + kLambdaTinyGroups - 1) / kLambdaTinyGroups;
+                t->arms[RL_ARM_LAM_TINY]++; t->arms[RL_ARM_LAM_ON_MAIN]++;
                 hipLaunchKernelGGL(k_lambda_tiny, dim3(nb), dim3(kLambdaTinyDocs * kLambdaTinyGroups),
                                    (size_t)kLambdaTinyGroups * lambda_tiny_group_bytes(c.k), s, g, (const int *)d.d_qcls[4], d.n_qcls[4]);
                 n_max += nb; g.blockmax = t->d_wmax + n_max;
@@ -108,6 +112,7 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
             for (int i = 0; i < lam_used; i++) { RL_HIP(hipEventRecord(t->ev_lam_join[i], t->lam_s[i])); RL_HIP(hipStreamWaitEvent(s, t->ev_lam_join[i], 0)); }
         } else {
             const unsigned nb = (unsigned)((c.N + kThreads - 1) / kThreads);
+            t->arms[RL_ARM_LAM_UNFUSED]++;
             hipLaunchKernelGGL(k_pair_terms, dim3(nb), dim3(kThreads), 0, s, g);
             hipLaunchKernelGGL(k_lambda_acc, dim3(nb), dim3(kThreads), 0, s, g);
             n_max = (int)nb;
@@ -126,7 +131,10 @@ static int enqueue_max_and_quant(rl_trainer *t, int n_max, bool &root_quant_fuse
     // The plain one-GPU root pass makes the fixed-point lambdas itself (k_hist<.., FQ>): one pass over the documents and one launch less a round.
     // Sharded, strict-order and sparse-column runs (their kernels between here and the root pass read q) and a regrown tree (q exists) keep k_quantize.
     root_quant_fused = t->knobs.fused_quant && !c.java && !c.sp_on && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs;       // (sharded runs too, round 6: max |lambda| is all-reduced before this point, nothing between here and the root pass reads q)
-    if (!root_quant_fused) hipLaunchKernelGGL(k_quantize, dim3(std::min(2048, (c.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, c);
+    if (!root_quant_fused) {
+        t->arms[RL_ARM_QUANTIZE]++;
+        hipLaunchKernelGGL(k_quantize, dim3(std::min(2048, (c.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, c);
+    }
     return RL_OK;
 }
 
@@ -139,7 +147,7 @@ static int enqueue_root(rl_trainer *t, const RoundPlan &pl, bool quant_fused)
         const double root_bytes = c.sp_on ? (double)c.N * ((double)(c.numFG - c.sp_ngroups) * kHistFG * 2.0 + 8.0) + (double)t->sp_entries * 4.0
                                           : (double)c.N * ((double)c.F * 2.0 + 8.0);
         ScopedTiming tm(t, RL_KERNEL_HIST_ROOT, root_bytes);
-        launch_hist<true>(c, t->knobs, pl.hist_gx, pl.rootChunks, pl.hist_lds, s, quant_fused);
+        launch_hist<true>(c, t->knobs, t->arms, pl.hist_gx, pl.rootChunks, pl.hist_lds, s, quant_fused);
         if (c.sp_on) {
             hipLaunchKernelGGL(k_hist_sp<kHistLdsStride>, dim3(c.sp_ngroups, pl.rootChunks), dim3(kSpThreads), (size_t)kHistFG * kHistLdsStride * 8, s, c, pl.rootCs);
         }
@@ -277,9 +285,10 @@ static int enqueue_growth_step(rl_trainer *t, const RoundPlan &pl, Growth &g, Ne
         hipLaunchKernelGGL(k_part_count, dim3(c.nTiles), dim3(kThreads), 0, s, c);
         hipLaunchKernelGGL(k_part_scatter<false>, dim3(c.nTiles), dim3(kThreads), 0, s, c);
     } else hipLaunchKernelGGL(k_part_scatter<true>, dim3(c.nTiles), dim3(kThreads), 0, s, c);
+    t->arms[RL_ARM_STEPS_ENQUEUED]++;
     {
         ScopedTiming tm(t, RL_KERNEL_HIST_NODE, 0.0);
-        launch_hist<false>(c, t->knobs, pl.hist_gx, c.maxChunks, pl.hist_lds, s);
+        launch_hist<false>(c, t->knobs, t->arms, pl.hist_gx, c.maxChunks, pl.hist_lds, s);
     }
     if (t->dist) {
         hipLaunchKernelGGL(k_hist_reduce, dim3(c.F, kSpec), dim3(kFinThreads), pl.red_lds, s, c, 0);

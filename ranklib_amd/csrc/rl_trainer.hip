@@ -103,6 +103,7 @@ struct rl_trainer {
     int32_t cr_groups = 0; double cr_entries = 0, cr_overflow = 0;          // compact rows (groups that use them; of the child passes (k_compact_rows): entries outside the mode bins, rows that need the dense fallback
     double err_max = 16.0;      // ERRScorer.MAX when the trainer was created (rl_set_err_max)
     int32_t round = 0;          // rounds enqueued so far
+    int64_t arms[RL_ARM_COUNT_] = {};      // RL_ARR_LAUNCH_ARMS: launches per kernel variant, counted where the host picks one (the tests assert the variant a knob selects)
     // growth progress reported by the device (Ctx::progress): the host keeps at most knobs.step_ahead growth steps in flight and
     // stops enqueuing steps of a finished tree; 0 = enqueue all L-1 steps blindly
     // (1: c2 409.5 -> 411.7 rounds/s against 3, profiles/r05g_ab_step_ahead_c2.txt -- fewer empty steps behind a finished tree)
@@ -523,6 +524,7 @@ static int enqueue_leaf_chains_owner(rl_trainer *t, const ChainSource &src)
     if (rcd) return rcd;
     std::vector<int64_t> scount(R), sdispl(R), rcount(R), rdispl(R);
     const bool dev_plan = t->d_xmail != nullptr && !t->knobs.dist_host_plan && nseg <= kPlanMaxSeg && R <= 64;       // (knobs.dist_host_plan: the host plan behind a stream synchronisation, as until round 5)
+    t->arms[dev_plan ? RL_ARM_XPLAN_DEVICE : RL_ARM_XPLAN_HOST]++;
     if (dev_plan) {
         // the plan on the device; the host only needs the byte counts of the transfers and reads them from a pinned mailbox below, after it has
         // enqueued the pack kernel (k_plan_exchange)
@@ -613,12 +615,15 @@ static int launch_rank(rl_trainer *t, DataSet &d, const double *scores, double *
                ranked ? d.d_ss : nullptr, ranked ? d.d_sl : nullptr, ranked ? d.d_srel : nullptr, ranked ? d.d_sidx : nullptr,
                out, t->p.metric_k, t->p.metric, ranked ? d.d_aux_i : nullptr, ranked ? d.d_aux_a : nullptr, ranked ? d.d_aux_b : nullptr, t->err_max,
                d.d_ext_rd};
-    if (d.n_tiny > 0)
+    if (d.n_tiny > 0) {
+        t->arms[RL_ARM_RANK_TINY]++;
         hipLaunchKernelGGL(k_rank_tiny, dim3((d.n_tiny + kRankTinyGroups - 1) / kRankTinyGroups), dim3(kRankTinyDocs * kRankTinyGroups), 0, t->stream, a,
                            (const int *)d.d_qtiny, d.n_tiny);
+    }
     if (!t->knobs.rank_split && d.n_big > 0 && d.n_small > 0) {
         const int wpb = kRankBlockThreads / 64;
         const size_t lds = std::max((size_t)d.max_big, (size_t)wpb * kLambdaWaveCap) * kRankLdsPerDoc;
+        t->arms[RL_ARM_RANK_MIXED]++; t->arms[RL_ARM_RANK_HUGE] += d.n_huge > 0 ? 1 : 0;
         hipLaunchKernelGGL(k_rank_mixed, dim3(d.n_big + (d.n_small + wpb - 1) / wpb), dim3(kRankBlockThreads), lds, t->stream, a, (const int *)d.d_qbig, d.n_big, d.max_big,
                            (const int *)d.d_qsmall, d.n_small, kLambdaWaveCap);
         if (d.n_huge > 0)
@@ -626,6 +631,8 @@ static int launch_rank(rl_trainer *t, DataSet &d, const double *scores, double *
         RL_HIP(hipGetLastError());
         return RL_OK;
     }
+    t->arms[RL_ARM_RANK_WAVE_LONG] += d.n_small_long > 0 ? 1 : 0; t->arms[RL_ARM_RANK_WAVE_SHORT] += d.n_small > d.n_small_long ? 1 : 0;
+    t->arms[RL_ARM_RANK_BLOCK] += d.n_big > 0 ? 1 : 0; t->arms[RL_ARM_RANK_HUGE] += d.n_huge > 0 ? 1 : 0;
     if (d.n_small_long > 0)       // (d_qsmall: longest first)
         hipLaunchKernelGGL(k_rank_wave, dim3((d.n_small_long + 3) / 4), dim3(kThreads), 4 * kLambdaWaveCap * kRankLdsPerDoc, t->stream, a,
                            (const int *)d.d_qsmall, d.n_small_long, kLambdaWaveCap);
@@ -641,8 +648,13 @@ static int launch_rank(rl_trainer *t, DataSet &d, const double *scores, double *
 }
 
 template <bool ROOT>
-static void launch_hist(const Ctx &c, const Knobs &kn, int gx, int gy, size_t lds, hipStream_t s, bool fq = false)
+static void launch_hist(const Ctx &c, const Knobs &kn, int64_t *arms, int gx, int gy, size_t lds, hipStream_t s, bool fq = false)
 {
+    // RL_ARR_LAUNCH_ARMS: one increment per launch, root and child passes apart; of a child pass also the grid and the LDS it was given
+    const auto took = [&](int arm, const dim3 &grid, size_t lds_bytes) {
+        arms[(ROOT ? RL_ARM_HIST_ROOT : RL_ARM_HIST_CHILD) + arm]++;
+        if (!ROOT) { arms[RL_ARM_CHILD_GRID_X] = grid.x; arms[RL_ARM_CHILD_GRID_Y] = grid.y; arms[RL_ARM_CHILD_LDS] = (int64_t)lds_bytes; }
+    };
     // the XCD-aware block map of k_hist wants a multiple of 8 chunks (the extra blocks exit); child passes: a bounded grid whose blocks walk the
     // step's chunks (k_hist), about one resident set of blocks (3 per CU)
     const int grid_blocks = kn.hist_grid.or_else(1024);
@@ -653,6 +665,7 @@ static void launch_hist(const Ctx &c, const Knobs &kn, int gx, int gy, size_t ld
     if (!ROOT) lds += kn.hist_ldspad;
     const dim3 g(gx, bounded(gx)), b(kThreads);
     if (!ROOT && c.crows && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs) {      // sparse data: compact rows (k_compact_rows)
+        took(RL_HARM_COMPACT, g, lds);
         hipLaunchKernelGGL((k_hist<false, 16, kHistLdsStride, false, false, kThreads, true>), g, b, lds, s, c);
         return;
     }
@@ -661,6 +674,7 @@ static void launch_hist(const Ctx &c, const Knobs &kn, int gx, int gy, size_t ld
         // the LDS atomics of ITS CU -- the same atomics on more CUs (the rows are read once per sub-block, from L2)
         const dim3 g2(gx * (16 / c.sub_child), bounded(gx * (16 / c.sub_child)));
         const size_t lds2 = (size_t)c.sub_child * kHistLdsStride * 12;
+        took(c.sub_child == 8 ? RL_HARM_SUB8 : RL_HARM_SUB4, g2, lds2);
         if (c.sub_child == 8) hipLaunchKernelGGL((k_hist<false, 8, kHistLdsStride, false, false, 256>), g2, dim3(256), lds2, s, c);
         else hipLaunchKernelGGL((k_hist<false, 4, kHistLdsStride, false, false, 256>), g2, dim3(256), lds2, s, c);
         return;
@@ -668,12 +682,14 @@ static void launch_hist(const Ctx &c, const Knobs &kn, int gx, int gy, size_t ld
     if (!ROOT && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs && !(c.p8 > 1) && c.hist_nt > kThreads) {
         // child passes: a step has few chunks (~12 per node), so the chip is mostly idle and every block is a chain of dependent row gathers --
         // larger blocks keep more of them in flight per chunk
+        took(c.hist_nt >= 1024 ? RL_HARM_NT1024 : RL_HARM_NT512, g, lds);
         if (c.hist_nt >= 1024) hipLaunchKernelGGL((k_hist<false, 16, kHistLdsStride, false, false, 1024>), g, dim3(1024), lds, s, c);
         else hipLaunchKernelGGL((k_hist<false, 16, kHistLdsStride, false, false, 512>), g, dim3(512), lds, s, c);
         return;
     }
     if constexpr (ROOT) {
         if (fq && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs) {      // root pass that quantises the lambdas itself (root_quant_fused)
+            took(c.p8 ? RL_HARM_FQ_PACKED : RL_HARM_FQ_ROWS16, g, lds);
             if (c.p8) hipLaunchKernelGGL((k_hist<true, 16, kHistLdsStride, false, true, kThreads, false, true>), g, b, lds, s, c);
             else hipLaunchKernelGGL((k_hist<true, 16, kHistLdsStride, false, false, kThreads, false, true>), g, b, lds, s, c);
             return;
@@ -682,6 +698,7 @@ static void launch_hist(const Ctx &c, const Knobs &kn, int gx, int gy, size_t ld
     if (c.sub == 16 && c.TS <= kHistLdsStride) {
         // packed rows for the root pass only (measured at c2: 43 % fewer bytes buy the root pass 9 % -- it is bound by LDS atomics, not by HBM --
         // and the child passes nothing: their extra bit-field work costs what the two 128-byte lines per document instead of three save)
+        took((c.p8 && (ROOT || c.p8 > 1)) ? (c.any_runs ? RL_HARM_PACKED_RUNS : RL_HARM_PACKED) : (c.any_runs ? RL_HARM_ROWS16_RUNS : RL_HARM_ROWS16), g, lds);
         if (c.p8 && (ROOT || c.p8 > 1)) {
             if (c.any_runs) hipLaunchKernelGGL((k_hist<ROOT, 16, kHistLdsStride, true, true>), g, b, lds, s, c);
             else hipLaunchKernelGGL((k_hist<ROOT, 16, kHistLdsStride, false, true>), g, b, lds, s, c);
@@ -689,6 +706,7 @@ static void launch_hist(const Ctx &c, const Knobs &kn, int gx, int gy, size_t ld
         else hipLaunchKernelGGL((k_hist<ROOT, 16, kHistLdsStride>), g, b, lds, s, c);
         return;
     }
+    took(RL_HARM_STRIDE, g, lds);
     switch (c.sub) {
     case 16: hipLaunchKernelGGL((k_hist<ROOT, 16, 0>), g, b, lds, s, c); break;
     case 8: hipLaunchKernelGGL((k_hist<ROOT, 8, 0>), g, b, lds, s, c); break;
@@ -1340,6 +1358,18 @@ int rl_get_array(rl_trainer *t, int32_t which, void *out, int64_t cap_bytes)
     case RL_ARR_SPARSE_INFO: {
         const int64_t v[8] = {c.sp_on ? c.sp_ngroups : 0, t->sp_entries, c.sp_on ? c.numFG - c.sp_ngroups : c.numFG, t->sp_cols,
                               c.crows ? t->cr_groups : 0, (int64_t)t->cr_entries, (int64_t)t->cr_overflow, c.cr_stride};
+        if (cap_bytes < (int64_t)sizeof(v)) return fail(RL_ERR_INVALID, "output buffer too small");
+        memcpy(out, v, sizeof(v));
+        return RL_OK;
+    }
+    case RL_ARR_LAUNCH_ARMS: {       // host counters (t->arms) and the settings in force: the knobs as read, what rl_init left in the context
+        int64_t v[RL_ARM_COUNT_];
+        memcpy(v, t->arms, sizeof(v));
+        v[RL_ARM_SET_STEP_AHEAD] = t->knobs.step_ahead; v[RL_ARM_SET_DIST_AHEAD] = t->knobs.dist_ahead;
+        v[RL_ARM_SET_P8] = c.p8; v[RL_ARM_SET_DM_ROOT] = c.dm_root; v[RL_ARM_SET_DM_DIV] = c.dm_div; v[RL_ARM_SET_SUB_CHILD] = c.sub_child; v[RL_ARM_SET_HIST_NT] = c.hist_nt;
+        v[RL_ARM_SET_ANY_RUNS] = c.any_runs; v[RL_ARM_SET_CROWS] = c.crows ? 1 : 0; v[RL_ARM_SET_TIE_ON] = c.tie_on; v[RL_ARM_SET_NODE_DIV] = c.node_div;
+        v[RL_ARM_SET_NODE_MIN] = c.node_min; v[RL_ARM_SET_BALANCE] = c.balance; v[RL_ARM_SET_BALANCE_TARGET] = c.balance_target; v[RL_ARM_SET_BALANCE_MIN] = c.balance_min;
+        v[RL_ARM_SET_BALANCE_CAP] = c.balance_cap; v[RL_ARM_SET_NODE_CHUNK] = c.node_chunk; v[RL_ARM_SET_MAX_CHUNKS] = c.maxChunks;
         if (cap_bytes < (int64_t)sizeof(v)) return fail(RL_ERR_INVALID, "output buffer too small");
         memcpy(out, v, sizeof(v));
         return RL_OK;

@@ -29,6 +29,21 @@ def test_library_exports_every_declared_symbol():
     assert L.rl_abi_version() == 5
 
 
+def test_launch_arm_indices_of_the_python_side_are_the_headers():
+    """RL_ARR_LAUNCH_ARMS is read by index: _native.ARM / HARM must name exactly the RL_ARM_* / RL_HARM_* values of include/rlhip.h, the array id
+    is appended behind the existing ones, and no earlier id has moved"""
+    hdr = open(os.path.join(ROOT, "include", "rlhip.h")).read()
+    for prefix, table in (("RL_ARM_", N.ARM), ("RL_HARM_", N.HARM)):
+        got = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b%s([A-Z0-9_]+) = (\d+)" % prefix, hdr)}
+        assert got == table, (prefix, sorted(set(got.items()) ^ set(table.items())))
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bRL_ARR_([A-Z0-9_]+) = (\d+)", hdr)}
+    assert ids == N.ARR and len(set(ids.values())) == len(ids)
+    assert ids["LAUNCH_ARMS"] == max(ids.values()) == 25 and ids["PIECE_STATS"] == 24 and ids["STEP_LOG"] == 20 and ids["LAMBDA"] == 1
+    # the counters fit between the last arm and the settings, nothing overlaps
+    idx = sorted(v for k, v in N.ARM.items() if k not in ("HIST_ROOT", "HIST_CHILD", "COUNT_"))
+    assert len(set(idx)) == len(idx) and idx[0] >= N.ARM["HIST_CHILD"] + N.HARM["COUNT_"] and idx[-1] < N.ARM["COUNT_"]
+
+
 def test_no_cpu_fallback_without_device(gpu_available):
     _ensure_built()
     if gpu_available:

@@ -144,7 +144,8 @@ def test_sharded_tie_break_with_a_rank_that_grows_its_arena(tmp_path):
 
 
 @pytest.mark.parametrize("world,metric,k,opt", [(2, "NDCG", 10, "noa2a"), (3, "NDCG", 10, "piecemiss"), (2, "NDCG", 10, "countpass,ownerx"), (3, "NDCG", 10, "ownerx"), (2, "NDCG", 10, "ownerx,noa2a"), (3, "NDCG", 10, "leafm1"), (2, "NDCG", 10, "qrel"), (3, "MAP", 0, "qrel"),
-                                                (2, "NDCG", 10, "dupcols"), (3, "NDCG", 10, "dupcols,regrow"), (2, "NDCG", 10, "tcm1"), (3, "NDCG", 10, "tcm1")])
+                                                (2, "NDCG", 10, "dupcols"), (3, "NDCG", 10, "dupcols,regrow"), (2, "NDCG", 10, "tcm1"), (3, "NDCG", 10, "tcm1"),
+                                                (2, "NDCG", 10, "ownerx,hostplan"), (2, "NDCG", 10, "ahead0"), (2, "NDCG", 10, "ahead2")])
 def test_sharded_options(world, metric, k, opt, tmp_path):
     """ownerx: the leaf-owner exchange (RLHIP_DIST_OWNER_CHAINS=1; what runs beyond 256 leaves) instead of the distributed float chains: lambda / weight of a
     leaf's documents travel to ONE owner rank -- at most 16 bytes per document that lives elsewhere, one all-to-all a round;
@@ -152,7 +153,10 @@ def test_sharded_options(world, metric, k, opt, tmp_path):
     GLOBAL document count); qrel: external relevance judgments, every rank passing the entries of its own lists; dupcols: duplicated columns -- ties
     over several features that share one cut are deferred to the per-tree batch, every rank checks the cuts on its own documents and the verdict
     is all-reduced (regrow: forced to fail, all ranks grow the tree again); tcm1: -tc -1, threshold tables of more than 4095 entries (the ranks merge
-    their distinct values at rl_init and split the tables into the same virtual features: LambdaMART.java:135-140 has no limit) -- each equals the one-GPU run"""
+    their distinct values at rl_init and split the tables into the same virtual features: LambdaMART.java:135-140 has no limit); hostplan: the plan of
+    the leaf-owner exchange made on the host behind a stream synchronisation (RLHIP_DIST_HOST_PLAN=1; it is the leaf-owner exchange's, so the case
+    runs with ownerx) instead of k_plan_exchange; ahead0 / ahead2: RLHIP_DIST_STEP_AHEAD, growth steps enqueued beyond the last one the host has seen
+    (default 1) -- each equals the one-GPU run"""
     cfg = (9000, 16, "mslr", 5, 10, 4)
     ref = single(*cfg, metric=metric, k=k, opts=tuple(opt.split(",")))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -162,6 +166,10 @@ def test_sharded_options(world, metric, k, opt, tmp_path):
         env["RLHIP_DIST_OWNER_CHAINS"] = "1"
     if "countpass" in opt:       # round 5's sharded partition (count pass + two-pass scatter, chunks by the per-node rule) instead of the single pass from local cumulative counts
         env["RLHIP_DIST_COUNT_PASS"] = "1"
+    if "hostplan" in opt:
+        env["RLHIP_DIST_HOST_PLAN"] = "1"
+    if "ahead0" in opt or "ahead2" in opt:
+        env["RLHIP_DIST_STEP_AHEAD"] = "0" if "ahead0" in opt else "2"
     if "piecemiss" in opt:       # every piece of a leaf's chain behind the first is treated as a detected window miss: its rank re-evaluates it from the exact start
         env["RLHIP_PIECE_FORCE_MISS"] = "1"
     out = str(tmp_path / "o.npz")
@@ -178,6 +186,14 @@ def test_sharded_options(world, metric, k, opt, tmp_path):
         st = z["dist_stats"].astype(np.float64)
         assert st[4] == cfg[5] + int(z["tie_stats"][9]) and st[5] > 0, st          # one leaf-owner exchange per round (one more for a tree grown a second time)
         assert st[5] / st[4] <= 16.0 * cfg[0] * (world - 1) / world * 0.95, st
+    # which variant rank 0 ran (RL_ARR_LAUNCH_ARMS): a knob that is not read would let the case pass on the default path
+    arms = z["arms"]
+    plans = cfg[5] + int(z["tie_stats"][9])
+    if "hostplan" in opt:
+        assert arms[N.ARM["XPLAN_HOST"]] == plans and arms[N.ARM["XPLAN_DEVICE"]] == 0, arms
+    elif "ownerx" in opt:
+        assert arms[N.ARM["XPLAN_DEVICE"]] == plans and arms[N.ARM["XPLAN_HOST"]] == 0, arms
+    assert arms[N.ARM["SET_DIST_AHEAD"]] == (0 if "ahead0" in opt else 2 if "ahead2" in opt else 1), arms
     if opt == "leafm1":
         assert max(len(t["feature"]) for t in trees) > 2 * cfg[4] - 1, "the trees never outgrew the explicit leaf budget: -leaf -1 was not exercised"
 
