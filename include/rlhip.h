@@ -52,7 +52,7 @@ enum {
     RL_ERR_UNSUPPORTED = -4, /* valid for RankLib but not built yet (documented in DESIGN.md) */
     RL_ERR_NO_DEVICE = -5,   /* no gfx950 device visible: there is NO CPU fallback */
     RL_ERR_COMM = -6,        /* RCCL failure */
-    RL_ERR_NO_BEST = -7      /* rl_ln_learn with a validation set: no epoch scored above 0.0, no model was saved (the Java throws) */
+    RL_ERR_NO_BEST = -7      /* rl_ln_learn / rl_rn_learn with a validation set: no epoch scored above 0.0, no model was saved (the Java throws) */
 };
 
 /* train / validation metric (-metric2t): metric/{NDCG,DCG,AP,ERR}Scorer.java.  P, RR and BEST are not built for
@@ -628,7 +628,7 @@ int  rl_lr_predict(int32_t device, const int32_t *feature_ids, int32_t n_feature
 
 /* ---- Neural-net models (RankNet -ranker 1, LambdaRank 5, ListNet 7: learning/neuralnet/) ---------------------------------
  * Scoring only: the forward pass RankNet.eval (RankNet.java:336-349), which LambdaRank and ListNet inherit, with the Java's double
- * arithmetic kept bit for bit.  Training is built for ListNet only (below).  The network is the one RankNet.wire() (:87-110)
+ * arithmetic kept bit for bit.  Training is built for ListNet and RankNet (below), not for LambdaRank.  The network is the one RankNet.wire() (:87-110)
  * makes: layer 0 holds the n_features inputs and a bias neuron of output 1.0, then come the hidden layers, then one output neuron;
  * every neuron past layer 0 computes 1.0 / (1.0 + exp(-wsum)) (LogiFunction.java:18-20) of wsum = 0.0, += source.output * weight over
  * its inLinks in order (Neuron.computeOutput, Neuron.java:68-76): the previous layer's neurons in order, the bias LAST. */
@@ -704,6 +704,61 @@ int  rl_ln_trace(const rl_ln *h, rl_ln_trace_rec *out, int64_t cap, int64_t *n);
 int  rl_ln_debug_doc_scores(const rl_ln *h, int32_t validation, double *out, int64_t cap);
 /* debug: ms of all epoch kernels together (device events) and of scoring + ranking both sets after every epoch (host clock) */
 int  rl_ln_debug_times(const rl_ln *h, double *epoch_ms, double *score_ms);
+
+/* ---- RankNet training (-ranker 1, learning/neuralnet/RankNet.java, Neuron.java) ------------------------------------------
+ * RankNet.learn() (:290-334) with the Java's double arithmetic kept bit for bit: the network of rl_net_create (n_features
+ * inputs and a bias neuron, n_hidden hidden layers, one output neuron).  Per epoch every ranked list is walked in order: the outputs of
+ * all its documents are computed with the weights as they are (batchFeedForward), then the weights are updated once per document, in
+ * order, from the pairs (i, j) with label_i > label_j (batchBackPropagate: Neuron.computeDelta / updateDelta / updateWeight).  After
+ * every epoch both sets are scored and ranked and the mis-ordered pairs of the training set are counted (estimateLoss :230-252, the
+ * count only); the best-on-validation rule, the restore and the refusals are rl_ln's.  The caller gives the start weights
+ * (rl_rn_set_weights); the library never sees a seed.  LambdaRank (-ranker 5) is not built. */
+typedef struct rl_rn rl_rn;             /* opaque */
+
+typedef struct {
+    int32_t  n_epochs;          /* RankNet.nIteration       default 100 (-epoch); < 0: RL_ERR_INVALID */
+    double   learning_rate;     /* Neuron.learningRate as RankNet.init() sets it, default 0.00005 (-lr); not finite: RL_ERR_INVALID */
+    int32_t  n_hidden;          /* RankNet.nHiddenLayer     default 1 (-layer); < 0: RL_ERR_INVALID */
+    const int32_t *hidden_sizes;/* [n_hidden] neurons per hidden layer (-node), copied by rl_rn_create; NULL: 10 each, the default of
+                                   RankNet.nHiddenNodePerLayer; a size < 1: RL_ERR_INVALID */
+    int32_t  metric;            /* RL_METRIC_*: NDCG, DCG, MAP, ERR, P, RR */
+    int32_t  metric_k;          /* the scorer's k (10; 0 for MAP) */
+    int32_t  device;            /* HIP device ordinal */
+    double   err_max;           /* ERRScorer.MAX (-gmax): default 16 */
+} rl_rn_params;
+
+typedef struct {
+    int32_t epoch;              /* 1 .. n_epochs */
+    int32_t saved;              /* 1 if this epoch became the best on validation */
+    int64_t misordered;         /* estimateLoss's misorderedPairs on the training set after the epoch */
+    int64_t total_pairs;        /* init()'s totalPairs: the training pairs with different labels (the same in every record) */
+    double  train;              /* scorer.score(rank(samples)) after the epoch, not rounded */
+    double  valid;              /* the same on the validation set (0 without one) */
+} rl_rn_trace_rec;
+
+void rl_rn_params_default(rl_rn_params *p);         /* 100, 0.00005, 1 hidden layer of 10, NDCG@10, device 0, err_max 16 */
+int  rl_rn_create(const rl_rn_params *p, rl_rn **out);
+void rl_rn_destroy(rl_rn *h);
+/* X, labels, qoff, qkey as rl_ln_set_train's; the lists are walked in the given order */
+int  rl_rn_set_train(rl_rn *h, const float *X, int64_t n_docs, int32_t n_features, const float *labels, const int32_t *qoff,
+                     int32_t n_queries, const int32_t *qkey);
+int  rl_rn_set_validation(rl_rn *h, const float *X, int64_t n_docs, const float *labels, const int32_t *qoff, int32_t n_queries,
+                          const int32_t *qkey);
+int  rl_rn_set_external_judgments(rl_rn *h, int32_t validation, const double *ideal_dcg, const int32_t *rel_doc_count);
+/* the start weights in rl_net_create's layout: per layer l = 1 .. n_hidden + 1 a row-major [n_l][n_{l-1} + 1], the bias last.  A wrong n
+ * is RL_ERR_INVALID.  Required before the handle learns (without them, or without a training set, learning is RL_ERR_INVALID); a later
+ * set_train discards them */
+int  rl_rn_set_weights(rl_rn *h, const double *w, int32_t n);
+int  rl_rn_learn(rl_rn *h);
+/* after learning, in the same layout: the restored best on validation, or the last epoch's.  w may be NULL (only *n is set) */
+int  rl_rn_get_weights(const rl_rn *h, double *w, int32_t cap, int32_t *n);
+int  rl_rn_scores(const rl_rn *h, double *train, double *valid);
+/* one record per epoch; out may be NULL (only *n is set); at most cap records are written */
+int  rl_rn_trace(const rl_rn *h, rl_rn_trace_rec *out, int64_t cap, int64_t *n);
+/* debug: the final weights' output for every document of the training (validation != 0: validation) set, as the scoring kernel wrote it */
+int  rl_rn_debug_doc_scores(const rl_rn *h, int32_t validation, double *out, int64_t cap);
+/* debug: ms of all epoch kernels together (device events) and of scoring, ranking and pair counting after every epoch (host clock) */
+int  rl_rn_debug_times(const rl_rn *h, double *epoch_ms, double *score_ms);
 
 #ifdef __cplusplus
 }

@@ -80,7 +80,16 @@ class RlLnTraceRec(C.Structure):
 
 
 LN_TRACE_DTYPE = np.dtype([("epoch", np.int32), ("saved", np.int32), ("train", np.float64), ("valid", np.float64)])
-RL_ERR_NO_BEST = -7                    # rl_ln_learn: no epoch scored above 0.0 on the validation set
+RL_ERR_NO_BEST = -7                    # rl_ln_learn / rl_rn_learn: no epoch scored above 0.0 on the validation set
+
+
+class RlRnParams(C.Structure):
+    _fields_ = [("n_epochs", C.c_int32), ("learning_rate", C.c_double), ("n_hidden", C.c_int32), ("hidden_sizes", C.POINTER(C.c_int32)),
+                ("metric", C.c_int32), ("metric_k", C.c_int32), ("device", C.c_int32), ("err_max", C.c_double)]
+
+
+RN_TRACE_DTYPE = np.dtype([("epoch", np.int32), ("saved", np.int32), ("misordered", np.int64), ("total_pairs", np.int64),
+                           ("train", np.float64), ("valid", np.float64)])
 
 RL_RANKER = dict(MART=0, LAMBDAMART=6)
 
@@ -127,6 +136,8 @@ ABI_SYMBOLS = [
     "rl_net_create", "rl_net_destroy", "rl_net_predict", "rl_net_predict_device", "rl_net_debug_path",
     "rl_ln_params_default", "rl_ln_create", "rl_ln_destroy", "rl_ln_set_train", "rl_ln_set_validation", "rl_ln_set_external_judgments",
     "rl_ln_set_weights", "rl_ln_learn", "rl_ln_get_weights", "rl_ln_scores", "rl_ln_trace", "rl_ln_debug_doc_scores", "rl_ln_debug_times",
+    "rl_rn_params_default", "rl_rn_create", "rl_rn_destroy", "rl_rn_set_train", "rl_rn_set_validation", "rl_rn_set_external_judgments",
+    "rl_rn_set_weights", "rl_rn_learn", "rl_rn_get_weights", "rl_rn_scores", "rl_rn_trace", "rl_rn_debug_doc_scores", "rl_rn_debug_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -206,7 +217,7 @@ def lib():
     L.rl_set_timing_flags.argtypes = [vp, i32]
     L.rl_debug_membench.argtypes = [i32, i32, i64, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     for pre, params in (("rl_ca_", RlCaParams), ("rl_ada_", RlAdaParams), ("rl_rb_", RlRbParams), ("rl_lr_", RlLrParams),
-                        ("rl_ln_", RlLnParams)):
+                        ("rl_ln_", RlLnParams), ("rl_rn_", RlRnParams)):
         if not hasattr(L, pre + "create"):      # (A/B builds of older sources lack the later linear rankers)
             continue
         fn = lambda name: getattr(L, pre + name)      # noqa: E731
@@ -245,6 +256,12 @@ def lib():
         L.rl_ln_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_ln_debug_doc_scores.argtypes = [vp, i32, vp, i64]
         L.rl_ln_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_rn_create"):
+        L.rl_rn_set_weights.argtypes = [vp, vp, i32]
+        L.rl_rn_get_weights.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        L.rl_rn_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.rl_rn_debug_doc_scores.argtypes = [vp, i32, vp, i64]
+        L.rl_rn_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(L, "rl_net_create"):
         L.rl_net_create.argtypes = [i32, vp, i32, vp, i32, vp, i32, C.POINTER(vp)]
         L.rl_net_destroy.argtypes = [vp]
@@ -897,8 +914,8 @@ class LinearRegTrainer(_LinearTrainer):
 
 
 class NoBestModelError(RankLibError):
-    """rl_ln_learn returned RL_ERR_NO_BEST: with a validation set, no epoch scored above 0.0 (learning.ListNet turns it into the Java's
-    message)"""
+    """rl_ln_learn / rl_rn_learn returned RL_ERR_NO_BEST: with a validation set, no epoch scored above 0.0 (learning.ListNet and RankNet
+    turn it into the Java's message)"""
 
 
 class ListNetTrainer(_LinearTrainer):
@@ -913,25 +930,25 @@ class ListNetTrainer(_LinearTrainer):
 
     def set_weights(self, w):
         w = np.ascontiguousarray(w, dtype=np.float64)
-        check(lib().rl_ln_set_weights(self.h, w.ctypes.data, w.size))
+        check(self._fn("set_weights")(self.h, w.ctypes.data, w.size))
 
     def learn(self):
-        rc = lib().rl_ln_learn(self.h)
+        rc = self._fn("learn")(self.h)
         if rc == RL_ERR_NO_BEST:
             raise NoBestModelError("%s (rlhip status %d)" % (lib().rl_last_error().decode("utf-8", "replace"), rc))
         check(rc)
 
     def weights(self):
         n = C.c_int32(0)
-        check(lib().rl_ln_get_weights(self.h, None, 0, C.byref(n)))
+        check(self._fn("get_weights")(self.h, None, 0, C.byref(n)))
         w = np.zeros(max(1, n.value), np.float64)
-        check(lib().rl_ln_get_weights(self.h, w.ctypes.data, n.value, C.byref(n)))
+        check(self._fn("get_weights")(self.h, w.ctypes.data, n.value, C.byref(n)))
         return w[:n.value]
 
     def doc_scores(self, validation=False):
         """[N] f64: the final weights' output for every document of the set, as k_ln_score wrote it"""
         out = np.zeros(max(1, self.Nv if validation else self.N), np.float64)
-        check(lib().rl_ln_debug_doc_scores(self.h, 1 if validation else 0, out.ctypes.data, out.size))
+        check(self._fn("debug_doc_scores")(self.h, 1 if validation else 0, out.ctypes.data, out.size))
         return out[:self.Nv if validation else self.N]
 
     def set_validation(self, X, labels, qoff, qkey=None):
@@ -941,8 +958,23 @@ class ListNetTrainer(_LinearTrainer):
     def times(self):
         """dict: epoch_ms (all k_ln_epoch launches, device events), score_ms (scoring + ranking after every epoch, host clock)"""
         e, s = C.c_double(0), C.c_double(0)
-        check(lib().rl_ln_debug_times(self.h, C.byref(e), C.byref(s)))
+        check(self._fn("debug_times")(self.h, C.byref(e), C.byref(s)))
         return dict(epoch_ms=e.value, score_ms=s.value)
+
+
+class RankNetTrainer(ListNetTrainer):
+    """Thin object wrapper over the rl_rn handle: RankNet.learn() on one GPU (rl_rn.inc in rl_ca.hip).  hidden_sizes: the hidden layers'
+    neuron counts ([] = -layer 0).  The start weights are the caller's (set_weights, NetModel's layout: per layer a row-major
+    [n_l][n_{l-1} + 1], the bias last); weights() returns the same layout.  trace(): RN_TRACE_DTYPE, one record per epoch."""
+    _prefix, _name, _trace_dtype = "rl_rn_", "RankNet", RN_TRACE_DTYPE
+
+    def __init__(self, n_epochs=100, learning_rate=0.00005, hidden_sizes=(10,), metric="NDCG", metric_k=10, device=0, err_max=16.0):
+        if not hasattr(lib(), "rl_rn_create"):
+            raise RankLibError("rlhip: this librlhip.so has no RankNet training (rl_rn_*)")
+        self.hidden = [int(v) for v in hidden_sizes]
+        hid = np.ascontiguousarray(self.hidden if self.hidden else [0], dtype=np.int32)      # a real pointer for an empty list too
+        self._open(RlRnParams, metric, metric_k, device, err_max, n_epochs=int(n_epochs), learning_rate=float(learning_rate),
+                   n_hidden=len(self.hidden), hidden_sizes=hid.ctypes.data_as(C.POINTER(C.c_int32)))
 
 
 def _predict_arrays(feature_ids, weights, rows):

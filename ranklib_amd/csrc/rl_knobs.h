@@ -118,4 +118,8 @@ inline int read_lr_rb_knob() { const int v = knob::value("RLHIP_LR_RB", 0); retu
 // sum chain (2) or its update (4); the weights such a run leaves are meaningless.  Anything else: the whole kernel
 inline int read_ln_skip_knob() { const int v = knob::value("RLHIP_LN_SKIP", 0); return (v == 1 || v == 2 || v == 4) ? v : 0; }
 
+// RankNet training (rl_rn::skip, read by rl_rn_create): a measuring aid of tools/rn_bench.py -- k_rn_epoch without its forward pass (1), its
+// deltas (2) or its update (4); the weights such a run leaves are meaningless.  Anything else: the whole kernel
+inline int read_rn_skip_knob() { const int v = knob::value("RLHIP_RN_SKIP", 0); return (v == 1 || v == 2 || v == 4) ? v : 0; }
+
 }  // namespace rl

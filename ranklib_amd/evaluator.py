@@ -1,17 +1,20 @@
-"""Command line of the `-ranker 6 / 0 / 8 / 4 / 3 / 2 / 9 / 7` paths: mirrors the flags of eval/Evaluator.java that reach LambdaMART, MART, Random
-Forests, Coordinate Ascent, AdaRank, RankBoost, Linear Regression and ListNet (:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
+"""Command line of the `-ranker 6 / 0 / 8 / 4 / 3 / 2 / 9 / 7 / 1` paths: mirrors the flags of eval/Evaluator.java that reach LambdaMART, MART, Random
+Forests, Coordinate Ascent, AdaRank, RankBoost, Linear Regression, ListNet and RankNet (:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
 
     python -m ranklib_amd.evaluator -train f -ranker 6 -metric2t NDCG@10 -tree 1000 -leaf 31 -save model.txt
     python -m ranklib_amd.evaluator -load model.txt -rank f -score out.txt
 
 -load also takes the model files of the neural-net rankers (## RankNet, ## LambdaRank, ## ListNet: learning/neuralnet/) for -test, -rank
--score / -indri, -idv, -norm and -qrel; they are scored on the GPU.  -train with -ranker 1 / 5 stays refused, and so does -ranker 7 unless
--netseed n (an rlhip extension) seeds ListNet's initial weights, which the Java draws from an unseeded Random:
+-score / -indri, -idv, -norm and -qrel; they are scored on the GPU.  -train with -ranker 5 stays refused, and so do -ranker 7 unless
+-netseed n and -ranker 1 unless -rnseed n (rlhip extensions) seed the initial weights, which the Java draws from an unseeded Random:
 
     python -m ranklib_amd.evaluator -train f -ranker 7 -netseed 3 -epoch 200 -metric2t NDCG@10 -validate v -save model.txt
+    python -m ranklib_amd.evaluator -train f -ranker 1 -rnseed 3 -epoch 50 -layer 1 -node 10 -lr 0.00005 -validate v -save model.txt
 
 With -ranker 7, -epoch n sets ListNet.nIteration, and -lr x, like the Java's (:294-296), sets ListNet.learningRate to Neuron.learningRate
 -- 0.001 -- whatever x is; without -lr the rate is ListNet's default 0.00001.  Both, and the seed, are restored when main returns.
+With -ranker 1 -rnseed n, -epoch, -layer, -node and -lr x set RankNet's nIteration, nHiddenLayer, nHiddenNodePerLayer and learningRate
+(= x, no quirk) for the run; in every other run those flags are parsed and leave RankNet's statics alone.
 """
 import logging
 import math
@@ -212,9 +215,11 @@ def main(argv=None):
     if not args:
         print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
-              "(-load also reads RankNet, LambdaRank and ListNet models; RankNet and LambdaRank are scored, not trained) | "
+              "(-load also reads RankNet, LambdaRank and ListNet models; LambdaRank is scored, not trained) | "
               "-train <file> -ranker 7 -netseed n [-epoch n] [-lr x] (ListNet; -netseed, an rlhip extension, seeds the initial weights and is required; "
-              "-lr x sets the learning rate to 0.001 whatever x is, as the Java does; without it 0.00001)")
+              "-lr x sets the learning rate to 0.001 whatever x is, as the Java does; without it 0.00001) | "
+              "-train <file> -ranker 1 -rnseed n [-epoch n] [-layer n] [-node n] [-lr x] (RankNet; -rnseed, an rlhip extension, seeds the initial weights "
+              "and is required; defaults 100 epochs, 1 hidden layer of 10 nodes, learning rate 0.00005; LambdaRank, -ranker 5, is not trained)")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
     Evaluator.mustHaveRelDoc = False
@@ -225,7 +230,7 @@ def main(argv=None):
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)
     ttSplit = tvSplit = 0.0
     foldCV, kcvModelDir, kcvModelFile = -1, "", ""
-    epochs = netSeed = None
+    epochs = netSeed = rnSeed = layers = nodes = lrValue = None
     lrGiven = False
     i = 0
     while i < len(args):                                    # :230-372 (flags are matched case-insensitively)
@@ -293,14 +298,13 @@ def main(argv=None):
         elif a == "-max": AdaRank.maxSelCount = int(nxt())
         elif a == "-l2": LinearRegRank.lambda_ = float(nxt())                               # :355-356, whatever -ranker says
         elif a == "-epoch": epochs = int(nxt())              # :284-288; reaches ListNet.nIteration in a -ranker 7 run only (below)
-        elif a == "-lr":                                    # :294-296; likewise
-            float(nxt())
+        elif a == "-lr":                                    # :294-296; likewise (and RankNet.learningRate in a -ranker 1 run)
+            lrValue = float(nxt())
             lrGiven = True
         elif a == "-netseed": netSeed = int(nxt())          # rlhip extension: seeds ListNet's initial weights (the Java's Random is unseeded)
-        elif a in ("-layer", "-node"):
-            # parameters of the rankers that are not trained here: parsed (the reference's own test passes -round -epoch to every
-            # ranker, test:eval/EvaluatorTest.java:207-220) and ignored
-            nxt()
+        elif a == "-rnseed": rnSeed = int(nxt())            # rlhip extension: seeds RankNet's initial weights, likewise
+        elif a == "-layer": layers = int(nxt())             # :290-293; reach RankNet's statics in a -ranker 1 -rnseed run only (below); every
+        elif a == "-node": nodes = int(nxt())               # other run parses and ignores them (test:eval/EvaluatorTest.java:207-220 passes them to every ranker)
         elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = RankNet.device = int(nxt())
         else:
             raise RankLibError("Unknown command-line parameter: " + args[i])     # :369-371 (incl. the documented -silent)
@@ -308,11 +312,13 @@ def main(argv=None):
     if not testMetric:
         testMetric = trainMetric                            # :379-381
     listnet = rankerType == 7 and netSeed is not None        # ListNet trains behind a seed only
-    if trainFile and rankerType not in _RANKER_TYPES and not listnet:
+    ranknet = rankerType == 1 and rnSeed is not None         # RankNet likewise, behind its own
+    if trainFile and rankerType not in _RANKER_TYPES and not listnet and not ranknet:
         raise RankLibError("rlhip builds -ranker 6 (LambdaMART), -ranker 0 (MART), -ranker 8 (Random Forests), -ranker 4 (Coordinate Ascent), "
                            "-ranker 3 (AdaRank), -ranker 2 (RankBoost) and -ranker 9 (Linear Regression) only: the neural-net rankers "
                            "(-ranker 1 RankNet, 5 LambdaRank, 7 ListNet) are out of scope"
-                           + ("; ListNet trains only with -netseed n, a seed for its initial weights" if rankerType == 7 else ""))
+                           + ("; ListNet trains only with -netseed n, a seed for its initial weights" if rankerType == 7 else
+                              "; RankNet trains only with -rnseed n, a seed for its initial weights" if rankerType == 1 else ""))
 
     def flows(rtype):                                       # :469-520
         nonlocal kcvModelDir, kcvModelFile
@@ -339,6 +345,22 @@ def main(argv=None):
                 e.test(savedModelFile, testFile, prpFile)
         return 0
 
+    if ranknet:
+        # RankNet's statics belong to this run only, as ListNet's below
+        saved = (RankNet.nIteration, RankNet.nHiddenLayer, RankNet.nHiddenNodePerLayer, RankNet.learningRate, RankNet.seed, Neuron.learningRate)
+        try:
+            RankNet.seed = rnSeed
+            if epochs is not None:
+                RankNet.nIteration = epochs                     # :284-288
+            if layers is not None:
+                RankNet.nHiddenLayer = layers                   # :290-291
+            if nodes is not None:
+                RankNet.nHiddenNodePerLayer = nodes             # :292-293
+            if lrGiven:
+                RankNet.learningRate = lrValue                  # :295
+            return flows(RankerType.RANKNET)
+        finally:
+            (RankNet.nIteration, RankNet.nHiddenLayer, RankNet.nHiddenNodePerLayer, RankNet.learningRate, RankNet.seed, Neuron.learningRate) = saved
     if not listnet:
         return flows(_RANKER_TYPES.get(rankerType, RankerType.LAMBDAMART))
     # ListNet's statics belong to this run only: the refusals and defaults other callers see are the same before and after it

@@ -11,8 +11,8 @@ RankLib's API read the same here:
     AdaRank                      learning/boosting/AdaRank.java:33-346  (learn and eval run on the GPU through librlhip.so)
     LinearRegRank                learning/LinearRegRank.java:23-240     (learn and eval run on the GPU through librlhip.so)
     RankNet / LambdaRank / ListNet   learning/neuralnet/RankNet.java:33-490, LambdaRank.java, ListNet.java:24-236
-                                 (model text in and out, eval on the GPU through librlhip.so; ListNet also trains there,
-                                 behind a seed; RankNet and LambdaRank training is not built)
+                                 (model text in and out, eval on the GPU through librlhip.so; ListNet and RankNet also train
+                                 there, each behind a seed; LambdaRank training is not built)
     RankerType / RankerFactory   learning/RankerType.java, learning/RankerFactory.java:36-118
     RankerTrainer                learning/RankerTrainer.java:23-56
 
@@ -1158,11 +1158,12 @@ class LinearRegRank(_LinearRanker):
 
 
 def _neural_refusal(type_name):
-    """what createRanker, init() and learn() say about RANKNET, LAMBDARANK and (without a seed) LISTNET: they load and score, they do not
-    train"""
+    """what createRanker, init() and learn() say about LAMBDARANK and (without a seed) RANKNET and LISTNET: they load and score, they do
+    not train"""
     return ("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank), 2 (RankBoost) and "
             "9 (Linear Regression); %s, one of the neural-net rankers, is out of scope (SURVEY.md 8)%s"
-            % (type_name, "; ListNet trains only with a seed for its initial weights (-netseed n / ListNet.seed)" if type_name == "LISTNET" else ""))
+            % (type_name, "; ListNet trains only with a seed for its initial weights (-netseed n / ListNet.seed)" if type_name == "LISTNET" else
+               "; RankNet trains only with a seed for its initial weights (-rnseed n / RankNet.seed)" if type_name == "RANKNET" else ""))
 
 
 class JavaRandom:
@@ -1196,8 +1197,8 @@ class JavaRandom:
 
 
 class Neuron:
-    """the one static of learning/neuralnet/Neuron.java that reaches ListNet: ListNet.init() copies ListNet.learningRate into it, and
-    `-lr x` copies it (0.001 unless an earlier init() changed it) into ListNet.learningRate (eval/Evaluator.java:294-296)"""
+    """the one static of learning/neuralnet/Neuron.java that reaches training: ListNet.init() and RankNet.init() copy their learningRate
+    into it, and `-lr x` copies it (0.001 unless an earlier init() changed it) into ListNet.learningRate (eval/Evaluator.java:294-296)"""
     learningRate = 0.001              # Neuron.java:22
 
 
@@ -1218,14 +1219,20 @@ class RankNet(Ranker):
     then the hidden layers, then one output neuron.  self.weights[l - 1] is layer l's matrix [n_l][n_{l-1} + 1]: row j = the weights of
     neuron j's inLinks (the previous layer's neurons in order, the bias last), the order eval() sums in.  A model file lists the weights by
     outLinks instead: input and hidden neurons feed the next layer's neurons in order, the bias neuron (line "0 F") every neuron of layer
-    1, then of layer 2, ..., then the output neuron.  init() and learn() are refused: training is not built (ListNet, a
-    subclass, trains behind a seed: DESIGN.md 15)."""
-    # process-global parameters, like the Java statics (:37-40); only nIteration is used here (the "## Epochs" line of model())
+    1, then of layer 2, ..., then the output neuron.
+
+    init() and learn() (:257-334) run on an MI355X (librlhip.so rl_rn_*: per epoch every list's forward pass, then one weight update per
+    document from its pairs, bit for bit the Java's doubles: DESIGN.md 16) -- but only with RankNet.seed set (-rnseed n, an rlhip
+    extension): the Java draws the initial weights from an unseeded static Random (Synapse.java:18,29).  Here every init() draws them from
+    a fresh java.util.Random(seed), two draws per synapse in wire()'s creation order.  With seed = None both stay refused.  LambdaRank, a
+    subclass, is refused whatever the seed; ListNet, another, looks at its own seed only."""
+    # process-global parameters, like the Java statics (:37-40)
     nIteration = 100
     nHiddenLayer = 1
     nHiddenNodePerLayer = 10
     learningRate = 0.00005
     device = 0
+    seed = None                       # rlhip extension (-rnseed): None = training refused
     _TYPE = "RANKNET"
     _LOAD = "RankNet"                 # the class whose loadFromString runs: LambdaRank inherits RankNet's, ListNet has its own copy
 
@@ -1234,12 +1241,94 @@ class RankNet(Ranker):
         self.hidden = []              # sizes of the hidden layers
         self.weights = []             # per layer past the input: np.float64 [n_l][n_{l-1} + 1]
         self._net = None
+        self._trainer = None
 
-    def init(self):
-        raise RankLibError(_neural_refusal(self._TYPE))
+    @staticmethod
+    def draw_synapse(rnd):
+        """Synapse.java:29: (nextInt(2) == 0 ? 1 : -1) * nextFloat() / 10 -- an int times a float, a FLOAT division by 10, widened"""
+        sign = np.float32(1 if rnd.nextInt(2) == 0 else -1)
+        return float(np.float32(np.float32(sign * rnd.nextFloat()) / np.float32(10)))
 
-    def learn(self):
-        raise RankLibError(_neural_refusal(self._TYPE))
+    @staticmethod
+    def initial_weights(seed, n):
+        """the matrices of a network of sizes n = [F, hidden ..., 1], drawn from java.util.Random(seed) in the order wire() (:87-110)
+        creates the synapses: input i to every neuron of layer 1 (i outer), then layer to layer (the source neuron outer), then the bias
+        to every neuron of layers 1, 2, ..."""
+        rnd = JavaRandom(seed)
+        w = [np.zeros((n[l], n[l - 1] + 1), np.float64) for l in range(1, len(n))]
+        for i in range(n[0]):
+            for j in range(n[1]):
+                w[0][j, i] = RankNet.draw_synapse(rnd)
+        for l in range(1, len(n) - 1):
+            for j in range(n[l]):
+                for k in range(n[l + 1]):
+                    w[l][k, j] = RankNet.draw_synapse(rnd)
+        for l in range(1, len(n)):
+            for j in range(n[l]):
+                w[l - 1][j, n[l - 1]] = RankNet.draw_synapse(rnd)
+        return w
+
+    def _trains(self):
+        """RankNet itself, and only behind RankNet.seed: LambdaRank inherits the attribute and stays refused"""
+        return self._TYPE == "RANKNET" and RankNet.seed is not None
+
+    def init(self):                   # :257-287
+        if not self._trains():
+            raise RankLibError(_neural_refusal(self._TYPE))
+        logger.info("Initializing... ")
+        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        if metric not in N.RL_CA_METRIC:
+            raise RankLibError("rlhip: the %s train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
+                               % (self.name(), self.scorer.name() if self.scorer else None))
+        hidden = [int(RankNet.nHiddenNodePerLayer)] * int(RankNet.nHiddenLayer)
+        start = self.initial_weights(RankNet.seed, [len(self.features)] + hidden + [1])
+        Neuron.learningRate = RankNet.learningRate          # :286
+        t = N.RankNetTrainer(n_epochs=RankNet.nIteration, learning_rate=Neuron.learningRate, hidden_sizes=hidden, metric=metric,
+                             metric_k=self.scorer.getK(), device=RankNet.device, err_max=ERRScorer.MAX)
+        _feed_linear_trainer(self, t, metric)
+        t.set_weights(np.concatenate([m.ravel() for m in start]))
+        self.hidden, self.weights, self._net = hidden, start, None
+        self._trainer = t
+
+    def learn(self):                  # :290-334
+        t = self._trainer
+        if not self._trains() or t is None:
+            raise RankLibError(_neural_refusal(self._TYPE))
+        nm, valid = self.scorer.name(), self.validationSamples is not None
+        logger.info("Training starts...")
+        self.printLogLn([7, 14, 9, 9], ["#epoch", "% mis-ordered", nm + "-T", nm + "-V"])
+        self.printLogLn([7, 14, 9, 9], [" ", "  pairs", " ", " "])
+        try:
+            try:
+                t.learn()
+            except N.NoBestModelError:
+                # bestModelOnValidation still holds its empty lists: l.get(0) throws (:206-223)
+                raise RankLibError("Error in NeuralNetwork.restoreBestModelOnValidation(): java.lang.IndexOutOfBoundsException: "
+                                   "Index 0 out of bounds for length 0") from None
+            for r in t.trace():           # :306: round(misorderedPairs / totalPairs, 4); the cross-entropy `error` is never printed
+                total = int(r["total_pairs"])
+                ratio = java_double_str(java_round(int(r["misordered"]) / total, 4)) if total else "NaN"
+                self.printLog([7, 14], [str(int(r["epoch"])), ratio])
+                self.printLog([9], [java_double_str(java_round(float(r["train"]), 4))])
+                if valid:
+                    self.printLog([9], [java_double_str(java_round(float(r["valid"]), 4))])
+                self.flushLog()
+            n = self._sizes()
+            flat, self.weights, at = np.array(t.weights(), np.float64), [], 0
+            for l in range(1, len(n)):
+                self.weights.append(flat[at:at + n[l] * (n[l - 1] + 1)].reshape(n[l], n[l - 1] + 1).copy())
+                at += n[l] * (n[l - 1] + 1)
+            self._net = None
+            ts, vs = t.scores()
+        finally:
+            t.close()
+            self._trainer = None
+        self.scoreOnTrainingData = java_round(ts, 4)
+        logger.info("Finished sucessfully.")
+        logger.info("%s on training data: %s", nm, java_double_str(self.scoreOnTrainingData))
+        if valid:
+            self.bestScoreOnValidationData = vs
+            logger.info("%s on validation data: %s", nm, java_double_str(java_round(vs, 4)))
 
     # --- the network's shape --------------------------------------------------------------------------------
     def _sizes(self):
@@ -1353,7 +1442,8 @@ class RankNet(Ranker):
 
 
 class LambdaRank(RankNet):
-    """learning/neuralnet/LambdaRank.java: RankNet's network, model text and eval; only training differs, and that is not built."""
+    """learning/neuralnet/LambdaRank.java: RankNet's network, model text and eval; only training differs, and that is not built:
+    init() and learn() refuse whatever RankNet.seed is (RankNet._trains)."""
     _TYPE = "LAMBDARANK"
 
     def name(self):                   # :136-138
@@ -1494,6 +1584,8 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
                 raise RankLibError("Could find the class \"%s\" you specified. Make sure the jar library is in your classpath." % rtype)
         if rtype.name == "LISTNET" and ListNet.seed is not None:      # trains behind a seed only
             r = ListNet()
+        elif rtype.name == "RANKNET" and RankNet.seed is not None:    # likewise
+            r = RankNet()
         elif rtype.name not in self.map:
             raise RankLibError(_neural_refusal(rtype.name))
         else:
