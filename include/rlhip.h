@@ -705,14 +705,20 @@ int  rl_ln_debug_doc_scores(const rl_ln *h, int32_t validation, double *out, int
 /* debug: ms of all epoch kernels together (device events) and of scoring + ranking both sets after every epoch (host clock) */
 int  rl_ln_debug_times(const rl_ln *h, double *epoch_ms, double *score_ms);
 
-/* ---- RankNet training (-ranker 1, learning/neuralnet/RankNet.java, Neuron.java) ------------------------------------------
+/* ---- RankNet and LambdaRank training (-ranker 1 / 5, learning/neuralnet/RankNet.java, LambdaRank.java, Neuron.java) ------
  * RankNet.learn() (:290-334) with the Java's double arithmetic kept bit for bit: the network of rl_net_create (n_features
  * inputs and a bias neuron, n_hidden hidden layers, one output neuron).  Per epoch every ranked list is walked in order: the outputs of
  * all its documents are computed with the weights as they are (batchFeedForward), then the weights are updated once per document, in
  * order, from the pairs (i, j) with label_i > label_j (batchBackPropagate: Neuron.computeDelta / updateDelta / updateWeight).  After
  * every epoch both sets are scored and ranked and the mis-ordered pairs of the training set are counted (estimateLoss :230-252, the
  * count only); the best-on-validation rule, the restore and the refusals are rl_ln's.  The caller gives the start weights
- * (rl_rn_set_weights); the library never sees a seed.  LambdaRank (-ranker 5) is not built. */
+ * (rl_rn_set_weights); the library never sees a seed.
+ *
+ * The same handle trains LambdaRank after rl_rn_set_lambdarank(h, 1): learn() is RankNet's, and per list the documents
+ * are first re-ranked by the current weights (stable, descending); the pairs of a document are then every j whose label differs, with
+ * target 1 where label_i > label_j and 0 elsewhere, and every pair carries the float weight |swapChange[i][j]| * sign of the train
+ * metric's scorer (NDCG, DCG, MAP or ERR) on the re-ranked list.  Its messages say "LambdaRank".  With this, every ranker of RankLib
+ * trains. */
 typedef struct rl_rn rl_rn;             /* opaque */
 
 typedef struct {
@@ -749,6 +755,10 @@ int  rl_rn_set_external_judgments(rl_rn *h, int32_t validation, const double *id
  * is RL_ERR_INVALID.  Required before the handle learns (without them, or without a training set, learning is RL_ERR_INVALID); a later
  * set_train discards them */
 int  rl_rn_set_weights(rl_rn *h, const double *w, int32_t n);
+/* on != 0: the handle trains LambdaRank (LambdaRank.java) instead of RankNet; 0 switches back.  A null handle is RL_ERR_INVALID, a call
+ * after rl_rn_learn RL_ERR_STATE; on with a train metric other than NDCG, DCG, MAP and ERR (P, RR: their swap changes are not built) is
+ * RL_ERR_UNSUPPORTED.  None of these looks at the device */
+int  rl_rn_set_lambdarank(rl_rn *h, int32_t on);
 int  rl_rn_learn(rl_rn *h);
 /* after learning, in the same layout: the restored best on validation, or the last epoch's.  w may be NULL (only *n is set) */
 int  rl_rn_get_weights(const rl_rn *h, double *w, int32_t cap, int32_t *n);

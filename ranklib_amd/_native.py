@@ -138,6 +138,7 @@ ABI_SYMBOLS = [
     "rl_ln_set_weights", "rl_ln_learn", "rl_ln_get_weights", "rl_ln_scores", "rl_ln_trace", "rl_ln_debug_doc_scores", "rl_ln_debug_times",
     "rl_rn_params_default", "rl_rn_create", "rl_rn_destroy", "rl_rn_set_train", "rl_rn_set_validation", "rl_rn_set_external_judgments",
     "rl_rn_set_weights", "rl_rn_learn", "rl_rn_get_weights", "rl_rn_scores", "rl_rn_trace", "rl_rn_debug_doc_scores", "rl_rn_debug_times",
+    "rl_rn_set_lambdarank",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -262,6 +263,8 @@ def lib():
         L.rl_rn_trace.argtypes = [vp, vp, i64, C.POINTER(i64)]
         L.rl_rn_debug_doc_scores.argtypes = [vp, i32, vp, i64]
         L.rl_rn_debug_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        if hasattr(L, "rl_rn_set_lambdarank"):
+            L.rl_rn_set_lambdarank.argtypes = [vp, i32]
     if hasattr(L, "rl_net_create"):
         L.rl_net_create.argtypes = [i32, vp, i32, vp, i32, vp, i32, C.POINTER(vp)]
         L.rl_net_destroy.argtypes = [vp]
@@ -965,16 +968,29 @@ class ListNetTrainer(_LinearTrainer):
 class RankNetTrainer(ListNetTrainer):
     """Thin object wrapper over the rl_rn handle: RankNet.learn() on one GPU (rl_rn.inc in rl_ca.hip).  hidden_sizes: the hidden layers'
     neuron counts ([] = -layer 0).  The start weights are the caller's (set_weights, NetModel's layout: per layer a row-major
-    [n_l][n_{l-1} + 1], the bias last); weights() returns the same layout.  trace(): RN_TRACE_DTYPE, one record per epoch."""
+    [n_l][n_{l-1} + 1], the bias last); weights() returns the same layout.  trace(): RN_TRACE_DTYPE, one record per epoch.
+    lambdarank=True: the handle trains LambdaRank (rl_rn_set_lambdarank: the lists re-ranked by the current weights, pairs in both
+    directions weighted by the train metric's swap change; NDCG, DCG, MAP or ERR)."""
     _prefix, _name, _trace_dtype = "rl_rn_", "RankNet", RN_TRACE_DTYPE
 
-    def __init__(self, n_epochs=100, learning_rate=0.00005, hidden_sizes=(10,), metric="NDCG", metric_k=10, device=0, err_max=16.0):
+    def __init__(self, n_epochs=100, learning_rate=0.00005, hidden_sizes=(10,), metric="NDCG", metric_k=10, device=0, err_max=16.0,
+                 lambdarank=False):
         if not hasattr(lib(), "rl_rn_create"):
             raise RankLibError("rlhip: this librlhip.so has no RankNet training (rl_rn_*)")
+        if lambdarank and not hasattr(lib(), "rl_rn_set_lambdarank"):
+            raise RankLibError("rlhip: this librlhip.so has no LambdaRank training (rl_rn_set_lambdarank)")
+        if lambdarank:
+            self._name = "LambdaRank"
         self.hidden = [int(v) for v in hidden_sizes]
         hid = np.ascontiguousarray(self.hidden if self.hidden else [0], dtype=np.int32)      # a real pointer for an empty list too
         self._open(RlRnParams, metric, metric_k, device, err_max, n_epochs=int(n_epochs), learning_rate=float(learning_rate),
                    n_hidden=len(self.hidden), hidden_sizes=hid.ctypes.data_as(C.POINTER(C.c_int32)))
+        if lambdarank:
+            try:
+                check(lib().rl_rn_set_lambdarank(self.h, 1))
+            except RankLibError:
+                self.close()
+                raise
 
 
 def _predict_arrays(feature_ids, weights, rows):

@@ -1,20 +1,23 @@
-"""Command line of the `-ranker 6 / 0 / 8 / 4 / 3 / 2 / 9 / 7 / 1` paths: mirrors the flags of eval/Evaluator.java that reach LambdaMART, MART, Random
-Forests, Coordinate Ascent, AdaRank, RankBoost, Linear Regression, ListNet and RankNet (:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
+"""Command line of the `-ranker 6 / 0 / 8 / 4 / 3 / 2 / 9 / 7 / 1 / 5` paths: mirrors the flags of eval/Evaluator.java that reach LambdaMART, MART, Random
+Forests, Coordinate Ascent, AdaRank, RankBoost, Linear Regression, ListNet, RankNet and LambdaRank (:230-377) and the train / test / load / score / rank flows (:669-708, :1076-1094, :1168-1194).
 
     python -m ranklib_amd.evaluator -train f -ranker 6 -metric2t NDCG@10 -tree 1000 -leaf 31 -save model.txt
     python -m ranklib_amd.evaluator -load model.txt -rank f -score out.txt
 
 -load also takes the model files of the neural-net rankers (## RankNet, ## LambdaRank, ## ListNet: learning/neuralnet/) for -test, -rank
--score / -indri, -idv, -norm and -qrel; they are scored on the GPU.  -train with -ranker 5 stays refused, and so do -ranker 7 unless
--netseed n and -ranker 1 unless -rnseed n (rlhip extensions) seed the initial weights, which the Java draws from an unseeded Random:
+-score / -indri, -idv, -norm and -qrel; they are scored on the GPU.  -train stays refused for -ranker 7 unless -netseed n, for -ranker 1
+unless -rnseed n and for -ranker 5 unless -lamseed n (rlhip extensions) seed the initial weights, which the Java draws from an unseeded
+Random:
 
     python -m ranklib_amd.evaluator -train f -ranker 7 -netseed 3 -epoch 200 -metric2t NDCG@10 -validate v -save model.txt
     python -m ranklib_amd.evaluator -train f -ranker 1 -rnseed 3 -epoch 50 -layer 1 -node 10 -lr 0.00005 -validate v -save model.txt
+    python -m ranklib_amd.evaluator -train f -ranker 5 -lamseed 3 -epoch 50 -metric2t NDCG@10 -validate v -save model.txt
 
 With -ranker 7, -epoch n sets ListNet.nIteration, and -lr x, like the Java's (:294-296), sets ListNet.learningRate to Neuron.learningRate
 -- 0.001 -- whatever x is; without -lr the rate is ListNet's default 0.00001.  Both, and the seed, are restored when main returns.
 With -ranker 1 -rnseed n, -epoch, -layer, -node and -lr x set RankNet's nIteration, nHiddenLayer, nHiddenNodePerLayer and learningRate
-(= x, no quirk) for the run; in every other run those flags are parsed and leave RankNet's statics alone.
+(= x, no quirk) for the run, and so they do with -ranker 5 -lamseed n (LambdaRank shares RankNet's statics, as in the Java); in every
+other run those flags are parsed and leave RankNet's statics alone.
 """
 import logging
 import math
@@ -23,7 +26,7 @@ import sys
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
                        stable_desc_order)
 from .metric import ERRScorer, MetricScorerFactory
 
@@ -215,11 +218,13 @@ def main(argv=None):
     if not args:
         print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
-              "(-load also reads RankNet, LambdaRank and ListNet models; LambdaRank is scored, not trained) | "
+              "(-load also reads RankNet, LambdaRank and ListNet models) | "
               "-train <file> -ranker 7 -netseed n [-epoch n] [-lr x] (ListNet; -netseed, an rlhip extension, seeds the initial weights and is required; "
               "-lr x sets the learning rate to 0.001 whatever x is, as the Java does; without it 0.00001) | "
               "-train <file> -ranker 1 -rnseed n [-epoch n] [-layer n] [-node n] [-lr x] (RankNet; -rnseed, an rlhip extension, seeds the initial weights "
-              "and is required; defaults 100 epochs, 1 hidden layer of 10 nodes, learning rate 0.00005; LambdaRank, -ranker 5, is not trained)")
+              "and is required; defaults 100 epochs, 1 hidden layer of 10 nodes, learning rate 0.00005) | "
+              "-train <file> -ranker 5 -lamseed n [-epoch n] [-layer n] [-node n] [-lr x] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] (LambdaRank; -lamseed, an rlhip "
+              "extension, seeds the initial weights and is required; the other flags and defaults are RankNet's)")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
     Evaluator.mustHaveRelDoc = False
@@ -230,7 +235,7 @@ def main(argv=None):
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)
     ttSplit = tvSplit = 0.0
     foldCV, kcvModelDir, kcvModelFile = -1, "", ""
-    epochs = netSeed = rnSeed = layers = nodes = lrValue = None
+    epochs = netSeed = rnSeed = lamSeed = layers = nodes = lrValue = None
     lrGiven = False
     i = 0
     while i < len(args):                                    # :230-372 (flags are matched case-insensitively)
@@ -303,6 +308,7 @@ def main(argv=None):
             lrGiven = True
         elif a == "-netseed": netSeed = int(nxt())          # rlhip extension: seeds ListNet's initial weights (the Java's Random is unseeded)
         elif a == "-rnseed": rnSeed = int(nxt())            # rlhip extension: seeds RankNet's initial weights, likewise
+        elif a == "-lamseed": lamSeed = int(nxt())          # rlhip extension: seeds LambdaRank's initial weights, likewise
         elif a == "-layer": layers = int(nxt())             # :290-293; reach RankNet's statics in a -ranker 1 -rnseed run only (below); every
         elif a == "-node": nodes = int(nxt())               # other run parses and ignores them (test:eval/EvaluatorTest.java:207-220 passes them to every ranker)
         elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = RankNet.device = int(nxt())
@@ -313,12 +319,14 @@ def main(argv=None):
         testMetric = trainMetric                            # :379-381
     listnet = rankerType == 7 and netSeed is not None        # ListNet trains behind a seed only
     ranknet = rankerType == 1 and rnSeed is not None         # RankNet likewise, behind its own
-    if trainFile and rankerType not in _RANKER_TYPES and not listnet and not ranknet:
+    lambdarank = rankerType == 5 and lamSeed is not None     # LambdaRank likewise
+    if trainFile and rankerType not in _RANKER_TYPES and not listnet and not ranknet and not lambdarank:
         raise RankLibError("rlhip builds -ranker 6 (LambdaMART), -ranker 0 (MART), -ranker 8 (Random Forests), -ranker 4 (Coordinate Ascent), "
                            "-ranker 3 (AdaRank), -ranker 2 (RankBoost) and -ranker 9 (Linear Regression) only: the neural-net rankers "
                            "(-ranker 1 RankNet, 5 LambdaRank, 7 ListNet) are out of scope"
                            + ("; ListNet trains only with -netseed n, a seed for its initial weights" if rankerType == 7 else
-                              "; RankNet trains only with -rnseed n, a seed for its initial weights" if rankerType == 1 else ""))
+                              "; RankNet trains only with -rnseed n, a seed for its initial weights" if rankerType == 1 else
+                              "; LambdaRank trains only with -lamseed n, a seed for its initial weights" if rankerType == 5 else ""))
 
     def flows(rtype):                                       # :469-520
         nonlocal kcvModelDir, kcvModelFile
@@ -345,11 +353,15 @@ def main(argv=None):
                 e.test(savedModelFile, testFile, prpFile)
         return 0
 
-    if ranknet:
-        # RankNet's statics belong to this run only, as ListNet's below
-        saved = (RankNet.nIteration, RankNet.nHiddenLayer, RankNet.nHiddenNodePerLayer, RankNet.learningRate, RankNet.seed, Neuron.learningRate)
+    if ranknet or lambdarank:
+        # RankNet's statics (LambdaRank shares them) belong to this run only, as ListNet's below
+        saved = (RankNet.nIteration, RankNet.nHiddenLayer, RankNet.nHiddenNodePerLayer, RankNet.learningRate, RankNet.seed, Neuron.learningRate,
+                 LambdaRank.lamseed)
         try:
-            RankNet.seed = rnSeed
+            if ranknet:
+                RankNet.seed = rnSeed
+            else:
+                LambdaRank.lamseed = lamSeed
             if epochs is not None:
                 RankNet.nIteration = epochs                     # :284-288
             if layers is not None:
@@ -358,9 +370,10 @@ def main(argv=None):
                 RankNet.nHiddenNodePerLayer = nodes             # :292-293
             if lrGiven:
                 RankNet.learningRate = lrValue                  # :295
-            return flows(RankerType.RANKNET)
+            return flows(RankerType.RANKNET if ranknet else RankerType.LAMBDARANK)
         finally:
-            (RankNet.nIteration, RankNet.nHiddenLayer, RankNet.nHiddenNodePerLayer, RankNet.learningRate, RankNet.seed, Neuron.learningRate) = saved
+            (RankNet.nIteration, RankNet.nHiddenLayer, RankNet.nHiddenNodePerLayer, RankNet.learningRate, RankNet.seed, Neuron.learningRate,
+             LambdaRank.lamseed) = saved
     if not listnet:
         return flows(_RANKER_TYPES.get(rankerType, RankerType.LAMBDAMART))
     # ListNet's statics belong to this run only: the refusals and defaults other callers see are the same before and after it

@@ -11,8 +11,8 @@ RankLib's API read the same here:
     AdaRank                      learning/boosting/AdaRank.java:33-346  (learn and eval run on the GPU through librlhip.so)
     LinearRegRank                learning/LinearRegRank.java:23-240     (learn and eval run on the GPU through librlhip.so)
     RankNet / LambdaRank / ListNet   learning/neuralnet/RankNet.java:33-490, LambdaRank.java, ListNet.java:24-236
-                                 (model text in and out, eval on the GPU through librlhip.so; ListNet and RankNet also train
-                                 there, each behind a seed; LambdaRank training is not built)
+                                 (model text in and out, eval on the GPU through librlhip.so; all three also train there, each
+                                 behind a seed of its own)
     RankerType / RankerFactory   learning/RankerType.java, learning/RankerFactory.java:36-118
     RankerTrainer                learning/RankerTrainer.java:23-56
 
@@ -1158,12 +1158,14 @@ class LinearRegRank(_LinearRanker):
 
 
 def _neural_refusal(type_name):
-    """what createRanker, init() and learn() say about LAMBDARANK and (without a seed) RANKNET and LISTNET: they load and score, they do
+    """what createRanker, init() and learn() say about RANKNET, LAMBDARANK and LISTNET without their seed: they load and score, they do
     not train"""
     return ("rlhip builds -ranker 6 (LambdaMART), 0 (MART), 8 (Random Forests), 4 (Coordinate Ascent), 3 (AdaRank), 2 (RankBoost) and "
             "9 (Linear Regression); %s, one of the neural-net rankers, is out of scope (SURVEY.md 8)%s"
             % (type_name, "; ListNet trains only with a seed for its initial weights (-netseed n / ListNet.seed)" if type_name == "LISTNET" else
-               "; RankNet trains only with a seed for its initial weights (-rnseed n / RankNet.seed)" if type_name == "RANKNET" else ""))
+               "; RankNet trains only with a seed for its initial weights (-rnseed n / RankNet.seed)" if type_name == "RANKNET" else
+               "; LambdaRank trains only with a seed for its initial weights (-lamseed n / LambdaRank.lamseed)" if type_name == "LAMBDARANK"
+               else ""))
 
 
 class JavaRandom:
@@ -1225,7 +1227,7 @@ class RankNet(Ranker):
     document from its pairs, bit for bit the Java's doubles: DESIGN.md 16) -- but only with RankNet.seed set (-rnseed n, an rlhip
     extension): the Java draws the initial weights from an unseeded static Random (Synapse.java:18,29).  Here every init() draws them from
     a fresh java.util.Random(seed), two draws per synapse in wire()'s creation order.  With seed = None both stay refused.  LambdaRank, a
-    subclass, is refused whatever the seed; ListNet, another, looks at its own seed only."""
+    subclass, looks at LambdaRank.lamseed only; ListNet, another, at its own seed only."""
     # process-global parameters, like the Java statics (:37-40)
     nIteration = 100
     nHiddenLayer = 1
@@ -1235,6 +1237,8 @@ class RankNet(Ranker):
     seed = None                       # rlhip extension (-rnseed): None = training refused
     _TYPE = "RANKNET"
     _LOAD = "RankNet"                 # the class whose loadFromString runs: LambdaRank inherits RankNet's, ListNet has its own copy
+    _LAMBDARANK = False               # the trainer's form: rl_rn_set_lambdarank
+    _METRICS = ("NDCG", "DCG", "MAP", "ERR", "P", "RR")
 
     def __init__(self, samples=None, features=None, scorer=None):
         super().__init__(samples, features, scorer)
@@ -1269,22 +1273,25 @@ class RankNet(Ranker):
         return w
 
     def _trains(self):
-        """RankNet itself, and only behind RankNet.seed: LambdaRank inherits the attribute and stays refused"""
+        """RankNet itself, and only behind RankNet.seed: LambdaRank inherits the attribute and does not look at it"""
         return self._TYPE == "RANKNET" and RankNet.seed is not None
+
+    def _seed(self):
+        return RankNet.seed
 
     def init(self):                   # :257-287
         if not self._trains():
             raise RankLibError(_neural_refusal(self._TYPE))
         logger.info("Initializing... ")
         metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
-        if metric not in N.RL_CA_METRIC:
-            raise RankLibError("rlhip: the %s train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
-                               % (self.name(), self.scorer.name() if self.scorer else None))
+        if metric not in N.RL_CA_METRIC or metric not in self._METRICS:
+            raise RankLibError("rlhip: the %s train metric must be one of %s (got %s)"
+                               % (self.name(), ", ".join(self._METRICS), self.scorer.name() if self.scorer else None))
         hidden = [int(RankNet.nHiddenNodePerLayer)] * int(RankNet.nHiddenLayer)
-        start = self.initial_weights(RankNet.seed, [len(self.features)] + hidden + [1])
+        start = self.initial_weights(self._seed(), [len(self.features)] + hidden + [1])
         Neuron.learningRate = RankNet.learningRate          # :286
         t = N.RankNetTrainer(n_epochs=RankNet.nIteration, learning_rate=Neuron.learningRate, hidden_sizes=hidden, metric=metric,
-                             metric_k=self.scorer.getK(), device=RankNet.device, err_max=ERRScorer.MAX)
+                             metric_k=self.scorer.getK(), device=RankNet.device, err_max=ERRScorer.MAX, lambdarank=self._LAMBDARANK)
         _feed_linear_trainer(self, t, metric)
         t.set_weights(np.concatenate([m.ravel() for m in start]))
         self.hidden, self.weights, self._net = hidden, start, None
@@ -1442,9 +1449,23 @@ class RankNet(Ranker):
 
 
 class LambdaRank(RankNet):
-    """learning/neuralnet/LambdaRank.java: RankNet's network, model text and eval; only training differs, and that is not built:
-    init() and learn() refuse whatever RankNet.seed is (RankNet._trains)."""
+    """learning/neuralnet/LambdaRank.java: RankNet's network, model text and eval, and RankNet's init() and learn() with four overrides
+    on the device (librlhip.so rl_rn_set_lambdarank: every list re-ranked by the current weights, pairs in both directions, each weighted
+    by the train metric's swap change, bit for bit the Java's doubles: DESIGN.md 17).  It trains only with LambdaRank.lamseed set
+    (-lamseed n, an rlhip extension): the initial weights come from a fresh java.util.Random(lamseed) in wire() order, and the other
+    statics (nIteration, nHiddenLayer, nHiddenNodePerLayer, learningRate) are RankNet's, shared as in the Java.  The attribute cannot be
+    called `seed`: LambdaRank.seed is RankNet's, inherited, and opens nothing here.  The train metric is one of NDCG, DCG, MAP, ERR (the
+    scorers whose swapChange is built)."""
+    lamseed = None                    # rlhip extension (-lamseed): None = training refused
     _TYPE = "LAMBDARANK"
+    _LAMBDARANK = True
+    _METRICS = ("NDCG", "DCG", "MAP", "ERR")      # metric.TRAINABLE
+
+    def _trains(self):
+        return LambdaRank.lamseed is not None
+
+    def _seed(self):
+        return LambdaRank.lamseed
 
     def name(self):                   # :136-138
         return "LambdaRank"
@@ -1586,6 +1607,8 @@ class RankerFactory:                  # learning/RankerFactory.java:36-118
             r = ListNet()
         elif rtype.name == "RANKNET" and RankNet.seed is not None:    # likewise
             r = RankNet()
+        elif rtype.name == "LAMBDARANK" and LambdaRank.lamseed is not None:      # likewise
+            r = LambdaRank()
         elif rtype.name not in self.map:
             raise RankLibError(_neural_refusal(rtype.name))
         else:

@@ -4,6 +4,7 @@ with the upload.
     python tools/rn_bench.py --shape small                # ~800 lists x ~20 documents x 46 features (LETOR 4.0-like), hidden [10]
     python tools/rn_bench.py --shape c2 --epochs 1        # ranklib_amd.synth c2 (3.77 M x 136)
     python tools/rn_bench.py --shape c2 --skip 0,1,2,4    # k_rn_epoch whole, then without its forward pass / deltas / update
+    python tools/rn_bench.py --shape small --lambdarank   # LambdaRank (-ranker 5): k_lrk_epoch, DESIGN.md 17
 
 One JSON line per run.  epoch_ms is k_rn_epoch between two device events, per epoch; score_ms is k_rn_score + k_rn_misordered + k_ca_trials
 on the training set after an epoch (a host clock around work that ends in a stream synchronisation), per epoch; wall_s is set_train +
@@ -11,7 +12,9 @@ learn, the host's column-major copy and the upload included.  floor_ms is the mo
 dependent f64 add: a step with P pairs walks the delta_i chain (P adds) and then, in every round of the update a thread
 takes (ceil(weights / 1024)), a sum_j chain of P adds, so an epoch cannot take less than 5.5 ns * total pairs * (1 + rounds).
 ratio = epoch_ms / floor_ms.  --skip runs a variant of the kernel that leaves one phase out (RLHIP_RN_SKIP, a measuring aid: its weights
-mean nothing): the difference to the whole kernel is what that phase costs.
+mean nothing): the difference to the whole kernel is what that phase costs.  With --lambdarank a step's pairs are every document whose
+label differs, in both directions, so the model's pair count is twice total_pairs (pairs in the JSON line); --skip 2 does not exist there
+(without the deltas the update would read values nobody wrote: the library runs the whole kernel).
 """
 import argparse
 import json
@@ -52,12 +55,12 @@ def floor_ms(pairs, nw):
     return float(ADD_NS * pairs * (1 + -(-nw // THREADS)) * 1e-6)
 
 
-def run(X, lab, qoff, metric, k, epochs, lr, seed, skip, hidden):
+def run(X, lab, qoff, metric, k, epochs, lr, seed, skip, hidden, lambdarank=False):
     if skip:
         os.environ["RLHIP_RN_SKIP"] = str(skip)
     else:
         os.environ.pop("RLHIP_RN_SKIP", None)
-    t = N.RankNetTrainer(n_epochs=epochs, learning_rate=lr, hidden_sizes=hidden, metric=metric, metric_k=k)
+    t = N.RankNetTrainer(n_epochs=epochs, learning_rate=lr, hidden_sizes=hidden, metric=metric, metric_k=k, lambdarank=lambdarank)
     t0 = time.perf_counter()
     t.set_train(X, lab, qoff)
     t.set_weights(np.concatenate([m.ravel() for m in RankNet.initial_weights(seed, [X.shape[1]] + list(hidden) + [1])]))
@@ -68,10 +71,10 @@ def run(X, lab, qoff, metric, k, epochs, lr, seed, skip, hidden):
     w = t.weights()
     tr = t.trace()
     t.close()
-    pairs = int(tr["total_pairs"][0]) if len(tr) else total_pairs(lab, qoff)
+    pairs = (int(tr["total_pairs"][0]) if len(tr) else total_pairs(lab, qoff)) * (2 if lambdarank else 1)
     fl = floor_ms(pairs, len(w))
     per = tm["epoch_ms"] / max(1, epochs)
-    return dict(skip=skip, epochs=epochs, hidden=list(hidden), n_weights=len(w), total_pairs=pairs, epoch_ms=round(per, 4),
+    return dict(ranker="LambdaRank" if lambdarank else "RankNet", skip=skip, epochs=epochs, hidden=list(hidden), n_weights=len(w), total_pairs=pairs, epoch_ms=round(per, 4),
                 floor_ms=round(fl, 4), ratio=round(per / fl, 3) if fl else None, score_ms=round(tm["score_ms"] / max(1, epochs), 3),
                 wall_s=round(wall, 4), max_abs_weight=float(np.max(np.abs(w))), train_score=ts,
                 misordered=[int(v) for v in tr["misordered"]])
@@ -88,6 +91,7 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--skip", default="0", help="comma-separated variants to run: 0 (the whole kernel), 1 (no forward pass), 2 (no deltas), 4 (no update)")
     ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--lambdarank", action="store_true", help="train LambdaRank (k_lrk_epoch) instead of RankNet")
     a = ap.parse_args()
     if a.shape == "small":
         X, lab, qoff = small_shape()
@@ -100,10 +104,10 @@ def main():
                 metric="%s@%d" % (a.metric, a.k), lr=a.lr)
     try:
         e = min(8, len(qoff) - 1)
-        run(X[:qoff[e]], lab[:qoff[e]], qoff[:e + 1], a.metric, a.k, 1, a.lr, a.seed, 0, hidden)      # warm-up
+        run(X[:qoff[e]], lab[:qoff[e]], qoff[:e + 1], a.metric, a.k, 1, a.lr, a.seed, 0, hidden, a.lambdarank)      # warm-up
         for skip in [int(v) for v in a.skip.split(",")]:
             for _ in range(a.repeat):
-                print(json.dumps(dict(head, **run(X, lab, qoff, a.metric, a.k, a.epochs, a.lr, a.seed, skip, hidden))), flush=True)
+                print(json.dumps(dict(head, **run(X, lab, qoff, a.metric, a.k, a.epochs, a.lr, a.seed, skip, hidden, a.lambdarank))), flush=True)
     except N.RankLibError as ex:
         print(json.dumps(dict(head, refused=str(ex))))
         return 1
