@@ -770,6 +770,27 @@ int  rl_rn_debug_doc_scores(const rl_rn *h, int32_t validation, double *out, int
 /* debug: ms of all epoch kernels together (device events) and of scoring, ranking and pair counting after every epoch (host clock) */
 int  rl_rn_debug_times(const rl_rn *h, double *epoch_ms, double *score_ms);
 
+/* ---- the Analyzer's Fisher randomisation test (stats/RandomPermutationTest.java:23-53) ------------------------------
+ * base [n] and targets [n_targets][n] hold the per-ranked-list performances in the iteration order of the baseline's HashMap, the
+ * "all" entry included.  Permutations perm_begin .. perm_begin + perm_count - 1 of every target are evaluated on the device, one lane
+ * each: permutation p draws its n / 10 + 1 ten-bit chunks from java.util.Random(seed)'s nextDouble draws [p D, (p + 1) D), D = n / 10 + 1
+ * (the Java's Random is unseeded: the seed is this library's extension); where a bit is 1, b[j] and t[j] swap places; the two means are
+ * serial f64 sums from 0.0 in array order and one IEEE division by n; pDiff = |mean(pb) - mean(pt)|.
+ * out_count[k]: permutations of target k with pDiff >= trueDiff (a NaN on either side never counts).  out_true_diff[k] =
+ * |mean(base) - mean(target k)|, computed on the host by the same literal loop.  out_pdiff: NULL, or every pDiff, [n_targets][perm_count].
+ * perm_begin splits a large run over several calls: the counts of the pieces add up to the whole run's.
+ * RL_ERR_INVALID: a null pointer, n < 1, n_targets < 1 or > 65535, perm_count < 1 or > 2^31 - 1, perm_begin < 0, or
+ * (perm_begin + perm_count) * 2 * (n / 10 + 1) LCG steps not below 2^63.  RL_ERR_NO_DEVICE without a gfx950 device: there is no CPU
+ * fallback. */
+int  rl_perm_test(int device, const double *base, const double *targets, int n, int n_targets, int64_t seed, int64_t perm_begin,
+                  int64_t perm_count, int64_t *out_count, double *out_true_diff, double *out_pdiff);
+/* debug (tools/perm_bench.py): add_ns = ns per f64 add of one dependent chain on the device (one wavefront; chain_adds and 2 * chain_adds
+ * adds between device events, the difference); with base and target not NULL also host_ms / host_count: the time and the count of the
+ * Java's loop as written (digit strings, copies into pb / pt) over permutations 0 .. perm_count - 1 on one host thread, the tool's
+ * yardstick.  The host part runs first and needs no device. */
+int  rl_debug_perm_calib(int device, const double *base, const double *target, int n, int64_t seed, int64_t perm_count, int64_t chain_adds,
+                         double *add_ns, double *host_ms, int64_t *host_count);
+
 #ifdef __cplusplus
 }
 #endif

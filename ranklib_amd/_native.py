@@ -139,6 +139,7 @@ ABI_SYMBOLS = [
     "rl_rn_params_default", "rl_rn_create", "rl_rn_destroy", "rl_rn_set_train", "rl_rn_set_validation", "rl_rn_set_external_judgments",
     "rl_rn_set_weights", "rl_rn_learn", "rl_rn_get_weights", "rl_rn_scores", "rl_rn_trace", "rl_rn_debug_doc_scores", "rl_rn_debug_times",
     "rl_rn_set_lambdarank",
+    "rl_perm_test", "rl_debug_perm_calib",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -272,6 +273,10 @@ def lib():
         L.rl_net_predict.argtypes = [vp, vp, i64, i32, vp]
         L.rl_net_predict_device.argtypes = [vp, vp, i64, i32, vp, vp]
         L.rl_net_debug_path.argtypes = [vp, C.POINTER(i32)]
+    if hasattr(L, "rl_perm_test"):      # (A/B builds of older sources lack the Analyzer's test)
+        L.rl_perm_test.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, i64, i64, i64, vp, vp, vp]
+        L.rl_debug_perm_calib.argtypes = [C.c_int, vp, vp, C.c_int, i64, i64, i64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(i64)]
     _lib = L
     return L
 
@@ -1027,3 +1032,32 @@ def lr_predict(feature_ids, weights, rows, device=0):
     check(L.rl_lr_predict(int(device), keep.ctypes.data, fid.size, w.ctypes.data, len(w), rows.ctypes.data, rows.shape[0], rows.shape[1],
                           out.ctypes.data))
     return out
+
+
+def perm_test(base, targets, seed, perm_begin=0, perm_count=10000, want_pdiff=False, device=0):
+    """rl_perm_test (rl_perm.inc): the Analyzer's randomisation test on the GPU.  base [n], targets [n_targets][n] in the baseline
+    HashMap's iteration order; returns (int64 counts [n_targets], f64 trueDiff [n_targets], f64 pDiff [n_targets][perm_count] or None)"""
+    L = lib()
+    if not hasattr(L, "rl_perm_test"):
+        raise RankLibError("rlhip: this librlhip.so has no randomisation test (rl_perm_test)")
+    b = np.ascontiguousarray(base, dtype=np.float64)
+    t = np.ascontiguousarray(targets, dtype=np.float64)
+    if b.ndim != 1 or t.ndim != 2 or t.shape[1] != b.shape[0]:
+        raise RankLibError("rlhip: perm_test takes base [n] and targets [n_targets][n]")
+    n, nt = int(b.shape[0]), int(t.shape[0])
+    count, td = np.zeros(max(1, nt), np.int64), np.zeros(max(1, nt), np.float64)
+    pd = np.zeros((nt, int(perm_count)), np.float64) if want_pdiff and nt >= 1 and n >= 1 and 1 <= perm_count <= 2 ** 31 - 1 else None
+    check(L.rl_perm_test(int(device), b.ctypes.data, t.ctypes.data, n, nt, int(seed), int(perm_begin), int(perm_count),
+                         count.ctypes.data, td.ctypes.data, None if pd is None else pd.ctypes.data))
+    return count[:nt], td[:nt], pd
+
+
+def perm_calib(chain_adds=1 << 22, base=None, target=None, seed=0, perm_count=1, device=0):
+    """rl_debug_perm_calib: (ns per dependent f64 add on the device, ms of the Java's loop as written on one host thread, its count)"""
+    ns, ms, cnt = C.c_double(0), C.c_double(0), C.c_int64(0)
+    b = None if base is None else np.ascontiguousarray(base, dtype=np.float64)
+    t = None if target is None else np.ascontiguousarray(target, dtype=np.float64)
+    check(lib().rl_debug_perm_calib(int(device), None if b is None else b.ctypes.data, None if t is None else t.ctypes.data,
+                                    0 if b is None else len(b), int(seed), int(perm_count), int(chain_adds), C.byref(ns), C.byref(ms),
+                                    C.byref(cnt)))
+    return ns.value, ms.value, cnt.value

@@ -527,3 +527,4 @@ int rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weig
 #include "rl_net.inc"      // RankNet / LambdaRank / ListNet models (-ranker 1 / 5 / 7): the forward pass, scoring only
 #include "rl_ln.inc"       // ListNet training (-ranker 7): k_ln_epoch walks the context's training lists, k_ca_trials ranks
 #include "rl_rn.inc"       // RankNet training (-ranker 1): k_rn_epoch walks the lists and their documents, net_layer scores, k_ca_trials ranks
+#include "rl_perm.inc"     // the Analyzer's randomisation test: k_perm_test draws its sign vectors from this unit's JavaRandom stream
