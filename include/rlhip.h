@@ -791,6 +791,31 @@ int  rl_perm_test(int device, const double *base, const double *targets, int n, 
 int  rl_debug_perm_calib(int device, const double *base, const double *target, int n, int64_t seed, int64_t perm_count, int64_t chain_adds,
                          double *add_ns, double *host_ms, int64_t *host_count);
 
+/* ---- test-time evaluation: rank and score every list of a file in one pass (eval/Evaluator.java:915-944) --------------
+ * scores [n_docs] (f64) and labels [n_docs] hold the documents of n_lists ranked lists, list q at qoff[q] .. qoff[q + 1] - 1.  Every list is
+ * ranked stable and descending by score (MergeSorter.sort(double[], false): -0.0 ties with 0.0, +-Infinity are ordinary values) and its
+ * metric is taken on the device as the Java scorer's serial f64 chain over the ranked labels, bit for bit:
+ * RL_METRIC_NDCG / DCG / MAP / ERR / P / RR and RL_METRIC_BEST (Best@k, reporting only: no trainer accepts it).  k is the scorer's k (MAP
+ * ignores it; plain RR has k = 0 and scores 0, as written), err_max is ERRScorer.MAX.
+ * qkey, ideal_dcg, rel_doc_count: NULL, or [n_lists] with the meaning they have in the trainers' external judgments: for NDCG a list
+ * whose ideal_dcg entry is not NaN is scored against it, and otherwise the FIRST list with its qkey decides the ideal DCG of every later
+ * list with the same key (NDCGScorer's idealGains cache; without qkey every list is its own key); for MAP rel_doc_count replaces the
+ * list's own count of relevant documents.
+ * out_metric [n_lists]: the value of every list; their mean is the caller's (the Java adds them serially in list order).  out_pos: NULL,
+ * or [n_docs], the 0-based position of every document in its list's ranking.  out_ideal: NULL, or [n_lists], the ideal DCG every list was
+ * scored against (NaN for the other metrics).
+ * Checked on the host before any device call -- RL_ERR_INVALID: a null scores / labels / qoff / out_metric, n_lists or n_docs < 1, qoff
+ * not starting at 0, not ending at n_docs or not strictly increasing, an unknown metric, a negative label, a negative rel_doc_count, a NaN
+ * score (the message names the list: the counting rank is undefined on NaN, rank such a list on the host); RL_ERR_UNSUPPORTED: a label of
+ * 2^24 or more.  RL_ERR_NO_DEVICE without a gfx950 device: there is no CPU fallback. */
+enum { RL_METRIC_BEST = 6 };
+int  rl_eval_lists(int32_t device, int32_t metric, int32_t k, double err_max, const double *scores, const float *labels, int64_t n_docs,
+                   const int32_t *qoff, int32_t n_lists, const int32_t *qkey, const double *ideal_dcg, const int32_t *rel_doc_count,
+                   double *out_metric, int32_t *out_pos, double *out_ideal);
+/* debug (tools/eval_bench.py): ms between two device events around the kernel launches of this thread's last rl_eval_lists call (the
+ * uploads before them and the copies back after them are not in it) */
+int  rl_debug_eval_times(double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ class RlParams(C.Structure):
 
 RL_METRIC = dict(NDCG=0, DCG=1, MAP=2, ERR=3)
 RL_CA_METRIC = dict(RL_METRIC, P=4, RR=5)      # Coordinate Ascent also trains on P@k and RR@k
+RL_EVAL_METRIC = dict(RL_CA_METRIC, BEST=6)    # eval_lists scores all seven; no trainer accepts BEST
 
 
 class RlCaParams(C.Structure):
@@ -140,6 +141,7 @@ ABI_SYMBOLS = [
     "rl_rn_set_weights", "rl_rn_learn", "rl_rn_get_weights", "rl_rn_scores", "rl_rn_trace", "rl_rn_debug_doc_scores", "rl_rn_debug_times",
     "rl_rn_set_lambdarank",
     "rl_perm_test", "rl_debug_perm_calib",
+    "rl_eval_lists", "rl_debug_eval_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -277,6 +279,9 @@ def lib():
         L.rl_perm_test.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, i64, i64, i64, vp, vp, vp]
         L.rl_debug_perm_calib.argtypes = [C.c_int, vp, vp, C.c_int, i64, i64, i64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(i64)]
+    if hasattr(L, "rl_eval_lists"):     # (A/B builds of older sources rank and score on the host)
+        L.rl_eval_lists.argtypes = [i32, i32, i32, C.c_double, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.rl_debug_eval_times.argtypes = [C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -1061,3 +1066,43 @@ def perm_calib(chain_adds=1 << 22, base=None, target=None, seed=0, perm_count=1,
                                     0 if b is None else len(b), int(seed), int(perm_count), int(chain_adds), C.byref(ns), C.byref(ms),
                                     C.byref(cnt)))
     return ns.value, ms.value, cnt.value
+
+
+def eval_lists(scores, labels, qoff, metric, k, err_max=16.0, qkey=None, ideal_dcg=None, rel_doc_count=None, want_pos=False, device=0):
+    """rl_eval_lists (rl_eval.inc): every list ranked stable and descending by its scores and scored by the metric, on the GPU.  scores
+    [n_docs] f64, labels [n_docs], qoff [n_lists + 1]; metric: a name of RL_EVAL_METRIC.  Returns (f64 metric per list, int32 0-based
+    position of every document in its list's ranking or None, f64 ideal DCG per list -- NaN unless the metric is NDCG)"""
+    L = lib()
+    if not hasattr(L, "rl_eval_lists"):
+        raise RankLibError("rlhip: this librlhip.so has no test-time evaluation (rl_eval_lists)")
+    m = str(metric).upper()
+    if m not in RL_EVAL_METRIC:
+        raise RankLibError("rlhip: eval_lists metric must be one of NDCG, DCG, MAP, ERR, P, RR, BEST (got %s)" % metric)
+    sc = np.ascontiguousarray(scores, dtype=np.float64)
+    lab = np.ascontiguousarray(labels, dtype=np.float32)
+    qo = np.ascontiguousarray(qoff, dtype=np.int32)
+    if sc.ndim != 1 or lab.shape != sc.shape or qo.ndim != 1 or qo.size < 1:
+        raise RankLibError("rlhip: eval_lists takes scores [n_docs], labels [n_docs] and qoff [n_lists + 1]")
+    nl = int(qo.size) - 1
+
+    def per_list(a, dtype, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != (nl,):
+            raise RankLibError("rlhip: eval_lists takes %s [n_lists]" % what)
+        return a
+    qk, idl, rdc = per_list(qkey, np.int32, "qkey"), per_list(ideal_dcg, np.float64, "ideal_dcg"), per_list(rel_doc_count, np.int32, "rel_doc_count")
+    out, ideal = np.zeros(max(1, nl), np.float64), np.zeros(max(1, nl), np.float64)
+    pos = np.zeros(max(1, sc.size), np.int32) if want_pos else None
+    ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+    check(L.rl_eval_lists(int(device), RL_EVAL_METRIC[m], int(k), float(err_max), sc.ctypes.data, lab.ctypes.data, int(sc.size), qo.ctypes.data,
+                          nl, ptr(qk), ptr(idl), ptr(rdc), out.ctypes.data, ptr(pos), ideal.ctypes.data))
+    return out[:nl], None if pos is None else pos[:sc.size], ideal[:nl]
+
+
+def eval_kernel_ms():
+    """rl_debug_eval_times: ms of the kernels of this thread's last eval_lists call, between device events"""
+    ms = C.c_double(0)
+    check(lib().rl_debug_eval_times(C.byref(ms)))
+    return ms.value

@@ -23,12 +23,14 @@ import logging
 import math
 import sys
 
+import numpy as np
+
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
 from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
                        stable_desc_order)
-from .metric import ERRScorer, MetricScorerFactory
+from .metric import DCGScorer, ERRScorer, MetricScorerFactory, score_lists
 
 logger = logging.getLogger("ranklib_amd")
 
@@ -38,6 +40,8 @@ class Evaluator:
     normalize = False                 # eval/Evaluator.java:553-554, set by -norm
     nml = normalizer.SumNormalizor()
     qrelFile = ""                     # :557, set by -qrel: TREC-style judgments, they only affect MAP and NDCG
+    batch = True                      # rlhip: the test-time flows score, rank and evaluate a whole file in one GPU pass (Ranker.evalLists +
+                                      # metric.score_lists); False: list by list on the host, the same output byte for byte
 
     def __init__(self, rType, trainMetric, testMetric):
         self.type = rType
@@ -67,12 +71,23 @@ class Evaluator:
             ranker = trainer.train(self.type, train, features, self.trainScorer)
         trainer.printTrainingTime()
         if test is not None:
-            s = self.testScorer.score(ranker.rank(test))
+            s = self._score_test(ranker, test)
             logger.info("%s on test data: %s", self.testScorer.name(), java_round(s, 4))
         if modelFile:
             ranker.save(modelFile)
             logger.info("Model saved to: %s", modelFile)
         return ranker
+
+    def _score_test(self, ranker, test):
+        """testScorer.score(ranker.rank(test)): the mean of the lists' values, a serial f64 sum in list order and one division"""
+        if not Evaluator.batch:
+            return self.testScorer.score(ranker.rank(test))
+        flat, _ = ranker.evalLists(test)
+        per, _ = score_lists(self.testScorer, test, flat)
+        s = 0.0
+        for v in per:
+            s += float(v)
+        return s / len(test)
 
     def _features(self, featureDefFile, samples):
         return FeatureManager.readFeature(featureDefFile) if featureDefFile else FeatureManager.getFeatureFromSampleVector(samples)
@@ -96,7 +111,7 @@ class Evaluator:
         if validation is not None and Evaluator.normalize:   # :723-727
             self.normalizeLists(validation, features)
         ranker = self._train(train, validation, features)
-        s = self.testScorer.score(ranker.rank(test))
+        s = self._score_test(ranker, test)
         logger.info("%s on test data: %s", self.testScorer.name(), java_round(s, 4))
         if modelFile:
             ranker.save(modelFile)
@@ -115,7 +130,7 @@ class Evaluator:
         ranker = self._train(train, validation, features)
         s = None
         if test is not None:
-            s = self.testScorer.score(ranker.rank(test))
+            s = self._score_test(ranker, test)
             logger.info("%s on test data: %s", self.testScorer.name(), java_round(s, 4))
         if modelFile:
             ranker.save(modelFile)
@@ -136,7 +151,7 @@ class Evaluator:
         scores, scoreOnTrain, scoreOnTest, totalScoreOnTest, totalTestSampleSize = [], 0.0, 0.0, 0.0, 0
         for i in range(nFold):
             ranker = self._train(trainingData[i], validationData[i] if tvs > 0 else None, features)
-            s2 = self.testScorer.score(ranker.rank(testData[i]))
+            s2 = self._score_test(ranker, testData[i])
             scoreOnTrain += ranker.getScoreOnTrainingData()
             scoreOnTest += s2
             totalScoreOnTest += s2 * len(testData[i])
@@ -161,6 +176,12 @@ class Evaluator:
         if Evaluator.normalize:                              # :1080-1082
             self.normalizeLists(test, ranker.getFeatures())
         with open(outputFile, "w", encoding="utf-8") as out:
+            if Evaluator.batch:
+                flat, qoff = ranker.evalLists(test)
+                for q, rl in enumerate(test):
+                    for j, v in enumerate(flat[int(qoff[q]):int(qoff[q + 1])]):
+                        out.write("%s\t%d\t%s\n" % (rl.getID(), j, java_double_str(float(v))))
+                return
             for rl in test:
                 for j, v in enumerate(ranker.evalList(rl)):
                     out.write("%s\t%d\t%s\n" % (rl.getID(), j, java_double_str(float(v))))
@@ -171,6 +192,17 @@ class Evaluator:
         if Evaluator.normalize:                              # :1173-1175
             self.normalizeLists(test, ranker.getFeatures())
         with open(indriFile, "w", encoding="utf-8") as out:
+            if Evaluator.batch:
+                flat, qoff = ranker.evalLists(test)
+                _, pos = score_lists(DCGScorer(1), test, flat, want_pos=True)      # any metric would do: the positions are what is read
+                for q, rl in enumerate(test):
+                    a, b = int(qoff[q]), int(qoff[q + 1])
+                    order = np.empty(b - a, np.int64)
+                    order[pos[a:b]] = np.arange(b - a)
+                    for i, j in enumerate(order):
+                        docno = rl.get(int(j)).getDescription().replace("#", "").strip()
+                        out.write("%s Q0 %s %d %s indri\n" % (rl.getID(), docno, i + 1, java_double_str(java_round(float(flat[a + int(j)]), 5))))
+                return
             for rl in test:
                 sc = ranker.evalList(rl)
                 for i, j in enumerate(stable_desc_order(sc)):
@@ -183,11 +215,18 @@ class Evaluator:
         if Evaluator.normalize:                              # :919-921
             self.normalizeLists(test, ranker.getFeatures())
         ids, scores, rankScore = [], [], 0.0
-        for rl in test:
-            l = ranker.rank(rl)
-            sc = self.testScorer.score(l)
-            ids.append(l.getID()); scores.append(sc)
-            rankScore += sc
+        if Evaluator.batch:
+            flat, _ = ranker.evalLists(test)
+            per, _ = score_lists(self.testScorer, test, flat)
+            for rl, v in zip(test, per):
+                ids.append(rl.getID()); scores.append(float(v))
+                rankScore += float(v)
+        else:
+            for rl in test:
+                l = ranker.rank(rl)
+                sc = self.testScorer.score(l)
+                ids.append(l.getID()); scores.append(sc)
+                rankScore += sc
         rankScore /= len(test)
         ids.append("all"); scores.append(rankScore)
         logger.info("%s on test data: %s", self.testScorer.name(), java_round(rankScore, 4))
@@ -230,6 +269,7 @@ def main(argv=None):
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False                             # :86
     Evaluator.qrelFile = ""
+    Evaluator.batch = True
     LambdaMART.fastLeaf = False                             # -fastleaf (rlhip extension)
     rankerType = 4                                          # the reference's default is Coordinate Ascent (:83)
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)

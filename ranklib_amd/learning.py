@@ -210,6 +210,31 @@ class Ranker:
     def evalList(self, rl):
         return [self.eval(dp) for dp in rl.rl]
 
+    EVAL_ROW_BYTES = 1 << 30          # evalLists: bytes of f32 rows one scoring call is given at most (whole lists; one list may exceed it)
+
+    def evalLists(self, samples):
+        """The scores of every document of every list, list after list: (f64 [n_docs], int64 qoff [len(samples) + 1]).  The documents
+        go through _evalDocs in chunks of whole lists whose rows stay under EVAL_ROW_BYTES."""
+        qoff = np.zeros(len(samples) + 1, np.int64)
+        np.cumsum([rl.size() for rl in samples], out=qoff[1:])
+        out = np.zeros(int(qoff[-1]), np.float64)
+        a = 0
+        while a < len(samples):
+            b, docs, width = a, 0, 1
+            while b < len(samples):
+                w = max(width, samples[b].getFeatureCount() + 1)
+                if b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
+                    break
+                docs, width, b = docs + samples[b].size(), w, b + 1
+            if docs:
+                out[int(qoff[a]):int(qoff[b])] = self._evalDocs([dp for rl in samples[a:b] for dp in rl.rl])
+            a = b
+        return out, qoff
+
+    def _evalDocs(self, dps):
+        """f64 scores of the documents dps; a ranker family overrides it with one call of its scoring kernel"""
+        return np.array([self.eval(dp) for dp in dps], np.float64)
+
     def save(self, modelFile):        # :106-122
         d = modelFile.rsplit("/", 1)[0] if "/" in modelFile else None
         if d:
@@ -381,6 +406,9 @@ class LambdaMART(Ranker):
 
     def evalList(self, rl):
         return [float(v) for v in self._model.predict_rows(self._rows(rl.rl))]
+
+    def _evalDocs(self, dps):
+        return self._model.predict_rows(self._rows(dps)).astype(np.float64)
 
     def createNew(self):
         return LambdaMART()
@@ -577,6 +605,13 @@ class RFRanker(Ranker):
             s += m.predict_rows(rows).astype(np.float64)
         return [float(v) for v in s / len(self._models)]
 
+    def _evalDocs(self, dps):         # the same per-bag (float) -> f64 sum and / nBag, every document of the chunk at once
+        rows = self._rows(dps)
+        s = np.zeros(len(rows), np.float64)
+        for m in self._models:
+            s += m.predict_rows(rows).astype(np.float64)
+        return s / len(self._models)
+
     def eval(self, dp):               # noqa: A003
         return self.evalList(RankList([dp]))[0]
 
@@ -737,6 +772,9 @@ class _LinearRanker(Ranker):
         if rl.size() == 0:
             return []
         return [float(v) for v in self._predict(rl.rl)]
+
+    def _evalDocs(self, dps):
+        return np.asarray(self._predict(dps), np.float64)
 
     def eval(self, dp):               # noqa: A003  the Java's eval(DataPoint): the same f64 sum, one row
         return self.evalList(RankList([dp]))[0]
@@ -1366,6 +1404,9 @@ class RankNet(Ranker):
             return []
         net = self._model()
         return [float(v) for v in net.predict_rows(_linear_rows(rl.rl, self.features))]
+
+    def _evalDocs(self, dps):
+        return self._model().predict_rows(_linear_rows(dps, self.features))
 
     def eval(self, dp):               # noqa: A003  :336-349
         return self.evalList(RankList([dp]))[0]

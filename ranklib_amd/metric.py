@@ -1,11 +1,13 @@
 """Host-side metric objects: what `-metric2t` / `-metric2T` parse to and what Evaluator uses to report a ranked test
 list.  Mirrors metric/MetricScorer.java, metric/{NDCG,DCG,AP,ERR,Precision,ReciprocalRank,BestAtK}Scorer.java and
 metric/MetricScorerFactory.java.  The per-round training / validation metric (NDCG, DCG, MAP or ERR) is computed on the
-GPU; these classes only score already-ranked lists for the test-time report, as Evaluator does."""
+GPU; these classes only score already-ranked lists for the test-time report, as Evaluator does.  score_lists runs that report for a
+whole file in one GPU call (rl_eval_lists); the classes stay as they are and are its reference."""
 import math
 
 import numpy as np
 
+from . import _native
 from ._native import RankLibError
 
 
@@ -244,6 +246,77 @@ def _f32(x):
 
 
 TRAINABLE = ("NDCG", "DCG", "MAP", "ERR")     # metrics whose swapChange the GPU lambda kernels implement
+
+EVAL_HOST_LEN = 2048                  # a list longer than this is ranked and scored on the host (the counting rank is O(n^2); measured: DESIGN.md 19)
+
+
+def score_lists(scorer, samples, flat_scores, want_pos=False):
+    """scorer.score(ranked list) of every list of samples, all lists in one _native.eval_lists call: flat_scores [n_docs] holds the
+    model's scores, list after list.  Returns (f64 value per list, int32 position of every document in its list's ranking or None).
+    What the scorer object holds is resolved per list id as _feed_linear_trainer does for the trainers -- idealGains (NDCG), relDocCount
+    (MAP), k, ERRScorer.MAX -- and the ideal DCGs the call computed are written back into idealGains, so the scorer is left as its own
+    scoreOne calls would have left it.  A list whose scores hold a NaN, or one longer than EVAL_HOST_LEN, takes the per-list host path
+    (stable_desc_order + scorer.score) in its place."""
+    from .learning import RankList, stable_desc_order
+    sc = np.ascontiguousarray(flat_scores, dtype=np.float64)
+    nl = len(samples)
+    qoff = np.zeros(nl + 1, np.int64)
+    np.cumsum([rl.size() for rl in samples], out=qoff[1:])
+    if sc.shape != (int(qoff[-1]),):
+        raise RankLibError("rlhip: score_lists takes one score per document (%d scores, %d documents)" % (sc.size, int(qoff[-1])))
+    name = scorer.name().split("@")[0].upper()
+    ids = [rl.getID() if rl.size() else None for rl in samples]
+    out = np.zeros(nl, np.float64)
+    pos = np.zeros(sc.size, np.int32) if want_pos else None
+    nan_at = np.flatnonzero(np.isnan(sc))
+    has_nan = np.zeros(nl, bool)
+    has_nan[np.searchsorted(qoff, nan_at, side="right") - 1] = True
+    lens = np.diff(qoff)
+    host = [q for q in range(nl) if has_nan[q] or lens[q] > EVAL_HOST_LEN or lens[q] == 0]
+    dev = [q for q in range(nl) if not (has_nan[q] or lens[q] > EVAL_HOST_LEN or lens[q] == 0)]
+
+    def on_host(q):
+        a, b = int(qoff[q]), int(qoff[q + 1])
+        order = stable_desc_order(sc[a:b])
+        out[q] = scorer.score(RankList(samples[q], list(order)))
+        if pos is not None:
+            pos[a + order] = np.arange(b - a, dtype=np.int32)
+
+    # a host list that is the first of its id in the file decides that id's idealGains entry, as it does list by list: it goes first
+    first_of_id = {}
+    for q, i in enumerate(ids):
+        first_of_id.setdefault(i, q)
+    later = []
+    for q in host:
+        if first_of_id[ids[q]] == q:
+            on_host(q)
+        else:
+            later.append(q)
+    if dev:
+        all_dev = len(dev) == nl
+        dq = qoff if all_dev else np.concatenate([[0], np.cumsum(lens[dev])])
+        take = slice(None) if all_dev else np.concatenate([np.arange(qoff[q], qoff[q + 1]) for q in dev])
+        labels = np.fromiter((dp.label for q in dev for dp in samples[q].rl), np.float32, count=int(dq[-1]))
+        keys, qkey, ideal, rdc = {}, None, None, None
+        gains = getattr(scorer, "idealGains", None)
+        if name == "NDCG":
+            qkey = np.array([keys.setdefault(ids[q], len(keys)) for q in dev], np.int32)
+            ideal = np.array([gains.get(ids[q], np.nan) for q in dev], np.float64)
+        counts = getattr(scorer, "relDocCount", None)
+        if name == "MAP" and counts is not None:
+            rdc = np.array([counts.get(ids[q], 0) for q in dev], np.int32)
+        m, p, used = _native.eval_lists(sc[take], labels, dq, name, scorer.k, err_max=ERRScorer.MAX, qkey=qkey, ideal_dcg=ideal,
+                                        rel_doc_count=rdc, want_pos=want_pos)
+        out[dev] = m
+        if pos is not None:
+            pos[take] = p
+        if name == "NDCG":
+            for j, q in enumerate(dev):
+                if ids[q] not in gains:
+                    gains[ids[q]] = float(used[j])
+    for q in later:
+        on_host(q)
+    return out, pos
 
 
 class MetricScorerFactory:            # metric/MetricScorerFactory.java:17-60
