@@ -816,6 +816,31 @@ int  rl_eval_lists(int32_t device, int32_t metric, int32_t k, double err_max, co
  * uploads before them and the copies back after them are not in it) */
 int  rl_debug_eval_times(double *kernel_ms);
 
+/* ---- feature normalisation: -norm sum | zscore | linear over every list of a file in one pass (features/SumNormalizor.java,
+ * ZScoreNormalizor.java, LinearNormalizer.java) -------------------------------------------------------------------------
+ * X is [n_docs][stride] float32, row-major, on the host; it is normalised in place (upload, one kernel, one copy back).  Row d is a
+ * DataPoint's fVals: column 0 is never a feature, and with row_len (NULL, or [n_docs]) row d holds features 1 .. row_len[d] - 1 only.
+ * List q is rows qoff[q] .. qoff[q + 1] - 1, the rules of rl_eval_lists.  cols [n_cols] are the feature ids to normalise = column indices
+ * into a row, without duplicates (the caller removes them, as Normalizer.removeDuplicateFeatures does); their order is irrelevant.
+ * Every list is normalised on its own, column by column, operation by operation as the Java does it: a NaN cell reads as 0.0f
+ * (getFeatureValue), the sums are serial f64 sums over the list's documents in order, linear is float arithmetic with Math.min / Math.max
+ * (-0.0f below +0.0f) from Float.MAX_VALUE / Float.MIN_VALUE.  times >= 1 applies the normaliser that many times in a row to every list,
+ * each pass reading what the one before wrote (the -kcv flow normalises every list nFold * nFold times).
+ * Only the cells the Java would setFeatureValue change; every other cell keeps its bits (a NaN's payload too): column 0, columns not in
+ * cols, cells past a row's row_len, and the columns of a list the Java leaves alone (sum: norm > 0 false; zscore: std > 0 false, NaN
+ * included -- a list of one document).
+ * Checked on the host before any device call -- RL_ERR_INVALID: a null X / qoff / cols; n_docs, n_lists, n_cols or times < 1;
+ * stride < 2; qoff not starting at 0, not ending at n_docs or not strictly increasing; an unknown kind; a column < 1 or >= stride; a
+ * duplicate column; a row_len entry < 1 or > stride; a requested column at or past some row's row_len (the message names the first such
+ * row and feature: -missingZero and the Java's error texts stay with the caller).  RL_ERR_NO_DEVICE without a gfx950 device: there is
+ * no CPU fallback. */
+enum { RL_NORM_SUM = 0, RL_NORM_ZSCORE = 1, RL_NORM_LINEAR = 2 };
+int  rl_normalize_lists(int32_t device, int32_t kind, float *X, int64_t n_docs, int32_t stride, const int32_t *row_len, const int32_t *qoff,
+                        int32_t n_lists, const int32_t *cols, int32_t n_cols, int32_t times);
+/* debug (tools/norm_bench.py): ms between two device events around the kernel launch of this thread's last rl_normalize_lists call (the
+ * upload before it and the copy back after it are not in it) */
+int  rl_debug_normalize_times(double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ class RlParams(C.Structure):
 
 RL_METRIC = dict(NDCG=0, DCG=1, MAP=2, ERR=3)
 RL_CA_METRIC = dict(RL_METRIC, P=4, RR=5)      # Coordinate Ascent also trains on P@k and RR@k
+RL_NORM_KIND = dict(sum=0, zscore=1, linear=2)   # RL_NORM_* of rlhip.h: the names -norm takes
 RL_EVAL_METRIC = dict(RL_CA_METRIC, BEST=6)    # eval_lists scores all seven; no trainer accepts BEST
 
 
@@ -142,6 +143,7 @@ ABI_SYMBOLS = [
     "rl_rn_set_lambdarank",
     "rl_perm_test", "rl_debug_perm_calib",
     "rl_eval_lists", "rl_debug_eval_times",
+    "rl_normalize_lists", "rl_debug_normalize_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -282,6 +284,9 @@ def lib():
     if hasattr(L, "rl_eval_lists"):     # (A/B builds of older sources rank and score on the host)
         L.rl_eval_lists.argtypes = [i32, i32, i32, C.c_double, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]
         L.rl_debug_eval_times.argtypes = [C.POINTER(C.c_double)]
+    if hasattr(L, "rl_normalize_lists"):    # (A/B builds of older sources normalise on the host)
+        L.rl_normalize_lists.argtypes = [i32, i32, vp, i64, i32, vp, vp, i32, vp, i32, i32]
+        L.rl_debug_normalize_times.argtypes = [C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -1105,4 +1110,55 @@ def eval_kernel_ms():
     """rl_debug_eval_times: ms of the kernels of this thread's last eval_lists call, between device events"""
     ms = C.c_double(0)
     check(lib().rl_debug_eval_times(C.byref(ms)))
+    return ms.value
+
+
+NORM_CHUNK_BYTES = 1 << 30            # rows of X one rl_normalize_lists call uploads (whole lists; a longer list is a call of its own)
+
+
+def normalize_lists(X, qoff, cols, kind, row_len=None, times=1, chunk_bytes=NORM_CHUNK_BYTES, device=0):
+    """rl_normalize_lists (rl_norm.inc): every list of X normalised IN PLACE on the GPU, column by column as the Java's normalisers do.
+    X [n_docs, stride]: a C-contiguous, writable float32 matrix whose rows are DataPoint.fVals (column 0 unused); qoff [n_lists + 1]; cols:
+    the feature ids, without duplicates; kind: sum, zscore or linear; row_len: None, or [n_docs] = len(fVals) of every row; times: that
+    many applications in a row.  The rows go in chunks of whole lists of at most chunk_bytes (a longer list is a chunk of its own); the
+    lists are independent, so the cut changes no bit.  Returns the number of native calls."""
+    L = lib()
+    if not hasattr(L, "rl_normalize_lists"):
+        raise RankLibError("rlhip: this librlhip.so has no normaliser (rl_normalize_lists)")
+    k = str(kind).lower()
+    if k not in RL_NORM_KIND:
+        raise RankLibError("rlhip: normalize_lists kind must be one of sum, zscore, linear (got %s)" % kind)
+    if not (isinstance(X, np.ndarray) and X.dtype == np.float32 and X.ndim == 2 and X.flags.c_contiguous and X.flags.writeable):
+        raise RankLibError("rlhip: normalize_lists takes a writable C-contiguous float32 matrix [n_docs, stride] (it is normalised in place)")
+    qo = np.ascontiguousarray(qoff, dtype=np.int32)
+    co = np.ascontiguousarray(cols, dtype=np.int32)
+    rl = None if row_len is None else np.ascontiguousarray(row_len, dtype=np.int32)
+    n, stride = X.shape
+    if qo.ndim != 1 or qo.size < 2 or co.ndim != 1 or (rl is not None and rl.shape != (n,)):
+        raise RankLibError("rlhip: normalize_lists takes qoff [n_lists + 1], cols [n_cols] and row_len [n_docs]")
+    nl = int(qo.size) - 1
+    row_bytes = stride * 4
+    # chunk ends: the last list whose end stays within the budget from the chunk's first row, at least one list
+    calls, a = 0, 0
+    whole = n * row_bytes <= chunk_bytes or not (qo[0] == 0 and qo[-1] == n and np.all(np.diff(qo) > 0))   # bad offsets: the C call's message
+    while a < nl:
+        if whole:
+            b = nl
+        else:
+            b = int(np.searchsorted(qo, int(qo[a]) + max(1, chunk_bytes // row_bytes), side="right")) - 1
+            b = min(nl, max(b, a + 1))
+        r0, r1 = (0, n) if whole else (int(qo[a]), int(qo[b]))
+        q = qo if whole else np.ascontiguousarray(qo[a:b + 1] - qo[a])
+        rlc = None if rl is None else rl[r0:r1]
+        check(L.rl_normalize_lists(int(device), RL_NORM_KIND[k], X.ctypes.data + r0 * row_bytes, r1 - r0, stride,
+                                   None if rlc is None else rlc.ctypes.data, q.ctypes.data, b - a, co.ctypes.data, int(co.size), int(times)))
+        calls += 1
+        a = b
+    return calls
+
+
+def normalize_kernel_ms():
+    """rl_debug_normalize_times: ms of the kernel of this thread's last rl_normalize_lists call, between device events"""
+    ms = C.c_double(0)
+    check(lib().rl_debug_normalize_times(C.byref(ms)))
     return ms.value

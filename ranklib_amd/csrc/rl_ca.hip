@@ -529,3 +529,4 @@ int rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weig
 #include "rl_rn.inc"       // RankNet training (-ranker 1): k_rn_epoch walks the lists and their documents, net_layer scores, k_ca_trials ranks
 #include "rl_perm.inc"     // the Analyzer's randomisation test: k_perm_test draws its sign vectors from this unit's JavaRandom stream
 #include "rl_eval.inc"     // test-time evaluation: k_eval_lists ranks and scores every list of a file (shares ca_pow2m1, ca_sync, CaBuf)
+#include "rl_norm.inc"     // -norm: k_normalize_lists normalises every list of a file in place (shares CaBuf, perm_device)

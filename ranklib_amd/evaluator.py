@@ -143,8 +143,11 @@ class Evaluator:
         trainingData, validationData, testData = FeatureManager.prepareCV(samples, nFold, tvs)
         if Evaluator.normalize:
             # :816-822, kept as written: ALL folds are normalised once per fold, and the folds share their DataPoints (RankList's copy
-            # constructor), so a list is normalised nFold x (the number of folds it appears in) times -- not idempotent in float arithmetic
-            for _ in range(nFold):
+            # constructor), so a list is normalised nFold x (the number of folds it appears in) times -- not idempotent in float arithmetic.
+            # Every list is in exactly nFold of the fold lists (train, validation or test of each fold): nFold * nFold applications, which
+            # the batched normaliser runs in one call on the file's own lists; where it cannot, the loop as written
+            done = Evaluator.nml.normalizeBatch(samples, features, times=nFold * nFold)
+            for _ in range(0 if done else nFold):
                 for group in (trainingData, validationData, testData):
                     for fold in group:
                         self.normalizeLists(fold, features)

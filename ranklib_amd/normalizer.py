@@ -3,7 +3,9 @@ is normalised on its own, in place, before training / scoring.  Mirrors features
 LinearNormalizer.java operation by operation -- the sums are sequential f64 sums over the list in document order, the casts to float
 happen where the Java's do -- because the normalised values are what LambdaMART.init() builds its thresholds from.
 
-Host-side preprocessing (numpy), as the reference's is host-side Java; nothing here runs on the GPU."""
+normalize(rl, fids) -- one list -- is host numpy, as the reference's is host-side Java.  normalizeAll hands a whole file to the GPU in one
+call (rl_normalize_lists, DESIGN.md 20: the same operations, one lane per list and column) where that changes nothing but the time; with
+Normalizer.batch = False, without a device, and for every file whose rows do not all hold every requested feature it runs list by list."""
 import numpy as np
 
 from .learning import DataPoint, RankLibError
@@ -60,13 +62,85 @@ def _seq_sum(A):                      # `acc += a[i]` over the documents, in ord
     return np.add.accumulate(A.astype(np.float64), axis=0)[-1]
 
 
+def _device_visible():
+    try:
+        from . import _native as N
+        return hasattr(N.lib(), "rl_normalize_lists") and N.device_count() > 0
+    except Exception:                 # noqa: BLE001 -- no library (a CPU-only checkout): the host path still works
+        return False
+
+
+def _row_matrix(fvs, lens):
+    """(B, first row) when the rows `fvs` are, in order, consecutive row views of one C-contiguous float32 matrix B (what the native
+    reader and the -cache reader make: `list(X)`, a short row cut to its own length); else None.  O(1) attribute reads per row."""
+    B = fvs[0].base
+    if not (isinstance(B, np.ndarray) and B.ndim == 2 and B.dtype == np.float32 and B.flags.c_contiguous and B.flags.writeable):
+        return None
+    step = B.shape[1] * 4
+    if step == 0 or max(lens) > B.shape[1]:
+        return None
+    for fv in fvs:
+        if fv.base is not B or fv.strides != (4,):
+            return None
+    addr = np.fromiter((fv.__array_interface__["data"][0] for fv in fvs), np.int64, len(fvs))
+    off = int(addr[0]) - B.ctypes.data
+    if off < 0 or off % step or off // step + len(fvs) > B.shape[0] or np.any(np.diff(addr) != step):
+        return None
+    return B, off // step
+
+
 class Normalizer:
+    batch = True                      # rlhip: normalizeAll hands a whole file to the GPU in one call (_native.normalize_lists, DESIGN.md 20)
+                                      # when a device is visible; False: list by list on the host, the same bits
+    kind = None                       # the name rl_normalize_lists knows the subclass by
+
     def normalize(self, rl, fids=None):
         raise NotImplementedError
 
     def normalizeAll(self, samples, fids=None):       # Normalizer.normalize(List<RankList>[, fids])
+        if self.normalizeBatch(samples, fids):
+            return
         for rl in samples:
             self.normalize(rl, fids)
+
+    def normalizeBatch(self, samples, fids=None, times=1):
+        """Every list of `samples` normalised `times` times in a row on the GPU; True when done.  False -- and nothing touched -- when
+        `batch` is off, no device is visible, or the list-by-list path would do anything but plain arithmetic on rows that hold every
+        requested feature: an empty list, a feature id a row does not name (an error, or -missingZero's 0), lists of different feature
+        counts without `fids`.  Rows that are views of one matrix are normalised there, in place; other rows are copied in and out."""
+        if not (Normalizer.batch and self.kind and samples and _device_visible()):
+            return False
+        if any(rl.size() == 0 for rl in samples):
+            return False
+        if fids is None:
+            fc = samples[0].getFeatureCount()
+            if any(rl.getFeatureCount() != fc for rl in samples):
+                return False
+            cols = list(range(1, fc + 1))
+        else:
+            cols = _unique(fids)
+        if not cols or min(cols) < 1:
+            return False
+        fvs = [dp.fVals for rl in samples for dp in rl.rl]
+        if any(not isinstance(fv, np.ndarray) or fv.dtype != np.float32 or fv.ndim != 1 or not fv.flags.writeable for fv in fvs):
+            return False
+        lens = list(map(len, fvs))
+        need = max(cols) + 1
+        if min(lens) < need or len(set(map(id, fvs))) != len(fvs):   # (a row listed twice would be normalised twice over, one after the other)
+            return False
+        from . import _native as N
+        qoff = np.zeros(len(samples) + 1, np.int32)
+        np.cumsum([rl.size() for rl in samples], out=qoff[1:])
+        whole = _row_matrix(fvs, lens)
+        if whole is not None:
+            B, r0 = whole
+            N.normalize_lists(B[r0:r0 + len(fvs)], qoff, cols, self.kind, row_len=lens, times=times)
+            return True
+        M = np.stack([fv[:need] for fv in fvs])       # one visit per DataPoint; the columns past the last requested one stay where they are
+        N.normalize_lists(M, qoff, cols, self.kind, times=times)
+        for fv, row in zip(fvs, M):
+            fv[:need] = row                           # the cells the kernel left alone come back with the bits they went with
+        return True
 
     @staticmethod
     def _fids(rl, fids):
@@ -74,6 +148,8 @@ class Normalizer:
 
 
 class SumNormalizor(Normalizer):      # features/SumNormalizor.java:18-70
+    kind = "sum"
+
     def name(self):
         return "sum"
 
@@ -88,6 +164,8 @@ class SumNormalizor(Normalizer):      # features/SumNormalizor.java:18-70
 
 
 class ZScoreNormalizor(Normalizer):   # features/ZScoreNormalizor.java:18-92
+    kind = "zscore"
+
     def name(self):
         return "zscore"
 
@@ -104,6 +182,8 @@ class ZScoreNormalizor(Normalizer):   # features/ZScoreNormalizor.java:18-92
 
 
 class LinearNormalizer(Normalizer):   # features/LinearNormalizer.java:18-68
+    kind = "linear"
+
     def name(self):
         return "linear"
 
