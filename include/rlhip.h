@@ -55,8 +55,9 @@ enum {
     RL_ERR_NO_BEST = -7      /* rl_ln_learn / rl_rn_learn with a validation set: no epoch scored above 0.0, no model was saved (the Java throws) */
 };
 
-/* train / validation metric (-metric2t): metric/{NDCG,DCG,AP,ERR}Scorer.java.  P, RR and BEST are not built for
- * training (RL_ERR_UNSUPPORTED); the host side can still report them on ranked lists. */
+/* train / validation metric (-metric2t): metric/{NDCG,DCG,AP,ERR}Scorer.java, and RL_METRIC_P / RL_METRIC_RR (metric/PrecisionScorer.java,
+ * metric/ReciprocalRankScorer.java; declared further down, with k >= 1).  RL_METRIC_BEST is not built for training (RL_ERR_UNSUPPORTED);
+ * the host side can still report it on ranked lists. */
 enum { RL_METRIC_NDCG = 0, RL_METRIC_DCG = 1, RL_METRIC_MAP = 2, RL_METRIC_ERR = 3 };
 /* ranker: the indices of eval/Evaluator.java:69-73 */
 enum { RL_RANKER_MART = 0, RL_RANKER_LAMBDAMART = 6 };
@@ -99,9 +100,10 @@ typedef struct {
     int32_t min_leaf_support;   /* LambdaMART.minLeafSupport    default 1    */
     int32_t early_stop_rounds;  /* LambdaMART.nRoundToStopEarly default 100  */
     float   learning_rate;      /* LambdaMART.learningRate      default 0.1F (a Java float) */
-    int32_t metric;             /* RL_METRIC_* */
-    int32_t metric_k;           /* the scorer's k: default 10 for NDCG / DCG / ERR (metric/DCGScorer.java:21,
-                                   metric/ERRScorer.java:28), 0 for MAP (metric/APScorer.java:37-39) */
+    int32_t metric;             /* RL_METRIC_*: NDCG, DCG, MAP, ERR, P, RR (RL_METRIC_BEST: RL_ERR_UNSUPPORTED) */
+    int32_t metric_k;           /* the scorer's k: default 10 for NDCG / DCG / ERR / P (metric/DCGScorer.java:21,
+                                   metric/ERRScorer.java:28, metric/PrecisionScorer.java:22), 0 for MAP (metric/APScorer.java:37-39);
+                                   P and RR need k >= 1 (RR's own default k = 0 scores 0 everywhere) */
     int32_t device;             /* HIP device ordinal */
     int32_t flags;              /* RL_FLAG_* */
     int32_t ranker;             /* RL_RANKER_LAMBDAMART (default) or RL_RANKER_MART (learning/tree/MART.java:47-65) */
@@ -345,7 +347,8 @@ enum {
     RL_ARM_LAM_FUSED = 32,      /* k_lambda_fused<., 0>: NDCG / DCG, column by row */
     RL_ARM_LAM_COMPACT = 33,    /* k_lambda_fused<., 0, true>: NDCG / DCG from the lists of active pairs (RLHIP_LAMBDA_COMPACT) */
     RL_ARM_LAM_ERR = 34,        /* k_lambda_fused<., 1> */
-    RL_ARM_LAM_MAP = 35,        /* k_lambda_fused<., 2> */
+    RL_ARM_LAM_MAP = 35,        /* k_lambda_fused<., 2>  (k_lambda_fused<., 3> and <., 4>, P and RR, have no arm: the table is full; their launches
+                                   are counted by stream only, RL_ARM_LAM_ON_SIDE / RL_ARM_LAM_ON_MAIN) */
     RL_ARM_LAM_UNFUSED = 36,    /* k_pair_terms + k_lambda_acc (counted once a round) */
     RL_ARM_LAM_ON_SIDE = 37,    /* of the fused launches, those enqueued on a side stream (RLHIP_LAMBDA_SIDE) */
     RL_ARM_LAM_ON_MAIN = 38,    /* ... and on the main stream (k_lambda_tiny included) */
@@ -412,7 +415,8 @@ int rl_reset_timing(rl_trainer *t);
  * A linear ranker trained by rl_ca_learn: the whole learn() loop of CoorAscent.java:67-202 with the Java's double arithmetic kept
  * bit for bit.  The trials of one search direction are evaluated in one pass on the GPU (rl_ca.hip); the keep / restore
  * decisions, the weights and the feature shuffle (java.util.Random(seed), Collections.shuffle) live on the host.
- * Train metrics: RL_METRIC_NDCG / DCG / MAP / ERR and, for this ranker only, P@k and RR@k. */
+ * Train metrics: RL_METRIC_NDCG / DCG / MAP / ERR and P@k and RR@k (the tree trainer and the linear rankers take these two as well;
+ * LambdaRank does not). */
 enum { RL_METRIC_P = 4, RL_METRIC_RR = 5 };
 
 typedef struct rl_ca rl_ca;             /* opaque */

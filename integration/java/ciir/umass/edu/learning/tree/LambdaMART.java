@@ -142,8 +142,9 @@ public class LambdaMART extends Ranker {
     public void init() {
         logger.info(() -> "Initializing... ");
         final String mname = scorer.name().split("@")[0];                  // "NDCG@10" -> "NDCG", "MAP" -> "MAP"
-        final int metric = "NDCG".equals(mname) ? 0 : "DCG".equals(mname) ? 1 : "MAP".equals(mname) ? 2 : "ERR".equals(mname) ? 3 : -1;
-        if (metric < 0) throw RankLibError.create("rlhip: the train metric must be NDCG, DCG, MAP or ERR (got " + scorer.name() + ")");
+        final int metric = "NDCG".equals(mname) ? 0 : "DCG".equals(mname) ? 1 : "MAP".equals(mname) ? 2 : "ERR".equals(mname) ? 3
+                : "P".equals(mname) ? 4 : "RR".equals(mname) ? 5 : -1;     // RL_METRIC_*; "RR" alone has k = 0: rl_create refuses it ("metric k out of range")
+        if (metric < 0) throw RankLibError.create("rlhip: the train metric must be NDCG, DCG, MAP, ERR, P or RR (got " + scorer.name() + ")");
         RlHipNative.setErrMax(ERRScorer.MAX);                                // -gmax (eval/Evaluator.java:241-242): the trainer created next uses it
         handle = RlHipNative.create(nTrees, nTreeLeaves, nThreshold, minLeafSupport, nRoundToStopEarly, learningRate, metric, scorer.getK(),
                 rankerId(), device, FeatureHistogram.samplingRate, seed++, javaOrder ? 16 : 0);

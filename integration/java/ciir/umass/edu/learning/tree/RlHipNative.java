@@ -6,7 +6,7 @@ import java.nio.FloatBuffer;
 final class RlHipNative {
     static { System.loadLibrary("rlhipjni"); }
     private RlHipNative() {}
-    /** metric: 0 NDCG, 1 DCG, 2 MAP, 3 ERR (RL_METRIC_*); ranker: 6 LambdaMART, 0 MART (RL_RANKER_*); flags: RL_FLAG_* (16 = RL_FLAG_JAVA_ORDER) */
+    /** metric: 0 NDCG, 1 DCG, 2 MAP, 3 ERR, 4 P, 5 RR (RL_METRIC_*; P and RR need k >= 1, 6 = BEST is refused); ranker: 6 LambdaMART, 0 MART (RL_RANKER_*); flags: RL_FLAG_* (16 = RL_FLAG_JAVA_ORDER) */
     static native long create(int nTrees, int nLeaves, int nThreshold, int minLeafSupport, int stopEarly, float lr, int metric, int k,
             int ranker, int device, float featureSamplingRate, long seed, int flags);
     static native void destroy(long h);

@@ -24,8 +24,8 @@ class RlParams(C.Structure):
                 ("ranker", C.c_int32), ("feature_sampling_rate", C.c_float), ("seed", C.c_uint64)]
 
 
-RL_METRIC = dict(NDCG=0, DCG=1, MAP=2, ERR=3)
-RL_CA_METRIC = dict(RL_METRIC, P=4, RR=5)      # Coordinate Ascent also trains on P@k and RR@k
+RL_METRIC = dict(NDCG=0, DCG=1, MAP=2, ERR=3, P=4, RR=5)      # the tree trainer's train metrics (RL_METRIC_* of rlhip.h)
+RL_CA_METRIC = dict(NDCG=0, DCG=1, MAP=2, ERR=3, P=4, RR=5)   # the linear rankers' (the same six; LambdaRank keeps its own four, learning.LambdaRank._METRICS)
 RL_NORM_KIND = dict(sum=0, zscore=1, linear=2)   # RL_NORM_* of rlhip.h: the names -norm takes
 RL_EVAL_METRIC = dict(RL_CA_METRIC, BEST=6)    # eval_lists scores all seven; no trainer accepts BEST
 

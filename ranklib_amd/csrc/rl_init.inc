@@ -96,7 +96,7 @@ static int init_shape(rl_trainer *t, InitWork &w)
     // the strict mode (every candidate already comes from the Java-order histogram)
     c.tie_on = (c.fs_size == F && !(t->p.flags & (RL_FLAG_JAVA_ORDER | RL_FLAG_FIRST_TIE)) && !kn.tie_off) ? 1 : 0;      // (sharded runs: decided below, once TS is known)
     // rows of a ranked list whose pairs the lambda loop visits (LambdaMART.java:375-377: j <= cutoff or k <= cutoff); for
-    // NDCG / DCG / ERR row `cutoff` itself only holds zero swap changes
+    // NDCG / DCG / ERR / P / RR row `cutoff` itself only holds zero swap changes (P, RR: every non-zero entry has min(i, j) < size <= k)
     c.k = (t->p.metric == RL_METRIC_MAP) ? t->p.metric_k + 1 : t->p.metric_k;
     c.rank = t->rank; c.n_ranks = t->n_ranks; c.sharded = t->dist ? 1 : 0;
     if (c.sharded) c.skip_last = 0;       // (the last split's lambda^2 sums travel with its histogram's all-reduce)
@@ -833,6 +833,7 @@ static int init_lambda_state(rl_trainer *t)
     }
     RL_HIP(t->pool.alloc(&t->d_wmax, (size_t)std::max(std::max(d.Q, (N + kThreads - 1) / kThreads), 2048) + 1));
     if (c.metric == RL_METRIC_MAP) RL_HIP(t->pool.alloc(&d.d_aux_i, (size_t)N));
+    if (c.metric == RL_METRIC_RR) RL_HIP(t->pool.alloc(&d.d_aux_i, (size_t)2 * d.Q));      // firstRank, secondRank of every list (written by the rank kernels)
     if (c.metric == RL_METRIC_ERR) {     // R[] / np[]: the rank kernels only ever write the top min(k, n) positions of a list, the rest stays 0
         RL_HIP(t->pool.alloc(&d.d_aux_a, (size_t)N)); RL_HIP(t->pool.alloc(&d.d_aux_b, (size_t)N));
         RL_HIP(hipMemset(d.d_aux_a, 0, (size_t)N * sizeof(double))); RL_HIP(hipMemset(d.d_aux_b, 0, (size_t)N * sizeof(double)));

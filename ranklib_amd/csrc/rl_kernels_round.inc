@@ -66,7 +66,7 @@ struct RankArgs {
     double *ss; float *sl; int *srel; int *sidx;     // ranked order (may be null for metric-only use)
     double *ndcg; int k;
     int metric;                  // RL_METRIC_*
-    int *aux_i; double *aux_a, *aux_b;   // ranked-order per-query tables for the swap changes of MAP / ERR (may be null)
+    int *aux_i; double *aux_a, *aux_b;   // ranked-order per-query tables for the swap changes of MAP / ERR, RR: aux_i[2 q], [2 q + 1] = firstRank, secondRank (may be null)
     double err_max;              // ERRScorer.MAX = 2^gmax (metric/ERRScorer.java:25, set by -gmax: eval/Evaluator.java:241-242)
     const int *rd_ext;           // MAP with -qrel: relDocCount of every list's qid (0 = not in the file), null = the list's own count (APScorer.java:86-94)
 };
@@ -74,7 +74,8 @@ struct RankArgs {
 __device__ __forceinline__ double err_R(int rel, double mx) { return (double)java_pow2m1(rel) / mx; }    // ERRScorer.java:71-73
 
 // The scorer's value of one ranked list + the ranked-order tables its swapChange needs, by ONE thread.  s_rel: int view of the ranked
-// labels (NDCG / DCG / ERR: (int)label of the top `size`, MAP: label > 0 of all n positions).
+// labels (NDCG / DCG / ERR: (int)label of the top `size`, MAP / P / RR: label > 0 of all n positions).
+__device__ __forceinline__ bool metric_binary_view(int metric) { return metric == RL_METRIC_MAP || metric == RL_METRIC_P || metric == RL_METRIC_RR; }
 __device__ void rank_metric(const RankArgs &a, int qi, int cur, int n, int size, const int *s_rel)
 {
     const bool is_map = a.metric == RL_METRIC_MAP;
@@ -97,6 +98,17 @@ __device__ void rank_metric(const RankArgs &a, int qi, int cur, int n, int size,
             }
             const int rdc = a.rd_ext ? a.rd_ext[qi] : count;
             res = (rdc == 0) ? 0.0 : ap / rdc;
+        } else if (a.metric == RL_METRIC_P) {                                   // PrecisionScorer.score :30-44
+            int count = 0;
+            for (int i = 0; i < size; i++) count += s_rel[i];
+            res = ((double)count) / size;
+        } else if (a.metric == RL_METRIC_RR) {                                  // ReciprocalRankScorer.score :26-35, and firstRank / secondRank of swapChange :49-61
+            const int rsize = (n > a.k) ? a.k : n;
+            int first = -1, second = -1;
+            for (int i = 0; i < rsize && second < 0; i++)
+                if (s_rel[i]) { if (first < 0) first = i; else second = i; }
+            res = (first < 0) ? 0.0 : (double)(1.0f / (float)(first + 1));      // a float division, widened
+            if (a.aux_i) { a.aux_i[2 * qi] = first; a.aux_i[2 * qi + 1] = second; }
         } else {                                                                // ERRScorer.score :45-64
             double sc = 0.0, p = 1.0;
             for (int i = 1; i <= size; i++) { const double R = err_R(s_rel[i - 1], a.err_max); sc += p * R / i; p *= (1.0 - R); }
@@ -115,7 +127,7 @@ __device__ void rank_metric(const RankArgs &a, int qi, int cur, int n, int size,
     }
 }
 
-// s_rel: int view of the ranked labels (NDCG / DCG / ERR: (int)label, MAP: label > 0), all n positions for MAP and
+// s_rel: int view of the ranked labels (NDCG / DCG / ERR: (int)label, MAP / P / RR: label > 0), all n positions for MAP and
 // for the aux tables, else the top `size`.
 template <int G, int CAP>
 __device__ void rank_query(const RankArgs &a, int qi, int tid, double *s_raw, int *s_rel, float *s_lab, int *s_idx)
@@ -128,7 +140,7 @@ __device__ void rank_query(const RankArgs &a, int qi, int tid, double *s_raw, in
     group_sync<G>();
     int size = a.k;
     if (a.k > n || a.k <= 0) size = n;
-    const bool is_map = a.metric == RL_METRIC_MAP;
+    const bool is_map = a.metric == RL_METRIC_MAP, bin_view = metric_binary_view(a.metric);
     // The ranked order is assembled in LDS and leaves in rows: written straight to ss[cur + pos] .. the 4- and 8-byte stores of a wavefront land
     // on as many memory sectors as it has lanes (four arrays: 15 M partial-sector writes a round at c2, the whole cost of these kernels).
     constexpr int PER = (CAP + G - 1) / G;
@@ -167,7 +179,7 @@ __device__ void rank_query(const RankArgs &a, int qi, int tid, double *s_raw, in
     for (int u = 0; u < PER; u++) {
         const int r = tid + u * G;
         if (r < n) {
-            s_raw[pos[u]] = v[u]; s_rel[pos[u]] = is_map ? (l[u] > 0.f ? 1 : 0) : (int)l[u];
+            s_raw[pos[u]] = v[u]; s_rel[pos[u]] = bin_view ? (l[u] > 0.f ? 1 : 0) : (int)l[u];
             if (a.ss) { s_lab[pos[u]] = l[u]; s_idx[pos[u]] = r; }
         }
     }
@@ -254,7 +266,7 @@ __global__ __launch_bounds__(kRankBlockThreads) void k_rank_huge(const RankArgs 
     const int cur = a.qoff[qi], n = a.qoff[qi + 1] - cur;
     int size = a.k;
     if (a.k > n || a.k <= 0) size = n;
-    const bool is_map = a.metric == RL_METRIC_MAP;
+    const bool bin_view = metric_binary_view(a.metric);
     int *s_rel = rel_scratch + cur;
     for (int base = 0; base < n; base += kRankBlockThreads * kRankHugeDocs) {   // block-uniform trip count (barriers inside)
         double v[kRankHugeDocs]; int r[kRankHugeDocs], pos[kRankHugeDocs];
@@ -275,7 +287,7 @@ __global__ __launch_bounds__(kRankBlockThreads) void k_rank_huge(const RankArgs 
         for (int u = 0; u < kRankHugeDocs; u++) {
             if (r[u] >= n) continue;
             const float l = a.labels[cur + r[u]];
-            s_rel[pos[u]] = is_map ? (l > 0.f ? 1 : 0) : (int)l;
+            s_rel[pos[u]] = bin_view ? (l > 0.f ? 1 : 0) : (int)l;
             if (a.ss) { a.ss[cur + pos[u]] = v[u]; a.sl[cur + pos[u]] = l; a.srel[cur + pos[u]] = (int)l; a.sidx[cur + pos[u]] = r[u]; }
         }
     }
@@ -379,6 +391,25 @@ __device__ double swap_change_abs(const LamArgs &g, int q, int cur, int n, int a
             change += ((double)(-rb * diff)) / (b + 1);
         }
         return fabs(change / rd);
+    }
+    if (g.metric == RL_METRIC_P) {                   // PrecisionScorer.java:57-77: only pairs a < size <= b; ((float) c) / size is a FLOAT division
+        const int size = (n > g.mk) ? g.mk : n;
+        const int ra = g.sl[cur + a] > 0.f ? 1 : 0, rb = g.sl[cur + b] > 0.f ? 1 : 0;
+        if (!(a < size && b >= size)) return 0.0;
+        return fabs((double)(((float)(rb - ra)) / (float)size));
+    }
+    if (g.metric == RL_METRIC_RR) {                  // ReciprocalRankScorer.java:48-107 (firstRank / secondRank: the rank kernel's, aux_i[2 q], [2 q + 1])
+        const int size = (n > g.mk) ? g.mk : n;
+        const int first = g.aux_i[2 * q], second = g.aux_i[2 * q + 1];
+        const double rr = (first != -1) ? 1.0 / (first + 1) : 0.0;                                  // :70-73
+        const int feff = (first != -1) ? first : size;                                              // :95
+        // the third loop (:99-105) runs last: its value stands where an entry is written twice
+        if (a < feff && b >= feff && g.sl[cur + b] > 0.f) return fabs(1.0 / (a + 1) - rr);
+        if (first != -1 && a == first && g.srel[cur + b] == 0) {                                    // "non-relevant" is ((int) label) == 0
+            if (b < size) return fabs((second == -1 || b < second) ? 1.0 / (b + 1) - rr : 1.0 / (second + 1) - rr);      // :74-83
+            return fabs((second == -1) ? -rr : 1.0 / (second + 1) - rr);                            // :84-93
+        }
+        return 0.0;
     }
     // ERRScorer.java:91-112; a < size.  labels / R / np beyond `size` are 0 in the Java, and the k-loop past `size`
     // only adds +-0 and multiplies by 1, so it stops at min(b, size).
@@ -550,8 +581,13 @@ __device__ double err_swap_abs(const int *top_rel, const double *top_R, const do
 // extra LDS of the ERR / MAP variants behind the K * 24 bytes of top-position tables
 __host__ __device__ inline size_t lambda_fused_extra_bytes(int mode, int K, int bt)
 {
-    return mode == 1 ? ((size_t)2 * K + (size_t)K * (K + 2)) * 8 : mode == 2 ? (size_t)bt * 8 + (((size_t)K * 4 + 7) & ~(size_t)7) : 0;
+    return mode == 1 ? ((size_t)2 * K + (size_t)K * (K + 2)) * 8 : mode == 2 ? (size_t)bt * 8 + (((size_t)K * 4 + 7) & ~(size_t)7) : 0;     // (P, RR: none)
 }
+
+// 1.0 / (p + 1) of every position the fused kernel can hold in its top tables (p < kLambdaFusedMaxK): the compiler's correctly rounded constants are the
+// quotients the Java computes (ReciprocalRankScorer.java:73,78,80,90,102)
+static_assert(kLambdaFusedMaxK == 16, "kInvPos covers the top positions of the fused lambda kernel");
+__constant__ double kInvPos[16] = {1.0 / 1, 1.0 / 2, 1.0 / 3, 1.0 / 4, 1.0 / 5, 1.0 / 6, 1.0 / 7, 1.0 / 8, 1.0 / 9, 1.0 / 10, 1.0 / 11, 1.0 / 12, 1.0 / 13, 1.0 / 14, 1.0 / 15, 1.0 / 16};
 
 // LDS of the compacted pair lists (CP) behind the top-position tables: gains [K] + one list of K * 64 two-byte entries per wavefront
 __host__ __device__ inline size_t lambda_fused_cp_bytes(int K, int bt) { return (size_t)K * 8 + (size_t)2 * K * bt; }
@@ -562,6 +598,9 @@ __host__ __device__ inline size_t lambda_fused_cp_bytes(int K, int bt) { return 
 // MODE 2: MAP.  The Java's loop over the relevant documents between a and b is a PREFIX of one sequential chain per row a (its
 //         start and its sign depend on the row's own label only, APScorer.java:145-159): the row's owner walks the chain once and leaves
 //         the running value in the term matrix, column b closes it with its own last term.
+// MODE 3: P.    |change| is one value per list, (double)(1.0f / size), for the pairs a < size <= b whose binary relevances differ (PrecisionScorer.java:57-77).
+// MODE 4: RR.   Every non-zero entry of ReciprocalRankScorer.swapChange (:48-107) is |1 / (p + 1) - rr| for a top position p (the row, the column, or
+//         secondRank) or rr itself: the reciprocals are constants (kInvPos), firstRank / secondRank / rr scalars of the wavefront, selects per pair.
 // CP (MODE 0): the pair terms are generated from per-wavefront LISTS of the active pairs instead of column by row.  A pair (a, b) contributes
 // only when its labels differ (LambdaMART.java:376) -- on MSLR-like labels four visits in ten are pairs of equal labels, and the branch-free
 // term costs them the same ~140 instructions as the others.  Every wavefront compacts the active (row, column) pairs of its own 64 columns
@@ -611,8 +650,21 @@ __global__ __launch_bounds__(BT) void k_lambda_fused(const LamArgs g, const int 
         rd = (n > 0) ? g.aux_i[cur + n - 1] : 0;        // rdCount: relevant documents of the list, or the judgment file's count (APScorer.java:124-133)
         if (g.rd_ext && rd != 0) rd = g.rd_ext[q];      // (count == 0: all changes are 0 either way, :141-143)
     }
+    const double p_unit = (MODE == 3) ? (double)(1.0f / (float)size) : 0.0;      // P: PrecisionScorer.java:73, ((float) c) / size with c = +-1
+    int rr_first = -1, rr_second = -1, rr_feff = size; double rr = 0.0, rr_vs = 0.0;
     for (int i = tid; i < K * 8; i += BT) M[(size_t)(i >> 3) * MS + BT + (i & 7)] = make_double2(0.0, 0.0);
     __syncthreads();
+    if constexpr (MODE == 4) {
+        // RR: firstRank / secondRank (ReciprocalRankScorer.java:49-61) from one ballot over the top labels, by every wavefront for itself: the results
+        // are scalars, and every 1.0 / (p + 1) the swap change needs has p < size <= 16 -- a table of constants, no division and no load chain
+        // in front of the pair loop (the first version read the rank kernel's aux_i and divided three times per thread: measured, DESIGN.md 21)
+        const int l = tid & 63;
+        const unsigned long long m = __ballot(l < size && top_l[min(l, K - 1)] > 0.f);
+        const unsigned long long m2 = m & (m - 1);
+        rr_first = __ffsll(m) - 1; rr_second = __ffsll(m2) - 1;                // (-1: none)
+        if (rr_first != -1) { rr = kInvPos[rr_first]; rr_feff = rr_first; }     // :70-73, :95
+        if (rr_second != -1) rr_vs = fabs(kInvPos[rr_second] - rr);
+    }
     if constexpr (MODE == 1) {
         for (int e = tid; e < size * KD; e += BT) { const int a = e / KD, cb = e - a * KD; x_D[e] = (cb > a) ? err_swap_abs(top_rel, x_a, x_b, size, a, cb) : 0.0; }
         __syncthreads();
@@ -719,6 +771,29 @@ __global__ __launch_bounds__(BT) void k_lambda_fused(const LamArgs g, const int 
                         M[(size_t)a * MS + tid] = pair_fin(p0, r0); M[(size_t)(a + 1) * MS + tid] = pair_fin(p1, r1);
                     }
                     if (a < size) M[(size_t)a * MS + tid] = pair_term_delta(a < na, top_l[a], lb, Dcol[a * KD], top_s[a], sb);
+                } else if constexpr (MODE == 3 || MODE == 4) {
+                    // what the column brings to its pairs, once: the swap change of a pair is then a few compares and selects of its row
+                    const bool relb = lb > 0.f;
+                    const bool p_below = b >= size;                                             // P: the column is past the cutoff
+                    const bool rr_c3 = relb && b >= rr_feff;                                    // RR :99-105: rows above firstRank against a relevant column
+                    const bool rr_c12 = rr_first != -1 && (int)lb == 0;                         // RR :74-93: the row firstRank against a "non-relevant" column
+                    double rr_top = 0.0;                                                        // |1.0 / (b + 1) - rr| of a column among the top positions
+                    if constexpr (MODE == 4) { if (b < size) rr_top = fabs(kInvPos[b] - rr); }
+                    const double rr_col = (b < size) ? ((rr_second == -1 || b < rr_second) ? rr_top : rr_vs)       // :77-81
+                                                     : ((rr_second == -1) ? rr : rr_vs);                           // :87-91  (|-rr| == rr)
+                    auto delta = [&](const int a) -> double {
+                        if constexpr (MODE == 3) return (p_below && (top_l[a] > 0.f) != relb) ? p_unit : 0.0;
+                        else return (rr_c3 && a < rr_feff) ? fabs(kInvPos[a] - rr) : ((rr_c12 && a == rr_first) ? rr_col : 0.0);   // the third loop is the last writer
+                    };
+                    int a = 0;
+                    for (; a + 2 <= size; a += 2) {
+                        const PairPre p0 = pair_pre_delta(a < na, top_l[a], lb, delta(a), top_s[a], sb);
+                        const PairPre p1 = pair_pre_delta(a + 1 < na, top_l[a + 1], lb, delta(a + 1), top_s[a + 1], sb);
+                        double r0, r1;
+                        rho_fdlibm2(p0.diff, p1.diff, r0, r1);
+                        M[(size_t)a * MS + tid] = pair_fin(p0, r0); M[(size_t)(a + 1) * MS + tid] = pair_fin(p1, r1);
+                    }
+                    if (a < size) M[(size_t)a * MS + tid] = pair_term_delta(a < na, top_l[a], lb, delta(a), top_s[a], sb);
                 } else {
                     const bool relb = valid && lb > 0.f;
                     const int rb = (tile == 0) ? rb0 : (valid ? g.aux_i[cur + b] : 0);

@@ -59,7 +59,9 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
                   t->d_T, c.lw, &c.st->maxabs_bits, c.N, c.k, c.k, c.metric, t->p.metric_k,
                   t->tr.d_aux_i, t->tr.d_aux_a, t->tr.d_aux_b, t->d_wmax, t->tr.d_ext_rd};
         if (t->d_T == nullptr) {
-            const int mode = (c.metric == RL_METRIC_ERR) ? 1 : (c.metric == RL_METRIC_MAP) ? 2 : 0;
+            const int mode = (c.metric == RL_METRIC_ERR) ? 1 : (c.metric == RL_METRIC_MAP) ? 2 : (c.metric == RL_METRIC_P) ? 3 : (c.metric == RL_METRIC_RR) ? 4 : 0;
+            // (P / RR launches are counted under no RL_ARM_LAM_* arm: the arm table is full, DESIGN.md 21; their stream is counted as every fused launch's)
+            static const int mode_arm[5] = {RL_ARM_LAM_FUSED, RL_ARM_LAM_ERR, RL_ARM_LAM_MAP, -1, -1};
             // knobs.lam_compact: NDCG / DCG pair terms from per-wavefront lists of the active pairs (k_lambda_fused<., 0, true>) instead of column by row.
             // Built and measured slower at NDCG@10 (profiles/r05i_ab_lambda_c2.txt: a wavefront's ~390 active pairs are 3.05 steps of 128, i.e. 4 against the 5 of
             // ten rows in pairs, and the lists cost LDS, registers and six ds_bpermute per pair); it is the shorter way from about NDCG@16 on.  Off by default.
@@ -82,12 +84,14 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
 #define RL_LAUNCH_FUSED(BT, cls)                                                                                                             \
             if (d.n_qcls[cls] > 0) {                                                                                                         \
                 hipStream_t ls = lam_stream();                                                                                               \
-                t->arms[cp ? RL_ARM_LAM_COMPACT : mode == 0 ? RL_ARM_LAM_FUSED : mode == 1 ? RL_ARM_LAM_ERR : RL_ARM_LAM_MAP]++;                  \
+                if (cp) t->arms[RL_ARM_LAM_COMPACT]++; else if (mode_arm[mode] >= 0) t->arms[mode_arm[mode]]++;                               \
                 t->arms[ls == s ? RL_ARM_LAM_ON_MAIN : RL_ARM_LAM_ON_SIDE]++;                                                                \
                 if (cp) hipLaunchKernelGGL((k_lambda_fused<BT, 0, true>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
                 else if (mode == 0) hipLaunchKernelGGL((k_lambda_fused<BT, 0>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
                 else if (mode == 1) hipLaunchKernelGGL((k_lambda_fused<BT, 1>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
-                else hipLaunchKernelGGL((k_lambda_fused<BT, 2>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
+                else if (mode == 2) hipLaunchKernelGGL((k_lambda_fused<BT, 2>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
+                else if (mode == 3) hipLaunchKernelGGL((k_lambda_fused<BT, 3>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
+                else hipLaunchKernelGGL((k_lambda_fused<BT, 4>), dim3(d.n_qcls[cls]), dim3(BT), lds_of(BT), ls, g, (const int *)d.d_qcls[cls], d.n_qcls[cls]); \
                 n_max += d.n_qcls[cls]; g.blockmax = t->d_wmax + n_max;                                                                      \
             }
             if (d.n_qcls[4] > 0 && mode == 0) {
@@ -97,7 +101,7 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
                                    (size_t)kLambdaTinyGroups * lambda_tiny_group_bytes(c.k), s, g, (const int *)d.d_qcls[4], d.n_qcls[4]);
                 n_max += nb; g.blockmax = t->d_wmax + n_max;
             } else {
-                // ERR / MAP: the lists of at most 16 documents take the block-per-query kernel too -- on the main stream: the side stream is for the
+                // ERR / MAP / P / RR: the lists of at most 16 documents take the block-per-query kernel too -- on the main stream: the side stream is for the
                 // widest class below (ADVICE r05: the first class launched used to take it)
                 const int keep = lam_used; lam_used = 1 << 20;
                 RL_LAUNCH_FUSED(64, 4)

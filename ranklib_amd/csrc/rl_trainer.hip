@@ -864,8 +864,8 @@ int rl_create(const rl_params *p, rl_trainer **out)
 {
     if (!p || !out) return fail(RL_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (p->metric < RL_METRIC_NDCG || p->metric > RL_METRIC_ERR)
-        return fail(RL_ERR_UNSUPPORTED, "train metric must be NDCG, DCG, MAP or ERR (P / RR / BEST are not built for training)");
+    if (p->metric < RL_METRIC_NDCG || p->metric > RL_METRIC_RR)
+        return fail(RL_ERR_UNSUPPORTED, "train metric must be NDCG, DCG, MAP, ERR, P or RR (BEST is not built for training)");
     if (p->metric == RL_METRIC_MAP ? p->metric_k < 0 : p->metric_k < 1) return fail(RL_ERR_UNSUPPORTED, "metric k out of range");
     if (p->ranker != RL_RANKER_LAMBDAMART && p->ranker != RL_RANKER_MART)
         return fail(RL_ERR_UNSUPPORTED, "ranker must be RL_RANKER_LAMBDAMART (6) or RL_RANKER_MART (0)");
@@ -935,6 +935,8 @@ int rl_create(const rl_params *p, rl_trainer **out)
     RL_HIP(hipFuncSetAttribute((const void *)k_lambda_fused<256, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLambdaFusedMaxK * (256 + 8) * 16 + 2048 + lambda_fused_cp_bytes(kLambdaFusedMaxK, 256)));
     RL_HIP(hipFuncSetAttribute((const void *)k_lambda_fused<256, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLambdaFusedMaxK * (256 + 8) * 16 + 8192));
     RL_HIP(hipFuncSetAttribute((const void *)k_lambda_fused<256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLambdaFusedMaxK * (256 + 8) * 16 + 8192));
+    RL_HIP(hipFuncSetAttribute((const void *)k_lambda_fused<256, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLambdaFusedMaxK * (256 + 8) * 16 + 2048));
+    RL_HIP(hipFuncSetAttribute((const void *)k_lambda_fused<256, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLambdaFusedMaxK * (256 + 8) * 16 + 2048));
     RL_HIP(hipFuncSetAttribute((const void *)k_chain_stitch, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     RL_HIP(hipFuncSetAttribute((const void *)k_tie_finish, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     *out = t.release();

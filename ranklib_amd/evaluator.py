@@ -4,6 +4,9 @@ Forests, Coordinate Ascent, AdaRank, RankBoost, Linear Regression, ListNet, Rank
     python -m ranklib_amd.evaluator -train f -ranker 6 -metric2t NDCG@10 -tree 1000 -leaf 31 -save model.txt
     python -m ranklib_amd.evaluator -load model.txt -rank f -score out.txt
 
+-metric2t takes NDCG@k, DCG@k, MAP, ERR@k, P@k and RR@k for every ranker but LambdaRank (-ranker 5: the first four).  Plain P is P@10;
+plain RR has k = 0 in the Java and scores 0 everywhere, so it is refused for training ("metric k out of range").  Best@k trains nothing.
+
 -load also takes the model files of the neural-net rankers (## RankNet, ## LambdaRank, ## ListNet: learning/neuralnet/) for -test, -rank
 -score / -indri, -idv, -norm and -qrel; they are scored on the GPU.  -train stays refused for -ranker 7 unless -netseed n, for -ranker 1
 unless -rnseed n and for -ranker 5 unless -lamseed n (rlhip extensions) seed the initial weights, which the Java draws from an unseeded
@@ -258,7 +261,7 @@ def main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
               "(-load also reads RankNet, LambdaRank and ListNet models) | "
               "-train <file> -ranker 7 -netseed n [-epoch n] [-lr x] (ListNet; -netseed, an rlhip extension, seeds the initial weights and is required; "

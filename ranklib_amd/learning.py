@@ -30,7 +30,7 @@ import numpy as np
 
 from . import _native as N
 from ._native import RankLibError
-from .metric import TRAINABLE, ERRScorer
+from .metric import TREE_TRAINABLE, ERRScorer
 
 logger = logging.getLogger("ranklib_amd")
 
@@ -319,8 +319,8 @@ class LambdaMART(Ranker):
     def init(self):                   # :68-166
         logger.info("Initializing... ")
         metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
-        if metric not in TRAINABLE:
-            raise RankLibError("rlhip: the train metric must be one of NDCG, DCG, MAP, ERR (got %s)" % (self.scorer.name() if self.scorer else None))
+        if metric not in TREE_TRAINABLE:
+            raise RankLibError("rlhip: the train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % (self.scorer.name() if self.scorer else None))
         cls = type(self)
         self.impacts = np.zeros(len(self.features))
         X, lab, qoff, qkey = flatten(self.samples, self.features)

@@ -245,7 +245,8 @@ def _f32(x):
     return np.float32(x)
 
 
-TRAINABLE = ("NDCG", "DCG", "MAP", "ERR")     # metrics whose swapChange the GPU lambda kernels implement
+TRAINABLE = ("NDCG", "DCG", "MAP", "ERR")     # metrics whose swapChange every GPU lambda kernel implements (LambdaRank's included)
+TREE_TRAINABLE = TRAINABLE + ("P", "RR")      # ... and those of the tree trainer's lambda kernels (LambdaMART, MART, the bags of Random Forests)
 
 EVAL_HOST_LEN = 2048                  # a list longer than this is ranked and scored on the host (the counting rank is O(n^2); measured: DESIGN.md 19)
 
