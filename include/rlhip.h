@@ -243,6 +243,16 @@ int  rl_letor_arrays(const rl_letor *l, float *labels, int32_t *last_fid, int64_
  * row_stride >= max_fid + 1; rows of flagged lines are all NaN */
 int  rl_letor_rows(const rl_letor *l, float *X, int64_t row_stride);
 void rl_letor_destroy(rl_letor *l);
+/* The way back (host only): DataPoint.toString (learning/DataPoint.java:188-199) of n_docs rows plus '\n' each, what
+ * FeatureManager.save writes (features/FeatureManager.java:455-476):
+ *   (int) label, " qid:" id " ", then for f = 1 .. row_len[i] - 1 every cell X[i * row_stride + f] that is not NaN as
+ *   f ":" Float.toString(cell), followed by a space unless f == row_len[i] - 1, then " " description.
+ * row_len[i] is the length of the row's fVals (column 0 unused), 0 <= row_len[i] <= row_stride; the qid and the description of row i
+ * are (offset, length) into `strings` (strings_len bytes).  Returns RL_OK and *needed = bytes of text (no NUL is written); if
+ * cap < *needed nothing is written.  Lines are formatted on at most 16 host threads. */
+int  rl_letor_format(const float *X, int64_t n_docs, int64_t row_stride, const int32_t *row_len, const float *labels, const char *strings,
+                     int64_t strings_len, const int64_t *qid_off, const int32_t *qid_len, const int64_t *desc_off, const int32_t *desc_len,
+                     char *buf, int64_t cap, int64_t *needed);
 
 /* ---- multi-GPU (one process per GPU; queries sharded across ranks) ---------- */
 #define RL_UNIQUE_ID_BYTES 128

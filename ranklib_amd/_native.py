@@ -125,7 +125,7 @@ ABI_SYMBOLS = [
     "rl_finish", "rl_num_trees", "rl_get_tree", "rl_get_round_metrics", "rl_best_validation", "rl_predict",
     "rl_model_to_text", "rl_model_from_text", "rl_model_destroy", "rl_model_num_trees", "rl_model_features",
     "rl_model_predict", "rl_model_predict_device", "rl_model_debug_path", "rl_dist_unique_id", "rl_dist_init", "rl_dist_init_callback", "rl_dist_stats", "rl_bin_stride", "rl_hist_features", "rl_quant_exponent", "rl_get_array", "rl_debug_exp", "rl_debug_rho", "rl_debug_float_chain", "rl_debug_fast_sum",
-    "rl_letor_parse", "rl_letor_info", "rl_letor_arrays", "rl_letor_rows", "rl_letor_destroy",
+    "rl_letor_parse", "rl_letor_info", "rl_letor_arrays", "rl_letor_rows", "rl_letor_destroy", "rl_letor_format",
     "rl_get_timing", "rl_reset_timing", "rl_set_timing_flags", "rl_debug_membench", "rl_set_err_max", "rl_tree_capacity",
     "rl_ca_params_default", "rl_ca_create", "rl_ca_destroy", "rl_ca_set_train", "rl_ca_set_validation", "rl_ca_set_external_judgments",
     "rl_ca_learn", "rl_ca_get_weights", "rl_ca_scores", "rl_ca_trace", "rl_ca_predict",
@@ -217,6 +217,8 @@ def lib():
     L.rl_letor_rows.argtypes = [vp, vp, i64]
     L.rl_letor_destroy.argtypes = [vp]
     L.rl_letor_destroy.restype = None
+    if hasattr(L, "rl_letor_format"):   # (A/B builds of older sources write LETOR text in Python)
+        L.rl_letor_format.argtypes = [vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.rl_get_timing.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
     L.rl_reset_timing.argtypes = [vp]
     L.rl_set_err_max.argtypes = [C.c_double]
@@ -370,6 +372,29 @@ def letor_parse(data):
         return out
     finally:
         lib().rl_letor_destroy(h)
+
+
+def letor_format(X, row_len, labels, strings, qid_off, qid_len, desc_off, desc_len, buf=None):
+    """Native LETOR writer (rl_letor_format): the text of DataPoint.toString plus a newline for every row of X [n][stride]; row i has
+    row_len[i] cells (column 0 unused), its qid and description are (offset, length) into the bytes `strings`.  Returns the text as a
+    uint8 array.  buf: a uint8 array to format into (reused by a caller that writes chunk after chunk; the result is then a view of it);
+    when it is too small the call is repeated with the size the first one reported."""
+    X = np.ascontiguousarray(X, np.float32)
+    n, stride = X.shape
+    row_len, qid_len, desc_len = (np.ascontiguousarray(a, np.int32) for a in (row_len, qid_len, desc_len))
+    qid_off, desc_off = np.ascontiguousarray(qid_off, np.int64), np.ascontiguousarray(desc_off, np.int64)
+    labels = np.ascontiguousarray(labels, np.float32)
+    if not (len(row_len) == len(labels) == len(qid_off) == len(qid_len) == len(desc_off) == len(desc_len) == n):
+        raise RankLibError("rlhip: letor_format takes one entry per row in every array")
+    need = C.c_int64(0)
+    while True:
+        cap = 0 if buf is None else buf.size
+        check(lib().rl_letor_format(X.ctypes.data, n, stride, row_len.ctypes.data, labels.ctypes.data, strings, len(strings), qid_off.ctypes.data,
+                                    qid_len.ctypes.data, desc_off.ctypes.data, desc_len.ctypes.data, None if buf is None else buf.ctypes.data,
+                                    cap, C.byref(need)))
+        if need.value <= cap:
+            return buf[:need.value] if buf is not None else np.empty(0, np.uint8)      # a view of buf: written out before the next call
+        buf = np.empty(need.value, np.uint8)
 
 
 def debug_float_chain(x, seg_start=None, device=0):

@@ -1,4 +1,4 @@
-// rl_letor.cpp -- host-side LETOR text parser behind the C ABI (include/rlhip.h: rl_letor_*).
+// rl_letor.cpp -- host-side LETOR text parser and writer behind the C ABI (include/rlhip.h: rl_letor_*).
 //
 // RankLib reads `label qid:ID fid:val fid:val ... # description` lines with String.split / Float.parseFloat
 // (learning/DataPoint.java:58-110, features/FeatureManager.java:199-235).  The host mirror in ranklib_amd/learning.py follows that
@@ -7,6 +7,9 @@
 // and FLAGS every line that is not plain `number qid:token (digits:number)*` so that the Python code parses -- and, where the
 // reference would, rejects -- exactly those lines itself.  Values are parsed by strtof: decimal -> float correctly rounded,
 // as Float.parseFloat does.
+//
+// rl_letor_format is the way back: DataPoint.toString (learning/DataPoint.java:188-199) of many rows, formatted on up to 16 host threads
+// with the Float.toString of rl_model.cpp (features/FeatureManager.java:455-476 writes a split file with it, line by line).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -19,6 +22,7 @@
 
 #include "../../include/rlhip.h"
 #include "rl_internal.h"
+#include "rl_model.h"
 
 struct rl_letor {
     const char *text = nullptr;
@@ -110,14 +114,66 @@ void fill_row(const char *p, const char *e, float *row)
     }
 }
 
-template <class F> void parallel_for(int64_t n, F fn)
+inline int64_t thread_count(int64_t n, int64_t most)
 {
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int64_t nt = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(hw, 64), n / 2048 + 1));
+    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(hw, most), n / 2048 + 1));
+}
+
+template <class F> void parallel_for(int64_t n, F fn)
+{
+    const int64_t nt = thread_count(n, 64);
     if (nt == 1) { fn(0, n); return; }
     std::vector<std::thread> th;
     for (int64_t k = 0; k < nt; k++) th.emplace_back([=]() { fn(n * k / nt, n * (k + 1) / nt); });
     for (auto &t : th) t.join();
+}
+
+// ---- the writer: DataPoint.toString (learning/DataPoint.java:188-199) ----------------------------------------------------------------
+constexpr int64_t kFormatThreads = 16;
+
+inline int32_t java_float_to_int(float v)      // (int) label: NaN is 0, and the cast saturates
+{
+    if (v != v) return 0;
+    if (v >= 2147483648.0f) return 2147483647;
+    if (v <= -2147483648.0f) return -2147483647 - 1;
+    return (int32_t)v;
+}
+
+inline void append_int(std::string &s, int64_t v)
+{
+    char b[24]; int k = 0;
+    uint64_t u = v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v;
+    do { b[k++] = (char)('0' + u % 10); u /= 10; } while (u);
+    if (v < 0) s.push_back('-');
+    while (k) s.push_back(b[--k]);
+}
+
+struct FormatArgs {
+    const float *X; int64_t row_stride; const int32_t *row_len; const float *labels; const char *strings;
+    const int64_t *qid_off; const int32_t *qid_len; const int64_t *desc_off; const int32_t *desc_len;
+};
+
+void format_lines(const FormatArgs &a, int64_t i0, int64_t i1, std::string &out)
+{
+    for (int64_t i = i0; i < i1; i++) {
+        append_int(out, java_float_to_int(a.labels[i]));
+        out += " qid:";
+        out.append(a.strings + a.qid_off[i], (size_t)a.qid_len[i]);
+        out.push_back(' ');
+        const float *row = a.X + i * a.row_stride;
+        const int32_t len = a.row_len[i];
+        for (int32_t f = 1; f < len; f++) {
+            if (row[f] != row[f]) continue;                                  // isUnknown: the cell AND its separator are skipped
+            append_int(out, f);
+            out.push_back(':');
+            out += rl::java_float_to_string(row[f]);
+            if (f != len - 1) out.push_back(' ');
+        }
+        out.push_back(' ');
+        out.append(a.strings + a.desc_off[i], (size_t)a.desc_len[i]);
+        out.push_back('\n');
+    }
 }
 
 }  // namespace
@@ -208,5 +264,38 @@ int rl_letor_rows(const rl_letor *L, float *X, int64_t row_stride)
 }
 
 void rl_letor_destroy(rl_letor *L) { delete L; }
+
+int rl_letor_format(const float *X, int64_t n_docs, int64_t row_stride, const int32_t *row_len, const float *labels, const char *strings,
+                    int64_t strings_len, const int64_t *qid_off, const int32_t *qid_len, const int64_t *desc_off, const int32_t *desc_len,
+                    char *buf, int64_t cap, int64_t *needed)
+{
+    if (!needed || n_docs < 0 || row_stride < 0 || strings_len < 0 || cap < 0 || (cap > 0 && !buf)) return rl::fail(RL_ERR_INVALID, "letor_format: bad argument");
+    *needed = 0;
+    if (n_docs == 0) return RL_OK;
+    if (!row_len || !labels || !qid_off || !qid_len || !desc_off || !desc_len || (!strings && strings_len > 0) || (!X && row_stride > 0))
+        return rl::fail(RL_ERR_INVALID, "letor_format: null argument");
+    for (int64_t i = 0; i < n_docs; i++) {
+        if (row_len[i] < 0 || row_len[i] > row_stride) return rl::fail(RL_ERR_INVALID, "letor_format: row_len of row " + std::to_string(i) + " is outside [0, row_stride]");
+        if (qid_len[i] < 0 || qid_off[i] < 0 || qid_off[i] > strings_len - qid_len[i] || desc_len[i] < 0 || desc_off[i] < 0 ||
+            desc_off[i] > strings_len - desc_len[i])
+            return rl::fail(RL_ERR_INVALID, "letor_format: a string of row " + std::to_string(i) + " lies outside the string buffer");
+    }
+    const FormatArgs a{X, row_stride, row_len, labels, strings, qid_off, qid_len, desc_off, desc_len};
+    const int64_t nt = thread_count(n_docs, kFormatThreads);
+    std::vector<std::string> part((size_t)nt);
+    if (nt == 1) format_lines(a, 0, n_docs, part[0]);
+    else {
+        std::vector<std::thread> th;
+        for (int64_t k = 0; k < nt; k++) th.emplace_back([&, k]() { format_lines(a, n_docs * k / nt, n_docs * (k + 1) / nt, part[(size_t)k]); });
+        for (auto &t : th) t.join();
+    }
+    int64_t total = 0;
+    for (auto &s : part) total += (int64_t)s.size();
+    *needed = total;
+    if (cap < total) return RL_OK;
+    char *p = buf;
+    for (auto &s : part) { memcpy(p, s.data(), s.size()); p += s.size(); }
+    return RL_OK;
+}
 
 }  // extern "C"

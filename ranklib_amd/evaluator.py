@@ -4,6 +4,20 @@ Forests, Coordinate Ascent, AdaRank, RankBoost, Linear Regression, ListNet, Rank
     python -m ranklib_amd.evaluator -train f -ranker 6 -metric2t NDCG@10 -tree 1000 -leaf 31 -save model.txt
     python -m ranklib_amd.evaluator -load model.txt -rank f -score out.txt
 
+The remaining flows of the reference's `main` (:492-545):
+
+    python -m ranklib_amd.evaluator -load f1.m -load f2.m -load f3.m -test f [-idv out]      the models of `-kcv 3 -kcvmd dir`: f is cut into
+                                                                                             the same 3 folds, model i scores fold i (:953-992)
+    python -m ranklib_amd.evaluator -load f1.m -load f2.m -test t1 -test t2 [-idv out]       model i scores file i (:1000-1033)
+    python -m ranklib_amd.evaluator -load f1.m -load f2.m -rank f -score out | -indri out    the same folds, scores / Indri run (:1103-1130, :1225-1262)
+    python -m ranklib_amd.evaluator -test f [-idv out]                                       no model: the metric of the file's own order (:885-907)
+    python -m ranklib_amd.evaluator -test f -score s                                         the file re-ranked by the numbers of s, one a line (:1040-1068)
+    python -m ranklib_amd.evaluator -rank f -indri out                                       the file's own order as an Indri run (:1201-1216)
+
+`-rank f` with neither -score nor -indri raises the Java's "This function has been removed." (:516-518).  With `Evaluator.batch` every
+fold, and every model-less flow, is one scoring call and one rl_eval_lists call; `Evaluator.batch = False` is the Java's loops, the same
+bytes.
+
 -metric2t takes NDCG@k, DCG@k, MAP, ERR@k, P@k and RR@k for every ranker but LambdaRank (-ranker 5: the first four).  Plain P is P@10;
 plain RR has k = 0 in the Java and scores 0 everywhere, so it is refused for training ("metric k out of range").  Best@k trains nothing.
 
@@ -31,7 +45,7 @@ import numpy as np
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RFRanker, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, java_double_str, java_round,
                        stable_desc_order)
 from .metric import DCGScorer, ERRScorer, MetricScorerFactory, score_lists
 
@@ -176,46 +190,138 @@ class Evaluator:
         logger.info("Total\t|   \t\t|  %s\t", java_round(totalScoreOnTest / totalTestSampleSize, 4))
         return scores
 
+    # ---- several models: the k-fold flows ---------------------------------------------------------------------------------
+    def _model_folds(self, modelFiles, test):
+        """(ranker f, the lists it is applied to) for f = 0 .. len(modelFiles) - 1, in that order and made when asked for.  test names
+        one file: it is cut into len(modelFiles) folds by FeatureManager.prepareCV, as -kcv cut the training file (:953-962).  test is a
+        list of files: file f as it is (:1000-1008).  Fold f is normalised with model f's features (:969-972)."""
+        nFold = len(modelFiles)
+        if isinstance(test, (list, tuple)):
+            if len(test) < nFold:                            # the Java ends in an IndexOutOfBoundsException
+                raise RankLibError("%d models were given and only %d test files: model f is applied to test file f" % (nFold, len(test)))
+            folds = None
+        else:
+            samples = _read_input(test)
+            logger.info("Preparing %d-fold test data... ", nFold)
+            _, _, folds = FeatureManager.prepareCV(samples, nFold)
+        for f in range(nFold):
+            fold = folds[f] if folds is not None else _read_input(test[f])
+            ranker = self.rFact.loadRankerFromFile(modelFiles[f])
+            if Evaluator.normalize:
+                self.normalizeLists(fold, ranker.getFeatures())
+            yield ranker, fold
+
+    def _report(self, ids, scores, rankScore, prpFile):
+        ids.append("all"); scores.append(rankScore)
+        logger.info("%s on test data: %s", self.testScorer.name(), java_round(rankScore, 4))
+        if prpFile:
+            self.savePerRankListPerformanceFile(ids, scores, prpFile)
+            logger.info("Per-ranked list performance saved to: %s", prpFile)
+        return rankScore
+
+    def _test_models(self, modelFiles, test, prpFile):      # test(List, String, prp) :953-992 and test(List, List, prp) :1000-1033
+        ids, scores, rankScore = [], [], 0.0
+        for ranker, fold in self._model_folds(modelFiles, test):
+            if not fold:
+                continue
+            if Evaluator.batch:                              # one scoring and one metric pass per fold, in fold order (DESIGN.md 19.3)
+                flat, _ = ranker.evalLists(fold)
+                per, _ = score_lists(self.testScorer, fold, flat)
+                for rl, v in zip(fold, per):
+                    ids.append(rl.getID()); scores.append(float(v))
+                    rankScore += float(v)
+            else:
+                for rl in fold:
+                    l = ranker.rank(rl)
+                    sc = self.testScorer.score(l)
+                    ids.append(l.getID()); scores.append(sc)
+                    rankScore += sc
+        rankScore = rankScore / len(ids)                     # :982: over the lists of all folds
+        return self._report(ids, scores, rankScore, prpFile)
+
+    def _write_scores(self, out, ranker, test):             # qid \t index \t Double.toString(eval)
+        if Evaluator.batch:
+            flat, qoff = ranker.evalLists(test)
+            for q, rl in enumerate(test):
+                for j, v in enumerate(flat[int(qoff[q]):int(qoff[q + 1])]):
+                    out.write("%s\t%d\t%s\n" % (rl.getID(), j, java_double_str(float(v))))
+            return
+        for rl in test:
+            for j, v in enumerate(ranker.evalList(rl)):
+                out.write("%s\t%d\t%s\n" % (rl.getID(), j, java_double_str(float(v))))
+
+    def _write_indri(self, out, ranker, test):              # qid Q0 docno rank score indri
+        if Evaluator.batch:
+            flat, qoff = ranker.evalLists(test)
+            _, pos = score_lists(DCGScorer(1), test, flat, want_pos=True)      # any metric would do: the positions are what is read
+            for q, rl in enumerate(test):
+                a, b = int(qoff[q]), int(qoff[q + 1])
+                order = np.empty(b - a, np.int64)
+                order[pos[a:b]] = np.arange(b - a)
+                for i, j in enumerate(order):
+                    docno = rl.get(int(j)).getDescription().replace("#", "").strip()
+                    out.write("%s Q0 %s %d %s indri\n" % (rl.getID(), docno, i + 1, java_double_str(java_round(float(flat[a + int(j)]), 5))))
+            return
+        for rl in test:
+            sc = ranker.evalList(rl)
+            for i, j in enumerate(stable_desc_order(sc)):
+                docno = rl.get(int(j)).getDescription().replace("#", "").strip()
+                out.write("%s Q0 %s %d %s indri\n" % (rl.getID(), docno, i + 1, java_double_str(java_round(float(sc[int(j)]), 5))))
+
     def score(self, modelFile, testFile, outputFile):      # :1076-1094: qid \t index \t score
+        """modelFile a list: score(List, String, out) :1103-1130, the file cut into len(modelFile) folds and model f applied to fold f;
+        testFile a list too: score(List, List, out) :1138-1160 (main never reaches it, in the Java either)"""
+        if isinstance(modelFile, (list, tuple)):
+            with open(outputFile, "w", encoding="utf-8") as out:
+                for ranker, fold in self._model_folds(modelFile, testFile):
+                    if fold:
+                        self._write_scores(out, ranker, fold)
+            return
         ranker = self.rFact.loadRankerFromFile(modelFile)
         test = _read_input(testFile)
         if Evaluator.normalize:                              # :1080-1082
             self.normalizeLists(test, ranker.getFeatures())
         with open(outputFile, "w", encoding="utf-8") as out:
-            if Evaluator.batch:
-                flat, qoff = ranker.evalLists(test)
-                for q, rl in enumerate(test):
-                    for j, v in enumerate(flat[int(qoff[q]):int(qoff[q + 1])]):
-                        out.write("%s\t%d\t%s\n" % (rl.getID(), j, java_double_str(float(v))))
-                return
-            for rl in test:
-                for j, v in enumerate(ranker.evalList(rl)):
-                    out.write("%s\t%d\t%s\n" % (rl.getID(), j, java_double_str(float(v))))
+            self._write_scores(out, ranker, test)
 
-    def rank(self, modelFile, testFile, indriFile):        # :1168-1194: qid Q0 docno rank score indri
+    def rank(self, modelFile, testFile, indriFile=None):   # :1168-1194: qid Q0 docno rank score indri
+        """modelFile a list: rank(List, String, indri) :1225-1262, the file cut into len(modelFile) folds and model f applied to fold f;
+        testFile a list too: rank(List, List, indri) :1270-1304 (main never reaches it, in the Java either).  Two arguments, or None for
+        the model: rank(testFile, indri) :1201-1216, the lists in the order they have"""
+        if indriFile is None:
+            modelFile, testFile, indriFile = None, modelFile, testFile
+        if modelFile is None:
+            test = _read_input(testFile)
+            with open(indriFile, "w", encoding="utf-8") as out:
+                for rl in test:
+                    for j in range(rl.size()):
+                        docno = rl.get(j).getDescription().replace("#", "").strip()
+                        out.write("%s Q0 %s %d %s indri\n" % (rl.getID(), docno, j + 1, java_double_str(java_round(1.0 - 0.0001 * j, 5))))
+            return
+        if isinstance(modelFile, (list, tuple)):
+            with open(indriFile, "w", encoding="utf-8") as out:
+                for ranker, fold in self._model_folds(modelFile, testFile):
+                    if fold:
+                        self._write_indri(out, ranker, fold)
+            return
         ranker = self.rFact.loadRankerFromFile(modelFile)
         test = _read_input(testFile)
         if Evaluator.normalize:                              # :1173-1175
             self.normalizeLists(test, ranker.getFeatures())
         with open(indriFile, "w", encoding="utf-8") as out:
-            if Evaluator.batch:
-                flat, qoff = ranker.evalLists(test)
-                _, pos = score_lists(DCGScorer(1), test, flat, want_pos=True)      # any metric would do: the positions are what is read
-                for q, rl in enumerate(test):
-                    a, b = int(qoff[q]), int(qoff[q + 1])
-                    order = np.empty(b - a, np.int64)
-                    order[pos[a:b]] = np.arange(b - a)
-                    for i, j in enumerate(order):
-                        docno = rl.get(int(j)).getDescription().replace("#", "").strip()
-                        out.write("%s Q0 %s %d %s indri\n" % (rl.getID(), docno, i + 1, java_double_str(java_round(float(flat[a + int(j)]), 5))))
-                return
-            for rl in test:
-                sc = ranker.evalList(rl)
-                for i, j in enumerate(stable_desc_order(sc)):
-                    docno = rl.get(int(j)).getDescription().replace("#", "").strip()
-                    out.write("%s Q0 %s %d %s indri\n" % (rl.getID(), docno, i + 1, java_double_str(java_round(float(sc[int(j)]), 5))))
+            self._write_indri(out, ranker, test)
 
-    def test(self, modelFile, testFile, prpFile=""):       # evaluate a saved model (:915-944); -idv: performance per ranked list
+    def test(self, modelFile, testFile=None, prpFile=""):  # evaluate a saved model (:915-944); -idv: performance per ranked list
+        """modelFile a list: test(List, String, prp) :953-992, the file cut into len(modelFile) folds and model f applied to fold f;
+        testFile a list too: test(List, List, prp) :1000-1033, model f applied to file f.  One argument, or None for the model:
+        test(testFile) / test(testFile, prp) :879-907, the lists scored in the order they have.  (Two strings are a model and a file, as
+        they have always been here: the Java's test(testFile, prpFile) is test(None, testFile, prpFile).)"""
+        if testFile is None:
+            modelFile, testFile = None, modelFile
+        if modelFile is None:
+            return self._test_input_order(testFile, prpFile)
+        if isinstance(modelFile, (list, tuple)):
+            return self._test_models(modelFile, testFile, prpFile)
         ranker = self.rFact.loadRankerFromFile(modelFile)
         test = _read_input(testFile)
         if Evaluator.normalize:                              # :919-921
@@ -234,11 +340,61 @@ class Evaluator:
                 ids.append(l.getID()); scores.append(sc)
                 rankScore += sc
         rankScore /= len(test)
-        ids.append("all"); scores.append(rankScore)
+        return self._report(ids, scores, rankScore, prpFile)
+
+    def _test_input_order(self, testFile, prpFile):         # test(testFile, prp) :885-907: testScorer.score(l) on every list as it was read
+        test = _read_input(testFile)
+        ids, scores, rankScore = [], [], 0.0
+        if Evaluator.batch:                                  # scores that fall strictly inside every list rank it as it stands
+            flat = np.concatenate([0.0 - np.arange(rl.size(), dtype=np.float64) for rl in test]) if test else np.zeros(0)
+            per, _ = score_lists(self.testScorer, test, flat)
+            for rl, v in zip(test, per):
+                ids.append(rl.getID()); scores.append(float(v))
+                rankScore += float(v)
+        else:
+            for rl in test:
+                sc = self.testScorer.score(rl)
+                ids.append(rl.getID()); scores.append(sc)
+                rankScore += sc
+        rankScore /= len(test)
+        return self._report(ids, scores, rankScore, prpFile)
+
+    def testWithScoreFile(self, testFile, scoreFile):      # :1040-1068
+        """Ranks every list of testFile by the scores of scoreFile -- one Double.parseDouble per non-empty trimmed line (the forms
+        analyzer.parse_java_double reads), dealt to the documents in file order, surplus numbers ignored -- and reports the mean of the
+        test metric.  Kept from the Java: what `-rank f -score out` writes (`id \\t j \\t score` lines) is NOT such a file; its lines do not
+        parse as one number.  Where the Java ends in an unchecked exception (a line that is no number, fewer numbers than documents) a
+        RankLibError names the line or the two counts."""
+        from .analyzer import _JAVA_TRIM, parse_java_double
+        from .features import smart_reader
+        test = _read_input(testFile)
+        values = []
+        with smart_reader(scoreFile) as f:
+            for no, content in enumerate(f, 1):
+                content = content.rstrip("\r\n").strip(_JAVA_TRIM)
+                if not content:
+                    continue
+                try:
+                    values.append(parse_java_double(content))
+                except ValueError as ex:
+                    raise RankLibError("Error in Evaluator::testWithScoreFile(): %s, line %d: %s" % (scoreFile, no, ex))
+        n_docs = sum(rl.size() for rl in test)
+        if len(values) < n_docs:
+            raise RankLibError("Error in Evaluator::testWithScoreFile(): %s holds %d scores, %s holds %d documents" % (scoreFile, len(values), testFile, n_docs))
+        flat = np.array(values[:n_docs], np.float64)
+        if Evaluator.batch:
+            per, _ = score_lists(self.testScorer, test, flat)
+            rankScore = 0.0
+            for v in per:
+                rankScore += float(v)
+            rankScore /= len(test)
+        else:
+            ranked, k = [], 0
+            for rl in test:
+                ranked.append(RankList(rl, list(stable_desc_order(flat[k:k + rl.size()]))))
+                k += rl.size()
+            rankScore = self.testScorer.score(ranked)         # evaluate(null, test) :654-660
         logger.info("%s on test data: %s", self.testScorer.name(), java_round(rankScore, 4))
-        if prpFile:
-            self.savePerRankListPerformanceFile(ids, scores, prpFile)
-            logger.info("Per-ranked list performance saved to: %s", prpFile)
         return rankScore
 
     def savePerRankListPerformanceFile(self, ids, scores, prpFile):       # :1343-1352: "<metric>   <qid>   <Double.toString(score)>"
@@ -257,13 +413,18 @@ _RANKER_TYPES = {0: RankerType.MART, 2: RankerType.RANKBOOST, 3: RankerType.ADAR
                  8: RankerType.RANDOM_FOREST, 9: RankerType.LINEAR_REGRESSION}
 
 
+_RANK_REMOVED = ("This function has been removed.\nConsider using -score in addition to your current parameters, "
+                 "and do the ranking yourself based on these scores.")       # :516-518
+
+
 def main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
         print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
-              "(-load also reads RankNet, LambdaRank and ListNet models) | "
+              "(-load also reads RankNet, LambdaRank and ListNet models; several -load: the models of a -kcv run, model i for fold i of the file, "
+              "or for the i-th -test file) | -test f [-idv out] | -test f -score s | -rank f -indri out (no model: the file's own order, or the order of the numbers in s) | "
               "-train <file> -ranker 7 -netseed n [-epoch n] [-lr x] (ListNet; -netseed, an rlhip extension, seeds the initial weights and is required; "
               "-lr x sets the learning rate to 0.001 whatever x is, as the Java does; without it 0.00001) | "
               "-train <file> -ranker 1 -rnseed n [-epoch n] [-layer n] [-node n] [-lr x] (RankNet; -rnseed, an rlhip extension, seeds the initial weights "
@@ -272,6 +433,7 @@ def main(argv=None):
               "extension, seeds the initial weights and is required; the other flags and defaults are RankNet's)")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
+    testFiles, savedModelFiles = [], []
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False                             # :86
     Evaluator.qrelFile = ""
@@ -299,9 +461,13 @@ def main(argv=None):
         elif a == "-metric2t": trainMetric = nxt()          # also captures -metric2T, exactly like the reference (:237-240)
         elif a == "-gmax": ERRScorer.MAX = math.pow(2.0, float(nxt()))      # eval/Evaluator.java:241-242
         elif a == "-validate": validationFile = nxt()
-        elif a == "-test": testFile = nxt()
+        elif a == "-test":                                  # :253-255: every -test is kept, testFile is the last one
+            testFile = nxt()
+            testFiles.append(testFile)
         elif a == "-save": modelFile = nxt()
-        elif a == "-load": savedModelFile = nxt()
+        elif a == "-load":                                  # :278-280: every -load is kept (the models of a -kcv run), savedModelFile is the last one
+            savedModelFile = nxt()
+            savedModelFiles.append(savedModelFile)
         elif a == "-rank": rankFile = nxt()
         elif a == "-score": scoreFile = nxt()
         elif a == "-indri": indriRankingFile = nxt()
@@ -390,13 +556,36 @@ def main(argv=None):
                 e.evaluate_tvs(trainFile, tvSplit, testFile or None, featureDescriptionFile or None, modelFile or None)
             else:
                 e.evaluate(trainFile, validationFile or None, testFile or None, featureDescriptionFile or None, modelFile or None)
-        elif savedModelFile:
+        elif savedModelFile and len(savedModelFiles) == 1:
             if rankFile and indriRankingFile:
                 e.rank(savedModelFile, rankFile, indriRankingFile)
             elif rankFile and scoreFile:
                 e.score(savedModelFile, rankFile, scoreFile)
             elif testFile:
                 e.test(savedModelFile, testFile, prpFile)
+            elif rankFile:
+                raise RankLibError(_RANK_REMOVED)
+        elif savedModelFile:                                # :492-545 with several models: those of a -kcv run, model f for fold f
+            if rankFile:
+                if scoreFile:
+                    e.score(savedModelFiles, rankFile, scoreFile)
+                elif indriRankingFile:
+                    e.rank(savedModelFiles, rankFile, indriRankingFile)
+                else:
+                    raise RankLibError(_RANK_REMOVED)
+            elif testFile:
+                e.test(savedModelFiles, testFiles if len(testFiles) > 1 else testFile, prpFile)
+        elif rankFile:                                      # no model: the input's own order
+            if scoreFile:                                   # (the Java goes on to load the model "")
+                raise RankLibError("-rank %s -score %s writes a model's scores: it needs -load" % (rankFile, scoreFile))
+            if not indriRankingFile:
+                raise RankLibError(_RANK_REMOVED)
+            e.rank(rankFile, indriRankingFile)
+        elif testFile:
+            if scoreFile:
+                e.testWithScoreFile(testFile, scoreFile)
+            else:
+                e.test(None, testFile, prpFile)
         return 0
 
     if ranknet or lambdarank:

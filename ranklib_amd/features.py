@@ -1,5 +1,10 @@
 """LETOR input: mirrors features/FeatureManager.java (readInput :187-245, readFeature :267-292,
-getFeatureFromSampleVector :303-322) and utilities/FileUtils.smartReader (.gz by extension)."""
+getFeatureFromSampleVector :303-322) and utilities/FileUtils.smartReader (.gz by extension); and the way back, save :455-476, with
+FeatureManager's own command line (main :37-169):
+
+    python -m ranklib_amd.features -input f [-input g ...] -output dir [-shuffle [-seed n]] [-k n [-tvs x]] [-tts x]
+    python -m ranklib_amd.features -feature_stats model.txt
+"""
 import gzip
 import logging
 import os
@@ -7,7 +12,7 @@ import os
 import numpy as np
 
 from ._native import RankLibError
-from .learning import DataPoint, RankList
+from .learning import DataPoint, JavaRandom, RankList
 
 logger = logging.getLogger("ranklib_amd")
 
@@ -213,3 +218,206 @@ class FeatureManager:
             if tvs > 0:
                 validationData.append(vali)
         return trainingData, validationData, testData
+
+    @staticmethod
+    def printQueriesForSplit(name, split):              # :413-428
+        if split is None:
+            logger.info("No %s split.", name)
+            return
+        for i, rankLists in enumerate(split):
+            logger.info("%s[%d]=", name, i)
+            for rl in rankLists:
+                logger.info(" \"%s\"", rl.getID())
+
+    @staticmethod
+    def readInputs(inputFiles):                          # readInput(List<String>) :252-260: the files in order, one after the other
+        samples = []
+        for f in inputFiles:
+            samples.extend(FeatureManager.readInput(f, False, False))
+        return samples
+
+    @staticmethod
+    def shuffle(samples, seed):
+        """Collections.shuffle(samples, new Random(seed)) in place: for i = size .. 2: swap(i - 1, rnd.nextInt(i)).  Past the JDK's
+        SHUFFLE_THRESHOLD the Java shuffles an array copy with the same draws and swaps, so this one loop is both.  The Java's own call is
+        unseeded (:116); the seed is an rlhip extension."""
+        rnd = JavaRandom(seed)
+        for i in range(len(samples), 1, -1):
+            j = rnd.nextInt(i)
+            samples[i - 1], samples[j] = samples[j], samples[i - 1]
+        return samples
+
+    # ---- writing LETOR text: save :455-476, a DataPoint.toString() and a newline per document ------------------------------------------
+    SAVE_CHUNK = 65536                # documents formatted per native call: bounds the text held in memory
+
+    @staticmethod
+    def save(samples, outputFile):
+        """The lines go through rl_letor_format (FeatureManager.native, like the reader) in chunks of SAVE_CHUNK documents; a chunk with
+        a non-ASCII id or description, and every chunk when the library does not load, goes through DataPoint.toString.  The bytes are
+        the same either way.  Kept from the Java: (int) label truncates a fractional label."""
+        docs = [dp for rl in samples for dp in rl.rl]
+        fmt = FeatureManager._native_format()
+        try:
+            with open(outputFile, "wb") as out:
+                buf = None
+                for a in range(0, len(docs), FeatureManager.SAVE_CHUNK):
+                    chunk = docs[a:a + FeatureManager.SAVE_CHUNK]
+                    text = None
+                    if fmt is not None:
+                        text, buf = FeatureManager._format_chunk(fmt, chunk, buf)
+                    if text is None:
+                        text = "".join(dp.toString() + "\n" for dp in chunk).encode("utf-8")
+                    out.write(text)
+        except RankLibError:
+            raise
+        except Exception as ex:       # noqa: BLE001 -- the reference wraps everything
+            raise RankLibError("Error in FeatureManager::save(): %s" % ex)
+
+    @staticmethod
+    def _native_format():
+        if not FeatureManager.native:
+            return None
+        try:
+            from . import _native as N
+            return N.letor_format if hasattr(N.lib(), "rl_letor_format") else None
+        except Exception:             # noqa: BLE001 -- no library (e.g. a CPU-only checkout): the Python writer still works
+            return None
+
+    @staticmethod
+    def _format_chunk(fmt, chunk, buf):
+        """(text of the chunk or None when it is not ASCII, the buffer to reuse)"""
+        n = len(chunk)
+        ids, descs = [dp.id for dp in chunk], [dp.description for dp in chunk]
+        try:
+            strings = ("".join(ids) + "".join(descs)).encode("ascii")
+        except UnicodeEncodeError:    # offsets into the bytes would not be offsets into the str
+            return None, buf
+        qid_len = np.fromiter(map(len, ids), np.int32, count=n)
+        desc_len = np.fromiter(map(len, descs), np.int32, count=n)
+        qid_off = np.cumsum(qid_len, dtype=np.int64) - qid_len
+        desc_off = int(qid_len.sum(dtype=np.int64)) + np.cumsum(desc_len, dtype=np.int64) - desc_len
+        row_len = np.fromiter((len(dp.fVals) for dp in chunk), np.int32, count=n)
+        stride = int(row_len.max())
+        if int(row_len.min()) == stride:
+            X = np.array([dp.fVals for dp in chunk], np.float32).reshape(n, stride)
+        else:
+            X = np.full((n, stride), np.nan, np.float32)
+            for i, dp in enumerate(chunk):
+                X[i, :row_len[i]] = dp.fVals
+        labels = np.fromiter((dp.label for dp in chunk), np.float32, count=n)
+        # an upper bound of the text: "-2147483648 qid:" id " ", per cell "fid:" a Float.toString of at most 15 characters and a space,
+        # " " description "\n".  Pages the text does not reach are never touched
+        bound = len(strings) + n * 19 + int(row_len.sum(dtype=np.int64)) * (len(str(stride)) + 17)
+        if buf is None or buf.size < bound:
+            buf = np.empty(bound, np.uint8)
+        return fmt(X, row_len, labels, strings, qid_off, qid_len, desc_off, desc_len, buf), buf
+
+
+def _file_name(pathName):             # FileUtils.getFileName :230-235
+    return pathName[max(pathName.rfind("/"), pathName.rfind("\\")) + 1:]
+
+
+USAGE = """Usage: python -m ranklib_amd.features <Params>
+Params:
+\t-input <file>\t\tSource data (ranked lists)
+\t-output <dir>\t\tThe output directory
+  [+] Shuffling
+\t-shuffle\t\tCreate a copy of the input file in which the ordering of all ranked lists (e.g. queries) is randomized.
+\t\t\t\t(the order among objects (e.g. documents) within each ranked list is certainly unchanged).
+\t[ -seed <n> ]\t\tSeed of the shuffle (rlhip extension; without it one is drawn and logged)
+  [+] k-fold Partitioning (sequential split)
+\t-k <fold>\t\tThe number of folds
+\t[ -tvs <x \\in [0..1]> ] Train-validation split ratio (x)(1.0-x)
+  [+] Train-test split
+\t-tts <x \\in [0..1]> ] Train-test split ratio (x)(1.0-x)
+  NOTE: If both -shuffle and -k are specified, the input data will be shuffled and then sequentially partitioned.
+Feature Statistics -- Saved model feature use frequencies and statistics.
+-input and -output parameters are not used.
+\t-feature_stats\tName of a saved, feature-limited, LTR model text file.
+\t\t\tDoes not process Coordinate Ascent, LambdaRank, ListNet or RankNet models.
+\t\t\tas they include all features rather than selected feature subsets."""
+
+
+def main(argv=None):                  # features/FeatureManager.java:37-169
+    """python -m ranklib_amd.features: -input f (repeatable) -output dir [-shuffle [-seed n]] [-k n [-tvs x]] [-tts x] | -feature_stats model.
+    Flags are matched case-insensitively and unknown ones ignored, as written; -seed is an rlhip extension (the Java's shuffle is unseeded)."""
+    import sys
+    args = list(sys.argv[1:] if argv is None else argv)
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    has_stats = "-feature_stats" in args                 # :50-51: this test, unlike the loop below, is case-sensitive
+    if (len(args) < 3 and not has_stats) or (len(args) != 2 and has_stats):
+        for line in USAGE.split("\n"):
+            logger.info(line)
+        return 0
+    rankingFiles, outputDir, modelFileName = [], "", ""
+    shuffle = doFeatureStats = False
+    nFold, tvs, tts, seed = 0, np.float32(-1), np.float32(-1), None
+    i = 0
+    while i < len(args):                                 # :79-96
+        a = args[i].lower()
+
+        def nxt():
+            nonlocal i
+            i += 1
+            if i >= len(args):
+                raise RankLibError("Missing value for " + args[i - 1])
+            return args[i]
+        if a == "-input": rankingFiles.append(nxt())
+        elif a == "-k": nFold = int(nxt())
+        elif a == "-shuffle": shuffle = True
+        elif a == "-tvs": tvs = np.float32(nxt())       # Float.parseFloat: the splits below are computed from the float's value
+        elif a == "-tts": tts = np.float32(nxt())
+        elif a == "-output":
+            outputDir = nxt()                            # FileUtils.makePathStandard :237-244
+            if outputDir[-1:] not in ("/", "\\"):
+                outputDir += os.sep
+        elif a == "-feature_stats":
+            doFeatureStats = True
+            modelFileName = nxt()
+        elif a == "-seed": seed = int(nxt())
+        i += 1
+    if nFold > 0 and tts != -1:                          # :98-101
+        logger.info("Error: Only one of k or tts should be specified.")
+        return 0
+    if shuffle or nFold > 0 or tts != -1:
+        samples = FeatureManager.readInputs(rankingFiles)
+        if not samples:
+            logger.info("Error: The input file is empty.")
+            return 0
+        fn = _file_name(rankingFiles[0])
+        if shuffle:                                      # :113-119
+            fn += ".shuffled"
+            logger.info("Shuffling... ")
+            if seed is None:
+                seed = int.from_bytes(os.urandom(8), "little", signed=True)
+                logger.info("seed = %d", seed)
+            FeatureManager.shuffle(samples, seed)
+            logger.info("Saving... ")
+            FeatureManager.save(samples, outputDir + fn)
+        if tts != -1:                                    # :121-135
+            logger.info("Splitting... ")
+            trains, tests = FeatureManager.prepareSplit(samples, float(tts))
+            logger.info("Saving splits...")
+            FeatureManager.save(trains, outputDir + "train." + fn)
+            FeatureManager.save(tests, outputDir + "test." + fn)
+        if nFold > 0:                                    # :137-158
+            logger.info("Partitioning... ")
+            trains, valis, tests = FeatureManager.prepareCV(samples, nFold, float(tvs))
+            FeatureManager.printQueriesForSplit("Train", trains)         # prepareCV's own lines :408-410, on this path only
+            FeatureManager.printQueriesForSplit("Validate", valis)
+            FeatureManager.printQueriesForSplit("Test", tests)
+            for f in range(len(trains)):
+                logger.info("Saving fold %d/%d... ", f + 1, nFold)
+                FeatureManager.save(trains[f], outputDir + "f%d.train.%s" % (f + 1, fn))
+                FeatureManager.save(tests[f], outputDir + "f%d.test.%s" % (f + 1, fn))
+                if tvs > 0:
+                    FeatureManager.save(valis[f], outputDir + "f%d.validation.%s" % (f + 1, fn))
+    elif doFeatureStats:                                 # :159-168
+        from .feature_stats import FeatureStats
+        FeatureStats(modelFileName).writeFeatureStats()
+    return 0
+
+
+if __name__ == "__main__":
+    import sys
+    sys.exit(main())

@@ -109,6 +109,23 @@ class DataPoint:
     def getDescription(self):
         return self.description
 
+    def toString(self):               # learning/DataPoint.java:188-199, kept as written: the label is cast to int, a cell that is NaN loses
+        fv = self.fVals               # its separator too, and the description follows one more space whether it is empty or not
+        last = len(fv) - 1
+        out = ["%d qid:%s " % (java_float_to_int(self.label), self.id)]
+        for i in range(1, last + 1):
+            v = fv[i]
+            if v == v:
+                out.append("%d:%s%s" % (i, java_float_str(v), "" if i == last else " "))
+        out.append(" " + self.description)
+        return "".join(out)
+
+
+def java_float_to_int(v):             # (int) of a Java float: NaN is 0, the cast truncates and saturates
+    if v != v:
+        return 0
+    return int(max(-2147483648.0, min(2147483647.0, v)))
+
 
 DenseDataPoint = DataPoint
 
@@ -477,6 +494,8 @@ def java_float_str(v):
     if f == 0:
         return "-0.0" if np.signbit(f) else "0.0"
     a = abs(float(f))
+    if a == math.inf:                 # (a feature value may be one: DataPoint.toString)
+        return "Infinity" if f > 0 else "-Infinity"
     if 1e-3 <= a < 1e7:
         r = np.format_float_positional(f, unique=True, trim="0")
         return r if "." in r else r + ".0"
@@ -634,7 +653,10 @@ class RFRanker(Ranker):
         out += "\n"
         return out + self.toString()
 
-    def loadFromString(self, fullText):   # :146-178: every "<ensemble> ... </ensemble>" block is one bag
+    @staticmethod
+    def ensembleBlocks(fullText):
+        """the "<ensemble> ... </ensemble>" blocks of a Random Forests model text, one per bag, in file order (no device is needed: what
+        loadFromString reads, and all the Combiner needs)"""
         text = "\n".join(ln for ln in fullText.split("\n") if not ln.startswith("##"))       # parsing/ModelLineProducer.java:43-78
         blocks = []
         pos = 0
@@ -649,6 +671,10 @@ class RFRanker(Ranker):
             pos = b + len("</ensemble>")
         if not blocks:
             raise RankLibError("Error in RFRanker::load(): no <ensemble> in the model")
+        return blocks
+
+    def loadFromString(self, fullText):   # :146-178: every "<ensemble> ... </ensemble>" block is one bag
+        blocks = self.ensembleBlocks(fullText)
         self.ensembles = [blk + "\n" for blk in blocks]
         self._models = [N.Model("## LambdaMART\n\n" + blk + "\n", LambdaMART.device) for blk in blocks]
         feats = []
