@@ -855,6 +855,31 @@ int  rl_normalize_lists(int32_t device, int32_t kind, float *X, int64_t n_docs, 
  * upload before it and the copy back after it are not in it) */
 int  rl_debug_normalize_times(double *kernel_ms);
 
+/* ---- a tree model after every requested number of trees, one pass over a file ----------------------------------------
+ * A model of T trees has stages t = 1 .. T: stage t is the ensemble of its first t trees with their weights.  A document's stage score
+ * is the prefix of Ensemble.eval's float chain (learning/tree/Ensemble.java:110-116): s_t = (float)((double)s_{t-1} + (double)out_t *
+ * (double)w_t), s_0 = 0.0f, out_t the leaf Split.eval reaches (a column at or beyond row_stride reads 0).  stages [n_stages] holds tree
+ * counts, strictly increasing, each in [1, T].  X and labels are HOST pointers, as in rl_model_predict.
+ * rl_model_predict_stages: out [n_stages][n_docs], the stage scores.
+ * rl_model_eval_stages: out_metric [n_stages][n_lists] is what rl_eval_lists returns for the stage's scores widened to f64 -- the stable
+ * descending rank (-0.0 ties with 0.0, +-Infinity are ordinary values) and the scorer's serial f64 chain, all seven metrics, bit for
+ * bit; qoff, qkey, ideal_dcg, rel_doc_count, metric, k, err_max and out_ideal are rl_eval_lists' arguments with its rules and error
+ * texts, and the ideal DCGs are resolved once per call.  A (stage, list) cell whose scores hold a NaN has out_nan = 1 and value 0.0 and
+ * is not ranked (the caller ranks it on the host); every other cell has out_nan = 0.  The stages are processed in chunks whose device
+ * scratch -- 4 bytes per document and stage, 16 where a list is longer than 6 144 documents -- stays within scratch_bytes (0 = 256 MiB);
+ * a chunk holds at least one stage.  The result does not depend on the chunking.
+ * RL_ERR_INVALID, the message naming the argument: a null pointer, n_stages < 1, a stage out of range or out of order, row_stride < 1,
+ * scratch_bytes < 0, a model without trees. */
+int  rl_model_predict_stages(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *stages, int32_t n_stages,
+                             float *out);
+int  rl_model_eval_stages(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const float *labels, const int32_t *qoff,
+                          int32_t n_lists, const int32_t *qkey, const double *ideal_dcg, const int32_t *rel_doc_count, int32_t metric,
+                          int32_t k, double err_max, const int32_t *stages, int32_t n_stages, int64_t scratch_bytes, double *out_metric,
+                          uint8_t *out_nan, double *out_ideal);
+/* debug (tools/stages_bench.py): ms between device events around the tree-walking and around the ranking launches of this thread's
+ * last rl_model_predict_stages / rl_model_eval_stages call, summed over its chunks */
+int  rl_debug_stage_times(double *walk_ms, double *rank_ms);
+
 #ifdef __cplusplus
 }
 #endif

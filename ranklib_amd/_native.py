@@ -144,6 +144,7 @@ ABI_SYMBOLS = [
     "rl_perm_test", "rl_debug_perm_calib",
     "rl_eval_lists", "rl_debug_eval_times",
     "rl_normalize_lists", "rl_debug_normalize_times",
+    "rl_model_predict_stages", "rl_model_eval_stages", "rl_debug_stage_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -289,6 +290,10 @@ def lib():
     if hasattr(L, "rl_normalize_lists"):    # (A/B builds of older sources normalise on the host)
         L.rl_normalize_lists.argtypes = [i32, i32, vp, i64, i32, vp, vp, i32, vp, i32, i32]
         L.rl_debug_normalize_times.argtypes = [C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_eval_stages"):  # (A/B builds of older sources score one truncated model per stage)
+        L.rl_model_predict_stages.argtypes = [vp, vp, i64, i32, vp, i32, vp]
+        L.rl_model_eval_stages.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, i32, i64, vp, vp, vp]
+        L.rl_debug_stage_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -706,6 +711,56 @@ class Model:
         """rows / scores are device pointers (e.g. torch tensors' data_ptr()); enqueued, not synchronised"""
         check(lib().rl_model_predict_device(self.h, C.c_void_p(dX_ptr), n_docs, row_stride, C.c_void_p(dOut_ptr),
                                             C.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def _stage_args(rows, stages):
+        L = lib()
+        if not hasattr(L, "rl_model_eval_stages"):
+            raise RankLibError("rlhip: this librlhip.so has no staged evaluation (rl_model_eval_stages)")
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        st = np.ascontiguousarray(stages, dtype=np.int32)
+        if rows.ndim != 2 or st.ndim != 1:
+            raise RankLibError("rlhip: staged evaluation takes rows [n_docs][row_stride] and stages [n_stages]")
+        return L, rows, st
+
+    def predict_stages(self, rows, stages):
+        """rl_model_predict_stages: f32 [len(stages)][n_docs], the scores of the model's first stages[i] trees (stages: tree counts,
+        strictly increasing, each in [1, num_trees()]); rows as in predict_rows"""
+        L, rows, st = self._stage_args(rows, stages)
+        out = np.zeros((st.size, rows.shape[0]), np.float32)
+        check(L.rl_model_predict_stages(self.h, rows.ctypes.data, rows.shape[0], rows.shape[1], st.ctypes.data, int(st.size), out.ctypes.data))
+        return out
+
+    def eval_stages(self, rows, labels, qoff, metric, k, stages, err_max=16.0, qkey=None, ideal_dcg=None, rel_doc_count=None, scratch_bytes=0):
+        """rl_model_eval_stages: every list ranked and scored, as eval_lists does it, under the model's first stages[i] trees, all stages
+        in one call.  Returns (f64 values [len(stages)][n_lists], uint8 NaN flags of the same shape -- a flagged cell holds 0.0 and was
+        not ranked --, f64 ideal DCG per list, NaN unless the metric is NDCG).  The other arguments are eval_lists'."""
+        L, rows, st = self._stage_args(rows, stages)
+        m = str(metric).upper()
+        if m not in RL_EVAL_METRIC:
+            raise RankLibError("rlhip: eval_stages metric must be one of NDCG, DCG, MAP, ERR, P, RR, BEST (got %s)" % metric)
+        lab = np.ascontiguousarray(labels, dtype=np.float32)
+        qo = np.ascontiguousarray(qoff, dtype=np.int32)
+        if lab.shape != (rows.shape[0],) or qo.ndim != 1 or qo.size < 1:
+            raise RankLibError("rlhip: eval_stages takes rows [n_docs][row_stride], labels [n_docs] and qoff [n_lists + 1]")
+        nl = int(qo.size) - 1
+
+        def per_list(a, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (nl,):
+                raise RankLibError("rlhip: eval_stages takes %s [n_lists]" % what)
+            return a
+        qk, idl, rdc = per_list(qkey, np.int32, "qkey"), per_list(ideal_dcg, np.float64, "ideal_dcg"), per_list(rel_doc_count, np.int32, "rel_doc_count")
+        out = np.zeros((st.size, max(1, nl)), np.float64)
+        nan = np.zeros((st.size, max(1, nl)), np.uint8)
+        ideal = np.zeros(max(1, nl), np.float64)
+        ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+        check(L.rl_model_eval_stages(self.h, rows.ctypes.data, rows.shape[0], rows.shape[1], lab.ctypes.data, qo.ctypes.data, nl, ptr(qk),
+                                     ptr(idl), ptr(rdc), RL_EVAL_METRIC[m], int(k), float(err_max), st.ctypes.data, int(st.size),
+                                     int(scratch_bytes), out.ctypes.data, nan.ctypes.data, ideal.ctypes.data))
+        return out[:, :nl], nan[:, :nl], ideal[:nl]
 
     def path(self):
         """MODEL_PATH_* of the last predict call: which kernel it took"""
@@ -1138,7 +1193,14 @@ def eval_kernel_ms():
     return ms.value
 
 
-NORM_CHUNK_BYTES = 1 << 30            # rows of X one rl_normalize_lists call uploads (whole lists; a longer list is a call of its own)
+def stage_times():
+    """rl_debug_stage_times: (walk ms, rank ms) of this thread's last predict_stages / eval_stages call, between device events"""
+    w, r = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_stage_times(C.byref(w), C.byref(r)))
+    return w.value, r.value
+
+
+NORM_CHUNK_BYTES = 1 << 30           # rows of X one rl_normalize_lists call uploads (whole lists; a longer list is a call of its own)
 
 
 def normalize_lists(X, qoff, cols, kind, row_len=None, times=1, chunk_bytes=NORM_CHUNK_BYTES, device=0):

@@ -29,6 +29,7 @@
 #include <memory>
 
 #include "rl_linear.inc"   // LinCtx and everything the four linear rankers share
+#include "rl_eval_dev.h"   // ca_pow2m1, ca_sync and the scorers of k_eval_lists: shared with the tree models' unit (rl_stage.inc)
 
 namespace rl {
 
@@ -45,7 +46,7 @@ struct CaArgs {
     double steps[kCaSteps];
 };
 
-__device__ __forceinline__ int ca_pow2m1(int rel) { return (int)(((unsigned)1 << (rel & 31)) - 1u); }   // DCGScorer.java:137-139, Java int arithmetic
+// ca_pow2m1 and ca_sync: rl_eval_dev.h
 
 // rel view of the labels: (int)label for NDCG / DCG / ERR, label > 0 for MAP / P / RR
 __device__ __forceinline__ int ca_rel(const CaArgs &a, float l)
@@ -91,13 +92,6 @@ __device__ double ca_metric(const CaArgs &a, int q, int n, const int *rel)
     for (int i = 0; i < rsize; i++)
         if (rel[i]) return (double)(1.0f / (float)(i + 1));
     return 0.0;
-}
-
-template <int G>
-__device__ __forceinline__ void ca_sync()
-{
-    if (G > kWave) __syncthreads();
-    else { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
 }
 
 // the last block of a direction: every trial's list-order f64 sum / Q.  The metrics are staged through LDS in coalesced rounds (stage:

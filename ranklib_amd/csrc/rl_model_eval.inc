@@ -100,9 +100,34 @@ static inline size_t eval_tiled_lds(int cols, int maxn)
 // number of steps, and since round 6 its chains drop out in phases as their trees end -- eight chains to the 7th tree's depth, six to the 5th's, four to the
 // 3rd's, two to the deepest's (see kEvalPhases) -- instead of all eight idling on their leaves to the last step: 26.8 -> 28.4 M docs/s.  The accumulator
 // adds the outputs in the ensemble's own order whatever walker produced them.
+//
+// STAGED (rl_stage.inc, DESIGN.md 23): the same walk over the trees [tbase, tbase + nt) of the model, tbase a multiple of the tile; only the
+// accumulation wavefront differs.  Its running sum starts from carry[doc] (the model's first tbase trees), it stores the sum to
+// sc[stage][doc] after every tree that ends one of the `ns` requested stages, and to carry[doc] after tree carry_at (a tile boundary, or -1).
+struct EvalStage {
+    const int32_t *stages; int32_t ns, tbase, carry_at;
+    float *carry, *sc;
+};
+
+// the accumulation of one walked tile: cnt trees whose outputs are at po[tree * kEvalDocs], the first of them tree tglob of the model
+template <bool STAGED>
+__device__ __forceinline__ void eval_accumulate(float &s, const float *po, const float *pw, int cnt, int tglob, const EvalStage &st, int &si,
+                                                int64_t n, int64_t di)
+{
+    for (int t = 0; t < cnt; t++) {
+        s = (float)((double)s + (double)po[t * kEvalDocs] * (double)pw[t]);   // Ensemble.java:113
+        if (STAGED) {
+            const int done = tglob + t + 1;                                    // trees of the model summed in s
+            if (si < st.ns && st.stages[si] == done) { st.sc[(size_t)si * n + di] = s; si++; }
+            if (done == st.carry_at) st.carry[di] = s;
+        }
+    }
+}
+
+template <bool STAGED>
 __global__ __launch_bounds__(kEvalThreads) void k_model_eval_tiled(const unsigned long long *nodes, const float *w, int MAXN, int nt,
                                                                    const float *X, int64_t n, int stride, int cols, float *out,
-                                                                   const unsigned char *perm, const unsigned char *gdepth)
+                                                                   const unsigned char *perm, const unsigned char *gdepth, const EvalStage st)
 {
     extern __shared__ unsigned char ev_raw[];
     float *sX = (float *)ev_raw;                                               // [cols][kEvalDocs]
@@ -122,6 +147,8 @@ __global__ __launch_bounds__(kEvalThreads) void k_model_eval_tiled(const unsigne
         for (int e = tid; e < nd * stride; e += kEvalThreads) { const int dd = e / stride, c = e - dd * stride; sX[c * kEvalDocs + dd] = src[e]; }
         for (int e = tid; e < (cols - stride) * kEvalDocs; e += kEvalThreads) sX[stride * kEvalDocs + e] = 0.f;
         float s = 0.f;                                                         // the accumulator wavefront's running Ensemble.eval sum
+        [[maybe_unused]] int si = 0;                                           // STAGED: the next requested stage
+        if (STAGED) { if (!walker && doc < nd) s = st.carry[d0 + doc]; }
         unsigned long long pre[kEvalPrefetch];
 #pragma unroll
         for (int u = 0; u < kEvalPrefetch; u++) { const int e = tid + u * kEvalThreads; pre[u] = (e < min(tile_words, nt * MAXN)) ? nodes[e] : 0ull; }
@@ -191,7 +218,7 @@ __global__ __launch_bounds__(kEvalThreads) void k_model_eval_tiled(const unsigne
                 }
             } else if (k > 0 && doc < nd) {                                    // accumulate the previous tile while this one is walked
                 const float *po = sO + (size_t)(cb ^ 1) * kEvalTreeTile * kEvalDocs + doc, *pw = sW + (cb ^ 1) * kEvalTreeTile;
-                for (int t = 0; t < tt_prev; t++) s = (float)((double)s + (double)po[t * kEvalDocs] * (double)pw[t]);   // Ensemble.java:113
+                eval_accumulate<STAGED>(s, po, pw, tt_prev, st.tbase + t0 - kEvalTreeTile, st, si, n, d0 + doc);
             }
             tt_prev = tt;
         }
@@ -200,9 +227,9 @@ __global__ __launch_bounds__(kEvalThreads) void k_model_eval_tiled(const unsigne
             if (k > 0) {
                 const int cb = (k - 1) & 1;
                 const float *po = sO + (size_t)cb * kEvalTreeTile * kEvalDocs + doc, *pw = sW + cb * kEvalTreeTile;
-                for (int t = 0; t < tt_prev; t++) s = (float)((double)s + (double)po[t * kEvalDocs] * (double)pw[t]);
+                eval_accumulate<STAGED>(s, po, pw, tt_prev, st.tbase + (k - 1) * kEvalTreeTile, st, si, n, d0 + doc);
             }
-            out[d0 + doc] = s;
+            if (!STAGED) out[d0 + doc] = s;
         }
     }
 }
@@ -320,7 +347,8 @@ int rl_model_from_text(const char *text, int32_t device, rl_model **out)
                 RL_HIP(hipMemcpy(m->d_gdepth, gd.data(), gd.size(), hipMemcpyHostToDevice));
                 RL_HIP(m->pool.alloc(&m->d_pack, en));
                 RL_HIP(hipMemcpy(m->d_pack, pk.data(), en * 8, hipMemcpyHostToDevice));
-                RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             }
         }
     }
@@ -350,15 +378,22 @@ int rl_model_features(const rl_model *m, int32_t *ids, int32_t cap, int32_t *n)
     return RL_OK;
 }
 
+// the staged rows' width and whether the tiled kernel takes this model at this row stride
+static bool model_eval_tiled_ok(const rl_model *m, int32_t row_stride, int &cols, size_t &lds)
+{
+    cols = (int)std::min<int64_t>(INT32_MAX, std::max<int64_t>(row_stride, (int64_t)m->maxcol + 1));     // (a feature id may be INT32_MAX)
+    lds = eval_tiled_lds(cols, m->maxn);
+    return m->d_pack && lds <= (size_t)160 * 1024 && !m->knobs.generic;
+}
+
 static int model_eval_launch(rl_model *m, const float *dX, int64_t n_docs, int32_t row_stride, float *dO, hipStream_t s)
 {
-    const int cols = (int)std::min<int64_t>(INT32_MAX, std::max<int64_t>(row_stride, (int64_t)m->maxcol + 1));     // (a feature id may be INT32_MAX)
-    const size_t lds = eval_tiled_lds(cols, m->maxn);
-    if (m->d_pack && lds <= (size_t)160 * 1024 && !m->knobs.generic) {
+    int cols; size_t lds;
+    if (model_eval_tiled_ok(m, row_stride, cols, lds)) {
         const int64_t tiles = (n_docs + kEvalDocs - 1) / kEvalDocs;
-        hipLaunchKernelGGL(k_model_eval_tiled, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256)), dim3(kEvalThreads), lds, s,
+        hipLaunchKernelGGL(k_model_eval_tiled<false>, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256)), dim3(kEvalThreads), lds, s,
                            (const unsigned long long *)m->d_pack, (const float *)m->d_w, m->maxn, (int)m->trees.size(), dX, n_docs, row_stride, cols, dO,
-                           (const unsigned char *)m->d_perm, (const unsigned char *)m->d_gdepth);
+                           (const unsigned char *)m->d_perm, (const unsigned char *)m->d_gdepth, EvalStage{});
         m->last_path = RL_MODEL_PATH_TILED;
     } else {
         hipLaunchKernelGGL(k_model_eval, dim3((unsigned)std::min<int64_t>(8192, (n_docs + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, m->ens,

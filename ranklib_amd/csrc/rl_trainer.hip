@@ -1473,3 +1473,4 @@ int rl_reset_timing(rl_trainer *t)
 }  // extern "C"
 
 #include "rl_model_eval.inc"
+#include "rl_stage.inc"      // the model after every requested number of trees: k_model_stage_scores walks, k_stage_eval ranks and scores

@@ -311,6 +311,14 @@ class Evaluator:
         with open(indriFile, "w", encoding="utf-8") as out:
             self._write_indri(out, ranker, test)
 
+    def readTestFile(self, ranker, testFile):
+        """a -test file as `-load model -test file` scores it (:915-921): read under -hr, normalised over the model's features under
+        -norm (ranklib_amd.stages prepares its files with this as well)"""
+        test = _read_input(testFile)
+        if Evaluator.normalize:                              # :919-921
+            self.normalizeLists(test, ranker.getFeatures())
+        return test
+
     def test(self, modelFile, testFile=None, prpFile=""):  # evaluate a saved model (:915-944); -idv: performance per ranked list
         """modelFile a list: test(List, String, prp) :953-992, the file cut into len(modelFile) folds and model f applied to fold f;
         testFile a list too: test(List, List, prp) :1000-1033, model f applied to file f.  One argument, or None for the model:
@@ -323,9 +331,7 @@ class Evaluator:
         if isinstance(modelFile, (list, tuple)):
             return self._test_models(modelFile, testFile, prpFile)
         ranker = self.rFact.loadRankerFromFile(modelFile)
-        test = _read_input(testFile)
-        if Evaluator.normalize:                              # :919-921
-            self.normalizeLists(test, ranker.getFeatures())
+        test = self.readTestFile(ranker, testFile)
         ids, scores, rankScore = [], [], 0.0
         if Evaluator.batch:
             flat, _ = ranker.evalLists(test)

@@ -252,6 +252,14 @@ class Ranker:
         """f64 scores of the documents dps; a ranker family overrides it with one call of its scoring kernel"""
         return np.array([self.eval(dp) for dp in dps], np.float64)
 
+    # rlhip: a model after its first t trees (DESIGN.md 23).  LambdaMART and MART have stages; bags are not stages, and a linear or
+    # neural model has none
+    def stagedScores(self, samples, scorer, stages=None):
+        raise RankLibError("rlhip: stagedScores needs a LambdaMART or MART model: a %s model has no stages" % self.name())
+
+    def truncated(self, t):
+        raise RankLibError("rlhip: truncated needs a LambdaMART or MART model: a %s model has no stages" % self.name())
+
     def save(self, modelFile):        # :106-122
         d = modelFile.rsplit("/", 1)[0] if "/" in modelFile else None
         if d:
@@ -427,6 +435,64 @@ class LambdaMART(Ranker):
     def _evalDocs(self, dps):
         return self._model.predict_rows(self._rows(dps)).astype(np.float64)
 
+    # --- stages: the model after its first t trees (rlhip) ---------------------------------------
+    def stagedScores(self, samples, scorer, stages=None):
+        """scorer's value of every list of samples under the model's first t trees, for every t of stages (tree counts, strictly
+        increasing; None: every tree): f64 [len(stages)][len(samples)], row i what metric.score_lists gives for truncated(stages[i]),
+        bit for bit.  One _native.Model.eval_stages call per chunk of whole lists whose rows stay under EVAL_ROW_BYTES; what the scorer
+        holds is resolved per list id exactly as score_lists does it, and the ideal DCGs the calls computed are written back into
+        idealGains.  A (stage, list) cell whose scores hold a NaN is filled on the host: predict_stages on that list's rows, then the
+        per-list path of score_lists.  Lists longer than metric.EVAL_HOST_LEN stay on the device (both paths give the same bits; the
+        host's would cost one sort per stage)."""
+        st = np.arange(1, self._model.num_trees() + 1, dtype=np.int32) if stages is None else np.ascontiguousarray(stages, dtype=np.int32)
+        name = scorer.name().split("@")[0].upper()
+        gains, counts = getattr(scorer, "idealGains", None), getattr(scorer, "relDocCount", None)
+        out = np.zeros((st.size, len(samples)), np.float64)
+        a = 0
+        while a < len(samples):
+            b, docs, width = a, 0, 1
+            while b < len(samples):
+                w = max(width, samples[b].getFeatureCount() + 1)
+                if b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
+                    break
+                docs, width, b = docs + samples[b].size(), w, b + 1
+            for q in range(a, b):
+                if not samples[q].size():                    # (the kernels take no empty list: the scorer's own answer, whatever the stage)
+                    out[:, q] = scorer.score(samples[q])
+            dev = [q for q in range(a, b) if samples[q].size()]
+            if dev:
+                rows = self._rows([dp for q in dev for dp in samples[q].rl])
+                dq = np.concatenate([[0], np.cumsum([samples[q].size() for q in dev])]).astype(np.int64)
+                labels = np.fromiter((dp.label for q in dev for dp in samples[q].rl), np.float32, count=int(dq[-1]))
+                ids = [samples[q].getID() for q in dev]
+                keys, qkey, ideal, rdc = {}, None, None, None
+                if name == "NDCG":
+                    qkey = np.array([keys.setdefault(i, len(keys)) for i in ids], np.int32)
+                    ideal = np.array([gains.get(i, np.nan) for i in ids], np.float64)
+                if name == "MAP" and counts is not None:
+                    rdc = np.array([counts.get(i, 0) for i in ids], np.int32)
+                vals, nan, used = self._model.eval_stages(rows, labels, dq, name, scorer.k, st, err_max=ERRScorer.MAX, qkey=qkey,
+                                                          ideal_dcg=ideal, rel_doc_count=rdc)
+                out[:, dev] = vals
+                if name == "NDCG":
+                    for j, i in enumerate(ids):
+                        if i not in gains:
+                            gains[i] = float(used[j])
+                for j in np.flatnonzero(nan.any(axis=0)):
+                    which = np.flatnonzero(nan[:, j])
+                    sc = self._model.predict_stages(rows[int(dq[j]):int(dq[j + 1])], st[which])
+                    for r, s in enumerate(which):
+                        order = stable_desc_order(sc[r].astype(np.float64))
+                        out[s, dev[j]] = scorer.score(RankList(samples[dev[j]], list(order)))
+            a = b
+        return out
+
+    def truncated(self, t):
+        """a ranker of this class holding the first t trees: its model text is truncate_model_text(model(), t)"""
+        r = self.createNew()
+        r.loadFromString(truncate_model_text(self._model_text, t))
+        return r
+
     def createNew(self):
         return LambdaMART()
 
@@ -467,6 +533,24 @@ class MART(LambdaMART):
 
     def name(self):                   # :41-44
         return "MART"
+
+
+def truncate_model_text(text, t):
+    """The text of a LambdaMART / MART model cut after its first t trees: everything before the first <tree> element as it stands (every
+    `##` line verbatim) with one comment line `## rlhip: first t of T trees` behind the last `##` line of that header, the first t <tree>
+    elements byte for byte, then </ensemble>.  t outside [1, T] is refused."""
+    import re
+    starts = [m.start() for m in re.finditer(r"^[ \t]*<tree\b", text, re.M)]
+    ends = [m.end() for m in re.finditer(r"</tree>[ \t]*\r?\n?", text)]
+    T = len(starts)
+    if T == 0 or len(ends) != T:
+        raise RankLibError("rlhip: truncated needs the text of a tree ensemble (found %d <tree> and %d </tree>)" % (T, len(ends)))
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 1 or t > T:
+        raise RankLibError("rlhip: truncated(t) takes 1 <= t <= %d, the model's trees (got %r)" % (T, t))
+    head = text[:starts[0]].splitlines(keepends=True)
+    at = max([i + 1 for i, ln in enumerate(head) if ln.startswith("##")], default=0)
+    head.insert(at, "## rlhip: first %d of %d trees\n" % (t, T))
+    return "".join(head) + text[starts[0]:ends[int(t) - 1]] + "</ensemble>\n"
 
 
 def java_double_str(v):
