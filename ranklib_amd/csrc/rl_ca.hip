@@ -28,6 +28,7 @@
 #include <map>
 #include <memory>
 
+#include "rl_lists_host.h" // the host side of a set of ranked lists: list rules, ideal DCGs (no HIP in it)
 #include "rl_linear.inc"   // LinCtx and everything the four linear rankers share
 #include "rl_eval_dev.h"   // ca_pow2m1, ca_sync and the scorers of k_eval_lists: shared with the tree models' unit (rl_stage.inc)
 
@@ -517,10 +518,10 @@ int rl_ca_predict(int32_t device, const int32_t *feature_ids, const double *weig
 #include "rl_ada.inc"      // AdaRank (-ranker 3): k_ada_weak shares ca_metric and the sets' length classes
 #include "rl_rb.inc"       // RankBoost (-ranker 2): its training lists sorted into getCorrectRanking() order in the context's set
 #include "rl_lr.inc"       // Linear Regression (-ranker 9): k_lr_gram reads the context's column-major training set
-// not a linear ranker, but it shares this unit's device buffers (CaBuf) and build
+// not a linear ranker, but it shares this unit's build
 #include "rl_net.inc"      // RankNet / LambdaRank / ListNet models (-ranker 1 / 5 / 7): the forward pass, scoring only
 #include "rl_ln.inc"       // ListNet training (-ranker 7): k_ln_epoch walks the context's training lists, k_ca_trials ranks
 #include "rl_rn.inc"       // RankNet training (-ranker 1): k_rn_epoch walks the lists and their documents, net_layer scores, k_ca_trials ranks
 #include "rl_perm.inc"     // the Analyzer's randomisation test: k_perm_test draws its sign vectors from this unit's JavaRandom stream
-#include "rl_eval.inc"     // test-time evaluation: k_eval_lists ranks and scores every list of a file (shares ca_pow2m1, ca_sync, CaBuf)
-#include "rl_norm.inc"     // -norm: k_normalize_lists normalises every list of a file in place (shares CaBuf, perm_device)
+#include "rl_eval.inc"     // test-time evaluation: k_eval_lists ranks and scores every list of a file (shares ca_pow2m1, ca_sync)
+#include "rl_norm.inc"     // -norm: k_normalize_lists normalises every list of a file in place

@@ -1,5 +1,5 @@
 // rl_eval.inc -- test-time evaluation: rank every list of a file by its scores and take each list's metric, one pass on gfx950.
-// DESIGN.md 19.  Included by rl_ca.hip's unit (it shares ca_pow2m1, ca_sync and CaBuf); k_ca_trials is not touched.
+// DESIGN.md 19.  Included by rl_ca.hip's unit (it shares ca_pow2m1 and ca_sync); k_ca_trials is not touched.
 //
 //   k_eval_lists<G, CAP>  a group of G threads owns one list.  Its scores go into LDS (CAP > 0) or stay in global memory (CAP == 0), every
 //                         document counts its position p = #{j : s[j] > s[i] or (s[j] == s[i] and j < i)} -- stable and descending,
@@ -75,13 +75,13 @@ int rl_eval_lists(int32_t device, int32_t metric, int32_t k, double err_max, con
     int rc = eval_prepare(metric, k, err_max, scores, labels, n_docs, qoff, n_lists, qkey, ideal_dcg, rel_doc_count, out_metric, ideal, disc,
                           err);
     if (rc) return fail(rc, err);
-    if ((rc = perm_device(device))) return rc;
+    if ((rc = open_device(device, true))) return rc;
     std::vector<int32_t> lists[4];
     for (int32_t q = 0; q < n_lists; q++) {
         const int n = qoff[q + 1] - qoff[q];
         lists[n <= kEvTiny ? 0 : n <= kEvWave ? 1 : n <= kEvBlock ? 2 : 3].push_back(q);
     }
-    CaBuf buf;
+    DevPool buf;
     EvArgs a;
     memset(&a, 0, sizeof(a));
     double *d_sc = nullptr, *d_ideal = nullptr, *d_disc = nullptr, *d_out = nullptr; float *d_lab = nullptr;

@@ -583,36 +583,12 @@ static int init_query_side(rl_trainer *t, InitWork &w)
 {
     Ctx &c = t->ctx;
     const int F = w.F;
-    int maxq = std::max(t->tr.maxq, t->has_valid ? t->va.maxq : 0);
-    std::vector<double> disc((size_t)maxq + 2);
-    for (size_t i = 0; i < disc.size(); i++) disc[i] = discount_of((int)i);
+    const std::vector<double> disc = discount_table(std::max(t->tr.maxq, t->has_valid ? t->va.maxq : 0));
     double *d_disc = nullptr;
     RL_HIP(t->pool.alloc(&d_disc, disc.size()));
     RL_HIP(hipMemcpy(d_disc, disc.data(), disc.size() * sizeof(double), hipMemcpyHostToDevice));
     c.disc = d_disc;
     {
-        std::map<int64_t, double> cache;
-        // -qrel: NDCGScorer.loadExternalRelevanceJudgment fills idealGains BEFORE any list is scored (:50-96): those qids never compute their own
-        auto preload = [&](DataSet &d, int64_t anon_base) {
-            for (int q = 0; q < d.Q && !d.ext_ideal.empty(); q++)
-                if (d.ext_ideal[q] == d.ext_ideal[q]) cache[d.has_key ? (int64_t)d.qkey[q] : anon_base + q] = d.ext_ideal[q];
-        };
-        preload(t->tr, (int64_t)1 << 40);
-        if (t->has_valid) preload(t->va, (int64_t)1 << 41);
-        const std::map<int64_t, double> external = cache;
-        auto run = [&](DataSet &d, int64_t anon_base, std::vector<double> &own, std::vector<double> &cached) {
-            own.resize(d.Q); cached.resize(d.Q);
-            for (int q = 0; q < d.Q; q++) {
-                const int n = d.qoff[q + 1] - d.qoff[q];
-                const int size = std::min(n, t->p.metric_k);
-                const int64_t key = d.has_key ? (int64_t)d.qkey[q] : anon_base + q;
-                { auto pre = external.find(key); if (pre != external.end()) { own[q] = cached[q] = pre->second; continue; } }
-                own[q] = ideal_dcg(d.labels.data() + d.qoff[q], n, size, disc);
-                auto it = cache.find(key);
-                if (it == cache.end()) it = cache.emplace(key, own[q]).first;   // score() fills the cache in list order
-                cached[q] = it->second;
-            }
-        };
         auto upload_rd = [&](DataSet &d) -> int {
             if (d.ext_rd.empty()) return RL_OK;
             RL_HIP(t->pool.alloc(&d.d_ext_rd, (size_t)d.Q));
@@ -620,15 +596,13 @@ static int init_query_side(rl_trainer *t, InitWork &w)
             return RL_OK;
         };
         { int rcu = upload_rd(t->tr); if (rcu) return rcu; if (t->has_valid) { rcu = upload_rd(t->va); if (rcu) return rcu; } }
-        std::vector<double> own, cached;
-        run(t->tr, (int64_t)1 << 40, own, cached);
-        int rc = upload_query_side(t, t->tr, own, cached);
+        // round 0 scores a list against its own ideal (ideal0), the later rounds against the cache's entry (ideal1): ideal_cache, rl_lists_host.h
+        const int k = t->p.metric_k;
+        std::vector<double> own[2], cached[2];
+        ideal_cache(t->tr, t->has_valid ? &t->va : nullptr, disc, [k](int n) { return std::min(n, k); }, cached, own);
+        int rc = upload_query_side(t, t->tr, own[0], cached[0]);
         if (rc) return rc;
-        if (t->has_valid) {
-            run(t->va, (int64_t)1 << 41, own, cached);
-            rc = upload_query_side(t, t->va, own, cached);
-            if (rc) return rc;
-        }
+        if (t->has_valid && (rc = upload_query_side(t, t->va, own[1], cached[1]))) return rc;
     }
     c.labels = t->tr.d_labels; c.qoff = t->tr.d_qoff; c.ideal0 = t->tr.d_ideal0; c.ideal1 = t->tr.d_ideal1;
     c.scores = t->tr.d_scores; c.ndcg_q = t->tr.d_ndcg;

@@ -228,3 +228,40 @@ int fail(int code, const std::string &msg);
             return rl::fail(RL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " at " + \
                                             __FILE__ + ":" + std::to_string(__LINE__));              \
     } while (0)
+
+namespace rl {
+
+// The device gate of every entry point, after its own argument checks: a device must be visible, the ordinal in range; the device
+// becomes current.  require_gfx950 = false for the entry points that have never tested the architecture (rl_*_predict, rl_model_from_text).
+inline int open_device(int32_t device, bool require_gfx950)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
+    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
+    RL_HIP(hipSetDevice(device));
+    if (!require_gfx950) return RL_OK;
+    hipDeviceProp_t prop;
+    RL_HIP(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+        return fail(RL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", librlhip is built for gfx950 only");
+    return RL_OK;
+}
+
+struct DevPool {                       // device allocations of one handle or one call, freed together
+    std::vector<void *> ptrs;
+    template <typename T> hipError_t alloc(T **p, size_t n)
+    {
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, (n > 1 ? n : 1) * sizeof(T));
+        if (e == hipSuccess) { ptrs.push_back(q); *p = (T *)q; }
+        return e;
+    }
+    void release(void *p)
+    {
+        for (auto &q : ptrs) if (q == p) { (void)hipFree(q); q = nullptr; }
+    }
+    ~DevPool() { for (void *q : ptrs) if (q) (void)hipFree(q); }
+};
+
+}  // namespace rl

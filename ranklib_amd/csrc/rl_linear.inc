@@ -44,27 +44,13 @@ __global__ void k_lin_score(double *out, const float *xc, const float *rows, int
     out[i] = s;
 }
 
-struct CaBuf {                         // device allocations of one handle, freed together
-    std::vector<void *> ptrs;
-    template <class T> hipError_t alloc(T **p, size_t count)
-    {
-        hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    ~CaBuf() { for (void *p : ptrs) (void)hipFree(p); }
-};
-
 struct CaClass {
     int32_t nq = 0; int32_t *d_qlist = nullptr;
     int64_t nh = 0; int64_t *d_hoff = nullptr;        // longest class only
 };
 
-struct CaSet {
-    int64_t N = 0; int32_t Q = 0, maxq = 0;
+struct CaSet : ListSetHost {           // the host side (labels, qoff, qkey, the -qrel tables): rl_lists_host.h
     std::vector<float> X;              // [N][F] as given
-    std::vector<float> labels; std::vector<int32_t> qoff, qkey; bool has_key = false;
-    std::vector<double> ext_ideal; std::vector<int32_t> ext_rd;
     float *d_xc = nullptr, *d_labels = nullptr; int32_t *d_qoff = nullptr, *d_rd = nullptr;
     double *d_ideal = nullptr, *d_cache = nullptr, *d_cache2 = nullptr;
     CaClass cls[4];
@@ -78,7 +64,7 @@ struct LinCtx {
     bool has_train = false, has_valid = false, uploaded = false, learned = false;
     CaSet tr, va;
     hipStream_t stream = nullptr;
-    CaBuf buf;
+    DevPool buf;
     double *d_disc = nullptr, *d_m = nullptr, *d_sums = nullptr; uint32_t *d_done = nullptr;
     double *h_sums = nullptr;
     int32_t *d_col = nullptr; double *d_thr = nullptr, *d_w = nullptr; int32_t model_cap = -1;   // lin_score_model's copy of the model
@@ -96,30 +82,14 @@ template <class H> static const LinCtx *lin_ctx(const H *h) { return h ? &h->ctx
 // rl_ca.hip: trials [0, T) of one direction on set d through k_ca_trials
 static int ca_trials(LinCtx *c, CaSet &d, const float *xcol, const double *steps, int T, int first, double *out);
 
-static double ca_discount(int i) { return 1.0 / (std::log((double)(i + 2)) / std::log(2.0)); }   // DCGScorer.java:26
-
-static double ca_ideal_dcg(const float *labels, int n, int topk, const std::vector<double> &disc)
-{   // NDCGScorer.getIdealDCG (:167-174)
-    std::vector<int> rel(n);
-    for (int i = 0; i < n; i++) rel[i] = (int)labels[i];
-    std::sort(rel.begin(), rel.end(), [](int a, int b) { return a > b; });
-    double dcg = 0;
-    for (int i = 0; i < topk; i++) dcg += (double)(int32_t)(((uint32_t)1 << (rel[i] & 31)) - 1u) * disc[i];
-    return dcg;
-}
-
 static int ca_check_set(const float *X, int64_t n, int32_t F, const float *labels, const int32_t *qoff, int32_t Q)
 {
     if (!X || !labels || !qoff) return fail(RL_ERR_INVALID, "null data pointer");
     if (n <= 0 || Q <= 0 || F <= 0) return fail(RL_ERR_INVALID, "There are no training samples / features");
     if (n >= (int64_t)2147483647 - 4096) return fail(RL_ERR_UNSUPPORTED, "more than 2^31 documents per GPU");
-    if (qoff[0] != 0 || (int64_t)qoff[Q] != n) return fail(RL_ERR_INVALID, "qoff must start at 0 and end at n_docs");
-    for (int32_t q = 0; q < Q; q++)
-        if (qoff[q + 1] <= qoff[q]) return fail(RL_ERR_INVALID, "qoff must be strictly increasing (empty ranked list)");
-    for (int64_t i = 0; i < n; i++) {
-        if (!(labels[i] >= 0)) return fail(RL_ERR_INVALID, "Relevance label cannot be negative. System will now exit.");
-        if (labels[i] >= 16777216.f) return fail(RL_ERR_UNSUPPORTED, "relevance label of 2^24 or more");
-    }
+    std::string err;
+    const int rc = check_lists("", labels, n, qoff, Q, err);
+    if (rc) return fail(rc, err);
     for (int64_t i = 0; i < n * F; i++) {
         if (std::isnan(X[i])) return fail(RL_ERR_INVALID, "NaN in X (a missing feature must be passed as 0)");
         if (std::isinf(X[i])) return fail(RL_ERR_UNSUPPORTED, "+-Infinity feature value: the Java's cached scores turn NaN (0 * Infinity), not reproduced (DESIGN.md 7)");
@@ -129,15 +99,8 @@ static int ca_check_set(const float *X, int64_t n, int32_t F, const float *label
 
 static void ca_store(CaSet &d, const float *X, int64_t n, int32_t F, const float *labels, const int32_t *qoff, int32_t Q, const int32_t *qkey)
 {
-    d.N = n; d.Q = Q;
+    d.store(labels, n, qoff, Q, qkey);
     d.X.assign(X, X + n * F);
-    d.labels.assign(labels, labels + n);
-    d.qoff.assign(qoff, qoff + Q + 1);
-    d.has_key = qkey != nullptr;
-    if (qkey) d.qkey.assign(qkey, qkey + Q); else d.qkey.clear();
-    d.maxq = 0;
-    for (int32_t q = 0; q < Q; q++) d.maxq = std::max(d.maxq, qoff[q + 1] - qoff[q]);
-    d.ext_ideal.clear(); d.ext_rd.clear();
 }
 
 static int ca_upload(LinCtx *c, CaSet &d, const std::vector<double> &ideal)
@@ -189,43 +152,18 @@ static int ca_upload(LinCtx *c, CaSet &d, const std::vector<double> &ideal)
     return RL_OK;
 }
 
-// ideal DCGs with the qid-keyed cache quirk (NDCGScorer.java:114-122,134-143), -qrel entries first: as rl_trainer.hip builds them
+// the discounts, the ideal DCGs (the qid-keyed cache with the -qrel entries first: ideal_cache, rl_lists_host.h) and both sets on the device
 static int ca_prepare(LinCtx *c)
 {
-    const int maxq = std::max(c->tr.maxq, c->has_valid ? c->va.maxq : 0);
-    std::vector<double> disc((size_t)maxq + 2);
-    for (size_t i = 0; i < disc.size(); i++) disc[i] = ca_discount((int)i);
+    const std::vector<double> disc = discount_table(std::max(c->tr.maxq, c->has_valid ? c->va.maxq : 0));
     RL_HIP(c->buf.alloc(&c->d_disc, disc.size()));
     RL_HIP(hipMemcpy(c->d_disc, disc.data(), disc.size() * sizeof(double), hipMemcpyHostToDevice));
-    std::map<int64_t, double> cache;
-    auto preload = [&](CaSet &d, int64_t anon_base) {
-        for (int q = 0; q < d.Q && !d.ext_ideal.empty(); q++)
-            if (d.ext_ideal[q] == d.ext_ideal[q]) cache[d.has_key ? (int64_t)d.qkey[q] : anon_base + q] = d.ext_ideal[q];
-    };
-    preload(c->tr, (int64_t)1 << 40);
-    if (c->has_valid) preload(c->va, (int64_t)1 << 41);
-    const std::map<int64_t, double> external = cache;
-    auto run = [&](CaSet &d, int64_t anon_base, std::vector<double> &cached) {
-        cached.resize(d.Q);
-        for (int q = 0; q < d.Q; q++) {
-            const int n = d.qoff[q + 1] - d.qoff[q];
-            const int size = (c->metric_k > n || c->metric_k <= 0) ? n : c->metric_k;
-            const int64_t key = d.has_key ? (int64_t)d.qkey[q] : anon_base + q;
-            { auto pre = external.find(key); if (pre != external.end()) { cached[q] = pre->second; continue; } }
-            auto it = cache.find(key);
-            if (it == cache.end()) it = cache.emplace(key, ca_ideal_dcg(d.labels.data() + d.qoff[q], n, size, disc)).first;
-            cached[q] = it->second;
-        }
-    };
-    std::vector<double> ideal;
-    run(c->tr, (int64_t)1 << 40, ideal);
-    int rc = ca_upload(c, c->tr, ideal);
+    const int k = c->metric_k;
+    std::vector<double> ideal[2];
+    ideal_cache(c->tr, c->has_valid ? &c->va : nullptr, disc, [k](int n) { return (k > n || k <= 0) ? n : k; }, ideal);
+    int rc = ca_upload(c, c->tr, ideal[0]);
     if (rc) return rc;
-    if (c->has_valid) {
-        run(c->va, (int64_t)1 << 41, ideal);
-        rc = ca_upload(c, c->va, ideal);
-        if (rc) return rc;
-    }
+    if (c->has_valid && (rc = ca_upload(c, c->va, ideal[1]))) return rc;
     RL_HIP(c->buf.alloc(&c->d_m, (size_t)std::max(c->tr.Q, c->has_valid ? c->va.Q : 0) * kCaSteps));
     RL_HIP(c->buf.alloc(&c->d_sums, (size_t)kCaSteps));
     RL_HIP(c->buf.alloc(&c->d_done, 1));
@@ -280,13 +218,9 @@ static int lin_finish(LinCtx *c, const LinModel &m)
 // rl_*_predict after the entry point's own argument checks: out[i] = the model's score of row i of X (m: host pointers)
 static int lin_predict(int32_t device, const LinModel &m, const float *X, int64_t n_docs, int32_t row_stride, double *out)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    if (n_docs == 0) return RL_OK;
-    RL_HIP(hipSetDevice(device));
-    CaBuf buf;
+    const int gate = open_device(device, false);      // prediction has never tested the architecture
+    if (gate || n_docs == 0) return gate;
+    DevPool buf;
     float *dX = nullptr; int32_t *dF = nullptr; double *dT = nullptr, *dW = nullptr, *dO = nullptr;
     RL_HIP(buf.alloc(&dX, (size_t)n_docs * row_stride));
     RL_HIP(buf.alloc(&dF, (size_t)m.nt));
@@ -310,15 +244,8 @@ static int lin_create(LinCtx *c, const char *name, int32_t metric, int32_t metri
 {
     if (metric < RL_METRIC_NDCG || metric > RL_METRIC_RR)
         return fail(RL_ERR_UNSUPPORTED, std::string(name) + " train metric must be NDCG, DCG, MAP, ERR, P or RR (BEST is not built for training)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    RL_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(RL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", librlhip is built for gfx950 only");
+    const int gate = open_device(device, true);
+    if (gate) return gate;
     if (!(err_max > 0.0) || !std::isfinite(err_max)) return fail(RL_ERR_INVALID, "err_max (ERRScorer.MAX) must be positive and finite");
     c->metric = metric; c->metric_k = metric_k; c->device = device; c->err_max = err_max;
     RL_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -365,14 +292,9 @@ static int lin_set_external_judgments(LinCtx *c, const char *api, int32_t valida
     if (!c) return fail(RL_ERR_INVALID, "null handle");
     if (c->uploaded) return fail(RL_ERR_STATE, std::string(api) + "set_external_judgments after " + api + "learn");
     if (validation ? !c->has_valid : !c->has_train) return fail(RL_ERR_STATE, "set the data first");
-    CaSet &d = validation ? c->va : c->tr;
-    d.ext_ideal.clear(); d.ext_rd.clear();
-    if (ideal_dcg) d.ext_ideal.assign(ideal_dcg, ideal_dcg + d.Q);
-    if (rel_doc_count) {
-        for (int q = 0; q < d.Q; q++) if (rel_doc_count[q] < 0) return fail(RL_ERR_INVALID, "negative relevant-document count");
-        d.ext_rd.assign(rel_doc_count, rel_doc_count + d.Q);
-    }
-    return RL_OK;
+    std::string err;
+    const int rc = (validation ? c->va : c->tr).set_external(ideal_dcg, rel_doc_count, err);
+    return rc ? fail(rc, err) : RL_OK;
 }
 
 // the guards of rl_*_learn; leaves the handle's device current

@@ -244,12 +244,10 @@ int rl_model_from_text(const char *text, int32_t device, rl_model **out)
     std::unique_ptr<rl_model> m(new rl_model());
     std::string err;
     if (!model_from_text(text, m->trees, err)) return fail(RL_ERR_INVALID, "Error in Emsemble(xmlRepresentation): " + err);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
+    const int gate = open_device(device, false);      // after the text is parsed; a model has never tested the architecture
+    if (gate) return gate;
     m->device = device;
     m->knobs.read();
-    RL_HIP(hipSetDevice(device));
     std::map<int32_t, int> fids;
     for (auto &t : m->trees) { m->maxn = std::max(m->maxn, t.n_nodes); for (int f : t.feature) if (f != -1) fids[f] = 0; }
     for (auto &kv : fids) m->features.push_back(kv.first);

@@ -196,7 +196,7 @@ struct rl_net {
     int32_t device = 0, F = 0, L = 0, nw = 0, maxw = 0;
     int32_t nacc = 0;                  // k_net_forward's instantiation; 0: k_net_forward_global
     int32_t off_fid = 0, off_a = 0, off_b = 0; size_t lds_bytes = 0;
-    rl::CaBuf buf;
+    rl::DevPool buf;
     int32_t *d_fid = nullptr, *d_dims = nullptr; double *d_w = nullptr, *d_scratch = nullptr;
     int32_t last_path = RL_NET_PATH_NONE;
 };
@@ -253,15 +253,8 @@ int rl_net_create(int32_t device, const int32_t *feature_ids, int32_t n_features
     if (need != (int64_t)n_weights)
         return fail(RL_ERR_INVALID, "n_weights is " + std::to_string(n_weights) + ", the network has " + std::to_string(need) +
                                     " (for every layer n_l * (n_{l-1} + 1))");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    RL_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(RL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", librlhip is built for gfx950 only");
+    const int gate = open_device(device, true);
+    if (gate) return gate;
     std::unique_ptr<rl_net> h(new rl_net());
     h->device = device; h->F = n_features; h->L = n_hidden + 1; h->nw = n_weights; h->maxw = maxw;
     net_plan(h.get(), dims);
@@ -318,7 +311,7 @@ int rl_net_predict(rl_net *net, const float *X, int64_t n_docs, int32_t row_stri
     if (n_docs == 0) return RL_OK;
     if (!X || !out) return fail(RL_ERR_INVALID, "null argument");
     RL_HIP(hipSetDevice(net->device));
-    CaBuf buf;
+    DevPool buf;
     float *dX = nullptr; double *dO = nullptr;
     RL_HIP(buf.alloc(&dX, (size_t)n_docs * row_stride));
     RL_HIP(buf.alloc(&dO, (size_t)n_docs));

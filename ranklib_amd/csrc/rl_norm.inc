@@ -1,5 +1,5 @@
 // rl_norm.inc -- feature normalisation (-norm sum | zscore | linear) of every ranked list of a file in one pass on gfx950.  DESIGN.md 20.
-// Included by rl_ca.hip's unit (it shares CaBuf and perm_device).  Built with -ffp-contract=off like the rest.  No CPU fallback.
+// Included by rl_ca.hip's unit.  Built with -ffp-contract=off like the rest.  No CPU fallback.
 //
 //   k_normalize_lists   one lane owns one (list, requested column) pair and walks the list's documents in order, as the Java's loops over
 //                       rl.get(i) do (features/SumNormalizor.java, ZScoreNormalizor.java, LinearNormalizer.java): two passes for sum and
@@ -122,12 +122,7 @@ static int nm_check(int32_t kind, const float *X, int64_t n_docs, int32_t stride
     if (kind < RL_NORM_SUM || kind > RL_NORM_LINEAR) return bad("unknown normaliser " + std::to_string(kind));
     if (n_docs < 1 || n_lists < 1 || n_cols < 1 || times < 1) return bad("n_docs, n_lists, n_cols and times must be >= 1");
     if (stride < 2) return bad("stride must be >= 2 (column 0 is never a feature)");
-    if (qoff[0] != 0) return bad("qoff must start at 0");
-    for (int32_t q = 0; q < n_lists; q++) {
-        if (qoff[q + 1] <= qoff[q]) return bad("qoff must be strictly increasing (empty ranked list " + std::to_string(q) + ")");
-        if ((int64_t)qoff[q + 1] > n_docs) return bad("qoff must end at n_docs (list " + std::to_string(q) + " runs past it)");
-    }
-    if ((int64_t)qoff[n_lists] != n_docs) return bad("qoff must end at n_docs");
+    if (const int rc = check_lists("rl_normalize_lists", nullptr, n_docs, qoff, n_lists, err)) return rc;      // no labels here: the qoff rules alone
     std::vector<char> seen((size_t)stride, 0);
     int32_t maxcol = 0;
     for (int32_t j = 0; j < n_cols; j++) {
@@ -164,12 +159,12 @@ int rl_normalize_lists(int32_t device, int32_t kind, float *X, int64_t n_docs, i
     std::string err;
     int rc = nm_check(kind, X, n_docs, stride, row_len, qoff, n_lists, cols, n_cols, times, err);
     if (rc) return fail(rc, err);
-    if ((rc = perm_device(device))) return rc;
+    if ((rc = open_device(device, true))) return rc;
     const int64_t n_pairs = (int64_t)n_lists * n_cols;
     const int64_t n_blocks = (n_pairs + kThreads - 1) / kThreads;
     if (n_blocks > (int64_t)2147483647) return fail(RL_ERR_UNSUPPORTED, "rl_normalize_lists: more than 2^31 blocks of (list, column) pairs");
     const size_t cells = (size_t)n_docs * (size_t)stride;
-    CaBuf buf;
+    DevPool buf;
     NmArgs a;
     memset(&a, 0, sizeof(a));
     int32_t *d_qoff = nullptr, *d_cols = nullptr;

@@ -106,20 +106,6 @@ static double perm_mean(const double *v, int n)
     return mean / n;
 }
 
-static int perm_device(int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    RL_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(RL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", librlhip is built for gfx950 only");
-    return RL_OK;
-}
-
 static double perm_next_double(JavaRandom &r)
 {   // Random.nextDouble: (((long) next(26) << 27) + next(27)) * 0x1.0p-53
     const int64_t hi = (int64_t)r.next(26) << 27;
@@ -166,12 +152,12 @@ int rl_perm_test(int device, const double *base, const double *targets, int n, i
     const int64_t D2 = 2 * ((int64_t)(n / 10) + 1);
     if (perm_begin > INT64_MAX - perm_count || perm_begin + perm_count > INT64_MAX / D2)
         return fail(RL_ERR_INVALID, "rl_perm_test: (perm_begin + perm_count) * 2 * (n / 10 + 1) LCG steps overflow 63 bits");
-    int rc = perm_device(device);
+    int rc = open_device(device, true);
     if (rc) return rc;
     std::vector<double> td((size_t)n_targets);
     const double mb = perm_mean(base, n);
     for (int k = 0; k < n_targets; k++) td[k] = std::fabs(mb - perm_mean(targets + (size_t)k * n, n));
-    CaBuf buf;
+    DevPool buf;
     double *d_b = nullptr, *d_t = nullptr, *d_td = nullptr, *d_pd = nullptr; unsigned long long *d_cnt = nullptr;
     RL_HIP(buf.alloc(&d_b, (size_t)n));
     RL_HIP(buf.alloc(&d_t, (size_t)n * n_targets));
@@ -207,9 +193,9 @@ int rl_debug_perm_calib(int device, const double *base, const double *target, in
         *host_count = perm_host_literal(base, target, n, seed, perm_count, trueDiff);
         *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    int rc = perm_device(device);
+    int rc = open_device(device, true);
     if (rc) return rc;
-    CaBuf buf;
+    DevPool buf;
     double *d_io = nullptr;
     RL_HIP(buf.alloc(&d_io, (size_t)2 * kWave));
     std::vector<double> io((size_t)2 * kWave, 1.0);

@@ -16,6 +16,7 @@
 #include <memory>
 
 #include "rl_internal.h"
+#include "rl_lists_host.h"
 #include "rl_knobs.h"
 #include "rl_device.h"
 #include "rl_wave.h"
@@ -38,39 +39,19 @@ static double g_err_max = 16.0;      // ERRScorer.MAX: a process-wide static in 
 void set_error(const std::string &msg) { g_err = msg; }
 int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
-struct DevPool {
-    std::vector<void *> ptrs;
-    template <typename T> hipError_t alloc(T **p, size_t n)
-    {
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) { ptrs.push_back(q); *p = (T *)q; }
-        return e;
-    }
-    void release(void *p)
-    {
-        for (auto &q : ptrs) if (q == p) { (void)hipFree(q); q = nullptr; }
-    }
-    ~DevPool() { for (void *q : ptrs) if (q) (void)hipFree(q); }
-};
-
-struct DataSet {
-    int64_t N = 0; int32_t Q = 0;
-    std::vector<float> labels; std::vector<int32_t> qoff, qkey; bool has_key = false;
+struct DataSet : ListSetHost {     // the host side (labels, qoff, qkey, the -qrel tables of rl_set_external_judgments): rl_lists_host.h
     float *d_X = nullptr;          // row-major rows [N][F]
     int64_t rows_next = -1;        // chunked upload (rl_set_rows): next row expected; -1 = the rows came with rl_set_train / rl_set_validation
     float *d_labels = nullptr; int32_t *d_qoff = nullptr; double *d_ideal0 = nullptr, *d_ideal1 = nullptr;
     double *d_scores = nullptr, *d_ndcg = nullptr;
     double *d_ss = nullptr; float *d_sl = nullptr; int32_t *d_srel = nullptr, *d_sidx = nullptr, *d_docq = nullptr;   // ranked order (training set only)
     int32_t *d_aux_i = nullptr; double *d_aux_a = nullptr, *d_aux_b = nullptr;   // swapChange tables of MAP / ERR in ranked order
-    // -qrel (rl_set_external_judgments): per list, the idealGains entry of its qid in the judgment file (NaN = none) and its relDocCount
-    std::vector<double> ext_ideal; std::vector<int32_t> ext_rd; int32_t *d_ext_rd = nullptr;
+    int32_t *d_ext_rd = nullptr;   // ext_rd on the device (null: none given)
     int32_t *d_qsmall = nullptr, *d_qbig = nullptr, *d_qtiny = nullptr; int32_t n_small = 0, n_big = 0, n_tiny = 0, max_big = 0, n_small_long = 0; bool all_small = false;
     int32_t *d_qhuge = nullptr, *d_relscratch = nullptr; int32_t n_huge = 0;      // lists beyond kLambdaBlockCap documents (k_rank_huge)
     // queries by length class for the fused lambda kernel: <= 64, <= 128, <= 192 documents, longer (tiled by 256); a block is as
     // wide as its class, so short lists do not leave most of a block idle
     int32_t *d_qcls[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; int32_t n_qcls[5] = {0, 0, 0, 0, 0};     // [4]: <= 16 documents (k_lambda_tiny)
-    int32_t maxq = 0;
 };
 
 struct TimingSlot { double ms = 0; int64_t launches = 0; double bytes = 0; };
@@ -161,46 +142,20 @@ namespace rl {
 
 static int check_trainer(const rl_trainer *t) { return t ? RL_OK : fail(RL_ERR_INVALID, "null trainer handle"); }
 
-// ---- host-side NDCG constants ------------------------------------------------------------------
-static double discount_of(int i) { return 1.0 / (std::log((double)(i + 2)) / std::log(2.0)); }   // DCGScorer.java:26
-
-static double ideal_dcg(const float *labels, int n, int topk, const std::vector<double> &disc)
-{   // NDCGScorer.getIdealDCG (:167-174)
-    std::vector<int> rel(n);
-    for (int i = 0; i < n; i++) rel[i] = (int)labels[i];
-    std::sort(rel.begin(), rel.end(), [](int a, int b) { return a > b; });
-    double dcg = 0;
-    for (int i = 0; i < topk; i++) dcg += (double)(int32_t)(((uint32_t)1 << (rel[i] & 31)) - 1u) * disc[i];      // Java int arithmetic (DCGScorer.java:137-139)
-    return dcg;
-}
-
 static int validate_dataset(const float *X, int64_t n, int32_t F, const float *labels, const int32_t *qoff, int32_t Q)
 {
     if (!labels || !qoff) return fail(RL_ERR_INVALID, "null data pointer");       // X == NULL: the rows follow through rl_set_rows
     if (n <= 0 || Q <= 0 || F <= 0) return fail(RL_ERR_INVALID, "There are no training samples / features");
     if (n >= (int64_t)2147483647 - 4096) return fail(RL_ERR_UNSUPPORTED, "more than 2^31 documents per GPU");
-    if (qoff[0] != 0 || (int64_t)qoff[Q] != n) return fail(RL_ERR_INVALID, "qoff must start at 0 and end at n_docs");
-    for (int32_t q = 0; q < Q; q++)
-        if (qoff[q + 1] <= qoff[q]) return fail(RL_ERR_INVALID, "qoff must be strictly increasing (empty ranked list)");
-    for (int64_t i = 0; i < n; i++) {
-        if (!(labels[i] >= 0)) return fail(RL_ERR_INVALID, "Relevance label cannot be negative. System will now exit.");  // DataPoint.java:71-73
-        // labels above 30 are legal: the gain (1 << l) - 1 wraps as Java ints do (gain_of).  The Java keeps a gain cache of l + 10 doubles
-        // (DCGScorer.java:131-140), so a label near 2^31 ends in an OutOfMemoryError there; the line is drawn where (int)label is exact
-        if (labels[i] >= 16777216.f) return fail(RL_ERR_UNSUPPORTED, "relevance label of 2^24 or more");
-    }
-    return RL_OK;
+    std::string err;
+    const int rc = check_lists("", labels, n, qoff, Q, err);
+    return rc ? fail(rc, err) : RL_OK;
 }
 
 static int load_dataset(rl_trainer *t, DataSet &d, const float *X, int64_t n, const float *labels, const int32_t *qoff,
                         int32_t Q, const int32_t *qkey)
 {
-    d.N = n; d.Q = Q;
-    d.labels.assign(labels, labels + n);
-    d.qoff.assign(qoff, qoff + Q + 1);
-    d.has_key = qkey != nullptr;
-    if (qkey) d.qkey.assign(qkey, qkey + Q); else d.qkey.clear();
-    d.maxq = 0;
-    for (int32_t q = 0; q < Q; q++) d.maxq = std::max(d.maxq, qoff[q + 1] - qoff[q]);
+    d.store(labels, n, qoff, Q, qkey);
     RL_HIP(t->pool.alloc(&d.d_X, (size_t)n * t->F));
     if (X) { RL_HIP(hipMemcpy(d.d_X, X, (size_t)n * t->F * sizeof(float), hipMemcpyHostToDevice)); d.rows_next = -1; }
     else d.rows_next = 0;
@@ -843,14 +798,9 @@ int rl_set_external_judgments(rl_trainer *t, int32_t validation, const double *i
     if (check_trainer(t)) return RL_ERR_INVALID;
     if (t->inited) return fail(RL_ERR_STATE, "rl_set_external_judgments must be called before rl_init");
     if (validation ? !t->has_valid : !t->has_train) return fail(RL_ERR_STATE, "set the data first");
-    DataSet &d = validation ? t->va : t->tr;
-    d.ext_ideal.clear(); d.ext_rd.clear();
-    if (ideal_dcg) d.ext_ideal.assign(ideal_dcg, ideal_dcg + d.Q);
-    if (rel_doc_count) {
-        for (int q = 0; q < d.Q; q++) if (rel_doc_count[q] < 0) return fail(RL_ERR_INVALID, "negative relevant-document count");
-        d.ext_rd.assign(rel_doc_count, rel_doc_count + d.Q);
-    }
-    return RL_OK;
+    std::string err;
+    const int rc = (validation ? t->va : t->tr).set_external(ideal_dcg, rel_doc_count, err);
+    return rc ? fail(rc, err) : RL_OK;
 }
 
 int rl_set_err_max(double max_gain)
@@ -880,15 +830,8 @@ int rl_create(const rl_params *p, rl_trainer **out)
         return fail(RL_ERR_INVALID, "RL_FLAG_FAST_LEAF with RL_FLAG_JAVA_ORDER: the strict mode is a parity instrument, its leaves are the Java's float running sums");
     if ((p->flags & RL_FLAG_FAST_LEAF) && (p->flags & RL_FLAG_SERIAL_CHAIN))
         return fail(RL_ERR_INVALID, "RL_FLAG_FAST_LEAF with RL_FLAG_SERIAL_CHAIN: the serial kernel evaluates the float running sums that the fast mode replaces");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RL_ERR_NO_DEVICE, "no HIP device visible: librlhip has no CPU fallback");
-    if (p->device < 0 || p->device >= ndev) return fail(RL_ERR_INVALID, "device ordinal out of range");
-    RL_HIP(hipSetDevice(p->device));
-    hipDeviceProp_t prop;
-    RL_HIP(hipGetDeviceProperties(&prop, p->device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail(RL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", librlhip is built for gfx950 only");
+    const int gate = open_device(p->device, true);
+    if (gate) return gate;
     std::unique_ptr<rl_trainer> t(new rl_trainer());
     t->p = *p;
     t->knobs.read();

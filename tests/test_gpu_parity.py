@@ -718,6 +718,19 @@ def test_bad_inputs_are_rejected_with_ranklib_style_errors():
 
 
 @pytest.mark.gpu
+def test_list_errors_name_the_list_in_every_trainer():
+    """the list rules are stated once (check_lists, rl_lists_host.h): the tree trainer and the linear handles refuse a bad qoff in the
+    words rl_eval_lists uses, with the offending list"""
+    X, lab, qoff = make(200, 3, "ns", 9)
+    for new in (lambda: N.Trainer(n_trees=1, n_leaves=4), lambda: N.CoorAscentTrainer(n_restart=1, n_max_iteration=1)):
+        t = new()
+        with pytest.raises(N.RankLibError, match="empty ranked list 1"):
+            t.set_train(X, lab, np.array([0, 100, 50, 200], np.int32))
+        with pytest.raises(N.RankLibError, match="qoff must end at n_docs"):
+            t.set_train(X, lab, np.array([0, 100, 150], np.int32))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["sparse", "dense", "rows"])
 def test_sparse_700_feature_shape_matches_the_oracle(mode, monkeypatch):
     """Yahoo-set1 shape (BASELINE.json configs[3]) in small: 700 columns, 175 of them all zero (one threshold + MAX_VALUE,
