@@ -6,6 +6,10 @@ One synthetic set serves every case: list lengths on both sides of every length 
 the cases use, one list of 600 documents (three tiles, two sweeps), labels 0 .. 4 with one in ten set to 0.5 (relevant as label > 0.0, non-relevant
 as (int) label == 0: ReciprocalRankScorer.java:75,85), every fourth list with few relevant documents (RR without a firstRank or a secondRank).  The restatement's rounds are computed once per (ranker, metric, k) and shared.
 
+The same rounds are compared under every mode of the trainer that touches these metrics: the ranking and stream knobs (RLHIP_RANK_SPLIT,
+RLHIP_TINY_MIN, RLHIP_LAMBDA_SIDE, RLHIP_LAMBDA_COMPACT, RLHIP_LAMBDA_UNFUSED), RL_FLAG_JAVA_ORDER, RL_FLAG_FIRST_TIE, RL_FLAG_FAST_LEAF, MART, two
+and three shards.  tests/test_gpu_tree_pr_branches.py reuses the comparison on data that reaches the swap changes' cases one by one.
+
 No case may pass vacuously: in every compared round the restatement gives a non-zero lambda to at least a quarter of the documents and every tree
 has a split (asserted where the restatement's rounds are recorded)."""
 import functools
@@ -15,11 +19,14 @@ import numpy as np
 import pytest
 
 import np_restatement as R
+import pr_cases
 import test_gpu_dist as TD
+import test_gpu_fast_leaf as TF
 from pr_restatement import P, RR
 from ranklib_amd import _native as N
 from ranklib_amd import evaluator
 from ranklib_amd.learning import FeatureHistogram, LambdaMART, RankerFactory, RFRanker, Sampler
+from tree_equiv import assert_equivalent
 
 pytestmark = pytest.mark.gpu
 
@@ -87,7 +94,8 @@ def flat(root):
     return np.array(feat, np.int32), np.array(thr, np.float32), np.array(out, np.float32), np.array(cnt, np.int64)
 
 
-def _restatement(ranker, metric, k, rounds, leaves, early_stop, train, valid):
+def _restatement(ranker, metric, k, rounds, leaves, early_stop, train, valid, cases=None):
+    """cases: names of tests/pr_cases.py that the lists, in the ranked order every round makes its lambdas in, have to reach"""
     X, lab, qoff = train
     m = R.LambdaMART(X, lab, qoff, n_trees=rounds, n_leaves=leaves, k=k, early_stop=early_stop, metric="NDCG", ranker=ranker)
     m.scorer = SCORERS[metric](k)
@@ -96,12 +104,15 @@ def _restatement(ranker, metric, k, rounds, leaves, early_stop, train, valid):
     m.init()
     recs = []
     for r in range(rounds):
+        if cases is not None:
+            got = pr_cases.reached(metric, k, lab, qoff, m.model_scores)
+            assert got >= cases, (metric, k, r, sorted(cases - got))
         root, tm, vm, stop = m.round()
         lam, w = np.array(m.pseudo, np.float64), np.array(m.weights, np.float64)
         # not vacuous: a quarter of the documents carry a lambda, the tree has a split
         assert np.count_nonzero(lam) >= len(lam) / 4, (ranker, metric, k, r, np.count_nonzero(lam), len(lam))
         assert root.feature_id != -1, (ranker, metric, k, r)
-        recs.append(dict(tree=flat(root), lam=lam, w=w, tm=np.float32(tm), vm=None if vm is None else np.float32(vm), stop=bool(stop),
+        recs.append(dict(root=root, tree=flat(root), lam=lam, w=w, tm=np.float32(tm), vm=None if vm is None else np.float32(vm), stop=bool(stop),
                          score=np.array(m.model_scores, np.float64)))
         if stop:
             break
@@ -126,20 +137,11 @@ def reference(ranker, metric, k):
     return _restatement(ranker, metric, k, ROUNDS, LEAVES, 100, train, valid)
 
 
-def run_gpu(ranker, metric, k, monkeypatch, env=None):
-    """the GPU trainer against reference(ranker, metric, k), round by round; returns the launch arms"""
-    for name, v in (env or {}).items():
-        monkeypatch.setenv("RLHIP_" + name, str(v))
-    ref = reference(ranker, metric, k)
-    mart = ranker == "MART"
-    (X, lab, qoff), valid = data()[0], data()[2 if mart else 1]
-    g = N.Trainer(n_trees=10 if mart else ROUNDS, n_leaves=LEAVES, metric=metric, metric_k=k, ranker=ranker, early_stop_rounds=1 if mart else 100)
-    g.set_train(X, lab, qoff)
-    g.set_validation(*valid)
-    g.init()
+def compare(g, ref, ctx0):
+    """an initialised trainer against recorded rounds of the restatement, round by round; returns the launch arms and closes the trainer"""
     for r, want in enumerate(ref["rounds"]):
         tg, tm, vm, stop = g.boost_round()
-        ctx = (ranker, metric, k, env, r)
+        ctx = ctx0 + (r,)
         assert np.array_equal(bits(g.array("LAMBDA"), np.int64), bits(want["lam"], np.int64)), ctx
         assert np.array_equal(bits(g.array("WEIGHT"), np.int64), bits(want["w"], np.int64)), ctx
         t = tg.trimmed()
@@ -150,14 +152,30 @@ def run_gpu(ranker, metric, k, monkeypatch, env=None):
         assert np.array_equal(np.asarray(t["count"], np.int64), cnt), ctx
         assert np.array_equal(bits(g.array("SCORE"), np.int64), bits(want["score"], np.int64)), ctx
         assert bits(np.float32(tm), np.uint32) == bits(want["tm"], np.uint32), (ctx, tm, want["tm"])
-        assert bits(np.float32(vm), np.uint32) == bits(want["vm"], np.uint32), (ctx, vm, want["vm"])
+        assert (vm is None) == (want["vm"] is None), ctx
+        if vm is not None:
+            assert bits(np.float32(vm), np.uint32) == bits(want["vm"], np.uint32), (ctx, vm, want["vm"])
         assert stop == want["stop"], ctx
     ts, vs = g.finish()
-    assert ts == ref["fin"] and vs == ref["vfin"], (ranker, metric, k, ts, ref["fin"], vs, ref["vfin"])
+    assert ts == ref["fin"] and vs == ref["vfin"], (ctx0, ts, ref["fin"], vs, ref["vfin"])
     assert g.num_trees() == ref["kept"]
     arms = g.array("LAUNCH_ARMS")
     g.close()
     return arms
+
+
+def run_gpu(ranker, metric, k, monkeypatch, env=None, flags=0):
+    """the GPU trainer against reference(ranker, metric, k), round by round; returns the launch arms"""
+    for name, v in (env or {}).items():
+        monkeypatch.setenv("RLHIP_" + name, str(v))
+    ref = reference(ranker, metric, k)
+    mart = ranker == "MART"
+    (X, lab, qoff), valid = data()[0], data()[2 if mart else 1]
+    g = N.Trainer(n_trees=10 if mart else ROUNDS, n_leaves=LEAVES, metric=metric, metric_k=k, ranker=ranker, early_stop_rounds=1 if mart else 100, flags=flags)
+    g.set_train(X, lab, qoff)
+    g.set_validation(*valid)
+    g.init()
+    return compare(g, ref, (ranker, metric, k, env, flags))
 
 
 def _fused_only(arms, rounds=ROUNDS):
@@ -169,7 +187,7 @@ def _fused_only(arms, rounds=ROUNDS):
 
 # ---- LambdaMART, one GPU ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("metric", ["P", "RR"])
-@pytest.mark.parametrize("k", [1, 3, 10, 16, 20])
+@pytest.mark.parametrize("k", [1, 3, 10, 16, 17, 20])
 def test_lambdamart_equals_the_restatement(metric, k, monkeypatch):
     arms = run_gpu("LAMBDAMART", metric, k, monkeypatch)
     if k <= 16:
@@ -195,6 +213,123 @@ def test_tiny_lists_in_their_own_launches(metric, monkeypatch):
     assert arms[ARM["LAM_ON_MAIN"]] + arms[ARM["LAM_ON_SIDE"]] == 5 * ROUNDS       # five length classes hold lists
 
 
+# ---- modes of the trainer: other rank kernels, other streams, the flags -------------------------------------------------------------------------
+def _rank_arms(arms):
+    return {a: int(arms[ARM[a]]) for a in ("RANK_TINY", "RANK_MIXED", "RANK_WAVE_LONG", "RANK_WAVE_SHORT", "RANK_BLOCK", "RANK_HUGE") if arms[ARM[a]]}
+
+
+# data(): lists in four length classes (64 | 128 | 192 | 256 wide), five with the lists of at most 16 documents apart; none beyond 5 000 documents
+MODES = [
+    ("RANK_SPLIT", {"RANK_SPLIT": 1}, lambda a: set(_rank_arms(a)) == {"RANK_WAVE_SHORT", "RANK_BLOCK"}),
+    ("RANK_SPLIT,TINY_MIN=1", {"RANK_SPLIT": 1, "TINY_MIN": 1},
+     lambda a: (set(_rank_arms(a)) == {"RANK_TINY", "RANK_WAVE_SHORT", "RANK_BLOCK"}
+                and a[ARM["LAM_ON_SIDE"]] == ROUNDS and a[ARM["LAM_ON_MAIN"]] == 4 * ROUNDS)),
+    ("LAMBDA_SIDE=0", {"LAMBDA_SIDE": 0}, lambda a: a[ARM["LAM_ON_SIDE"]] == 0 and a[ARM["LAM_ON_MAIN"]] == 4 * ROUNDS),
+    ("LAMBDA_SIDE=1", {}, lambda a: a[ARM["LAM_ON_SIDE"]] == ROUNDS and a[ARM["LAM_ON_MAIN"]] == 3 * ROUNDS and "RANK_MIXED" in _rank_arms(a)),
+    ("LAMBDA_SIDE=2", {"LAMBDA_SIDE": 2}, lambda a: a[ARM["LAM_ON_SIDE"]] == 2 * ROUNDS and a[ARM["LAM_ON_MAIN"]] == 2 * ROUNDS),
+    ("LAMBDA_SIDE=3", {"LAMBDA_SIDE": 3}, lambda a: a[ARM["LAM_ON_SIDE"]] == 3 * ROUNDS and a[ARM["LAM_ON_MAIN"]] == ROUNDS),
+    ("LAMBDA_COMPACT", {"LAMBDA_COMPACT": 1}, lambda a: a[ARM["LAM_ON_SIDE"]] == ROUNDS and a[ARM["LAM_ON_MAIN"]] == 3 * ROUNDS),      # NDCG's and DCG's: nothing may change
+]
+
+
+@pytest.mark.parametrize("metric", ["P", "RR"])
+@pytest.mark.parametrize("name,env,check", MODES, ids=[m[0] for m in MODES])
+def test_ranking_and_stream_knobs_keep_every_bit(name, env, check, metric, monkeypatch):
+    arms = run_gpu("LAMBDAMART", metric, 10, monkeypatch, env)
+    _fused_only(arms)                                                    # (LAM_COMPACT == 0 among them)
+    assert check(arms), (name, _rank_arms(arms), int(arms[ARM["LAM_ON_SIDE"]]), int(arms[ARM["LAM_ON_MAIN"]]))
+
+
+def test_rank_split_writes_first_and_second_for_the_pair_term_matrix(monkeypatch):
+    """RR@20 is unfused: swap_change_abs reads firstRank / secondRank from the table k_rank_wave and k_rank_block wrote"""
+    arms = run_gpu("LAMBDAMART", "RR", 20, monkeypatch, {"RANK_SPLIT": 1})
+    assert arms[ARM["LAM_UNFUSED"]] == ROUNDS and arms[ARM["LAM_ON_MAIN"]] + arms[ARM["LAM_ON_SIDE"]] == 0
+    assert set(_rank_arms(arms)) == {"RANK_WAVE_SHORT", "RANK_BLOCK"}
+
+
+@pytest.mark.parametrize("metric", ["P", "RR"])
+def test_java_order_flag(metric, monkeypatch):
+    """RL_FLAG_JAVA_ORDER, the strict mode: split gains from the f64 histogram RankLib itself would hold; everything as in the default mode"""
+    _fused_only(run_gpu("LAMBDAMART", metric, 10, monkeypatch, flags=N.RL_FLAG_JAVA_ORDER))
+
+
+class _RefTree:
+    """a restatement tree with the interface tree_equiv.assert_equivalent reads"""
+    def __init__(self, root):
+        feat, thr, out, cnt = flat(root)
+        left, right = np.full(len(feat), -1, np.int32), np.full(len(feat), -1, np.int32)
+        stack = []                                                       # pre-order: the left child follows its parent, the right one the left subtree
+        for i in range(len(feat)):
+            if stack:
+                p = stack.pop()
+                (left if left[p] == -1 else right)[p] = i
+                if right[p] == -1:
+                    stack.append(p)
+            if feat[i] != -1:
+                stack.append(i)
+        self.n_nodes = len(feat)
+        self._t = dict(feature=feat, threshold=thr, left=left, right=right, output=out, count=cnt)
+
+    def trimmed(self):
+        return self._t
+
+
+def _trainer(metric, k, flags, valid=True):
+    (X, lab, qoff), v = data()[0], data()[1]
+    g = N.Trainer(n_trees=ROUNDS, n_leaves=LEAVES, metric=metric, metric_k=k, ranker="LAMBDAMART", early_stop_rounds=100, flags=flags)
+    g.set_train(X, lab, qoff)
+    if valid:
+        g.set_validation(*v)
+    g.init()
+    return g
+
+
+@pytest.mark.parametrize("metric", ["P", "RR"])
+def test_first_tie_flag(metric):
+    """RL_FLAG_FIRST_TIE: no tie is resolved the Java's way, so a stored (feature, threshold) may be another member of a tie; every tree is the
+    reference's function and partition on the training set (tests/tree_equiv.py) and the lambdas, weights, scores and train metric of every
+    round keep their bits.  Without a validation set: the other member of a tie may send a validation row the other way."""
+    ref = reference("LAMBDAMART", metric, 10)
+    X = data()[0][0]
+    g = _trainer(metric, 10, N.RL_FLAG_FIRST_TIE, valid=False)
+    for r, want in enumerate(ref["rounds"]):
+        tg, tm, _, stop = g.boost_round()
+        ctx = (metric, r)
+        assert np.array_equal(bits(g.array("LAMBDA"), np.int64), bits(want["lam"], np.int64)), ctx
+        assert np.array_equal(bits(g.array("WEIGHT"), np.int64), bits(want["w"], np.int64)), ctx
+        assert_equivalent(_RefTree(want["root"]), tg, X, ctx)
+        assert np.array_equal(bits(g.array("SCORE"), np.int64), bits(want["score"], np.int64)), ctx
+        assert bits(np.float32(tm), np.uint32) == bits(want["tm"], np.uint32), (ctx, tm, want["tm"])
+        assert not stop
+    assert g.array("TIE_STATS")[0] == 0                                  # no resolution ran
+    g.close()
+
+
+@pytest.mark.parametrize("metric", ["P", "RR"])
+def test_fast_leaf_flag(metric):
+    """RL_FLAG_FAST_LEAF: round 1 has the reference's lambdas, weights and tree with leaf outputs within 1e-5 of the reference's (the mode's stated
+    bound); every round is self-consistent as tests/test_gpu_fast_leaf.py has it (outputs are the restated f64 reduction of the
+    round's own lambdas and weights over the leaf's members, the scores move by them)"""
+    want = reference("LAMBDAMART", metric, 10)["rounds"][0]
+    X = data()[0][0]
+    g = _trainer(metric, 10, N.RL_FLAG_FAST_LEAF, valid=False)
+    prev = g.array("SCORE")
+    for r in range(ROUNDS):
+        tg, _, _, _ = g.boost_round()
+        rec = dict(tree=tg.trimmed(), lam=g.array("LAMBDA"), w=g.array("WEIGHT"), before=prev, after=g.array("SCORE"))
+        prev = rec["after"]
+        if r == 0:
+            feat, thr, out, cnt = want["tree"]
+            assert np.array_equal(bits(rec["lam"], np.int64), bits(want["lam"], np.int64))
+            assert np.array_equal(bits(rec["w"], np.int64), bits(want["w"], np.int64))
+            assert np.array_equal(rec["tree"]["feature"], feat) and np.array_equal(bits(rec["tree"]["threshold"], np.uint32), bits(thr, np.uint32))
+            assert np.array_equal(np.asarray(rec["tree"]["count"], np.int64), cnt)
+            assert np.max(np.abs(rec["tree"]["output"].astype(np.float64) - out.astype(np.float64))) <= 1e-5
+        assert np.count_nonzero(rec["lam"]) >= len(rec["lam"]) / 4 and rec["tree"]["feature"][0] != -1, (metric, r)
+        TF._check_round(X, rec, False, "%s round %d" % (metric, r + 1))
+    g.close()
+
+
 # ---- MART: the scorer only reports ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("metric", ["P", "RR"])
 def test_mart_with_validation_and_early_stop(metric, monkeypatch):
@@ -208,6 +343,11 @@ def test_mart_with_validation_and_early_stop(metric, monkeypatch):
 @pytest.mark.parametrize("metric", ["P", "RR"])
 def test_two_shards_equal_one(metric, tmp_path):
     TD.k_shards_against_one_shard(2, "LAMBDAMART", metric, 5, (6000, 16, "mslr", 5, 10, 3), tmp_path)
+
+
+@pytest.mark.parametrize("world,ranker,metric", [(2, "MART", "P"), (3, "LAMBDAMART", "RR")])
+def test_mart_sharded_and_three_shards(world, ranker, metric, tmp_path):
+    TD.k_shards_against_one_shard(world, ranker, metric, 5, (6000, 16, "mslr", 5, 10, 3), tmp_path)
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------------------------
