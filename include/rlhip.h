@@ -880,6 +880,40 @@ int  rl_model_eval_stages(rl_model *m, const float *X, int64_t n_docs, int32_t r
  * last rl_model_predict_stages / rl_model_eval_stages call, summed over its chunks */
 int  rl_debug_stage_times(double *walk_ms, double *rank_ms);
 
+/* ---- permutation feature importance of a tree model, one pass over a file --------------------------------------------
+ * A cell (c, r), c < n_columns, r < n_repeats, is column columns[c] under repeat r; donor [n_repeats][n_docs] holds document indices
+ * in [0, n_docs).  The permuted score of document i in cell (c, r) is Ensemble.eval's float chain (learning/tree/Ensemble.java:110-116,
+ * s = (float)((double)s + (double)out * (double)w), s_0 = 0.0f) on row i with the value of column columns[c] taken from row
+ * donor[r][i]; a column at or beyond row_stride reads 0 on both sides, so such a cell equals the base.  The base is the unpermuted
+ * scores (and their per-list values); it goes through the same kernels as one extra cell.  donor[r] need not be a permutation: any
+ * in-range map is legal, and the same donor[r] serves every column of repeat r.  columns may repeat and need no order.  X, labels,
+ * columns and donor are HOST pointers; rows, labels and tables are uploaded once per call.
+ * rl_model_predict_permuted: out [n_columns][n_repeats][n_docs], out_base [n_docs] (may be NULL).
+ * rl_model_eval_permuted: out_metric [n_columns][n_repeats][n_lists] is what rl_eval_lists returns for the cell's scores widened to f64
+ * -- all seven metrics, the stable descending rank with -0.0 tying 0.0, bit for bit what the materialised permuted matrix gives through
+ * rl_model_predict and rl_eval_lists; out_base [n_lists] likewise for the base.  A (cell, list) whose scores hold a NaN has out_nan
+ * (out_base_nan) = 1 and value 0.0 and is not ranked, exactly as rl_model_eval_stages treats a (stage, list).  The list arguments are
+ * rl_eval_lists' with its rules and error texts.  The cells are processed in chunks whose device scratch -- 4 bytes per document and
+ * cell, 16 where a list is longer than 6 144 documents -- stays within scratch_bytes (0 = 256 MiB); a chunk holds at least one cell.
+ * The result does not depend on the chunking.  Inside a chunk the kernel takes RL_PERMUTED_BATCH cells per document at a time.
+ * RL_ERR_INVALID, the message naming the argument: a null pointer, n_columns < 1, n_repeats < 1, a negative column, a donor entry
+ * outside [0, n_docs), row_stride < 1, scratch_bytes < 0, a model without trees (the model is looked at after the other arguments).
+ * rl_model_debug_path reports RL_MODEL_PATH_PERMUTED after either call: one kernel serves packed and unpacked models. */
+#ifndef RL_PERMUTED_BATCH
+#define RL_PERMUTED_BATCH 16
+#endif
+enum { RL_MODEL_PATH_PERMUTED = 3 };
+int  rl_model_predict_permuted(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *columns, int32_t n_columns,
+                               const int32_t *donor, int32_t n_repeats, float *out_base, float *out);
+int  rl_model_eval_permuted(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const float *labels, const int32_t *qoff,
+                            int32_t n_lists, const int32_t *qkey, const double *ideal_dcg, const int32_t *rel_doc_count, int32_t metric,
+                            int32_t k, double err_max, const int32_t *columns, int32_t n_columns, const int32_t *donor, int32_t n_repeats,
+                            int64_t scratch_bytes, double *out_base, uint8_t *out_base_nan, double *out_metric, uint8_t *out_nan,
+                            double *out_ideal);
+/* debug (tools/importance_bench.py): as rl_debug_stage_times, for this thread's last rl_model_predict_permuted / rl_model_eval_permuted
+ * call */
+int  rl_debug_permuted_times(double *walk_ms, double *rank_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,7 @@ ABI_SYMBOLS = [
     "rl_eval_lists", "rl_debug_eval_times",
     "rl_normalize_lists", "rl_debug_normalize_times",
     "rl_model_predict_stages", "rl_model_eval_stages", "rl_debug_stage_times",
+    "rl_model_predict_permuted", "rl_model_eval_permuted", "rl_debug_permuted_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -294,6 +295,10 @@ def lib():
         L.rl_model_predict_stages.argtypes = [vp, vp, i64, i32, vp, i32, vp]
         L.rl_model_eval_stages.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, i32, i64, vp, vp, vp]
         L.rl_debug_stage_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_eval_permuted"):  # (A/B builds of older sources score one permuted copy per cell)
+        L.rl_model_predict_permuted.argtypes = [vp, vp, i64, i32, vp, i32, vp, i32, vp, vp]
+        L.rl_model_eval_permuted.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, i32, vp, i32, i64, vp, vp, vp, vp, vp]
+        L.rl_debug_permuted_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -679,6 +684,8 @@ class Trainer:
 
 
 MODEL_PATH_NONE, MODEL_PATH_TILED, MODEL_PATH_GENERIC = 0, 1, 2
+MODEL_PATH_PERMUTED = 3             # rl_model_predict_permuted / rl_model_eval_permuted: one kernel for every model
+PERMUTED_BATCH = 16                 # RL_PERMUTED_BATCH (rlhip.h): cells k_model_permuted_scores takes per document at a time
 
 
 class Model:
@@ -761,6 +768,67 @@ class Model:
                                      ptr(idl), ptr(rdc), RL_EVAL_METRIC[m], int(k), float(err_max), st.ctypes.data, int(st.size),
                                      int(scratch_bytes), out.ctypes.data, nan.ctypes.data, ideal.ctypes.data))
         return out[:, :nl], nan[:, :nl], ideal[:nl]
+
+    @staticmethod
+    def _permuted_args(rows, columns, donor):
+        L = lib()
+        if not hasattr(L, "rl_model_eval_permuted"):
+            raise RankLibError("rlhip: this librlhip.so has no permuted evaluation (rl_model_eval_permuted)")
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        cols = np.ascontiguousarray(columns, dtype=np.int32)
+        don = np.ascontiguousarray(donor, dtype=np.int32)
+        if don.ndim == 1:
+            don = don[None, :]
+        if rows.ndim != 2 or cols.ndim != 1 or don.ndim != 2 or don.shape[1] != rows.shape[0]:
+            raise RankLibError("rlhip: permuted evaluation takes rows [n_docs][row_stride], columns [n_columns] and donor [n_repeats][n_docs]")
+        return L, rows, cols, np.ascontiguousarray(don)
+
+    def predict_permuted(self, rows, columns, donor):
+        """rl_model_predict_permuted: (f32 base scores [n_docs], f32 [len(columns)][n_repeats][n_docs]) -- cell (c, r) holds the scores of
+        rows with column columns[c] of row i taken from row donor[r][i]; donor [n_repeats][n_docs] (or [n_docs]: one repeat), any map into
+        [0, n_docs); rows as in predict_rows"""
+        L, rows, cols, don = self._permuted_args(rows, columns, donor)
+        base = np.zeros(rows.shape[0], np.float32)
+        out = np.zeros((cols.size, don.shape[0], rows.shape[0]), np.float32)
+        check(L.rl_model_predict_permuted(self.h, rows.ctypes.data, rows.shape[0], rows.shape[1], cols.ctypes.data, int(cols.size), don.ctypes.data,
+                                          int(don.shape[0]), base.ctypes.data, out.ctypes.data))
+        return base, out
+
+    def eval_permuted(self, rows, labels, qoff, metric, k, columns, donor, err_max=16.0, qkey=None, ideal_dcg=None, rel_doc_count=None,
+                      scratch_bytes=0):
+        """rl_model_eval_permuted: every list ranked and scored, as eval_lists does it, under the unpermuted rows and under every
+        (column, repeat) cell of predict_permuted, in one call.  Returns (f64 base values [n_lists], uint8 base NaN flags [n_lists],
+        f64 values [len(columns)][n_repeats][n_lists], uint8 NaN flags of the same shape -- a flagged cell holds 0.0 and was not ranked --,
+        f64 ideal DCG per list, NaN unless the metric is NDCG).  The other arguments are eval_lists'."""
+        L, rows, cols, don = self._permuted_args(rows, columns, donor)
+        m = str(metric).upper()
+        if m not in RL_EVAL_METRIC:
+            raise RankLibError("rlhip: eval_permuted metric must be one of NDCG, DCG, MAP, ERR, P, RR, BEST (got %s)" % metric)
+        lab = np.ascontiguousarray(labels, dtype=np.float32)
+        qo = np.ascontiguousarray(qoff, dtype=np.int32)
+        if lab.shape != (rows.shape[0],) or qo.ndim != 1 or qo.size < 1:
+            raise RankLibError("rlhip: eval_permuted takes rows [n_docs][row_stride], labels [n_docs] and qoff [n_lists + 1]")
+        nl = int(qo.size) - 1
+
+        def per_list(a, dtype, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (nl,):
+                raise RankLibError("rlhip: eval_permuted takes %s [n_lists]" % what)
+            return a
+        qk, idl, rdc = per_list(qkey, np.int32, "qkey"), per_list(ideal_dcg, np.float64, "ideal_dcg"), per_list(rel_doc_count, np.int32, "rel_doc_count")
+        w = max(1, nl)
+        base, bnan = np.zeros(w, np.float64), np.zeros(w, np.uint8)
+        out = np.zeros((cols.size, don.shape[0], w), np.float64)
+        nan = np.zeros((cols.size, don.shape[0], w), np.uint8)
+        ideal = np.zeros(w, np.float64)
+        ptr = lambda a: None if a is None else a.ctypes.data      # noqa: E731
+        check(L.rl_model_eval_permuted(self.h, rows.ctypes.data, rows.shape[0], rows.shape[1], lab.ctypes.data, qo.ctypes.data, nl, ptr(qk),
+                                       ptr(idl), ptr(rdc), RL_EVAL_METRIC[m], int(k), float(err_max), cols.ctypes.data, int(cols.size),
+                                       don.ctypes.data, int(don.shape[0]), int(scratch_bytes), base.ctypes.data, bnan.ctypes.data,
+                                       out.ctypes.data, nan.ctypes.data, ideal.ctypes.data))
+        return base[:nl], bnan[:nl], out[:, :, :nl], nan[:, :, :nl], ideal[:nl]
 
     def path(self):
         """MODEL_PATH_* of the last predict call: which kernel it took"""
@@ -1197,6 +1265,13 @@ def stage_times():
     """rl_debug_stage_times: (walk ms, rank ms) of this thread's last predict_stages / eval_stages call, between device events"""
     w, r = C.c_double(0), C.c_double(0)
     check(lib().rl_debug_stage_times(C.byref(w), C.byref(r)))
+    return w.value, r.value
+
+
+def permuted_times():
+    """rl_debug_permuted_times: (walk ms, rank ms) of this thread's last predict_permuted / eval_permuted call, between device events"""
+    w, r = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_permuted_times(C.byref(w), C.byref(r)))
     return w.value, r.value
 
 

@@ -188,6 +188,77 @@ struct StageWalk {
     }
 };
 
+// The ranking half of a call: the lists by length class, the scorer's tables on the device and the four-class launch of k_stage_eval over
+// the `ns` score rows of a chunk -- stages for rl_model_eval_stages, permuted cells for rl_model_eval_permuted (rl_permimp.inc).
+struct StageRank {
+    std::vector<int32_t> lists[4];
+    int32_t *d_qlist[4] = {nullptr, nullptr, nullptr, nullptr};
+    StArgs a;
+    StageRank() { memset(&a, 0, sizeof(a)); }
+    void classify(const int32_t *qoff, int32_t n_lists)
+    {
+        for (int32_t q = 0; q < n_lists; q++) {
+            const int n = qoff[q + 1] - qoff[q];
+            lists[n <= kEvTiny ? 0 : n <= kEvWave ? 1 : n <= kEvBlock ? 2 : 3].push_back(q);
+        }
+    }
+    // scratch of one score row: its floats, and where a list is past the LDS class its keys and ranked labels as well
+    int64_t bytes_per_row(int64_t n_docs) const
+    {
+        return n_docs * (int64_t)(sizeof(float) + (lists[3].empty() ? 0 : sizeof(unsigned long long) + sizeof(float)));
+    }
+    // d_sc: [chunk][n_docs], the rows the walk writes.  Allocates the outputs [chunk][n_lists] (a.out, a.nan).
+    int upload(DevPool &pool, const float *d_sc, int chunk, const float *labels, int64_t n_docs, const int32_t *qoff, int32_t n_lists,
+               const std::vector<double> &ideal, const std::vector<double> &disc, const int32_t *rel_doc_count, int32_t metric, int32_t k,
+               double err_max)
+    {
+        float *d_lab = nullptr;
+        double *d_ideal = nullptr, *d_disc = nullptr;
+        int32_t *d_qoff = nullptr, *d_rd = nullptr;
+        RL_HIP(pool.alloc(&d_lab, (size_t)n_docs));
+        RL_HIP(pool.alloc(&d_qoff, (size_t)n_lists + 1));
+        RL_HIP(pool.alloc(&d_ideal, (size_t)n_lists));
+        RL_HIP(pool.alloc(&d_disc, disc.size()));
+        RL_HIP(pool.alloc(&a.out, (size_t)chunk * n_lists));
+        RL_HIP(pool.alloc(&a.nan, (size_t)chunk * n_lists));
+        if (!lists[3].empty()) { RL_HIP(pool.alloc(&a.gkey, (size_t)chunk * n_docs)); RL_HIP(pool.alloc(&a.glab, (size_t)chunk * n_docs)); }
+        RL_HIP(hipMemcpy(d_lab, labels, (size_t)n_docs * sizeof(float), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(d_qoff, qoff, ((size_t)n_lists + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(d_ideal, ideal.data(), (size_t)n_lists * sizeof(double), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(d_disc, disc.data(), disc.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (rel_doc_count) {
+            RL_HIP(pool.alloc(&d_rd, (size_t)n_lists));
+            RL_HIP(hipMemcpy(d_rd, rel_doc_count, (size_t)n_lists * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        for (int c = 0; c < 4; c++) {
+            if (lists[c].empty()) continue;
+            RL_HIP(pool.alloc(&d_qlist[c], lists[c].size()));
+            RL_HIP(hipMemcpy(d_qlist[c], lists[c].data(), lists[c].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        a.ev.labels = d_lab; a.ev.qoff = d_qoff; a.ev.ideal = d_ideal; a.ev.rd_ext = d_rd; a.ev.disc = d_disc;
+        a.ev.metric = metric; a.ev.k = k; a.ev.err_max = err_max;
+        a.sc = d_sc; a.n_docs = n_docs; a.n_lists = n_lists;
+        return RL_OK;
+    }
+    // every list of every length class under the first ns score rows
+    int launch(int ns)
+    {
+        static const int G[4] = {kEvTiny, kWave, kThreads, kThreads};
+        for (int c = 0; c < 4; c++) {
+            if (lists[c].empty()) continue;
+            a.ev.qlist = d_qlist[c]; a.ev.nq = (int32_t)lists[c].size();
+            const int gpb = kThreads / G[c];
+            const dim3 grid((unsigned)((a.ev.nq + gpb - 1) / gpb), (unsigned)ns), block(kThreads);
+            if (c == 0) hipLaunchKernelGGL((k_stage_eval<kEvTiny, kEvTiny>), grid, block, 0, 0, a);
+            else if (c == 1) hipLaunchKernelGGL((k_stage_eval<kWave, kEvWave>), grid, block, 0, 0, a);
+            else if (c == 2) hipLaunchKernelGGL((k_stage_eval<kThreads, kEvBlock>), grid, block, 0, 0, a);
+            else hipLaunchKernelGGL((k_stage_eval<kThreads, 0>), grid, block, 0, 0, a);
+            RL_HIP(hipGetLastError());
+        }
+        return RL_OK;
+    }
+};
+
 struct StageEvents {
     hipEvent_t e[3] = {nullptr, nullptr, nullptr};
     hipError_t create() { for (auto &x : e) { hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; } return hipSuccess; }
@@ -249,51 +320,22 @@ int rl_model_eval_stages(rl_model *m, const float *X, int64_t n_docs, int32_t ro
     if (rc) return fail(rc, err);
     g_st_walk_ms = g_st_rank_ms = 0.0;
     RL_HIP(hipSetDevice(m->device));
-    std::vector<int32_t> lists[4];
-    for (int32_t q = 0; q < n_lists; q++) {
-        const int n = qoff[q + 1] - qoff[q];
-        lists[n <= kEvTiny ? 0 : n <= kEvWave ? 1 : n <= kEvBlock ? 2 : 3].push_back(q);
-    }
-    const bool has_long = !lists[3].empty();
+    StageRank rank;
+    rank.classify(qoff, n_lists);
     // a stage of the chunk: its float scores, and where a list is past the LDS class its keys and ranked labels as well
-    const int chunk = stage_chunk(scratch_bytes, n_docs * (int64_t)(sizeof(float) + (has_long ? sizeof(unsigned long long) + sizeof(float) : 0)), n_stages);
+    const int chunk = stage_chunk(scratch_bytes, rank.bytes_per_row(n_docs), n_stages);
     DevPool pool;
-    StArgs a;
-    memset(&a, 0, sizeof(a));
-    float *dX = nullptr, *d_carry = nullptr, *d_sc = nullptr, *d_lab = nullptr;
-    double *d_ideal = nullptr, *d_disc = nullptr, *d_out = nullptr; uint8_t *d_nan = nullptr;
-    int32_t *d_stages = nullptr, *d_qoff = nullptr, *d_rd = nullptr, *d_qlist[4] = {nullptr, nullptr, nullptr, nullptr};
+    float *dX = nullptr, *d_carry = nullptr, *d_sc = nullptr;
+    int32_t *d_stages = nullptr;
     RL_HIP(pool.alloc(&dX, (size_t)n_docs * row_stride));
     RL_HIP(pool.alloc(&d_carry, (size_t)n_docs));
     RL_HIP(pool.alloc(&d_sc, (size_t)chunk * n_docs));
     RL_HIP(pool.alloc(&d_stages, (size_t)n_stages));
-    RL_HIP(pool.alloc(&d_lab, (size_t)n_docs));
-    RL_HIP(pool.alloc(&d_qoff, (size_t)n_lists + 1));
-    RL_HIP(pool.alloc(&d_ideal, (size_t)n_lists));
-    RL_HIP(pool.alloc(&d_disc, disc.size()));
-    RL_HIP(pool.alloc(&d_out, (size_t)chunk * n_lists));
-    RL_HIP(pool.alloc(&d_nan, (size_t)chunk * n_lists));
-    if (has_long) { RL_HIP(pool.alloc(&a.gkey, (size_t)chunk * n_docs)); RL_HIP(pool.alloc(&a.glab, (size_t)chunk * n_docs)); }
     RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(d_stages, stages, (size_t)n_stages * sizeof(int32_t), hipMemcpyHostToDevice));
     RL_HIP(hipMemset(d_carry, 0, (size_t)n_docs * sizeof(float)));
-    RL_HIP(hipMemcpy(d_lab, labels, (size_t)n_docs * sizeof(float), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_qoff, qoff, ((size_t)n_lists + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_ideal, ideal.data(), (size_t)n_lists * sizeof(double), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_disc, disc.data(), disc.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (rel_doc_count) {
-        RL_HIP(pool.alloc(&d_rd, (size_t)n_lists));
-        RL_HIP(hipMemcpy(d_rd, rel_doc_count, (size_t)n_lists * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    for (int c = 0; c < 4; c++) {
-        if (lists[c].empty()) continue;
-        RL_HIP(pool.alloc(&d_qlist[c], lists[c].size()));
-        RL_HIP(hipMemcpy(d_qlist[c], lists[c].data(), lists[c].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    a.ev.labels = d_lab; a.ev.qoff = d_qoff; a.ev.ideal = d_ideal; a.ev.rd_ext = d_rd; a.ev.disc = d_disc;
-    a.ev.metric = metric; a.ev.k = k; a.ev.err_max = err_max;
-    a.sc = d_sc; a.n_docs = n_docs; a.out = d_out; a.nan = d_nan; a.n_lists = n_lists;
-    static const int G[4] = {kEvTiny, kWave, kThreads, kThreads};
+    rc = rank.upload(pool, d_sc, chunk, labels, n_docs, qoff, n_lists, ideal, disc, rel_doc_count, metric, k, err_max);
+    if (rc) return rc;
     StageEvents ev;
     RL_HIP(ev.create());
     StageWalk walk(m, dX, n_docs, row_stride, d_carry, d_sc);
@@ -303,20 +345,11 @@ int rl_model_eval_stages(rl_model *m, const float *X, int64_t n_docs, int32_t ro
         walk.launch(d_stages + s0, ns, stages[s0 + ns - 1]);
         RL_HIP(hipGetLastError());
         RL_HIP(hipEventRecord(ev.e[1], 0));
-        for (int c = 0; c < 4; c++) {
-            if (lists[c].empty()) continue;
-            a.ev.qlist = d_qlist[c]; a.ev.nq = (int32_t)lists[c].size();
-            const int gpb = kThreads / G[c];
-            const dim3 grid((unsigned)((a.ev.nq + gpb - 1) / gpb), (unsigned)ns), block(kThreads);
-            if (c == 0) hipLaunchKernelGGL((k_stage_eval<kEvTiny, kEvTiny>), grid, block, 0, 0, a);
-            else if (c == 1) hipLaunchKernelGGL((k_stage_eval<kWave, kEvWave>), grid, block, 0, 0, a);
-            else if (c == 2) hipLaunchKernelGGL((k_stage_eval<kThreads, kEvBlock>), grid, block, 0, 0, a);
-            else hipLaunchKernelGGL((k_stage_eval<kThreads, 0>), grid, block, 0, 0, a);
-            RL_HIP(hipGetLastError());
-        }
+        rc = rank.launch(ns);
+        if (rc) return rc;
         RL_HIP(hipEventRecord(ev.e[2], 0));
-        RL_HIP(hipMemcpy(out_metric + (size_t)s0 * n_lists, d_out, (size_t)ns * n_lists * sizeof(double), hipMemcpyDeviceToHost));
-        RL_HIP(hipMemcpy(out_nan + (size_t)s0 * n_lists, d_nan, (size_t)ns * n_lists, hipMemcpyDeviceToHost));
+        RL_HIP(hipMemcpy(out_metric + (size_t)s0 * n_lists, rank.a.out, (size_t)ns * n_lists * sizeof(double), hipMemcpyDeviceToHost));
+        RL_HIP(hipMemcpy(out_nan + (size_t)s0 * n_lists, rank.a.nan, (size_t)ns * n_lists, hipMemcpyDeviceToHost));
         float ms = 0.f;
         RL_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
         g_st_walk_ms += (double)ms;

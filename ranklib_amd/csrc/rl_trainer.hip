@@ -1417,3 +1417,4 @@ int rl_reset_timing(rl_trainer *t)
 
 #include "rl_model_eval.inc"
 #include "rl_stage.inc"      // the model after every requested number of trees: k_model_stage_scores walks, k_stage_eval ranks and scores
+#include "rl_permimp.inc"    // permutation importance: k_model_permuted_scores walks every (column, repeat) cell, k_stage_eval ranks and scores

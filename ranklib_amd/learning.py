@@ -260,6 +260,36 @@ class Ranker:
     def truncated(self, t):
         raise RankLibError("rlhip: truncated needs a LambdaMART or MART model: a %s model has no stages" % self.name())
 
+    # rlhip: permutation feature importance: what a feature is worth under the scorer on these lists
+    def _importanceFeatures(self, features):
+        feats = sorted({int(f) for f in (self.features if features is None else features)})
+        if not feats:
+            raise RankLibError("rlhip: permutationImportance has no feature to measure")
+        if feats[0] < 1:
+            raise RankLibError("rlhip: permutationImportance takes feature ids >= 1 (got %d)" % feats[0])
+        return feats
+
+    def permutationImportance(self, samples, scorer, features=None, repeats=5, seed=1, within=False):
+        """importance.Importance of features (None: the model's own, ascending) on samples under scorer: per feature and repeat the
+        documents receive that feature's value from the document importance.donor_maps names (a permutation of the whole file, or with
+        within one inside every list; the same map serves every feature of a repeat), the file is scored and ranked again, and the
+        importance is the base mean minus the mean over repeats.  This is the generic path, for every ranker: per cell a permuted copy
+        of the documents goes through evalLists and metric.score_lists."""
+        from . import importance as I
+        from .metric import score_lists
+        feats = self._importanceFeatures(features)
+        donors = I.donor_maps([rl.size() for rl in samples], repeats, seed, within)
+        flat, _ = self.evalLists(samples)
+        base, _ = score_lists(scorer, samples, flat)
+        dps = [dp for rl in samples for dp in rl.rl]
+        values = np.zeros((len(feats), repeats, len(samples)), np.float64)
+        for c, f in enumerate(feats):
+            for r in range(repeats):
+                perm = permuted_lists(samples, dps, f, donors[r])
+                flat, _ = self.evalLists(perm)
+                values[c, r], _ = score_lists(scorer, perm, flat)
+        return I.summarize(feats, base, values)
+
     def save(self, modelFile):        # :106-122
         d = modelFile.rsplit("/", 1)[0] if "/" in modelFile else None
         if d:
@@ -305,6 +335,23 @@ class Ranker:
 
     def printParameters(self):
         raise NotImplementedError
+
+
+def permuted_lists(samples, dps, fid, donor):
+    """samples with feature fid of document i (dps[i], the documents in file order) taken from document donor[i]: new lists of new
+    DataPoints, everything else shared.  A document without the feature donates the unknown value (NaN, which reads as 0)."""
+    out, i = [], 0
+    for rl in samples:
+        pts = []
+        for dp in rl.rl:
+            src = dps[int(donor[i])].fVals
+            fv = np.full(max(len(dp.fVals), fid + 1), np.nan, np.float32)
+            fv[:len(dp.fVals)] = dp.fVals
+            fv[fid] = src[fid] if fid < len(src) else np.nan
+            pts.append(DataPoint.from_parsed(dp.label, dp.id, dp.description, fv))
+            i += 1
+        out.append(RankList(pts))
+    return out
 
 
 def java_round(val, n):               # utilities/SimpleMath.java:54-60
@@ -486,6 +533,71 @@ class LambdaMART(Ranker):
                         out[s, dev[j]] = scorer.score(RankList(samples[dev[j]], list(order)))
             a = b
         return out
+
+    # --- permutation importance in one pass (rlhip) ----------------------------------------------
+    def permutationImportance(self, samples, scorer, features=None, repeats=5, seed=1, within=False):
+        """Ranker.permutationImportance, bit for bit, without a permuted copy per cell: every (feature, repeat) cell and the base are
+        walked, ranked and scored by _native.Model.eval_permuted.  Without within a document's donor may be any document of the file,
+        so every list's donor rows have to be in the call: ONE call takes the whole file, whatever EVAL_ROW_BYTES says.  With within
+        the donors stay in their lists and the file goes in chunks of whole lists whose rows stay under EVAL_ROW_BYTES.  What the scorer
+        holds is resolved per list id as score_lists does it.  A cell whose scores hold a NaN is filled on the host, as stagedScores
+        fills a stage: that list's permuted rows through predict_rows, then the per-list path of score_lists."""
+        from . import importance as I
+        feats = self._importanceFeatures(features)
+        cols = np.array(feats, np.int32)
+        sizes = [rl.size() for rl in samples]
+        donors = I.donor_maps(sizes, repeats, seed, within)
+        doc0 = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        name = scorer.name().split("@")[0].upper()
+        gains, counts = getattr(scorer, "idealGains", None), getattr(scorer, "relDocCount", None)
+        base = np.zeros(len(samples), np.float64)
+        values = np.zeros((len(feats), repeats, len(samples)), np.float64)
+        a = 0
+        while a < len(samples):
+            b, docs, width = a, 0, 1
+            while b < len(samples):
+                w = max(width, samples[b].getFeatureCount() + 1)
+                if within and b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
+                    break
+                docs, width, b = docs + samples[b].size(), w, b + 1
+            for q in range(a, b):
+                if not samples[q].size():                    # (the kernels take no empty list: the scorer's own answer, whatever the cell)
+                    base[q] = values[:, :, q] = scorer.score(samples[q])
+            dev = [q for q in range(a, b) if samples[q].size()]
+            if dev:
+                rows = self._rows([dp for q in dev for dp in samples[q].rl])
+                dq = np.concatenate([[0], np.cumsum([samples[q].size() for q in dev])]).astype(np.int64)
+                don = donors[:, int(doc0[a]):int(doc0[b])] - np.int32(doc0[a])      # (empty lists hold no document: the chunk's rows are contiguous)
+                labels = np.fromiter((dp.label for q in dev for dp in samples[q].rl), np.float32, count=int(dq[-1]))
+                ids = [samples[q].getID() for q in dev]
+                keys, qkey, ideal, rdc = {}, None, None, None
+                if name == "NDCG":
+                    qkey = np.array([keys.setdefault(i, len(keys)) for i in ids], np.int32)
+                    ideal = np.array([gains.get(i, np.nan) for i in ids], np.float64)
+                if name == "MAP" and counts is not None:
+                    rdc = np.array([counts.get(i, 0) for i in ids], np.int32)
+                bv, bnan, vals, nan, used = self._model.eval_permuted(rows, labels, dq, name, scorer.k, cols, don, err_max=ERRScorer.MAX,
+                                                                      qkey=qkey, ideal_dcg=ideal, rel_doc_count=rdc)
+                base[dev] = bv
+                values[:, :, dev] = vals
+                if name == "NDCG":
+                    for j, i in enumerate(ids):
+                        if i not in gains:
+                            gains[i] = float(used[j])
+
+                def on_host(j, c, r):
+                    lo, hi = int(dq[j]), int(dq[j + 1])
+                    part = rows[lo:hi].copy()
+                    if c is not None and feats[c] < rows.shape[1]:
+                        part[:, feats[c]] = rows[don[r, lo:hi], feats[c]]
+                    order = stable_desc_order(self._model.predict_rows(part).astype(np.float64))
+                    return scorer.score(RankList(samples[dev[j]], list(order)))
+                for j in np.flatnonzero(bnan):
+                    base[dev[j]] = on_host(j, None, 0)
+                for c, r, j in np.argwhere(nan):
+                    values[c, r, dev[j]] = on_host(j, c, r)
+            a = b
+        return I.summarize(feats, base, values)
 
     def truncated(self, t):
         """a ranker of this class holding the first t trees: its model text is truncate_model_text(model(), t)"""
