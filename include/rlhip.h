@@ -179,6 +179,21 @@ int rl_init(rl_trainer *t);
  * float-accumulated per-round values of :216 / :237 (valid_metric untouched without validation data). */
 int rl_boost_round(rl_trainer *t, rl_tree *out, float *train_metric, float *valid_metric, int32_t *stop);
 
+/* Resume: the T0 trees of a saved model -- `text` is what rl_model_to_text wrote, one <ensemble> -- become rounds 0 .. T0 - 1 of
+ * this trainer, replayed on its own data instead of grown.  After rl_init, before the first round and before rl_finish (else RL_ERR_STATE).
+ * Afterwards the trainer stands where the trainer that grew those trees stood after round T0, bit for bit: RL_ARR_SCORE / RL_ARR_VALID_SCORE
+ * are the f64 chains  s += (double)learning_rate * (double)output  over the T0 trees in order, the training lists are ranked by them,
+ * rl_get_round_metrics(r < T0) are the float means of the scores after tree r, rl_best_validation is rebuilt by rl_boost_round's strict >
+ * over those rounds, and *stop (may be NULL) is the early-stop test of LambdaMART.java:248 at round T0 - 1.  Adoption itself never stops;
+ * rl_boost_round goes on with round T0 (n_trees stays the TOTAL number of trees; T0 == n_trees leaves rl_finish only).  The adopted trees'
+ * `count` is -1 and `deviance` NaN in rl_get_tree: diagnostics the text does not hold.
+ * scratch_bytes bounds the per-tree stage scores the replay keeps at a time (8 bytes per document of both data sets and tree; 0 = 256 MiB;
+ * at least one tree); it cannot change a bit of the result.
+ * RL_ERR_INVALID, the message naming the cause: null text, text the parser refuses, more than one <ensemble>, no trees, more trees than
+ * n_trees, a tree with more nodes than rl_tree_capacity, a split on a feature id that is not among the trainer's feature_ids, a tree
+ * weight whose bits differ from learning_rate (per-tree weights are not built), scratch_bytes < 0.  A sharded trainer: RL_ERR_UNSUPPORTED. */
+int rl_adopt_model_text(rl_trainer *t, const char *text, int64_t scratch_bytes, int32_t *stop);
+
 /* Enqueue n rounds without any host synchronisation (no validation set allowed: early stopping needs
  * the host).  rl_sync waits for them; trees and per-round metrics are then available through
  * rl_get_tree / rl_get_round_metrics. */
@@ -375,7 +390,11 @@ enum {
     RL_ARM_SET_P8 = 48, RL_ARM_SET_DM_ROOT = 49, RL_ARM_SET_DM_DIV = 50, RL_ARM_SET_SUB_CHILD = 51, RL_ARM_SET_HIST_NT = 52, RL_ARM_SET_ANY_RUNS = 53,
     RL_ARM_SET_CROWS = 54, RL_ARM_SET_TIE_ON = 55, RL_ARM_SET_NODE_DIV = 56, RL_ARM_SET_NODE_MIN = 57, RL_ARM_SET_BALANCE = 58, RL_ARM_SET_BALANCE_TARGET = 59,
     RL_ARM_SET_BALANCE_MIN = 60, RL_ARM_SET_BALANCE_CAP = 61, RL_ARM_SET_NODE_CHUNK = 62, RL_ARM_SET_MAX_CHUNKS = 63,
-    RL_ARM_COUNT_ = 64
+    /* rl_adopt_model_text: launches of k_replay_scores (one per data set and chunk of trees) by arm.  The table grew behind its 64th entry for them:
+     * rl_get_array copies as many entries as the caller's buffer holds, 64 at least */
+    RL_ARM_REPLAY_TILED = 64,   /* rows staged into an LDS tile */
+    RL_ARM_REPLAY_DIRECT = 65,  /* rows read from global memory: more than 640 features, or RLHIP_REPLAY_DIRECT */
+    RL_ARM_COUNT_ = 66
 };
 /* The device's two exp implementations (rho of learning/tree/LambdaMART.java:383) on n arguments: the branch-free one the
  * lambda kernels use and the literal fdlibm e_exp transcription; both must equal StrictMath.exp bit for bit. */

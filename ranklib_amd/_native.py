@@ -115,7 +115,7 @@ ARM = dict(HIST_ROOT=0, HIST_CHILD=12, RANK_TINY=24, RANK_MIXED=25, RANK_WAVE_LO
            LAM_MART=30, LAM_TINY=31, LAM_FUSED=32, LAM_COMPACT=33, LAM_ERR=34, LAM_MAP=35, LAM_UNFUSED=36, LAM_ON_SIDE=37, LAM_ON_MAIN=38,
            QUANTIZE=39, XPLAN_HOST=40, XPLAN_DEVICE=41, STEPS_ENQUEUED=42, SET_STEP_AHEAD=43, SET_DIST_AHEAD=44, CHILD_GRID_X=45, CHILD_GRID_Y=46, CHILD_LDS=47,
            SET_P8=48, SET_DM_ROOT=49, SET_DM_DIV=50, SET_SUB_CHILD=51, SET_HIST_NT=52, SET_ANY_RUNS=53, SET_CROWS=54, SET_TIE_ON=55, SET_NODE_DIV=56,
-           SET_NODE_MIN=57, SET_BALANCE=58, SET_BALANCE_TARGET=59, SET_BALANCE_MIN=60, SET_BALANCE_CAP=61, SET_NODE_CHUNK=62, SET_MAX_CHUNKS=63, COUNT_=64)
+           SET_NODE_MIN=57, SET_BALANCE=58, SET_BALANCE_TARGET=59, SET_BALANCE_MIN=60, SET_BALANCE_CAP=61, SET_NODE_CHUNK=62, SET_MAX_CHUNKS=63, REPLAY_TILED=64, REPLAY_DIRECT=65, COUNT_=66)
 KERNEL = dict(HIST_ROOT=0, HIST_NODE=1, LAMBDA=2)
 
 # every symbol include/rlhip.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -146,6 +146,7 @@ ABI_SYMBOLS = [
     "rl_normalize_lists", "rl_debug_normalize_times",
     "rl_model_predict_stages", "rl_model_eval_stages", "rl_debug_stage_times",
     "rl_model_predict_permuted", "rl_model_eval_permuted", "rl_debug_permuted_times",
+    "rl_adopt_model_text",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -299,6 +300,8 @@ def lib():
         L.rl_model_predict_permuted.argtypes = [vp, vp, i64, i32, vp, i32, vp, i32, vp, vp]
         L.rl_model_eval_permuted.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, i32, vp, i32, i64, vp, vp, vp, vp, vp]
         L.rl_debug_permuted_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_adopt_model_text"):     # (A/B builds of older sources cannot resume)
+        L.rl_adopt_model_text.argtypes = [vp, C.c_char_p, i64, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -578,6 +581,15 @@ class Trainer:
         if t:
             t.n_nodes = ct.n_nodes
         return t, np.float32(tm.value), (np.float32(vm.value) if self.has_valid else None), bool(stop.value)
+
+    def adopt_model_text(self, text, scratch_bytes=0):
+        """resume: the trees of `text` (what model_text() wrote) become this trainer's first rounds, replayed on its data; after
+        init(), before the first round.  Returns the early-stop test at the last adopted round; round_metrics(r) holds the adopted rounds' values"""
+        if not hasattr(lib(), "rl_adopt_model_text"):
+            raise RankLibError("this librlhip.so has no rl_adopt_model_text: it cannot resume")
+        stop = C.c_int32(0)
+        check(lib().rl_adopt_model_text(self.h, None if text is None else text.encode("ascii"), scratch_bytes, C.byref(stop)))
+        return bool(stop.value)
 
     def boost_rounds_async(self, n):
         check(lib().rl_boost_rounds_async(self.h, n))

@@ -1315,8 +1315,9 @@ int rl_get_array(rl_trainer *t, int32_t which, void *out, int64_t cap_bytes)
         v[RL_ARM_SET_ANY_RUNS] = c.any_runs; v[RL_ARM_SET_CROWS] = c.crows ? 1 : 0; v[RL_ARM_SET_TIE_ON] = c.tie_on; v[RL_ARM_SET_NODE_DIV] = c.node_div;
         v[RL_ARM_SET_NODE_MIN] = c.node_min; v[RL_ARM_SET_BALANCE] = c.balance; v[RL_ARM_SET_BALANCE_TARGET] = c.balance_target; v[RL_ARM_SET_BALANCE_MIN] = c.balance_min;
         v[RL_ARM_SET_BALANCE_CAP] = c.balance_cap; v[RL_ARM_SET_NODE_CHUNK] = c.node_chunk; v[RL_ARM_SET_MAX_CHUNKS] = c.maxChunks;
-        if (cap_bytes < (int64_t)sizeof(v)) return fail(RL_ERR_INVALID, "output buffer too small");
-        memcpy(out, v, sizeof(v));
+        // (the table grew behind its 64th entry, the two replay arms: a caller built against the 64-entry table gets those 64)
+        if (cap_bytes < (int64_t)(RL_ARM_REPLAY_TILED * sizeof(int64_t))) return fail(RL_ERR_INVALID, "output buffer too small");
+        memcpy(out, v, std::min<size_t>(sizeof(v), (size_t)cap_bytes));
         return RL_OK;
     }
     case RL_ARR_TIE_STATS: {
@@ -1418,3 +1419,4 @@ int rl_reset_timing(rl_trainer *t)
 #include "rl_model_eval.inc"
 #include "rl_stage.inc"      // the model after every requested number of trees: k_model_stage_scores walks, k_stage_eval ranks and scores
 #include "rl_permimp.inc"    // permutation importance: k_model_permuted_scores walks every (column, repeat) cell, k_stage_eval ranks and scores
+#include "rl_resume.inc"     // resume: rl_adopt_model_text replays a saved model's trees as this trainer's first rounds (k_replay_scores)

@@ -45,7 +45,7 @@ import numpy as np
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, RESUME_NOT_BAGS, java_double_str, java_round,
                        stable_desc_order)
 from .metric import DCGScorer, ERRScorer, MetricScorerFactory, score_lists
 
@@ -424,10 +424,17 @@ _RANK_REMOVED = ("This function has been removed.\nConsider using -score in addi
 
 
 def main(argv=None):
+    try:
+        return _main(argv)
+    finally:      # -resume / -checkpoint belong to this command line only: a later LambdaMART of the process starts from nothing again
+        LambdaMART.resumeFrom, LambdaMART.checkpointFile, LambdaMART.checkpointEvery = None, None, 100
+
+
+def _main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-resume model] [-checkpoint file [-every n]] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
               "(-load also reads RankNet, LambdaRank and ListNet models; several -load: the models of a -kcv run, model i for fold i of the file, "
               "or for the i-th -test file) | -test f [-idv out] | -test f -score s | -rank f -indri out (no model: the file's own order, or the order of the numbers in s) | "
@@ -436,7 +443,11 @@ def main(argv=None):
               "-train <file> -ranker 1 -rnseed n [-epoch n] [-layer n] [-node n] [-lr x] (RankNet; -rnseed, an rlhip extension, seeds the initial weights "
               "and is required; defaults 100 epochs, 1 hidden layer of 10 nodes, learning rate 0.00005) | "
               "-train <file> -ranker 5 -lamseed n [-epoch n] [-layer n] [-node n] [-lr x] [-metric2t NDCG@k|DCG@k|MAP|ERR@k] (LambdaRank; -lamseed, an rlhip "
-              "extension, seeds the initial weights and is required; the other flags and defaults are RankNet's)")
+              "extension, seeds the initial weights and is required; the other flags and defaults are RankNet's) | "
+              "-resume model, -checkpoint file [-every n] are rlhip extensions of a -train -ranker 6|0 run: -resume continues the run that wrote the model "
+              "(its trees are this run's first rounds, -tree stays the total; from a -checkpoint file the result is the uninterrupted run's bit for bit, "
+              "from a final -save model early stopping restarts at its best validation prefix); -checkpoint writes all trees so far to the file after "
+              "every n-th round (default 100), complete or not at all")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
     testFiles, savedModelFiles = [], []
@@ -445,6 +456,8 @@ def main(argv=None):
     Evaluator.qrelFile = ""
     Evaluator.batch = True
     LambdaMART.fastLeaf = False                             # -fastleaf (rlhip extension)
+    LambdaMART.resumeFrom, LambdaMART.checkpointFile, LambdaMART.checkpointEvery = None, None, 100      # -resume, -checkpoint, -every (rlhip extensions)
+    resumeFile, everyGiven = "", False
     rankerType = 4                                          # the reference's default is Coordinate Ascent (:83)
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)
     ttSplit = tvSplit = 0.0
@@ -498,6 +511,11 @@ def main(argv=None):
             RFRanker.rType = RankerType(rt)
         elif a == "-seed": RFRanker.seed = FeatureHistogram.seed = CoorAscent.seed = int(nxt())     # rlhip extension: the Java draws are unseeded
         elif a == "-fastleaf": LambdaMART.fastLeaf = True   # rlhip extension: RL_FLAG_FAST_LEAF for -ranker 6 / 0 / 8 (leaf values within tolerance, not bit for bit)
+        elif a == "-resume": resumeFile = nxt()             # rlhip extension: the saved model whose trees are this run's first rounds
+        elif a == "-checkpoint": LambdaMART.checkpointFile = nxt()      # rlhip extension: all trees so far, after every -every n-th round
+        elif a == "-every":
+            LambdaMART.checkpointEvery = int(nxt())
+            everyGiven = True
         elif a == "-thread": nxt()                          # CPU thread pool of the reference: irrelevant here
         elif a == "-tts": ttSplit = float(nxt())            # :245-250
         elif a == "-tvs": tvSplit = float(nxt())
@@ -535,6 +553,26 @@ def main(argv=None):
         i += 1
     if not testMetric:
         testMetric = trainMetric                            # :379-381
+    if resumeFile or LambdaMART.checkpointFile or everyGiven:
+        what = "-resume" if resumeFile else "-checkpoint" if LambdaMART.checkpointFile else "-every"
+        if everyGiven and not LambdaMART.checkpointFile:
+            raise RankLibError("rlhip: -every n belongs to -checkpoint file")
+        if LambdaMART.checkpointEvery < 1:
+            raise RankLibError("rlhip: -every must be >= 1 (got %d)" % LambdaMART.checkpointEvery)
+        if not trainFile:
+            raise RankLibError("rlhip: %s continues or saves a training run: it needs -train" % what)
+        if rankerType == 8:
+            raise RankLibError(RESUME_NOT_BAGS)
+        if rankerType not in (0, 6):
+            raise RankLibError("rlhip: %s is built for the tree trainers, -ranker 6 (LambdaMART) and -ranker 0 (MART), not for -ranker %d" % (what, rankerType))
+        if foldCV != -1:
+            raise RankLibError("rlhip: %s with -kcv: every fold is a run of its own, one file cannot continue or hold them all" % what)
+        if resumeFile:
+            try:
+                with open(resumeFile, encoding="ascii") as f:
+                    LambdaMART.resumeFrom = f.read()
+            except (OSError, UnicodeDecodeError) as ex:
+                raise RankLibError("rlhip: -resume %s cannot be read as a model text: %s" % (resumeFile, ex))
     listnet = rankerType == 7 and netSeed is not None        # ListNet trains behind a seed only
     ranknet = rankerType == 1 and rnSeed is not None         # RankNet likewise, behind its own
     lambdarank = rankerType == 5 and lamSeed is not None     # LambdaRank likewise

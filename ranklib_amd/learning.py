@@ -24,6 +24,7 @@ import enum
 import random
 import logging
 import math
+import os
 import time
 
 import numpy as np
@@ -366,6 +367,10 @@ class FeatureHistogram:
     seed = 0          # not in the Java (it draws from an unseeded Random): makes the draw reproducible, see rlhip.h rl_params.seed
 
 
+RESUME_NOT_BAGS = ("rlhip: -resume / -checkpoint continue one LambdaMART (-ranker 6) or MART (-ranker 0) run; the bags of Random Forests "
+                   "(-ranker 8) are trainers of their own and are not built for it")
+
+
 class LambdaMART(Ranker):
     """learning/tree/LambdaMART.java with init()/learn() executed on an MI355X (librlhip.so)."""
     # process-global parameters, like the Java statics (:37-42)
@@ -378,6 +383,13 @@ class LambdaMART(Ranker):
     device = 0
     fastLeaf = False          # not in the Java (-fastleaf): leaf sums as the fixed f64 reduction of RL_FLAG_FAST_LEAF instead of the float running
                               # sums of :401-408; inherited by MART and, through these classes, by the bags of Random Forests
+    # not in the Java either (-resume / -checkpoint): the text of a saved model whose trees become this run's first rounds (nTrees stays
+    # the TOTAL number of trees); a file that receives model() of all trees so far -- not rolled back -- after every checkpointEvery-th round.  A run
+    # resumed from such a checkpoint is the uninterrupted run bit for bit; resumed from a FINAL model, which was rolled back to its best validation
+    # prefix, it restarts early stopping from that prefix -- a legitimate "train further", not the uninterrupted run
+    resumeFrom = None
+    checkpointFile = None
+    checkpointEvery = 100
     _RANKER = "LAMBDAMART"
 
     def __init__(self, samples=None, features=None, scorer=None):
@@ -425,7 +437,26 @@ class LambdaMART(Ranker):
             if ideal is not None or rdc is not None:
                 t.set_external_judgments(validation, ideal, rdc)
         t.init()
+        self._resumed, self._resume_stop = 0, False
+        if cls.resumeFrom is not None:
+            self._resume_stop = t.adopt_model_text(cls.resumeFrom)
+            self._resumed = t.num_trees()
         self._trainer = t
+
+    def _logRound(self, m, tm, vm):
+        self.printLog([7], [str(m + 1)])
+        self.printLog([9], [java_double_str(java_round(float(tm), 4))])
+        if vm is not None:
+            self.printLog([9], [java_double_str(java_round(float(vm), 4))])
+        self.flushLog()
+
+    def _writeCheckpoint(self, t):
+        """all trees so far, complete or not at all: the text goes to a file beside the checkpoint and is moved over it in one step"""
+        cls = type(self)
+        tmp = cls.checkpointFile + ".tmp"
+        with open(tmp, "w", encoding="ascii") as f:
+            f.write(t.model_text())
+        os.replace(tmp, cls.checkpointFile)
 
     def learn(self):                  # :169-272
         cls = type(self)
@@ -436,13 +467,14 @@ class LambdaMART(Ranker):
             self.printLogLn([7, 9, 9], ["#iter", nm + "-T", nm + "-V"])
         else:
             self.printLogLn([7, 9], ["#iter", nm + "-T"])
-        for m in range(cls.nTrees):
-            self.printLog([7], [str(m + 1)])
+        resumed = getattr(self, "_resumed", 0)
+        for m in range(resumed):      # the adopted rounds' lines, as the run that grew them printed them
+            self._logRound(m, *t.round_metrics(m))
+        for m in range(resumed, 0 if getattr(self, "_resume_stop", False) else cls.nTrees):
             _, tm, vm, stop = t.boost_round(want_tree=False)
-            self.printLog([9], [java_double_str(java_round(float(tm), 4))])
-            if vm is not None:
-                self.printLog([9], [java_double_str(java_round(float(vm), 4))])
-            self.flushLog()
+            self._logRound(m, tm, vm)
+            if cls.checkpointFile and (m + 1) % cls.checkpointEvery == 0:
+                self._writeCheckpoint(t)
             if stop:
                 break
         ts, vs = t.finish()           # rollback to the best validation model + scorer.score(rank(samples))
@@ -761,6 +793,8 @@ class RFRanker(Ranker):
     def init(self):                   # :57-69 -- overwrites LambdaMART's statics and never restores them, like the Java
         logger.info("Initializing... ")
         cls = type(self)
+        if LambdaMART.resumeFrom is not None or LambdaMART.checkpointFile:
+            raise RankLibError(RESUME_NOT_BAGS)
         self.ensembles = [None] * cls.nBag
         LambdaMART.nTrees = cls.nTrees
         LambdaMART.nTreeLeaves = cls.nTreeLeaves
