@@ -121,6 +121,94 @@ def test_host_transport_over_gloo(world, tmp_path):
     assert all(("ok%d" % k) in r.stdout for k in range(world))
 
 
+@pytest.fixture(scope="module")
+def shapes():
+    import dist_shapes
+    return {name: dist_shapes.make(name) for name in dist_shapes.SHAPES}
+
+
+def test_shards_of_every_named_shape_concatenate_to_the_unsharded_arrays(shapes):
+    """tests/dist_shapes.py: what the ranks of tests/dist_worker.py train on, put together again, is what the oracle of
+    tests/test_gpu_dist_shapes.py trains on -- and a second call builds the same arrays (parent and workers build them separately)"""
+    import dist_shapes
+    for name, (X, lab, qoff) in shapes.items():
+        s = dist_shapes.SHAPES[name]
+        assert X.dtype == np.float32 and lab.dtype == np.float32 and qoff.dtype == np.int32 and X.shape == (int(qoff[-1]), s.feat), name
+        assert s.docs in (0, X.shape[0]) and qoff[0] == 0 and (np.diff(qoff) > 0).all(), name
+        assert not np.isnan(X).any(), name
+        for world in (2, 3):
+            parts = [D.shard(X, lab, qoff, r, world) for r in range(world)]
+            assert np.array_equal(np.concatenate([p[0] for p in parts]), X), (name, world)
+            assert np.array_equal(np.concatenate([p[1] for p in parts]), lab), (name, world)
+            assert all(p[2][0] == 0 and p[2][-1] == len(p[0]) for p in parts), (name, world)
+            assert np.array_equal(np.concatenate([np.diff(p[2]) for p in parts]), np.diff(qoff)), (name, world)
+    X2, lab2, qoff2 = dist_shapes.make("split_decision")
+    X, lab, qoff = shapes["split_decision"]
+    assert np.array_equal(X2, X) and np.array_equal(lab2, lab) and np.array_equal(qoff2, qoff)
+
+
+def test_named_shapes_are_what_they_claim(shapes):
+    """the statistics that rl_init thresholds, in numpy: share of cells outside a column's most frequent value (compact rows: at most 5 cells a row
+    of a 16-column group), share of such cells followed by an equal value (k_run_stats: a column comes in runs at 0.9)"""
+    import dist_shapes as S
+    out, eq = S.share_outside_mode, S.share_equal_neighbours
+    # sparse: about a quarter of the columns all zero, the others behind the first 20 are ~85 % zeros
+    X, _, _ = shapes["sparse"]
+    dead = [f for f in range(X.shape[1]) if not X[:, f].any()]
+    assert 0.15 * X.shape[1] <= len(dead) <= 0.35 * X.shape[1] and min(dead) >= 20, dead
+    assert all(0.8 <= float((X[:, f] == 0).mean()) <= 0.9 for f in range(20, X.shape[1]) if f not in dead)
+    # runs: five query-level columns, two duplicated ones
+    X, _, qoff = shapes["runs"]
+    assert all(eq(X[:, f]) >= 0.9 for f in S.QLEVEL_COLS) and np.array_equal(X[:, 18], X[:, 2])
+    # split_decision: the halves of world = 2 differ in both statistics, on the columns built for it and on no other
+    X, _, qoff = shapes["split_decision"]
+    q, h = S.half(qoff)
+    assert D.shard(X, X[:, 0], qoff, 0, 2)[0].shape[0] == h and 0.4 * len(X) < h < 0.6 * len(X)
+    for f in S.QLEVEL_COLS:
+        assert eq(X[:h, f]) >= 0.95 and eq(X[h:, f]) <= 0.1, (f, eq(X[:h, f]), eq(X[h:, f]))
+    for f in S.SPARSE_BLOCK:
+        assert out(X[:h, f]) <= 0.2 and out(X[h:, f]) >= 0.95, (f, out(X[:h, f]), out(X[h:, f]))
+    others = [f for f in range(X.shape[1]) if f not in S.QLEVEL_COLS and f not in S.SPARSE_BLOCK]
+    assert all(eq(X[:h, f]) < 0.9 and eq(X[h:, f]) < 0.9 for f in others)
+    # (the first rank's rows of the sparse block average under 5 cells outside the mode a group, the second rank's all 16)
+    blk = X[:, list(S.SPARSE_BLOCK)]
+    assert (blk[:h] != 0).sum() <= 5.0 * h * 2 and (blk[h:] != 0).sum() >= 15.0 * (len(X) - h) * 2
+    # split_crows: no column in runs; per 16-column group the first half has more than 5 cells a row outside the mode bins, the second far fewer,
+    # and the whole file fewer than 5 -- the all-reduced look allows the compact rows, the per-rank verdict differs
+    X, _, qoff = shapes["split_crows"]
+    _, h = S.half(qoff)
+    assert all(eq(X[:, f]) < 0.5 and abs(out(X[:, f]) - float((X[:, f] != 0).mean())) < 1e-9 for f in range(X.shape[1]))      # (every column's mode is zero)
+    per_group = lambda A: (A != 0).reshape(len(A), -1, 16).sum(2)
+    assert per_group(X[:h]).mean(0).min() > 6.0 and per_group(X[h:]).mean(0).max() < 2.0 and per_group(X).mean() < 5.0
+    assert (per_group(X[h:]) > 8).mean() < 0.01
+    # dead_here
+    X, _, qoff = shapes["dead_here"]
+    _, h = S.half(qoff)
+    for f in S.DEAD_HALF_COLS:
+        assert len(np.unique(X[:h, f])) == 1 and len(np.unique(X[h:, f])) > 16, f
+    assert len(np.unique(X[:, S.DEAD_COL])) == 1
+    v, cnt = np.unique(X[:, S.MODE_ABSENT_COL], return_counts=True)
+    assert v[np.argmax(cnt)] == S.MODE_VALUE and not (X[:h, S.MODE_ABSENT_COL] == S.MODE_VALUE).any() and len(np.unique(X[:h, S.MODE_ABSENT_COL])) > 4
+    # wide tables: more distinct values than -tc
+    for name in ("wide_table", "wide_table_tie_off"):
+        X, _, _ = shapes[name]
+        assert sum(len(np.unique(X[:, f])) > S.SHAPES[name].tc for f in range(X.shape[1])) >= 2, name
+    assert S.SHAPES["wide_table"].tc + 1 > 264 and 16 * (S.SHAPES["wide_table"].tc + 1) * 4 <= 60 * 1024 < 16 * (S.SHAPES["wide_table_tie_off"].tc + 1) * 4
+    assert S.SHAPES["deep"].leaves > 256 and shapes["wide"][0].shape[1] == 3000
+    # one_long_list: rank 0 holds the long list alone; every other rank has less than a partition tile, one of three less than a chunk
+    for name in ("one_long_list", "one_long_list_map"):
+        X, lab, qoff = shapes[name]
+        assert qoff[1] == S.LONG_LIST > 5000 and len(qoff) == 62 and 8 <= np.diff(qoff)[1:].min() and np.diff(qoff)[1:].max() <= 12
+        for world in (2, 3):
+            sizes = [D.shard(X, lab, qoff, r, world)[0].shape[0] for r in range(world)]
+            assert sizes[0] == S.LONG_LIST and max(sizes[1:]) < 2048, sizes
+        assert min(sizes) < 256, sizes
+    # inf_and_wrapped
+    X, lab, _ = shapes["inf_and_wrapped"]
+    assert sorted(f for f in range(X.shape[1]) if np.isinf(X[:, f]).any()) == [0, 3]
+    assert all((X[:, f] == np.inf).any() and (X[:, f] == -np.inf).any() for f in (0, 3)) and lab.max() == 34 and (lab > 30).sum() > 100
+
+
 def test_leaf_owners_are_balanced_and_rank_invariant():
     rg = np.random.RandomState(3)
     for R in (1, 2, 3, 8):

@@ -101,19 +101,28 @@ def test_one_rank_sharded_path_without_a_progress_word_equals_plain_path(monkeyp
     same(ref, single(*CFG_TIES, dist_mode="cb1"))
 
 
+def launch_workers(world, port, out, cfg, ranker, metric, k, opts=None, worker_env=None):
+    """`world` ranks of tests/dist_worker.py on the one GPU (torch.distributed.run, gloo); returns what rank 0 saved.  (tests/test_gpu_dist_shapes.py too)"""
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", **(worker_env or {}))
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(ROOT, "tests", "dist_worker.py"), out] + [str(v) for v in cfg] + [ranker, metric, str(k)] + ([opts] if opts else [])
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return np.load(out)
+
+
+def saved_run(z, rounds):
+    """(trees, per-round metrics, scores, final metric) of a worker's output, as single() returns them"""
+    trees = [{k: z["t%d_%s" % (i, k)] for k in ("feature", "threshold", "left", "right", "output", "deviance", "count")} for i in range(rounds)]
+    return trees, [float(v) for v in z["mets"]], z["scores"], float(z["final"])
+
+
 def k_shards_against_one_shard(world, ranker, metric, k, cfg, tmp_path, worker_env=None):
     CFG = cfg
     ref = single(*CFG, ranker=ranker, metric=metric, k=k)
-    out = str(tmp_path / "dist.npz")
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", **(worker_env or {}))
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(29511 + world), os.path.join(ROOT, "tests", "dist_worker.py"), out] + [str(v) for v in CFG] + [ranker, metric, str(k)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    z = np.load(out)
+    z = launch_workers(world, 29511 + world, str(tmp_path / "dist.npz"), CFG, ranker, metric, k, worker_env=worker_env)
     rounds = CFG[5]
-    trees = [{k: z["t%d_%s" % (i, k)] for k in ("feature", "threshold", "left", "right", "output", "deviance", "count")} for i in range(rounds)]
-    same(ref, (trees, [float(v) for v in z["mets"]], z["scores"], float(z["final"])))
+    same(ref, saved_run(z, rounds))
     # round 6, distributed float chains (rl_dist.inc "piece mode"): NO document's lambda / weight leaves its rank -- every rank evaluates its own pieces
     # of every leaf and only per-piece tables (260 bytes per leaf, value array and rank), totals and drifts are all-gathered: the bytes of a round do
     # not grow with the documents (the leaf-owner exchange that remains for > 256 leaves is covered by test_sharded_options[ownerx])
@@ -194,6 +203,12 @@ def test_sharded_options(world, metric, k, opt, tmp_path):
     elif "ownerx" in opt:
         assert arms[N.ARM["XPLAN_DEVICE"]] == plans and arms[N.ARM["XPLAN_HOST"]] == 0, arms
     assert arms[N.ARM["SET_DIST_AHEAD"]] == (0 if "ahead0" in opt else 2 if "ahead2" in opt else 1), arms
+    if opt == "tcm1":
+        # the "off" side of the tie-break: tables of more than 4095 entries are split into virtual features, which switches the lazy tie-break off on one
+        # GPU as well (init_hist_features), and TS = 4095 is beyond the gathered sort of a sharded run besides -- every rank keeps the first tied
+        # candidate, as the one-GPU run does.  The "on" side at a table wider than the LDS row stride is wide_table of tests/test_gpu_dist_shapes.py; the
+        # tables that only a SHARDED run switches off (961 .. 4095 entries) are its wide_table_tie_off
+        assert (z["arms_all"][:, N.ARM["SET_TIE_ON"]] == 0).all(), z["arms_all"][:, N.ARM["SET_TIE_ON"]]
     if opt == "leafm1":
         assert max(len(t["feature"]) for t in trees) > 2 * cfg[4] - 1, "the trees never outgrew the explicit leaf budget: -leaf -1 was not exercised"
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_ffi as O
+from dist_shapes import duplicate_columns as _duplicate_columns, query_level_columns as _query_level_columns
 from ranklib_amd import _native as N
 from ranklib_amd import synth
 from tree_equiv import assert_equivalent
@@ -34,24 +35,10 @@ def same_f32(a, b):
 
 
 # ---- data sets ------------------------------------------------------------------------------------------------------------------------------
-def _duplicate_columns(X):
-    """two columns repeat two others (one rescaled: other thresholds, the same cuts): exact ties over several features, so the lazy tie-break
-    stalls or defers and re-enters the growth bookkeeping"""
-    X = X.copy()
-    X[:, 18] = X[:, 2]
-    X[:, 22] = 2.0 * X[:, 10] + 1.0
-    return X
-
-
-def _query_level_columns(X, qoff, seed):
-    """five columns with one value per query (as test_query_level_columns_take_the_quad_folded_histogram_path): rl_init flags them, any_runs holds"""
-    rng = np.random.default_rng(seed)
-    X = X.copy()
-    nq = len(qoff) - 1
-    for j in range(5):
-        vals = rng.random(nq).astype(np.float32) if j % 2 else np.floor(rng.random(nq) * 3).astype(np.float32)
-        X[:, 2 * j + 1] = np.repeat(vals, np.diff(qoff))
-    return X
+# _duplicate_columns: two columns repeat two others (one rescaled: other thresholds, the same cuts): exact ties over several features, so the lazy
+# tie-break stalls or defers and re-enters the growth bookkeeping.  _query_level_columns: five columns with one value per query (as
+# test_query_level_columns_take_the_quad_folded_histogram_path): rl_init flags them, any_runs holds.  Both live in tests/dist_shapes.py, whose shape
+# `runs` is set B below for the sharded cases of tests/test_gpu_dist_shapes.py
 
 
 def _oracle_rounds(X, lab, qoff, valid, rounds, leaves, metric="NDCG", k=10, per_query=False):
