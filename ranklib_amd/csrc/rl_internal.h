@@ -179,7 +179,7 @@ struct Ctx {
                               // cum_cnt_loc[node][best_f][best_t], so the single-pass partition and exact chunks need no count pass (null: unsharded)
     long long *part_sum; int32_t *part_cnt;                            // [maxChunks][F][TS]
     long long *part_tot;                                               // [maxChunks] sum of q over the chunk's samples
-    struct FeatBest *fb;                                               // [kSpec][2][F] per-feature best split of each new node (rl_kernels_round.inc)
+    struct FeatBest *fb;                                               // [kSpec][2][F] per-feature best split of each new node (rl_k_best.inc)
     unsigned long long *fb_root;                                       // [2] exact root total of the round
     unsigned long long *fb_sq;                                         // [kSpec] lambda^2 sum of each slot's left child (published by k_hist_finish block (0, slot))
     int32_t *tile_cnt;                                                 // [nTiles]

@@ -1,17 +1,20 @@
-// rl_kernels_round.inc -- gfx950 kernels of one boosting round (included by rl_trainer.hip).
+// rl_kernels_round.inc -- gfx950 kernels of one boosting round (included by rl_trainer.hip).  K1 .. K3 and K7 .. K10 are in this file; the
+// growth step of a tree (K4 .. K6) is included between them, one rl_k_*.inc piece per stage.
 //
 // K1  k_rank_*, k_lambda_fused / k_pair_terms + k_lambda_acc, k_mart_residual, k_max_reduce
 //                       per-query stable rank + pairwise swap change x sigmoid   LambdaMART.java:361-396, MART.java:47-51
 // K1b k_quantize        lambda -> order-independent fixed point                   (DESIGN.md 3 "exact sums")
 // K2/3 k_hist<ROOT>     LDS-staged per-chunk histograms                           FeatureHistogram.java:126-146,166-195
 // K4/5 k_hist_finish    chunk reduction, prefix over thresholds, sibling = parent - built child, per-feature gain scan
+//      rl_k_finish.inc (its helpers and k_hist_reduce: rl_k_reduce.inc; the per-feature best-split exchange: rl_k_best.inc)
 //                                                                                 FeatureHistogram.java:141-145,189-194,222-264
 //      select_step      (last block of k_hist_finish) best-first growth bookkeeping, speculative slots
-//                                                                                 RegressionTree.java:58-87,147-157
+//      rl_k_select.inc                                                            RegressionTree.java:58-87,147-157
 // K6  k_part_scatter<LOOKBACK> (+ k_part_count when sharded)  stable partition    FeatureHistogram.java:328-341
+//      rl_k_partition.inc
 // K7  k_leaf_table, k_leaf_output, k_score_update (+ rl_chain.inc)                LambdaMART.java:398-415, 203-210
 // K8  per-query metric in k_rank_*, float mean via rl_chain.inc / k_float_mean    LambdaMART.java:442-483
-// K10 k_ensemble_eval, k_valid_update (k_model_eval* live in rl_trainer.hip)      Ensemble.java:110-116, Split.java:115-125
+// K10 k_ensemble_eval, k_valid_update (k_model_eval* live in rl_model_eval.inc)   Ensemble.java:110-116, Split.java:115-125
 
 namespace rl {
 
@@ -1485,1502 +1488,16 @@ __global__ __launch_bounds__(NT) void k_hist(const Ctx c)
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// K4/K5: one block per feature.
-//   * sum the chunk partials of the (left) node into exact 128-bit bin totals
-//   * inclusive prefix over threshold index -> cumulative sum / count   (FeatureHistogram.java:141-145,189-194)
-//   * right sibling = parent - left                                     (FeatureHistogram.java:222-234)
-//   * gain scan S = sl^2/cl + sr^2/cr per child, first maximum wins     (FeatureHistogram.java:236-264)
-// LDS: TS x (hi, lo, cnt).
-// ------------------------------------------------------------------------------------------------
-constexpr int kParCacheTS = 1024;     // hist_finish_body keeps the parent's cumulative entries in LDS up to this many bins per feature
-struct Best { double S; int t; };
-__device__ __forceinline__ Best better(Best a, Best b)
-{   // larger S wins; on equal S the lower threshold index (the one the Java loop meets first)
-    if (b.S > a.S || (b.S == a.S && b.t >= 0 && (a.t < 0 || b.t < a.t))) return b;
-    return a;
-}
+}  // namespace rl
 
-// block-wide best of two candidates at once (built child, sibling): one pair of barriers for both
-__device__ void block_best2(Best &a, Best &b, Best *sh /* [2 * kFinThreads / 64] */, int nw_ = 0)
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        Best u; u.S = __shfl_xor(a.S, o); u.t = __shfl_xor(a.t, o);
-        a = better(a, u);
-        Best w; w.S = __shfl_xor(b.S, o); w.t = __shfl_xor(b.t, o);
-        b = better(b, w);
-    }
-    const int NW = nw_ ? nw_ : (int)(blockDim.x >> 6);          // (the finish kernels run with 320 threads, or 192 on wide data: k_hist_finish_wide; blockDim.x is a load)
-    __syncthreads();
-    if (lane_id() == 0) { sh[threadIdx.x >> 6] = a; sh[NW + (threadIdx.x >> 6)] = b; }
-    __syncthreads();
-    a = sh[0]; b = sh[NW];
-    for (int i = 1; i < NW; i++) { a = better(a, sh[i]); b = better(b, sh[NW + i]); }
-}
+// K4/K5 and K6, the growth step of a tree: one piece per stage, each a namespace rl block of its own, in dependency order
+#include "rl_k_reduce.inc"
+#include "rl_k_best.inc"
+#include "rl_k_select.inc"
+#include "rl_k_finish.inc"
+#include "rl_k_partition.inc"
 
-__device__ __forceinline__ double gain_S(double sl, int cl, double total, int ctot, int mls, bool &ok)
-{
-    const int cr = ctot - cl;
-    ok = !(cl < mls || cr < mls);
-    if (!ok) return -1.0;
-    const double sr = total - sl;                                    // FeatureHistogram.java:251
-    return sl * sl / cl + sr * sr / cr;                              // :253
-}
-
-
-// The mode bin was skipped by k_hist: bin[mode] = (sum over the node's samples) - (sum of the other bins), exact in
-// fixed point.  s_hi/s_lo/s_cnt hold the per-bin totals (mode bin = 0); every thread calls this.
-// have_pre: the caller has requested the thread's first chunk total (chunk ch0 + threadIdx.x) and the feature's mode bin already, together with its
-// other loads (each was a dependent memory round trip in the middle of every finish block)
-__device__ void rebuild_mode_bin(const Ctx &c, int f, int T, int ch0, int nch, int cnt_local, bool with_counts, long long *s_hi,
-                                 unsigned long long *s_lo, int *s_cnt, i128 *sh_red /* kFinThreads/64 */, int *sh_redc,
-                                 bool have_pre = false, long long tot_pre = 0, int mode_pre = 0)
-{
-    i128 part = 0; int cpart = 0;
-    for (int t = threadIdx.x; t < T; t += (int)blockDim.x) { part += make_i128(s_hi[t], s_lo[t]); cpart += s_cnt[t]; }
-    for (int ch = threadIdx.x; ch < nch; ch += (int)blockDim.x)
-        part -= (i128)((have_pre && ch == (int)threadIdx.x) ? tot_pre : c.part_tot[ch0 + ch]);      // others - total
-    for (int o = 32; o > 0; o >>= 1) {
-        uint32_t w0 = (uint32_t)(u128)part, w1 = (uint32_t)((u128)part >> 32), w2 = (uint32_t)((u128)part >> 64), w3 = (uint32_t)((u128)part >> 96);
-        w0 = __shfl_xor(w0, o); w1 = __shfl_xor(w1, o); w2 = __shfl_xor(w2, o); w3 = __shfl_xor(w3, o);
-        part += (i128)(((u128)w3 << 96) | ((u128)w2 << 64) | ((u128)w1 << 32) | (u128)w0);
-        cpart += __shfl_xor(cpart, o);
-    }
-    if (lane_id() == 0) { sh_red[threadIdx.x >> 6] = part; sh_redc[threadIdx.x >> 6] = cpart; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        i128 others_minus_total = 0; int oc = 0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); i++) { others_minus_total += sh_red[i]; oc += sh_redc[i]; }
-        const int m = have_pre ? mode_pre : c.mode[f];
-        const i128 v = -others_minus_total;
-        s_hi[m] = hi_of(v); s_lo[m] = lo_of(v);
-        if (with_counts) s_cnt[m] = cnt_local - oc;
-    }
-    __syncthreads();
-}
-
-// multi-GPU: bin totals of the accumulated node as int64 limbs (a = v >> 44, b = v & (2^44-1), count) so that a plain
-// int64 sum all-reduce of the limbs is exact; tail = the per-split scalars that travel with it
-constexpr int kLimbShift = 44;
-__global__ __launch_bounds__(kFinThreads) void k_hist_reduce(const Ctx c, int is_root)
-{   // grid (F, slots)
-    extern __shared__ unsigned long long sh_raw[];
-    __shared__ i128 sh_red[kFinThreads / 64];
-    __shared__ int sh_redc[kFinThreads / 64];
-    const TreeState *st = c.st;
-    const int slot = blockIdx.y;
-    int nodeB = 0, ch0 = 0, nodeS = 0, nodeP = 0, sl_cs = 0, sl_cnt = -1;
-    const bool active = is_root || (!st->done && slot < st->nslots);
-    if (!is_root && active) {
-        const SlotRec &sl = st->slot[slot];
-        nodeB = sl.build_left ? sl.left : sl.right; nodeS = sl.build_left ? sl.right : sl.left; nodeP = sl.node; ch0 = sl.chunk0; sl_cs = sl.cs;
-        if (sl.nleft >= 0) sl_cnt = sl.build_left ? sl.nleft : sl.pcount - sl.nleft;
-    }
-    const int f = blockIdx.x;
-    const int TS = c.TS, T = c.nthr[f];
-    long long *s_hi = (long long *)sh_raw;
-    unsigned long long *s_lo = sh_raw + TS;
-    int *s_cnt = (int *)(sh_raw + 2 * TS);
-    const int cntB = is_root ? c.N : (active ? (sl_cnt >= 0 ? sl_cnt : c.nodes[nodeB].count) : 0);
-    const int csB = is_root ? chunk_docs<true>(c, cntB) : (sl_cs > 0 ? sl_cs : chunk_docs<false>(c, cntB));      // (balance_slots)
-    const int nch = (cntB + csB - 1) / csB;
-    const int W = c.limb_words;
-    const size_t slot_words = (size_t)c.F * TS * W + 4;
-    long long *out = c.dist_buf + slot * slot_words + (size_t)f * TS * W;
-    for (int t = threadIdx.x; t < T; t += kFinThreads) {
-        i128 acc = 0; int cacc = 0;
-        // (batches of eight chunk partials in flight, as in hist_finish_body: one at a time every chunk was a memory round trip)
-        constexpr int kRedBatch = 8;
-        const size_t cstride = (size_t)c.F * TS;
-        const long long *ps = c.part_sum + ((size_t)ch0 * c.F + f) * TS + t;
-        const int *pc = c.part_cnt + ((size_t)ch0 * c.F + f) * TS + t;
-        unsigned long long lo = 0; long long hi = 0;
-        for (int ch = 0; ch < nch; ch += kRedBatch) {
-            long long v[kRedBatch]; int cn[kRedBatch];
-#pragma unroll
-            for (int u = 0; u < kRedBatch; u++) { const size_t o = (size_t)min(ch + u, nch - 1) * cstride; v[u] = ps[o]; cn[u] = is_root ? 0 : pc[o]; }
-#pragma unroll
-            for (int u = 0; u < kRedBatch; u++)
-                if (ch + u < nch) { lo += (unsigned long long)(unsigned)v[u]; hi += (v[u] >> 32); cacc += cn[u]; }
-        }
-        acc += (i128)lo + (((i128)hi) << 32);
-        s_hi[t] = hi_of(acc); s_lo[t] = lo_of(acc); s_cnt[t] = cacc;
-    }
-    __syncthreads();
-    rebuild_mode_bin(c, f, T, ch0, nch, cntB, !is_root, s_hi, s_lo, s_cnt, sh_red, sh_redc);
-    if (!is_root && active && c.cum_cnt_loc) {
-        // this rank's cumulative counts of the built child and (parent - built) of its sibling: what tells the next partition of either node its
-        // local left size (prepare_children)
-        __syncthreads();
-        __shared__ int sh_wc[kFinThreads / 64];
-        int32_t *cb = c.cum_cnt_loc + ((size_t)nodeB * c.F + f) * TS, *cs_ = c.cum_cnt_loc + ((size_t)nodeS * c.F + f) * TS;
-        const int32_t *cp = c.cum_cnt_loc + ((size_t)nodeP * c.F + f) * TS;
-        int carry = 0;
-        for (int t0 = 0; t0 < T; t0 += kFinThreads) {
-            const int t = t0 + (int)threadIdx.x;
-            const int v = t < T ? s_cnt[t] : 0, pv = t < T ? cp[t] : 0;
-            const int inc = (int)wave_scan_u32((unsigned)v);
-            if (lane_id() == 63) sh_wc[threadIdx.x >> 6] = inc;
-            __syncthreads();
-            int off = carry, all = 0;
-#pragma unroll
-            for (int w = 0; w < kFinThreads / 64; w++) { if (w < (int)(threadIdx.x >> 6)) off += sh_wc[w]; all += sh_wc[w]; }
-            if (t < T) { cb[t] = off + inc; cs_[t] = pv - (off + inc); }
-            carry += all;
-            __syncthreads();
-        }
-    }
-    for (int t = threadIdx.x; t < T; t += kFinThreads) {
-        const i128 acc = make_i128(s_hi[t], s_lo[t]);
-        const long long hi = (long long)(acc >> kLimbShift), lo = (long long)(acc & ((((i128)1) << kLimbShift) - 1));
-        const long long cn = is_root ? 0 : (long long)s_cnt[t];
-        if (W == 3) { out[3 * t] = hi; out[3 * t + 1] = lo; out[3 * t + 2] = cn; }
-        else { out[2 * t] = hi * 4294967296ll + cn; out[2 * t + 1] = lo; }       // |hi| < 2^30 and the global count < 2^31 (checked at init)
-    }
-    if (f == 0) {
-        __shared__ long long sh_sq[kFinThreads / 64];
-        const long long sqv = is_root ? st->root_sq : (active ? slot_sq_left(c, st->slot[slot], sh_sq) : 0);
-        if (threadIdx.x == 0) c.dist_buf[slot * slot_words + (size_t)c.F * TS * W] = sqv;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-#ifdef RL_PHASE_CLOCKS
-#define RL_CLK(cond, k) do { if (cond) { const long long t_ = strict_clock(); if (threadIdx.x == 0) c.clk[(c.st->step & 63) * 32 + (k)] = t_; } } while (0)
-#else
-#define RL_CLK(cond, k) do { } while (0)
-#endif
-
-// Growth bookkeeping (select_step), run by the LAST block of k_hist_finish to arrive: best split of the new nodes
-// across features (lowest feature index wins a tie, FeatureHistogram.java:302-309), then the best-first
-// bookkeeping of RegressionTree.fit (:58-87) on LDS copies of TreeState, the node records and the queue (a single
-// lane walking device memory pays ~1 us per dependent access).
-//
-// Speculative best-first growth.  RegressionTree.fit pops one node at a time, so a literal device version pays the
-// latency of a chain of dependent kernels per split.  Here every step PREPARES up to kSpec nodes from the front of
-// the queue at once (partition, child histograms, child best splits); the fit loop itself is replayed exactly and
-// only COMMITS prepared nodes in the order the Java pops them.  Preparing a node writes nothing a committed node can
-// see (new node records, the other ping-pong half of the node's own sample range, new histogram slots), so a
-// prepared node that the loop never reaches (leaf budget exhausted) simply stays a leaf.
-// ------------------------------------------------------------------------------------------------
-// Per-feature results of k_hist_finish travel from its blocks to the one block that runs select_step INSIDE the same
-// launch: agent-scope (write-through) stores, s_waitcnt, arrival counter -- no device-wide fence (on this 8-XCD
-// part a __threadfence() per block costs an L2 write-back each).
-struct FeatBest {           // best split of one feature for one new node + the cumulative histogram entry there
-    unsigned long long S;    // double bits
-    unsigned long long hi, lo;   // exact cumulative fixed-point sum at the split (= the left child's total)
-    unsigned long long tc;   // (t << 32) | count at the split; bit 62: another threshold of this feature reaches the same S exactly
-};
-constexpr unsigned long long kFbTie = 1ull << 62, kFbTieDiff = 1ull << 61;
-constexpr int kStepLogCap = 8192;      // entries of Ctx::steplog
-template <class T> __device__ __forceinline__ void st_agent(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// What the finish blocks published (write-through stores, completed before they arrived) is read by the block that runs select_step with PLAIN loads
-// behind ONE agent-scope acquire fence at its entry (it invalidates the stale lines this CU / XCD may hold of the records' fixed addresses).  Relaxed
-// atomic loads were correct too, but the compiler completes each group of them (s_waitcnt vmcnt(0)) before it issues the next: a lane's five
-// records were five dependent memory round trips in the step's serial tail, 22 with 700 features.
-template <class T> __device__ __forceinline__ T ld_agent(const T *p) { return *p; }
-
-// tie: bit 0 = another threshold of the feature reaches the same S, bit 1 = ... and cuts off other documents
-__device__ __forceinline__ void publish_best(const Ctx &c, int slot, int side, int f, double S, int t, int cl, long long hi, unsigned long long lo, int tie = 0)
-{
-    FeatBest *o = c.fb + ((size_t)slot * 2 + side) * c.F + f;         // one 32-byte record: a single write-through line
-    st_agent(&o->S, (unsigned long long)__double_as_longlong(S));
-    st_agent(&o->hi, (unsigned long long)hi); st_agent(&o->lo, lo);
-    st_agent(&o->tc, ((unsigned long long)(unsigned)t << 32) | (unsigned)cl | ((tie & 1) ? kFbTie : 0ull) | ((tie & 2) ? kFbTieDiff : 0ull));
-}
-
-// best split across features (lowest feature index wins a tie, FeatureHistogram.java:302-309).  A HALF wavefront per
-// (slot, side): the 2 * kSpec reductions of a step then fit into one pass over the block's wavefronts.  `valid` is uniform
-// in the half; every lane of the wavefront must call (shuffles).
-// Feature sampling (c.fs_size < F, Random Forests): the node's draw = the fs_size features with the smallest keys
-// feature_key(h, f), visited in key order, so a feature's RANK among the keys replaces its index: rank >= fs_size = not
-// drawn, lowest rank wins a tie (:283-309).  fkeys: F words of LDS scratch owned by this half.
-// The two sample sets a candidate cuts a node into, as an exact key: (documents, fixed-point sum) of the SMALLER side (of the side with the
-// smaller sum when the counts are equal).  Candidates with equal keys have exactly equal true gains -- the same cut, or a mirrored one whose
-// f64 S differs in the last bits only because sumRight = total - sumLeft is rounded (rl_tie.inc re-decides both kinds in the Java's order).
-#ifndef RL_FB_BATCH
-#define RL_FB_BATCH 8
-#endif
-struct PartKey { int cnt; i128 sum; };
-__device__ __forceinline__ PartKey part_key(int cl, i128 sl, int ctot, i128 tot)
-{
-    const int cr = ctot - cl; const i128 sr = tot - sl;
-    PartKey k;
-    if (cl < cr) { k.cnt = cl; k.sum = sl; }
-    else if (cl > cr) { k.cnt = cr; k.sum = sr; }
-    else { k.cnt = cl; k.sum = sl < sr ? sl : sr; }
-    return k;
-}
-
-// nthi / ntlo / nctot: the node's exact totals (for the mirrored-cut check; unused without the lazy tie-break)
-// WIDE (k_select: the bookkeeping kernel of data with hundreds of features, where the block is alone on the chip and registers are free): all the gains
-// of the lane's share (up to kWideS x 32 features) are requested at once and stay in registers for the tie pass -- at 700 features the three batches of
-// eight, the winner's fields and the tie pass's second scan of the gains were seven dependent round trips (8-9 us of every growth step).
-constexpr int kWideS = 24;
-template <bool WIDE = false>
-__device__ __forceinline__ void half_wave_best_feature(const Ctx &c, bool valid, int slot, int side, unsigned long long h, unsigned long long *fkeys,
-                                       double &S, int &f, int &t, int &cl, long long &hi, unsigned long long &lo, int &tie,
-                                       long long nthi = 0, unsigned long long ntlo = 0, int nctot = 0)
-{
-    const FeatBest *o = c.fb + ((size_t)slot * 2 + side) * c.F;
-    const int hl = lane_id() & 31, hbase = lane_id() & 32;
-    const bool sampling = c.fs_on != 0;
-    if (sampling) {       // (the draw is over the REAL features: every run of a split threshold table carries its column's key -- Ctx::fcol, rl_init)
-        if (valid) for (int i = hl; i < c.F; i += 32) fkeys[i] = feature_key(h, c.fcol[i] & 0x7fffffff);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-    }
-    // every lane keeps the whole record of its best feature: the winner's fields come from a lane, not from a second
-    // round trip to memory
-    double bs = -1.0; int bf = -1, br = 0x7fffffff;
-    unsigned long long bhi = 0, blo = 0, btc = 0;
-    bool eq = false;            // another feature of this lane's share reaches the lane's best S exactly
-    // Up to 32 * kFbFull features (the MSLR shape: 136): every lane asks for the WHOLE records of its share at once -- one memory round trip for the
-    // gains, the winner's fields and the tie pass below, instead of three dependent ones (6-9 us of the step's serial tail were these loads).
-    constexpr int kFbFull = 5;
-    const bool small = !sampling && c.F <= 32 * kFbFull;
-    unsigned long long kS[kFbFull], kH[kFbFull], kL[kFbFull], kT[kFbFull];
-    [[maybe_unused]] unsigned long long wS[WIDE ? kWideS : 1];
-#pragma unroll
-    for (int u = 0; u < kFbFull; u++) { kS[u] = 0xbff0000000000000ull; kH[u] = kL[u] = kT[u] = 0ull; }
-    if (valid && small) {
-#pragma unroll
-        for (int u = 0; u < kFbFull; u++) {
-            const int i = hl + 32 * u;
-            if (i < c.F) { kS[u] = ld_agent(&o[i].S); kH[u] = ld_agent(&o[i].hi); kL[u] = ld_agent(&o[i].lo); kT[u] = ld_agent(&o[i].tc); }
-        }
-#pragma unroll
-        for (int u = 0; u < kFbFull; u++) {
-            const int i = hl + 32 * u;
-            const double s = __longlong_as_double((long long)kS[u]);
-            if (s == bs && s > -1.0) eq = true;
-            if (s > bs) { eq = false; bs = s; bf = i; br = i; bhi = kH[u]; blo = kL[u]; btc = kT[u]; }         // (ascending i: the first of equal gains stays)
-        }
-    } else if (WIDE && valid && !sampling && c.F <= 32 * kWideS) {
-#pragma unroll
-        for (int u = 0; u < kWideS; u++) wS[u] = ld_agent(&o[min(hl + 32 * u, c.F - 1)].S);
-#pragma unroll
-        for (int u = 0; u < kWideS; u++) {
-            const int i = hl + 32 * u;
-            if (i >= c.F) wS[u] = 0xbff0000000000000ull /* -1.0 */;
-            const double s = __longlong_as_double((long long)wS[u]);
-            if (s == bs && s > -1.0) eq = true;
-            if (s > bs) { eq = false; bs = s; bf = i; br = i; }         // (ascending i: the first of equal gains stays)
-        }
-        if (bf >= 0) { bhi = ld_agent(&o[bf].hi); blo = ld_agent(&o[bf].lo); btc = ld_agent(&o[bf].tc); }
-    } else if (valid && !sampling) {
-        // Eight gains per lane are requested at once (the loads are agent-scope atomics: one at a time they cost a memory round trip per feature of
-        // the lane's share -- 22 of them with 700 features, 16-19 us of this block's serial tail); the rest of a record is fetched for the lane's best only.
-        constexpr int B = RL_FB_BATCH;
-        for (int i0 = hl; i0 < c.F; i0 += 32 * B) {
-            unsigned long long rs[B];
-#pragma unroll
-            for (int u = 0; u < B; u++) { const int i = i0 + 32 * u; rs[u] = (i < c.F) ? ld_agent(&o[i].S) : 0xbff0000000000000ull /* -1.0 */; }
-#pragma unroll
-            for (int u = 0; u < B; u++) {
-                const int i = i0 + 32 * u;
-                const double s = __longlong_as_double((long long)rs[u]);
-                if (s == bs && s > -1.0) eq = true;
-                if (s > bs) { eq = false; bs = s; bf = i; br = i; }         // (ascending i: the first of equal gains stays)
-            }
-        }
-        if (bf >= 0) { bhi = ld_agent(&o[bf].hi); blo = ld_agent(&o[bf].lo); btc = ld_agent(&o[bf].tc); }
-    } else if (valid) {
-        for (int i = hl; i < c.F; i += 32) {
-            const unsigned long long rs = ld_agent(&o[i].S), rh = ld_agent(&o[i].hi), rl = ld_agent(&o[i].lo), rt = ld_agent(&o[i].tc);
-            int rank = i;
-            {
-                const unsigned long long ki = fkeys[i];
-                rank = 0;
-                // one count per real column: fcol[g] < 0 marks the later runs of a split table (they share their column's rank; the lower run wins an equal gain)
-                const int ci = c.fcol[i] & 0x7fffffff;
-                for (int g = 0; g < c.F; g++) { const int cg = c.fcol[g]; const unsigned long long kg = fkeys[g]; rank += (cg >= 0) && ((kg < ki) || (kg == ki && cg < ci)); }
-                if (rank >= c.fs_size) continue;
-            }
-            const double s = __longlong_as_double((long long)rs);
-            if (s == bs && s > -1.0) eq = true;
-            if (s > bs || (s == bs && s > -1.0 && rank < br)) { if (s > bs) eq = false; bs = s; bf = i; br = rank; bhi = rh; blo = rl; btc = rt; }
-        }
-    }
-    RL_CLK(slot == 0 && side == 0 && valid, 17);       // the lane's share of the records has arrived and is reduced
-    const int own = bf;         // this lane's candidate (its fields are in bhi / blo / btc)
-    const double own_s = bs;
-    for (int d = 16; d > 0; d >>= 1) {
-        const double s = __shfl_xor(bs, d); const int ff = __shfl_xor(bf, d), rr = __shfl_xor(br, d);
-        if (s > bs || (s == bs && ff >= 0 && (bf < 0 || rr < br || (rr == br && ff < bf)))) { bs = s; bf = ff; br = rr; }
-    }
-    S = bs; f = bf; t = -1; cl = 0; hi = 0; lo = 0;
-    // the winner is the own candidate of exactly one lane of this half (ranks are distinct)
-    RL_CLK(slot == 0 && side == 0 && valid, 18);       // ... across the half wavefront
-    const unsigned long long ownmask = __ballot(bf >= 0 && own == bf) >> hbase;
-    const int src = hbase + (int)__builtin_ctzll(ownmask | (1ull << 63));
-    const unsigned long long tc = (unsigned long long)__shfl((long long)btc, src);
-    const long long h2 = __shfl((long long)bhi, src); const unsigned long long l2 = (unsigned long long)__shfl((long long)blo, src);
-    // exact ties (rl_tie.inc): several features reach the best S (2), or only other thresholds of the winning feature do (1)
-    unsigned long long cross = __ballot(bf >= 0 && own >= 0 && own_s == bs && (own != bf || eq)) >> hbase;
-    bool other_cut = false;     // a tied candidate of this lane's share does not have the winner's (left count, left sum): a mirrored or a different cut
-    if (c.tie_on) {       // mirrored cuts of other features: equal partition keys although the f64 S differ by a rounding
-        bool mir = false;
-        if (valid && bf >= 0 && small) {
-            const i128 ntot = make_i128(nthi, ntlo);
-            const i128 wsl = make_i128(h2, l2);
-            const PartKey wk = part_key((int)(unsigned)tc, wsl, nctot, ntot);
-#pragma unroll
-            for (int u = 0; u < kFbFull; u++) {
-                const int i = hl + 32 * u;
-                if (i == bf) continue;
-                const double s = __longlong_as_double((long long)kS[u]);
-                if (!(s > -1.0) || fabs(s - bs) > 1e-9 * fabs(bs)) continue;
-                const unsigned long long itc = kT[u];
-                const i128 isl = make_i128((long long)kH[u], kL[u]);
-                const PartKey k = part_key((int)(unsigned)itc, isl, nctot, ntot);
-                const bool keq = (k.cnt == wk.cnt && k.sum == wk.sum);
-                mir |= keq;
-                if (keq || s == bs) other_cut |= !((unsigned)itc == (unsigned)tc && isl == wsl) || (itc & kFbTieDiff) != 0;
-            }
-        } else if (WIDE && valid && bf >= 0 && !sampling && c.F <= 32 * kWideS) {
-            const i128 ntot = make_i128(nthi, ntlo);
-            const i128 wsl = make_i128(h2, l2);
-            const PartKey wk = part_key((int)(unsigned)tc, wsl, nctot, ntot);
-            // the near-equal gains of the share as bit masks (registers cannot be indexed by a run-time u); the records behind them -- rare -- come from memory
-            unsigned near = 0u, exact = 0u;
-#pragma unroll
-            for (int u = 0; u < kWideS; u++) {
-                const double s = __longlong_as_double((long long)wS[u]);
-                if (hl + 32 * u != bf && s > -1.0 && !(fabs(s - bs) > 1e-9 * fabs(bs))) { near |= 1u << u; if (s == bs) exact |= 1u << u; }
-            }
-            while (near) {
-                const int u = __builtin_ctz(near);
-                near &= near - 1u;
-                const int i = hl + 32 * u;
-                const unsigned long long itc = ld_agent(&o[i].tc);
-                const i128 isl = make_i128((long long)ld_agent(&o[i].hi), ld_agent(&o[i].lo));
-                const PartKey k = part_key((int)(unsigned)itc, isl, nctot, ntot);
-                const bool keq = (k.cnt == wk.cnt && k.sum == wk.sum);
-                mir |= keq;
-                if (keq || ((exact >> u) & 1u)) other_cut |= !((unsigned)itc == (unsigned)tc && isl == wsl) || (itc & kFbTieDiff) != 0;
-            }
-        } else if (valid && bf >= 0) {
-            const i128 ntot = make_i128(nthi, ntlo);
-            const i128 wsl = make_i128(h2, l2);
-            const PartKey wk = part_key((int)(unsigned)tc, wsl, nctot, ntot);
-            constexpr int B = RL_FB_BATCH;
-            for (int i0 = hl; i0 < c.F; i0 += 32 * B) {
-              unsigned long long rs[B];
-#pragma unroll
-              for (int u = 0; u < B; u++) { const int i = i0 + 32 * u; rs[u] = (i < c.F) ? ld_agent(&o[i].S) : 0xbff0000000000000ull; }
-#pragma unroll
-              for (int u = 0; u < B; u++) {
-                const int i = i0 + 32 * u;
-                if (i == bf) continue;
-                const double s = __longlong_as_double((long long)rs[u]);
-                if (!(s > -1.0) || fabs(s - bs) > 1e-9 * fabs(bs)) continue;
-                const unsigned long long itc = ld_agent(&o[i].tc);
-                const i128 isl = make_i128((long long)ld_agent(&o[i].hi), ld_agent(&o[i].lo));
-                const PartKey k = part_key((int)(unsigned)itc, isl, nctot, ntot);
-                const bool keq = (k.cnt == wk.cnt && k.sum == wk.sum);
-                mir |= keq;
-                if (keq || s == bs) other_cut |= !((unsigned)itc == (unsigned)tc && isl == wsl) || (itc & kFbTieDiff) != 0;
-              }
-            }
-        }
-        cross |= __ballot(mir) >> hbase;
-    }
-    RL_CLK(slot == 0 && side == 0 && valid, 19);       // tie pass
-    const bool any_other = (__ballot(other_cut) >> hbase) & 0xffffffffull;
-    tie = 0;
-    if (bf >= 0) {
-        t = (int)((tc >> 32) & 0xffffu); cl = (int)(unsigned)tc; hi = h2; lo = l2;
-        // 2 = the Java's noise picks among several features, or among thresholds with other counts; 1 = thresholds of the winning feature that all cut
-        // off the same documents; 4 (with 2) = every tied candidate of every feature cuts off the winner's (left count, exact left sum) -- the same
-        // documents unless a coincidence of lambdas says otherwise, which the deferred tie-break verifies (rl_tie.inc); bits 8..: lanes (of 32)
-        // whose share holds a tied feature
-        tie = (cross & 0xffffffffull) ? (2 | (__builtin_popcountll(cross & 0xffffffffull) << 8)) : ((tc & kFbTieDiff) ? 2 : ((tc & kFbTie) ? 1 : 0));
-        if ((cross & 0xffffffffull) && !any_other && !(tc & kFbTieDiff)) tie |= 4;
-    }
-}
-
-__device__ __forceinline__ void queue_insert_lds(int *q, double *qd, int &qsize, int node, double d)
-{   // RegressionTree.insert (:147-157): before the first element whose deviance is <= the new one's
-    int i = 0;
-    while (i < qsize) { if (qd[i] > d) i++; else break; }
-    for (int j = qsize; j > i; j--) { q[j] = q[j - 1]; qd[j] = qd[j - 1]; }
-    q[i] = node; qd[i] = d;
-    qsize++;
-}
-
-// histogram chunks of a node of cnt samples (as k_hist cuts it)
-__device__ __forceinline__ int node_chunks(const Ctx &c, int cnt) { return cnt <= 0 ? 0 : (cnt + chunk_docs<false>(c, cnt) - 1) / chunk_docs<false>(c, cnt); }
-
-// Put node p into slot `sl` of the next growth step: its children l, l+1 get node records (global counts / exact
-// totals from p's cumulative histogram); their local sample ranges are set by the partition kernel.
-// tile0 / chunk0 are filled by the caller (prefix over the slots).
-__device__ __forceinline__ void prepare_children(const Ctx &c, NodeRec *N, int p, int l, SlotRec &sl)
-{
-    NodeRec &P = N[p];
-    const int r = l + 1;
-    const int cl = P.best_cl;                                    // cumulative histogram entry at the split
-    const long long thi = P.best_hi; const unsigned long long tlo = P.best_lo;
-    NodeRec Lc, Rc;
-    Lc.start = P.start; Lc.count = 0; Lc.gcount = cl; Lc.buf = 1 - P.buf; Lc.parent = p; Lc.left = Lc.right = -1;
-    Rc.start = P.start; Rc.count = 0; Rc.gcount = P.gcount - cl; Rc.buf = 1 - P.buf; Rc.parent = p; Rc.left = Rc.right = -1;
-    const i128 tl = make_i128(thi, tlo);                        // exact: same sample set as the left child
-    const i128 tr = make_i128(P.tot_hi, P.tot_lo) - tl;
-    Lc.tot_hi = hi_of(tl); Lc.tot_lo = lo_of(tl);
-    Rc.tot_hi = hi_of(tr); Rc.tot_lo = lo_of(tr);
-    Lc.best_f = Lc.best_t = Rc.best_f = Rc.best_t = -1; Lc.best_S = Rc.best_S = -1.0;
-    Lc.best_cl = Rc.best_cl = 0; Lc.best_hi = Rc.best_hi = 0; Lc.best_lo = Rc.best_lo = 0;
-    Lc.deviance = Rc.deviance = 0.0; Lc.sum_response = Rc.sum_response = 0.0; Lc.sq_response = Rc.sq_response = 0.0;
-    Lc.sq = Rc.sq = 0;
-    Lc.output = Rc.output = 0.f;
-    Lc.pl = Lc.pr = Rc.pl = Rc.pr = -1; Lc.fid = Rc.fid = -1; Lc.prepared = Rc.prepared = 0;
-    Lc.tie = Rc.tie = 0; Lc.ph = child_hash(P.ph, 0); Rc.ph = child_hash(P.ph, 1);
-    N[l] = Lc; N[r] = Rc;
-    P.pl = l; P.pr = r; P.prepared = 1;
-    sl.node = p; sl.left = l; sl.right = r;
-    sl.build_left = (cl <= P.gcount - cl) ? 1 : 0;
-    sl.pstart = P.start; sl.pcount = P.count; sl.pbuf = P.buf; sl.f = P.best_f; sl.t = P.best_t;
-    sl.tile0 = 0; sl.ntiles = (P.count + kPartTile - 1) / kPartTile;
-    // chunks of the child that is accumulated: exact on one GPU; an upper bound of the LOCAL part when sharded
-    sl.chunk0 = 0; sl.cs = 0; sl.skip_hist = 0;
-    if (!c.sharded) { sl.nchunks = node_chunks(c, sl.build_left ? cl : P.gcount - cl); sl.nleft = cl; }
-    else if (c.cum_cnt_loc) {       // sharded, round 6: this rank's share of the left child from its own cumulative counts (k_hist_reduce keeps them beside the all-reduced ones)
-        const int nl = c.cum_cnt_loc[((size_t)p * c.F + P.best_f) * c.TS + P.best_t];
-        sl.nleft = nl; sl.nchunks = node_chunks(c, sl.build_left ? nl : P.count - nl);
-        N[l].count = nl; N[r].start = P.start + nl; N[r].count = P.count - nl;
-    } else { sl.nchunks = (P.count == 0) ? 0 : max(64, P.count / c.node_chunk + 1) + 1; sl.nleft = -1; }
-    sl.sq_left = 0;
-    atomicAdd(&c.grow_docs[0], (unsigned long long)(sl.build_left ? cl : P.gcount - cl));
-    atomicAdd(&c.grow_docs[1], (unsigned long long)P.gcount);
-}
-
-// Balanced chunks for a step that fills the chip (one GPU: the built children's sizes are known).  chunk_docs gives a large node the largest
-// chunk, and the first steps of a c2 tree came to 810 / 1 692 / 1 233 (chunk, group) blocks for the 768 places of the chip (three 50 KB blocks per
-// CU): CUs ended up with 3 to 5 (5 to 8) blocks and the launch lasted until the fullest CU was done (HISTORY.md 10.5, profiles/r04_block_placement_*).
-// Here the step's documents are cut into k x balance_target chunks of ONE size (<= 2^14 documents: what an int64 accumulator holds), the same
-// size for every node of the step, and launch_hist launches exactly balance_target rows of blocks, so every block row works through k chunks.
-// balance_target = 56: 56 rows x 9 feature groups = 504 blocks = TWO per CU, which is what saturates a CU's LDS atomic unit; a third block on
-// some CUs (80 rows) makes those CUs 1.5 x as slow as the others (measured: 80 rows +1 %, 56 rows +3 %, 64 / 72 rows worse than none).
-// Steps of at most balance_min chunks keep the per-node rule (finer cuts only add partial histograms to flush and to reduce).  One thread calls
-// this, after prepare_children, before the prefix over the slots.  Exact integer sums: the cut changes no result.
-__device__ __forceinline__ void balance_slots(const Ctx &c, SlotRec *slot, int ns)
-{
-    if ((c.sharded && !c.cum_cnt_loc) || !c.balance) return;       // (local sizes unknown: chunk_docs' rule.  Until round 6 a ONE-rank communicator was balanced while k_hist_reduce
-                                                                    // cut its nodes by chunk_docs' rule: runs of more than 28 chunks a step summed the wrong partials, tools/dist_scale_check.py)
-    int legacy = 0; unsigned D = 0;       // (the built children of a step are disjoint: D <= N < 2^31 -- 32-bit divisions; a 64-bit one is ~100 instructions of the step's serial tail)
-    int cnt[kSpec];
-    for (int j = 0; j < ns && j < kSpec; j++) {
-        cnt[j] = slot[j].build_left ? slot[j].nleft : slot[j].pcount - slot[j].nleft;
-        legacy += slot[j].nchunks; D += (unsigned)cnt[j];
-    }
-    const int T = c.balance_target, cap = c.balance_cap;
-    if (legacy <= c.balance_min) return;
-    const unsigned tcap = (unsigned)T * (unsigned)cap;
-    const int k = (int)(D / tcap + (D % tcap != 0u ? 1u : 0u));
-    const int target = k * T;
-    int cs = (int)((D / (unsigned)target + (D % (unsigned)target != 0u ? 1u : 0u) + 255u) & ~255u);
-    for (;;) {
-        if (cs > cap) cs = cap;
-        int tot = 0;
-        for (int j = 0; j < ns && j < kSpec; j++) tot += (cnt[j] + cs - 1) / cs;
-        if (tot <= target || cs >= cap) break;
-        cs += 256;
-    }
-    int tot = 0;
-    for (int j = 0; j < ns && j < kSpec; j++) tot += (cnt[j] + cs - 1) / cs;
-    if (tot > c.maxChunks) return;   // (the partial-histogram buffers hold maxChunks rows)
-    for (int j = 0; j < ns && j < kSpec; j++) { slot[j].cs = cs; slot[j].nchunks = (cnt[j] + cs - 1) / cs; }
-}
-
-__device__ __forceinline__ double variance_of(double sq, double sum, int n) { return sq - sum * sum / n; }  // :348-350
-
-__device__ __forceinline__ void copy_words(void *dst, const void *src, int nwords8)
-{
-    for (int i = threadIdx.x; i < nwords8; i += blockDim.x) ((unsigned long long *)dst)[i] = ((const unsigned long long *)src)[i];
-}
-
-__device__ __forceinline__ bool can_split(const Ctx &c, const NodeRec &X)
-{   // RegressionTree.fit :74-77 (too few samples) and FeatureHistogram.findBestSplit :267-269, :311-313
-    if (X.gcount < 2 * c.mls) return false;
-    const bool zero_dev = (X.deviance >= 0.0 && X.deviance <= 0.0);
-    return !(zero_dev || X.best_S == -1.0);
-}
-
-// lazy tie-break (rl_tie.inc): of the nodes about to be partitioned, those whose exactly tied best split the Java's rounding noise decides
-// and that have not been resolved yet -- several features tie (2), or only thresholds of one feature do (1) but the node is a RIGHT child,
-// whose Java histogram is parent - left (FeatureHistogram.java:222-234) instead of a sum of its own samples.  One thread calls this.
-// A tie of kind 1 in a right child does NOT stall: every tied threshold cuts off the same documents, so the node is partitioned at once and only
-// its stored threshold is re-decided, together with the tree's other such nodes, before the tree is exported (NodeRec::tie bit 0x40, `deferred`).
-__device__ __forceinline__ int stalled_nodes(NodeRec *N, const int *sel, int nsel, int32_t *out, int *deferred, bool xdefer)
-{
-    int n = 0;
-    for (int i = 0; i < nsel; i++) {
-        NodeRec &X = N[sel[i]];
-        if ((X.tie & 0xc0) || (X.tie & 3) == 0) continue;
-        const bool right = X.parent >= 0 && N[X.parent].pr == sel[i];
-        if ((X.tie & 3) == 2) {
-            if (xdefer && (X.tie & 4)) { X.tie |= 0x40; *deferred = 1; }       // several features, one cut: partition now, name the feature later
-            else out[n++] = sel[i];
-        } else if (right) { X.tie |= 0x40; *deferred = 1; }
-    }
-    return n;
-}
-
-// bytes of dynamic LDS select_step needs
-__host__ __device__ inline size_t select_lds_bytes(int L, int NC, bool nodes_in_lds, int F = 0, bool sampling = false)
-{
-    return sizeof(TreeState) + (nodes_in_lds ? (size_t)NC * sizeof(NodeRec) : 0) + (size_t)(L + 2) * 12 + (size_t)kSpec * 2 * 16 + 64 +
-           (sampling ? (size_t)2 * kSpec * F * 8 + 8 : 0);
-}
-
-// Called by every thread of ONE block (the last one of k_hist_finish).  smem: TreeState | NodeRec[NC] (only if it
-// fits, else the records are used in place) | qd[L+2] | bS[2 kSpec] | q[L+2] | bf, bt[2 kSpec] | sel[kSpec]
-// NL (node records in LDS) is a template parameter: with a run-time choice between the LDS copy and c.nodes every access to a record was a FLAT
-// load / store followed by a wait on both counters -- the fit loop's chain of dependent record reads ran at global-memory latency.
-template <bool NL, bool WIDE = false>
-__device__ __forceinline__ void select_step_t(const Ctx &c, bool is_root, unsigned char *smem, bool dist)
-{
-    constexpr bool nodes_in_lds = NL;
-    static_assert(sizeof(TreeState) % 16 == 0 && sizeof(NodeRec) % 8 == 0, "copied as 8-byte words");
-    TreeState &st = *(TreeState *)smem;
-    unsigned char *ptr = smem + sizeof(TreeState);
-    NodeRec *N = c.nodes;
-    if (nodes_in_lds) { N = (NodeRec *)ptr; ptr += (size_t)c.NC * sizeof(NodeRec); }
-    const int QC = c.L + 2;              // queue capacity
-    double *qd = (double *)ptr; ptr += (size_t)QC * 8;
-    double *bS = (double *)ptr; ptr += 2 * kSpec * 8;
-    int *q = (int *)ptr; ptr += (size_t)QC * 4;
-    int *bf = (int *)ptr; ptr += 2 * kSpec * 4;
-    int *bt = (int *)ptr; ptr += 2 * kSpec * 4;
-    int *sel = (int *)ptr; ptr += kSpec * 4;
-    unsigned long long *fkeys = (unsigned long long *)(((size_t)ptr + 7) & ~(size_t)7);      // [2 kSpec][F], only with feature sampling
-    __shared__ int bcl[2 * kSpec], btie[2 * kSpec]; __shared__ long long bhi[2 * kSpec]; __shared__ unsigned long long blo[2 * kSpec];
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6, nwaves = blockDim.x >> 6;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // see ld_agent
-#ifdef RL_PHASE_CLOCKS
-    { const long long t_ = strict_clock(); if (!is_root && threadIdx.x == 0) c.clk[(c.st->step & 63) * 32 + 14] = t_; }      // select entry
-#endif
-    copy_words(&st, c.st, sizeof(TreeState) / 8);
-    __syncthreads();
-    const int E = st.E, E2 = st.E2;
-
-    if (is_root) {
-        if (wave == 0) {
-            double S0; int f0, t0, cl0, tie0; long long hi0; unsigned long long lo0;
-            const unsigned long long h0 = root_hash(c.seed, st.tree_seq);       // tree_seq = trees started before this one
-            half_wave_best_feature(c, lane < 32, 0, 0, h0, fkeys, S0, f0, t0, cl0, hi0, lo0, tie0,
-                                   (long long)ld_agent((const unsigned long long *)&c.fb_root[0]), ld_agent((const unsigned long long *)&c.fb_root[1]), c.cum_cnt[(size_t)c.nthr[0] - 1]);
-            if (lane == 0) {
-                NodeRec R;
-                R.start = 0; R.count = c.N; R.buf = 0; R.parent = -1; R.left = R.right = -1;
-                R.gcount = c.cum_cnt[(size_t)c.nthr[0] - 1];            // global N (static counts; feature 0, last bin)
-                R.tot_hi = (long long)ld_agent((const unsigned long long *)&c.fb_root[0]); R.tot_lo = ld_agent((const unsigned long long *)&c.fb_root[1]);
-                // sharded: the all-reduced sum (st.root_sq stays this rank's own: a tree that is grown a second time reduces it again)
-                R.sq = c.sharded ? c.dist_buf[(size_t)c.F * c.TS * c.limb_words] : st.root_sq;
-                R.sum_response = fixed_to_double(make_i128(R.tot_hi, R.tot_lo), E);
-                R.sq_response = fixed_to_double((i128)R.sq, E2);
-                if (c.java) { R.sum_response = c.jtot[0]; R.sq_response = c.jtot[1]; }      // sequential sums over k = 0 .. N-1 (:133-137)
-                R.deviance = 3.4028234663852886e38;           // Float.MAX_VALUE  (RegressionTree.java:60)
-                R.best_S = S0; R.best_f = f0; R.best_t = t0; R.output = 0.f;
-                R.best_cl = cl0; R.best_hi = hi0; R.best_lo = lo0;
-                R.pl = R.pr = -1; R.fid = 0; R.prepared = 0; R.tie = c.fs_on ? 0 : tie0; R.ph = h0;
-                st.n_nodes = 1; st.qsize = 0; st.taken = 0; st.done = 0; st.nslots = 0; st.n_splits = 0; st.stall_n = 0; st.defer_any = 0;
-                st.step = 0; st.tree_seq++;
-                st.tiles_total = 0; st.chunks_total = 0; st.arrive = 0; st.epoch++;
-                for (int j = 0; j < kSpec * 16; j++) (&st.arrive1[0][0])[j] = 0;
-                N[0] = R;
-                if (S0 == -1.0) st.done = 1;                  // root cannot split: single-leaf tree (:64-67,86)
-                else if (c.tie_on && (R.tie & 3) == 2 && !((c.tie_on & 2) && (R.tie & 4))) { st.stall_n = 1; st.stall_node[0] = 0; }      // several features tie at the root: the Java's noise decides (rl_tie.inc)
-                else {
-                    if (c.tie_on && (R.tie & 3) == 2) { N[0].tie |= 0x40; st.defer_any = 1; }      // ... over one and the same cut: deferred
-                    prepare_children(c, N, 0, 1, st.slot[0]);
-                    balance_slots(c, st.slot, 1);
-                    st.n_nodes = 3; st.nslots = 1; st.tiles_total = st.slot[0].ntiles; st.chunks_total = st.slot[0].nchunks;
-                    c.grow_stats[0]++; c.grow_stats[1]++;
-                }
-                c.grow_stats[3]++;
-            }
-        }
-        __syncthreads();
-        if (nodes_in_lds) copy_words(c.nodes, N, st.n_nodes * (int)(sizeof(NodeRec) / 8));
-        copy_words(c.st, &st, sizeof(TreeState) / 8);
-        if (tid == 0 && c.progress)
-            __hip_atomic_store(c.progress, ((unsigned long long)(unsigned)st.tree_seq << 32) | (st.stall_n > 0 ? (1ull << 31) : 0ull) | (st.defer_any ? (1ull << 30) : 0ull) | (st.done ? 1ull : 0ull),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        return;
-    }
-
-    RL_CLK(true, 8);
-    // A. best split per (slot, side) by one wavefront each; LDS copies of the node records and the queue
-    const int ns = st.nslots, qs0 = st.qsize, nn0 = st.n_nodes;
-    long long sq_left_v = 0;        // unsharded: sum of lambda^2 over the left child, reduced from the partition's per-tile partials by block (0, slot)
-    if (!dist && tid < ns) sq_left_v = (long long)ld_agent(&c.fb_sq[tid]);
-    // the node records and the queue are fetched first: their loads are in flight while the per-feature records are reduced
-    constexpr int kPre = 8;
-    const int nw8 = nodes_in_lds ? nn0 * (int)(sizeof(NodeRec) / 8) : 0;
-    unsigned long long pre[kPre];
-#pragma unroll
-    for (int u = 0; u < kPre; u++) { const int i = tid + u * (int)blockDim.x; pre[u] = i < nw8 ? ((const unsigned long long *)c.nodes)[i] : 0ull; }
-    const int q_pre = tid < qs0 ? c.queue[tid] : 0;
-#ifdef RL_PHASE_CLOCKS
-    if (tid == 0) c.clk[(c.st->step & 63) * 32 + 16] = (long long)wall_clock64();      // (no wait: the loads above stay in flight)
-#endif
-    for (int p0 = 2 * wave; p0 < 2 * ns; p0 += 2 * nwaves) {
-        const int pi = p0 + (lane >> 5);
-        double S; int f, t, cl, tie; long long hi; unsigned long long lo;
-        unsigned long long h = 0;
-        if (c.fs_on && pi < 2 * ns) h = c.nodes[(pi & 1) ? st.slot[pi >> 1].right : st.slot[pi >> 1].left].ph;
-        long long nthi = 0; unsigned long long ntlo = 0; int nctot = 0;
-        if (c.tie_on && pi < 2 * ns) { const NodeRec &Ch = c.nodes[(pi & 1) ? st.slot[pi >> 1].right : st.slot[pi >> 1].left]; nthi = Ch.tot_hi; ntlo = Ch.tot_lo; nctot = Ch.gcount; }
-        half_wave_best_feature<WIDE>(c, pi < 2 * ns, pi >> 1, pi & 1, h, fkeys + (size_t)min(pi, 2 * kSpec - 1) * c.F, S, f, t, cl, hi, lo, tie, nthi, ntlo, nctot);
-        if ((lane & 31) == 0 && pi < 2 * ns) { bS[pi] = S; bf[pi] = f; bt[pi] = t; bcl[pi] = cl; bhi[pi] = hi; blo[pi] = lo; btie[pi] = c.fs_on ? 0 : tie; }
-    }
-    RL_CLK(true, 15);
-#pragma unroll
-    for (int u = 0; u < kPre; u++) { const int i = tid + u * (int)blockDim.x; if (i < nw8) ((unsigned long long *)N)[i] = pre[u]; }
-    for (int i = tid + kPre * (int)blockDim.x; i < nw8; i += blockDim.x) ((unsigned long long *)N)[i] = ((const unsigned long long *)c.nodes)[i];
-    if (tid < qs0) q[tid] = q_pre;
-    for (int i = tid + (int)blockDim.x; i < qs0; i += blockDim.x) q[i] = c.queue[i];
-    __syncthreads();
-    RL_CLK(true, 9);
-    // B. complete the children of the nodes prepared by the step that just ran (one thread per slot)
-    if (!dist) { if (tid < ns) st.slot[tid].sq_left = sq_left_v; }
-    else if (tid < ns) st.slot[tid].sq_left = c.dist_buf[(size_t)tid * ((size_t)c.F * c.TS * c.limb_words + 4) + (size_t)c.F * c.TS * c.limb_words];     // all-reduced
-    __syncthreads();
-    if (tid < ns) {
-        const SlotRec &sl = st.slot[tid];
-        NodeRec &P = N[sl.node]; NodeRec &Lc = N[sl.left]; NodeRec &Rc = N[sl.right];
-        if (sl.build_left) { Lc.sq = sl.sq_left; Rc.sq = P.sq - Lc.sq; }       // sq_left: the BUILT child's sum (k_part_scatter)
-        else { Rc.sq = sl.sq_left; Lc.sq = P.sq - Rc.sq; }
-        Lc.sum_response = fixed_to_double(make_i128(Lc.tot_hi, Lc.tot_lo), E);
-        Rc.sum_response = fixed_to_double(make_i128(Rc.tot_hi, Rc.tot_lo), E);
-        Lc.sq_response = fixed_to_double((i128)Lc.sq, E2);
-        Rc.sq_response = fixed_to_double((i128)Rc.sq, E2);
-        if (c.java) {       // left: sequential sums over its samples (:182-186); right: parent - left (:202-203)
-            Lc.sum_response = c.jtot[2 * tid]; Lc.sq_response = c.jtot[2 * tid + 1];
-            Rc.sum_response = P.sum_response - Lc.sum_response; Rc.sq_response = P.sq_response - Lc.sq_response;
-        }
-        Lc.deviance = variance_of(Lc.sq_response, Lc.sum_response, Lc.gcount);
-        Rc.deviance = variance_of(Rc.sq_response, Rc.sum_response, Rc.gcount);
-        Lc.best_S = bS[2 * tid]; Lc.best_f = bf[2 * tid]; Lc.best_t = bt[2 * tid];
-        Lc.best_cl = bcl[2 * tid]; Lc.best_hi = bhi[2 * tid]; Lc.best_lo = blo[2 * tid];
-        Rc.best_S = bS[2 * tid + 1]; Rc.best_f = bf[2 * tid + 1]; Rc.best_t = bt[2 * tid + 1];
-        Rc.best_cl = bcl[2 * tid + 1]; Rc.best_hi = bhi[2 * tid + 1]; Rc.best_lo = blo[2 * tid + 1];
-        Lc.tie = btie[2 * tid]; Rc.tie = btie[2 * tid + 1];
-    }
-    __syncthreads();
-    RL_CLK(true, 10);
-    // C. RegressionTree.fit's loop (:70-85), as far as prepared nodes allow, then the choice of the next slots.
-    if (QC <= 64) {
-        // Wavefront version: lane p holds queue entry p (node, deviance, can-split, prepared) in registers;
-        // insert = ballot + shift, pop = shift.  (A single lane walking LDS pays ~50 ns per dependent access.)
-        if (wave == 0) {
-            int qn = (lane < qs0) ? q[lane] : -1;
-            double qdv = 0.0; bool cs = false, prep = false;
-            if (qn >= 0) { const NodeRec &X = N[qn]; qdv = X.deviance; cs = can_split(c, X); prep = X.prepared != 0; }
-            int qsize = qs0, taken = st.taken, n_splits = st.n_splits, ncommit = 0;
-            const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-            auto insert = [&](int node, double d, bool ncs) {          // RegressionTree.insert (:147-157)
-                const int pos = __builtin_popcountll(__ballot(lane < qsize && qdv > d));
-                const int un = __shfl_up(qn, 1); const double ud = __shfl_up(qdv, 1);
-                const int uc = __shfl_up((int)cs, 1), up = __shfl_up((int)prep, 1);
-                if (lane > pos) { qn = un; qdv = ud; cs = uc != 0; prep = up != 0; }
-                else if (lane == pos) { qn = node; qdv = d; cs = ncs; prep = false; }
-                qsize++;
-            };
-            auto pop = [&]() {
-                qn = __shfl_down(qn, 1); qdv = __shfl_down(qdv, 1);
-                cs = __shfl_down((int)cs, 1) != 0; prep = __shfl_down((int)prep, 1) != 0;
-                qsize--;
-            };
-            // a split becomes part of the tree: sp.set(.., var) (:352), children enter the queue (:66-67, :82-83)
-            auto commit = [&](int p) {
-                NodeRec &X = N[p];
-                const int l = X.pl, r = X.pr;
-                const int child = (lane == 0) ? l : r;
-                double dch = 0.0; int cch = 0;
-                if (lane < 2) { dch = N[child].deviance; cch = can_split(c, N[child]) ? 1 : 0; }
-                const double dl = __shfl(dch, 0), dr = __shfl(dch, 1);
-                const int csl = __shfl(cch, 0), csr = __shfl(cch, 1);
-                if (lane == 0) {
-                    X.left = l; X.right = r;
-                    X.deviance = variance_of(X.sq_response, X.sum_response, X.gcount);
-                    N[l].fid = 2 * n_splits + 1; N[r].fid = 2 * n_splits + 2;
-                    c.grow_docs[2] += (unsigned long long)N[l].gcount; c.grow_docs[3] += (unsigned long long)X.gcount;
-                    if (c.steplog && X.tie) {       // debug: committed splits whose best candidate was tied, and the Java-order derivation chain they hang on
-                        const int e = atomicAdd(&c.steplog[0], 1);
-                        if (e < kStepLogCap) {
-                            int *o = c.steplog + 8 + 8 * e;
-                            int cur = p, nchain = 1, mx = X.gcount; long long tot = X.gcount;
-                            const bool is_right = X.parent >= 0 && N[X.parent].pr == p;
-                            while (N[cur].parent >= 0 && N[N[cur].parent].pr == cur) {       // a right child: parent - left sibling
-                                const int par = N[cur].parent, sib = N[par].pl;
-                                mx = max(mx, N[sib].gcount); tot += N[sib].gcount; nchain++;
-                                cur = par;
-                            }
-                            if (cur != p) { mx = max(mx, N[cur].gcount); tot += N[cur].gcount; nchain++; }
-                            o[0] = st.tree_seq; o[1] = 1; o[2] = X.tie & 255; o[3] = (is_right ? 1 : 0) | ((X.tie >> 8) << 1); o[4] = X.gcount; o[5] = mx; o[6] = nchain; o[7] = (int)min(tot, (long long)0x7fffffff);
-                        }
-                    }
-                }
-                n_splits++; ncommit++;
-                insert(l, dl, csl != 0);
-                insert(r, dr, csr != 0);
-            };
-            if (ns == 1 && st.slot[0].node == 0) commit(0);              // the root is split unconditionally (:62-67)
-            bool done = true;
-            while (taken + qsize < c.L && qsize > 0) {
-                const int leaf = __shfl(qn, 0);
-                const bool cs0 = __shfl((int)cs, 0) != 0, prep0 = __shfl((int)prep, 0) != 0;
-                if (!cs0) { pop(); taken++; continue; }
-                if (prep0) { pop(); commit(leaf); continue; }
-                done = false;
-                break;
-            }
-            // next step: the first kSpec unprepared nodes in queue order that the leaf budget can still reach
-            int nsel = 0, err = 0;
-            if (!done) {
-                const int budget = c.L - (taken + qsize);                         // splits left (>= 1)
-                const bool inq = lane < qsize;
-                const int ahead = __builtin_popcountll(__ballot(inq && cs) & below);          // splittable nodes before p
-                const bool cand = inq && cs && !prep && ahead < budget;
-                const unsigned long long cmask = __ballot(cand);
-                const int rank = __builtin_popcountll(cmask & below);
-                nsel = min(__builtin_popcountll(cmask), kSpec);
-                while (nsel > 0 && nn0 + 2 * nsel > c.NC) nsel--;
-                if (cand && rank < nsel) sel[rank] = qn;
-                if (nsel == 0) { done = true; err = 1; }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            int nstall = 0;
-            if (c.tie_on && lane == 0) nstall = stalled_nodes(N, sel, nsel, st.stall_node, &st.defer_any, (c.tie_on & 2) != 0);
-            nstall = __shfl(nstall, 0);
-            if (nstall > 0) nsel = 0;                 // nothing is partitioned until the host has resolved the ties (rl_tie.inc)
-            if (lane == 0) st.stall_n = nstall;
-            if (lane < qsize) c.queue[lane] = qn;
-            if (lane == 0) {
-                st.done = done ? 1 : 0; if (err && !st.error) st.error = 1;
-                st.nslots = nsel; st.qsize = qsize; st.taken = taken; st.n_splits = n_splits;
-                c.grow_stats[2] += ncommit;
-                if (nsel > 0) { c.grow_stats[0]++; c.grow_stats[1] += nsel; }
-            }
-        }
-    } else {
-        for (int i = tid; i < qs0; i += blockDim.x) qd[i] = N[q[i]].deviance;
-        __syncthreads();
-        if (tid == 0) {       // serial version for very wide trees
-            int head = 0, qsize = qs0, ncommit = 0;
-            auto commit = [&](int p) {
-                NodeRec &X = N[p];
-                X.left = X.pl; X.right = X.pr;
-                X.deviance = variance_of(X.sq_response, X.sum_response, X.gcount);
-                N[X.left].fid = 2 * st.n_splits + 1; N[X.right].fid = 2 * st.n_splits + 2;
-                c.grow_docs[2] += (unsigned long long)N[X.left].gcount; c.grow_docs[3] += (unsigned long long)X.gcount;
-                st.n_splits++;
-                ncommit++;
-                int n = qsize - head;
-                queue_insert_lds(q + head, qd + head, n, X.left, N[X.left].deviance);
-                queue_insert_lds(q + head, qd + head, n, X.right, N[X.right].deviance);
-                qsize = head + n;
-            };
-            if (ns == 1 && st.slot[0].node == 0) commit(0);
-            bool done = true;
-            while ((c.L == -1 || st.taken + (qsize - head) < c.L) && (qsize - head) > 0) {
-                const int leaf = q[head];
-                const NodeRec &X = N[leaf];
-                if (!can_split(c, X)) { head++; st.taken++; continue; }
-                if (X.prepared) { head++; commit(leaf); continue; }
-                done = false;
-                break;
-            }
-            st.done = done ? 1 : 0;
-            int nsel = 0;
-            if (!done) {
-                const int budget = (c.L == -1) ? 0x7fffffff : c.L - (st.taken + (qsize - head));
-                int ahead = 0;
-                for (int p = head; p < qsize && nsel < kSpec && ahead < budget; p++) {
-                    const NodeRec &X = N[q[p]];
-                    if (!can_split(c, X)) continue;
-                    ahead++;
-                    if (X.prepared) continue;
-                    if (nn0 + 2 * (nsel + 1) > c.NC) { if (nsel == 0) st.error = 1; break; }
-                    sel[nsel++] = q[p];
-                }
-                if (nsel == 0) { st.done = 1; if (!st.error) st.error = 2; }
-            }
-            st.stall_n = c.tie_on ? stalled_nodes(N, sel, nsel, st.stall_node, &st.defer_any, (c.tie_on & 2) != 0) : 0;
-            if (st.stall_n > 0) nsel = 0;
-            st.nslots = nsel;
-            st.qsize = qsize - head;
-            for (int i = 0; i < st.qsize; i++) c.queue[i] = q[head + i];
-            c.grow_stats[2] += ncommit;
-            if (nsel > 0) { c.grow_stats[0]++; c.grow_stats[1] += nsel; }
-        }
-    }
-    __syncthreads();
-    RL_CLK(true, 11);
-    // D. children records of the selected nodes (one thread per slot: the histogram reads are independent)
-    const int nsel = st.nslots;
-    if (tid < nsel) prepare_children(c, N, sel[tid], nn0 + 2 * tid, st.slot[tid]);
-    if (c.steplog && tid < nsel) {        // debug: what every growth step works on
-        const int e = atomicAdd(&c.steplog[0], 1);
-        if (e < kStepLogCap) {
-            int *o = c.steplog + 8 + 8 * e; const NodeRec &P = N[sel[tid]];
-            o[0] = st.tree_seq; o[1] = 0; o[2] = st.step + 1; o[3] = tid; o[4] = P.gcount; o[5] = st.slot[tid].build_left ? P.best_cl : P.gcount - P.best_cl; o[6] = P.tie; o[7] = nsel;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int tiles = 0, chunks = 0;
-        balance_slots(c, st.slot, nsel);
-        for (int j = 0; j < nsel; j++) {
-            st.slot[j].tile0 = tiles; tiles += st.slot[j].ntiles;
-            st.slot[j].chunk0 = chunks; chunks += st.slot[j].nchunks;
-        }
-        st.tiles_total = tiles; st.chunks_total = chunks;
-        st.n_nodes = nn0 + 2 * nsel;
-        st.arrive = 0; st.epoch++;
-        for (int j = 0; j < kSpec * 16; j++) (&st.arrive1[0][0])[j] = 0;
-    }
-    __syncthreads();
-    RL_CLK(true, 12);
-    if (nodes_in_lds) copy_words(c.nodes, N, st.n_nodes * (int)(sizeof(NodeRec) / 8));
-    RL_CLK(true, 13);
-#ifdef RL_PHASE_CLOCKS
-    if (tid == 0 && st.tree_seq == c.trace_tree) c.clk[(st.step & 63) * 32 + 28] = (long long)wall_clock64();      // end of this step's bookkeeping
-#endif
-    if (tid == 0) st.step++;
-    __syncthreads();
-    copy_words(c.st, &st, sizeof(TreeState) / 8);
-    // tell the host how far the tree is (relaxed system-scope store: no fence, nothing else is read through it)
-    if (tid == 0 && c.progress)
-        __hip_atomic_store(c.progress, ((unsigned long long)(unsigned)st.tree_seq << 32) | (st.stall_n > 0 ? (1ull << 31) : 0ull) | (st.defer_any ? (1ull << 30) : 0ull) |
-                                           ((unsigned long long)((unsigned)st.step & 0x1fffffffu) << 1) | (st.done ? 1ull : 0ull),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-template <bool WIDE = false>
-__device__ __forceinline__ void select_step(const Ctx &c, bool is_root, unsigned char *smem, bool nodes_in_lds, bool dist)
-{
-    if (nodes_in_lds) select_step_t<true, WIDE>(c, is_root, smem, dist);
-    else select_step_t<false, WIDE>(c, is_root, smem, dist);
-}
-
-// SELECT: the last block to arrive runs select_step (one launch per growth step's finish).  !SELECT: the per-feature work only; the bookkeeping
-// follows as a launch of its own (k_select) -- for wide data, see k_hist_finish_wide.
-constexpr int kFinWideThreads = 192;     // three wavefronts: 10 blocks a CU at 8 wavefronts per SIMD (2 560 resident blocks)
-template <bool ROOT, bool DIST, bool JAVA, bool SELECT>
-__device__ __forceinline__ void hist_finish_body(const Ctx &c, int nodes_in_lds, unsigned long long *sh_raw)
-{   // grid (F, slots)
-    TreeState *st = c.st;
-    RL_TR_BEGIN();
-    constexpr int kNT = SELECT ? kFinThreads : kFinWideThreads;      // threads of the block (blockDim.x is a load from the dispatch packet)
-    // B = the node whose histogram was accumulated from its samples, S = its sibling (= parent - B)
-    int nodeB = 0, nodeS = -1, nodeP = -1, sideB = 0, ch0 = 0;
-    const int slot = blockIdx.y;
-    // everything the block needs from the step's tables is requested at once (the slot record is copied whole, valid or not: slot < kSpec), and the
-    // feature's threshold count comes from a table parallel to `live`: each of these was a dependent memory round trip at the top of every block
-    const int st_done = st->done, st_nslots = st->nslots, E = st->E;
-#ifndef RL_FIN_BATCH
-#define RL_FIN_BATCH 1
-#endif
-#if RL_FIN_BATCH
-    SlotRec sl_c;
-    if (!ROOT) sl_c = st->slot[slot];
-#else
-    const SlotRec &sl_c = st->slot[ROOT ? 0 : slot];
-#endif
-    const int f = (!DIST && c.live) ? c.live[blockIdx.x] : (int)blockIdx.x;
-    const int TS = c.TS, T = (!DIST && c.live) ? c.live_nthr[blockIdx.x] : c.nthr[f];
-    if (!ROOT) {
-        if (st_done || slot >= st_nslots) return;
-        const SlotRec &sl = sl_c;
-        nodeP = sl.node; ch0 = sl.chunk0;
-        if (sl.build_left) { nodeB = sl.left; nodeS = sl.right; sideB = 0; }
-        else { nodeB = sl.right; nodeS = sl.left; sideB = 1; }
-    }
-    [[maybe_unused]] const bool clk0 = !ROOT && blockIdx.x == 0 && blockIdx.y == 0;
-    RL_CLK(clk0, 0);
-    RL_TR_MARK(1);
-    long long *s_hi = (long long *)sh_raw;
-    unsigned long long *s_lo = sh_raw + TS;
-    int *s_cnt = (int *)(sh_raw + 2 * TS);
-    [[maybe_unused]] double *s_j = (double *)((unsigned char *)sh_raw + (((size_t)TS * 20 + 7) & ~(size_t)7));   // JAVA: f64 cumulative sums of the left child / the root
-    // the parent's cumulative entries, kept as the gain scan reads them: the tie check and the sibling's published record used to fetch theirs from memory again
-    // (a dependent round trip each, at the end of every block)
-    unsigned char *s_par = (unsigned char *)sh_raw + (((size_t)TS * 20 + 7) & ~(size_t)7) + (JAVA ? (size_t)TS * 8 : 0);
-    [[maybe_unused]] long long *s_phi = (long long *)s_par;
-    [[maybe_unused]] unsigned long long *s_plo = (unsigned long long *)(s_par + (size_t)TS * 8);
-    [[maybe_unused]] int *s_pcn = (int *)(s_par + (size_t)TS * 16);
-    const bool pcache = TS <= kParCacheTS;          // (threshold tables beyond that keep the old behaviour: twice the LDS would not fit a CU at -tc 4095)
-    __shared__ Best sh_best[2 * (kFinThreads / 64)];
-    __shared__ i128 sh_red[kFinThreads / 64];
-    __shared__ int sh_redc[kFinThreads / 64];
-
-    // block (0, slot) also folds the partition's per-tile lambda^2 partials of its slot (select_step used to do that in the serial tail)
-    __shared__ long long sh_sqw[kFinThreads / 64];
-    long long sqacc = 0;
-    const bool sq_block = !ROOT && !DIST && blockIdx.x == 0;
-    if (sq_block) {
-        const SlotRec &sl = sl_c;
-        // (eight per thread and trip, unconditional from a clamped index: one at a time the 1 841 tile partials of a 3.8 M-document parent were six serial round trips)
-        constexpr int kSqBatch = 8;
-        for (int i0 = (int)threadIdx.x; i0 < sl.ntiles; i0 += kSqBatch * kNT) {
-            long long v[kSqBatch];
-#pragma unroll
-            for (int u = 0; u < kSqBatch; u++) v[u] = c.tile_sq[sl.tile0 + min(i0 + u * kNT, sl.ntiles - 1)];
-#pragma unroll
-            for (int u = 0; u < kSqBatch; u++) if (i0 + u * kNT < sl.ntiles) sqacc += v[u];
-        }
-    }
-    int cntB_ = ROOT ? c.N : 0;
-    if (!ROOT) {
-        const SlotRec &slb = sl_c;
-        cntB_ = (slb.nleft >= 0) ? (slb.build_left ? slb.nleft : slb.pcount - slb.nleft) : c.nodes[nodeB].count;      // one GPU: known from the slot
-    }
-    const int cntB = cntB_;
-    const int csB = (!ROOT && sl_c.cs > 0) ? sl_c.cs : chunk_docs<ROOT>(c, cntB);      // (balance_slots)
-    const int nch = (cntB + csB - 1) / csB;
-    const size_t slotB = ((size_t)nodeB * c.F + f) * TS;
-    // the parent's cumulative entry this thread needs in the gain scan: requested now, with the chunk partials, not after the prefix
-    // (every gain-scan iteration of the thread: two with the 192-thread blocks of k_hist_finish_wide and 257 bins)
-    constexpr int kPreIt = SELECT ? 1 : 2;
-    long long pre_phi[kPreIt]; unsigned long long pre_plo[kPreIt]; int pre_pcnt[kPreIt];
-#pragma unroll
-    for (int u = 0; u < kPreIt; u++) {
-        pre_phi[u] = 0; pre_plo[u] = 0; pre_pcnt[u] = 0;
-        if (RL_FIN_BATCH && !ROOT) {
-            const size_t o = ((size_t)nodeP * c.F + f) * TS + min((int)threadIdx.x + u * kNT, TS - 1);       // (clamped, unconditional)
-            pre_phi[u] = c.cum_hi[o]; pre_plo[u] = c.cum_lo[o]; pre_pcnt[u] = c.cum_cnt[o];
-        }
-    }
-    // ... the parent's totals (its last cumulative entry; the same address for every thread) ...
-    long long tp_hi = 0; unsigned long long tp_lo = 0; int tp_cn = 0;
-    if (!ROOT) { const size_t o = ((size_t)nodeP * c.F + f) * TS + (T - 1); tp_hi = c.cum_hi[o]; tp_lo = c.cum_lo[o]; tp_cn = c.cum_cnt[o]; }
-    // ... and what the mode-bin rebuild needs: this thread's chunk total and the feature's mode bin
-    long long pre_tot = 0; int pre_mode = 0;
-    if (!DIST) { pre_tot = c.part_tot[ch0 + max(min((int)threadIdx.x, nch - 1), 0)]; pre_mode = c.mode[f]; }
-    if (DIST) {     // totals were reduced over the chunks by k_hist_reduce and over the ranks by the all-reduce
-        const int W = c.limb_words;
-        const size_t slot_words = (size_t)c.F * TS * W + 4;
-        const long long *in = c.dist_buf + slot * slot_words + (size_t)f * TS * W;
-        for (int t = threadIdx.x; t < T; t += kNT) {
-            long long hi, lo, cn;
-            if (W == 3) { hi = in[3 * t]; lo = in[3 * t + 1]; cn = in[3 * t + 2]; }
-            else { const long long w0 = in[2 * t]; cn = w0 & 0xffffffffll; hi = w0 >> 32; lo = in[2 * t + 1]; }   // the counts of all ranks sum to < 2^31
-            const i128 acc = (((i128)hi) << kLimbShift) + (i128)lo;
-            s_hi[t] = hi_of(acc); s_lo[t] = lo_of(acc); s_cnt[t] = (int)cn;
-        }
-    } else {
-        const size_t cstride = (size_t)c.F * TS;
-        for (int t = threadIdx.x; t < T; t += kNT) {
-            i128 acc = 0;
-            int cacc = 0;
-            const long long *ps = c.part_sum + ((size_t)ch0 * c.F + f) * TS + t;
-            const int *pc = c.part_cnt + ((size_t)ch0 * c.F + f) * TS + t;
-            // Latency-bound: kFinBatch chunk partials are requested before the first is used (the 64-bit halves are summed separately so that no carry chain
-            // ties a load to the previous one).  The loads are written as a batch of their own, unconditional, from a clamped chunk index: left to the scheduler
-            // under k_hist_finish_wide's 64-register cap every load was completed before the next was issued (ten serial round trips for the five chunks of a
-            // c3 node: 10 of the block's 22 us).
-            constexpr int kFinBatch = ROOT ? 32 : (SELECT ? 16 : 8);        // (the root pass has hundreds of chunks and no counts to load)
-            unsigned long long lo = 0; long long hi = 0;
-            for (int ch = 0; ch < nch; ch += kFinBatch) {
-                long long v[kFinBatch]; int cn[kFinBatch];
-#pragma unroll
-                for (int u = 0; u < kFinBatch; u++) {
-                    const size_t o = (size_t)min(ch + u, nch - 1) * cstride;
-                    v[u] = ps[o];
-                    cn[u] = ROOT ? 0 : pc[o];
-                }
-#pragma unroll
-                for (int u = 0; u < kFinBatch; u++)
-                    if (ch + u < nch) { lo += (unsigned long long)(unsigned)v[u]; hi += (v[u] >> 32); cacc += cn[u]; }
-            }
-            acc += (i128)lo + (((i128)hi) << 32);
-            s_hi[t] = hi_of(acc); s_lo[t] = lo_of(acc); s_cnt[t] = cacc;
-        }
-    }
-    if (JAVA) for (int t = threadIdx.x; t < T; t += kNT) s_j[t] = c.jbin[((size_t)slot * c.F + f) * TS + t];
-    if (sq_block) {
-        for (int o = 32; o > 0; o >>= 1) sqacc += __shfl_xor(sqacc, o);
-        if (lane_id() == 0) sh_sqw[threadIdx.x >> 6] = sqacc;
-    }
-    __syncthreads();
-    if (sq_block && threadIdx.x == 0) { sqacc = 0; for (int w = 0; w < (kNT >> 6); w++) sqacc += sh_sqw[w]; }
-    RL_CLK(clk0, 1);
-    RL_TR_MARK(2);
-    if (!DIST) rebuild_mode_bin(c, f, T, ch0, nch, cntB, !ROOT, s_hi, s_lo, s_cnt, sh_red, sh_redc, true, pre_tot, pre_mode);
-    RL_CLK(clk0, 2);
-    // prefix over t by wavefront 0: lane-local segment scan + wave scan of segment totals
-    if (threadIdx.x < 64) {
-        const int seg = (T + 63) / 64;
-        const int b0 = min((int)threadIdx.x * seg, T), b1 = min(b0 + seg, T);
-        i128 run = 0; int crun = 0;
-        for (int t = b0; t < b1; t++) {
-            run += make_i128(s_hi[t], s_lo[t]); crun += s_cnt[t];
-            s_hi[t] = hi_of(run); s_lo[t] = lo_of(run); s_cnt[t] = crun;
-        }
-        i128 inc = run; int cinc = crun;
-        for (int d = 1; d < 64; d <<= 1) {
-            i128 u = shfl_up_i128(inc, d); int cu = __shfl_up(cinc, d);
-            if ((int)threadIdx.x >= d) { inc += u; cinc += cu; }
-        }
-        const i128 off = inc - run; const int coff = cinc - crun;
-        for (int t = b0; t < b1; t++) {
-            const i128 v = make_i128(s_hi[t], s_lo[t]) + off;
-            s_hi[t] = hi_of(v); s_lo[t] = lo_of(v); s_cnt[t] += coff;
-        }
-    } else if (JAVA && threadIdx.x == 64) {
-        // sum[f][t] += sum[f][t-1] for t = 1 .. T-1, in that order (FeatureHistogram.java:141-145,189-194): one dependent chain
-        double run = s_j[0];
-        for (int t = 1; t < T; t++) { run = s_j[t] + run; s_j[t] = run; }
-    }
-    __syncthreads();
-
-    RL_CLK(clk0, 3);
-    RL_TR_MARK(3);
-    const size_t slotP = ROOT ? 0 : ((size_t)nodeP * c.F + f) * TS;
-    const size_t slotS = ROOT ? 0 : ((size_t)nodeS * c.F + f) * TS;
-    // node totals = last cumulative bin (identical for every feature because the sums are exact)
-    const i128 totB = make_i128(s_hi[T - 1], s_lo[T - 1]);
-    i128 totS = 0;
-    int ctotB, ctotS = 0;
-    if (ROOT) {
-        ctotB = c.cum_cnt[slotB + T - 1];
-    } else {
-        ctotB = s_cnt[T - 1];
-        totS = make_i128(tp_hi, tp_lo) - totB;
-        ctotS = tp_cn - ctotB;
-    }
-    double sumB = fixed_to_double(totB, E), sumS = fixed_to_double(totS, E);
-    if (JAVA) {
-        // node totals in the Java's order: the built (left) node's sumResponse is the sequential sum over its samples, the right
-        // sibling's is parent - left (:202-203); B / S are whichever of the two the exact path accumulated / derived
-        const double sumL = c.jtot[2 * slot];
-        const double sumR = ROOT ? 0.0 : c.nodes[nodeP].sum_response - sumL;
-        sumB = (sideB == 0) ? sumL : sumR; sumS = (sideB == 0) ? sumR : sumL;
-    }
-    Best bb = {-1.0, -1}, bs = {-1.0, -1};
-    bool eqb = false, eqs = false;        // a later threshold of this thread reaches the thread's best S exactly
-    bool eqbd = false, eqsd = false;      // ... with another left count (different sample sets: only possible beyond kFinThreads thresholds)
-    int bbc = 0, bsc = 0;                 // left counts at the thread's best candidates
-    for (int t = threadIdx.x; t < T; t += kNT) {
-        const i128 vb = make_i128(s_hi[t], s_lo[t]);
-        c.cum_hi[slotB + t] = s_hi[t]; c.cum_lo[slotB + t] = s_lo[t];
-        int cb;
-        if (ROOT) cb = c.cum_cnt[slotB + t];
-        else { cb = s_cnt[t]; c.cum_cnt[slotB + t] = cb; }
-        bool ok;
-        double vbd, vsd = 0.0;
-        if (JAVA) {
-            const double jl_t = s_j[t];                                                  // left child (or root), cumulative
-            const double jr_t = ROOT ? 0.0 : c.jcum[slotP + t] - jl_t;                   // FeatureHistogram.java:230
-            vbd = (sideB == 0) ? jl_t : jr_t; vsd = (sideB == 0) ? jr_t : jl_t;
-            c.jcum[slotB + t] = vbd;
-            if (!ROOT) c.jcum[slotS + t] = vsd;
-        } else vbd = fixed_to_double(vb, E);
-        double S = gain_S(vbd, cb, sumB, ctotB, c.mls, ok);
-        if (ok && S == bb.S) { eqb = true; eqbd |= (cb != bbc); }
-        if (ok && S > bb.S) { bb.S = S; bb.t = t; bbc = cb; eqb = false; eqbd = false; }
-        if (!ROOT) {
-            const int it = (t - (int)threadIdx.x) / kNT;
-            long long phi; unsigned long long plo; int pcn;
-            if (RL_FIN_BATCH && it == 0) { phi = pre_phi[0]; plo = pre_plo[0]; pcn = pre_pcnt[0]; }
-            else if (RL_FIN_BATCH && kPreIt > 1 && it == 1) { phi = pre_phi[kPreIt - 1]; plo = pre_plo[kPreIt - 1]; pcn = pre_pcnt[kPreIt - 1]; }
-            else { phi = c.cum_hi[slotP + t]; plo = c.cum_lo[slotP + t]; pcn = c.cum_cnt[slotP + t]; }
-            if (pcache) { s_phi[t] = phi; s_plo[t] = plo; s_pcn[t] = pcn; }
-            const i128 vs = make_i128(phi, plo) - vb;      // FeatureHistogram.java:230-231
-            const int cs2 = pcn - cb;
-            c.cum_hi[slotS + t] = hi_of(vs); c.cum_lo[slotS + t] = lo_of(vs); c.cum_cnt[slotS + t] = cs2;
-            if (!JAVA) vsd = fixed_to_double(vs, E);
-            S = gain_S(vsd, cs2, sumS, ctotS, c.mls, ok);
-            if (ok && S == bs.S) { eqs = true; eqsd |= (cs2 != bsc); }
-            if (ok && S > bs.S) { bs.S = S; bs.t = t; bsc = cs2; eqs = false; eqsd = false; }
-        }
-    }
-    RL_CLK(clk0, 4);
-    RL_TR_MARK(4);
-    const Best myb = bb, mys = bs;
-    block_best2(bb, bs, sh_best, kNT >> 6);
-    // exact ties inside the feature: some other threshold reaches the winner's S bit for bit (the same two sample sets: an empty-bin plateau).
-    // The first one wins here as in the Java -- unless the Java's node histogram is a difference (a right child), see rl_tie.inc
-    // (__syncthreads_or answers "any thread non-zero", not the bitwise OR of the arguments: one call per side)
-    int tiebits = 0;
-    if (!JAVA) {
-        tiebits = __syncthreads_or((myb.t >= 0 && myb.S == bb.S && (myb.t != bb.t || eqb)) ? 1 : 0) ? 1 : 0;
-        if (!ROOT) tiebits |= __syncthreads_or((mys.t >= 0 && mys.S == bs.S && (mys.t != bs.t || eqs)) ? 1 : 0) ? 2 : 0;
-        // Do all tied thresholds cut off the SAME documents?  Thresholds of one feature are nested, so an equal left count means identical sets:
-        // the partition is then known whatever the Java's noise picks and only the stored threshold has to wait for it (rl_tie.inc: deferred).
-        if (tiebits & 1) {
-            const int wc = ROOT ? c.cum_cnt[slotB + bb.t] : s_cnt[bb.t];
-            if (__syncthreads_or((myb.t >= 0 && myb.S == bb.S && ((myb.t != bb.t && bbc != wc) || eqbd)) ? 1 : 0)) tiebits |= 4;
-        }
-        if (tiebits & 2) {
-            const int wc = (pcache ? s_pcn[bs.t] : c.cum_cnt[slotP + bs.t]) - s_cnt[bs.t];
-            if (__syncthreads_or((mys.t >= 0 && mys.S == bs.S && ((mys.t != bs.t && bsc != wc) || eqsd)) ? 1 : 0)) tiebits |= 8;
-        }
-    }
-    RL_CLK(clk0, 5);
-    RL_TR_MARK(5);
-
-    // publish this feature's results, then count the block as arrived; the last block runs the growth bookkeeping
-    __shared__ int sh_last;
-    if (threadIdx.x == 0) {
-        {
-            const int t = max(bb.t, 0);
-            publish_best(c, slot, sideB, f, bb.S, bb.t, ROOT ? c.cum_cnt[slotB + t] : s_cnt[t], s_hi[t], s_lo[t], (tiebits & 1) | ((tiebits >> 1) & 2));
-        }
-        if (!ROOT) {
-            const int t = max(bs.t, 0);
-            const i128 vs = (pcache ? make_i128(s_phi[t], s_plo[t]) : make_i128(c.cum_hi[slotP + t], c.cum_lo[slotP + t])) - make_i128(s_hi[t], s_lo[t]);
-            publish_best(c, slot, 1 - sideB, f, bs.S, bs.t, (pcache ? s_pcn[t] : c.cum_cnt[slotP + t]) - s_cnt[t], hi_of(vs), lo_of(vs), ((tiebits >> 1) & 1) | ((tiebits >> 2) & 2));
-        }
-        if (sq_block) st_agent(&c.fb_sq[slot], (unsigned long long)sqacc);
-        if (ROOT && blockIdx.x == 0) { st_agent((unsigned long long *)&c.fb_root[0], (unsigned long long)hi_of(totB)); st_agent((unsigned long long *)&c.fb_root[1], lo_of(totB)); }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        RL_CLK(clk0, 6);
-        if (!ROOT) RL_TR_END(2, blockIdx.y * gridDim.x + blockIdx.x);
-        if (!SELECT) return;
-        // two-level arrival: hundreds of blocks on ONE counter serialise in L2 (the last block saw ~11 us of it); <= 16 groups
-        // of features per slot count first, the last block of a group counts on the top-level word
-        const int F = (int)gridDim.x, gs = (F + 15) / 16, grp = (int)blockIdx.x / gs, ngrp = (F + gs - 1) / gs;
-        const int in_grp = min(gs, F - grp * gs);
-        sh_last = 0;
-        // (release on arrival, acquire for the block that arrives last: ADVICE r04 -- the relaxed form rested on every producer store being a write-through
-        // st_agent and on the consumer's one acquire fence; the fused kernel is the fall-back path since round 5 / 6, the ordering costs it nothing measurable)
-        if (__hip_atomic_fetch_add(&st->arrive1[slot][grp], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == in_grp - 1) {
-            const int target = ROOT ? ngrp : ngrp * st_nslots;
-            sh_last = (__hip_atomic_fetch_add(&st->arrive, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == target - 1) ? 1 : 0;
-        }
-    }
-    RL_CLK(clk0, 7);
-    if (!SELECT) return;
-    __syncthreads();
-    if (!sh_last) return;
-    // the growth steps' fused kernel carries ONE instantiation of the bookkeeping (node records in LDS: the host takes the two-launch path when
-    // they do not fit, enqueue_growth_step) -- its speed depends on its size: a second inlined copy costs scalar spills and scratch in every block
-    if (!ROOT && !DIST && !JAVA) select_step_t<true>(c, false, (unsigned char *)sh_raw, false);
-    else select_step(c, ROOT, (unsigned char *)sh_raw, nodes_in_lds != 0, DIST);
-}
-
-template <bool ROOT, bool DIST, bool JAVA = false>
-#ifndef RL_FIN_WAVES
-#define RL_FIN_WAVES 4
-#endif
-#if RL_FIN_WAVES
-__attribute__((amdgpu_waves_per_eu(RL_FIN_WAVES)))
-#endif
-__global__ __launch_bounds__(kFinThreads) void k_hist_finish(const Ctx c, int nodes_in_lds)
-{   // grid (F, slots); the last block to arrive also runs select_step
-    extern __shared__ unsigned long long sh_raw[];
-    hist_finish_body<ROOT, DIST, JAVA, true>(c, nodes_in_lds, sh_raw);
-}
-
-// Wide data (hundreds of live features x kSpec slots = thousands of blocks a step): the bookkeeping that ONE block runs sets the register budget of
-// all of them (96 VGPRs = 5 blocks a CU = 1280 resident blocks: a step's blocks came in two rounds and the last block waited 15-45 us for the
-// second).  Without it the per-feature work needs 56 registers: 8 blocks a CU, one round; select_step then costs a launch of its own (~5 us).
-__attribute__((amdgpu_waves_per_eu(8)))
-__global__ __launch_bounds__(kFinWideThreads) void k_hist_finish_wide(const Ctx c)
-{
-    extern __shared__ unsigned long long sh_raw[];
-    hist_finish_body<false, false, false, false>(c, 0, sh_raw);
-}
-__global__ __launch_bounds__(kFinThreads) void k_select(const Ctx c, int nodes_in_lds)
-{
-    extern __shared__ unsigned long long sh_raw[];
-    if (c.st->done || c.st->nslots <= 0) return;        // a finished or stalled tree: the step is empty (the fused kernel's blocks all leave before they arrive)
-    select_step<true>(c, false, (unsigned char *)sh_raw, nodes_in_lds != 0, false);
-}
-
-// ------------------------------------------------------------------------------------------------
-// K6: stable partition of the sample lists of the step's nodes by bin[f*][k] <= t*.  grid = tiles of all slots.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_part_count(const Ctx c)
-{   // sharded runs only: left members per tile
-    const TreeState *st = c.st;
-    const int j = slot_of_tile(st, blockIdx.x);
-    if (j < 0) return;
-    const SlotRec &sl = st->slot[j];
-    const int cnt = sl.pcount, t = sl.t;
-    const bool root = (sl.node == 0);
-    const int *src = root ? nullptr : c.idx[sl.pbuf] + sl.pstart;
-    const int base = (blockIdx.x - sl.tile0) * kPartTile;
-    const uint16_t *b = c.bins + (size_t)sl.f * c.Npad;
-    constexpr int PER = kPartTile / kThreads;
-    int ks[PER]; unsigned short bv[PER];
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-        const int pos = base + i * kThreads + threadIdx.x;
-        ks[i] = (pos < cnt) ? (root ? pos : src[pos]) : -1;
-    }
-#pragma unroll
-    for (int i = 0; i < PER; i++) bv[i] = b[max(ks[i], 0)];          // unconditional gathers (see k_part_scatter)
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < PER; i++) n += (ks[i] >= 0) && ((int)bv[i] <= t);
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-    __shared__ int part[4];
-    if (lane_id() == 0) part[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) c.tile_cnt[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-}
-
-// Tile descriptors of the single-pass partition (decoupled look-back): (epoch << 34) | (status << 32) | left count.
-// epoch = growth step counter, so descriptors of earlier steps are simply invalid (no clearing pass).
-constexpr unsigned long long kDescAgg = 1ull, kDescPrefix = 2ull;
-__device__ __forceinline__ unsigned long long make_desc(int epoch, unsigned long long status, int v)
-{
-    return ((unsigned long long)(epoch & 0x3fffffff) << 34) | (status << 32) | (unsigned)v;
-}
-
-// exclusive number of left members in the tiles before local tile `ltile` of this slot; publishes this tile's
-// aggregate first and its inclusive prefix afterwards.  Called by wavefront 0 of the block (all 64 lanes).
-// Blocks are dispatched in blockIdx order, so every tile looked at belongs to a block that is running or finished.
-__device__ int lookback_exclusive(unsigned long long *desc, int ltile, int epoch, int tile_left, int *error)
-{
-    const int lane = lane_id();
-    if (ltile == 0) {
-        if (lane == 0) __hip_atomic_store(&desc[0], make_desc(epoch, kDescPrefix, tile_left), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return 0;
-    }
-    if (lane == 0) __hip_atomic_store(&desc[ltile], make_desc(epoch, kDescAgg, tile_left), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long tag = (unsigned long long)(epoch & 0x3fffffff);
-    int excl = 0, look = ltile - 1, spins = 0;
-    // kLookWin windows of 64 predecessors are requested at once: the tiles of a step run concurrently, so their aggregates are all there after one
-    // memory round trip, while a prefix only appears once a tile has finished its own look-back -- walking back 64 tiles per round trip put
-    // (tiles / 64) round trips on the last tile of a large node (8 for a 1 M-document parent).  The windows are consumed nearest first exactly as
-    // before; the first one that is not complete yet ends the batch and is asked for again.
-#ifndef RL_LOOK_WIN
-#define RL_LOOK_WIN 8
-#endif
-    constexpr int kLookWin = RL_LOOK_WIN;
-    bool found = false;
-    while (!found) {
-        unsigned long long dw[kLookWin];
-#pragma unroll
-        for (int u = 0; u < kLookWin; u++) {
-            const int i = look - 64 * u - lane;               // lane 0 = nearest predecessor of the window
-            dw[u] = make_desc(epoch, kDescPrefix, 0);         // before the first tile: prefix 0
-            if (i >= 0) dw[u] = __hip_atomic_load(&desc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // (one reduction per batch, on the DPP path: a __shfl_xor is a ds_bpermute, and six dependent LDS round trips per window -- 48 per batch -- were
-        // most of the 4-5 us a tile waited AFTER its last predecessor had published)
-        bool stale = false;
-        unsigned acc = 0u;
-#pragma unroll
-        for (int u = 0; u < kLookWin; u++) {
-            if (found || stale) continue;
-            const unsigned long long d = dw[u];
-            const bool valid = ((d >> 34) == tag) && (((d >> 32) & 3ull) != 0ull);
-            const bool isp = valid && (((d >> 32) & 3ull) == kDescPrefix);
-            const unsigned long long vmask = __ballot(valid), pmask = __ballot(isp);
-            const int fp = pmask ? __builtin_ctzll(pmask) : 64;                // nearest lane holding an inclusive prefix
-            const unsigned long long need = (fp >= 63) ? ~0ull : ((1ull << (fp + 1)) - 1ull);
-            if ((vmask & need) == need) {
-                acc += (lane <= fp) ? (unsigned)d : 0u;
-                if (pmask) found = true;
-                else look -= 64;
-            } else stale = true;
-        }
-        excl += (int)wave_sum_u32(acc);
-        if (stale && !found) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1 << 22)) { if (lane == 0) atomicExch(error, 3); break; }      // never hang the GPU
-        }
-    }
-    if (lane == 0) __hip_atomic_store(&desc[ltile], make_desc(epoch, kDescPrefix, excl + tile_left), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return excl;
-}
-
-// Two-level form of the same (round 5).  With every tile of a large node resident at once nobody finds a published PREFIX to stop at: tile i walked
-// back over all i aggregates -- n^2 / 128 uncached wave loads on 15 KB of descriptors (13.6 MB at 1 841 tiles, a handful of memory channels) -- and
-// the look-back ended 9-17 us after the last count had been published (profiles/r05c_step_trace_*).  Here a tile reads ONE window: the aggregates
-// of its own group of 64 tiles; the last tile of a group publishes the group's total, and a tile adds the totals of the groups before its own
-// (one more window per 4 096 tiles): 1 KB per tile, two dependent round trips behind the slowest publication.
-__device__ __forceinline__ unsigned long long ld_desc(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ int lookback2_exclusive(unsigned long long *desc, unsigned long long *gdesc, int ltile, int epoch, int tile_left, int *error)
-{
-    const int lane = lane_id();
-    const int g = ltile >> 6, r = ltile & 63;
-    if (lane == 0) __hip_atomic_store(&desc[ltile], make_desc(epoch, kDescAgg, tile_left), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long tag = (unsigned long long)(epoch & 0x3fffffff);
-    const int ngw = (g + 63) >> 6;                       // windows of group totals before this tile's group
-    constexpr int kGW = 8;                               // in flight together (32 768 tiles); more are walked in further trips
-    int excl = 0, spins = 0;
-    // own group: aggregates of the tiles before this one
-    bool have_in = (r == 0);
-    unsigned gdone = 0u;                                 // bit u: window u of the group totals has been summed
-    int gw0 = 0;
-    while (true) {
-        unsigned long long din = make_desc(epoch, kDescAgg, 0);
-        if (!have_in && lane < r) din = ld_desc(&desc[(g << 6) + lane]);
-        unsigned long long dg[kGW];
-#pragma unroll
-        for (int u = 0; u < kGW; u++) {
-            dg[u] = make_desc(epoch, kDescPrefix, 0);
-            const int gi = ((gw0 + u) << 6) + lane;
-            if (gw0 + u < ngw && !((gdone >> u) & 1u) && gi < g) dg[u] = ld_desc(&gdesc[gi]);
-        }
-        unsigned acc = 0u;
-        if (!have_in) {
-            const bool ok = ((din >> 34) == tag) && (((din >> 32) & 3ull) != 0ull);
-            if (__ballot(!ok) == 0ull) {
-                const unsigned mine = (lane < r) ? (unsigned)din : 0u;
-                const unsigned in_sum = wave_sum_u32(mine);
-                excl += (int)in_sum;
-                have_in = true;
-                // the last tile of a full group publishes the group's total (nobody needs the total of the node's last, partial group)
-                if (r == 63 && lane == 0)
-                    __hip_atomic_store(&gdesc[g], make_desc(epoch, kDescPrefix, (int)in_sum + tile_left), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        bool all_g = true;
-#pragma unroll
-        for (int u = 0; u < kGW; u++) {
-            if (gw0 + u >= ngw || ((gdone >> u) & 1u)) continue;
-            const bool ok = ((dg[u] >> 34) == tag) && (((dg[u] >> 32) & 3ull) == kDescPrefix);
-            if (__ballot(!ok) == 0ull) { acc += (unsigned)dg[u]; gdone |= 1u << u; }
-            else all_g = false;
-        }
-        excl += (int)wave_sum_u32(acc);
-        if (all_g && gw0 + kGW < ngw) { gw0 += kGW; gdone = 0u; all_g = false; if (have_in) continue; }
-        if (have_in && all_g) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > (1 << 22)) { if (lane == 0) atomicExch(error, 3); break; }      // never hang the GPU
-    }
-    return excl;
-}
-
-// (Measured and dropped, round 5: group totals ACCUMULATED by the tiles -- one agent-scope atomic add of (1 << 32 | count) per tile on its group's word,
-// valid at 64 arrivals -- so that the two windows no longer depend on each other: 64 same-address atomics per word serialise at the memory side,
-// c2 414 -> 364 rounds/s.)
-// LOOKBACK (one GPU: the size of the left child is known from the count histogram): single pass.
-// !LOOKBACK (sharded: local sizes unknown): second pass after k_part_count.
-// Samples are read and written row-wise (thread t takes samples t, t+256, ..): every load is coalesced and each
-// wavefront writes one contiguous run to the left list and one to the right list per row.  The fixed-point lambda of the
-// built child's members is written in list order next to their ids (ql): its histogram pass reads it contiguously.
-#ifndef RL_PART_WAVES
-#define RL_PART_WAVES 0
-#endif
-template <bool LOOKBACK>
-__global__ __launch_bounds__(kThreads)
-#if RL_PART_WAVES
-__attribute__((amdgpu_waves_per_eu(RL_PART_WAVES)))
-#endif
-void k_part_scatter(const Ctx c)
-{
-    TreeState *st = c.st;
-    RL_TR_BEGIN();
-    const int j = slot_of_tile(st, blockIdx.x);
-    if (j < 0) return;
-    const SlotRec sl = st->slot[j];                                 // (copied whole: one batch of loads)
-    const int epoch = st->epoch;
-    const int cnt = sl.pcount, t = sl.t, pstart = sl.pstart, pbuf = sl.pbuf;
-    const bool root = (sl.node == 0);
-    const bool bl = sl.build_left != 0;         // the child whose histogram is accumulated from its documents (the smaller one)
-    RL_TR_MARK(1);
-    const int *src = root ? nullptr : c.idx[pbuf] + pstart;
-    const int ltile = blockIdx.x - sl.tile0;
-    const int base = ltile * kPartTile;
-    constexpr int PER = kPartTile / kThreads, NW = kThreads / 64;
-    const uint16_t *b = c.bins + (size_t)sl.f * c.Npad;
-    __shared__ int wl[PER * NW + 1];
-    __shared__ int sh_tileoff, sh_total;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    int ks[PER]; unsigned long long bal[PER];
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-        const int pos = base + i * kThreads + threadIdx.x;
-        ks[i] = (pos < cnt) ? (root ? pos : src[pos]) : -1;
-    }
-    // (every gather below is UNCONDITIONAL, from a clamped index: a load inside `if (member)` sits in its own exec region and the compiler completes it
-    // -- s_waitcnt vmcnt(0) -- before it issues the next one: the eight bin gathers and the eight lambda gathers of a thread were sixteen serial memory
-    // round trips.  Lanes that do not need a value read element 0: one broadcast line)
-    bool isl[PER];
-    {
-        unsigned short bv[PER];
-#pragma unroll
-        for (int i = 0; i < PER; i++) bv[i] = b[max(ks[i], 0)];
-#pragma unroll
-        for (int i = 0; i < PER; i++) isl[i] = (ks[i] >= 0) && ((int)bv[i] <= t);
-    }
-    RL_TR_MARK(2);
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-        bal[i] = __ballot(isl[i]);
-        if (lane == 0) wl[i * NW + wave] = __builtin_popcountll(bal[i]);
-    }
-    __syncthreads();
-    RL_TR_MARK(3);
-    if (wave == 0) {       // exclusive prefix over the (row, wave) runs of the tile
-        static_assert(PER * NW <= 64, "one wave scan over the tile's (row, wave) runs");
-        const int v = (lane < PER * NW) ? wl[lane] : 0;
-        const int inc = (int)wave_scan_u32((unsigned)v);
-        const int tile_left = (int)readlane_u32((unsigned)inc, PER * NW - 1);
-        if (lane < PER * NW) wl[lane] = inc - v;
-        int tileoff, nleft;
-        if (LOOKBACK) {
-#if RL_LOOKBACK2
-            tileoff = lookback2_exclusive(c.tile_desc + sl.tile0, c.tile_gdesc + (sl.tile0 >> 6) + j, ltile, epoch, tile_left, &st->error);
-#else
-            tileoff = lookback_exclusive(c.tile_desc + sl.tile0, ltile, epoch, tile_left, &st->error);
-#endif
-            nleft = sl.nleft;
-        } else {           // left members in earlier tiles, and in all tiles (= local size of the left child)
-            const int *tc = c.tile_cnt + sl.tile0;
-            int pre = 0, tot = 0;
-            for (int i = lane; i < sl.ntiles; i += 64) { const int x = tc[i]; tot += x; if (i < ltile) pre += x; }
-            for (int o = 32; o > 0; o >>= 1) { pre += __shfl_xor(pre, o); tot += __shfl_xor(tot, o); }
-            tileoff = pre; nleft = tot;
-        }
-        if (lane == 0) { sh_tileoff = tileoff; sh_total = nleft; }
-    }
-    // Only the BUILT child's histogram pass reads lambda in list order, and lambda^2 is needed as one sum per child: both are fetched by document id
-    // for the members of the built child alone.  The lists themselves carry document ids only: a partition moves 8 bytes per document of the parent
-    // instead of 40.  The gathers are requested HERE -- after the tile's count has been published, by wavefronts 1.. while wavefront 0 waits in the
-    // look-back (and by wavefront 0 after it): requested before the barrier above (round 4) they sat between a tile and the publication of its
-    // count, and every later tile's look-back waits for the slowest publication before it.
-    long long qv[PER], rv[PER];
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-        const bool mine = (ks[i] >= 0) && (isl[i] == bl);
-        const int ka = mine ? ks[i] : 0;
-        qv[i] = c.q[ka]; rv[i] = c.r[ka];
-    }
-#pragma unroll
-    for (int i = 0; i < PER; i++) if (!((ks[i] >= 0) && (isl[i] == bl))) { qv[i] = 0ll; rv[i] = 0ll; }
-    __syncthreads();
-    const int tileoff = sh_tileoff, nleft = sh_total;
-    RL_TR_MARK(4);
-    int *dstL = c.idx[1 - pbuf] + pstart;
-    long long *qL = c.ql[1 - pbuf] + pstart;
-    if (ltile == 0 && threadIdx.x == 0) {       // local list ranges of the two children
-        NodeRec &Lw = c.nodes[sl.left]; NodeRec &Rw = c.nodes[sl.right];
-        Lw.start = pstart; Lw.count = nleft;
-        Rw.start = pstart + nleft; Rw.count = cnt - nleft;
-    }
-    long long sq = 0;
-    const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-#pragma unroll
-    for (int i = 0; i < PER; i++) {
-        if (ks[i] < 0) continue;
-        const int pos = base + i * kThreads + threadIdx.x;
-        const int lbefore = tileoff + wl[i * NW + wave] + __builtin_popcountll(bal[i] & below);   // left members before pos
-        const int d = isl[i] ? lbefore : nleft + (pos - lbefore);       // stable: left run, then right run
-        dstL[d] = ks[i];
-        if (isl[i] == bl) { qL[d] = qv[i]; sq += rv[i]; }
-    }
-    // fixed-point sum of lambda^2 over the tile's members of the BUILT child: one partial per tile (summed by slot_sq_left / k_hist_finish block
-    // (0, slot)); thousands of atomics on one address would serialise in L2.  The sibling's sum is parent - built, exactly (integers).
-    RL_TR_MARK(5);
-    sq = (long long)wave_sum_u64((unsigned long long)sq);
-    __shared__ long long sh_sq[NW];
-    if (lane == 0) sh_sq[wave] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) { long long v = 0; for (int w = 0; w < NW; w++) v += sh_sq[w]; c.tile_sq[blockIdx.x] = v; }
-    RL_TR_END(0, blockIdx.x);
-}
+namespace rl {
 
 // ------------------------------------------------------------------------------------------------
 // K7: leaves.  k_leaf_table lists the leaves in ascending `start` == left-first DFS order

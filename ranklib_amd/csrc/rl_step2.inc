@@ -398,7 +398,7 @@ __device__ __forceinline__ void half_best_small(const Ctx &c, bool valid, const 
 // The same for data with hundreds of histogram features (up to 32 x kWideS = 768: the Yahoo-set1 shape): the lane's share is up to kWideS records, so only
 // their GAINS are requested up front (wS: feature hl + 32 u, -1.0 beyond F); every lane then fetches the rest of its own best record (one more round
 // trip, all lanes at once), and the tie pass reads the records of the near-equal gains -- rare -- from memory.  half_wave_best_feature<WIDE>'s logic
-// (rl_kernels_round.inc) with the reductions on the DPP path.
+// (rl_k_best.inc) with the reductions on the DPP path.
 __device__ __forceinline__ void half_best_wide(const Ctx &c, bool valid, const FeatBest *o, const unsigned long long (&wS)[kWideS],
                                                long long nthi, unsigned long long ntlo, int nctot,
                                                double &S, int &f, int &t, int &cl, long long &hi, unsigned long long &lo, int &tie)

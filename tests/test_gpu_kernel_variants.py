@@ -190,7 +190,7 @@ def node_chunks(cnt, node_div, node_min, node_chunk):
 
 
 def balance_slots(cnts, node_div, node_min, node_chunk, target, bmin, cap, max_chunks):
-    """balance_slots (rl_kernels_round.inc): None when the step keeps chunk_docs' rule, else (k, chunk size, chunks of the step)"""
+    """balance_slots (rl_k_select.inc): None when the step keeps chunk_docs' rule, else (k, chunk size, chunks of the step)"""
     legacy = sum(node_chunks(c, node_div, node_min, node_chunk) for c in cnts)
     D = sum(cnts)
     if legacy <= bmin:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Where the time of k_hist_finish / select_step goes: device wall-clock stamps of one tree's growth steps.
-Needs a library built with -DRL_PHASE_CLOCKS (make -C ranklib_amd/csrc EXTRA=-DRL_PHASE_CLOCKS LIB=...), selected with RLHIP_LIB.
+Needs a library built with -DRL_PHASE_CLOCKS (the line ranklib_amd/csrc/Makefile runs, plus that define, into a file of its own), selected with RLHIP_LIB.
 usage (GPU box): RLHIP_LIB=... python tools/phase_clocks.py [shape] [rounds]
-build: cd ranklib_amd/csrc && hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -DRL_PHASE_CLOCKS -shared -o ../lib/variants/clk.so -x hip rl_trainer.hip -x hip rl_model.cpp"""
+build: cd ranklib_amd/csrc && hipcc -O3 -std=c++17 -fPIC -ffp-contract=off --offload-arch=gfx950 -Wall -Wno-unused-function -DRL_PHASE_CLOCKS -shared -o ../lib/variants/clk.so -x hip rl_trainer.hip -x hip rl_model.cpp -x hip rl_letor.cpp -x hip rl_ca.hip"""
 import os
 import sys
 
