@@ -348,7 +348,7 @@ enum {
                                    since rl_create), and the layout settings in force.  Indexed by the RL_ARM_* values below */
 };
 /* RL_ARR_LAUNCH_ARMS.  The histogram kernel's arms are counted apart for the root pass (RL_ARM_HIST_ROOT + arm) and the child passes (RL_ARM_HIST_CHILD + arm):
- * an arm names the k_hist instantiation launch_hist chose (rl_trainer.hip), in the order it looks for one. */
+ * an arm names the k_hist instantiation launch_hist chose (rl_launch.inc), in the order it looks for one. */
 enum {
     RL_HARM_COMPACT = 0,        /* child passes from compact rows (sparse data, RLHIP_CROWS) */
     RL_HARM_SUB8 = 1,           /* child passes, 8 features and 256 threads a block (RLHIP_SUB_CHILD=8) */

@@ -1,6 +1,6 @@
 // rl_k_best.inc -- K4/K5, second part: how a feature's best split reaches the block that runs select_step.  RL_CLK, FeatBest, the agent-scope
 // stores and loads, publish_best, PartKey and half_wave_best_feature (the best feature of a new node, with the tie flags).
-// Included by rl_kernels_round.inc; needs the part of that file ahead of the include (the i128 helpers; strict_clock under RL_PHASE_CLOCKS).
+// Included by rl_kernels_round.inc; needs that file's i128 helpers and, under RL_PHASE_CLOCKS, the strict_clock of its trace block.
 
 namespace rl {
 

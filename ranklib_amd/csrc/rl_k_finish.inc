@@ -1,6 +1,6 @@
 // rl_k_finish.inc -- K4/K5, the kernels: hist_finish_body (chunk reduction, prefix over thresholds, sibling = parent - built child, gain scan) and
-// its three entry points k_hist_finish, k_hist_finish_wide and k_select.  Included by rl_kernels_round.inc; needs the part of that file ahead
-// of the include (the i128 helpers, chunk_docs, RL_TR_*), rl_k_reduce.inc, rl_k_best.inc and rl_k_select.inc.
+// its three entry points k_hist_finish, k_hist_finish_wide and k_select.  Included by rl_kernels_round.inc; needs that file's i128 helpers and
+// trace block (RL_TR_*), rl_k_hist.inc (chunk_docs), rl_k_reduce.inc, rl_k_best.inc and rl_k_select.inc.
 
 namespace rl {
 

@@ -1,5 +1,5 @@
 // rl_k_partition.inc -- K6: the stable partition of the sample lists.  k_part_count (sharded runs), the tile descriptors, both decoupled look-backs and
-// k_part_scatter.  Included by rl_kernels_round.inc; needs the part of that file ahead of the include (slot_of_tile, RL_TR_*) and none of
+// k_part_scatter.  Included by rl_kernels_round.inc; needs that file's trace block (RL_TR_*), rl_k_hist.inc (slot_of_tile) and none of
 // the other pieces.
 
 namespace rl {

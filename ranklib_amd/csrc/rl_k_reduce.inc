@@ -1,6 +1,6 @@
 // rl_k_reduce.inc -- K4/K5, first part: what the finish shares with the sharded reduction.  Best and block_best2, gain_S, rebuild_mode_bin,
-// and k_hist_reduce (a rank's bin totals as limbs for the all-reduce).  Included by rl_kernels_round.inc; needs the part of that file ahead
-// of the include (the i128 helpers, chunk_docs, slot_sq_left).
+// and k_hist_reduce (a rank's bin totals as limbs for the all-reduce).  Included by rl_kernels_round.inc; needs that file's i128 helpers
+// and rl_k_hist.inc (chunk_docs, slot_sq_left).
 
 namespace rl {
 

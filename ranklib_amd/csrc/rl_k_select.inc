@@ -1,6 +1,6 @@
 // rl_k_select.inc -- select_step: the best-first growth bookkeeping of RegressionTree.fit with speculative slots, run by the last block of the finish
 // (or by k_select).  queue_insert_lds, node_chunks, prepare_children, balance_slots, can_split, stalled_nodes, select_step_t, select_step.
-// Included by rl_kernels_round.inc; needs the part of that file ahead of the include (the i128 helpers, chunk_docs, strict_clock) and
+// Included by rl_kernels_round.inc; needs that file's i128 helpers and trace block (strict_clock), rl_k_hist.inc (chunk_docs) and
 // rl_k_best.inc (half_wave_best_feature, FeatBest, RL_CLK).
 
 namespace rl {

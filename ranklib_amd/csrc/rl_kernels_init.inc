@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void k_docmajor(const uint16_t *gbins, ui
     }
 }
 
-// compact rows (rl_kernels_round.inc, hist_chunk<.., CR>): per (document, group) the entries outside the columns' mode bins as 16-bit words
+// compact rows (rl_k_hist.inc, hist_chunk<.., CR>): per (document, group) the entries outside the columns' mode bins as 16-bit words
 // (column-in-group << 12 | bin), ascending, padded with 0xffff; more than eight entries: first word 0xfffe (the dense row is read instead).
 // crows [Npad][cr_stride] uint4, document-major.  stats[2 g] += entries of group g, stats[2 g + 1] += its rows with more than eight
 // (a thread walks consecutive (document, group) pairs of ONE group stripe: i = g * Npad + k, so a wavefront's counts belong to one group
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void k_compact_rows(const uint16_t *gbins
     }
 }
 
-// packed rows from the (pre-scaled) 16-bit rows: pbins / phib group-major, pdbins document-major (rl_kernels_round.inc pbin8_of)
+// packed rows from the (pre-scaled) 16-bit rows: pbins / phib group-major, pdbins document-major (rl_k_hist.inc pbin8_of)
 __global__ __launch_bounds__(kThreads) void k_pack_rows(const uint16_t *gbins, unsigned char *pbins, uint16_t *phib, unsigned char *pdbins, int Npad, int numFG, int pd_stride)
 {
     const size_t total = (size_t)Npad * numFG;

@@ -1,4 +1,7 @@
-// rl_trainer.hip -- host orchestration + C ABI of librlhip.so (see include/rlhip.h).
+// rl_trainer.hip -- host orchestration + C ABI of librlhip.so (see include/rlhip.h): the translation unit's includes, `struct rl_trainer`, the
+// timing helpers, the small helpers between the stages, and the extern "C" entries.  Every multi-stage host sequence has a file of its own,
+// included where it is needed: rl_chain_host.inc (float chains), rl_launch.inc (the k_rank_* / k_hist launchers), rl_tie_host.inc
+// (resolve_ties), rl_round.inc (enqueue_round), rl_init.inc (rl_init).
 //
 // One handle = one GPU = one HIP stream.  After rl_init everything a boosting round needs is resident in
 // HBM; a round is a fixed sequence of kernel launches with NO host synchronisation inside it: the tree is
@@ -256,420 +259,12 @@ static void collect_timing(rl_trainer *t)
     }
 }
 
+}  // namespace rl
 
-// ---- exact parallel float chains (rl_chain.inc) ------------------------------------------------------
-static size_t chain_stitch_lds(const ChainBufs &b)
-{
-    const size_t ng1 = (size_t)(b.cap_chunks / b.group + 2), ng2 = ng1 / kChainSuper + 2;
-    return (ng1 * (kChainW + 1) + ng2 * kChainW) * sizeof(uint32_t);
-}
+#include "rl_chain_host.inc"   // the host side of the exact float chains: enqueue_chain, the two sharded leaf-sum exchanges, enqueue_metric_mean
+#include "rl_launch.inc"       // launch_rank and launch_hist<ROOT>: which k_rank_* / k_hist instantiation a data set and a Ctx get
 
-static int alloc_chain(rl_trainer *t, ChainBufs &b, int maxseg, int A, int64_t n, bool hint = false)
-{
-    memset(&b, 0, sizeof(b));
-    b.maxseg = maxseg; b.A = A;
-    b.cap_tiles = n / kChainTile + maxseg + 2;
-    b.cap_chunks = b.cap_tiles + maxseg + 2;
-    b.cap_n = std::max<int64_t>(n, b.cap_chunks);
-    // stitch tables in LDS: first-level groups of `group` chunks (the smaller the group, the shorter the chain of dependent loads)
-    b.group = kChainBlock;
-    while (chain_stitch_lds(b) > 152 * 1024) {
-        b.group *= 2;
-        if (b.group > 65536) return fail(RL_ERR_UNSUPPORTED, "data set too large for the float-chain stitch kernel");
-    }
-    RL_HIP(t->pool.alloc(&b.plan, (size_t)1));
-    RL_HIP(t->pool.alloc(&b.seg_start, (size_t)maxseg + 2)); RL_HIP(t->pool.alloc(&b.seg_tile0, (size_t)maxseg + 2));
-    RL_HIP(t->pool.alloc(&b.xs, (size_t)A * b.cap_n)); RL_HIP(t->pool.alloc(&b.pre, (size_t)A * b.cap_n));
-    RL_HIP(t->pool.alloc(&b.tile_tot, (size_t)A * b.cap_tiles)); RL_HIP(t->pool.alloc(&b.tile_base, (size_t)A * b.cap_tiles));
-    RL_HIP(t->pool.alloc(&b.bnd, (size_t)A * b.cap_tiles));
-    RL_HIP(t->pool.alloc(&b.cbase, (size_t)A * b.cap_chunks)); RL_HIP(t->pool.alloc(&b.drift, (size_t)A * b.cap_chunks));
-    RL_HIP(t->pool.alloc(&b.drift2, (size_t)A * b.cap_chunks));
-    RL_HIP(t->pool.alloc(&b.gkey, (size_t)A * b.cap_chunks)); RL_HIP(t->pool.alloc(&b.gkey2, (size_t)A * b.cap_chunks));
-    RL_HIP(t->pool.alloc(&b.R, (size_t)A * b.cap_chunks * kChainW));
-    RL_HIP(t->pool.alloc(&b.comp0, (size_t)A * (b.cap_chunks / kChainBlock + 1) * kChainW));
-    RL_HIP(t->pool.alloc(&b.result, (size_t)A * maxseg)); RL_HIP(t->pool.alloc(&b.miss, (size_t)A * maxseg));
-    RL_HIP(t->pool.alloc(&b.st_status, (size_t)A * maxseg)); RL_HIP(t->pool.alloc(&b.st_chunk, (size_t)A * maxseg));
-    RL_HIP(t->pool.alloc(&b.st_key, (size_t)A * maxseg)); RL_HIP(t->pool.alloc(&b.st_delta, (size_t)A * maxseg));
-    RL_HIP(t->pool.alloc(&b.st_win, (size_t)A * maxseg));
-    b.lds_words = (int32_t)(chain_stitch_lds(b) / 4);
-    RL_HIP(hipMemset(b.st_status, 0, (size_t)A * maxseg * sizeof(int32_t)));
-    RL_HIP(hipMemset(b.miss, 0, (size_t)A * maxseg * sizeof(int32_t)));
-    RL_HIP(t->pool.alloc(&b.arrive, (size_t)1)); RL_HIP(hipMemset(b.arrive, 0, sizeof(unsigned long long)));
-    if (hint) {      // optional, like the trainer's progress word
-        if (hipHostMalloc((void **)&b.h_progress, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-            *b.h_progress = 0;
-            t->pinned.push_back(b.h_progress);
-            if (hipHostGetDevicePointer((void **)&b.progress, b.h_progress, 0) != hipSuccess) { b.progress = nullptr; b.h_progress = nullptr; (void)hipGetLastError(); }
-        } else { b.h_progress = nullptr; (void)hipGetLastError(); }
-    }
-    RL_HIP(t->pool.alloc(&b.stats, (size_t)4));
-    RL_HIP(hipMemset(b.stats, 0, 4 * sizeof(int32_t)));
-    RL_HIP(hipMemset(b.plan, 0, sizeof(ChainPlan)));
-    return RL_OK;
-}
-
-// the plan must already be on the device (k_leaf_table / k_plan_single); grids are sized by capacity
-// bounded wait on a pinned progress word written by the device (a scheduling hint, never a correctness dependency)
-template <class Pred>
-static bool spin_until(const unsigned long long *word, Pred ok, unsigned long long &w)
-{
-    w = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-    if (ok(w)) return true;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 1;; spins++) {
-        w = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-        if (ok(w)) return true;
-        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return false;
-    }
-}
-
-static void enqueue_chain(rl_trainer *t, const ChainBufs &b_in, const ChainSource &src, hipStream_t s = nullptr)
-{
-    if (!s) s = t->stream;
-    // The device cuts its repair passes into windows (kChainWinMax chunks) only when the host watches them and keeps repairing (the progress word);
-    // a host that enqueues its passes blindly (no pinned word, RLHIP_STEP_AHEAD=0) gets passes that rebuild everything that remains -- otherwise a
-    // chain longer than kChainRepairs windows ended in the serial fallback (exact, but ~100 ms for a 40 M-document leaf).
-    ChainBufs b = b_in;
-    if (!(b.h_progress != nullptr && t->knobs.step_ahead > 0)) { b.progress = nullptr; b.h_progress = nullptr; }
-    const unsigned tb = (unsigned)((b.cap_tiles + 3) / 4);
-    hipLaunchKernelGGL(k_chain_prefix, dim3(tb), dim3(kThreads), 0, s, b, src);
-    hipLaunchKernelGGL(k_chain_scan_tiles, dim3(b.A), dim3(kScanThreads), 0, s, b);
-    hipLaunchKernelGGL(k_chain_bounds, dim3(tb, b.A), dim3(kThreads), 0, s, b);
-    const dim3 p1grid((unsigned)((b.cap_chunks * 16 + kThreads - 1) / kThreads), b.A);
-    hipLaunchKernelGGL(k_chain_pass1<false>, p1grid, dim3(kThreads), 0, s, b);
-    hipLaunchKernelGGL(k_chain_guess, dim3(b.A), dim3(kScanThreads), 0, s, b);
-    const dim3 tgrid((unsigned)((b.cap_chunks + kThreads / 64 - 1) / (kThreads / 64)), b.A);       // one wavefront per chunk
-    const size_t lds = chain_stitch_lds(b);
-    // every stitch pass carries a tag; with a progress word (ChainBufs::h_progress) the host looks at the result of the pass
-    // before the last one it enqueued and leaves the remaining repair passes (near-empty launches) away once nothing is open
-    const unsigned long long seq = ++t->chain_seq;
-    t->chain_calls[b.h_progress ? 0 : 1]++;
-    bool hint = b.h_progress != nullptr && t->knobs.step_ahead > 0, clean = false;
-    const dim3 cgrid((unsigned)((b.cap_chunks / kChainBlock + kThreads / 64) / (kThreads / 64)), b.A);       // one wavefront per block of kChainBlock chunks
-    hipLaunchKernelGGL(k_chain_tables<false>, tgrid, dim3(kThreads), 0, s, b, 0);
-    hipLaunchKernelGGL(k_chain_compose, cgrid, dim3(kThreads), 0, s, b, 0);
-    hipLaunchKernelGGL(k_chain_stitch, dim3(b.maxseg, b.A), dim3(kScanThreads), lds, s, b, 0, seq << 16);
-    // With the hint the host sees every stitch's outcome before it enqueues the next repair pass, so it repairs for as long as a segment is open
-    // (a chain of tens of millions of elements needs a pass per window of 8192 chunks and one per window miss; the serial finish of a chain
-    // that long costs 100 ms) and enqueues nothing on a clean round; without it exactly kChainRepairs passes are enqueued blindly.
-    for (int rep = 0; rep < (hint ? kChainRepairsMax : kChainRepairs); rep++) {
-        if (hint) {      // (a repair pass is four launches: none is enqueued before the stitch it would repair has reported)
-            const unsigned long long want = (seq << 16) | (unsigned)rep;            // the stitch before repair pass rep (0 = the first stitch)
-            unsigned long long w;
-            const auto tw0 = std::chrono::steady_clock::now();
-            const bool seen = spin_until(b.h_progress, [&](unsigned long long v) { return (v >> 1) >= want; }, w);
-            t->chain_wait_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - tw0).count();
-            if (!seen) { hint = false; t->chain_timeouts++; }
-            else if ((w >> 17) == seq && !(w & 1)) { clean = true; break; }
-        }
-        t->chain_repairs[b.h_progress ? 0 : 1]++;
-        hipLaunchKernelGGL(k_chain_pass1<true>, p1grid, dim3(kThreads), 0, s, b);
-        hipLaunchKernelGGL(k_chain_recentre, dim3(b.maxseg, b.A), dim3(kScanThreads), 0, s, b);
-        hipLaunchKernelGGL(k_chain_tables<true>, tgrid, dim3(kThreads), 0, s, b, 1);
-        hipLaunchKernelGGL(k_chain_compose, cgrid, dim3(kThreads), 0, s, b, 1);
-        hipLaunchKernelGGL(k_chain_stitch, dim3(b.maxseg, b.A), dim3(kScanThreads), lds, s, b, 1, (seq << 16) | (unsigned)(rep + 1));
-    }
-    if (!clean) hipLaunchKernelGGL(k_chain_fallback, dim3(b.maxseg, b.A), dim3(64), 0, s, b);
-}
-
-// float s = 0; for (q) s += ndcg_q; s / Q   -- serial for short lists, exact parallel chain otherwise
-// the ordinary repair passes on the segments k_chain_arm has opened (exact start states known), until the host has seen them closed
-static void chain_repair_rounds(rl_trainer *t, const ChainBufs &b, hipStream_t s)
-{
-    const dim3 p1grid((unsigned)((b.cap_chunks * 16 + kThreads - 1) / kThreads), b.A);
-    const dim3 tgrid((unsigned)((b.cap_chunks + kThreads / 64 - 1) / (kThreads / 64)), b.A);
-    const dim3 cgrid((unsigned)((b.cap_chunks / kChainBlock + kThreads / 64) / (kThreads / 64)), b.A);
-    const size_t lds = chain_stitch_lds(b);
-    const unsigned long long seq = ++t->chain_seq;
-    bool hint = b.h_progress != nullptr && t->knobs.step_ahead > 0, clean = false;
-    for (int rep = 0; rep < (hint ? kChainRepairsMax : kChainRepairs); rep++) {
-        t->chain_repairs[b.h_progress ? 0 : 1]++;
-        hipLaunchKernelGGL(k_chain_pass1<true>, p1grid, dim3(kThreads), 0, s, b);
-        hipLaunchKernelGGL(k_chain_recentre, dim3(b.maxseg, b.A), dim3(kScanThreads), 0, s, b);
-        hipLaunchKernelGGL(k_chain_tables<true>, tgrid, dim3(kThreads), 0, s, b, 1);
-        hipLaunchKernelGGL(k_chain_compose, cgrid, dim3(kThreads), 0, s, b, 1);
-        hipLaunchKernelGGL(k_chain_stitch, dim3(b.maxseg, b.A), dim3(kScanThreads), lds, s, b, 1, (seq << 16) | (unsigned)(rep + 1));
-        if (hint) {
-            const unsigned long long want = (seq << 16) | (unsigned)(rep + 1);
-            unsigned long long w;
-            const bool seen = spin_until(b.h_progress, [&](unsigned long long v) { return (v >> 1) >= want; }, w);
-            if (!seen) { hint = false; t->chain_timeouts++; }
-            else if ((w >> 17) == seq && !(w & 1)) { clean = true; break; }
-        }
-    }
-    if (!clean) hipLaunchKernelGGL(k_chain_fallback, dim3(b.maxseg, b.A), dim3(64), 0, s, b);
-}
-
-// Sharded runs, round 6: the leaves' float sums from this rank's own pieces (rl_dist.inc, "piece mode"): three small all-gathers, no document leaves its rank.
-static int enqueue_leaf_chains_pieces(rl_trainer *t, const ChainSource &src)
-{
-    Ctx &c = t->ctx;
-    hipStream_t s = t->stream;
-    ChainBufs b = t->leaf_chain;
-    if (!(b.h_progress != nullptr && t->knobs.step_ahead > 0)) { b.progress = nullptr; b.h_progress = nullptr; }
-    const int R = t->n_ranks, me = t->dist->rank, A = b.A, MS = b.maxseg, nseg = std::max(c.L, 2), n = A * MS;
-    int rcd = t->dist->allgather(c.leaf_start, t->d_gls, (size_t)t->lsstride * sizeof(int32_t), s);       // the pieces' lengths on every rank
-    if (rcd) return rcd;
-    const unsigned tb = (unsigned)((b.cap_tiles + 3) / 4), nb = (unsigned)((n + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(k_chain_prefix, dim3(tb), dim3(kThreads), 0, s, b, src);
-    hipLaunchKernelGGL(k_chain_scan_tiles, dim3(b.A), dim3(kScanThreads), 0, s, b);
-    hipLaunchKernelGGL(k_piece_totals, dim3(nb), dim3(kThreads), 0, s, b, t->d_pc_loc);
-    rcd = t->dist->allgather(t->d_pc_loc, t->d_pc_all, (size_t)n * sizeof(double), s);
-    if (rcd) return rcd;
-    hipLaunchKernelGGL(k_piece_base, dim3(nb), dim3(kThreads), 0, s, (const double *)t->d_pc_all, n, me, t->d_pc_base, 0);
-    b.seg_base = t->d_pc_base; b.ptab = t->d_ptab;
-    hipLaunchKernelGGL(k_chain_bounds, dim3(tb, b.A), dim3(kThreads), 0, s, b);
-    const dim3 p1grid((unsigned)((b.cap_chunks * 16 + kThreads - 1) / kThreads), b.A);
-    hipLaunchKernelGGL(k_chain_pass1<false>, p1grid, dim3(kThreads), 0, s, b);
-    hipLaunchKernelGGL(k_piece_drifts, dim3(MS, b.A), dim3(64), 0, s, b, t->d_pc_loc);
-    rcd = t->dist->allgather(t->d_pc_loc, t->d_pc_all, (size_t)n * sizeof(double), s);
-    if (rcd) return rcd;
-    hipLaunchKernelGGL(k_piece_base, dim3(nb), dim3(kThreads), 0, s, (const double *)t->d_pc_all, n, me, t->d_pc_base, 1);
-    hipLaunchKernelGGL(k_chain_guess, dim3(b.A), dim3(kScanThreads), 0, s, b);
-    const dim3 tgrid((unsigned)((b.cap_chunks + kThreads / 64 - 1) / (kThreads / 64)), b.A);
-    const dim3 cgrid((unsigned)((b.cap_chunks / kChainBlock + kThreads / 64) / (kThreads / 64)), b.A);
-    const size_t lds = chain_stitch_lds(b);
-    const unsigned long long seq = ++t->chain_seq;
-    t->chain_calls[b.h_progress ? 0 : 1]++;
-    hipLaunchKernelGGL(k_chain_tables<false>, tgrid, dim3(kThreads), 0, s, b, 0);
-    hipLaunchKernelGGL(k_chain_compose, cgrid, dim3(kThreads), 0, s, b, 0);
-    hipLaunchKernelGGL(k_chain_stitch, dim3(b.maxseg, b.A), dim3(kScanThreads), lds, s, b, 0, seq << 16);
-    rcd = t->dist->allgather(t->d_ptab, t->d_gtab, (size_t)n * (kChainW + 1) * sizeof(uint32_t), s);
-    if (rcd) return rcd;
-    hipLaunchKernelGGL(k_chain_cross, dim3(1), dim3(kThreads), 0, s, (const uint32_t *)t->d_gtab, (const int32_t *)t->d_gls, t->lsstride, R, nseg, A, MS, me, t->xstate,
-                       (const uint32_t *)t->d_res_all, 0, t->knobs.piece_force, b.result, t->d_xmail, ++t->xmail_tag);
-    ChainBufs br = b; br.ptab = nullptr;            // (the repair passes stitch from ONE known state)
-    for (int round = 0;; round++) {
-        // every rank sees the same gathered tables, hence the same pending pieces: the rounds of this loop -- and their collectives -- are the same everywhere
-        const auto t0w = std::chrono::steady_clock::now();
-        unsigned spins = 0;
-        while (__atomic_load_n(&t->h_xmail[2], __ATOMIC_ACQUIRE) != t->xmail_tag) {
-            if ((++spins & 0xffff) == 0) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q != hipSuccess && q != hipErrorNotReady) return fail(RL_ERR_HIP, std::string("device error in the leaves' float chains: ") + hipGetErrorString(q));
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0w).count() > t->knobs.dist_timeout_s)
-                    return fail(RL_ERR_COMM, "timed out waiting for the leaves' float chains (a rank of the job is missing from a collective?)");
-            }
-        }
-        const long long pend = t->h_xmail[0], mine = t->h_xmail[1];
-        if (pend == 0) break;
-        if (round > R * n + 8) return fail(RL_ERR_STATE, "the leaves' float chains did not close (internal error)");
-        t->piece_rounds++; t->piece_misses += pend;
-        hipLaunchKernelGGL(k_chain_arm, dim3(1), dim3(kThreads), 0, s, br, t->xstate, me, br.progress ? 1 : 0);
-        if (mine > 0) chain_repair_rounds(t, br, s);
-        hipLaunchKernelGGL(k_chain_resolved, dim3(1), dim3(kThreads), 0, s, br, t->xstate, me, t->d_res_loc);
-        rcd = t->dist->allgather(t->d_res_loc, t->d_res_all, (size_t)n * sizeof(uint32_t), s);
-        if (rcd) return rcd;
-        hipLaunchKernelGGL(k_chain_cross, dim3(1), dim3(kThreads), 0, s, (const uint32_t *)t->d_gtab, (const int32_t *)t->d_gls, t->lsstride, R, nseg, A, MS, me, t->xstate,
-                           (const uint32_t *)t->d_res_all, 1, t->knobs.piece_force, b.result, t->d_xmail, ++t->xmail_tag);
-    }
-    return RL_OK;
-}
-
-// Sharded runs, the leaf-owner exchange (rl_dist.inc): lambda / weight of a leaf's documents go to the leaf's owner rank only, which evaluates the
-// chains over the whole leaf (t->gchain); the 2 L float sums come back to every rank.
-static int enqueue_leaf_chains_owner(rl_trainer *t, const ChainSource &src)
-{
-    Ctx &c = t->ctx;
-    hipStream_t s = t->stream;
-    const ChainBufs &lb = t->leaf_chain;
-    const int R = t->n_ranks, me = t->dist->rank, nseg = std::max(c.L, 2), MS = t->gchain.maxseg;      // -leaf 1 still has two leaves (the root always splits)
-    hipLaunchKernelGGL(k_chain_prefix, dim3((unsigned)((lb.cap_tiles + 3) / 4)), dim3(kThreads), 0, s, lb, src);      // local values in leaf order -> lb.xs
-    int rcd = t->dist->allgather(c.leaf_start, t->d_gls, (size_t)t->lsstride * sizeof(int32_t), s);
-    if (rcd) return rcd;
-    std::vector<int64_t> scount(R), sdispl(R), rcount(R), rdispl(R);
-    const bool dev_plan = t->d_xmail != nullptr && !t->knobs.dist_host_plan && nseg <= kPlanMaxSeg && R <= 64;       // (knobs.dist_host_plan: the host plan behind a stream synchronisation, as until round 5)
-    t->arms[dev_plan ? RL_ARM_XPLAN_DEVICE : RL_ARM_XPLAN_HOST]++;
-    if (dev_plan) {
-        // the plan on the device; the host only needs the byte counts of the transfers and reads them from a pinned mailbox below, after it has
-        // enqueued the pack kernel (k_plan_exchange)
-        hipLaunchKernelGGL(k_plan_exchange, dim3(1), dim3(64), 0, s, (const int32_t *)t->d_gls, R, t->lsstride, nseg, MS, me, t->d_own, t->d_xtab, t->d_xmail, ++t->xmail_tag);
-    } else {
-        // the send / receive counts of the exchange have to be known to the host: one small copy per round (sharded runs are host-paced anyway)
-        std::vector<int32_t> &gls = t->h_gls;
-        gls.resize((size_t)R * t->lsstride);
-        RL_HIP(hipMemcpyAsync(gls.data(), t->d_gls, gls.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        RL_HIP(hipStreamSynchronize(s));
-        auto len_of = [&](int r, int l) { return (long long)gls[(size_t)r * t->lsstride + l + 1] - gls[(size_t)r * t->lsstride + l]; };
-        std::vector<int32_t> &own = t->h_own; own.assign((size_t)MS, 0);
-        {   // owners: largest leaf first onto the least loaded rank (every rank computes the same map from the same table)
-            std::vector<long long> glen((size_t)nseg, 0), load((size_t)R, 0);
-            std::vector<int32_t> order((size_t)nseg);
-            for (int l = 0; l < nseg; l++) { order[l] = l; for (int r = 0; r < R; r++) glen[l] += len_of(r, l); }
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return glen[a] > glen[b]; });
-            for (int l : order) {
-                if (glen[l] == 0) { own[l] = l % R; continue; }
-                int o = 0;
-                for (int r = 1; r < R; r++) if (load[r] < load[o]) o = r;
-                own[l] = o; load[o] += glen[l];
-            }
-        }
-        std::vector<long long> &tab = t->h_xtab; tab.assign((size_t)MS * (R + 1), 0);       // pack_off [MS] | asm_off [R][MS]
-        long long cur = 0;
-        for (int d = 0; d < R; d++) {
-            sdispl[d] = cur * 8;
-            if (d != me) for (int l = 0; l < nseg; l++) if (own[l] == d) { tab[l] = cur; cur += 2 * len_of(me, l); }       // (own leaves: not packed, k_chain_assemble)
-            scount[d] = cur * 8 - sdispl[d];
-        }
-        cur = 0;
-        for (int r = 0; r < R; r++) {
-            rdispl[r] = cur * 8;
-            if (r != me) for (int l = 0; l < nseg; l++) if (own[l] == me) { tab[(size_t)MS * (1 + r) + l] = cur; cur += 2 * len_of(r, l); }
-            rcount[r] = cur * 8 - rdispl[r];
-        }
-        RL_HIP(hipMemcpyAsync(t->d_own, own.data(), (size_t)MS * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        RL_HIP(hipMemcpyAsync(t->d_xtab, tab.data(), tab.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-    }
-    const LeafExchange lx{t->d_own, t->d_xtab, t->d_xtab + MS};
-    hipLaunchKernelGGL(k_chain_pack, dim3(nseg, 2, kLeafXferZ), dim3(kThreads), 0, s, (const double *)lb.xs, lb.cap_n, (const int32_t *)c.leaf_start, nseg, lx, t->d_send, me);
-    if (dev_plan) {       // the mailbox: the tag is stored last (release); a device error or a dead peer must end the wait
-        const auto t0w = std::chrono::steady_clock::now();
-        unsigned spins = 0;
-        while (__atomic_load_n(&t->h_xmail[4 * R], __ATOMIC_ACQUIRE) != t->xmail_tag) {
-            if ((++spins & 0xffff) == 0) {
-                const hipError_t q = hipStreamQuery(s);
-                if (q != hipSuccess && q != hipErrorNotReady) return fail(RL_ERR_HIP, std::string("device error before the leaf-owner exchange: ") + hipGetErrorString(q));
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0w).count() > t->knobs.dist_timeout_s)
-                    return fail(RL_ERR_COMM, "timed out waiting for the plan of the leaf-owner exchange (a rank of the job is missing from a collective?)");
-            }
-        }
-        for (int r = 0; r < R; r++) { scount[r] = t->h_xmail[r]; sdispl[r] = t->h_xmail[R + r]; rcount[r] = t->h_xmail[2 * R + r]; rdispl[r] = t->h_xmail[3 * R + r]; }
-    }
-    rcd = t->dist->alltoallv(t->d_send, scount.data(), sdispl.data(), t->d_gx, rcount.data(), rdispl.data(), s);
-    if (rcd) return rcd;
-    hipLaunchKernelGGL(k_plan_global, dim3(1), dim3(64), 0, s, (const int32_t *)t->d_gls, R, t->lsstride, nseg, t->gchain, (const int32_t *)t->d_own, me);
-    hipLaunchKernelGGL(k_chain_assemble, dim3(nseg, 2, kLeafXferZ), dim3(kThreads), 0, s, (const double *)t->d_gx, (const int32_t *)t->d_gls, R, t->lsstride, nseg, lx,
-                       t->gchain, me, (const double *)lb.xs, lb.cap_n, (const int32_t *)c.leaf_start);
-    ChainSource gsrc{t->gchain.xs, t->gchain.xs + t->gchain.cap_n, nullptr, nullptr, nullptr, nullptr};
-    enqueue_chain(t, t->gchain, gsrc);
-    if (R > 1) {       // every rank evaluated its own leaves: exchange the 2 L float sums
-        rcd = t->dist->allgather(t->gchain.result, t->d_gres, (size_t)2 * MS * sizeof(float), s);
-        if (rcd) return rcd;
-        hipLaunchKernelGGL(k_chain_pick, dim3((2 * nseg + kThreads - 1) / kThreads), dim3(kThreads), 0, s, (const float *)t->d_gres, R, 2,
-                           MS, nseg, (const int32_t *)t->d_own, t->gchain.result);
-    }
-    return RL_OK;
-}
-
-static void enqueue_metric_mean(rl_trainer *t, const double *ndcg_q, int Q, float *out, hipStream_t s = nullptr)
-{
-    if (!s) s = t->stream;
-    if (Q <= 4096 || (t->p.flags & RL_FLAG_SERIAL_CHAIN)) { hipLaunchKernelGGL(k_float_mean, dim3(1), dim3(64), 0, s, ndcg_q, Q, out); return; }
-    hipLaunchKernelGGL(k_plan_single, dim3(1), dim3(64), 0, s, t->metric_chain, Q);
-    ChainSource src{ndcg_q, nullptr, nullptr, nullptr, nullptr, nullptr};
-    enqueue_chain(t, t->metric_chain, src, s);
-    hipLaunchKernelGGL(k_metric_finish, dim3(1), dim3(64), 0, s, t->metric_chain, Q, out);
-}
-
-// ---- per-query kernels on a data set -------------------------------------------------------------
-// rank every query by `scores` (stable, descending) and leave NDCG@k per query in `out`; with `ranked` the
-// ranked-order arrays of the data set are refreshed too (they feed the next round's lambdas)
-static int launch_rank(rl_trainer *t, DataSet &d, const double *scores, double *out, bool ranked)
-{
-    RankArgs a{scores, d.d_labels, d.d_qoff, d.d_ideal1, t->ctx.disc,
-               ranked ? d.d_ss : nullptr, ranked ? d.d_sl : nullptr, ranked ? d.d_srel : nullptr, ranked ? d.d_sidx : nullptr,
-               out, t->p.metric_k, t->p.metric, ranked ? d.d_aux_i : nullptr, ranked ? d.d_aux_a : nullptr, ranked ? d.d_aux_b : nullptr, t->err_max,
-               d.d_ext_rd};
-    if (d.n_tiny > 0) {
-        t->arms[RL_ARM_RANK_TINY]++;
-        hipLaunchKernelGGL(k_rank_tiny, dim3((d.n_tiny + kRankTinyGroups - 1) / kRankTinyGroups), dim3(kRankTinyDocs * kRankTinyGroups), 0, t->stream, a,
-                           (const int *)d.d_qtiny, d.n_tiny);
-    }
-    if (!t->knobs.rank_split && d.n_big > 0 && d.n_small > 0) {
-        const int wpb = kRankBlockThreads / 64;
-        const size_t lds = std::max((size_t)d.max_big, (size_t)wpb * kLambdaWaveCap) * kRankLdsPerDoc;
-        t->arms[RL_ARM_RANK_MIXED]++; t->arms[RL_ARM_RANK_HUGE] += d.n_huge > 0 ? 1 : 0;
-        hipLaunchKernelGGL(k_rank_mixed, dim3(d.n_big + (d.n_small + wpb - 1) / wpb), dim3(kRankBlockThreads), lds, t->stream, a, (const int *)d.d_qbig, d.n_big, d.max_big,
-                           (const int *)d.d_qsmall, d.n_small, kLambdaWaveCap);
-        if (d.n_huge > 0)
-            hipLaunchKernelGGL(k_rank_huge, dim3(d.n_huge), dim3(kRankBlockThreads), 0, t->stream, a, (const int *)d.d_qhuge, d.n_huge, d.d_relscratch);
-        RL_HIP(hipGetLastError());
-        return RL_OK;
-    }
-    t->arms[RL_ARM_RANK_WAVE_LONG] += d.n_small_long > 0 ? 1 : 0; t->arms[RL_ARM_RANK_WAVE_SHORT] += d.n_small > d.n_small_long ? 1 : 0;
-    t->arms[RL_ARM_RANK_BLOCK] += d.n_big > 0 ? 1 : 0; t->arms[RL_ARM_RANK_HUGE] += d.n_huge > 0 ? 1 : 0;
-    if (d.n_small_long > 0)       // (d_qsmall: longest first)
-        hipLaunchKernelGGL(k_rank_wave, dim3((d.n_small_long + 3) / 4), dim3(kThreads), 4 * kLambdaWaveCap * kRankLdsPerDoc, t->stream, a,
-                           (const int *)d.d_qsmall, d.n_small_long, kLambdaWaveCap);
-    if (d.n_small > d.n_small_long)
-        hipLaunchKernelGGL(k_rank_wave, dim3((d.n_small - d.n_small_long + 3) / 4), dim3(kThreads), 4 * kRankShort * kRankLdsPerDoc, t->stream, a,
-                           (const int *)d.d_qsmall + d.n_small_long, d.n_small - d.n_small_long, kRankShort);
-    if (d.n_big > 0)
-        hipLaunchKernelGGL(k_rank_block, dim3(d.n_big), dim3(kRankBlockThreads), (size_t)d.max_big * kRankLdsPerDoc, t->stream, a, d.d_qbig, d.n_big, d.max_big);
-    if (d.n_huge > 0)
-        hipLaunchKernelGGL(k_rank_huge, dim3(d.n_huge), dim3(kRankBlockThreads), 0, t->stream, a, (const int *)d.d_qhuge, d.n_huge, d.d_relscratch);
-    RL_HIP(hipGetLastError());
-    return RL_OK;
-}
-
-template <bool ROOT>
-static void launch_hist(const Ctx &c, const Knobs &kn, int64_t *arms, int gx, int gy, size_t lds, hipStream_t s, bool fq = false)
-{
-    // RL_ARR_LAUNCH_ARMS: one increment per launch, root and child passes apart; of a child pass also the grid and the LDS it was given
-    const auto took = [&](int arm, const dim3 &grid, size_t lds_bytes) {
-        arms[(ROOT ? RL_ARM_HIST_ROOT : RL_ARM_HIST_CHILD) + arm]++;
-        if (!ROOT) { arms[RL_ARM_CHILD_GRID_X] = grid.x; arms[RL_ARM_CHILD_GRID_Y] = grid.y; arms[RL_ARM_CHILD_LDS] = (int64_t)lds_bytes; }
-    };
-    // the XCD-aware block map of k_hist wants a multiple of 8 chunks (the extra blocks exit); child passes: a bounded grid whose blocks walk the
-    // step's chunks (k_hist), about one resident set of blocks (3 per CU)
-    const int grid_blocks = kn.hist_grid.or_else(1024);
-    // (balanced steps -- balance_slots -- want exactly balance_target rows: block row r then works through the chunks r, r + balance_target, ..)
-    const bool grid_env = kn.hist_grid.set;
-    const auto bounded = [&](int gxx) { return ROOT ? ((gy + 7) & ~7) : (c.balance && (!c.sharded || c.cum_cnt_loc) && !grid_env) ? std::min((gy + 7) & ~7, c.balance_target)
-                                                                      : std::min((gy + 7) & ~7, std::max(8, ((grid_blocks + gxx - 1) / gxx + 7) & ~7)); };
-    if (!ROOT) lds += kn.hist_ldspad;
-    const dim3 g(gx, bounded(gx)), b(kThreads);
-    if (!ROOT && c.crows && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs) {      // sparse data: compact rows (k_compact_rows)
-        took(RL_HARM_COMPACT, g, lds);
-        hipLaunchKernelGGL((k_hist<false, 16, kHistLdsStride, false, false, kThreads, true>), g, b, lds, s, c);
-        return;
-    }
-    if (!ROOT && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs && !(c.p8 > 1) && c.sub_child < 16) {
-        // child passes, features of a group spread over 16 / sub_child blocks: a step of a few chunks leaves most CUs idle while every block is bound by
-        // the LDS atomics of ITS CU -- the same atomics on more CUs (the rows are read once per sub-block, from L2)
-        const dim3 g2(gx * (16 / c.sub_child), bounded(gx * (16 / c.sub_child)));
-        const size_t lds2 = (size_t)c.sub_child * kHistLdsStride * 12;
-        took(c.sub_child == 8 ? RL_HARM_SUB8 : RL_HARM_SUB4, g2, lds2);
-        if (c.sub_child == 8) hipLaunchKernelGGL((k_hist<false, 8, kHistLdsStride, false, false, 256>), g2, dim3(256), lds2, s, c);
-        else hipLaunchKernelGGL((k_hist<false, 4, kHistLdsStride, false, false, 256>), g2, dim3(256), lds2, s, c);
-        return;
-    }
-    if (!ROOT && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs && !(c.p8 > 1) && c.hist_nt > kThreads) {
-        // child passes: a step has few chunks (~12 per node), so the chip is mostly idle and every block is a chain of dependent row gathers --
-        // larger blocks keep more of them in flight per chunk
-        took(c.hist_nt >= 1024 ? RL_HARM_NT1024 : RL_HARM_NT512, g, lds);
-        if (c.hist_nt >= 1024) hipLaunchKernelGGL((k_hist<false, 16, kHistLdsStride, false, false, 1024>), g, dim3(1024), lds, s, c);
-        else hipLaunchKernelGGL((k_hist<false, 16, kHistLdsStride, false, false, 512>), g, dim3(512), lds, s, c);
-        return;
-    }
-    if constexpr (ROOT) {
-        if (fq && c.sub == 16 && c.TS <= kHistLdsStride && !c.any_runs) {      // root pass that quantises the lambdas itself (root_quant_fused)
-            took(c.p8 ? RL_HARM_FQ_PACKED : RL_HARM_FQ_ROWS16, g, lds);
-            if (c.p8) hipLaunchKernelGGL((k_hist<true, 16, kHistLdsStride, false, true, kThreads, false, true>), g, b, lds, s, c);
-            else hipLaunchKernelGGL((k_hist<true, 16, kHistLdsStride, false, false, kThreads, false, true>), g, b, lds, s, c);
-            return;
-        }
-    }
-    if (c.sub == 16 && c.TS <= kHistLdsStride) {
-        // packed rows for the root pass only (measured at c2: 43 % fewer bytes buy the root pass 9 % -- it is bound by LDS atomics, not by HBM --
-        // and the child passes nothing: their extra bit-field work costs what the two 128-byte lines per document instead of three save)
-        took((c.p8 && (ROOT || c.p8 > 1)) ? (c.any_runs ? RL_HARM_PACKED_RUNS : RL_HARM_PACKED) : (c.any_runs ? RL_HARM_ROWS16_RUNS : RL_HARM_ROWS16), g, lds);
-        if (c.p8 && (ROOT || c.p8 > 1)) {
-            if (c.any_runs) hipLaunchKernelGGL((k_hist<ROOT, 16, kHistLdsStride, true, true>), g, b, lds, s, c);
-            else hipLaunchKernelGGL((k_hist<ROOT, 16, kHistLdsStride, false, true>), g, b, lds, s, c);
-        } else if (c.any_runs) hipLaunchKernelGGL((k_hist<ROOT, 16, kHistLdsStride, true>), g, b, lds, s, c);
-        else hipLaunchKernelGGL((k_hist<ROOT, 16, kHistLdsStride>), g, b, lds, s, c);
-        return;
-    }
-    took(RL_HARM_STRIDE, g, lds);
-    switch (c.sub) {
-    case 16: hipLaunchKernelGGL((k_hist<ROOT, 16, 0>), g, b, lds, s, c); break;
-    case 8: hipLaunchKernelGGL((k_hist<ROOT, 8, 0>), g, b, lds, s, c); break;
-    case 4: hipLaunchKernelGGL((k_hist<ROOT, 4, 0>), g, b, lds, s, c); break;
-    case 2: hipLaunchKernelGGL((k_hist<ROOT, 2, 0>), g, b, lds, s, c); break;
-    default: hipLaunchKernelGGL((k_hist<ROOT, 1, 0>), g, b, lds, s, c); break;
-    }
-}
+namespace rl {
 
 // multi-GPU: per-query values of all ranks in global query order (ranks hold ascending contiguous query ranges)
 static int gather_queries(rl_trainer *t, const double *local, const double **out, bool valid = false)

@@ -89,7 +89,7 @@ class TorchHostTransport:
         return out
 
 
-# ---- the leaf-owner exchange, restated on the host (what rl_trainer.hip enqueue_leaf_chains_owner + rl_dist.inc do per round; CPU tests) ----
+# ---- the leaf-owner exchange, restated on the host (what rl_chain_host.inc enqueue_leaf_chains_owner + rl_dist.inc do per round; CPU tests) ----
 def leaf_owners(glen, n_ranks):
     """owner rank of every leaf: largest leaf (documents over all ranks) first onto the least loaded rank, lowest rank on a tie;
     empty leaf slots go to l % n_ranks.  Every rank computes this from the same gathered leaf tables."""

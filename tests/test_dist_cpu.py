@@ -69,7 +69,7 @@ assert m.view(np.float64)[0] == 1.5 + world - 1
 # 3. all-gather keeps rank order
 g = tr.allgather(np.full(5, rank, np.uint8))
 assert list(g) == [r for r in range(world) for _ in range(5)]
-# 4. the leaf-owner exchange (ranklib_amd/dist.py leaf_exchange_plan = what rl_trainer.hip does per round): documents of a global data set
+# 4. the leaf-owner exchange (ranklib_amd/dist.py leaf_exchange_plan = what rl_chain_host.inc enqueue_leaf_chains_owner does per round): documents of a global data set
 #    live on the ranks in contiguous ascending ranges; every leaf's values must reach its owner in global document order
 rg = np.random.RandomState(7)
 Ndoc, L = 5000, 9

@@ -180,7 +180,7 @@ def up256(v):
 
 
 def chunk_docs(cnt, node_div, node_min, node_chunk):
-    """chunk_docs<false> (rl_kernels_round.inc): documents per histogram chunk of a child node of cnt documents"""
+    """chunk_docs<false> (rl_k_hist.inc): documents per histogram chunk of a child node of cnt documents"""
     return min(node_chunk, max(max(node_min, 256), up256((cnt + node_div - 1) // node_div)))
 
 
