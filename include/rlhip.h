@@ -933,6 +933,51 @@ int  rl_model_eval_permuted(rl_model *m, const float *X, int64_t n_docs, int32_t
  * call */
 int  rl_debug_permuted_times(double *walk_ms, double *rank_ms);
 
+/* ---- per-document feature contributions of a tree model, one pass over a file ----------------------------------------
+ * Which features put a document where it is: Saabas path attribution, as XGBoost's pred_contribs with approx_contribs has it.  The
+ * model has trees t = 0 .. T-1 with float weights w_t; the nodes j of a tree are numbered in the pre-order of the model text; a leaf
+ * has feature -1 and a float `out`.
+ * WALK: Split.eval as everywhere.  At a split on feature id f: v = (f < row_stride) ? row[f] : 0, left iff v <= thr (a NaN goes right).
+ * COVER: c[t][j], uint64, counts the background rows whose walk in tree t visits node j; c[t][0] is the number of background rows.
+ * Model text holds no counts, so rl_model_cover counts them on a background file; with accumulate != 0 the call's counts are added to
+ * those the model has.  n_docs == 0 is legal: it leaves all counts zero, or with accumulate as they were.
+ * NODE VALUE: val[t][j], f64, children first.  A leaf's is (double)out.  A split's, with children l, r and a = c[l], b = c[r] (a = b = 1
+ * where a + b == 0: the background never reached the node), is ((double)a * val[l] + (double)b * val[r]) / (double)(a + b), the
+ * operations in that order, each rounded (no FMA).  The values are made again after every rl_model_cover call.
+ * CONTRIBUTIONS of a row, f64: the requested feature ids are columns[0 .. C-1]; there are C + 2 slots, 0 .. C-1, rest = C, bias = C + 1.
+ *     acc[0 .. C+1] = +0.0
+ *     for t = 0 .. T-1:  W = (double)w_t;  acc[bias] = acc[bias] + W * val[t][0];  j = 0
+ *         while j is a split on feature f and the walk goes on to node n:
+ *             d = W * (val[t][n] - val[t][j]);  s = the place of f in columns, or rest;  acc[s] = acc[s] + d;  j = n
+ * so every slot is one serial f64 chain, in tree order, then path order.  out is [n_docs][C + 2], row-major.  columns == NULL (then
+ * n_columns only has to be >= 0): the columns are the model's features in rl_model_features' order, and rest is exactly +0.0.  A requested
+ * id the model never splits on gets +0.0.
+ * The slots of a row sum to the f64 sum over the trees of (double)w_t * (double)out of the leaf reached, up to f64 rounding (a
+ * telescoping sum).  That is NOT rl_model_predict's score, which is Ensemble.eval's float chain: the two differ by float rounding.
+ * X, columns and out are HOST pointers.  The rows are processed in chunks whose device buffers -- the rows and 8 (C + 2) bytes of
+ * output per row -- stay within scratch_bytes (0 = 256 MiB); a chunk holds at least one row.  The result does not depend on the
+ * chunking, nor on the number of column passes the kernel needs when C + 2 slots do not fit its LDS (rl_debug_contrib_passes).
+ * rl_model_get_cover: *n_nodes is the tree's node count; count and value [cap] receive its covers and node values (either may be NULL).
+ * RL_ERR_INVALID, the message naming the argument, before the device is touched: a null model / X / out, n_docs < 0, row_stride < 1,
+ * n_columns < 0, columns given with n_columns < 1, a negative column, a column listed twice, scratch_bytes < 0, a model without trees,
+ * tree out of range, cap below the tree's node count (*n_nodes is still set).  RL_ERR_STATE: rl_model_predict_contribs or
+ * rl_model_get_cover before any rl_model_cover.  RL_ERR_UNSUPPORTED: more than 2^31 rows per call, a tree of more than 5 103 nodes (the LDS).
+ * rl_model_debug_path reports RL_MODEL_PATH_COVER / RL_MODEL_PATH_CONTRIBS after rl_model_cover / rl_model_predict_contribs. */
+int  rl_model_cover(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, int32_t accumulate);
+int  rl_model_cover_rows(const rl_model *m, int64_t *n_rows);
+int  rl_model_get_cover(const rl_model *m, int32_t tree, uint64_t *count, double *value, int32_t cap, int32_t *n_nodes);
+int  rl_model_predict_contribs(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *columns,
+                               int32_t n_columns, int64_t scratch_bytes, double *out);
+enum { RL_MODEL_PATH_COVER = 4, RL_MODEL_PATH_CONTRIBS = 5 };
+/* out [n_docs]: per row the f64 sum over the trees, in tree order, s = s + (double)w_t * (double)out of the leaf the walk reaches -- what
+ * the row's contributions sum to up to f64 rounding (local accuracy), from a walk of its own.  Needs no cover.  The same row checks. */
+int  rl_model_predict_leaf_sums(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, double *out);
+/* debug (tools/contrib_bench.py): ms between device events around the k_model_cover launches of this thread's last rl_model_cover call
+ * and around the k_model_contribs launches of its last rl_model_predict_contribs call, summed over the chunks */
+int  rl_debug_contrib_times(double *cover_ms, double *walk_ms);
+/* debug: the column passes of this thread's last rl_model_predict_contribs call */
+int  rl_debug_contrib_passes(int32_t *passes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,7 @@ ABI_SYMBOLS = [
     "rl_normalize_lists", "rl_debug_normalize_times",
     "rl_model_predict_stages", "rl_model_eval_stages", "rl_debug_stage_times",
     "rl_model_predict_permuted", "rl_model_eval_permuted", "rl_debug_permuted_times",
+    "rl_model_cover", "rl_model_cover_rows", "rl_model_get_cover", "rl_model_predict_contribs", "rl_model_predict_leaf_sums", "rl_debug_contrib_times", "rl_debug_contrib_passes",
     "rl_adopt_model_text",
 ]
 
@@ -300,6 +301,14 @@ def lib():
         L.rl_model_predict_permuted.argtypes = [vp, vp, i64, i32, vp, i32, vp, i32, vp, vp]
         L.rl_model_eval_permuted.argtypes = [vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, vp, i32, vp, i32, i64, vp, vp, vp, vp, vp]
         L.rl_debug_permuted_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_predict_contribs"):  # (A/B builds of older sources have no contributions)
+        L.rl_model_cover.argtypes = [vp, vp, i64, i32, i32]
+        L.rl_model_cover_rows.argtypes = [vp, C.POINTER(i64)]
+        L.rl_model_get_cover.argtypes = [vp, i32, vp, vp, i32, C.POINTER(i32)]
+        L.rl_model_predict_contribs.argtypes = [vp, vp, i64, i32, vp, i32, i64, vp]
+        L.rl_model_predict_leaf_sums.argtypes = [vp, vp, i64, i32, vp]
+        L.rl_debug_contrib_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.rl_debug_contrib_passes.argtypes = [C.POINTER(i32)]
     if hasattr(L, "rl_adopt_model_text"):     # (A/B builds of older sources cannot resume)
         L.rl_adopt_model_text.argtypes = [vp, C.c_char_p, i64, C.POINTER(i32)]
     _lib = L
@@ -698,6 +707,7 @@ class Trainer:
 MODEL_PATH_NONE, MODEL_PATH_TILED, MODEL_PATH_GENERIC = 0, 1, 2
 MODEL_PATH_PERMUTED = 3             # rl_model_predict_permuted / rl_model_eval_permuted: one kernel for every model
 PERMUTED_BATCH = 16                 # RL_PERMUTED_BATCH (rlhip.h): cells k_model_permuted_scores takes per document at a time
+MODEL_PATH_COVER, MODEL_PATH_CONTRIBS = 4, 5      # rl_model_cover (k_model_cover) / rl_model_predict_contribs (k_model_contribs)
 
 
 class Model:
@@ -841,6 +851,65 @@ class Model:
                                        don.ctypes.data, int(don.shape[0]), int(scratch_bytes), base.ctypes.data, bnan.ctypes.data,
                                        out.ctypes.data, nan.ctypes.data, ideal.ctypes.data))
         return base[:nl], bnan[:nl], out[:, :, :nl], nan[:, :, :nl], ideal[:nl]
+
+    @staticmethod
+    def _contrib_rows(rows):
+        L = lib()
+        if not hasattr(L, "rl_model_predict_contribs"):
+            raise RankLibError("rlhip: this librlhip.so has no feature contributions (rl_model_predict_contribs)")
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2:
+            raise RankLibError("rlhip: feature contributions take rows [n_docs][row_stride]")
+        return L, rows, (rows if rows.size else np.zeros(1, np.float32))      # (no rows: still a pointer that is not null)
+
+    def cover(self, rows, accumulate=False):
+        """rl_model_cover: count, per node, the rows of a background file whose walk visits it, and make the node values from the counts
+        (DESIGN.md 26).  accumulate: add to the counts of earlier calls instead of replacing them.  rows as in predict_rows."""
+        L, rows, buf = self._contrib_rows(rows)
+        check(L.rl_model_cover(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], 1 if accumulate else 0))
+
+    def cover_rows(self):
+        """rl_model_cover_rows: the background rows counted so far"""
+        n = C.c_int64(0)
+        check(lib().rl_model_cover_rows(self.h, C.byref(n)))
+        return n.value
+
+    def cover_of(self, tree):
+        """rl_model_get_cover: (uint64 covers, float64 node values) of the nodes of one tree, in the pre-order of the model text"""
+        L, n = lib(), C.c_int32(0)
+        L.rl_model_get_cover(self.h, int(tree), None, None, -1, C.byref(n))       # (refused: cap is below; the node count is still set)
+        counts, values = np.zeros(max(1, n.value), np.uint64), np.zeros(max(1, n.value), np.float64)
+        check(L.rl_model_get_cover(self.h, int(tree), counts.ctypes.data, values.ctypes.data, n.value, C.byref(n)))
+        return counts[:n.value], values[:n.value]
+
+    def predict_contribs(self, rows, columns=None, scratch_bytes=0):
+        """rl_model_predict_contribs: (float64 [n_docs][C + 2], the C column ids).  Column c < C holds the contribution of feature
+        columns[c] to every row's score, column C what the features not asked for contribute, column C + 1 the bias: Saabas path
+        attribution over the covers of the last cover() calls.  columns=None: the model's features(), and column C is +0.0.  A row's
+        columns sum to the f64 sum of its weighted leaf outputs -- predict_rows' float chain up to float rounding."""
+        L, rows, buf = self._contrib_rows(rows)
+        if columns is None:
+            ids, cols, nc = [int(f) for f in self.features()], None, 0
+        else:
+            cols = np.ascontiguousarray(columns, dtype=np.int32)
+            if cols.ndim != 1:
+                raise RankLibError("rlhip: feature contributions take columns [n_columns]")
+            ids, nc = [int(c) for c in cols], int(cols.size)
+            if not nc:
+                cols = np.zeros(1, np.int32)          # (an empty list is refused by the library, by name: it must not arrive as NULL)
+        out = np.zeros((rows.shape[0], len(ids) + 2), np.float64)
+        obuf = out if out.size else np.zeros(1, np.float64)
+        check(L.rl_model_predict_contribs(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], None if cols is None else cols.ctypes.data, nc,
+                                          int(scratch_bytes), obuf.ctypes.data))
+        return out, ids
+
+    def leaf_sums(self, rows):
+        """rl_model_predict_leaf_sums: float64 [n_docs], per row the f64 sum of weight * leaf output over the trees -- what the row's
+        contributions sum to up to f64 rounding"""
+        L, rows, buf = self._contrib_rows(rows)
+        out = np.zeros(max(1, rows.shape[0]), np.float64)
+        check(L.rl_model_predict_leaf_sums(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], out.ctypes.data))
+        return out[:rows.shape[0]]
 
     def path(self):
         """MODEL_PATH_* of the last predict call: which kernel it took"""
@@ -1278,6 +1347,20 @@ def stage_times():
     w, r = C.c_double(0), C.c_double(0)
     check(lib().rl_debug_stage_times(C.byref(w), C.byref(r)))
     return w.value, r.value
+
+
+def contrib_times():
+    """rl_debug_contrib_times: (cover ms, walk ms) of this thread's last cover / predict_contribs calls, between device events"""
+    c, w = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_contrib_times(C.byref(c), C.byref(w)))
+    return c.value, w.value
+
+
+def contrib_passes():
+    """rl_debug_contrib_passes: the column passes of this thread's last predict_contribs call"""
+    p = C.c_int32(0)
+    check(lib().rl_debug_contrib_passes(C.byref(p)))
+    return p.value
 
 
 def permuted_times():

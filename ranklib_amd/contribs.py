@@ -1,0 +1,145 @@
+"""python -m ranklib_amd.contribs: which features put a document where it is -- per-document feature contributions of a LambdaMART /
+MART model (Saabas path attribution, XGBoost's pred_contribs with approx_contribs) in one GPU pass per file (LambdaMART.contributions,
+DESIGN.md 26).  RankLib's model text holds no node counts, so every node's cover is counted on a background file first, usually the
+training file.  A document's contributions sum to the f64 sum of its weighted leaf outputs, which is the model's score up to the float
+rounding of Ensemble.eval's chain -- not its bits.
+
+  -load model            the model (one)
+  -background file       the file the nodes' covers are counted on (repeatable: the counts add up)
+  -test file             the file whose documents are explained (one)
+  -feature file          the features to report, one id per line as for the evaluator; what the others contribute goes to `rest`
+                         (default: every feature the model splits on)
+  -norm, -missingZero, -device   as in ranklib_amd.evaluator: the files are prepared by the code its -load -test uses
+  -out tsv               one line per document: qid <TAB> index in its list <TAB> the model's score (Float.toString) and then
+                         fid:value ... rest:value bias:value, the values as Double.toString
+  -summary tsv           one line per feature: id <TAB> mean |contribution| over the file <TAB> mean contribution, sorted by the first
+                         descending, then by id (`rest` and `bias` are printed, not written).  The sums are math.fsum over the documents,
+                         divided once: exactly rounded, so the order of the documents does not matter.
+
+It also prints the largest |sum of a document's slots - f64 sum of its weighted leaf outputs| over the file, the right-hand side from a
+walk of its own on the device (rl_model_predict_leaf_sums), chunk by chunk as the contributions go.
+"""
+import logging
+import math
+import sys
+
+import numpy as np
+
+from . import normalizer
+from ._native import RankLibError
+
+logger = logging.getLogger("ranklib_amd")
+
+
+def _means(col):
+    col = [float(v) for v in col]
+    return math.fsum(abs(v) for v in col) / len(col), math.fsum(col) / len(col)
+
+
+def summary_lines(ids, matrix):
+    """the -summary lines of contributions [docs][len(ids) + 2]: one per feature"""
+    from .learning import java_double_str
+    rows = sorted(((f,) + _means(matrix[:, c]) for c, f in enumerate(ids)), key=lambda r: (-r[1], r[0]))
+    return ["%d\t%s\t%s" % (f, java_double_str(a), java_double_str(m)) for f, a, m in rows]
+
+
+def main(argv=None):
+    from .evaluator import Evaluator
+    from .features import FeatureManager
+    from .learning import DataPoint, LambdaMART, RankerFactory, RankerType, java_double_str, java_float_str
+    args = list(sys.argv[1:] if argv is None else argv)
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    if not args:
+        print("Usage: -load model -background file [-background file ...] -test file [-feature file] [-norm sum|zscore|linear] [-missingZero] "
+              "[-device d] [-out tsv] [-summary tsv]")
+        return 0
+    models, backgrounds, testFiles = [], [], []
+    featureFile, outFile, summaryFile = "", "", ""
+    Evaluator.mustHaveRelDoc = False
+    Evaluator.normalize = False
+    Evaluator.qrelFile = ""
+    i = 0
+    while i < len(args):                                    # flags are matched case-insensitively, as the evaluator matches them
+        a = args[i].lower()
+
+        def nxt():
+            nonlocal i
+            i += 1
+            if i >= len(args):
+                raise RankLibError("Missing value for " + args[i - 1])
+            return args[i]
+        if a == "-load": models.append(nxt())
+        elif a == "-background": backgrounds.append(nxt())
+        elif a == "-test": testFiles.append(nxt())
+        elif a == "-feature": featureFile = nxt()
+        elif a == "-out": outFile = nxt()
+        elif a == "-summary": summaryFile = nxt()
+        elif a == "-missingzero": DataPoint.missingZero = True
+        elif a == "-norm":
+            Evaluator.nml = normalizer.create(nxt())
+            Evaluator.normalize = True
+        elif a == "-device": LambdaMART.device = int(nxt())
+        else:
+            raise RankLibError("Unknown command-line parameter: " + args[i])
+        i += 1
+    if len(models) != 1:
+        raise RankLibError("ranklib_amd.contribs takes exactly one -load model (got %d)" % len(models))
+    if not backgrounds:
+        raise RankLibError("ranklib_amd.contribs needs a -background file: the model text holds no node counts")
+    if len(testFiles) != 1:
+        raise RankLibError("ranklib_amd.contribs needs a -test file, exactly one (got %d)" % len(testFiles))
+    ranker = RankerFactory().loadRankerFromFile(models[0])
+    if not isinstance(ranker, LambdaMART):
+        ranker.contributions([], None)                      # the refusal, naming the model type
+    features = [int(f) for f in FeatureManager.readFeature(featureFile)] if featureFile else None
+    e = Evaluator(RankerType.LAMBDAMART, "ERR@10", "ERR@10")
+    for k, f in enumerate(backgrounds):
+        ranker.countCover(e.readTestFile(ranker, f), accumulate=k > 0)
+    test = e.readTestFile(ranker, testFiles[0])
+    cols = None if features is None else features
+    ids = [int(f) for f in ranker._model.features()] if cols is None else cols
+    parts, scores, worst = [], [], 0.0
+    for rows in ranker._rowChunks(test):                    # whole lists, the rows of a chunk under EVAL_ROW_BYTES
+        part = ranker._model.predict_contribs(rows, cols)[0]
+        parts.append(part)
+        scores.append(ranker._model.predict_rows(rows))
+        with np.errstate(all="ignore"):
+            total = np.zeros(len(rows), np.float64)
+            for c in range(part.shape[1]):                  # slot after slot: a serial f64 sum per document
+                total = total + part[:, c]
+            gap = np.abs(total - ranker._model.leaf_sums(rows))
+        gap = gap[np.isfinite(gap)]
+        if gap.size:
+            worst = max(worst, float(gap.max()))
+    if not parts:
+        parts, scores = [ranker._model.predict_contribs(np.zeros((0, 1), np.float32), cols)[0]], [np.zeros(0, np.float32)]
+    matrix, scores = np.concatenate(parts), np.concatenate(scores)
+    n_docs = matrix.shape[0]
+    logger.info("%d documents, %d features, background of %d rows", n_docs, len(ids), ranker._model.cover_rows())
+    logger.info("Largest |sum of contributions - f64 sum of weighted leaf outputs|: %s", java_double_str(worst))
+    names = [str(f) for f in ids] + ["rest", "bias"]
+    if outFile:
+        with open(outFile, "w", encoding="ascii") as out:
+            d = 0
+            for rl in test:
+                for k in range(rl.size()):
+                    out.write("%s\t%d\t%s\t%s\n" % (rl.getID(), k, java_float_str(scores[d]),
+                                                    "\t".join("%s:%s" % (nm, java_double_str(float(v))) for nm, v in zip(names, matrix[d]))))
+                    d += 1
+        logger.info("Contributions saved to: %s", outFile)
+    lines = summary_lines(ids, matrix) if n_docs else []
+    logger.info("feature\tmean |contribution|\tmean contribution")
+    for ln in lines:
+        logger.info(ln)
+    for nm, c in (("rest", len(ids)), ("bias", len(ids) + 1)):
+        if n_docs:
+            logger.info("%s\t%s\t%s", nm, *[java_double_str(v) for v in _means(matrix[:, c])])
+    if summaryFile:
+        with open(summaryFile, "w", encoding="ascii") as out:
+            out.write("".join(ln + "\n" for ln in lines))
+        logger.info("Summary saved to: %s", summaryFile)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

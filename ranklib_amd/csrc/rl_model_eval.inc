@@ -15,6 +15,11 @@ struct rl_model {
     int32_t maxcol = 0;                     // largest column any node reads
     EvalKnobs knobs;                        // RLHIP_EVAL_*, read by rl_model_from_text
     int32_t last_path = RL_MODEL_PATH_NONE; // the kernel the last predict call took (rl_model_debug_path)
+    // contributions (rl_contrib.inc): the background's covers and the node values made from them, [trees][maxn]; empty before rl_model_cover
+    std::vector<uint64_t> cover;
+    std::vector<double> value;
+    int64_t cover_rows = 0;
+    void *d_cover_nodes = nullptr;          // the trees as k_model_cover stages them (made by the first rl_model_cover call)
 };
 
 namespace rl {

@@ -261,6 +261,14 @@ class Ranker:
     def truncated(self, t):
         raise RankLibError("rlhip: truncated needs a LambdaMART or MART model: a %s model has no stages" % self.name())
 
+    # rlhip: per-document feature contributions walk the paths of one ensemble of trees
+    def countCover(self, background, accumulate=False):
+        raise RankLibError("rlhip: contributions needs a LambdaMART or MART model: a %s model has no trees%s" % (
+            self.name(), " of one ensemble: a forest is several ensembles averaged" if self.name() == "Random Forests" else ""))
+
+    def contributions(self, samples, background, features=None):
+        self.countCover(background)
+
     # rlhip: permutation feature importance: what a feature is worth under the scorer on these lists
     def _importanceFeatures(self, features):
         feats = sorted({int(f) for f in (self.features if features is None else features)})
@@ -630,6 +638,47 @@ class LambdaMART(Ranker):
                     values[c, r, dev[j]] = on_host(j, c, r)
             a = b
         return I.summarize(feats, base, values)
+
+    # --- per-document feature contributions (rlhip) ----------------------------------------------
+    def _rowChunks(self, samples):
+        """the documents of samples as rows, in chunks of whole lists whose rows stay under EVAL_ROW_BYTES"""
+        a = 0
+        while a < len(samples):
+            b, docs, width = a, 0, 1
+            while b < len(samples):
+                w = max(width, samples[b].getFeatureCount() + 1)
+                if b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
+                    break
+                docs, width, b = docs + samples[b].size(), w, b + 1
+            dps = [dp for q in range(a, b) for dp in samples[q].rl]
+            if dps:
+                yield self._rows(dps)
+            a = b
+
+    def countCover(self, background, accumulate=False):
+        """count, per node, the documents of `background` whose walk visits it (_native.Model.cover): RankLib's model text holds no node
+        counts, so the node values contributions() works with come from a background file, usually the training file.  accumulate: add
+        to the counts of earlier calls."""
+        if not accumulate:
+            self._model.cover(np.zeros((0, 1), np.float32))
+        for rows in self._rowChunks(background):
+            self._model.cover(rows, accumulate=True)
+
+    def contributions(self, samples, background, features=None):
+        """Which features put a document where it is: (f64 [documents of samples in file order][C + 2], the C feature ids).  Column c
+        holds what feature ids[c] contributes to every document's score, column C what the features not asked for contribute, column
+        C + 1 the bias -- Saabas path attribution over node values averaged with the covers of `background` (None: the counts of earlier
+        countCover calls).  features None: every feature the model splits on.  A row sums to the f64 sum of the document's weighted leaf
+        outputs: the model's score up to the float rounding of Ensemble.eval's chain, not its bits.  One _native.Model.predict_contribs
+        call per chunk of whole lists whose rows stay under EVAL_ROW_BYTES."""
+        if background is not None:
+            self.countCover(background)
+        cols = None if features is None else [int(f) for f in features]
+        ids = [int(f) for f in self._model.features()] if cols is None else cols
+        parts = [self._model.predict_contribs(rows, cols)[0] for rows in self._rowChunks(samples)]
+        if not parts:                                        # no document: the library still checks the columns and that covers exist
+            parts = [self._model.predict_contribs(np.zeros((0, 1), np.float32), cols)[0]]
+        return np.concatenate(parts), ids
 
     def truncated(self, t):
         """a ranker of this class holding the first t trees: its model text is truncate_model_text(model(), t)"""
