@@ -978,6 +978,50 @@ int  rl_debug_contrib_times(double *cover_ms, double *walk_ms);
 /* debug: the column passes of this thread's last rl_model_predict_contribs call */
 int  rl_debug_contrib_passes(int32_t *passes);
 
+/* ---- exact TreeSHAP contributions of a tree model, one pass over a file ------------------------------------------------
+ * rl_model_predict_contribs with the Shapley values themselves in place of Saabas' path attribution: XGBoost's pred_contribs without
+ * approx_contribs, path-dependent TreeSHAP.  WALK, COVER c[t][j], NODE VALUE val[t][j], W = (double)w_t, the slots (columns[0 .. C-1],
+ * rest = C, bias = C + 1, columns == NULL) and the row rule v = (f < row_stride) ? row[f] : 0 are those of the section above.
+ * VALUE OF A FEATURE SET: for tree t, a row and a set S of feature ids, v_S(j) of a node j is (double)out at a leaf; at a split on f in S
+ * v_S of the child the row's walk takes; at a split on f not in S (a v_S(l) + b v_S(r)) / (a + b), a = c[l], b = c[r], a = b = 1 where
+ * a + b == 0.  v_{}(0) = val[t][0]; v_all(0) is the row's leaf output.  The contribution of feature i in tree t is its Shapley value
+ * phi_i(t) in the game S -> v_S(0) over the features the tree splits on; the model's is the sum over t of W phi_i(t); the bias slot is the
+ * sum over t of W val[t][0], the chain of rl_model_predict_contribs' bias slot and therefore its bits.
+ * COMPUTED FORM (path form: every row meets every leaf).  Every slot is one serial f64 chain, in tree order, then leaf order (the
+ * pre-order of the model text), then element order.  The ELEMENTS e = 1 .. d of a leaf are the distinct features of its root-to-leaf
+ * path in order of first appearance, each with its slot, with z_e -- the f64 product, in root-to-leaf order, of the ratios
+ * (double)c[child on the path] / (double)(a + b) of the path's splits on the feature (a = b = 1 where a + b == 0: a split the background
+ * never reached gives 1/2) -- and with those splits' conditions.  Per row o_e = 1.0 if the row's own decision (v <= thr goes left,
+ * anything else, a NaN included, goes right) is the path's direction at EVERY split of the element, else 0.0.  Tables, one f64 quotient
+ * each: A[l][i] = (i+1)/(l+1), B[l][i] = (l-i)/(l+1), U[l][i] = (l+1)/(i+1), R[l][i] = (l+1)/(l-i).  Per (row, leaf):
+ *     w[0] = 1.0
+ *     for l = 1 .. d:   w[l] = 0.0;   for i = l-1 .. 0:   w[i+1] = w[i+1] + o_l * (w[i] * A[l][i]);   w[i] = (z_l * w[i]) * B[l][i]
+ *     for e = 1 .. d, unless o_e == z_e (possible only at 0 and 1: the term is zero, and a division by a zero cover stays out):
+ *         o_e == 1:   tot = 0; nxt = w[d];   for i = d-1 .. 0:   tmp = nxt * U[d][i];  tot = tot + tmp;  nxt = w[i] - (tmp * z_e) * B[d][i]
+ *         o_e == 0:   tot = 0;               for i = d-1 .. 0:   tot = tot + w[i] * R[d][i];             then tot = tot / z_e
+ *         acc[slot_e] = acc[slot_e] + ((tot * (o_e - z_e)) * (double)out_leaf) * W
+ * every operation rounded, no FMA.  (The o_e == 0 arm is the sum of w[i] / (z_e B[d][i]) with the division by z_e taken out of the sum
+ * and 1 / B as a table: one division per element instead of d.)  A single-leaf tree adds to bias only.  out is [n_docs][C + 2] as
+ * rl_model_predict_contribs has it; a requested id the model never splits on gets +0.0, and rest is exactly +0.0 under columns == NULL.
+ * The slots of a row sum to rl_model_predict_leaf_sums' value up to f64 rounding (local accuracy: a property, not a definition).
+ * ACCURACY: the unwind subtracts.  Against the same form in exact arithmetic, a row's slots were together within 1 x 2^-52 x (the sum
+ * over trees and leaves of |W out|) on ordinary models, but 3 856 of those units off on a chain of 30 DISTINCT features: twelve of the
+ * 52 mantissa bits, fourteen in the worst row seen.  Less than half the mantissa, but worth knowing.
+ * The result does not depend on the grid, the block width, the chunking under scratch_bytes or the number of column passes
+ * (rl_debug_shap_passes).  rl_model_shap_limits: *max_path is the model's longest element list, *limit the most the kernel takes (32:
+ * every tree of up to 33 leaves whatever its shape); it needs no cover.
+ * RL_ERR_INVALID: the cases of rl_model_predict_contribs, the message naming this entry point.  RL_ERR_STATE: before any
+ * rl_model_cover.  RL_ERR_UNSUPPORTED, before the device is touched: more than 2^31 rows per call; a path of more than *limit distinct
+ * features, the message naming tree and leaf.  rl_model_debug_path reports RL_MODEL_PATH_SHAP afterwards. */
+int  rl_model_predict_shap(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *columns,
+                           int32_t n_columns, int64_t scratch_bytes, double *out);
+enum { RL_MODEL_PATH_SHAP = 6 };
+int  rl_model_shap_limits(const rl_model *m, int32_t *max_path, int32_t *limit);
+/* debug (tools/shap_bench.py): ms between device events around the k_model_shap launches of this thread's last rl_model_predict_shap
+ * call, summed over the chunks; and the column passes of that call */
+int  rl_debug_shap_times(double *walk_ms);
+int  rl_debug_shap_passes(int32_t *passes);
+
 #ifdef __cplusplus
 }
 #endif

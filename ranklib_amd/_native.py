@@ -147,6 +147,7 @@ ABI_SYMBOLS = [
     "rl_model_predict_stages", "rl_model_eval_stages", "rl_debug_stage_times",
     "rl_model_predict_permuted", "rl_model_eval_permuted", "rl_debug_permuted_times",
     "rl_model_cover", "rl_model_cover_rows", "rl_model_get_cover", "rl_model_predict_contribs", "rl_model_predict_leaf_sums", "rl_debug_contrib_times", "rl_debug_contrib_passes",
+    "rl_model_predict_shap", "rl_model_shap_limits", "rl_debug_shap_times", "rl_debug_shap_passes",
     "rl_adopt_model_text",
 ]
 
@@ -309,6 +310,11 @@ def lib():
         L.rl_model_predict_leaf_sums.argtypes = [vp, vp, i64, i32, vp]
         L.rl_debug_contrib_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_debug_contrib_passes.argtypes = [C.POINTER(i32)]
+    if hasattr(L, "rl_model_predict_shap"):   # (A/B builds of older sources have Saabas contributions only)
+        L.rl_model_predict_shap.argtypes = [vp, vp, i64, i32, vp, i32, i64, vp]
+        L.rl_model_shap_limits.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        L.rl_debug_shap_times.argtypes = [C.POINTER(C.c_double)]
+        L.rl_debug_shap_passes.argtypes = [C.POINTER(i32)]
     if hasattr(L, "rl_adopt_model_text"):     # (A/B builds of older sources cannot resume)
         L.rl_adopt_model_text.argtypes = [vp, C.c_char_p, i64, C.POINTER(i32)]
     _lib = L
@@ -708,6 +714,7 @@ MODEL_PATH_NONE, MODEL_PATH_TILED, MODEL_PATH_GENERIC = 0, 1, 2
 MODEL_PATH_PERMUTED = 3             # rl_model_predict_permuted / rl_model_eval_permuted: one kernel for every model
 PERMUTED_BATCH = 16                 # RL_PERMUTED_BATCH (rlhip.h): cells k_model_permuted_scores takes per document at a time
 MODEL_PATH_COVER, MODEL_PATH_CONTRIBS = 4, 5      # rl_model_cover (k_model_cover) / rl_model_predict_contribs (k_model_contribs)
+MODEL_PATH_SHAP = 6                               # rl_model_predict_shap (k_model_shap)
 
 
 class Model:
@@ -887,6 +894,22 @@ class Model:
         columns[c] to every row's score, column C what the features not asked for contribute, column C + 1 the bias: Saabas path
         attribution over the covers of the last cover() calls.  columns=None: the model's features(), and column C is +0.0.  A row's
         columns sum to the f64 sum of its weighted leaf outputs -- predict_rows' float chain up to float rounding."""
+        return self._predict_slots("rl_model_predict_contribs", rows, columns, scratch_bytes)
+
+    def predict_shap(self, rows, columns=None, scratch_bytes=0):
+        """rl_model_predict_shap: predict_contribs' layout with exact path-dependent TreeSHAP values in place of Saabas' path attribution
+        (DESIGN.md 27): every row meets every leaf of every tree, about two orders of magnitude more work."""
+        if not hasattr(lib(), "rl_model_predict_shap"):
+            raise RankLibError("rlhip: this librlhip.so has no exact contributions (rl_model_predict_shap)")
+        return self._predict_slots("rl_model_predict_shap", rows, columns, scratch_bytes)
+
+    def shap_limits(self):
+        """rl_model_shap_limits: (the most distinct features on one root-to-leaf path of the model, the most predict_shap takes)"""
+        d, p = C.c_int32(0), C.c_int32(0)
+        check(lib().rl_model_shap_limits(self.h, C.byref(d), C.byref(p)))
+        return d.value, p.value
+
+    def _predict_slots(self, entry, rows, columns, scratch_bytes):
         L, rows, buf = self._contrib_rows(rows)
         if columns is None:
             ids, cols, nc = [int(f) for f in self.features()], None, 0
@@ -899,8 +922,8 @@ class Model:
                 cols = np.zeros(1, np.int32)          # (an empty list is refused by the library, by name: it must not arrive as NULL)
         out = np.zeros((rows.shape[0], len(ids) + 2), np.float64)
         obuf = out if out.size else np.zeros(1, np.float64)
-        check(L.rl_model_predict_contribs(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], None if cols is None else cols.ctypes.data, nc,
-                                          int(scratch_bytes), obuf.ctypes.data))
+        check(getattr(L, entry)(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], None if cols is None else cols.ctypes.data, nc,
+                                int(scratch_bytes), obuf.ctypes.data))
         return out, ids
 
     def leaf_sums(self, rows):
@@ -1360,6 +1383,20 @@ def contrib_passes():
     """rl_debug_contrib_passes: the column passes of this thread's last predict_contribs call"""
     p = C.c_int32(0)
     check(lib().rl_debug_contrib_passes(C.byref(p)))
+    return p.value
+
+
+def shap_times():
+    """rl_debug_shap_times: walk ms of this thread's last predict_shap call, between device events"""
+    w = C.c_double(0)
+    check(lib().rl_debug_shap_times(C.byref(w)))
+    return w.value
+
+
+def shap_passes():
+    """rl_debug_shap_passes: the column passes of this thread's last predict_shap call"""
+    p = C.c_int32(0)
+    check(lib().rl_debug_shap_passes(C.byref(p)))
     return p.value
 
 

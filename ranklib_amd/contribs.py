@@ -9,6 +9,9 @@ rounding of Ensemble.eval's chain -- not its bits.
   -test file             the file whose documents are explained (one)
   -feature file          the features to report, one id per line as for the evaluator; what the others contribute goes to `rest`
                          (default: every feature the model splits on)
+  -exact                 exact Shapley values (path-dependent TreeSHAP, XGBoost's pred_contribs without approx_contribs)
+                         in place of Saabas' path attribution: the same files and the same local-accuracy line, from about two orders
+                         of magnitude more work on the device
   -norm, -missingZero, -device   as in ranklib_amd.evaluator: the files are prepared by the code its -load -test uses
   -out tsv               one line per document: qid <TAB> index in its list <TAB> the model's score (Float.toString) and then
                          fid:value ... rest:value bias:value, the values as Double.toString
@@ -51,10 +54,11 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
         print("Usage: -load model -background file [-background file ...] -test file [-feature file] [-norm sum|zscore|linear] [-missingZero] "
-              "[-device d] [-out tsv] [-summary tsv]")
+              "[-device d] [-out tsv] [-summary tsv] [-exact]")
         return 0
     models, backgrounds, testFiles = [], [], []
     featureFile, outFile, summaryFile = "", "", ""
+    exact = False
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
     Evaluator.qrelFile = ""
@@ -74,6 +78,7 @@ def main(argv=None):
         elif a == "-feature": featureFile = nxt()
         elif a == "-out": outFile = nxt()
         elif a == "-summary": summaryFile = nxt()
+        elif a == "-exact": exact = True
         elif a == "-missingzero": DataPoint.missingZero = True
         elif a == "-norm":
             Evaluator.nml = normalizer.create(nxt())
@@ -99,8 +104,9 @@ def main(argv=None):
     cols = None if features is None else features
     ids = [int(f) for f in ranker._model.features()] if cols is None else cols
     parts, scores, worst = [], [], 0.0
+    predict = ranker._model.predict_shap if exact else ranker._model.predict_contribs
     for rows in ranker._rowChunks(test):                    # whole lists, the rows of a chunk under EVAL_ROW_BYTES
-        part = ranker._model.predict_contribs(rows, cols)[0]
+        part = predict(rows, cols)[0]
         parts.append(part)
         scores.append(ranker._model.predict_rows(rows))
         with np.errstate(all="ignore"):
@@ -112,10 +118,12 @@ def main(argv=None):
         if gap.size:
             worst = max(worst, float(gap.max()))
     if not parts:
-        parts, scores = [ranker._model.predict_contribs(np.zeros((0, 1), np.float32), cols)[0]], [np.zeros(0, np.float32)]
+        parts, scores = [predict(np.zeros((0, 1), np.float32), cols)[0]], [np.zeros(0, np.float32)]
     matrix, scores = np.concatenate(parts), np.concatenate(scores)
     n_docs = matrix.shape[0]
     logger.info("%d documents, %d features, background of %d rows", n_docs, len(ids), ranker._model.cover_rows())
+    if exact:
+        logger.info("Exact Shapley values (path-dependent TreeSHAP)")
     logger.info("Largest |sum of contributions - f64 sum of weighted leaf outputs|: %s", java_double_str(worst))
     names = [str(f) for f in ids] + ["rest", "bias"]
     if outFile:

@@ -266,7 +266,7 @@ class Ranker:
         raise RankLibError("rlhip: contributions needs a LambdaMART or MART model: a %s model has no trees%s" % (
             self.name(), " of one ensemble: a forest is several ensembles averaged" if self.name() == "Random Forests" else ""))
 
-    def contributions(self, samples, background, features=None):
+    def contributions(self, samples, background, features=None, exact=False):
         self.countCover(background)
 
     # rlhip: permutation feature importance: what a feature is worth under the scorer on these lists
@@ -664,20 +664,23 @@ class LambdaMART(Ranker):
         for rows in self._rowChunks(background):
             self._model.cover(rows, accumulate=True)
 
-    def contributions(self, samples, background, features=None):
+    def contributions(self, samples, background, features=None, exact=False):
         """Which features put a document where it is: (f64 [documents of samples in file order][C + 2], the C feature ids).  Column c
         holds what feature ids[c] contributes to every document's score, column C what the features not asked for contribute, column
         C + 1 the bias -- Saabas path attribution over node values averaged with the covers of `background` (None: the counts of earlier
         countCover calls).  features None: every feature the model splits on.  A row sums to the f64 sum of the document's weighted leaf
         outputs: the model's score up to the float rounding of Ensemble.eval's chain, not its bits.  One _native.Model.predict_contribs
-        call per chunk of whole lists whose rows stay under EVAL_ROW_BYTES."""
+        call per chunk of whole lists whose rows stay under EVAL_ROW_BYTES.  exact: the Shapley values themselves, path-dependent
+        TreeSHAP (_native.Model.predict_shap), in the same layout: consistent where Saabas' attribution depends on which
+        feature sits higher in a tree, at about two orders of magnitude more work."""
         if background is not None:
             self.countCover(background)
         cols = None if features is None else [int(f) for f in features]
         ids = [int(f) for f in self._model.features()] if cols is None else cols
-        parts = [self._model.predict_contribs(rows, cols)[0] for rows in self._rowChunks(samples)]
+        predict = self._model.predict_shap if exact else self._model.predict_contribs
+        parts = [predict(rows, cols)[0] for rows in self._rowChunks(samples)]
         if not parts:                                        # no document: the library still checks the columns and that covers exist
-            parts = [self._model.predict_contribs(np.zeros((0, 1), np.float32), cols)[0]]
+            parts = [predict(np.zeros((0, 1), np.float32), cols)[0]]
         return np.concatenate(parts), ids
 
     def truncated(self, t):
