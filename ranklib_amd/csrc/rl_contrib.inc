@@ -1,5 +1,6 @@
 // rl_contrib.inc -- per-document feature contributions of a tree model (Saabas path attribution) in one pass over a file.  DESIGN.md 26.
-// Included at the end of rl_trainer.hip, after rl_permimp.inc (it uses rl_model, DevPool, StageEvents and kStageScratchDefault).
+// Included at the end of rl_trainer.hip, after rl_model_rows.inc (it uses rl_model and RowStream, the loop that streams a file's rows
+// through its kernels).  SlotPass, SlotPlan and slot_stream -- the column plan of a call and its passes -- are shared with rl_shap.inc.
 //
 //   k_model_cover     one lane per background row.  A block stages a tile of trees in LDS as 16-byte nodes, walks its rows through the
 //                     tile (Split.eval: a column at or beyond row_stride reads 0, `v <= thr` goes left, so a NaN goes right) and counts
@@ -71,11 +72,17 @@ __global__ __launch_bounds__(kThreads) void k_model_cover(const CoverNode *nodes
     }
 }
 
-struct ContribArgs {
-    const ContribNode *nodes; const float *w; int MAXN, nt, tile;
-    const float *X; int64_t n; int stride;
+// What k_model_contribs and k_model_shap share: one lane per row, a block of D rows, the f64 accumulators sA [slots of the pass][D + 1] in
+// LDS (a lane reads and writes only its own column), and the block's result stored transposed.
+struct SlotPass {
+    const float *X; int64_t n; int stride;                             // the chunk's rows
     int32_t s0, ns, slots, bias;                                       // the pass: slots [s0, s0 + ns) of `slots` = C + 2; bias = C + 1
     double *out;                                                       // [n][slots]
+};
+
+struct ContribArgs {
+    const ContribNode *nodes; const float *w; int MAXN, nt, tile;
+    SlotPass p;
 };
 
 __global__ __launch_bounds__(kContribDocsMax) void k_model_contribs(const ContribArgs a)
@@ -84,11 +91,11 @@ __global__ __launch_bounds__(kContribDocsMax) void k_model_contribs(const Contri
     ContribNode *sN = (ContribNode *)cb_raw;                           // [tile][MAXN]
     double *sA = (double *)(sN + (size_t)a.tile * a.MAXN);             // [ns][D + 1]
     const int D = (int)blockDim.x, AS = D + 1, tid = threadIdx.x;
-    const int bias = a.bias - a.s0;                                    // in [0, ns) in the pass that holds it
+    const int bias = a.p.bias - a.p.s0;                                // in [0, ns) in the pass that holds it
     const int64_t d0 = (int64_t)blockIdx.x * D;                        // one row tile per block: the grid is ceil(n / D), n < 2^31
-    const int nd = (int)min((int64_t)D, a.n - d0);
-    for (int s = 0; s < a.ns; s++) sA[s * AS + tid] = 0.0;
-    const float *row = a.X + (size_t)(d0 + (tid < nd ? tid : 0)) * a.stride;
+    const int nd = (int)min((int64_t)D, a.p.n - d0);
+    for (int s = 0; s < a.p.ns; s++) sA[s * AS + tid] = 0.0;
+    const float *row = a.p.X + (size_t)(d0 + (tid < nd ? tid : 0)) * a.p.stride;
     for (int t0 = 0; t0 < a.nt; t0 += a.tile) {
         const int tt = min(a.tile, a.nt - t0), words = tt * a.MAXN * (kContribNodeBytes / 16);
         __syncthreads();                                               // the tile before is walked
@@ -100,22 +107,22 @@ __global__ __launch_bounds__(kContribDocsMax) void k_model_contribs(const Contri
                 const ContribNode *tn = sN + t * a.MAXN;
                 const double W = (double)a.w[t0 + t];
                 ContribNode cur = tn[0];
-                if ((unsigned)bias < (unsigned)a.ns) sA[bias * AS + tid] = sA[bias * AS + tid] + W * cur.val;
+                if ((unsigned)bias < (unsigned)a.p.ns) sA[bias * AS + tid] = sA[bias * AS + tid] + W * cur.val;
                 while (cur.feat != -1) {
-                    const float v = (cur.feat < a.stride) ? row[cur.feat] : 0.f;       // -missingZero  DenseDataPoint.java:22-25
+                    const float v = (cur.feat < a.p.stride) ? row[cur.feat] : 0.f;     // -missingZero  DenseDataPoint.java:22-25
                     const ContribNode nx = tn[(v <= cur.thr) ? cur.left : cur.right];   // Split.java:118
                     const double d = W * (nx.val - cur.val);
-                    const int s = cur.slot - a.s0;
-                    if ((unsigned)s < (unsigned)a.ns) sA[s * AS + tid] = sA[s * AS + tid] + d;
+                    const int s = cur.slot - a.p.s0;
+                    if ((unsigned)s < (unsigned)a.p.ns) sA[s * AS + tid] = sA[s * AS + tid] + d;
                     cur = nx;
                 }
             }
         }
     }
     __syncthreads();
-    for (int e = tid; e < nd * a.ns; e += D) {                         // transposed: adjacent lanes, adjacent slots of one document
-        const int dd = e / a.ns, s = e - dd * a.ns;
-        a.out[(size_t)(d0 + dd) * a.slots + a.s0 + s] = sA[s * AS + dd];
+    for (int e = tid; e < nd * a.p.ns; e += D) {                       // transposed: adjacent lanes, adjacent slots of one document
+        const int dd = e / a.p.ns, s = e - dd * a.p.ns;
+        a.p.out[(size_t)(d0 + dd) * a.p.slots + a.p.s0 + s] = sA[s * AS + dd];
     }
 }
 
@@ -143,6 +150,82 @@ __global__ __launch_bounds__(kThreads) void k_model_leaf_sums(const EnsTree e, c
 static thread_local double g_cb_cover_ms = 0.0, g_cb_walk_ms = 0.0;    // the last calls of this thread, device events
 static thread_local int32_t g_cb_passes = 0;
 
+// The columns of a contributions call (the arguments', or every feature of the model) as sorted (id, place) pairs, the C + 2 slots they
+// make -- the columns, the rest, the bias -- and how the slots go through the kernel: rows of a block and slots of a pass, set by the
+// kernel's own plan (contrib_plan, shap_plan).
+struct SlotPlan {
+    std::vector<std::pair<int32_t, int32_t>> sorted;
+    int64_t C = 0, slots = 0, per_pass = 0;
+    int docs = 0;
+    int32_t passes() const { return (int32_t)((slots + per_pass - 1) / per_pass); }
+};
+
+static SlotPlan slot_plan(const rl_model *m, const int32_t *columns, int32_t n_columns)
+{
+    SlotPlan sp;
+    const std::vector<int32_t> cols = columns ? std::vector<int32_t>(columns, columns + n_columns) : m->features;
+    sp.C = (int64_t)cols.size(); sp.slots = sp.C + 2;
+    sp.sorted.resize((size_t)sp.C);
+    for (int64_t c = 0; c < sp.C; c++) sp.sorted[(size_t)c] = {cols[(size_t)c], (int32_t)c};
+    std::sort(sp.sorted.begin(), sp.sorted.end());
+    return sp;
+}
+
+// The rows of a call through `kernel`, whose other arguments a holds: chunks of rows and of their output [chunk][slots] within
+// scratch_bytes, and per chunk the column passes, one launch per per_pass slots; lds(ns) is the kernel's dynamic LDS for a pass of ns slots.
+template <class Args, class Lds>
+static int slot_stream(void (*kernel)(const Args), Args &a, const SlotPlan &sp, const float *X, int64_t n_docs, int32_t row_stride,
+                       int64_t scratch_bytes, double *out, RowStream &rows, Lds lds)
+{
+    const int rc = rows.open(n_docs, row_stride, scratch_bytes, (int64_t)row_stride * 4 + 8 * sp.slots);
+    if (rc) return rc;
+    RL_HIP(rows.pool.alloc(&a.p.out, (size_t)rows.chunk * sp.slots));
+    a.p.X = rows.dX; a.p.stride = row_stride; a.p.slots = (int32_t)sp.slots; a.p.bias = (int32_t)(sp.C + 1);
+    return rows.run(X, n_docs, row_stride, [&](int64_t nr) -> int {
+        a.p.n = nr;
+        for (int64_t s0 = 0; s0 < sp.slots; s0 += sp.per_pass) {
+            a.p.s0 = (int32_t)s0; a.p.ns = (int32_t)std::min(sp.per_pass, sp.slots - s0);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((nr + sp.docs - 1) / sp.docs)), dim3(sp.docs), lds(a.p.ns), 0, a);
+            RL_HIP(hipGetLastError());
+        }
+        return RL_OK;
+    }, a.p.out, out, sp.slots);
+}
+
+// the leaves' counts of n_docs background rows, leaf [trees][maxn]
+static int cover_count(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, int tile, size_t lds, std::vector<uint64_t> &leaf)
+{
+    RL_HIP(hipSetDevice(m->device));
+    if (!m->d_cover_nodes) {                                           // the trees as k_model_cover stages them, made by the model's first call
+        std::vector<CoverNode> cn(leaf.size(), CoverNode{-1, 0.f, -1, -1});
+        for (size_t t = 0; t < m->trees.size(); t++) {
+            const HostTree &h = m->trees[t];
+            for (int j = 0; j < h.n_nodes; j++) cn[t * m->maxn + j] = CoverNode{h.feature[j], h.threshold[j], h.left[j], h.right[j]};
+        }
+        CoverNode *d = nullptr;
+        RL_HIP(m->pool.upload(&d, cn.data(), cn.size()));
+        m->d_cover_nodes = d;
+    }
+    RL_HIP(hipFuncSetAttribute((const void *)k_model_cover, hipFuncAttributeMaxDynamicSharedMemorySize, kContribLds));
+    RowStream rows;
+    int rc = rows.open(n_docs, row_stride, 0, (int64_t)row_stride * 4);
+    if (rc) return rc;
+    unsigned long long *d_cover = nullptr;
+    RL_HIP(rows.pool.alloc(&d_cover, leaf.size()));
+    RL_HIP(hipMemset(d_cover, 0, leaf.size() * sizeof(unsigned long long)));
+    rc = rows.run(X, n_docs, row_stride, [&](int64_t nr) -> int {
+        hipLaunchKernelGGL(k_model_cover, dim3((unsigned)std::min<int64_t>(kCoverBlocks, (nr + kThreads - 1) / kThreads)), dim3(kThreads), lds, 0,
+                           (const CoverNode *)m->d_cover_nodes, m->maxn, (int)m->trees.size(), tile, (const float *)rows.dX, nr, row_stride, d_cover);
+        RL_HIP(hipGetLastError());
+        return RL_OK;
+    }, (const char *)nullptr, (char *)nullptr, 0);
+    g_cb_cover_ms = rows.ms;
+    if (rc) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the covers are copied as they are");
+    RL_HIP(hipMemcpy(leaf.data(), d_cover, leaf.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return RL_OK;
+}
+
 }  // namespace rl
 
 extern "C" {
@@ -158,44 +241,7 @@ int rl_model_cover(rl_model *m, const float *X, int64_t n_docs, int32_t row_stri
     if (lds > (size_t)kContribLds) return fail(RL_ERR_UNSUPPORTED, "rl_model_cover: a tree of " + std::to_string(m->maxn) + " nodes does not fit the LDS");
     g_cb_cover_ms = 0.0;
     std::vector<uint64_t> leaf(en, 0);
-    if (n_docs > 0) {
-        RL_HIP(hipSetDevice(m->device));
-        if (!m->d_cover_nodes) {
-            std::vector<CoverNode> cn(en, CoverNode{-1, 0.f, -1, -1});
-            for (size_t t = 0; t < T; t++) {
-                const HostTree &h = m->trees[t];
-                for (int j = 0; j < h.n_nodes; j++) cn[t * m->maxn + j] = CoverNode{h.feature[j], h.threshold[j], h.left[j], h.right[j]};
-            }
-            CoverNode *d = nullptr;
-            RL_HIP(m->pool.alloc(&d, en));
-            RL_HIP(hipMemcpy(d, cn.data(), en * sizeof(CoverNode), hipMemcpyHostToDevice));
-            m->d_cover_nodes = d;
-        }
-        RL_HIP(hipFuncSetAttribute((const void *)k_model_cover, hipFuncAttributeMaxDynamicSharedMemorySize, kContribLds));
-        const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_docs, kStageScratchDefault / ((int64_t)row_stride * 4)));
-        DevPool pool;
-        float *dX = nullptr; unsigned long long *d_cover = nullptr;
-        RL_HIP(pool.alloc(&dX, (size_t)chunk * row_stride));
-        RL_HIP(pool.alloc(&d_cover, en));
-        RL_HIP(hipMemset(d_cover, 0, en * sizeof(unsigned long long)));
-        StageEvents ev;
-        RL_HIP(ev.create());
-        for (int64_t r0 = 0; r0 < n_docs; r0 += chunk) {
-            const int64_t nr = std::min(chunk, n_docs - r0);
-            RL_HIP(hipMemcpy(dX, X + (size_t)r0 * row_stride, (size_t)nr * row_stride * sizeof(float), hipMemcpyHostToDevice));
-            RL_HIP(hipEventRecord(ev.e[0], 0));
-            hipLaunchKernelGGL(k_model_cover, dim3((unsigned)std::min<int64_t>(kCoverBlocks, (nr + kThreads - 1) / kThreads)), dim3(kThreads), lds, 0,
-                               (const CoverNode *)m->d_cover_nodes, m->maxn, (int)T, tile, (const float *)dX, nr, row_stride, d_cover);
-            RL_HIP(hipGetLastError());
-            RL_HIP(hipEventRecord(ev.e[1], 0));
-            RL_HIP(hipDeviceSynchronize());
-            float ms = 0.f;
-            RL_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-            g_cb_cover_ms += (double)ms;
-        }
-        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the covers are copied as they are");
-        RL_HIP(hipMemcpy(leaf.data(), d_cover, en * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
+    if (n_docs > 0 && (rc = cover_count(m, X, n_docs, row_stride, tile, lds, leaf))) return rc;
     const bool add = accumulate != 0 && !m->cover.empty();
     if (!add) { m->cover.assign(en, 0); m->cover_rows = 0; }
     m->value.assign(en, 0.0);
@@ -245,61 +291,34 @@ int rl_model_predict_contribs(rl_model *m, const float *X, int64_t n_docs, int32
     if (!rc) rc = contrib_check_columns(w, columns, n_columns, scratch_bytes, out, err);
     if (rc) return fail(rc, err);
     if (m->cover.empty()) return fail(RL_ERR_STATE, w + "no rl_model_cover call has been made on this model");
-    const std::vector<int32_t> cols = columns ? std::vector<int32_t>(columns, columns + n_columns) : m->features;
-    const int64_t C = (int64_t)cols.size(), slots = C + 2;
-    int docs; int64_t per_pass;
-    if (!contrib_plan(m->maxn, slots, docs, per_pass))
+    SlotPlan sp = slot_plan(m, columns, n_columns);
+    if (!contrib_plan(m->maxn, sp.slots, sp.docs, sp.per_pass))
         return fail(RL_ERR_UNSUPPORTED, w + "a tree of " + std::to_string(m->maxn) + " nodes does not fit the LDS");
     g_cb_walk_ms = 0.0;
-    g_cb_passes = (int32_t)((slots + per_pass - 1) / per_pass);
+    g_cb_passes = sp.passes();
     if (n_docs == 0) return RL_OK;
     RL_HIP(hipSetDevice(m->device));
     const size_t T = m->trees.size(), en = T * (size_t)m->maxn;
-    std::vector<std::pair<int32_t, int32_t>> sorted((size_t)C);
-    for (int64_t c = 0; c < C; c++) sorted[(size_t)c] = {cols[(size_t)c], (int32_t)c};
-    std::sort(sorted.begin(), sorted.end());
     std::vector<ContribNode> cn(en, ContribNode{-1, 0.f, -1, -1, 0.0, -1, 0});
     std::vector<int32_t> slot((size_t)m->maxn);
     for (size_t t = 0; t < T; t++) {
         const HostTree &h = m->trees[t];
-        contrib_node_slots(h, sorted, (int32_t)C, slot.data());
+        contrib_node_slots(h, sp.sorted, (int32_t)sp.C, slot.data());
         for (int j = 0; j < h.n_nodes; j++)
             cn[t * m->maxn + j] = ContribNode{h.feature[j], h.threshold[j], h.left[j], h.right[j], m->value[t * m->maxn + j], slot[(size_t)j], 0};
     }
-    const int tile = contrib_tree_tile(m->maxn);
-    // the rows of a chunk and their 8 (C + 2) bytes of output stay within scratch_bytes; a chunk holds at least one row
-    const int64_t budget = scratch_bytes > 0 ? scratch_bytes : kStageScratchDefault;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_docs, budget / ((int64_t)row_stride * 4 + 8 * slots)));
-    DevPool pool;
+    RowStream rows;
     ContribArgs a;
     memset(&a, 0, sizeof(a));
-    ContribNode *d_nodes = nullptr; float *dX = nullptr;
-    RL_HIP(pool.alloc(&d_nodes, en));
-    RL_HIP(pool.alloc(&dX, (size_t)chunk * row_stride));
-    RL_HIP(pool.alloc(&a.out, (size_t)chunk * slots));
-    RL_HIP(hipMemcpy(d_nodes, cn.data(), en * sizeof(ContribNode), hipMemcpyHostToDevice));
+    ContribNode *d_nodes = nullptr;
+    RL_HIP(rows.pool.upload(&d_nodes, cn.data(), en));
     RL_HIP(hipFuncSetAttribute((const void *)k_model_contribs, hipFuncAttributeMaxDynamicSharedMemorySize, kContribLds));
-    a.nodes = d_nodes; a.w = m->d_w; a.MAXN = m->maxn; a.nt = (int)T; a.tile = tile; a.X = dX; a.stride = row_stride;
-    a.slots = (int32_t)slots; a.bias = (int32_t)(C + 1);
-    StageEvents ev;
-    RL_HIP(ev.create());
-    for (int64_t r0 = 0; r0 < n_docs; r0 += chunk) {
-        const int64_t nr = std::min(chunk, n_docs - r0);
-        a.n = nr;
-        RL_HIP(hipMemcpy(dX, X + (size_t)r0 * row_stride, (size_t)nr * row_stride * sizeof(float), hipMemcpyHostToDevice));
-        RL_HIP(hipEventRecord(ev.e[0], 0));
-        for (int64_t s0 = 0; s0 < slots; s0 += per_pass) {
-            a.s0 = (int32_t)s0; a.ns = (int32_t)std::min(per_pass, slots - s0);
-            const size_t lds = (size_t)tile * m->maxn * sizeof(ContribNode) + (size_t)a.ns * (docs + 1) * sizeof(double);
-            hipLaunchKernelGGL(k_model_contribs, dim3((unsigned)((nr + docs - 1) / docs)), dim3(docs), lds, 0, a);
-            RL_HIP(hipGetLastError());
-        }
-        RL_HIP(hipEventRecord(ev.e[1], 0));
-        RL_HIP(hipMemcpy(out + (size_t)r0 * slots, a.out, (size_t)nr * slots * sizeof(double), hipMemcpyDeviceToHost));
-        float ms = 0.f;
-        RL_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        g_cb_walk_ms += (double)ms;
-    }
+    a.nodes = d_nodes; a.w = m->d_w; a.MAXN = m->maxn; a.nt = (int)T; a.tile = contrib_tree_tile(m->maxn);
+    const size_t tile_bytes = (size_t)a.tile * m->maxn * sizeof(ContribNode);
+    rc = slot_stream(k_model_contribs, a, sp, X, n_docs, row_stride, scratch_bytes, out, rows,
+                     [&](int ns) { return tile_bytes + (size_t)ns * (sp.docs + 1) * sizeof(double); });
+    g_cb_walk_ms = rows.ms;
+    if (rc) return rc;
     m->last_path = RL_MODEL_PATH_CONTRIBS;
     return RL_OK;
 }
@@ -313,20 +332,16 @@ int rl_model_predict_leaf_sums(rl_model *m, const float *X, int64_t n_docs, int3
     if (!out) return fail(RL_ERR_INVALID, w + "null output");
     if (n_docs == 0) return RL_OK;
     RL_HIP(hipSetDevice(m->device));
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_docs, kStageScratchDefault / ((int64_t)row_stride * 4 + 8)));
-    DevPool pool;
-    float *dX = nullptr; double *dO = nullptr;
-    RL_HIP(pool.alloc(&dX, (size_t)chunk * row_stride));
-    RL_HIP(pool.alloc(&dO, (size_t)chunk));
-    for (int64_t r0 = 0; r0 < n_docs; r0 += chunk) {
-        const int64_t nr = std::min(chunk, n_docs - r0);
-        RL_HIP(hipMemcpy(dX, X + (size_t)r0 * row_stride, (size_t)nr * row_stride * sizeof(float), hipMemcpyHostToDevice));
+    RowStream rows;
+    double *dO = nullptr;
+    if ((rc = rows.open(n_docs, row_stride, 0, (int64_t)row_stride * 4 + 8))) return rc;
+    RL_HIP(rows.pool.alloc(&dO, (size_t)rows.chunk));
+    return rows.run(X, n_docs, row_stride, [&](int64_t nr) -> int {
         hipLaunchKernelGGL(k_model_leaf_sums, dim3((unsigned)std::min<int64_t>(8192, (nr + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, m->ens,
-                           (const float *)m->d_w, m->maxn, (int)m->trees.size(), (const float *)dX, nr, row_stride, dO);
+                           (const float *)m->d_w, m->maxn, (int)m->trees.size(), (const float *)rows.dX, nr, row_stride, dO);
         RL_HIP(hipGetLastError());
-        RL_HIP(hipMemcpy(out + r0, dO, (size_t)nr * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return RL_OK;
+        return RL_OK;
+    }, dO, out, 1);
 }
 
 int rl_debug_contrib_times(double *cover_ms, double *walk_ms)

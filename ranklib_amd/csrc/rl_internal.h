@@ -257,6 +257,12 @@ struct DevPool {                       // device allocations of one handle or on
         if (e == hipSuccess) { ptrs.push_back(q); *p = (T *)q; }
         return e;
     }
+    // alloc and a blocking host-to-device copy of n elements (n == 0: the one-element allocation, nothing copied)
+    template <typename T> hipError_t upload(T **p, const T *src, size_t n)
+    {
+        const hipError_t e = alloc(p, n);
+        return (e != hipSuccess || n == 0) ? e : hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice);
+    }
     void release(void *p)
     {
         for (auto &q : ptrs) if (q == p) { (void)hipFree(q); q = nullptr; }

@@ -1,17 +1,19 @@
 // rl_model_eval.inc -- the scoring-only model: an ensemble loaded from RankLib model text, its two evaluation kernels and the rl_model_* ABI.
-// Included at the end of rl_trainer.hip (it uses DevPool, EnsTree and HostTree).
+// Included at the end of rl_trainer.hip (it uses DevPool, EnsTree and HostTree).  Which models the tiled kernel takes and the
+// packed format it walks are stated in rl_eval_pack_host.h, host only; rl_model_from_text uploads what eval_pack returns.
+#include "rl_eval_pack_host.h"
+
 struct rl_model {
     int32_t device = 0;
     std::vector<HostTree> trees;
     std::vector<int32_t> features;
     int32_t maxn = 1;
-    bool uniform_weight = true;
     DevPool pool;
     EnsTree ens;
     float *d_w = nullptr;
     unsigned long long *d_pack = nullptr;   // packed nodes for k_model_eval_tiled (null when the model does not fit the packing)
-    unsigned char *d_perm = nullptr;        // [tiles][kEvalTreeTile] trees of a tile by descending depth (255 = none): walker wavefront p takes ranks 8 p .. 8 p + 7
-    unsigned char *d_gdepth = nullptr;      // [tiles][kEvalParts] deepest leaf among a walker's trees = its lockstep walk length
+    unsigned char *d_perm = nullptr;        // EvalPack::perm [tiles][kEvalTreeTile]: chain u of walker p walks tree perm[p * kEvalPer + u] of the tile (255 = none); the tile's trees by descending depth, dealt round the walkers
+    unsigned char *d_gdepth = nullptr;      // EvalPack::meta [tiles][kEvalMetaDepths]: every walker's steps (its deepest tree), then per walker the steps at which its phases end
     int32_t maxcol = 0;                     // largest column any node reads
     EvalKnobs knobs;                        // RLHIP_EVAL_*, read by rl_model_from_text
     int32_t last_path = RL_MODEL_PATH_NONE; // the kernel the last predict call took (rl_model_debug_path)
@@ -51,10 +53,10 @@ __global__ __launch_bounds__(kThreads) void k_model_eval(const EnsTree e, const 
 //     -missingZero): a lane reads sX[c * kEvalDocs + doc], so the bank is doc % 32 whatever column the lane's path asks
 //     for -- conflict-free;
 //   * trees stream through LDS in tiles of kEvalTreeTile as packed 8-byte nodes, children adjacent (right = left + 1):
-//       bits 0..31 threshold (or leaf output) float bits | 32..47 byte offset of the column in sX (0xFFFF = leaf)
+//       bits 0..31 threshold (or leaf output) float bits | 32..47 byte offset of the column in sX (0: a leaf, see the walk below)
 //       | 48..63 byte offset of the left child in the tree
 //     so a step is: load node, load value, compare, add -- 7 VALU + 2 LDS instructions;
-//   * walker wavefront p (of kEvalParts) owns trees [p*kEvalPer, (p+1)*kEvalPer) of the tile for all documents: kEvalPer
+//   * walker wavefront p (of kEvalParts) owns the kEvalPer trees perm[p*kEvalPer .. (p+1)*kEvalPer) of the tile for all documents: kEvalPer
 //     chains per lane in lockstep (a leaf is a fixed point of the step, so finished trees idle in place).  The walk is
 //     bound by instruction issue (13 per chain step), not by LDS latency.  Measured and dropped: refilling a finished chain
 //     with the lane's next tree (fewer steps, but a leaf branch that some lane takes at almost every step: 8.2 M docs/s
@@ -65,36 +67,7 @@ __global__ __launch_bounds__(kThreads) void k_model_eval(const EnsTree e, const 
 //   * the next tile of trees is fetched into registers while the current one is walked.
 // Needs: column offsets and child offsets that fit 16 bits, and the LDS budget; otherwise k_model_eval runs.
 // ------------------------------------------------------------------------------------------------
-#ifndef RL_EVAL_PARTS
-#define RL_EVAL_PARTS 4
-#endif
-#ifndef RL_EVAL_PER
-#define RL_EVAL_PER 8
-#endif
-constexpr int kEvalDocs = 64, kEvalParts = RL_EVAL_PARTS, kEvalPer = RL_EVAL_PER, kEvalTreeTile = kEvalParts * kEvalPer;
-constexpr int kEvalThreads = kEvalDocs * (kEvalParts + 1), kEvalPrefetch = 8;     // 8-byte words each thread prefetches per tile
-// Phases of a walker's walk (round 6; see the loop): chains still walking after the first phase, the second, .. and in the last one.  Same box,
-// alternating libraries, 30 M rows x 10 000 trees (profiles/r06w_ab_infer_phased_walk.txt): one loop of eight chains 26.8 M docs/s | 8 -> 4: 27.9 |
-// 8 -> 4 -> 2: 27.5 | 8 -> 6 -> 4 -> 2: 28.3 - 28.5 | a staircase 8 -> 7 -> .. -> 1: 23.3.
-#ifndef RL_EVAL_PHASES
-#define RL_EVAL_PHASES 3
-#endif
-#if RL_EVAL_PHASES == 1
-constexpr int kEvalPhases = 1, kEvalPh1 = 4, kEvalPh2 = 2, kEvalPhLast = 4;
-#elif RL_EVAL_PHASES == 2
-constexpr int kEvalPhases = 2, kEvalPh1 = 4, kEvalPh2 = 2, kEvalPhLast = 2;
-#else
-constexpr int kEvalPhases = 3, kEvalPh1 = 6, kEvalPh2 = 4, kEvalPhLast = 2;
-#endif
-static_assert(kEvalPer >= kEvalPh1 && kEvalPh1 >= kEvalPh2 && kEvalPh2 >= kEvalPhLast && kEvalPhLast >= 1, "a phase walks the deepest chains of the phase before it");
-constexpr int kEvalMetaDepths = kEvalParts * (1 + kEvalPhases);      // per tile: every walker's steps, then the steps at which its phases end
-
-static inline size_t eval_tiled_lds(int cols, int maxn)
-{
-    return (size_t)cols * kEvalDocs * 4 + (size_t)kEvalTreeTile * maxn * 8 + (size_t)2 * kEvalTreeTile * kEvalDocs * 4 + 2 * kEvalTreeTile * 4 + 2 * (kEvalTreeTile + kEvalMetaDepths);
-}
-
-// cols = max(row_stride, largest column any node reads + 1)
+// (the tile constants, eval_tiled_lds and the packed format itself: rl_eval_pack_host.h)
 //
 // The walk (round 4).  A leaf is packed as a node that loops onto itself: it "reads" column 0 -- no RankLib feature has id 0; the staged tile holds
 // -infinity there -- so `x <= value` is always true and its left-child offset is its own.  A chain step is then the same eight instructions for
@@ -240,22 +213,13 @@ __global__ __launch_bounds__(kEvalThreads) void k_model_eval_tiled(const unsigne
 }
 }  // namespace rl
 
-extern "C" {
+namespace rl {
 
-int rl_model_from_text(const char *text, int32_t device, rl_model **out)
+// the stages of rl_model_from_text, after the text is parsed and the device is open
+
+// the trees as EnsTree arrays [trees][maxn] (what k_model_eval and the other per-document kernels walk) and the trees' weights
+static int model_upload_ens(rl_model *m)
 {
-    if (!text || !out) return fail(RL_ERR_INVALID, "null argument");
-    *out = nullptr;
-    std::unique_ptr<rl_model> m(new rl_model());
-    std::string err;
-    if (!model_from_text(text, m->trees, err)) return fail(RL_ERR_INVALID, "Error in Emsemble(xmlRepresentation): " + err);
-    const int gate = open_device(device, false);      // after the text is parsed; a model has never tested the architecture
-    if (gate) return gate;
-    m->device = device;
-    m->knobs.read();
-    std::map<int32_t, int> fids;
-    for (auto &t : m->trees) { m->maxn = std::max(m->maxn, t.n_nodes); for (int f : t.feature) if (f != -1) fids[f] = 0; }
-    for (auto &kv : fids) m->features.push_back(kv.first);
     const size_t nt = m->trees.size(), en = std::max<size_t>(1, nt * m->maxn);
     std::vector<int32_t> fi(en, -1), le(en, -1), ri(en, -1);
     std::vector<float> th(en, 0.f), ou(en, 0.f), w(std::max<size_t>(1, nt), 0.f);
@@ -268,93 +232,45 @@ int rl_model_from_text(const char *text, int32_t device, rl_model **out)
         }
     }
     memset(&m->ens, 0, sizeof(m->ens));
-    RL_HIP(m->pool.alloc(&m->ens.feat_idx, en)); RL_HIP(m->pool.alloc(&m->ens.left, en)); RL_HIP(m->pool.alloc(&m->ens.right, en));
-    RL_HIP(m->pool.alloc(&m->ens.thr, en)); RL_HIP(m->pool.alloc(&m->ens.out, en)); RL_HIP(m->pool.alloc(&m->d_w, w.size()));
-    RL_HIP(hipMemcpy(m->ens.feat_idx, fi.data(), en * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(m->ens.left, le.data(), en * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(m->ens.right, ri.data(), en * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(m->ens.thr, th.data(), en * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(m->ens.out, ou.data(), en * 4, hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(m->d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-    {   // packed nodes (see k_model_eval_tiled): breadth-first renumbering puts siblings next to each other
-        int maxcol = 0;
-        for (int32_t f : m->features) maxcol = std::max(maxcol, f);
-        m->maxcol = maxcol;
-        bool ok = nt > 0 && (size_t)m->maxn * 8 < 0x10000 && ((size_t)maxcol + 1) * kEvalDocs * 4 < 0xffff &&
-                  (size_t)kEvalTreeTile * m->maxn <= (size_t)kEvalThreads * kEvalPrefetch;
-        for (int32_t f : m->features) ok = ok && f >= 1;        // column 0 is what a packed leaf reads (no RankLib feature has id 0: learning/DataPoint.java:33)
-        if (ok) {
-            std::vector<unsigned long long> pk(en, 0ull);           // (padding: a leaf at offset 0 with value +0.0)
-            std::vector<int> order, newid, lvl;
-            std::vector<int> tdepth(nt, 0);
-            for (size_t i = 0; i < nt && ok; i++) {
-                const HostTree &t = m->trees[i];
-                order.assign(1, 0); newid.assign(t.n_nodes, -1); newid[0] = 0; lvl.assign(1, 0);
-                for (size_t h = 0; h < order.size(); h++) {
-                    const int j = order[h];
-                    if (t.feature[j] == -1) continue;
-                    if (t.left[j] < 0 || t.right[j] < 0 || t.left[j] >= t.n_nodes || t.right[j] >= t.n_nodes || (int)order.size() + 2 > t.n_nodes) { ok = false; break; }
-                    newid[t.left[j]] = (int)order.size(); order.push_back(t.left[j]); lvl.push_back(lvl[h] + 1);
-                    newid[t.right[j]] = (int)order.size(); order.push_back(t.right[j]); lvl.push_back(lvl[h] + 1);
-                    tdepth[i] = std::max(tdepth[i], lvl[h] + 1);
-                }
-                for (size_t h = 0; h < order.size() && ok; h++) {
-                    const int j = order[h];
-                    const bool leaf = t.feature[j] == -1;
-                    uint32_t bits; const float fv = leaf ? t.output[j] : t.threshold[j];
-                    memcpy(&bits, &fv, 4);
-                    if (leaf && std::isnan(fv)) { ok = false; break; }       // a leaf loops through `-inf <= value`: NaN outputs take the generic kernel
-                    // leaf: reads column 0 (-infinity in the staged tile) and its left child is itself
-                    const unsigned long long co = leaf ? 0ull : (unsigned long long)t.feature[j] * kEvalDocs * 4;
-                    const unsigned long long lo = leaf ? (unsigned long long)h * 8 : (unsigned long long)newid[t.left[j]] * 8;
-                    pk[i * m->maxn + h] = (unsigned long long)bits | (co << 32) | (lo << 48);
-                }
-                if (tdepth[i] > 250) ok = false;
-            }
-            if (ok) {
-                // the trees of a tile go to the walker wavefronts by descending depth (stable), eight each
-                const size_t ntl = (nt + kEvalTreeTile - 1) / kEvalTreeTile;
-                std::vector<unsigned char> pm(ntl * kEvalTreeTile, 255), gd(ntl * kEvalMetaDepths, 0);       // gd: per tile the walkers' steps, then per walker the steps at which its phases end
-                std::vector<int> idx;
-                for (size_t tl = 0; tl < ntl; tl++) {
-                    const size_t t0 = tl * kEvalTreeTile, tt = std::min<size_t>(kEvalTreeTile, nt - t0);
-                    idx.resize(tt);
-                    for (size_t q = 0; q < tt; q++) idx[q] = (int)q;
-                    std::stable_sort(idx.begin(), idx.end(), [&](int a2, int b2) { return tdepth[t0 + a2] > tdepth[t0 + b2]; });
-                    // The sorted trees are dealt ROUND the walkers (walker p: ranks p, p + 4, p + 8, ..; deepest first inside a walker as the phases need it): every
-                    // walker spans the tile's whole range of depths, so its chains drop out early and the four walkers reach the tile's barrier together.
-                    // With eight consecutive ranks each (rounds 4 - 5, RLHIP_EVAL_DEAL=0) walker 0 held the eight deepest trees -- little to drop, and the others
-                    // waited for it: 28.2 against 28.8 M docs/s (profiles/r06w_ab_infer_phased_walk.txt).
-                    if (m->knobs.deal && tt == (size_t)kEvalTreeTile) {
-                        std::vector<int> rr(tt);
-                        for (size_t q = 0; q < tt; q++) rr[(q % kEvalParts) * kEvalPer + q / kEvalParts] = idx[q];
-                        idx = rr;
-                    }
-                    for (size_t q = 0; q < tt; q++) {
-                        pm[tl * kEvalTreeTile + q] = (unsigned char)idx[q];
-                        unsigned char &g = gd[tl * kEvalMetaDepths + q / kEvalPer];
-                        g = std::max<unsigned char>(g, (unsigned char)std::max(tdepth[t0 + idx[q]], 1));      // (a single-leaf tree still stores its output: one step)
-                    }
-                    // a phase of n chains ends when the walker's (n' + 1)-th tree (n' = the next phase's chains) is done: that tree's depth.  A walker with fewer
-                    // trees: 0 (the phase is skipped).  RLHIP_EVAL_PHASED=0: every phase runs to the walker's full depth (one loop, rounds 4 - 5).
-                    const int next_ch[3] = {kEvalPhases >= 2 ? kEvalPh1 : kEvalPhLast, kEvalPhases >= 3 ? kEvalPh2 : kEvalPhLast, kEvalPhLast};
-                    for (int p = 0; p < kEvalParts; p++)
-                        for (int ph = 0; ph < kEvalPhases; ph++) {
-                            const size_t q = (size_t)p * kEvalPer + next_ch[ph];
-                            unsigned char &e = gd[tl * kEvalMetaDepths + kEvalParts + p * kEvalPhases + ph];
-                            e = !m->knobs.phased ? gd[tl * kEvalMetaDepths + p] : (q < tt ? (unsigned char)std::max(tdepth[t0 + idx[q]], 1) : 0);
-                        }
-                }
-                RL_HIP(m->pool.alloc(&m->d_perm, pm.size())); RL_HIP(m->pool.alloc(&m->d_gdepth, gd.size()));
-                RL_HIP(hipMemcpy(m->d_perm, pm.data(), pm.size(), hipMemcpyHostToDevice));
-                RL_HIP(hipMemcpy(m->d_gdepth, gd.data(), gd.size(), hipMemcpyHostToDevice));
-                RL_HIP(m->pool.alloc(&m->d_pack, en));
-                RL_HIP(hipMemcpy(m->d_pack, pk.data(), en * 8, hipMemcpyHostToDevice));
-                RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            }
-        }
-    }
+    RL_HIP(m->pool.upload(&m->ens.feat_idx, fi.data(), en)); RL_HIP(m->pool.upload(&m->ens.left, le.data(), en));
+    RL_HIP(m->pool.upload(&m->ens.right, ri.data(), en)); RL_HIP(m->pool.upload(&m->ens.thr, th.data(), en));
+    RL_HIP(m->pool.upload(&m->ens.out, ou.data(), en)); RL_HIP(m->pool.upload(&m->d_w, w.data(), w.size()));
+    return RL_OK;
+}
+
+// what eval_pack made of the model, for k_model_eval_tiled; a model it refuses keeps d_pack null and takes k_model_eval
+static int model_upload_pack(rl_model *m, const EvalPack &pk)
+{
+    m->maxcol = pk.maxcol;
+    if (!pk.ok) return RL_OK;
+    RL_HIP(m->pool.upload(&m->d_perm, pk.perm.data(), pk.perm.size()));
+    RL_HIP(m->pool.upload(&m->d_gdepth, pk.meta.data(), pk.meta.size()));
+    RL_HIP(m->pool.upload(&m->d_pack, pk.nodes.data(), pk.nodes.size()));
+    RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBudget));
+    RL_HIP(hipFuncSetAttribute((const void *)k_model_eval_tiled<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBudget));
+    return RL_OK;
+}
+
+}  // namespace rl
+
+extern "C" {
+
+int rl_model_from_text(const char *text, int32_t device, rl_model **out)
+{
+    if (!text || !out) return fail(RL_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::unique_ptr<rl_model> m(new rl_model());
+    std::string err;
+    if (!model_from_text(text, m->trees, err)) return fail(RL_ERR_INVALID, "Error in Emsemble(xmlRepresentation): " + err);
+    int rc = open_device(device, false);      // after the text is parsed; a model has never tested the architecture
+    if (rc) return rc;
+    m->device = device;
+    m->knobs.read();
+    std::map<int32_t, int> fids;                // the model's features, ascending, each once, and its largest tree
+    for (auto &t : m->trees) { m->maxn = std::max(m->maxn, t.n_nodes); for (int f : t.feature) if (f != -1) fids[f] = 0; }
+    for (auto &kv : fids) m->features.push_back(kv.first);
+    if ((rc = model_upload_ens(m.get()))) return rc;
+    if ((rc = model_upload_pack(m.get(), eval_pack(m->trees, m->maxn, m->knobs.deal, m->knobs.phased)))) return rc;
     *out = m.release();
     return RL_OK;
 }
@@ -386,7 +302,7 @@ static bool model_eval_tiled_ok(const rl_model *m, int32_t row_stride, int &cols
 {
     cols = (int)std::min<int64_t>(INT32_MAX, std::max<int64_t>(row_stride, (int64_t)m->maxcol + 1));     // (a feature id may be INT32_MAX)
     lds = eval_tiled_lds(cols, m->maxn);
-    return m->d_pack && lds <= (size_t)160 * 1024 && !m->knobs.generic;
+    return m->d_pack && lds <= kEvalLdsBudget && !m->knobs.generic;
 }
 
 static int model_eval_launch(rl_model *m, const float *dX, int64_t n_docs, int32_t row_stride, float *dO, hipStream_t s)
@@ -413,13 +329,12 @@ int rl_model_predict(rl_model *m, const float *X, int64_t n_docs, int32_t row_st
     if (!X || !out || n_docs < 0 || row_stride < 1) return fail(RL_ERR_INVALID, "bad argument");
     if (n_docs == 0) return RL_OK;
     RL_HIP(hipSetDevice(m->device));
+    DevPool pool;
     float *dX = nullptr, *dO = nullptr;
-    RL_HIP(hipMalloc((void **)&dX, (size_t)n_docs * row_stride * sizeof(float)));
-    RL_HIP(hipMalloc((void **)&dO, (size_t)n_docs * sizeof(float)));
-    RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
-    int rc = model_eval_launch(m, dX, n_docs, row_stride, dO, 0);
+    RL_HIP(pool.upload(&dX, X, (size_t)n_docs * row_stride));
+    RL_HIP(pool.alloc(&dO, (size_t)n_docs));
+    const int rc = model_eval_launch(m, dX, n_docs, row_stride, dO, 0);
     if (rc == RL_OK) { RL_HIP(hipDeviceSynchronize()); RL_HIP(hipMemcpy(out, dO, (size_t)n_docs * sizeof(float), hipMemcpyDeviceToHost)); }
-    (void)hipFree(dX); (void)hipFree(dO);
     return rc;
 }
 

@@ -1,6 +1,7 @@
 // rl_permimp.inc -- permutation feature importance of a tree model in one pass over a file: every (column, repeat) cell's scores and
 // per-list metric values without a permuted copy of the rows.  DESIGN.md 24.
-// Included at the end of rl_trainer.hip, after rl_stage.inc (it uses StageRank, stage_chunk, StageEvents and k_stage_eval).
+// Included at the end of rl_trainer.hip, after rl_stage.inc (it uses StageRank, StageEvents, k_stage_eval and stage_chunk: a chunk of cells is
+// at least one cell and at most gridDim.y batches' worth).
 //
 //   k_model_permuted_scores<B>   one lane per document, blockIdx.y over batches of B cells.  Cell g < n_columns * n_repeats is column
 //                                columns[g / n_repeats] under repeat g % n_repeats; one more cell, the last, is the base (it has no column).  A
@@ -171,15 +172,11 @@ struct PermWalk {
             }
         }
         float *dX = nullptr; int32_t *d_cols = nullptr, *d_donor = nullptr; uint8_t *d_uses = nullptr;
-        RL_HIP(pool.alloc(&dX, (size_t)n_docs * row_stride));
-        RL_HIP(pool.alloc(&d_cols, (size_t)n_columns));
-        RL_HIP(pool.alloc(&d_donor, (size_t)n_repeats * n_docs));
-        RL_HIP(pool.alloc(&d_uses, uses.size()));
+        RL_HIP(pool.upload(&dX, X, (size_t)n_docs * row_stride));
+        RL_HIP(pool.upload(&d_cols, columns, (size_t)n_columns));
+        RL_HIP(pool.upload(&d_donor, donor, (size_t)n_repeats * n_docs));
+        RL_HIP(pool.upload(&d_uses, uses.data(), uses.size()));
         RL_HIP(pool.alloc(&a.sc, (size_t)chunk * n_docs));
-        RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(d_cols, columns, (size_t)n_columns * sizeof(int32_t), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(d_donor, donor, (size_t)n_repeats * n_docs * sizeof(int32_t), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(d_uses, uses.data(), uses.size(), hipMemcpyHostToDevice));
         a.X = dX; a.columns = d_cols; a.donor = d_donor; d_uses0 = d_uses;
         return RL_OK;
     }
@@ -194,12 +191,6 @@ struct PermWalk {
         return a.nc;
     }
 };
-
-// the chunk size: at least one cell, at most gridDim.y batches' worth
-static int perm_chunk(int64_t scratch_bytes, int64_t bytes_per_cell, int32_t total)
-{
-    return stage_chunk(scratch_bytes, bytes_per_cell, total);
-}
 
 }  // namespace rl
 
@@ -216,7 +207,7 @@ int rl_model_predict_permuted(rl_model *m, const float *X, int64_t n_docs, int32
     DevPool pool;
     PermWalk walk;
     const int32_t total = n_columns * n_repeats + 1;
-    rc = walk.prepare(pool, m, X, n_docs, row_stride, columns, n_columns, donor, n_repeats, perm_chunk(0, n_docs * (int64_t)sizeof(float), total));
+    rc = walk.prepare(pool, m, X, n_docs, row_stride, columns, n_columns, donor, n_repeats, stage_chunk(0, n_docs * (int64_t)sizeof(float), total));
     if (rc) return rc;
     StageEvents ev;
     RL_HIP(ev.create());
@@ -261,7 +252,7 @@ int rl_model_eval_permuted(rl_model *m, const float *X, int64_t n_docs, int32_t 
     const int32_t total = n_columns * n_repeats + 1;
     DevPool pool;
     PermWalk walk;
-    rc = walk.prepare(pool, m, X, n_docs, row_stride, columns, n_columns, donor, n_repeats, perm_chunk(scratch_bytes, rank.bytes_per_row(n_docs), total));
+    rc = walk.prepare(pool, m, X, n_docs, row_stride, columns, n_columns, donor, n_repeats, stage_chunk(scratch_bytes, rank.bytes_per_row(n_docs), total));
     if (rc) return rc;
     rc = rank.upload(pool, walk.a.sc, walk.chunk, labels, n_docs, qoff, n_lists, ideal, disc, rel_doc_count, metric, k, err_max);
     if (rc) return rc;

@@ -1,6 +1,6 @@
 // rl_shap.inc -- exact path-dependent TreeSHAP contributions of a tree model in one pass over a file.  DESIGN.md 27.
-// Included at the end of rl_trainer.hip, after rl_contrib.inc (it uses rl_model's covers and node values, DevPool, StageEvents and
-// kStageScratchDefault).
+// Included at the end of rl_trainer.hip, after rl_contrib.inc (it uses rl_model's covers and node values, RowStream, and rl_contrib.inc's
+// SlotPass, SlotPlan and slot_stream: the slots of a call and its column passes go the way k_model_contribs' do).
 //
 //   k_model_shap      one lane per row, a block of 64, 128 or 256 rows; every row meets every leaf of every tree.  LDS holds the
 //                     accumulators [slot of the pass][D + 1] f64 as k_model_contribs has them, and the per-lane array w[wd][D] f64 of the
@@ -24,9 +24,7 @@ struct ShapArgs {
     const double *root;                                                // [nt] val[t][0]
     const float *w; const double *tb;                                  // the trees' weights; A, B, U, R [kShapT][kShapT] one behind the other
     int nt;
-    const float *X; int64_t n; int stride;
-    int32_t s0, ns, slots, bias;                                       // the pass: slots [s0, s0 + ns) of `slots` = C + 2; bias = C + 1
-    double *out;                                                       // [n][slots]
+    SlotPass p;
 };
 
 __global__ __launch_bounds__(kShapDocsMax) void k_model_shap(const ShapArgs a)
@@ -34,27 +32,28 @@ __global__ __launch_bounds__(kShapDocsMax) void k_model_shap(const ShapArgs a)
     extern __shared__ __align__(16) unsigned char shp_raw[];
     const int D = (int)blockDim.x, AS = D + 1, tid = threadIdx.x;
     double *sA = (double *)shp_raw;                                     // [ns][D + 1]
-    double *sW = sA + (size_t)a.ns * AS + tid;                         // [wd][D], this lane's column
+    double *sW = sA + (size_t)a.p.ns * AS + tid;                         // [wd][D], this lane's column
     const double *tA = a.tb, *tB = tA + kShapT * kShapT, *tU = tB + kShapT * kShapT, *tR = tU + kShapT * kShapT;
-    const int bias = a.bias - a.s0;                                    // in [0, ns) in the pass that holds it
+    const int s0 = a.p.s0, ns = a.p.ns;
+    const int bias = a.p.bias - s0;                                    // in [0, ns) in the pass that holds it
     const int64_t d0 = (int64_t)blockIdx.x * D;                        // one row tile per block: the grid is ceil(n / D), n < 2^31
-    const int nd = (int)min((int64_t)D, a.n - d0);
-    for (int s = 0; s < a.ns; s++) sA[s * AS + tid] = 0.0;
-    const float *row = a.X + (size_t)(d0 + (tid < nd ? tid : 0)) * a.stride;       // (a lane beyond the rows walks the first one's and stores nothing)
+    const int nd = (int)min((int64_t)D, a.p.n - d0);
+    for (int s = 0; s < ns; s++) sA[s * AS + tid] = 0.0;
+    const float *row = a.p.X + (size_t)(d0 + (tid < nd ? tid : 0)) * a.p.stride;       // (a lane beyond the rows walks the first one's and stores nothing)
     for (int t = 0; t < a.nt; t++) {
         const double W = (double)a.w[t];
-        if ((unsigned)bias < (unsigned)a.ns) sA[bias * AS + tid] = sA[bias * AS + tid] + W * a.root[t];
+        if ((unsigned)bias < (unsigned)ns) sA[bias * AS + tid] = sA[bias * AS + tid] + W * a.root[t];
         for (int lf = a.leaf0[t]; lf < a.leaf0[t + 1]; lf++) {
             const ShapLeaf leaf = a.leaves[lf];
             const ShapElem *el = a.elems + leaf.el0;
             const int d = leaf.d;
             bool mine = false;
-            for (int e = 0; e < d; e++) mine |= (unsigned)(el[e].slot - a.s0) < (unsigned)a.ns;
+            for (int e = 0; e < d; e++) mine |= (unsigned)(el[e].slot - s0) < (unsigned)ns;
             if (!mine) continue;                                       // (wave-uniform, and a single-leaf tree adds to bias only)
             unsigned om = 0u;                                          // bit e: the row's own decision is the path's at every split of element e
             for (int e = 0; e < d; e++) {
                 const int f = el[e].feat;
-                const float v = (f < a.stride) ? row[f] : 0.f;         // -missingZero  DenseDataPoint.java:22-25
+                const float v = (f < a.p.stride) ? row[f] : 0.f;         // -missingZero  DenseDataPoint.java:22-25
                 const ShapCond *c = a.conds + el[e].c0;
                 bool ok = true;
                 for (int k = 0; k < el[e].nc; k++) ok &= ((v <= c[k].thr) == (c[k].left != 0));     // Split.java:118: a NaN goes right
@@ -75,8 +74,8 @@ __global__ __launch_bounds__(kShapDocsMax) void k_model_shap(const ShapArgs a)
             const double *Ud = tU + d * kShapT, *Bd = tB + d * kShapT, *Rd = tR + d * kShapT;
             const double wd = sW[d * D];
             for (int e = 0; e < d; e++) {                              // unwind
-                const int s = el[e].slot - a.s0;
-                if ((unsigned)s >= (unsigned)a.ns) continue;
+                const int s = el[e].slot - s0;
+                if ((unsigned)s >= (unsigned)ns) continue;
                 const double z = el[e].z;
                 const bool on = (om >> e) & 1u;
                 const double o = on ? 1.0 : 0.0;
@@ -95,9 +94,9 @@ __global__ __launch_bounds__(kShapDocsMax) void k_model_shap(const ShapArgs a)
         }
     }
     __syncthreads();
-    for (int e = tid; e < nd * a.ns; e += D) {                         // transposed: adjacent lanes, adjacent slots of one document
-        const int dd = e / a.ns, s = e - dd * a.ns;
-        a.out[(size_t)(d0 + dd) * a.slots + a.s0 + s] = sA[s * AS + dd];
+    for (int e = tid; e < nd * ns; e += D) {                           // transposed: adjacent lanes, adjacent slots of one document
+        const int dd = e / ns, s = e - dd * ns;
+        a.p.out[(size_t)(d0 + dd) * a.p.slots + s0 + s] = sA[s * AS + dd];
     }
 }
 
@@ -128,73 +127,41 @@ int rl_model_predict_shap(rl_model *m, const float *X, int64_t n_docs, int32_t r
     if (m->cover.empty()) return fail(RL_ERR_STATE, w + "no rl_model_cover call has been made on this model");
     int32_t longest = 0;
     if (shap_check_paths(w, m->trees, &longest, err)) return fail(RL_ERR_UNSUPPORTED, err);
-    const std::vector<int32_t> cols = columns ? std::vector<int32_t>(columns, columns + n_columns) : m->features;
-    const int64_t C = (int64_t)cols.size(), slots = C + 2;
+    SlotPlan sp = slot_plan(m, columns, n_columns);
     const int wd = longest + 1;
-    int docs; int64_t per_pass;
-    if (!shap_plan(wd, slots, docs, per_pass)) return fail(RL_ERR_UNSUPPORTED, w + "the LDS has no room for one slot");
+    if (!shap_plan(wd, sp.slots, sp.docs, sp.per_pass)) return fail(RL_ERR_UNSUPPORTED, w + "the LDS has no room for one slot");
     g_sh_walk_ms = 0.0;
-    g_sh_passes = (int32_t)((slots + per_pass - 1) / per_pass);
+    g_sh_passes = sp.passes();
     if (n_docs == 0) return RL_OK;
     RL_HIP(hipSetDevice(m->device));
     const size_t T = m->trees.size();
-    std::vector<std::pair<int32_t, int32_t>> sorted((size_t)C);
-    for (int64_t c = 0; c < C; c++) sorted[(size_t)c] = {cols[(size_t)c], (int32_t)c};
-    std::sort(sorted.begin(), sorted.end());
     ShapPaths paths;
     std::vector<double> root(T);
     std::vector<int32_t> slot((size_t)m->maxn);
     for (size_t t = 0; t < T; t++) {
         const HostTree &h = m->trees[t];
-        contrib_node_slots(h, sorted, (int32_t)C, slot.data());
+        contrib_node_slots(h, sp.sorted, (int32_t)sp.C, slot.data());
         shap_tree_paths(h, m->cover.data() + t * m->maxn, slot.data(), paths);
         root[t] = m->value[t * m->maxn];
     }
     const std::vector<double> tb = shap_tables();
-    // the rows of a chunk and their 8 (C + 2) bytes of output stay within scratch_bytes; a chunk holds at least one row
-    const int64_t budget = scratch_bytes > 0 ? scratch_bytes : kStageScratchDefault;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_docs, budget / ((int64_t)row_stride * 4 + 8 * slots)));
-    DevPool pool;
+    RowStream rows;
     ShapArgs a;
     memset(&a, 0, sizeof(a));
     int32_t *d_leaf0 = nullptr; ShapLeaf *d_leaves = nullptr; ShapElem *d_elems = nullptr; ShapCond *d_conds = nullptr;
-    double *d_root = nullptr, *d_tb = nullptr; float *dX = nullptr;
-    RL_HIP(pool.alloc(&d_leaf0, paths.leaf0.size()));
-    RL_HIP(pool.alloc(&d_leaves, paths.leaves.size()));
-    RL_HIP(pool.alloc(&d_elems, std::max<size_t>(1, paths.elems.size())));
-    RL_HIP(pool.alloc(&d_conds, std::max<size_t>(1, paths.conds.size())));
-    RL_HIP(pool.alloc(&d_root, T));
-    RL_HIP(pool.alloc(&d_tb, tb.size()));
-    RL_HIP(pool.alloc(&dX, (size_t)chunk * row_stride));
-    RL_HIP(pool.alloc(&a.out, (size_t)chunk * slots));
-    RL_HIP(hipMemcpy(d_leaf0, paths.leaf0.data(), paths.leaf0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_leaves, paths.leaves.data(), paths.leaves.size() * sizeof(ShapLeaf), hipMemcpyHostToDevice));
-    if (!paths.elems.empty()) RL_HIP(hipMemcpy(d_elems, paths.elems.data(), paths.elems.size() * sizeof(ShapElem), hipMemcpyHostToDevice));
-    if (!paths.conds.empty()) RL_HIP(hipMemcpy(d_conds, paths.conds.data(), paths.conds.size() * sizeof(ShapCond), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_root, root.data(), T * sizeof(double), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_tb, tb.data(), tb.size() * sizeof(double), hipMemcpyHostToDevice));
+    double *d_root = nullptr, *d_tb = nullptr;
+    RL_HIP(rows.pool.upload(&d_leaf0, paths.leaf0.data(), paths.leaf0.size()));
+    RL_HIP(rows.pool.upload(&d_leaves, paths.leaves.data(), paths.leaves.size()));
+    RL_HIP(rows.pool.upload(&d_elems, paths.elems.data(), paths.elems.size()));
+    RL_HIP(rows.pool.upload(&d_conds, paths.conds.data(), paths.conds.size()));
+    RL_HIP(rows.pool.upload(&d_root, root.data(), T));
+    RL_HIP(rows.pool.upload(&d_tb, tb.data(), tb.size()));
     RL_HIP(hipFuncSetAttribute((const void *)k_model_shap, hipFuncAttributeMaxDynamicSharedMemorySize, kShapLds));
-    a.leaf0 = d_leaf0; a.leaves = d_leaves; a.elems = d_elems; a.conds = d_conds; a.root = d_root; a.w = m->d_w; a.tb = d_tb;
-    a.nt = (int)T; a.X = dX; a.stride = row_stride; a.slots = (int32_t)slots; a.bias = (int32_t)(C + 1);
-    StageEvents ev;
-    RL_HIP(ev.create());
-    for (int64_t r0 = 0; r0 < n_docs; r0 += chunk) {
-        const int64_t nr = std::min(chunk, n_docs - r0);
-        a.n = nr;
-        RL_HIP(hipMemcpy(dX, X + (size_t)r0 * row_stride, (size_t)nr * row_stride * sizeof(float), hipMemcpyHostToDevice));
-        RL_HIP(hipEventRecord(ev.e[0], 0));
-        for (int64_t s0 = 0; s0 < slots; s0 += per_pass) {
-            a.s0 = (int32_t)s0; a.ns = (int32_t)std::min(per_pass, slots - s0);
-            const size_t lds = ((size_t)a.ns * (docs + 1) + (size_t)wd * docs) * sizeof(double);
-            hipLaunchKernelGGL(k_model_shap, dim3((unsigned)((nr + docs - 1) / docs)), dim3(docs), lds, 0, a);
-            RL_HIP(hipGetLastError());
-        }
-        RL_HIP(hipEventRecord(ev.e[1], 0));
-        RL_HIP(hipMemcpy(out + (size_t)r0 * slots, a.out, (size_t)nr * slots * sizeof(double), hipMemcpyDeviceToHost));
-        float ms = 0.f;
-        RL_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        g_sh_walk_ms += (double)ms;
-    }
+    a.leaf0 = d_leaf0; a.leaves = d_leaves; a.elems = d_elems; a.conds = d_conds; a.root = d_root; a.w = m->d_w; a.tb = d_tb; a.nt = (int)T;
+    rc = slot_stream(k_model_shap, a, sp, X, n_docs, row_stride, scratch_bytes, out, rows,
+                     [&](int ns) { return ((size_t)ns * (sp.docs + 1) + (size_t)wd * sp.docs) * sizeof(double); });
+    g_sh_walk_ms = rows.ms;
+    if (rc) return rc;
     m->last_path = RL_MODEL_PATH_SHAP;
     return RL_OK;
 }

@@ -215,26 +215,16 @@ struct StageRank {
         float *d_lab = nullptr;
         double *d_ideal = nullptr, *d_disc = nullptr;
         int32_t *d_qoff = nullptr, *d_rd = nullptr;
-        RL_HIP(pool.alloc(&d_lab, (size_t)n_docs));
-        RL_HIP(pool.alloc(&d_qoff, (size_t)n_lists + 1));
-        RL_HIP(pool.alloc(&d_ideal, (size_t)n_lists));
-        RL_HIP(pool.alloc(&d_disc, disc.size()));
+        RL_HIP(pool.upload(&d_lab, labels, (size_t)n_docs));
+        RL_HIP(pool.upload(&d_qoff, qoff, (size_t)n_lists + 1));
+        RL_HIP(pool.upload(&d_ideal, ideal.data(), (size_t)n_lists));
+        RL_HIP(pool.upload(&d_disc, disc.data(), disc.size()));
         RL_HIP(pool.alloc(&a.out, (size_t)chunk * n_lists));
         RL_HIP(pool.alloc(&a.nan, (size_t)chunk * n_lists));
         if (!lists[3].empty()) { RL_HIP(pool.alloc(&a.gkey, (size_t)chunk * n_docs)); RL_HIP(pool.alloc(&a.glab, (size_t)chunk * n_docs)); }
-        RL_HIP(hipMemcpy(d_lab, labels, (size_t)n_docs * sizeof(float), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(d_qoff, qoff, ((size_t)n_lists + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(d_ideal, ideal.data(), (size_t)n_lists * sizeof(double), hipMemcpyHostToDevice));
-        RL_HIP(hipMemcpy(d_disc, disc.data(), disc.size() * sizeof(double), hipMemcpyHostToDevice));
-        if (rel_doc_count) {
-            RL_HIP(pool.alloc(&d_rd, (size_t)n_lists));
-            RL_HIP(hipMemcpy(d_rd, rel_doc_count, (size_t)n_lists * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        for (int c = 0; c < 4; c++) {
-            if (lists[c].empty()) continue;
-            RL_HIP(pool.alloc(&d_qlist[c], lists[c].size()));
-            RL_HIP(hipMemcpy(d_qlist[c], lists[c].data(), lists[c].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        if (rel_doc_count) RL_HIP(pool.upload(&d_rd, rel_doc_count, (size_t)n_lists));
+        for (int c = 0; c < 4; c++)
+            if (!lists[c].empty()) RL_HIP(pool.upload(&d_qlist[c], lists[c].data(), lists[c].size()));
         a.ev.labels = d_lab; a.ev.qoff = d_qoff; a.ev.ideal = d_ideal; a.ev.rd_ext = d_rd; a.ev.disc = d_disc;
         a.ev.metric = metric; a.ev.k = k; a.ev.err_max = err_max;
         a.sc = d_sc; a.n_docs = n_docs; a.n_lists = n_lists;
@@ -279,12 +269,10 @@ int rl_model_predict_stages(rl_model *m, const float *X, int64_t n_docs, int32_t
     DevPool pool;
     float *dX = nullptr, *d_carry = nullptr, *d_sc = nullptr; int32_t *d_stages = nullptr;
     const int chunk = stage_chunk(0, n_docs * (int64_t)sizeof(float), n_stages);
-    RL_HIP(pool.alloc(&dX, (size_t)n_docs * row_stride));
+    RL_HIP(pool.upload(&dX, X, (size_t)n_docs * row_stride));
     RL_HIP(pool.alloc(&d_carry, (size_t)n_docs));
     RL_HIP(pool.alloc(&d_sc, (size_t)chunk * n_docs));
-    RL_HIP(pool.alloc(&d_stages, (size_t)n_stages));
-    RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_stages, stages, (size_t)n_stages * sizeof(int32_t), hipMemcpyHostToDevice));
+    RL_HIP(pool.upload(&d_stages, stages, (size_t)n_stages));
     RL_HIP(hipMemset(d_carry, 0, (size_t)n_docs * sizeof(float)));
     StageEvents ev;
     RL_HIP(ev.create());
@@ -327,12 +315,10 @@ int rl_model_eval_stages(rl_model *m, const float *X, int64_t n_docs, int32_t ro
     DevPool pool;
     float *dX = nullptr, *d_carry = nullptr, *d_sc = nullptr;
     int32_t *d_stages = nullptr;
-    RL_HIP(pool.alloc(&dX, (size_t)n_docs * row_stride));
+    RL_HIP(pool.upload(&dX, X, (size_t)n_docs * row_stride));
     RL_HIP(pool.alloc(&d_carry, (size_t)n_docs));
     RL_HIP(pool.alloc(&d_sc, (size_t)chunk * n_docs));
-    RL_HIP(pool.alloc(&d_stages, (size_t)n_stages));
-    RL_HIP(hipMemcpy(dX, X, (size_t)n_docs * row_stride * sizeof(float), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(d_stages, stages, (size_t)n_stages * sizeof(int32_t), hipMemcpyHostToDevice));
+    RL_HIP(pool.upload(&d_stages, stages, (size_t)n_stages));
     RL_HIP(hipMemset(d_carry, 0, (size_t)n_docs * sizeof(float)));
     rc = rank.upload(pool, d_sc, chunk, labels, n_docs, qoff, n_lists, ideal, disc, rel_doc_count, metric, k, err_max);
     if (rc) return rc;
