@@ -1022,6 +1022,45 @@ int  rl_model_shap_limits(const rl_model *m, int32_t *max_path, int32_t *limit);
 int  rl_debug_shap_times(double *walk_ms);
 int  rl_debug_shap_passes(int32_t *passes);
 
+/* ---- partial dependence and ICE curves of a tree model, one pass over a file -------------------------------------------
+ * How the score moves as one feature moves.  columns[0 .. C-1] are feature ids, each >= 0, in any order, repeats allowed; grid_off
+ * [C + 1] is a CSR offset array, grid_off[0] == 0, strictly increasing; grid [grid_off[C]] holds f32 grid values.  CELL j, grid_off[c] <=
+ * j < grid_off[c+1], is column columns[c] set to grid[j].  The grid values of one column are strictly ascending under <: no NaN, no equal
+ * values, not -0.0 beside 0.0; +-Infinity are ordinary values.
+ * The ICE score of document i in cell j is Ensemble.eval's float chain (learning/tree/Ensemble.java:110-116, s = (float)((double)s +
+ * (double)out * (double)w), s_0 = 0.0f; v <= thr goes left, a NaN in another column goes right) on row i TAKEN AS PADDED WITH ZEROS TO ANY
+ * WIDTH, column columns[c] then set to grid[j]: a column at or beyond row_stride is substituted all the same (unlike the permuted cells
+ * above, where both sides read 0).  Bit for bit what the matrix materialised on the host, widened with zeros where needed, gives through
+ * rl_model_predict.  The BASE is the unsubstituted scores, out_base [n_docs] (may be NULL).
+ * Per cell two f64 sums in ONE FIXED ORDER that depends on nothing but n_docs: with RL_PARTIAL_SUM_BLOCK = 256 (part of this
+ * definition, not a kernel's block size), partial p is the serial chain over the documents [256 p, 256 p + 256) in document order,
+ * starting from +0.0; the total is the serial chain over the partials in order, starting from +0.0.  S1 sums (double)ice; S2 sums d * d,
+ * d = (double)ice - (double)base, every operation rounded, no FMA.  out_mean[j] = S1 / (double)n_docs is the partial-dependence value;
+ * out_shift2[j] = S2 / (double)n_docs is the mean squared move away from the document's own score.  NaN and Infinity propagate as IEEE
+ * gives them; there are no flags.  out_ice [cells][n_docs] f32 may be NULL: then nothing of that size crosses the bus.
+ * X, columns, grid_off, grid and the outputs are HOST pointers; rows and tables are uploaded once per call.  The cells are processed in
+ * chunks whose device scratch -- 4 bytes per document and cell, plus the base -- stays within scratch_bytes (0 = 256 MiB); a chunk
+ * holds at least one cell.  The result does not depend on the chunking.  Inside a chunk the kernel takes up to RL_PARTIAL_BATCH cells
+ * of one column per document at a time.
+ * RL_ERR_INVALID, the message naming the argument, all checked before the model so that a machine without a device reaches them: null
+ * X, columns, grid_off, grid, out_mean or out_shift2; n_docs < 1; row_stride < 1; n_columns < 1; a negative column; grid_off[0] != 0, an
+ * empty or descending grid_off; a grid value that is NaN or not greater than its predecessor ("grid[c][g] = ..."); scratch_bytes < 0.
+ * Then a null model and a model without trees.  RL_ERR_UNSUPPORTED: more than 2^31 documents or cells per call.
+ * rl_model_debug_path reports RL_MODEL_PATH_PARTIAL afterwards: one kernel serves packed and unpacked models. */
+#ifndef RL_PARTIAL_BATCH
+#define RL_PARTIAL_BATCH 16
+#endif
+#ifndef RL_PARTIAL_SUM_BLOCK
+#define RL_PARTIAL_SUM_BLOCK 256
+#endif
+enum { RL_MODEL_PATH_PARTIAL = 7 };
+int  rl_model_predict_partial(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *columns, int32_t n_columns,
+                              const int32_t *grid_off, const float *grid, int64_t scratch_bytes, float *out_base, double *out_mean,
+                              double *out_shift2, float *out_ice);
+/* debug (tools/partial_bench.py): ms between device events around the walking and around the reducing launches of this thread's last
+ * rl_model_predict_partial call, summed over its chunks */
+int  rl_debug_partial_times(double *walk_ms, double *reduce_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,7 @@ ABI_SYMBOLS = [
     "rl_model_cover", "rl_model_cover_rows", "rl_model_get_cover", "rl_model_predict_contribs", "rl_model_predict_leaf_sums", "rl_debug_contrib_times", "rl_debug_contrib_passes",
     "rl_model_predict_shap", "rl_model_shap_limits", "rl_debug_shap_times", "rl_debug_shap_passes",
     "rl_adopt_model_text",
+    "rl_model_predict_partial", "rl_debug_partial_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -317,6 +318,9 @@ def lib():
         L.rl_debug_shap_passes.argtypes = [C.POINTER(i32)]
     if hasattr(L, "rl_adopt_model_text"):     # (A/B builds of older sources cannot resume)
         L.rl_adopt_model_text.argtypes = [vp, C.c_char_p, i64, C.POINTER(i32)]
+    if hasattr(L, "rl_model_predict_partial"):  # (A/B builds of older sources have no partial dependence)
+        L.rl_model_predict_partial.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp]
+        L.rl_debug_partial_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -715,6 +719,9 @@ MODEL_PATH_PERMUTED = 3             # rl_model_predict_permuted / rl_model_eval_
 PERMUTED_BATCH = 16                 # RL_PERMUTED_BATCH (rlhip.h): cells k_model_permuted_scores takes per document at a time
 MODEL_PATH_COVER, MODEL_PATH_CONTRIBS = 4, 5      # rl_model_cover (k_model_cover) / rl_model_predict_contribs (k_model_contribs)
 MODEL_PATH_SHAP = 6                               # rl_model_predict_shap (k_model_shap)
+MODEL_PATH_PARTIAL = 7                            # rl_model_predict_partial (k_model_partial_scores, k_partial_reduce)
+PARTIAL_BATCH = 16                                # RL_PARTIAL_BATCH (rlhip.h): cells of one column k_model_partial_scores takes per document at a time
+PARTIAL_SUM_BLOCK = 256                           # RL_PARTIAL_SUM_BLOCK (rlhip.h): the documents of one partial sum, part of the definition
 
 
 class Model:
@@ -933,6 +940,34 @@ class Model:
         out = np.zeros(max(1, rows.shape[0]), np.float64)
         check(L.rl_model_predict_leaf_sums(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], out.ctypes.data))
         return out[:rows.shape[0]]
+
+    def predict_partial(self, rows, columns, grids, ice=False, scratch_bytes=0):
+        """rl_model_predict_partial: partial dependence and ICE curves.  grids: one array of f32 grid values per entry of
+        columns, each strictly ascending; cell j is the j-th value of the grids laid end to end.  Returns (f32 base scores [n_docs],
+        f64 mean [cells] -- the partial-dependence values --, f64 shift2 [cells], the mean squared move away from the base, and f32
+        ice [cells][n_docs] or None): cell j holds the scores of rows, padded with zeros to any width, with its column set to its grid
+        value.  The sums take the fixed order of include/rlhip.h; rows as in predict_rows."""
+        L = lib()
+        if not hasattr(L, "rl_model_predict_partial"):
+            raise RankLibError("rlhip: this librlhip.so has no partial dependence (rl_model_predict_partial)")
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        cols = np.ascontiguousarray(columns, dtype=np.int32)
+        gs = [np.ascontiguousarray(g, dtype=np.float32) for g in grids]
+        if rows.ndim != 2 or cols.ndim != 1 or len(gs) != cols.size or any(g.ndim != 1 for g in gs):
+            raise RankLibError("rlhip: partial dependence takes rows [n_docs][row_stride], columns [n_columns] and one 1-d grid per column")
+        off = np.zeros(cols.size + 1, np.int32)
+        np.cumsum([g.size for g in gs], out=off[1:])
+        grid = np.concatenate(gs + [np.zeros(1, np.float32)])      # (never an empty buffer: the library names what is wrong)
+        cells = int(off[-1])
+        base = np.zeros(max(1, rows.shape[0]), np.float32)
+        mean, shift2 = np.zeros(max(1, cells), np.float64), np.zeros(max(1, cells), np.float64)
+        out = np.zeros((cells, rows.shape[0]), np.float32) if ice else None
+        buf = rows if rows.size else np.zeros(1, np.float32)
+        cbuf = cols if cols.size else np.zeros(1, np.int32)
+        check(L.rl_model_predict_partial(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], cbuf.ctypes.data, int(cols.size), off.ctypes.data,
+                                         grid.ctypes.data, int(scratch_bytes), base.ctypes.data, mean.ctypes.data, shift2.ctypes.data,
+                                         out.ctypes.data if ice and out.size else None))
+        return base[:rows.shape[0]], mean[:cells], shift2[:cells], out
 
     def path(self):
         """MODEL_PATH_* of the last predict call: which kernel it took"""
@@ -1398,6 +1433,13 @@ def shap_passes():
     p = C.c_int32(0)
     check(lib().rl_debug_shap_passes(C.byref(p)))
     return p.value
+
+
+def partial_times():
+    """rl_debug_partial_times: (walk ms, reduce ms) of this thread's last predict_partial call, between device events"""
+    w, r = C.c_double(0.0), C.c_double(0.0)
+    check(lib().rl_debug_partial_times(C.byref(w), C.byref(r)))
+    return w.value, r.value
 
 
 def permuted_times():

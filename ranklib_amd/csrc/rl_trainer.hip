@@ -1014,6 +1014,7 @@ int rl_reset_timing(rl_trainer *t)
 #include "rl_model_eval.inc"
 #include "rl_stage.inc"      // the model after every requested number of trees: k_model_stage_scores walks, k_stage_eval ranks and scores
 #include "rl_permimp.inc"    // permutation importance: k_model_permuted_scores walks every (column, repeat) cell, k_stage_eval ranks and scores
+#include "rl_partial.inc"    // partial dependence and ICE curves: k_model_partial_scores walks every (column, grid value) cell, k_partial_reduce sums them in one fixed order
 #include "rl_model_rows.inc" // RowStream: a file's rows through a model kernel chunk by chunk, the host loop of the four entry points below
 #include "rl_contrib.inc"    // contributions of the features to a document's score: k_model_cover counts a background file, k_model_contribs walks the paths
 #include "rl_shap.inc"       // the same as exact TreeSHAP values: k_model_shap runs every row through the recurrence of every leaf

@@ -299,6 +299,36 @@ class Ranker:
                 values[c, r], _ = score_lists(scorer, perm, flat)
         return I.summarize(feats, base, values)
 
+    # rlhip: partial dependence and ICE curves: how the score moves as one feature moves
+    def _partialFeatures(self, features):
+        feats = sorted({int(f) for f in (self.features if features is None else features)})
+        if not feats:
+            raise RankLibError("rlhip: partialDependence has no feature to vary")
+        if feats[0] < 1:
+            raise RankLibError("rlhip: partialDependence takes feature ids >= 1 (got %d)" % feats[0])
+        return feats
+
+    def partialDependence(self, samples, features=None, grid=20, ice=False):
+        """partial.Partial of features (None: the model's own, ascending) on samples: per feature the grid partial.grid_for gives (grid:
+        a count of order statistics, or "thresholds" for a tree model) and per grid value the mean score of the documents with the
+        feature set to it, its difference from the base mean and the rms move of a document away from its own score; with ice the
+        per-document scores of every cell too.  This is the generic path, for every ranker: per cell a substituted copy of the
+        documents goes through evalLists, and the sums take the fixed order of include/rlhip.h (partial.fixed_order_sums)."""
+        from . import partial as P
+        feats = self._partialFeatures(features)
+        if not sum(rl.size() for rl in samples):
+            raise RankLibError("rlhip: partialDependence needs at least one document")
+        grids = [P.grid_for(self, samples, f, grid) for f in feats]
+        base, _ = self.evalLists(samples)
+        mean, shift2, curves = [], [], []
+        for f, g in zip(feats, grids):
+            sc = np.stack([self.evalLists(substituted_lists(samples, f, v))[0] for v in g])
+            sums = [P.fixed_order_sums(s, base) for s in sc]
+            mean.append(np.array([s1 for s1, _ in sums], np.float64) / float(len(base)))
+            shift2.append(np.array([s2 for _, s2 in sums], np.float64) / float(len(base)))
+            curves.append(sc)
+        return P.summarize(feats, grids, base, mean, shift2, curves if ice else None)
+
     def save(self, modelFile):        # :106-122
         d = modelFile.rsplit("/", 1)[0] if "/" in modelFile else None
         if d:
@@ -359,6 +389,21 @@ def permuted_lists(samples, dps, fid, donor):
             fv[fid] = src[fid] if fid < len(src) else np.nan
             pts.append(DataPoint.from_parsed(dp.label, dp.id, dp.description, fv))
             i += 1
+        out.append(RankList(pts))
+    return out
+
+
+def substituted_lists(samples, fid, value):
+    """samples with feature fid of every document set to value: new lists of new DataPoints, everything else shared.  A document too
+    short for the feature is widened with the unknown value (NaN, which reads as 0)."""
+    out = []
+    for rl in samples:
+        pts = []
+        for dp in rl.rl:
+            fv = np.full(max(len(dp.fVals), fid + 1), np.nan, np.float32)
+            fv[:len(dp.fVals)] = dp.fVals
+            fv[fid] = value
+            pts.append(DataPoint.from_parsed(dp.label, dp.id, dp.description, fv))
         out.append(RankList(pts))
     return out
 
@@ -638,6 +683,22 @@ class LambdaMART(Ranker):
                     values[c, r, dev[j]] = on_host(j, c, r)
             a = b
         return I.summarize(feats, base, values)
+
+    # --- partial dependence in one pass (rlhip) --------------------------------------------------
+    def partialDependence(self, samples, features=None, grid=20, ice=False):
+        """Ranker.partialDependence, bit for bit, without a substituted copy per cell: every (feature, grid value) cell and the base are
+        walked and summed by _native.Model.predict_partial.  A mean does not split over calls, so ONE call takes the whole file,
+        whatever EVAL_ROW_BYTES says, as permutationImportance does without within."""
+        from . import partial as P
+        feats = self._partialFeatures(features)
+        dps = [dp for rl in samples for dp in rl.rl]
+        if not dps:
+            raise RankLibError("rlhip: partialDependence needs at least one document")
+        grids = [P.grid_for(self, samples, f, grid) for f in feats]
+        base, mean, shift2, sc = self._model.predict_partial(self._rows(dps), feats, grids, ice=ice)
+        off = np.concatenate([[0], np.cumsum([len(g) for g in grids])]).astype(np.int64)
+        cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(feats))]      # noqa: E731
+        return P.summarize(feats, grids, base.astype(np.float64), cut(mean), cut(shift2), cut(sc.astype(np.float64)) if ice else None)
 
     # --- per-document feature contributions (rlhip, DESIGN.md 26) ----------------------------------------------
     def _rowChunks(self, samples):
