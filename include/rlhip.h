@@ -1022,6 +1022,47 @@ int  rl_model_shap_limits(const rl_model *m, int32_t *max_path, int32_t *limit);
 int  rl_debug_shap_times(double *walk_ms);
 int  rl_debug_shap_passes(int32_t *passes);
 
+/* ---- SHAP interaction values of a tree model, one pass over a file ------------------------------------------------------
+ * Which features work together: XGBoost's pred_interactions beside pred_contribs.  WALK, COVER, NODE VALUE, W = (double)w_t, the slots
+ * (columns[0 .. C-1], rest = C, bias = C + 1, columns == NULL), the row rule, the ELEMENTS of a leaf with z_e, o_e and their conditions,
+ * the tables A, B, U, R and the three steps start / extend / unwind are those of the two sections above; no FMA.
+ * MEANING: for tree t with player set N, the features it splits on, k = |N|, and features p != q,
+ *     PHI_pq(t) = sum over S in N without {p, q} of |S|! (k - |S| - 2)! / (2 (k - 1)!) * (v_{S+p+q} - v_{S+p} - v_{S+q} + v_S)
+ * with the v_S(0) of rl_model_predict_shap; the model's value is the sum over t of W PHI_pq(t), added into the cell [slot_p][slot_q].
+ * Pairs whose two features share a slot are not walked at all (without columns == NULL that can only happen in rest).
+ * RESULT: out [n_docs][C + 2][C + 2] f64.  Cell [i][j], i != j, both <= C, has i as the CONDITIONED slot and j as the ATTRIBUTED slot
+ * (XGBoost's layout).
+ * OFF-DIAGONAL CELL: one serial f64 chain from +0.0, in tree order, then leaf order (the pre-order of the model text), then conditioned
+ * element c in element order, then attributed element e in element order.  For a leaf with elements 1 .. d, d >= 2, and a conditioned
+ * element c with o_c != z_c: the reduced list is the leaf's elements without c, in order, of length d - 1; start and extend run on it
+ * with the tables at l = 1 .. d - 1; the unwind runs with the tables at d - 1 for every e != c of the reduced list with o_e != z_e and
+ * slot_e != slot_c and gives tot; then, each rounded and in this order,
+ *     x = (tot * (o_e - z_e)) * (double)out_leaf;   x = x * ((o_c - z_c) * 0.5);   x = x * W;   cell[slot_c][slot_e] = cell[slot_c][slot_e] + x
+ * The conditioned element is never divided by, so z_c == 0 with o_c == 1 is taken.  A leaf with one element, and a single-leaf tree,
+ * add nothing here.
+ * DIAGONAL CELL, i <= C: r = phi_i, the bits rl_model_predict_shap gives for that slot and row with the same columns; for j = 0 .. C
+ * ascending, j != i: r = r - out[i][j]; out[i][i] = r.
+ * BIAS: out[C+1][C+1] is the bits of the SHAP bias slot; every other cell of row C + 1 and column C + 1 is +0.0.  A requested id the
+ * model never splits on has +0.0 in its whole row and column; under columns == NULL so has rest.
+ * PROPERTIES, not definitions: row i sums to phi_i and the matrix to rl_model_predict_leaf_sums' value up to f64 rounding; out[i][j]
+ * and out[j][i] are equal in exact arithmetic but are two f64 chains and may differ in their last bits: both are kept as computed,
+ * nothing is symmetrised (that would change what a restricted column list gives).
+ * The result does not depend on the grid, the block width, the chunking -- per row the row itself, 8 (C + 2)^2 bytes of result and
+ * 8 (C + 2) bytes of SHAP values stay within scratch_bytes (0 = 256 MiB), a chunk holds at least one row -- or the number of column
+ * passes (rl_debug_interact_passes).
+ * RL_ERR_INVALID: the cases of rl_model_predict_contribs, the message naming this entry point.  RL_ERR_STATE: before any
+ * rl_model_cover.  RL_ERR_UNSUPPORTED, before the device is touched: more than 2^31 rows per call; a path of more than 32 distinct
+ * features (rl_model_shap_limits); more than 65 535 conditioned slots (C + 1).  n_docs == 0 is legal and launches nothing.
+ * rl_model_debug_path reports RL_MODEL_PATH_INTERACT afterwards. */
+int  rl_model_predict_interactions(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *columns,
+                                   int32_t n_columns, int64_t scratch_bytes, double *out);
+enum { RL_MODEL_PATH_INTERACT = 8 };
+/* debug (tools/interact_bench.py): ms between device events around the k_model_interact and k_interact_finish launches, and around the
+ * k_model_shap launches, of this thread's last rl_model_predict_interactions call, summed over the chunks; and the column passes of
+ * k_model_interact in that call */
+int  rl_debug_interact_times(double *walk_ms, double *shap_ms);
+int  rl_debug_interact_passes(int32_t *passes);
+
 /* ---- partial dependence and ICE curves of a tree model, one pass over a file -------------------------------------------
  * How the score moves as one feature moves.  columns[0 .. C-1] are feature ids, each >= 0, in any order, repeats allowed; grid_off
  * [C + 1] is a CSR offset array, grid_off[0] == 0, strictly increasing; grid [grid_off[C]] holds f32 grid values.  CELL j, grid_off[c] <=

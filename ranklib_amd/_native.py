@@ -150,6 +150,7 @@ ABI_SYMBOLS = [
     "rl_model_predict_shap", "rl_model_shap_limits", "rl_debug_shap_times", "rl_debug_shap_passes",
     "rl_adopt_model_text",
     "rl_model_predict_partial", "rl_debug_partial_times",
+    "rl_model_predict_interactions", "rl_debug_interact_times", "rl_debug_interact_passes",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -321,6 +322,10 @@ def lib():
     if hasattr(L, "rl_model_predict_partial"):  # (A/B builds of older sources have no partial dependence)
         L.rl_model_predict_partial.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp]
         L.rl_debug_partial_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_predict_interactions"):  # (A/B builds of older sources have no interaction values)
+        L.rl_model_predict_interactions.argtypes = [vp, vp, i64, i32, vp, i32, i64, vp]
+        L.rl_debug_interact_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.rl_debug_interact_passes.argtypes = [C.POINTER(i32)]
     _lib = L
     return L
 
@@ -720,6 +725,7 @@ PERMUTED_BATCH = 16                 # RL_PERMUTED_BATCH (rlhip.h): cells k_model
 MODEL_PATH_COVER, MODEL_PATH_CONTRIBS = 4, 5      # rl_model_cover (k_model_cover) / rl_model_predict_contribs (k_model_contribs)
 MODEL_PATH_SHAP = 6                               # rl_model_predict_shap (k_model_shap)
 MODEL_PATH_PARTIAL = 7                            # rl_model_predict_partial (k_model_partial_scores, k_partial_reduce)
+MODEL_PATH_INTERACT = 8                           # rl_model_predict_interactions (k_model_shap, k_model_interact, k_interact_finish)
 PARTIAL_BATCH = 16                                # RL_PARTIAL_BATCH (rlhip.h): cells of one column k_model_partial_scores takes per document at a time
 PARTIAL_SUM_BLOCK = 256                           # RL_PARTIAL_SUM_BLOCK (rlhip.h): the documents of one partial sum, part of the definition
 
@@ -916,7 +922,16 @@ class Model:
         check(lib().rl_model_shap_limits(self.h, C.byref(d), C.byref(p)))
         return d.value, p.value
 
-    def _predict_slots(self, entry, rows, columns, scratch_bytes):
+    def predict_interactions(self, rows, columns=None, scratch_bytes=0):
+        """rl_model_predict_interactions: (float64 [n_docs][C + 2][C + 2], the C column ids) -- SHAP interaction values.
+        Cell [i][j], i != j, is what features ids[i] and ids[j] do together that neither does alone, i the conditioned and j the
+        attributed slot; the diagonal is the SHAP value of predict_shap less the row's other cells, so row i sums to it; [C + 1][C + 1]
+        is the bias, the rest of its row and column +0.0.  About the mean element count of a leaf times predict_shap's work."""
+        if not hasattr(lib(), "rl_model_predict_interactions"):
+            raise RankLibError("rlhip: this librlhip.so has no interaction values (rl_model_predict_interactions)")
+        return self._predict_slots("rl_model_predict_interactions", rows, columns, scratch_bytes, square=True)
+
+    def _predict_slots(self, entry, rows, columns, scratch_bytes, square=False):
         L, rows, buf = self._contrib_rows(rows)
         if columns is None:
             ids, cols, nc = [int(f) for f in self.features()], None, 0
@@ -927,7 +942,7 @@ class Model:
             ids, nc = [int(c) for c in cols], int(cols.size)
             if not nc:
                 cols = np.zeros(1, np.int32)          # (an empty list is refused by the library, by name: it must not arrive as NULL)
-        out = np.zeros((rows.shape[0], len(ids) + 2), np.float64)
+        out = np.zeros((rows.shape[0],) + (len(ids) + 2,) * (2 if square else 1), np.float64)
         obuf = out if out.size else np.zeros(1, np.float64)
         check(getattr(L, entry)(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], None if cols is None else cols.ctypes.data, nc,
                                 int(scratch_bytes), obuf.ctypes.data))
@@ -1432,6 +1447,20 @@ def shap_passes():
     """rl_debug_shap_passes: the column passes of this thread's last predict_shap call"""
     p = C.c_int32(0)
     check(lib().rl_debug_shap_passes(C.byref(p)))
+    return p.value
+
+
+def interact_times():
+    """rl_debug_interact_times: (walk ms, shap ms) of this thread's last predict_interactions call, between device events"""
+    w, s = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_interact_times(C.byref(w), C.byref(s)))
+    return w.value, s.value
+
+
+def interact_passes():
+    """rl_debug_interact_passes: the column passes k_model_interact took in this thread's last predict_interactions call"""
+    p = C.c_int32(0)
+    check(lib().rl_debug_interact_passes(C.byref(p)))
     return p.value
 
 

@@ -12,6 +12,13 @@ rounding of Ensemble.eval's chain -- not its bits.
   -exact                 exact Shapley values (path-dependent TreeSHAP, XGBoost's pred_contribs without approx_contribs)
                          in place of Saabas' path attribution: the same files and the same local-accuracy line, from about two orders
                          of magnitude more work on the device
+  -interactions tsv      SHAP interaction values (XGBoost's pred_interactions) summed over the file; implies -exact, and
+                         -out / -summary still work beside it.  One line per unordered pair i < j of the reported features:
+                         fi <TAB> fj <TAB> mean |out[i][j] + out[j][i]| <TAB> mean (out[i][j] + out[j][i]), and one line
+                         fi <TAB> fi <TAB> mean |out[i][i]| <TAB> mean out[i][i] per feature, sorted by the first number descending, then
+                         by the ids (pairs with `rest` are printed, not written).  Every sum over the documents is one serial f64 chain
+                         in file order, carried from chunk to chunk, so it does not depend on the chunking; each is divided once.
+                         Per-document matrices: LambdaMART.interactions.
   -norm, -missingZero, -device   as in ranklib_amd.evaluator: the files are prepared by the code its -load -test uses
   -out tsv               one line per document: qid <TAB> index in its list <TAB> the model's score (Float.toString) and then
                          fid:value ... rest:value bias:value, the values as Double.toString
@@ -46,6 +53,37 @@ def summary_lines(ids, matrix):
     return ["%d\t%s\t%s" % (f, java_double_str(a), java_double_str(m)) for f, a, m in rows]
 
 
+def chain_sums(carry, values):
+    """carry [cells] + the serial f64 chain over values [docs][cells] in document order: cumsum is a serial chain (partial.fixed_order_sums'
+    device), and its first element is the carry, so a file summed chunk after chunk gives the bits of one chain over the file"""
+    with np.errstate(all="ignore"):
+        return np.cumsum(np.concatenate([np.asarray(carry, np.float64)[None], np.asarray(values, np.float64)]), axis=0)[-1]
+
+
+def pair_values(matrix):
+    """[docs][C + 1][C + 1] of interaction values [docs][C + 2][C + 2]: cell [i][j], i != j, holds out[i][j] + out[j][i] (one rounded
+    sum; the two orders give the same bits), cell [i][i] holds out[i][i]; the bias row and column are left out"""
+    m = np.asarray(matrix, np.float64)[:, :-1, :-1]
+    with np.errstate(all="ignore"):
+        v = m + m.transpose(0, 2, 1)
+    k = np.arange(m.shape[1])
+    v[:, k, k] = m[:, k, k]
+    return v
+
+
+def pair_lines(ids, abs_sums, sums, n_docs):
+    """(the -interactions lines, the lines of the pairs with rest): abs_sums and sums [C + 1][C + 1] are the chains of |pair_values| and
+    pair_values over n_docs documents"""
+    from .learning import java_double_str
+    C = len(ids)
+    names = [int(f) for f in ids] + ["rest"]
+    rows = [(float(abs_sums[i, j]) / n_docs, float(sums[i, j]) / n_docs, i, j) for i in range(C + 1) for j in range(i, C + 1)]
+    keep = sorted((r for r in rows if r[3] < C), key=lambda r: (-r[0], names[r[2]], names[r[3]]))
+    rest = sorted((r for r in rows if r[3] == C), key=lambda r: (-r[0], r[2]))
+    fmt = lambda r: "%s\t%s\t%s\t%s" % (names[r[2]], names[r[3]], java_double_str(r[0]), java_double_str(r[1]))      # noqa: E731
+    return [fmt(r) for r in keep], [fmt(r) for r in rest]
+
+
 def main(argv=None):
     from .evaluator import Evaluator
     from .features import FeatureManager
@@ -54,10 +92,10 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
         print("Usage: -load model -background file [-background file ...] -test file [-feature file] [-norm sum|zscore|linear] [-missingZero] "
-              "[-device d] [-out tsv] [-summary tsv] [-exact]")
+              "[-device d] [-out tsv] [-summary tsv] [-exact] [-interactions tsv]")
         return 0
     models, backgrounds, testFiles = [], [], []
-    featureFile, outFile, summaryFile = "", "", ""
+    featureFile, outFile, summaryFile, pairFile = "", "", "", ""
     exact = False
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
@@ -79,6 +117,9 @@ def main(argv=None):
         elif a == "-out": outFile = nxt()
         elif a == "-summary": summaryFile = nxt()
         elif a == "-exact": exact = True
+        elif a == "-interactions":
+            pairFile = nxt()
+            exact = True
         elif a == "-missingzero": DataPoint.missingZero = True
         elif a == "-norm":
             Evaluator.nml = normalizer.create(nxt())
@@ -105,8 +146,27 @@ def main(argv=None):
     ids = [int(f) for f in ranker._model.features()] if cols is None else cols
     parts, scores, worst = [], [], 0.0
     predict = ranker._model.predict_shap if exact else ranker._model.predict_contribs
+    S = len(ids) + 2
+    pair_abs, pair_sum = np.zeros((S - 1, S - 1)), np.zeros((S - 1, S - 1))
+    gap_row = gap_sym = gap_all = 0.0
     for rows in ranker._rowChunks(test):                    # whole lists, the rows of a chunk under EVAL_ROW_BYTES
         part = predict(rows, cols)[0]
+        step = max(1, ranker.EVAL_ROW_BYTES // (8 * S * S))  # a chunk's matrices stay under EVAL_ROW_BYTES, as in LambdaMART.interactions
+        for a0 in range(0, len(rows) if pairFile else 0, step):
+            sub = rows[a0:a0 + step]
+            inter = ranker._model.predict_interactions(sub, cols)[0]
+            vals = pair_values(inter)
+            pair_abs, pair_sum = chain_sums(pair_abs, np.abs(vals)), chain_sums(pair_sum, vals)
+            with np.errstate(all="ignore"):
+                rs = np.zeros(inter.shape[:2], np.float64)
+                for c in range(S):                          # cell after cell: a serial f64 sum per document and row of its matrix
+                    rs = rs + inter[:, :, c]
+                cs = np.zeros(len(sub), np.float64)
+                for c in range(S):
+                    cs = cs + rs[:, c]
+                gaps = [np.abs(rs - part[a0:a0 + len(sub)]), np.abs(inter - inter.transpose(0, 2, 1)), np.abs(cs - ranker._model.leaf_sums(sub))]
+            gaps = [float(g[np.isfinite(g)].max()) if np.isfinite(g).any() else 0.0 for g in gaps]
+            gap_row, gap_sym, gap_all = max(gap_row, gaps[0]), max(gap_sym, gaps[1]), max(gap_all, gaps[2])
         parts.append(part)
         scores.append(ranker._model.predict_rows(rows))
         with np.errstate(all="ignore"):
@@ -146,6 +206,17 @@ def main(argv=None):
         with open(summaryFile, "w", encoding="ascii") as out:
             out.write("".join(ln + "\n" for ln in lines))
         logger.info("Summary saved to: %s", summaryFile)
+    if pairFile:
+        kept, rest = pair_lines(ids, pair_abs, pair_sum, n_docs) if n_docs else ([], [])
+        logger.info("feature\tfeature\tmean |interaction|\tmean interaction")
+        for ln in kept + rest:
+            logger.info(ln)
+        logger.info("Largest |sum of a row of interaction values - its exact contribution|: %s", java_double_str(gap_row))
+        logger.info("Largest |out[i][j] - out[j][i]|: %s", java_double_str(gap_sym))
+        logger.info("Largest |sum of interaction values - f64 sum of weighted leaf outputs|: %s", java_double_str(gap_all))
+        with open(pairFile, "w", encoding="ascii") as out:
+            out.write("".join(ln + "\n" for ln in kept))
+        logger.info("Interaction values saved to: %s", pairFile)
     return 0
 
 

@@ -1,5 +1,5 @@
 // rl_model_rows.inc -- how the rows of a file stream through a model kernel: the one host loop of rl_model_cover, rl_model_predict_contribs,
-// rl_model_predict_shap and rl_model_predict_leaf_sums.  DESIGN.md 28.
+// rl_model_predict_shap, rl_model_predict_interactions and rl_model_predict_leaf_sums.  DESIGN.md 28.
 // Included at the end of rl_trainer.hip, after rl_permimp.inc and before rl_contrib.inc (it uses DevPool, StageEvents and kStageScratchDefault).
 // The staged and the permuted walks (StageWalk, PermWalk) keep all rows on the device and chunk over stages and cells: they are not its business.
 namespace rl {

@@ -100,6 +100,34 @@ __global__ __launch_bounds__(kShapDocsMax) void k_model_shap(const ShapArgs a)
     }
 }
 
+// The tables of a call on the device, in `pool`: the path tables of every tree under the slots of sp and the model's covers (left in
+// `paths` for the caller), the root values and the factor tables; `a` is ready but for its SlotPass.  Shared with rl_interact.inc.
+static int shap_upload(const rl_model *m, const SlotPlan &sp, DevPool &pool, ShapPaths &paths, ShapArgs &a)
+{
+    const size_t T = m->trees.size();
+    std::vector<double> root(T);
+    std::vector<int32_t> slot((size_t)m->maxn);
+    for (size_t t = 0; t < T; t++) {
+        const HostTree &h = m->trees[t];
+        contrib_node_slots(h, sp.sorted, (int32_t)sp.C, slot.data());
+        shap_tree_paths(h, m->cover.data() + t * m->maxn, slot.data(), paths);
+        root[t] = m->value[t * m->maxn];
+    }
+    const std::vector<double> tb = shap_tables();
+    memset(&a, 0, sizeof(a));
+    int32_t *d_leaf0 = nullptr; ShapLeaf *d_leaves = nullptr; ShapElem *d_elems = nullptr; ShapCond *d_conds = nullptr;
+    double *d_root = nullptr, *d_tb = nullptr;
+    RL_HIP(pool.upload(&d_leaf0, paths.leaf0.data(), paths.leaf0.size()));
+    RL_HIP(pool.upload(&d_leaves, paths.leaves.data(), paths.leaves.size()));
+    RL_HIP(pool.upload(&d_elems, paths.elems.data(), paths.elems.size()));
+    RL_HIP(pool.upload(&d_conds, paths.conds.data(), paths.conds.size()));
+    RL_HIP(pool.upload(&d_root, root.data(), T));
+    RL_HIP(pool.upload(&d_tb, tb.data(), tb.size()));
+    RL_HIP(hipFuncSetAttribute((const void *)k_model_shap, hipFuncAttributeMaxDynamicSharedMemorySize, kShapLds));
+    a.leaf0 = d_leaf0; a.leaves = d_leaves; a.elems = d_elems; a.conds = d_conds; a.root = d_root; a.w = m->d_w; a.tb = d_tb; a.nt = (int)T;
+    return RL_OK;
+}
+
 static thread_local double g_sh_walk_ms = 0.0;                         // the last call of this thread, device events
 static thread_local int32_t g_sh_passes = 0;
 
@@ -134,30 +162,10 @@ int rl_model_predict_shap(rl_model *m, const float *X, int64_t n_docs, int32_t r
     g_sh_passes = sp.passes();
     if (n_docs == 0) return RL_OK;
     RL_HIP(hipSetDevice(m->device));
-    const size_t T = m->trees.size();
-    ShapPaths paths;
-    std::vector<double> root(T);
-    std::vector<int32_t> slot((size_t)m->maxn);
-    for (size_t t = 0; t < T; t++) {
-        const HostTree &h = m->trees[t];
-        contrib_node_slots(h, sp.sorted, (int32_t)sp.C, slot.data());
-        shap_tree_paths(h, m->cover.data() + t * m->maxn, slot.data(), paths);
-        root[t] = m->value[t * m->maxn];
-    }
-    const std::vector<double> tb = shap_tables();
     RowStream rows;
     ShapArgs a;
-    memset(&a, 0, sizeof(a));
-    int32_t *d_leaf0 = nullptr; ShapLeaf *d_leaves = nullptr; ShapElem *d_elems = nullptr; ShapCond *d_conds = nullptr;
-    double *d_root = nullptr, *d_tb = nullptr;
-    RL_HIP(rows.pool.upload(&d_leaf0, paths.leaf0.data(), paths.leaf0.size()));
-    RL_HIP(rows.pool.upload(&d_leaves, paths.leaves.data(), paths.leaves.size()));
-    RL_HIP(rows.pool.upload(&d_elems, paths.elems.data(), paths.elems.size()));
-    RL_HIP(rows.pool.upload(&d_conds, paths.conds.data(), paths.conds.size()));
-    RL_HIP(rows.pool.upload(&d_root, root.data(), T));
-    RL_HIP(rows.pool.upload(&d_tb, tb.data(), tb.size()));
-    RL_HIP(hipFuncSetAttribute((const void *)k_model_shap, hipFuncAttributeMaxDynamicSharedMemorySize, kShapLds));
-    a.leaf0 = d_leaf0; a.leaves = d_leaves; a.elems = d_elems; a.conds = d_conds; a.root = d_root; a.w = m->d_w; a.tb = d_tb; a.nt = (int)T;
+    ShapPaths paths;
+    if ((rc = shap_upload(m, sp, rows.pool, paths, a))) return rc;
     rc = slot_stream(k_model_shap, a, sp, X, n_docs, row_stride, scratch_bytes, out, rows,
                      [&](int ns) { return ((size_t)ns * (sp.docs + 1) + (size_t)wd * sp.docs) * sizeof(double); });
     g_sh_walk_ms = rows.ms;

@@ -1018,4 +1018,5 @@ int rl_reset_timing(rl_trainer *t)
 #include "rl_model_rows.inc" // RowStream: a file's rows through a model kernel chunk by chunk, the host loop of the four entry points below
 #include "rl_contrib.inc"    // contributions of the features to a document's score: k_model_cover counts a background file, k_model_contribs walks the paths
 #include "rl_shap.inc"       // the same as exact TreeSHAP values: k_model_shap runs every row through the recurrence of every leaf
+#include "rl_interact.inc"   // SHAP interaction values: k_model_interact runs that recurrence once per conditioned element, k_interact_finish makes the diagonal
 #include "rl_resume.inc"     // resume: rl_adopt_model_text replays a saved model's trees as this trainer's first rounds (k_replay_scores)

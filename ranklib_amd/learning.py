@@ -269,6 +269,9 @@ class Ranker:
     def contributions(self, samples, background, features=None, exact=False):
         self.countCover(background)
 
+    def interactions(self, samples, background, features=None):
+        self.countCover(background)
+
     # rlhip: permutation feature importance: what a feature is worth under the scorer on these lists
     def _importanceFeatures(self, features):
         feats = sorted({int(f) for f in (self.features if features is None else features)})
@@ -742,6 +745,30 @@ class LambdaMART(Ranker):
         parts = [predict(rows, cols)[0] for rows in self._rowChunks(samples)]
         if not parts:                                        # no document: the library still checks the columns and that covers exist
             parts = [predict(np.zeros((0, 1), np.float32), cols)[0]]
+        return np.concatenate(parts), ids
+
+    def _interactionChunks(self, samples, n_slots):
+        """the row chunks of _rowChunks cut again so that a chunk's result [rows][n_slots][n_slots] f64 stays under EVAL_ROW_BYTES
+        (a chunk holds at least one row)"""
+        step = max(1, Ranker.EVAL_ROW_BYTES // (8 * n_slots * n_slots))
+        for rows in self._rowChunks(samples):
+            for a in range(0, len(rows), step):
+                yield rows[a:a + step]
+
+    def interactions(self, samples, background, features=None):
+        """Which features work together: (f64 [documents of samples in file order][C + 2][C + 2], the C feature ids) -- SHAP
+        interaction values, XGBoost's pred_interactions (_native.Model.predict_interactions), over the covers of
+        `background` (None: the counts of earlier countCover calls).  features None: every feature the model splits on.  Cell [i][j],
+        i != j, is the joint effect of features ids[i] and ids[j], [i][i] what is left of feature i's exact contribution
+        (contributions(exact=True)) when its row's other cells are taken away, row and column C what the features not asked for do,
+        [C + 1][C + 1] the bias.  The rows go in chunks whose result stays under EVAL_ROW_BYTES."""
+        if background is not None:
+            self.countCover(background)
+        cols = None if features is None else [int(f) for f in features]
+        ids = [int(f) for f in self._model.features()] if cols is None else cols
+        parts = [self._model.predict_interactions(rows, cols)[0] for rows in self._interactionChunks(samples, len(ids) + 2)]
+        if not parts:                                        # no document: the library still checks the columns and that covers exist
+            parts = [self._model.predict_interactions(np.zeros((0, 1), np.float32), cols)[0]]
         return np.concatenate(parts), ids
 
     def truncated(self, t):
