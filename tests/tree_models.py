@@ -233,7 +233,9 @@ def probe_pool(trees):
 
 def probe_rows(rng, trees, n, width, special=0.1):
     """n rows of `width` columns drawn from probe_pool (one cell in ten from SPECIAL_VALUES); the first rows hold one pool value in every
-    column, so every value meets every threshold.  Column 0 is 0, as in a DataPoint."""
+    column, so every value meets every threshold.  Column 0 is 0, as in a DataPoint.  With the cases' 200 rows this prefix
+    (len(pool) + 12 rows) is nearly or wholly the whole row set -- 200 of 200 on count_37, 180 on feature_0: right for scoring, next to
+    nothing for attribution.  tests/walk_cases.py builds the row sets of the other walks' tests from the prefix and the mixed part."""
     pool = probe_pool(trees)
     rows = pool[rng.integers(0, len(pool), (n, width))]
     sp = rng.random((n, width)) < special
