@@ -35,7 +35,6 @@ import sys
 
 import numpy as np
 
-from . import normalizer
 from ._native import RankLibError
 
 logger = logging.getLogger("ranklib_amd")
@@ -85,9 +84,9 @@ def pair_lines(ids, abs_sums, sums, n_docs):
 
 
 def main(argv=None):
-    from .evaluator import Evaluator
+    from .evaluator import ArgCursor, Evaluator, common_flag
     from .features import FeatureManager
-    from .learning import DataPoint, LambdaMART, RankerFactory, RankerType, java_double_str, java_float_str
+    from .learning import LambdaMART, RankerFactory, RankerType, java_double_str, java_float_str, result_steps
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
@@ -100,16 +99,9 @@ def main(argv=None):
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
     Evaluator.qrelFile = ""
-    i = 0
-    while i < len(args):                                    # flags are matched case-insensitively, as the evaluator matches them
-        a = args[i].lower()
-
-        def nxt():
-            nonlocal i
-            i += 1
-            if i >= len(args):
-                raise RankLibError("Missing value for " + args[i - 1])
-            return args[i]
+    cur = ArgCursor(args)
+    nxt = cur.nxt
+    for a in cur:
         if a == "-load": models.append(nxt())
         elif a == "-background": backgrounds.append(nxt())
         elif a == "-test": testFiles.append(nxt())
@@ -120,14 +112,8 @@ def main(argv=None):
         elif a == "-interactions":
             pairFile = nxt()
             exact = True
-        elif a == "-missingzero": DataPoint.missingZero = True
-        elif a == "-norm":
-            Evaluator.nml = normalizer.create(nxt())
-            Evaluator.normalize = True
-        elif a == "-device": LambdaMART.device = int(nxt())
-        else:
-            raise RankLibError("Unknown command-line parameter: " + args[i])
-        i += 1
+        elif not common_flag(a, nxt, reader_only=True):     # no -gmax, -qrel, -hr here, and -device is LambdaMART's alone
+            cur.unknown()
     if len(models) != 1:
         raise RankLibError("ranklib_amd.contribs takes exactly one -load model (got %d)" % len(models))
     if not backgrounds:
@@ -151,9 +137,8 @@ def main(argv=None):
     gap_row = gap_sym = gap_all = 0.0
     for rows in ranker._rowChunks(test):                    # whole lists, the rows of a chunk under EVAL_ROW_BYTES
         part = predict(rows, cols)[0]
-        step = max(1, ranker.EVAL_ROW_BYTES // (8 * S * S))  # a chunk's matrices stay under EVAL_ROW_BYTES, as in LambdaMART.interactions
-        for a0 in range(0, len(rows) if pairFile else 0, step):
-            sub = rows[a0:a0 + step]
+        for a0, b0 in result_steps(len(rows) if pairFile else 0, 8 * S * S):      # pieces whose matrices stay under EVAL_ROW_BYTES
+            sub = rows[a0:b0]
             inter = ranker._model.predict_interactions(sub, cols)[0]
             vals = pair_values(inter)
             pair_abs, pair_sum = chain_sums(pair_abs, np.abs(vals)), chain_sums(pair_sum, vals)

@@ -423,6 +423,48 @@ _RANK_REMOVED = ("This function has been removed.\nConsider using -score in addi
                  "and do the ranking yourself based on these scores.")       # :516-518
 
 
+class ArgCursor:
+    """A command line read from left to right, by every command line of the package: iterating gives each flag in lower case (flags are
+    matched case-insensitively, :230-372), nxt() the value that follows the flag in hand, and unknown() is the Java's refusal of it"""
+
+    def __init__(self, args):
+        self.args, self.i = args, 0
+
+    def __iter__(self):
+        while self.i < len(self.args):
+            yield self.args[self.i].lower()
+            self.i += 1
+
+    def nxt(self):
+        self.i += 1
+        if self.i >= len(self.args):
+            raise RankLibError("Missing value for " + self.args[self.i - 1])
+        return self.args[self.i]
+
+    def unknown(self):                # :369-371
+        raise RankLibError("Unknown command-line parameter: " + self.args[self.i])
+
+
+def common_flag(a, nxt, reader_only=False):
+    """The flags that the tools around a loaded model (stages, importance, partial, contribs) share with this command line, with its
+    meaning: True when a was one of them.  reader_only: the tool applies no metric and takes tree models alone (contribs), so it knows
+    the file reader's -missingZero and -norm, a -device that is LambdaMART's alone, and none of -gmax, -qrel, -hr."""
+    if a == "-missingzero": DataPoint.missingZero = True
+    elif a == "-norm":
+        Evaluator.nml = normalizer.create(nxt())
+        Evaluator.normalize = True
+    elif a == "-device":
+        LambdaMART.device = int(nxt())
+        if not reader_only:
+            CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = RankNet.device = LambdaMART.device
+    elif reader_only: return False
+    elif a == "-gmax": ERRScorer.MAX = math.pow(2.0, float(nxt()))
+    elif a == "-qrel": Evaluator.qrelFile = nxt()
+    elif a == "-hr": Evaluator.mustHaveRelDoc = True
+    else: return False
+    return True
+
+
 def main(argv=None):
     try:
         return _main(argv)
@@ -464,16 +506,9 @@ def _main(argv=None):
     foldCV, kcvModelDir, kcvModelFile = -1, "", ""
     epochs = netSeed = rnSeed = lamSeed = layers = nodes = lrValue = None
     lrGiven = False
-    i = 0
-    while i < len(args):                                    # :230-372 (flags are matched case-insensitively)
-        a = args[i].lower()
-
-        def nxt():
-            nonlocal i
-            i += 1
-            if i >= len(args):
-                raise RankLibError("Missing value for " + args[i - 1])
-            return args[i]
+    cur = ArgCursor(args)
+    nxt = cur.nxt
+    for a in cur:                                           # :230-372 (flags are matched case-insensitively)
         if a == "-train": trainFile = nxt()
         elif a == "-ranker": rankerType = int(nxt())
         elif a == "-feature": featureDescriptionFile = nxt()
@@ -549,8 +584,7 @@ def _main(argv=None):
         elif a == "-node": nodes = int(nxt())               # other run parses and ignores them (test:eval/EvaluatorTest.java:207-220 passes them to every ranker)
         elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = RankNet.device = int(nxt())
         else:
-            raise RankLibError("Unknown command-line parameter: " + args[i])     # :369-371 (incl. the documented -silent)
-        i += 1
+            cur.unknown()                                   # :369-371 (incl. the documented -silent)
     if not testMetric:
         testMetric = trainMetric                            # :379-381
     if resumeFile or LambdaMART.checkpointFile or everyGiven:

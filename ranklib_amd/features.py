@@ -352,16 +352,10 @@ def main(argv=None):                  # features/FeatureManager.java:37-169
     rankingFiles, outputDir, modelFileName = [], "", ""
     shuffle = doFeatureStats = False
     nFold, tvs, tts, seed = 0, np.float32(-1), np.float32(-1), None
-    i = 0
-    while i < len(args):                                 # :79-96
-        a = args[i].lower()
-
-        def nxt():
-            nonlocal i
-            i += 1
-            if i >= len(args):
-                raise RankLibError("Missing value for " + args[i - 1])
-            return args[i]
+    from .evaluator import ArgCursor                     # (the evaluator imports this module)
+    cur = ArgCursor(args)
+    nxt = cur.nxt
+    for a in cur:                                        # :79-96
         if a == "-input": rankingFiles.append(nxt())
         elif a == "-k": nFold = int(nxt())
         elif a == "-shuffle": shuffle = True
@@ -375,7 +369,6 @@ def main(argv=None):                  # features/FeatureManager.java:37-169
             doFeatureStats = True
             modelFileName = nxt()
         elif a == "-seed": seed = int(nxt())
-        i += 1
     if nFold > 0 and tts != -1:                          # :98-101
         logger.info("Error: Only one of k or tts should be specified.")
         return 0

@@ -31,7 +31,7 @@ import numpy as np
 
 from . import _native as N
 from ._native import RankLibError
-from .metric import TREE_TRAINABLE, ERRScorer
+from .metric import TREE_TRAINABLE, ERRScorer, held_judgments, id_keys, keep_ideals, metric_name
 
 logger = logging.getLogger("ranklib_amd")
 
@@ -163,11 +163,10 @@ def flatten(samples, features):
     X = np.zeros((n, F), np.float32)
     labels = np.zeros(n, np.float32)
     qoff = np.zeros(len(samples) + 1, np.int32)
-    keys, qkey = {}, np.zeros(len(samples), np.int32)
+    qkey = id_keys(rl.getID() for rl in samples)
     fa = np.asarray(features, np.int64)
     k = 0
     for q, rl in enumerate(samples):
-        qkey[q] = keys.setdefault(rl.getID(), len(keys))
         for dp in rl.rl:
             fv = dp.fVals
             if fa.size and (fa.min() <= 0 or fa.max() >= len(fv)):
@@ -179,6 +178,54 @@ def flatten(samples, features):
             k += 1
         qoff[q + 1] = k
     return X, labels, qoff, qkey
+
+
+def dense_rows(dps, need=None, checked=None):
+    """The documents dps as f32 rows for the scoring kernels: column f holds feature id f, an unknown cell (NaN) reads 0, and the rows are
+    as wide as the longest document and as id need asks.  Unless -missingZero is set a document too short for an id a model reads is
+    refused with DenseDataPoint.getFeatureValue's message, by the rule of the model's family.  The tree rankers (checked None) look at
+    need alone, the model's largest feature id, name it, and never refuse id 0: a model without features has need == 0.  The linear and
+    neural rankers (checked: their feature ids; need: the largest of them) look at every id in order, document by document, refuse
+    f <= 0 too and name the first id that fails."""
+    if need is None:
+        need = max([int(f) for f in checked] + [0])
+    width = max([need + 1] + [len(dp.fVals) for dp in dps])
+    rows = np.zeros((len(dps), width), np.float32)
+    for i, dp in enumerate(dps):
+        fv = dp.fVals
+        rows[i, :len(fv)] = np.where(np.isnan(fv), np.float32(0), fv)
+    if not DataPoint.missingZero:
+        for dp in dps:
+            n = len(dp.fVals)
+            for f in ([need] if checked is None else checked):
+                if f >= n or (f <= 0 and checked is not None):
+                    raise RankLibError("Error in DenseDataPoint::getFeatureValue(): requesting unspecified feature, fid=%d" % f)
+    return rows
+
+
+def list_chunks(samples, limit):
+    """(a, b) index pairs that cut samples into chunks of whole lists samples[a:b] whose f32 rows stay within limit bytes; None: one
+    chunk for the whole file.  The rows of a chunk are as wide as its widest list (getFeatureCount() + 1 columns, at least one), a chunk
+    always takes its first list, however large, and a further list joins unless that makes (docs + size) * width * 4 > limit: with
+    the callers' limit the test reads `> Ranker.EVAL_ROW_BYTES`, not `>=`, so rows that fill the limit exactly stay together."""
+    a = 0
+    while a < len(samples):
+        b, docs, width = a, 0, 1
+        while b < len(samples):
+            w = max(width, samples[b].getFeatureCount() + 1)
+            if limit is not None and b > a and (docs + samples[b].size()) * w * 4 > limit:
+                break
+            docs, width, b = docs + samples[b].size(), w, b + 1
+        yield a, b
+        a = b
+
+
+def result_steps(n_rows, bytes_per_row):
+    """(a, b) index pairs that cut n_rows rows into pieces whose results, bytes_per_row each, stay within Ranker.EVAL_ROW_BYTES; a piece
+    holds at least one row"""
+    step = max(1, Ranker.EVAL_ROW_BYTES // bytes_per_row)
+    for a in range(0, n_rows, step):
+        yield a, min(a + step, n_rows)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -236,17 +283,9 @@ class Ranker:
         qoff = np.zeros(len(samples) + 1, np.int64)
         np.cumsum([rl.size() for rl in samples], out=qoff[1:])
         out = np.zeros(int(qoff[-1]), np.float64)
-        a = 0
-        while a < len(samples):
-            b, docs, width = a, 0, 1
-            while b < len(samples):
-                w = max(width, samples[b].getFeatureCount() + 1)
-                if b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
-                    break
-                docs, width, b = docs + samples[b].size(), w, b + 1
-            if docs:
+        for a, b in list_chunks(samples, Ranker.EVAL_ROW_BYTES):
+            if qoff[b] > qoff[a]:
                 out[int(qoff[a]):int(qoff[b])] = self._evalDocs([dp for rl in samples[a:b] for dp in rl.rl])
-            a = b
         return out, qoff
 
     def _evalDocs(self, dps):
@@ -272,15 +311,16 @@ class Ranker:
     def interactions(self, samples, background, features=None):
         self.countCover(background)
 
-    # rlhip: permutation feature importance: what a feature is worth under the scorer on these lists
-    def _importanceFeatures(self, features):
+    def _askedFeatures(self, features, who, to_do):
+        """the feature ids a per-feature method works on, ascending and distinct (None: the model's own); who and to_do word the refusals"""
         feats = sorted({int(f) for f in (self.features if features is None else features)})
         if not feats:
-            raise RankLibError("rlhip: permutationImportance has no feature to measure")
+            raise RankLibError("rlhip: %s has no feature to %s" % (who, to_do))
         if feats[0] < 1:
-            raise RankLibError("rlhip: permutationImportance takes feature ids >= 1 (got %d)" % feats[0])
+            raise RankLibError("rlhip: %s takes feature ids >= 1 (got %d)" % (who, feats[0]))
         return feats
 
+    # rlhip: permutation feature importance (DESIGN.md 24): what a feature is worth under the scorer on these lists
     def permutationImportance(self, samples, scorer, features=None, repeats=5, seed=1, within=False):
         """importance.Importance of features (None: the model's own, ascending) on samples under scorer: per feature and repeat the
         documents receive that feature's value from the document importance.donor_maps names (a permutation of the whole file, or with
@@ -289,7 +329,7 @@ class Ranker:
         of the documents goes through evalLists and metric.score_lists."""
         from . import importance as I
         from .metric import score_lists
-        feats = self._importanceFeatures(features)
+        feats = self._askedFeatures(features, "permutationImportance", "measure")
         donors = I.donor_maps([rl.size() for rl in samples], repeats, seed, within)
         flat, _ = self.evalLists(samples)
         base, _ = score_lists(scorer, samples, flat)
@@ -303,14 +343,6 @@ class Ranker:
         return I.summarize(feats, base, values)
 
     # rlhip: partial dependence and ICE curves: how the score moves as one feature moves
-    def _partialFeatures(self, features):
-        feats = sorted({int(f) for f in (self.features if features is None else features)})
-        if not feats:
-            raise RankLibError("rlhip: partialDependence has no feature to vary")
-        if feats[0] < 1:
-            raise RankLibError("rlhip: partialDependence takes feature ids >= 1 (got %d)" % feats[0])
-        return feats
-
     def partialDependence(self, samples, features=None, grid=20, ice=False):
         """partial.Partial of features (None: the model's own, ascending) on samples: per feature the grid partial.grid_for gives (grid:
         a count of order statistics, or "thresholds" for a tree model) and per grid value the mean score of the documents with the
@@ -318,7 +350,7 @@ class Ranker:
         per-document scores of every cell too.  This is the generic path, for every ranker: per cell a substituted copy of the
         documents goes through evalLists, and the sums take the fixed order of include/rlhip.h (partial.fixed_order_sums)."""
         from . import partial as P
-        feats = self._partialFeatures(features)
+        feats = self._askedFeatures(features, "partialDependence", "vary")
         if not sum(rl.size() for rl in samples):
             raise RankLibError("rlhip: partialDependence needs at least one document")
         grids = [P.grid_for(self, samples, f, grid) for f in feats]
@@ -458,40 +490,18 @@ class LambdaMART(Ranker):
 
     def init(self):                   # :68-166
         logger.info("Initializing... ")
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        metric = metric_name(self.scorer) if self.scorer is not None else None
         if metric not in TREE_TRAINABLE:
             raise RankLibError("rlhip: the train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)" % (self.scorer.name() if self.scorer else None))
         cls = type(self)
         self.impacts = np.zeros(len(self.features))
-        X, lab, qoff, qkey = flatten(self.samples, self.features)
-        nk = int(qkey.max()) + 1 if len(qkey) else 0
+        train = flatten(self.samples, self.features)          # before the trainer exists, as ever: a row that cannot be read is refused first
         N.set_err_max(ERRScorer.MAX)              # the reference's static ERRScorer.MAX (-gmax) reaches the kernels through the library's static
         t = N.Trainer(n_trees=cls.nTrees, n_leaves=cls.nTreeLeaves, learning_rate=cls.learningRate, n_threshold=cls.nThreshold,
                       min_leaf_support=cls.minLeafSupport, early_stop_rounds=cls.nRoundToStopEarly, metric_k=self.scorer.getK(),
                       device=cls.device, metric=metric, ranker=self._RANKER, flags=N.RL_FLAG_FAST_LEAF if cls.fastLeaf else 0,
                       feature_sampling_rate=FeatureHistogram.samplingRate, seed=FeatureHistogram.seed)
-        t.set_train(X, lab, qoff, feature_ids=self.features, qkey=qkey)
-        if self.validationSamples is not None:
-            Xv, lv, qv, _ = flatten(self.validationSamples, self.features)
-            ids = {}
-            for q, rl in enumerate(self.samples):
-                ids.setdefault(rl.getID(), int(qkey[q]))
-            vkey = np.array([ids.setdefault(rl.getID(), nk + i) for i, rl in enumerate(self.validationSamples)], np.int32)
-            t.set_validation(Xv, lv, qv, qkey=vkey)
-        # what the scorer object already holds reaches the trainer list by list: idealGains entries (-qrel, NDCGScorer.java:50-96 -- or any
-        # earlier use of the same scorer object: a cached entry is a cached entry) and relDocCount (-qrel, APScorer.java:45-66)
-        for validation, lists in ((False, self.samples), (True, self.validationSamples)):
-            if lists is None:
-                continue
-            ideal = rdc = None
-            gains = getattr(self.scorer, "idealGains", None)
-            if metric == "NDCG" and gains:
-                ideal = np.array([gains.get(rl.getID(), np.nan) for rl in lists], np.float64)
-            counts = getattr(self.scorer, "relDocCount", None)
-            if metric == "MAP" and counts is not None:
-                rdc = np.array([counts.get(rl.getID(), 0) for rl in lists], np.int32)
-            if ideal is not None or rdc is not None:
-                t.set_external_judgments(validation, ideal, rdc)
+        feed_trainer(self, t, metric, lambda lists: train if lists is self.samples else flatten(lists, self.features), feature_ids=self.features)
         t.init()
         self._resumed, self._resume_stop = 0, False
         if cls.resumeFrom is not None:
@@ -549,17 +559,7 @@ class LambdaMART(Ranker):
 
     # --- scoring: Ensemble.eval (float accumulation) on the GPU -------------------------------------------
     def _rows(self, dps):
-        width = max([int(max(self._model.features(), default=0)) + 1] + [len(dp.fVals) for dp in dps])
-        rows = np.zeros((len(dps), width), np.float32)
-        for i, dp in enumerate(dps):
-            fv = dp.fVals
-            rows[i, :len(fv)] = np.where(np.isnan(fv), np.float32(0), fv)
-        if not DataPoint.missingZero:
-            need = int(max(self._model.features(), default=0))
-            for dp in dps:
-                if need >= len(dp.fVals):
-                    raise RankLibError("Error in DenseDataPoint::getFeatureValue(): requesting unspecified feature, fid=%d" % need)
-        return rows
+        return dense_rows(dps, int(max(self._model.features(), default=0)))
 
     def eval(self, dp):               # noqa: A003  :275-277
         return float(self._model.predict_rows(self._rows([dp]))[0])
@@ -580,47 +580,39 @@ class LambdaMART(Ranker):
         per-list path of score_lists.  Lists longer than metric.EVAL_HOST_LEN stay on the device (both paths give the same bits; the
         host's would cost one sort per stage)."""
         st = np.arange(1, self._model.num_trees() + 1, dtype=np.int32) if stages is None else np.ascontiguousarray(stages, dtype=np.int32)
-        name = scorer.name().split("@")[0].upper()
-        gains, counts = getattr(scorer, "idealGains", None), getattr(scorer, "relDocCount", None)
+        name = metric_name(scorer)
         out = np.zeros((st.size, len(samples)), np.float64)
-        a = 0
-        while a < len(samples):
-            b, docs, width = a, 0, 1
-            while b < len(samples):
-                w = max(width, samples[b].getFeatureCount() + 1)
-                if b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
-                    break
-                docs, width, b = docs + samples[b].size(), w, b + 1
-            for q in range(a, b):
-                if not samples[q].size():                    # (the kernels take no empty list: the scorer's own answer, whatever the stage)
-                    out[:, q] = scorer.score(samples[q])
-            dev = [q for q in range(a, b) if samples[q].size()]
-            if dev:
-                rows = self._rows([dp for q in dev for dp in samples[q].rl])
-                dq = np.concatenate([[0], np.cumsum([samples[q].size() for q in dev])]).astype(np.int64)
-                labels = np.fromiter((dp.label for q in dev for dp in samples[q].rl), np.float32, count=int(dq[-1]))
-                ids = [samples[q].getID() for q in dev]
-                keys, qkey, ideal, rdc = {}, None, None, None
-                if name == "NDCG":
-                    qkey = np.array([keys.setdefault(i, len(keys)) for i in ids], np.int32)
-                    ideal = np.array([gains.get(i, np.nan) for i in ids], np.float64)
-                if name == "MAP" and counts is not None:
-                    rdc = np.array([counts.get(i, 0) for i in ids], np.int32)
-                vals, nan, used = self._model.eval_stages(rows, labels, dq, name, scorer.k, st, err_max=ERRScorer.MAX, qkey=qkey,
-                                                          ideal_dcg=ideal, rel_doc_count=rdc)
-                out[:, dev] = vals
-                if name == "NDCG":
-                    for j, i in enumerate(ids):
-                        if i not in gains:
-                            gains[i] = float(used[j])
-                for j in np.flatnonzero(nan.any(axis=0)):
-                    which = np.flatnonzero(nan[:, j])
-                    sc = self._model.predict_stages(rows[int(dq[j]):int(dq[j + 1])], st[which])
-                    for r, s in enumerate(which):
-                        order = stable_desc_order(sc[r].astype(np.float64))
-                        out[s, dev[j]] = scorer.score(RankList(samples[dev[j]], list(order)))
-            a = b
+        for a, b in list_chunks(samples, Ranker.EVAL_ROW_BYTES):
+            empty, dev, rows, dq, labels, ids = self._devChunk(samples, a, b)
+            for q in empty:                                  # the scorer's own answer, whatever the stage
+                out[:, q] = scorer.score(samples[q])
+            if not dev:
+                continue
+            qkey, ideal, rdc = held_judgments(scorer, name, ids)
+            vals, nan, used = self._model.eval_stages(rows, labels, dq, name, scorer.k, st, err_max=ERRScorer.MAX, qkey=qkey,
+                                                      ideal_dcg=ideal, rel_doc_count=rdc)
+            out[:, dev] = vals
+            keep_ideals(scorer, name, ids, used)
+            for j in np.flatnonzero(nan.any(axis=0)):
+                which = np.flatnonzero(nan[:, j])
+                sc = self._model.predict_stages(rows[int(dq[j]):int(dq[j + 1])], st[which])
+                for r, s in enumerate(which):
+                    order = stable_desc_order(sc[r].astype(np.float64))
+                    out[s, dev[j]] = scorer.score(RankList(samples[dev[j]], list(order)))
         return out
+
+    def _devChunk(self, samples, a, b):
+        """What one device call over the lists samples[a:b] takes: (empty, the indices of the lists without a document, which the kernels
+        do not take; dev, the indices of the others; rows, their documents; dq, the int64 offsets of the lists of dev into rows; the
+        documents' labels; ids, the id of every list of dev).  Without a list for the device everything after dev is None."""
+        empty = [q for q in range(a, b) if not samples[q].size()]
+        dev = [q for q in range(a, b) if samples[q].size()]
+        if not dev:
+            return empty, dev, None, None, None, None
+        rows = self._rows([dp for q in dev for dp in samples[q].rl])
+        dq = np.concatenate([[0], np.cumsum([samples[q].size() for q in dev])]).astype(np.int64)
+        labels = np.fromiter((dp.label for q in dev for dp in samples[q].rl), np.float32, count=int(dq[-1]))
+        return empty, dev, rows, dq, labels, [samples[q].getID() for q in dev]
 
     # --- permutation importance in one pass (rlhip, DESIGN.md 24) ----------------------------------------------
     def permutationImportance(self, samples, scorer, features=None, repeats=5, seed=1, within=False):
@@ -631,60 +623,39 @@ class LambdaMART(Ranker):
         holds is resolved per list id as score_lists does it.  A cell whose scores hold a NaN is filled on the host, as stagedScores
         fills a stage: that list's permuted rows through predict_rows, then the per-list path of score_lists."""
         from . import importance as I
-        feats = self._importanceFeatures(features)
+        feats = self._askedFeatures(features, "permutationImportance", "measure")
         cols = np.array(feats, np.int32)
         sizes = [rl.size() for rl in samples]
         donors = I.donor_maps(sizes, repeats, seed, within)
         doc0 = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        name = scorer.name().split("@")[0].upper()
-        gains, counts = getattr(scorer, "idealGains", None), getattr(scorer, "relDocCount", None)
+        name = metric_name(scorer)
         base = np.zeros(len(samples), np.float64)
         values = np.zeros((len(feats), repeats, len(samples)), np.float64)
-        a = 0
-        while a < len(samples):
-            b, docs, width = a, 0, 1
-            while b < len(samples):
-                w = max(width, samples[b].getFeatureCount() + 1)
-                if within and b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
-                    break
-                docs, width, b = docs + samples[b].size(), w, b + 1
-            for q in range(a, b):
-                if not samples[q].size():                    # (the kernels take no empty list: the scorer's own answer, whatever the cell)
-                    base[q] = values[:, :, q] = scorer.score(samples[q])
-            dev = [q for q in range(a, b) if samples[q].size()]
-            if dev:
-                rows = self._rows([dp for q in dev for dp in samples[q].rl])
-                dq = np.concatenate([[0], np.cumsum([samples[q].size() for q in dev])]).astype(np.int64)
-                don = donors[:, int(doc0[a]):int(doc0[b])] - np.int32(doc0[a])      # (empty lists hold no document: the chunk's rows are contiguous)
-                labels = np.fromiter((dp.label for q in dev for dp in samples[q].rl), np.float32, count=int(dq[-1]))
-                ids = [samples[q].getID() for q in dev]
-                keys, qkey, ideal, rdc = {}, None, None, None
-                if name == "NDCG":
-                    qkey = np.array([keys.setdefault(i, len(keys)) for i in ids], np.int32)
-                    ideal = np.array([gains.get(i, np.nan) for i in ids], np.float64)
-                if name == "MAP" and counts is not None:
-                    rdc = np.array([counts.get(i, 0) for i in ids], np.int32)
-                bv, bnan, vals, nan, used = self._model.eval_permuted(rows, labels, dq, name, scorer.k, cols, don, err_max=ERRScorer.MAX,
-                                                                      qkey=qkey, ideal_dcg=ideal, rel_doc_count=rdc)
-                base[dev] = bv
-                values[:, :, dev] = vals
-                if name == "NDCG":
-                    for j, i in enumerate(ids):
-                        if i not in gains:
-                            gains[i] = float(used[j])
+        for a, b in list_chunks(samples, Ranker.EVAL_ROW_BYTES if within else None):
+            empty, dev, rows, dq, labels, ids = self._devChunk(samples, a, b)
+            for q in empty:                                  # the scorer's own answer, whatever the cell
+                base[q] = values[:, :, q] = scorer.score(samples[q])
+            if not dev:
+                continue
+            don = donors[:, int(doc0[a]):int(doc0[b])] - np.int32(doc0[a])      # (empty lists hold no document: the chunk's rows are contiguous)
+            qkey, ideal, rdc = held_judgments(scorer, name, ids)
+            bv, bnan, vals, nan, used = self._model.eval_permuted(rows, labels, dq, name, scorer.k, cols, don, err_max=ERRScorer.MAX,
+                                                                  qkey=qkey, ideal_dcg=ideal, rel_doc_count=rdc)
+            base[dev] = bv
+            values[:, :, dev] = vals
+            keep_ideals(scorer, name, ids, used)
 
-                def on_host(j, c, r):
-                    lo, hi = int(dq[j]), int(dq[j + 1])
-                    part = rows[lo:hi].copy()
-                    if c is not None and feats[c] < rows.shape[1]:
-                        part[:, feats[c]] = rows[don[r, lo:hi], feats[c]]
-                    order = stable_desc_order(self._model.predict_rows(part).astype(np.float64))
-                    return scorer.score(RankList(samples[dev[j]], list(order)))
-                for j in np.flatnonzero(bnan):
-                    base[dev[j]] = on_host(j, None, 0)
-                for c, r, j in np.argwhere(nan):
-                    values[c, r, dev[j]] = on_host(j, c, r)
-            a = b
+            def on_host(j, c, r):
+                lo, hi = int(dq[j]), int(dq[j + 1])
+                part = rows[lo:hi].copy()
+                if c is not None and feats[c] < rows.shape[1]:
+                    part[:, feats[c]] = rows[don[r, lo:hi], feats[c]]
+                order = stable_desc_order(self._model.predict_rows(part).astype(np.float64))
+                return scorer.score(RankList(samples[dev[j]], list(order)))
+            for j in np.flatnonzero(bnan):
+                base[dev[j]] = on_host(j, None, 0)
+            for c, r, j in np.argwhere(nan):
+                values[c, r, dev[j]] = on_host(j, c, r)
         return I.summarize(feats, base, values)
 
     # --- partial dependence in one pass (rlhip, DESIGN.md 29) --------------------------------------------------
@@ -693,7 +664,7 @@ class LambdaMART(Ranker):
         walked and summed by _native.Model.predict_partial.  A mean does not split over calls, so ONE call takes the whole file,
         whatever EVAL_ROW_BYTES says, as permutationImportance does without within."""
         from . import partial as P
-        feats = self._partialFeatures(features)
+        feats = self._askedFeatures(features, "partialDependence", "vary")
         dps = [dp for rl in samples for dp in rl.rl]
         if not dps:
             raise RankLibError("rlhip: partialDependence needs at least one document")
@@ -706,18 +677,10 @@ class LambdaMART(Ranker):
     # --- per-document feature contributions (rlhip) ----------------------------------------------
     def _rowChunks(self, samples):
         """the documents of samples as rows, in chunks of whole lists whose rows stay under EVAL_ROW_BYTES"""
-        a = 0
-        while a < len(samples):
-            b, docs, width = a, 0, 1
-            while b < len(samples):
-                w = max(width, samples[b].getFeatureCount() + 1)
-                if b > a and (docs + samples[b].size()) * w * 4 > Ranker.EVAL_ROW_BYTES:
-                    break
-                docs, width, b = docs + samples[b].size(), w, b + 1
+        for a, b in list_chunks(samples, Ranker.EVAL_ROW_BYTES):
             dps = [dp for q in range(a, b) for dp in samples[q].rl]
             if dps:
                 yield self._rows(dps)
-            a = b
 
     def countCover(self, background, accumulate=False):
         """count, per node, the documents of `background` whose walk visits it (_native.Model.cover): RankLib's model text holds no node
@@ -750,10 +713,9 @@ class LambdaMART(Ranker):
     def _interactionChunks(self, samples, n_slots):
         """the row chunks of _rowChunks cut again so that a chunk's result [rows][n_slots][n_slots] f64 stays under EVAL_ROW_BYTES
         (a chunk holds at least one row)"""
-        step = max(1, Ranker.EVAL_ROW_BYTES // (8 * n_slots * n_slots))
         for rows in self._rowChunks(samples):
-            for a in range(0, len(rows), step):
-                yield rows[a:a + step]
+            for a, b in result_steps(len(rows), 8 * n_slots * n_slots):
+                yield rows[a:b]
 
     def interactions(self, samples, background, features=None):
         """Which features work together: (f64 [documents of samples in file order][C + 2][C + 2], the C feature ids) -- SHAP
@@ -974,28 +936,11 @@ class RFRanker(Ranker):
         for i, f in enumerate(self.features):
             logger.info(" Feature %d reduced error %s", f, impacts[i])
 
-    def _rows(self, dps):
-        need = max(int(max(m.features(), default=0)) for m in self._models)
-        width = max([need + 1] + [len(dp.fVals) for dp in dps])
-        rows = np.zeros((len(dps), width), np.float32)
-        for i, dp in enumerate(dps):
-            fv = dp.fVals
-            rows[i, :len(fv)] = np.where(np.isnan(fv), np.float32(0), fv)
-        if not DataPoint.missingZero:
-            for dp in dps:
-                if need >= len(dp.fVals):
-                    raise RankLibError("Error in DenseDataPoint::getFeatureValue(): requesting unspecified feature, fid=%d" % need)
-        return rows
+    def evalList(self, rl):
+        return [float(v) for v in self._evalDocs(rl.rl)]
 
-    def evalList(self, rl):           # :109-115 for every document of the list: double s += (float) ensemble.eval; s / nBag
-        rows = self._rows(rl.rl)
-        s = np.zeros(len(rows), np.float64)
-        for m in self._models:
-            s += m.predict_rows(rows).astype(np.float64)
-        return [float(v) for v in s / len(self._models)]
-
-    def _evalDocs(self, dps):         # the same per-bag (float) -> f64 sum and / nBag, every document of the chunk at once
-        rows = self._rows(dps)
+    def _evalDocs(self, dps):         # :109-115 for every document at once: double s += (float) ensemble.eval; s / nBag
+        rows = dense_rows(dps, max(int(max(m.features(), default=0)) for m in self._models))
         s = np.zeros(len(rows), np.float64)
         for m in self._models:
             s += m.predict_rows(rows).astype(np.float64)
@@ -1071,15 +1016,18 @@ class RFRanker(Ranker):
         logger.info("Learning rate: %s", java_float_str(cls.learningRate))
 
 
-def _feed_linear_trainer(ranker, t, metric, flat=None):
-    """The training / validation lists of a CoorAscent or AdaRank ranker into its rl_ca / rl_ada trainer t, with the NDCG ideal-DCG keys
-    shared across the two sets and the external judgments the scorer holds (see LambdaMART.init).  flat: the ranker's own flatten(samples)
-    where the columns are not the feature list's (LinearRegRank)."""
+def feed_trainer(ranker, t, metric, flat=None, **train_args):
+    """The training / validation lists of a ranker into its trainer t (the tree trainer, or one of the linear and neural ones), with the
+    NDCG ideal-DCG keys shared across the two sets: a validation list whose id the training set holds takes that id's key, the others
+    continue after the training keys.  Then what the scorer object already holds reaches the trainer list by list: idealGains entries
+    (-qrel, NDCGScorer.java:50-96 -- or any earlier use of the same scorer object: a cached entry is a cached entry), sent only when
+    there is one, and relDocCount (-qrel, APScorer.java:45-66).  flat: the ranker's own flatten(samples) where the columns are not the
+    feature list's (LinearRegRank); train_args: further arguments of t.set_train (the tree trainer's feature_ids)."""
     if flat is None:
         flat = lambda lists: flatten(lists, ranker.features)      # noqa: E731
     X, lab, qoff, qkey = flat(ranker.samples)
     nk = int(qkey.max()) + 1 if len(qkey) else 0
-    t.set_train(X, lab, qoff, qkey=qkey)
+    t.set_train(X, lab, qoff, qkey=qkey, **train_args)
     if ranker.validationSamples is not None:
         Xv, lv, qv, _ = flat(ranker.validationSamples)
         ids = {}
@@ -1087,34 +1035,14 @@ def _feed_linear_trainer(ranker, t, metric, flat=None):
             ids.setdefault(rl.getID(), int(qkey[q]))
         vkey = np.array([ids.setdefault(rl.getID(), nk + i) for i, rl in enumerate(ranker.validationSamples)], np.int32)
         t.set_validation(Xv, lv, qv, qkey=vkey)
-    for validation, lists in ((False, ranker.samples), (True, ranker.validationSamples)):      # what the scorer object holds
+    for validation, lists in ((False, ranker.samples), (True, ranker.validationSamples)):
         if lists is None:
             continue
-        ideal = rdc = None
-        gains = getattr(ranker.scorer, "idealGains", None)
-        if metric == "NDCG" and gains:
-            ideal = np.array([gains.get(rl.getID(), np.nan) for rl in lists], np.float64)
-        counts = getattr(ranker.scorer, "relDocCount", None)
-        if metric == "MAP" and counts is not None:
-            rdc = np.array([counts.get(rl.getID(), 0) for rl in lists], np.int32)
+        _, ideal, rdc = held_judgments(ranker.scorer, metric, [rl.getID() for rl in lists])
+        if not getattr(ranker.scorer, "idealGains", None):       # where a scoring call sends an array of NaN, a trainer is sent nothing
+            ideal = None
         if ideal is not None or rdc is not None:
             t.set_external_judgments(validation, ideal, rdc)
-
-
-def _linear_rows(dps, fids):
-    """DataPoint rows for rl_ca_predict: column f = feature ID f (NaN read as 0), wide enough for every fid in fids"""
-    fmax = max([int(f) for f in fids] + [0])
-    width = max([fmax + 1] + [len(dp.fVals) for dp in dps])
-    rows = np.zeros((len(dps), width), np.float32)
-    for i, dp in enumerate(dps):
-        fv = dp.fVals
-        rows[i, :len(fv)] = np.where(np.isnan(fv), np.float32(0), fv)
-    if not DataPoint.missingZero:
-        for dp in dps:
-            for f in fids:
-                if f <= 0 or f >= len(dp.fVals):
-                    raise RankLibError("Error in DenseDataPoint::getFeatureValue(): requesting unspecified feature, fid=%d" % f)
-    return rows
 
 
 def _key_value_line(fullText):
@@ -1145,7 +1073,7 @@ class _LinearRanker(Ranker):
 
     def _train_metric(self):
         """the scorer's metric as the trainers name it; the linear rankers train on all six"""
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        metric = metric_name(self.scorer) if self.scorer is not None else None
         if metric not in N.RL_CA_METRIC:
             raise RankLibError("rlhip: the %s train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
                                % (self.name(), self.scorer.name() if self.scorer else None))
@@ -1204,7 +1132,7 @@ class CoorAscent(_LinearRanker):
         t = N.CoorAscentTrainer(n_restart=cls.nRestart, n_max_iteration=cls.nMaxIteration, step_base=cls.stepBase, step_scale=cls.stepScale,
                                 tolerance=cls.tolerance, regularized=cls.regularized, slack=cls.slack, metric=metric,
                                 metric_k=self.scorer.getK(), device=cls.device, seed=cls.seed, err_max=ERRScorer.MAX)
-        _feed_linear_trainer(self, t, metric)
+        feed_trainer(self, t, metric)
         self._trainer = t
 
     def learn(self):                  # :67-202
@@ -1234,7 +1162,7 @@ class CoorAscent(_LinearRanker):
 
     # --- scoring: 0.0 + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_ca_predict) -----------------
     def _predict(self, dps):          # eval :229-235
-        return N.ca_predict(self.features, self.weight, _linear_rows(dps, self.features), type(self).device)
+        return N.ca_predict(self.features, self.weight, dense_rows(dps, checked=self.features), type(self).device)
 
     def createNew(self):
         return CoorAscent()
@@ -1322,7 +1250,7 @@ class AdaRank(_LinearRanker):
         t = N.AdaRankTrainer(n_iteration=cls.nIteration, tolerance=cls.tolerance, train_with_enqueue=cls.trainWithEnqueue,
                              max_sel_count=cls.maxSelCount, metric=metric, metric_k=self.scorer.getK(), device=cls.device,
                              err_max=ERRScorer.MAX)
-        _feed_linear_trainer(self, t, metric)
+        feed_trainer(self, t, metric)
         self.rankers, self.rweight = [], []
         self._trainer = t
 
@@ -1352,7 +1280,7 @@ class AdaRank(_LinearRanker):
 
     # --- scoring: 0.0 + w[0] x[f0] + w[1] x[f1] + ... in f64 on the GPU (rl_ca_predict, repeated fids) -----------------
     def _predict(self, dps):          # eval :265-271
-        return N.ca_predict(self.rankers, self.rweight, _linear_rows(dps, self.rankers), type(self).device)
+        return N.ca_predict(self.rankers, self.rweight, dense_rows(dps, checked=self.rankers), type(self).device)
 
     def createNew(self):
         return AdaRank()
@@ -1411,7 +1339,7 @@ class RankBoost(_LinearRanker):
         cls = type(self)
         t = N.RankBoostTrainer(n_iteration=cls.nIteration, n_threshold=cls.nThreshold, metric=metric, metric_k=self.scorer.getK(),
                                device=cls.device, err_max=ERRScorer.MAX)
-        _feed_linear_trainer(self, t, metric)
+        feed_trainer(self, t, metric)
         self.wRankers, self.rWeight = [], []
         self._trainer = t
 
@@ -1440,7 +1368,7 @@ class RankBoost(_LinearRanker):
     # --- scoring: 0.0 + w[0] h_0(x) + w[1] h_1(x) + ... in f64 on the GPU (rl_rb_predict, repeated fids) ---------------
     def _predict(self, dps):          # eval :348-355
         fids = [f for f, _ in self.wRankers]
-        return N.rb_predict(fids, [t for _, t in self.wRankers], self.rWeight, _linear_rows(dps, fids), type(self).device)
+        return N.rb_predict(fids, [t for _, t in self.wRankers], self.rWeight, dense_rows(dps, checked=fids), type(self).device)
 
     def createNew(self):
         return RankBoost()
@@ -1529,7 +1457,7 @@ class LinearRegRank(_LinearRanker):
             return X, lab, qoff, qkey
 
         t = N.LinearRegTrainer(lambda_=cls.lambda_, metric=metric, metric_k=self.scorer.getK(), device=cls.device, err_max=ERRScorer.MAX)
-        _feed_linear_trainer(self, t, metric, flat)
+        feed_trainer(self, t, metric, flat)
         t.set_features(nVar, [f - 1 if 1 <= f <= width else -1 for f in feats])
         self._trainer = t
 
@@ -1552,7 +1480,7 @@ class LinearRegRank(_LinearRanker):
         if len(self.features) > len(self.weight):
             raise RankLibError("rlhip: Linear Regression has %d features to score with but only %d weights; the Java ends in an "
                                "ArrayIndexOutOfBoundsException in eval" % (len(self.features), len(self.weight)))
-        return N.lr_predict(self.features, self.weight, _linear_rows(dps, self.features), type(self).device)
+        return N.lr_predict(self.features, self.weight, dense_rows(dps, checked=self.features), type(self).device)
 
     def createNew(self):
         return LinearRegRank()
@@ -1717,7 +1645,7 @@ class RankNet(Ranker):
         if not self._trains():
             raise RankLibError(_neural_refusal(self._TYPE))
         logger.info("Initializing... ")
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        metric = metric_name(self.scorer) if self.scorer is not None else None
         if metric not in N.RL_CA_METRIC or metric not in self._METRICS:
             raise RankLibError("rlhip: the %s train metric must be one of %s (got %s)"
                                % (self.name(), ", ".join(self._METRICS), self.scorer.name() if self.scorer else None))
@@ -1726,7 +1654,7 @@ class RankNet(Ranker):
         Neuron.learningRate = RankNet.learningRate          # :286
         t = N.RankNetTrainer(n_epochs=RankNet.nIteration, learning_rate=Neuron.learningRate, hidden_sizes=hidden, metric=metric,
                              metric_k=self.scorer.getK(), device=RankNet.device, err_max=ERRScorer.MAX, lambdarank=self._LAMBDARANK)
-        _feed_linear_trainer(self, t, metric)
+        feed_trainer(self, t, metric)
         t.set_weights(np.concatenate([m.ravel() for m in start]))
         self.hidden, self.weights, self._net = hidden, start, None
         self._trainer = t
@@ -1799,10 +1727,10 @@ class RankNet(Ranker):
         if rl.size() == 0:
             return []
         net = self._model()
-        return [float(v) for v in net.predict_rows(_linear_rows(rl.rl, self.features))]
+        return [float(v) for v in net.predict_rows(dense_rows(rl.rl, checked=self.features))]
 
     def _evalDocs(self, dps):
-        return self._model().predict_rows(_linear_rows(dps, self.features))
+        return self._model().predict_rows(dense_rows(dps, checked=self.features))
 
     def eval(self, dp):               # noqa: A003  :336-349
         return self.evalList(RankList([dp]))[0]
@@ -1943,7 +1871,7 @@ class ListNet(RankNet):
         if cls.seed is None:
             raise RankLibError(_neural_refusal(self._TYPE))
         logger.info("Initializing... ")
-        metric = self.scorer.name().split("@")[0].upper() if self.scorer is not None else None
+        metric = metric_name(self.scorer) if self.scorer is not None else None
         if metric not in N.RL_CA_METRIC:
             raise RankLibError("rlhip: the %s train metric must be one of NDCG, DCG, MAP, ERR, P, RR (got %s)"
                                % (self.name(), self.scorer.name() if self.scorer else None))
@@ -1952,7 +1880,7 @@ class ListNet(RankNet):
         Neuron.learningRate = cls.learningRate              # :97
         t = N.ListNetTrainer(n_epochs=cls.nIteration, learning_rate=Neuron.learningRate, metric=metric, metric_k=self.scorer.getK(),
                              device=cls.device, err_max=ERRScorer.MAX)
-        _feed_linear_trainer(self, t, metric)
+        feed_trainer(self, t, metric)
         t.set_weights(start)
         self.hidden, self.weights, self._net = [], [start.reshape(1, F + 1)], None
         self._trainer = t

@@ -251,12 +251,47 @@ TREE_TRAINABLE = TRAINABLE + ("P", "RR")      # ... and those of the tree traine
 EVAL_HOST_LEN = 2048                  # a list longer than this is ranked and scored on the host (the counting rank is O(n^2); measured: DESIGN.md 19)
 
 
+# ---- what a scorer object holds, resolved per list id ---------------------------------------------------------------------
+def metric_name(scorer):
+    """the scorer's metric as the library names it: "NDCG@10" -> "NDCG" """
+    return scorer.name().split("@")[0].upper()
+
+
+def id_keys(ids):
+    """int32 key per id: equal ids share a key, and the keys count up in first-seen order (NDCGScorer caches one ideal DCG per id, so
+    the first list of an id decides for the later ones)"""
+    keys = {}
+    return np.array([keys.setdefault(i, len(keys)) for i in ids], np.int32)
+
+
+def held_judgments(scorer, name, ids):
+    """(qkey, ideal_dcg, rel_doc_count) of one scoring call over the lists with these ids, None where the metric has none: NDCG gets the
+    keys of id_keys and the idealGains entries, NaN for an id without one; MAP gets relDocCount's entries, 0 for an id without one, once
+    a -qrel file has made the table"""
+    qkey = ideal = rdc = None
+    if name == "NDCG":
+        qkey = id_keys(ids)
+        gains = getattr(scorer, "idealGains", None) or {}
+        ideal = np.array([gains.get(i, np.nan) for i in ids], np.float64)
+    if name == "MAP" and getattr(scorer, "relDocCount", None) is not None:
+        rdc = np.array([scorer.relDocCount.get(i, 0) for i in ids], np.int32)
+    return qkey, ideal, rdc
+
+
+def keep_ideals(scorer, name, ids, used):
+    """after the call: the ideal DCGs it worked with go into idealGains for the ids that had no entry (an entry is never replaced), so
+    the scorer is left as its own scoreOne calls would have left it"""
+    if name == "NDCG":
+        for i, v in zip(ids, used):
+            if i not in scorer.idealGains:
+                scorer.idealGains[i] = float(v)
+
+
 def score_lists(scorer, samples, flat_scores, want_pos=False):
     """scorer.score(ranked list) of every list of samples, all lists in one _native.eval_lists call: flat_scores [n_docs] holds the
     model's scores, list after list.  Returns (f64 value per list, int32 position of every document in its list's ranking or None).
-    What the scorer object holds is resolved per list id as _feed_linear_trainer does for the trainers -- idealGains (NDCG), relDocCount
-    (MAP), k, ERRScorer.MAX -- and the ideal DCGs the call computed are written back into idealGains, so the scorer is left as its own
-    scoreOne calls would have left it.  A list whose scores hold a NaN, or one longer than EVAL_HOST_LEN, takes the per-list host path
+    What the scorer object holds is resolved per list id (held_judgments: idealGains for NDCG, relDocCount for MAP; k, ERRScorer.MAX)
+    and the ideal DCGs the call computed are written back into idealGains (keep_ideals).  A list whose scores hold a NaN, or one longer than EVAL_HOST_LEN, takes the per-list host path
     (stable_desc_order + scorer.score) in its place."""
     from .learning import RankList, stable_desc_order
     sc = np.ascontiguousarray(flat_scores, dtype=np.float64)
@@ -265,7 +300,7 @@ def score_lists(scorer, samples, flat_scores, want_pos=False):
     np.cumsum([rl.size() for rl in samples], out=qoff[1:])
     if sc.shape != (int(qoff[-1]),):
         raise RankLibError("rlhip: score_lists takes one score per document (%d scores, %d documents)" % (sc.size, int(qoff[-1])))
-    name = scorer.name().split("@")[0].upper()
+    name = metric_name(scorer)
     ids = [rl.getID() if rl.size() else None for rl in samples]
     out = np.zeros(nl, np.float64)
     pos = np.zeros(sc.size, np.int32) if want_pos else None
@@ -298,23 +333,14 @@ def score_lists(scorer, samples, flat_scores, want_pos=False):
         dq = qoff if all_dev else np.concatenate([[0], np.cumsum(lens[dev])])
         take = slice(None) if all_dev else np.concatenate([np.arange(qoff[q], qoff[q + 1]) for q in dev])
         labels = np.fromiter((dp.label for q in dev for dp in samples[q].rl), np.float32, count=int(dq[-1]))
-        keys, qkey, ideal, rdc = {}, None, None, None
-        gains = getattr(scorer, "idealGains", None)
-        if name == "NDCG":
-            qkey = np.array([keys.setdefault(ids[q], len(keys)) for q in dev], np.int32)
-            ideal = np.array([gains.get(ids[q], np.nan) for q in dev], np.float64)
-        counts = getattr(scorer, "relDocCount", None)
-        if name == "MAP" and counts is not None:
-            rdc = np.array([counts.get(ids[q], 0) for q in dev], np.int32)
+        dev_ids = [ids[q] for q in dev]
+        qkey, ideal, rdc = held_judgments(scorer, name, dev_ids)
         m, p, used = _native.eval_lists(sc[take], labels, dq, name, scorer.k, err_max=ERRScorer.MAX, qkey=qkey, ideal_dcg=ideal,
                                         rel_doc_count=rdc, want_pos=want_pos)
         out[dev] = m
         if pos is not None:
             pos[take] = p
-        if name == "NDCG":
-            for j, q in enumerate(dev):
-                if ids[q] not in gains:
-                    gains[ids[q]] = float(used[j])
+        keep_ideals(scorer, name, dev_ids, used)
     for q in later:
         on_host(q)
     return out, pos

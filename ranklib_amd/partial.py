@@ -21,13 +21,11 @@ squared move of a document away from its own score: its spread over a feature's 
 """
 import collections
 import logging
-import math
 import re
 import sys
 
 import numpy as np
 
-from . import normalizer
 from ._native import PARTIAL_SUM_BLOCK, RankLibError
 
 logger = logging.getLogger("ranklib_amd")
@@ -132,10 +130,9 @@ def ice_lines(result):
 
 
 def main(argv=None):
-    from .evaluator import Evaluator
+    from .evaluator import ArgCursor, Evaluator, common_flag
     from .features import FeatureManager
-    from .learning import (AdaRank, CoorAscent, DataPoint, LambdaMART, LinearRegRank, RankBoost, RankerFactory, RankerType, RankNet)
-    from .metric import ERRScorer
+    from .learning import RankerFactory, RankerType
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
@@ -147,33 +144,17 @@ def main(argv=None):
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
     Evaluator.qrelFile = ""
-    i = 0
-    while i < len(args):                                    # flags are matched case-insensitively, as the evaluator matches them
-        a = args[i].lower()
-
-        def nxt():
-            nonlocal i
-            i += 1
-            if i >= len(args):
-                raise RankLibError("Missing value for " + args[i - 1])
-            return args[i]
+    cur = ArgCursor(args)
+    nxt = cur.nxt
+    for a in cur:
         if a == "-load": models.append(nxt())
         elif a == "-test": testFiles.append(nxt())
         elif a == "-grid": grid = nxt()
         elif a == "-feature": featureFile = nxt()
         elif a == "-out": outFile = nxt()
         elif a == "-ice": iceFile = nxt()
-        elif a == "-gmax": ERRScorer.MAX = math.pow(2.0, float(nxt()))
-        elif a == "-qrel": Evaluator.qrelFile = nxt()
-        elif a == "-missingzero": DataPoint.missingZero = True
-        elif a == "-hr": Evaluator.mustHaveRelDoc = True
-        elif a == "-norm":
-            Evaluator.nml = normalizer.create(nxt())
-            Evaluator.normalize = True
-        elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = RankNet.device = int(nxt())
-        else:
-            raise RankLibError("Unknown command-line parameter: " + args[i])
-        i += 1
+        elif not common_flag(a, nxt):
+            cur.unknown()
     if len(models) != 1:
         raise RankLibError("ranklib_amd.partial takes exactly one -load model (got %d)" % len(models))
     if len(testFiles) != 1:

@@ -13,15 +13,11 @@ model cut at its best point.  RankLib has this only as the validation roll-back 
 A file's mean at a stage is the serial f64 sum of its lists' values in list order divided by the list count, as Evaluator.test has it.
 """
 import logging
-import math
 import sys
 
-from . import normalizer
 from ._native import RankLibError
-from .evaluator import Evaluator
-from .learning import (AdaRank, CoorAscent, DataPoint, LambdaMART, LinearRegRank, RankBoost, RankerFactory, RankerType, RankNet,
-                       java_double_str)
-from .metric import ERRScorer
+from .evaluator import ArgCursor, Evaluator, common_flag
+from .learning import LambdaMART, RankerFactory, RankerType, java_double_str
 
 logger = logging.getLogger("ranklib_amd")
 
@@ -70,16 +66,9 @@ def main(argv=None):
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
     Evaluator.qrelFile = ""
-    i = 0
-    while i < len(args):                                    # flags are matched case-insensitively, as the evaluator matches them
-        a = args[i].lower()
-
-        def nxt():
-            nonlocal i
-            i += 1
-            if i >= len(args):
-                raise RankLibError("Missing value for " + args[i - 1])
-            return args[i]
+    cur = ArgCursor(args)
+    nxt = cur.nxt
+    for a in cur:
         if a == "-load": models.append(nxt())
         elif a == "-test": testFiles.append(nxt())
         elif a == "-metric2t": metric = nxt()
@@ -87,17 +76,8 @@ def main(argv=None):
         elif a == "-curve": curveFile = nxt()
         elif a == "-save": saveFile = nxt()
         elif a == "-pick": pick = int(nxt())
-        elif a == "-gmax": ERRScorer.MAX = math.pow(2.0, float(nxt()))
-        elif a == "-qrel": Evaluator.qrelFile = nxt()
-        elif a == "-missingzero": DataPoint.missingZero = True
-        elif a == "-hr": Evaluator.mustHaveRelDoc = True
-        elif a == "-norm":
-            Evaluator.nml = normalizer.create(nxt())
-            Evaluator.normalize = True
-        elif a == "-device": LambdaMART.device = CoorAscent.device = AdaRank.device = RankBoost.device = LinearRegRank.device = RankNet.device = int(nxt())
-        else:
-            raise RankLibError("Unknown command-line parameter: " + args[i])
-        i += 1
+        elif not common_flag(a, nxt):
+            cur.unknown()
     if len(models) != 1:
         raise RankLibError("ranklib_amd.stages takes exactly one -load model (got %d)" % len(models))
     if not testFiles:

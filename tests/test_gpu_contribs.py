@@ -9,11 +9,12 @@ import numpy as np
 import pytest
 
 import contrib_restatement as CR
+import list_cases as LC
 import tree_models as TM
 from ranklib_amd import _native as N
 from ranklib_amd import contribs as CL
 from ranklib_amd.features import FeatureManager
-from ranklib_amd.learning import LambdaMART, MART, RankerFactory, java_double_str, java_float_str
+from ranklib_amd.learning import LambdaMART, MART, Ranker, RankerFactory, java_double_str, java_float_str
 
 pytestmark = pytest.mark.gpu
 
@@ -289,6 +290,31 @@ def test_row_chunks_change_no_bit():
     each, _ = m.predict_contribs(rows[:5], scratch_bytes=1)                # a chunk holds at least one row
     assert np.array_equal(u64(each), u64(whole[:5]))
     assert CR.same_f64(whole, CR.contribs(trees, w, reference("count_37", 257)[1], rows, feats)) is None
+
+
+def test_covers_and_contributions_in_chunks_of_whole_lists_equal_the_one_chunk(monkeypatch):
+    """list_cases under its small limit: countCover and both kinds of contributions go in five calls each (one list alone over the
+    limit, an empty list inside a chunk) and give the bits of the one call"""
+    samples, bg = LC.lists(), LC.lists(seed=10)
+    ranker = RankerFactory().loadRankerFromString(LC.model_text())
+    calls = {"cover": [], "predict_contribs": [], "predict_shap": []}
+    for nm in calls:
+        monkeypatch.setattr(ranker._model, nm, lambda rows, *a, _f=getattr(ranker._model, nm), _c=calls[nm], **kw: (_c.append(len(rows)), _f(rows, *a, **kw))[1])
+
+    def run():
+        for c in calls.values():
+            del c[:]
+        ranker.countCover(bg)
+        return ranker._model.cover_rows(), ranker.contributions(samples, None, exact=False), ranker.contributions(samples, None, exact=True)
+    n_one, (approx_one, ids), (exact_one, _) = run()
+    assert calls == {"cover": [0, sum(LC.SIZES)], "predict_contribs": [sum(LC.SIZES)], "predict_shap": [sum(LC.SIZES)]}      # (the reset, then the file)
+    monkeypatch.setattr(Ranker, "EVAL_ROW_BYTES", LC.SMALL_LIMIT)
+    n_many, (approx_many, ids_many), (exact_many, _) = run()
+    assert calls == {"cover": [0] + LC.CHUNK_ROWS, "predict_contribs": LC.CHUNK_ROWS, "predict_shap": LC.CHUNK_ROWS}
+    assert n_many == n_one == sum(LC.SIZES) and ids_many == ids
+    assert approx_one.shape == exact_one.shape == (sum(LC.SIZES), len(ids) + 2)
+    assert np.array_equal(u64(approx_many), u64(approx_one)) and np.array_equal(u64(exact_many), u64(exact_one))
+    assert not np.array_equal(u64(approx_one), u64(exact_one)) and approx_one[:, :len(ids)].any()
 
 
 # ---- 6. against the public path ------------------------------------------------------------------------------------------------------------

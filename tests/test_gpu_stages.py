@@ -7,13 +7,14 @@ import numpy as np
 import pytest
 
 import eval_lists_restatement as ER
+import list_cases as LC
 import stages_restatement as SR
 import tree_models as TM
 from ranklib_amd import _native as N
 from ranklib_amd import evaluator, stages
 from ranklib_amd import metric as M
 from ranklib_amd.features import FeatureManager
-from ranklib_amd.learning import RankerFactory, java_float_str
+from ranklib_amd.learning import Ranker, RankerFactory, java_float_str
 
 pytestmark = pytest.mark.gpu
 
@@ -374,3 +375,31 @@ def test_command_line(tmp_path):
         f.write("## Coordinate Ascent\n## Restart = 5\n2:0.5 4:-0.25 6:0.125")
     with pytest.raises(N.RankLibError, match="Coordinate Ascent"):
         stages.main(["-load", lin, "-test", f1])
+
+
+# ---- 11. chunks of whole lists ---------------------------------------------------------------------------------------------------------
+SCORERS = {"NDCG@10": lambda: M.NDCGScorer(10), "MAP": M.APScorer, "ERR@3": lambda: M.ERRScorer(3)}
+
+
+@pytest.mark.parametrize("metric", sorted(SCORERS))
+def test_staged_scores_in_chunks_of_whole_lists_equal_the_one_chunk(metric, monkeypatch):
+    """list_cases under its small limit: five eval_stages calls (one ends in the empty list, one list alone over the limit, the second
+    list of the shared id in a later call than the first) give the bits of the one call, and leave the scorer with the same entries"""
+    samples = LC.lists()
+    ranker = RankerFactory().loadRankerFromString(LC.model_text())
+    calls = []
+    inner = ranker._model.eval_stages
+    monkeypatch.setattr(ranker._model, "eval_stages", lambda rows, *a, **kw: (calls.append(len(rows)), inner(rows, *a, **kw))[1])
+    one_scorer, many_scorer = SCORERS[metric](), SCORERS[metric]()
+    one = ranker.stagedScores(samples, one_scorer)
+    assert calls == [sum(LC.SIZES)] and one.shape == (6, len(LC.SIZES))
+    del calls[:]
+    monkeypatch.setattr(Ranker, "EVAL_ROW_BYTES", LC.SMALL_LIMIT)
+    many = ranker.stagedScores(samples, many_scorer)
+    assert calls == LC.CHUNK_ROWS
+    assert np.array_equal(bits(many), bits(one))
+    assert np.array_equal(bits(one[:, 2]), bits(np.zeros(6)))        # the empty list: the scorer's own answer
+    assert (bits(one[0]) != bits(one[-1])).any()                     # the stages are told apart
+    gains = getattr(one_scorer, "idealGains", None)
+    assert getattr(many_scorer, "idealGains", None) == gains
+    assert (set(gains) == set(LC.IDS) - {None}) if metric == "NDCG@10" else gains is None
