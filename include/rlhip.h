@@ -194,6 +194,33 @@ int rl_boost_round(rl_trainer *t, rl_tree *out, float *train_metric, float *vali
  * weight whose bits differ from learning_rate (per-tree weights are not built), scratch_bytes < 0.  A sharded trainer: RL_ERR_UNSUPPORTED. */
 int rl_adopt_model_text(rl_trainer *t, const char *text, int64_t scratch_bytes, int32_t *stop);
 
+/* Refit: the T0 trees of a saved model keep their structure -- features, thresholds, children -- and get new leaf values from this
+ * trainer's data.  `text` and the moment of the call are rl_adopt_model_text's: after rl_init, before the first round.  For r = 0 .. T0 - 1 in order:
+ *   1. lambda and w of the current modelScores, exactly as round r of training computes them (MART: label - score); the trainer's metric and
+ *      flags apply as in a normal round.
+ *   2. every training document is walked down tree r on its RAW ROW, value <= threshold goes left (Split.java:115-125); the model's thresholds
+ *      need not be bin boundaries of this data.
+ *   3. the leaves are taken in left-first DFS order (Split.leaves), the documents of a leaf in ASCENDING DOCUMENT INDEX, the order
+ *      Split.getSamples() has after stable partitions of 0 .. N-1.
+ *   4. the new value of a leaf: LambdaMART the two float running sums of LambdaMART.java:401-413, 0 when s2 == 0; MART s1 / count
+ *      (MART.java:54-65); evaluated by the leaf evaluator the flags select (default chains, RL_FLAG_SERIAL_CHAIN, RL_FLAG_FAST_LEAF).
+ *   5. a leaf no document reaches keeps its old output.
+ *   6. decay == 0: the stored output is the new value, no arithmetic (bit equal whatever the old output was); else it is
+ *      (float)((double)decay * (double)old + (1.0 - (double)decay) * (double)new).
+ *   7. the tree with its new outputs replaces tree r; modelScores[k] += (double)learning_rate * (double)output; the round's ranking and float-mean
+ *      metric, and for a validation set the score update, ranking and metric, as behind a trained round.
+ * Afterwards the trainer stands at round T0 as after rl_adopt_model_text: rl_get_round_metrics(r < T0) hold the refit rounds' values,
+ * rl_best_validation is rebuilt by the strict >, *stop (may be NULL) is the test of LambdaMART.java:248 at round T0 - 1, rl_boost_round goes on
+ * with round T0 on this data, rl_finish and rl_model_to_text work.  rl_get_tree reports the documents that reached each node as `count`;
+ * `deviance` stays NaN.  Refitting a model on the data and parameters it was trained with, decay 0, gives the model back bit for bit.
+ * RL_ERR_INVALID: what rl_adopt_model_text refuses, a decay that is NaN, negative or >= 1, a tree with more leaves than the leaf machinery
+ * takes (n_leaves of the trainer, at most 512; the message states the number).  A sharded trainer: RL_ERR_UNSUPPORTED. */
+int rl_refit_model_text(rl_trainer *t, const char *text, float decay, int32_t *stop);
+
+/* out[3]: launches of the routing kernel of rl_refit_model_text that staged the rows in LDS, launches that read them from global memory (more
+ * than 640 features, or RLHIP_REFIT_DIRECT), leaves that kept their old output because no document reached them. */
+int rl_debug_refit_stats(const rl_trainer *t, int64_t *out);
+
 /* Enqueue n rounds without any host synchronisation (no validation set allowed: early stopping needs
  * the host).  rl_sync waits for them; trees and per-round metrics are then available through
  * rl_get_tree / rl_get_round_metrics. */

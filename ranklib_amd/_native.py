@@ -149,6 +149,7 @@ ABI_SYMBOLS = [
     "rl_model_cover", "rl_model_cover_rows", "rl_model_get_cover", "rl_model_predict_contribs", "rl_model_predict_leaf_sums", "rl_debug_contrib_times", "rl_debug_contrib_passes",
     "rl_model_predict_shap", "rl_model_shap_limits", "rl_debug_shap_times", "rl_debug_shap_passes",
     "rl_adopt_model_text",
+    "rl_refit_model_text", "rl_debug_refit_stats",
     "rl_model_predict_partial", "rl_debug_partial_times",
     "rl_model_predict_interactions", "rl_debug_interact_times", "rl_debug_interact_passes",
 ]
@@ -319,6 +320,9 @@ def lib():
         L.rl_debug_shap_passes.argtypes = [C.POINTER(i32)]
     if hasattr(L, "rl_adopt_model_text"):     # (A/B builds of older sources cannot resume)
         L.rl_adopt_model_text.argtypes = [vp, C.c_char_p, i64, C.POINTER(i32)]
+    if hasattr(L, "rl_refit_model_text"):     # (A/B builds of older sources cannot refit)
+        L.rl_refit_model_text.argtypes = [vp, C.c_char_p, C.c_float, C.POINTER(i32)]
+        L.rl_debug_refit_stats.argtypes = [vp, C.POINTER(i64)]
     if hasattr(L, "rl_model_predict_partial"):  # (A/B builds of older sources have no partial dependence)
         L.rl_model_predict_partial.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp]
         L.rl_debug_partial_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -614,6 +618,22 @@ class Trainer:
         stop = C.c_int32(0)
         check(lib().rl_adopt_model_text(self.h, None if text is None else text.encode("ascii"), scratch_bytes, C.byref(stop)))
         return bool(stop.value)
+
+    def refit_model_text(self, text, decay=0.0):
+        """refit: the trees of `text` keep their structure and get new leaf values from this trainer's data, blended with the old ones
+        by `decay` in [0, 1) (0: the new values alone); after init(), before the first round.  Returns the early-stop test at the last refit
+        round; round_metrics(r) holds the refit rounds' values, boost_round() goes on behind them"""
+        if not hasattr(lib(), "rl_refit_model_text"):
+            raise RankLibError("this librlhip.so has no rl_refit_model_text: it cannot refit")
+        stop = C.c_int32(0)
+        check(lib().rl_refit_model_text(self.h, None if text is None else text.encode("ascii"), float(decay), C.byref(stop)))
+        return bool(stop.value)
+
+    def refit_stats(self):
+        """rl_debug_refit_stats: (routing launches through the LDS tile, routing launches from global memory, leaves that kept their old output)"""
+        out = (C.c_int64 * 3)()
+        check(lib().rl_debug_refit_stats(self.h, out))
+        return tuple(int(v) for v in out)
 
     def boost_rounds_async(self, n):
         check(lib().rl_boost_rounds_async(self.h, n))

@@ -41,7 +41,7 @@ struct Knobs {
     double dist_timeout_s = 300.0;
     bool balance = true, skip_last = true, step2 = true, sel2_wide = true, fused_quant = true, score_stream = true, dm_root = false, lam_compact = false;
     bool rank_split = false, runs_off = false, jhist_v1 = false, lambda_unfused = false, tie_off = false, tie_no_xdefer = false, tie_walk = false, tie_force_regrow = false;
-    bool dist_count_pass = false, dist_host_plan = false, dist_owner_chains = false, tie_prof = false, chain_prof = false, steplog = false, replay_direct = false;
+    bool dist_count_pass = false, dist_host_plan = false, dist_owner_chains = false, tie_prof = false, chain_prof = false, steplog = false, replay_direct = false, refit_direct = false;
 
     void read()
     {
@@ -79,6 +79,8 @@ struct Knobs {
         lam_compact = nonzero("RLHIP_LAMBDA_COMPACT");                                          // NDCG / DCG pair terms from per-wavefront lists of the active pairs
         // -- resume (rl_resume.inc)
         replay_direct = present("RLHIP_REPLAY_DIRECT");                                         // k_replay_scores reads the rows from global memory instead of an LDS tile (cross-check, tools/resume_bench.py)
+        // -- refit (rl_refit.inc)
+        refit_direct = present("RLHIP_REFIT_DIRECT");                                           // k_refit_route reads the rows from global memory instead of an LDS tile (cross-check, tools/refit_bench.py)
         // -- lazy Java-order tie-break (rl_tie.inc, rl_tie_host.inc)
         tie_off = present("RLHIP_TIE_OFF");                                                     // keep the first candidate of an exact tie
         tie_no_xdefer = present("RLHIP_TIE_NO_XDEFER");                                         // stall on ties over several features instead of deferring them

@@ -121,19 +121,14 @@ static int upload_adopted(rl_trainer *t, const std::vector<HostTree> &trees, con
     return RL_OK;
 }
 
-}  // namespace rl
-
-extern "C" int rl_adopt_model_text(rl_trainer *t, const char *text, int64_t scratch_bytes, int32_t *stop)
+// what rl_adopt_model_text and rl_refit_model_text (rl_refit.inc) ask of a handle and a text before anything is uploaded; `w` opens every message
+static int check_adoptable(rl_trainer *t, const std::string &w, const char *text, bool refit, std::vector<HostTree> &trees, std::map<int32_t, int32_t> &col_of)
 {
-    const std::string w = "rl_adopt_model_text: ";
-    if (check_trainer(t)) return RL_ERR_INVALID;
     if (!text) return fail(RL_ERR_INVALID, w + "null text");
-    if (scratch_bytes < 0) return fail(RL_ERR_INVALID, w + "scratch_bytes must be >= 0");
     if (!t->inited) return fail(RL_ERR_STATE, w + "rl_init has not been called");
     if (t->finished) return fail(RL_ERR_STATE, w + "rl_finish has been called");
-    if (t->round != 0) return fail(RL_ERR_STATE, w + "a model is adopted before the first round (this trainer has " + std::to_string(t->round) + ")");
-    if (t->dist) return fail(RL_ERR_UNSUPPORTED, w + "a sharded trainer cannot adopt a model (the replay is not built for shards)");
-    std::vector<HostTree> trees;
+    if (t->round != 0) return fail(RL_ERR_STATE, w + "a model is " + (refit ? "refitted" : "adopted") + " before the first round (this trainer has " + std::to_string(t->round) + ")");
+    if (t->dist) return fail(RL_ERR_UNSUPPORTED, w + "a sharded trainer cannot " + (refit ? "refit a model (the routing is not built for shards)" : "adopt a model (the replay is not built for shards)"));
     std::string err;
     if (!model_from_text(text, trees, err)) return fail(RL_ERR_INVALID, w + "Error in Emsemble(xmlRepresentation): " + err);
     {   // one <ensemble>: the parser stops behind the first
@@ -147,7 +142,6 @@ extern "C" int rl_adopt_model_text(rl_trainer *t, const char *text, int64_t scra
     if (trees.size() > (size_t)t->p.n_trees)
         return fail(RL_ERR_INVALID, w + "the model has " + std::to_string(trees.size()) + " trees, the trainer's n_trees is " + std::to_string(t->p.n_trees) +
                                     " (-tree is the total number of trees)");
-    std::map<int32_t, int32_t> col_of;
     for (int f = 0; f < t->F; f++) col_of.emplace(t->feature_ids[f], f);       // (a repeated id: its first column)
     for (int r = 0; r < T0; r++) {
         const HostTree &h = trees[r];
@@ -166,9 +160,48 @@ extern "C" int rl_adopt_model_text(rl_trainer *t, const char *text, int64_t scra
             return fail(RL_ERR_INVALID, w + "tree " + std::to_string(r) + " has weight " + java_float_to_string(h.weight) + ", the trainer's learning_rate is " +
                                         java_float_to_string(t->p.learning_rate) + " (per-tree weights are not built: resume under the shrinkage the model was trained with)");
     }
+    return RL_OK;
+}
+
+// behind the last of T0 adopted or refitted rounds: everything keyed by the index of a tree moves on by T0 -- the round counter, the trees kept, the
+// device's count of trees started (the seeded feature draw of a split attempt is keyed by it: root_hash) and the host's mirror of it -- then the
+// rounds' metrics come to the host, best_round / best_score are rebuilt and *stop is the test of :248 at round T0 - 1
+static int settle_adopted(rl_trainer *t, int T0, int32_t *stop)
+{
+    Ctx &c = t->ctx;
+    int32_t seq = 0;
+    RL_HIP(hipStreamSynchronize(t->stream));
+    RL_HIP(hipMemcpy(&seq, &c.st->tree_seq, sizeof(seq), hipMemcpyDeviceToHost));
+    seq += T0;
+    RL_HIP(hipMemcpy(&c.st->tree_seq, &seq, sizeof(seq), hipMemcpyHostToDevice));
+    t->tree_seq += (uint32_t)T0;
+    t->round = T0; t->n_kept = T0;
+    int rc = sync_rounds(t);       // the rounds' metrics -> h_metrics, synced_rounds = T0
+    if (rc) return rc;
+    if (t->has_valid)              // rl_boost_round's strict > over the rounds in order (LambdaMART.java:237-243)
+        for (int r = 0; r < T0; r++) {
+            const double score = t->h_metrics[2 * (size_t)r + 1];
+            if (score > t->best_score) { t->best_score = score; t->best_round = r; }
+        }
+    if (stop) *stop = ((T0 - 1) - t->best_round > t->p.early_stop_rounds) ? 1 : 0;      // :248 at round T0 - 1
+    return RL_OK;
+}
+
+}  // namespace rl
+
+extern "C" int rl_adopt_model_text(rl_trainer *t, const char *text, int64_t scratch_bytes, int32_t *stop)
+{
+    const std::string w = "rl_adopt_model_text: ";
+    if (check_trainer(t)) return RL_ERR_INVALID;
+    if (scratch_bytes < 0) return fail(RL_ERR_INVALID, w + "scratch_bytes must be >= 0");
+    std::vector<HostTree> trees;
+    std::map<int32_t, int32_t> col_of;
+    int rc = check_adoptable(t, w, text, false, trees, col_of);
+    if (rc) return rc;
+    const int T0 = (int)trees.size();
     RL_HIP(hipSetDevice(t->p.device));
     RL_HIP(hipStreamSynchronize(t->stream));
-    int rc = upload_adopted(t, trees, col_of);
+    rc = upload_adopted(t, trees, col_of);
     if (rc) return rc;
     // stage scratch: 8 bytes per document and tree, both data sets; at least one tree per chunk
     const int64_t per_tree = 8 * ((int64_t)t->tr.N + (t->has_valid ? (int64_t)t->va.N : 0));
@@ -196,22 +229,5 @@ extern "C" int rl_adopt_model_text(rl_trainer *t, const char *text, int64_t scra
         }
         RL_HIP(hipGetLastError());
     }
-    // everything keyed by the index of a tree moves on by T0: the round counter, the trees kept, the device's count of trees started (the seeded
-    // feature draw of a split attempt is keyed by it: root_hash) and the host's mirror of it
-    int32_t seq = 0;
-    RL_HIP(hipStreamSynchronize(t->stream));
-    RL_HIP(hipMemcpy(&seq, &c.st->tree_seq, sizeof(seq), hipMemcpyDeviceToHost));
-    seq += T0;
-    RL_HIP(hipMemcpy(&c.st->tree_seq, &seq, sizeof(seq), hipMemcpyHostToDevice));
-    t->tree_seq += (uint32_t)T0;
-    t->round = T0; t->n_kept = T0;
-    rc = sync_rounds(t);           // the adopted rounds' metrics -> h_metrics, synced_rounds = T0
-    if (rc) return rc;
-    if (t->has_valid)              // rl_boost_round's strict > over the rounds in order (LambdaMART.java:237-243)
-        for (int r = 0; r < T0; r++) {
-            const double score = t->h_metrics[2 * (size_t)r + 1];
-            if (score > t->best_score) { t->best_score = score; t->best_round = r; }
-        }
-    if (stop) *stop = ((T0 - 1) - t->best_round > t->p.early_stop_rounds) ? 1 : 0;      // :248 at round T0 - 1
-    return RL_OK;
+    return settle_adopted(t, T0, stop);
 }

@@ -400,14 +400,15 @@ static int enqueue_leaf_outputs(rl_trainer *t, bool stream_scores)
 }
 
 // ---- score update, the tree's export, the round's metrics --------------------------------------------------------
-static int enqueue_scores_and_metrics(rl_trainer *t, bool stream_scores)
+// (export_tree = false: a refit round, rl_refit.inc -- its tree is in t->ens already, with thresholds that are not in the trainer's own table)
+static int enqueue_scores_and_metrics(rl_trainer *t, bool stream_scores, bool export_tree = true)
 {
     Ctx &c = t->ctx;
     hipStream_t s = t->stream;
     const int m = t->round;
     if (stream_scores) hipLaunchKernelGGL(k_score_stream, dim3(std::max(1, std::min(2048, (c.N + kScoreBatch * kThreads - 1) / (kScoreBatch * kThreads)))), dim3(kThreads), 0, s, c);
     else hipLaunchKernelGGL(k_score_update, dim3(std::max(1, std::min(4096, (c.N + kScoreBatch * kThreads - 1) / (kScoreBatch * kThreads)))), dim3(kThreads), 0, s, c);
-    hipLaunchKernelGGL(k_export_tree, dim3(1), dim3(kThreads), 0, s, c, t->ens, m);
+    if (export_tree) hipLaunchKernelGGL(k_export_tree, dim3(1), dim3(kThreads), 0, s, c, t->ens, m);
     RL_HIP(hipGetLastError());
     // per-round training metric (LambdaMART.java:216)
     // (sharded runs, round 6: the per-query values are gathered on the main stream -- one communicator, one stream -- and the float mean over the
@@ -448,6 +449,13 @@ static int enqueue_scores_and_metrics(rl_trainer *t, bool stream_scores)
     return RL_OK;
 }
 
+// the score update streams over the documents when the leaf sums' gather can leave every document's leaf behind (one GPU, parallel chains, <= 1024 leaves)
+static bool round_streams_scores(const rl_trainer *t)
+{
+    const Ctx &c = t->ctx;
+    return t->knobs.score_stream && !(t->p.flags & RL_FLAG_SERIAL_CHAIN) && c.leaf_of != nullptr && c.L > 0 && c.L <= 1024;       // (sharded runs too, round 6: the local gather in leaf order leaves every document's leaf behind)
+}
+
 static int enqueue_round(rl_trainer *t)
 {
     Ctx &c = t->ctx;
@@ -455,8 +463,7 @@ static int enqueue_round(rl_trainer *t)
     // cut is not one -- rl_tie.inc, k_tie_verify; nothing a round keeps has been written by then)
     const int tie_mode = c.tie_on;
     struct TieModeRestore { Ctx &c; int v; ~TieModeRestore() { c.tie_on = v; } } tie_mode_restore{c, tie_mode};
-    // the score update streams over the documents when the leaf sums' gather can leave every document's leaf behind (one GPU, parallel chains, <= 1024 leaves)
-    const bool stream_scores = t->knobs.score_stream && !(t->p.flags & RL_FLAG_SERIAL_CHAIN) && c.leaf_of != nullptr && c.L > 0 && c.L <= 1024;       // (sharded runs too, round 6: the local gather in leaf order leaves every document's leaf behind)
+    const bool stream_scores = round_streams_scores(t);
     RoundPlan pl;
     int rc = round_plan(t, pl);
     if (rc) return rc;

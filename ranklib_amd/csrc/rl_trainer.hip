@@ -87,6 +87,7 @@ struct rl_trainer {
     int32_t cr_groups = 0; double cr_entries = 0, cr_overflow = 0;          // compact rows (groups that use them; of the child passes (k_compact_rows): entries outside the mode bins, rows that need the dense fallback
     double err_max = 16.0;      // ERRScorer.MAX when the trainer was created (rl_set_err_max)
     int32_t round = 0;          // rounds enqueued so far
+    int64_t refit_stats[3] = {0, 0, 0};    // rl_debug_refit_stats: k_refit_route launches through the LDS tile / from global memory, leaves that kept their old output
     int64_t arms[RL_ARM_COUNT_] = {};      // RL_ARR_LAUNCH_ARMS: launches per kernel variant, counted where the host picks one (the tests assert the variant a knob selects)
     // growth progress reported by the device (Ctx::progress): the host keeps at most knobs.step_ahead growth steps in flight and
     // stops enqueuing steps of a finished tree; 0 = enqueue all L-1 steps blindly
@@ -1020,3 +1021,4 @@ int rl_reset_timing(rl_trainer *t)
 #include "rl_shap.inc"       // the same as exact TreeSHAP values: k_model_shap runs every row through the recurrence of every leaf
 #include "rl_interact.inc"   // SHAP interaction values: k_model_interact runs that recurrence once per conditioned element, k_interact_finish makes the diagonal
 #include "rl_resume.inc"     // resume: rl_adopt_model_text replays a saved model's trees as this trainer's first rounds (k_replay_scores)
+#include "rl_refit.inc"      // refit: rl_refit_model_text keeps those trees' structure and recomputes their leaf values on this trainer's data (k_refit_route)

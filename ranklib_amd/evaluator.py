@@ -45,7 +45,7 @@ import numpy as np
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, RESUME_NOT_BAGS, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, RESUME_NOT_BAGS, REFIT_NOT_BAGS, java_double_str, java_round,
                        stable_desc_order)
 from .metric import DCGScorer, ERRScorer, MetricScorerFactory, score_lists
 
@@ -468,15 +468,16 @@ def common_flag(a, nxt, reader_only=False):
 def main(argv=None):
     try:
         return _main(argv)
-    finally:      # -resume / -checkpoint belong to this command line only: a later LambdaMART of the process starts from nothing again
+    finally:      # -resume / -checkpoint / -refit belong to this command line only: a later LambdaMART of the process starts from nothing again
         LambdaMART.resumeFrom, LambdaMART.checkpointFile, LambdaMART.checkpointEvery = None, None, 100
+        LambdaMART.refitFrom, LambdaMART.refitDecay = None, 0.0
 
 
 def _main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-resume model] [-checkpoint file [-every n]] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-resume model] [-checkpoint file [-every n]] [-refit model [-decay x]] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
               "(-load also reads RankNet, LambdaRank and ListNet models; several -load: the models of a -kcv run, model i for fold i of the file, "
               "or for the i-th -test file) | -test f [-idv out] | -test f -score s | -rank f -indri out (no model: the file's own order, or the order of the numbers in s) | "
@@ -489,7 +490,10 @@ def _main(argv=None):
               "-resume model, -checkpoint file [-every n] are rlhip extensions of a -train -ranker 6|0 run: -resume continues the run that wrote the model "
               "(its trees are this run's first rounds, -tree stays the total; from a -checkpoint file the result is the uninterrupted run's bit for bit, "
               "from a final -save model early stopping restarts at its best validation prefix); -checkpoint writes all trees so far to the file after "
-              "every n-th round (default 100), complete or not at all")
+              "every n-th round (default 100), complete or not at all | "
+              "-refit model [-decay x] is an rlhip extension of a -train -ranker 6|0 run: the model's trees keep their features and thresholds and get "
+              "new leaf values from the training file, stored as x * old + (1 - x) * new (x in [0, 1), default 0: the new values alone); -tree stays "
+              "the total: equal to the model's tree count the run only refits, larger it trains further behind the refit trees")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
     testFiles, savedModelFiles = [], []
@@ -499,7 +503,9 @@ def _main(argv=None):
     Evaluator.batch = True
     LambdaMART.fastLeaf = False                             # -fastleaf (rlhip extension)
     LambdaMART.resumeFrom, LambdaMART.checkpointFile, LambdaMART.checkpointEvery = None, None, 100      # -resume, -checkpoint, -every (rlhip extensions)
+    LambdaMART.refitFrom, LambdaMART.refitDecay = None, 0.0                                             # -refit, -decay (rlhip extensions)
     resumeFile, everyGiven = "", False
+    refitFile, decayGiven = "", None
     rankerType = 4                                          # the reference's default is Coordinate Ascent (:83)
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)
     ttSplit = tvSplit = 0.0
@@ -547,6 +553,8 @@ def _main(argv=None):
         elif a == "-seed": RFRanker.seed = FeatureHistogram.seed = CoorAscent.seed = int(nxt())     # rlhip extension: the Java draws are unseeded
         elif a == "-fastleaf": LambdaMART.fastLeaf = True   # rlhip extension: RL_FLAG_FAST_LEAF for -ranker 6 / 0 / 8 (leaf values within tolerance, not bit for bit)
         elif a == "-resume": resumeFile = nxt()             # rlhip extension: the saved model whose trees are this run's first rounds
+        elif a == "-refit": refitFile = nxt()               # rlhip extension: the saved model whose trees get new leaf values from this run's data
+        elif a == "-decay": decayGiven = float(nxt())       # rlhip extension: the share of the old leaf value a refit keeps
         elif a == "-checkpoint": LambdaMART.checkpointFile = nxt()      # rlhip extension: all trees so far, after every -every n-th round
         elif a == "-every":
             LambdaMART.checkpointEvery = int(nxt())
@@ -587,6 +595,27 @@ def _main(argv=None):
             cur.unknown()                                   # :369-371 (incl. the documented -silent)
     if not testMetric:
         testMetric = trainMetric                            # :379-381
+    if refitFile or decayGiven is not None:
+        if not refitFile:
+            raise RankLibError("rlhip: -decay x belongs to -refit model")
+        if decayGiven is not None and not (0.0 <= decayGiven < 1.0):       # (NaN fails both comparisons)
+            raise RankLibError("rlhip: -decay must be in [0, 1) (got %s): the share of the old leaf value a refit keeps" % decayGiven)
+        if not trainFile:
+            raise RankLibError("rlhip: -refit recomputes a model's leaf values on training data: it needs -train")
+        if rankerType == 8:
+            raise RankLibError(REFIT_NOT_BAGS)
+        if rankerType not in (0, 6):
+            raise RankLibError("rlhip: -refit is built for the tree trainers, -ranker 6 (LambdaMART) and -ranker 0 (MART), not for -ranker %d" % rankerType)
+        if foldCV != -1:
+            raise RankLibError("rlhip: -refit with -kcv: every fold is a run of its own, one model cannot be refitted into them all")
+        if resumeFile:
+            raise RankLibError("rlhip: -refit together with -resume: a model is either adopted as it is or refitted")
+        try:
+            with open(refitFile, encoding="ascii") as f:
+                LambdaMART.refitFrom = f.read()
+        except (OSError, UnicodeDecodeError) as ex:
+            raise RankLibError("rlhip: -refit %s cannot be read as a model text: %s" % (refitFile, ex))
+        LambdaMART.refitDecay = 0.0 if decayGiven is None else decayGiven
     if resumeFile or LambdaMART.checkpointFile or everyGiven:
         what = "-resume" if resumeFile else "-checkpoint" if LambdaMART.checkpointFile else "-every"
         if everyGiven and not LambdaMART.checkpointFile:

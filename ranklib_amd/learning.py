@@ -457,6 +457,8 @@ class FeatureHistogram:
 
 RESUME_NOT_BAGS = ("rlhip: -resume / -checkpoint continue one LambdaMART (-ranker 6) or MART (-ranker 0) run; the bags of Random Forests "
                    "(-ranker 8) are trainers of their own and are not built for it")
+REFIT_NOT_BAGS = ("rlhip: -refit recomputes the leaf values of one LambdaMART (-ranker 6) or MART (-ranker 0) model; the bags of Random Forests "
+                  "(-ranker 8) are trainers of their own and are not built for it")
 
 
 class LambdaMART(Ranker):
@@ -478,6 +480,11 @@ class LambdaMART(Ranker):
     resumeFrom = None
     checkpointFile = None
     checkpointEvery = 100
+    # -refit / -decay: the text of a saved model whose trees keep their structure and get new leaf values from this run's training data
+    # -- stored output = refitDecay * old + (1 - refitDecay) * new, in [0, 1); 0: the new values alone -- as this run's first rounds; nTrees stays the
+    # TOTAL: equal to the model's tree count the run only refits, larger it trains further behind the refit trees
+    refitFrom = None
+    refitDecay = 0.0
     _RANKER = "LAMBDAMART"
 
     def __init__(self, samples=None, features=None, scorer=None):
@@ -507,6 +514,11 @@ class LambdaMART(Ranker):
         if cls.resumeFrom is not None:
             self._resume_stop = t.adopt_model_text(cls.resumeFrom)
             self._resumed = t.num_trees()
+        if cls.refitFrom is not None:      # the refit rounds are printed and continued like adopted ones (learn)
+            if cls.resumeFrom is not None:
+                raise RankLibError("rlhip: refitFrom together with resumeFrom: a model is either adopted as it is or refitted")
+            self._resume_stop = t.refit_model_text(cls.refitFrom, cls.refitDecay)
+            self._resumed = t.num_trees()
         self._trainer = t
 
     def _logRound(self, m, tm, vm):
@@ -534,7 +546,7 @@ class LambdaMART(Ranker):
         else:
             self.printLogLn([7, 9], ["#iter", nm + "-T"])
         resumed = getattr(self, "_resumed", 0)
-        for m in range(resumed):      # the adopted rounds' lines, as the run that grew them printed them
+        for m in range(resumed):      # the adopted rounds' lines, as the run that grew them printed them (refit rounds: from rl_get_round_metrics too)
             self._logRound(m, *t.round_metrics(m))
         for m in range(resumed, 0 if getattr(self, "_resume_stop", False) else cls.nTrees):
             _, tm, vm, stop = t.boost_round(want_tree=False)
@@ -897,6 +909,8 @@ class RFRanker(Ranker):
         cls = type(self)
         if LambdaMART.resumeFrom is not None or LambdaMART.checkpointFile:
             raise RankLibError(RESUME_NOT_BAGS)
+        if LambdaMART.refitFrom is not None:
+            raise RankLibError(REFIT_NOT_BAGS)
         self.ensembles = [None] * cls.nBag
         LambdaMART.nTrees = cls.nTrees
         LambdaMART.nTreeLeaves = cls.nTreeLeaves
