@@ -875,6 +875,13 @@ int  rl_eval_lists(int32_t device, int32_t metric, int32_t k, double err_max, co
 /* debug (tools/eval_bench.py): ms between two device events around the kernel launches of this thread's last rl_eval_lists call (the
  * uploads before them and the copies back after them are not in it) */
 int  rl_debug_eval_times(double *kernel_ms);
+/* debug (tests): the length classes of rl_eval_lists as this library was built.  edges [cap >= 5] receives the longest list of the tiny,
+ * the wave, the block (counting) and the in-LDS sort class and then the tile length of the multi-block sort class, which takes every
+ * longer list; *n = 5.  Needs no device.  RL_ERR_INVALID: a null pointer or cap < 5. */
+int  rl_debug_eval_classes(int32_t *edges, int32_t cap, int32_t *n);
+/* debug (tests): lists_per_class [cap >= 5] receives how many lists this thread's last rl_eval_lists call ranked in the tiny, wave, block,
+ * in-LDS sort and multi-block sort class (zeros before the first call).  Needs no device.  RL_ERR_INVALID: a null pointer or cap < 5. */
+int  rl_debug_eval_path(int64_t *lists_per_class, int32_t cap);
 
 /* ---- feature normalisation: -norm sum | zscore | linear over every list of a file in one pass (features/SumNormalizor.java,
  * ZScoreNormalizor.java, LinearNormalizer.java) -------------------------------------------------------------------------

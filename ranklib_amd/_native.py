@@ -142,7 +142,7 @@ ABI_SYMBOLS = [
     "rl_rn_set_weights", "rl_rn_learn", "rl_rn_get_weights", "rl_rn_scores", "rl_rn_trace", "rl_rn_debug_doc_scores", "rl_rn_debug_times",
     "rl_rn_set_lambdarank",
     "rl_perm_test", "rl_debug_perm_calib",
-    "rl_eval_lists", "rl_debug_eval_times",
+    "rl_eval_lists", "rl_debug_eval_times", "rl_debug_eval_classes", "rl_debug_eval_path",
     "rl_normalize_lists", "rl_debug_normalize_times",
     "rl_model_predict_stages", "rl_model_eval_stages", "rl_debug_stage_times",
     "rl_model_predict_permuted", "rl_model_eval_permuted", "rl_debug_permuted_times",
@@ -294,6 +294,9 @@ def lib():
     if hasattr(L, "rl_eval_lists"):     # (A/B builds of older sources rank and score on the host)
         L.rl_eval_lists.argtypes = [i32, i32, i32, C.c_double, vp, vp, i64, vp, i32, vp, vp, vp, vp, vp, vp]
         L.rl_debug_eval_times.argtypes = [C.POINTER(C.c_double)]
+    if hasattr(L, "rl_debug_eval_path"):    # (A/B builds of older sources count every list's rank)
+        L.rl_debug_eval_classes.argtypes = [vp, i32, C.POINTER(i32)]
+        L.rl_debug_eval_path.argtypes = [vp, i32]
     if hasattr(L, "rl_normalize_lists"):    # (A/B builds of older sources normalise on the host)
         L.rl_normalize_lists.argtypes = [i32, i32, vp, i64, i32, vp, vp, i32, vp, i32, i32]
         L.rl_debug_normalize_times.argtypes = [C.POINTER(C.c_double)]
@@ -1433,6 +1436,24 @@ def eval_kernel_ms():
     ms = C.c_double(0)
     check(lib().rl_debug_eval_times(C.byref(ms)))
     return ms.value
+
+
+EVAL_CLASSES = ("tiny", "wave", "block", "sort_lds", "sort_multi")
+
+
+def eval_classes():
+    """rl_debug_eval_classes: {"tiny", "wave", "block", "sort_lds": the longest list of the class; "tile": the records one block of the
+    multi-block sort class sorts} of rl_eval_lists as the library was built.  Needs no device"""
+    e, n = np.zeros(8, np.int32), C.c_int32(0)
+    check(lib().rl_debug_eval_classes(e.ctypes.data, int(e.size), C.byref(n)))
+    return dict(zip(EVAL_CLASSES[:4] + ("tile",), (int(v) for v in e[:n.value])))
+
+
+def eval_path():
+    """rl_debug_eval_path: {class of EVAL_CLASSES: lists this thread's last eval_lists call ranked in it}"""
+    c = np.zeros(len(EVAL_CLASSES), np.int64)
+    check(lib().rl_debug_eval_path(c.ctypes.data, int(c.size)))
+    return dict(zip(EVAL_CLASSES, (int(v) for v in c)))
 
 
 def stage_times():

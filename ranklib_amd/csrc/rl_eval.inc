@@ -9,8 +9,9 @@
 //                         ranklib_amd/metric.py statement for statement (ev_metric).  Length classes, this kernel's own:
 //                           <= kEvTiny  (16)    G = 16, 16 lists per block
 //                           <= kEvWave  (256)   one wavefront per list, 4 lists per block
-//                           <= kEvBlock (6144)  one block per list: 6144 x (8 B score + 4 B label) = 72 KiB of LDS, two blocks per CU
-//                           longer              one block per list, scores read from global memory, ranked labels in global scratch
+//                           <= kEvSort          one block per list: kEvSort x (8 B score + 4 B label) of LDS
+//                           longer              not counted: sorted, rl_eval_sort.inc (the count is O(n^2); the sweep of DESIGN.md 19.4
+//                                               places kEvSort where the sort overtakes it)
 //                         Nothing is summed on the device: MetricScorer.score(List) and Evaluator.test add the lists' values serially on
 //                         the host.
 //
@@ -20,9 +21,10 @@
 
 namespace rl {
 
-// kEvTiny / kEvWave / kEvBlock, EvArgs and ev_metric (the scorers): rl_eval_dev.h, shared with k_stage_eval (rl_stage.inc)
+// kEvTiny / kEvWave / kEvSort, EvArgs and ev_metric (the scorers): rl_eval_dev.h, shared with k_stage_eval (rl_stage.inc)
 
-// one list by one group of G threads; s_sc / s_lab: the group's LDS (CAP > 0 entries each)
+// one list by one group of G threads; s_sc / s_lab: the group's LDS (CAP > 0 entries each; CAP == 0, scores and ranked labels in global
+// memory, is no longer launched)
 template <int G, int CAP>
 __device__ void ev_group(const EvArgs &a, int slot, int tid, double *s_sc, float *s_lab)
 {
@@ -61,6 +63,7 @@ __global__ __launch_bounds__(kThreads) void k_eval_lists(const EvArgs a)
 }
 
 static thread_local double g_ev_kernel_ms = 0.0;     // the last rl_eval_lists call of this thread: its launches between two device events
+static thread_local int64_t g_ev_path[kEvClasses] = {0, 0, 0, 0, 0};      // ... and the lists it ranked in each class
 
 }  // namespace rl
 
@@ -76,16 +79,14 @@ int rl_eval_lists(int32_t device, int32_t metric, int32_t k, double err_max, con
                           err);
     if (rc) return fail(rc, err);
     if ((rc = open_device(device, true))) return rc;
-    std::vector<int32_t> lists[4];
-    for (int32_t q = 0; q < n_lists; q++) {
-        const int n = qoff[q + 1] - qoff[q];
-        lists[n <= kEvTiny ? 0 : n <= kEvWave ? 1 : n <= kEvBlock ? 2 : 3].push_back(q);
-    }
+    EvSplit split;
+    eval_split(qoff, n_lists, kEvEdges, split);
+    const std::vector<int32_t> *lists = split.lists;
     DevPool buf;
     EvArgs a;
     memset(&a, 0, sizeof(a));
     double *d_sc = nullptr, *d_ideal = nullptr, *d_disc = nullptr, *d_out = nullptr; float *d_lab = nullptr;
-    int32_t *d_qoff = nullptr, *d_rd = nullptr, *d_pos = nullptr, *d_qlist[4] = {nullptr, nullptr, nullptr, nullptr};
+    int32_t *d_qoff = nullptr, *d_rd = nullptr, *d_pos = nullptr, *d_qlist[3] = {nullptr, nullptr, nullptr};
     RL_HIP(buf.alloc(&d_sc, (size_t)n_docs));
     RL_HIP(buf.alloc(&d_lab, (size_t)n_docs));
     RL_HIP(buf.alloc(&d_qoff, (size_t)n_lists + 1));
@@ -102,31 +103,32 @@ int rl_eval_lists(int32_t device, int32_t metric, int32_t k, double err_max, con
         RL_HIP(hipMemcpy(d_rd, rel_doc_count, (size_t)n_lists * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     if (out_pos) RL_HIP(buf.alloc(&d_pos, (size_t)n_docs));
-    if (!lists[3].empty()) RL_HIP(buf.alloc(&a.glab, (size_t)n_docs));
-    for (int c = 0; c < 4; c++) {
+    if (!lists[kEvClsSortMulti].empty()) RL_HIP(buf.alloc(&a.glab, (size_t)n_docs));
+    for (int c = 0; c <= kEvClsBlock; c++) {
         if (lists[c].empty()) continue;
         RL_HIP(buf.alloc(&d_qlist[c], lists[c].size()));
         RL_HIP(hipMemcpy(d_qlist[c], lists[c].data(), lists[c].size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     a.sc = d_sc; a.labels = d_lab; a.qoff = d_qoff; a.ideal = d_ideal; a.rd_ext = d_rd; a.disc = d_disc; a.out = d_out; a.pos = d_pos;
     a.metric = metric; a.k = k; a.err_max = err_max;
-    static const int G[4] = {kEvTiny, kWave, kThreads, kThreads};
+    static const int G[3] = {kEvTiny, kWave, kThreads};
     hipEvent_t e0 = nullptr, e1 = nullptr;
     struct EvGuard { hipEvent_t &a, &b; ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } guard{e0, e1};
     RL_HIP(hipEventCreate(&e0));
     RL_HIP(hipEventCreate(&e1));
     RL_HIP(hipEventRecord(e0, 0));
-    for (int c = 0; c < 4; c++) {
+    for (int c = 0; c <= kEvClsBlock; c++) {
         if (lists[c].empty()) continue;
         a.qlist = d_qlist[c]; a.nq = (int32_t)lists[c].size();
         const int gpb = kThreads / G[c];
         const dim3 grid((unsigned)((a.nq + gpb - 1) / gpb)), block(kThreads);
         if (c == 0) hipLaunchKernelGGL((k_eval_lists<kEvTiny, kEvTiny>), grid, block, 0, 0, a);
         else if (c == 1) hipLaunchKernelGGL((k_eval_lists<kWave, kEvWave>), grid, block, 0, 0, a);
-        else if (c == 2) hipLaunchKernelGGL((k_eval_lists<kThreads, kEvBlock>), grid, block, 0, 0, a);
-        else hipLaunchKernelGGL((k_eval_lists<kThreads, 0>), grid, block, 0, 0, a);
+        else hipLaunchKernelGGL((k_eval_lists<kThreads, kEvSort>), grid, block, 0, 0, a);
         RL_HIP(hipGetLastError());
     }
+    if (!lists[kEvClsSortLds].empty() && (rc = ev_sort_lds(a, split, qoff, buf))) return rc;
+    if (!lists[kEvClsSortMulti].empty() && (rc = ev_sort_multi(a, split, buf))) return rc;
     RL_HIP(hipEventRecord(e1, 0));
     RL_HIP(hipMemcpy(out_metric, d_out, (size_t)n_lists * sizeof(double), hipMemcpyDeviceToHost));
     if (out_pos) RL_HIP(hipMemcpy(out_pos, d_pos, (size_t)n_docs * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -134,6 +136,7 @@ int rl_eval_lists(int32_t device, int32_t metric, int32_t k, double err_max, con
     float ms = 0.f;
     RL_HIP(hipEventElapsedTime(&ms, e0, e1));
     g_ev_kernel_ms = (double)ms;
+    for (int c = 0; c < kEvClasses; c++) g_ev_path[c] = (int64_t)lists[c].size();
     return RL_OK;
 }
 
@@ -141,6 +144,24 @@ int rl_debug_eval_times(double *kernel_ms)
 {
     if (!kernel_ms) return fail(RL_ERR_INVALID, "rl_debug_eval_times: null argument");
     *kernel_ms = g_ev_kernel_ms;
+    return RL_OK;
+}
+
+int rl_debug_eval_classes(int32_t *edges, int32_t cap, int32_t *n)
+{
+    const int32_t v[5] = {kEvTiny, kEvWave, kEvSort, kEvSortLds, kEvSortTile};
+    const std::string err = !n ? std::string("null argument") : eval_debug_check(edges, cap, 5);
+    if (!err.empty()) return fail(RL_ERR_INVALID, "rl_debug_eval_classes: " + err);
+    std::copy(v, v + 5, edges);
+    *n = 5;
+    return RL_OK;
+}
+
+int rl_debug_eval_path(int64_t *lists_per_class, int32_t cap)
+{
+    const std::string err = eval_debug_check(lists_per_class, cap, kEvClasses);
+    if (!err.empty()) return fail(RL_ERR_INVALID, "rl_debug_eval_path: " + err);
+    std::copy(g_ev_path, g_ev_path + kEvClasses, lists_per_class);
     return RL_OK;
 }
 

@@ -16,6 +16,9 @@ __device__ __forceinline__ void ca_sync()
 }
 
 constexpr int kEvTiny = 16, kEvWave = 256, kEvBlock = 6144;
+// rl_eval_lists alone (rl_eval.inc, rl_eval_sort.inc): a list longer than kEvSort is ranked by a sort, up to kEvSortLds inside one
+// block's LDS.  kEvSort is placed by the sweep of DESIGN.md 19.4: the smallest swept length from which the sort is not slower.
+constexpr int kEvSort = 512, kEvSortLds = 13312;
 
 struct EvArgs {
     const double *sc; const float *labels; const int32_t *qoff; const double *ideal; const int32_t *rd_ext; const double *disc;

@@ -53,6 +53,52 @@ inline int eval_prepare_lists(const char *who, int32_t metric, int32_t k, double
     return RL_OK;
 }
 
+// ---- the length classes of rl_eval_lists and the tables of its sort classes (rl_eval_sort.inc), sized on the host ---------------------
+enum { kEvClsTiny = 0, kEvClsWave, kEvClsBlock, kEvClsSortLds, kEvClsSortMulti, kEvClasses };
+
+// tiny < wave < sort < sort_lds: the longest list of the tiny, wave, block (counting) and in-LDS sort class; tile: the records one block
+// of the multi-block class sorts; piece: the records one block merges, a divisor of tile
+struct EvEdges { int32_t tiny, wave, sort, sort_lds, tile, piece; };
+
+struct EvSplit {
+    std::vector<int32_t> lists[kEvClasses];      // the lists of each class, in file order
+    // multi-block class, one entry per list and a last one: where its records start in the scratch, its first tile, its first piece
+    std::vector<int32_t> moff, toff, poff;
+    int32_t passes = 0;                          // merge launches: ceil(log2(most tiles of a list))
+};
+
+inline int eval_class_of(int32_t n, const EvEdges &e)
+{
+    return n <= e.tiny ? kEvClsTiny : n <= e.wave ? kEvClsWave : n <= e.sort ? kEvClsBlock : n <= e.sort_lds ? kEvClsSortLds : kEvClsSortMulti;
+}
+
+// qoff has passed check_lists: it starts at 0, increases strictly and ends below 2^31 - 4096, so every table stays inside int32
+inline void eval_split(const int32_t *qoff, int32_t n_lists, const EvEdges &e, EvSplit &s)
+{
+    s.moff.assign(1, 0); s.toff.assign(1, 0); s.poff.assign(1, 0);
+    int32_t most = 1;
+    for (int32_t q = 0; q < n_lists; q++) {
+        const int32_t n = qoff[q + 1] - qoff[q];
+        const int c = eval_class_of(n, e);
+        s.lists[c].push_back(q);
+        if (c != kEvClsSortMulti) continue;
+        const int32_t tiles = (n - 1) / e.tile + 1;
+        s.moff.push_back(s.moff.back() + n);
+        s.toff.push_back(s.toff.back() + tiles);
+        s.poff.push_back(s.poff.back() + (n - 1) / e.piece + 1);
+        most = std::max(most, tiles);
+    }
+    for (s.passes = 0; ((int64_t)1 << s.passes) < most; s.passes++) {}
+}
+
+// rl_debug_eval_classes / rl_debug_eval_path: the argument rules.  Empty, or the message (without the caller's name).
+inline std::string eval_debug_check(const void *out, int32_t cap, int32_t need)
+{
+    if (!out) return "null argument";
+    if (cap < need) return "cap " + std::to_string(cap) + " is below the " + std::to_string(need) + " entries written";
+    return std::string();
+}
+
 inline int eval_prepare(int32_t metric, int32_t k, double err_max, const double *scores, const float *labels, int64_t n_docs,
                         const int32_t *qoff, int32_t n_lists, const int32_t *qkey, const double *ideal_dcg, const int32_t *rel_doc_count,
                         const double *out_metric, std::vector<double> &ideal, std::vector<double> &disc, std::string &err)

@@ -589,8 +589,8 @@ class LambdaMART(Ranker):
         bit for bit.  One _native.Model.eval_stages call per chunk of whole lists whose rows stay under EVAL_ROW_BYTES; what the scorer
         holds is resolved per list id exactly as score_lists does it, and the ideal DCGs the calls computed are written back into
         idealGains.  A (stage, list) cell whose scores hold a NaN is filled on the host: predict_stages on that list's rows, then the
-        per-list path of score_lists.  Lists longer than metric.EVAL_HOST_LEN stay on the device (both paths give the same bits; the
-        host's would cost one sort per stage)."""
+        per-list path of score_lists.  metric.EVAL_HOST_LEN is not consulted: a list of any length stays on the device, ranked by
+        k_stage_eval's count (rl_eval_lists' sort, DESIGN.md 19.5, is not used here)."""
         st = np.arange(1, self._model.num_trees() + 1, dtype=np.int32) if stages is None else np.ascontiguousarray(stages, dtype=np.int32)
         name = metric_name(scorer)
         out = np.zeros((st.size, len(samples)), np.float64)

@@ -248,7 +248,7 @@ def _f32(x):
 TRAINABLE = ("NDCG", "DCG", "MAP", "ERR")     # metrics whose swapChange every GPU lambda kernel implements (LambdaRank's included)
 TREE_TRAINABLE = TRAINABLE + ("P", "RR")      # ... and those of the tree trainer's lambda kernels (LambdaMART, MART, the bags of Random Forests)
 
-EVAL_HOST_LEN = 2048                  # a list longer than this is ranked and scored on the host (the counting rank is O(n^2); measured: DESIGN.md 19)
+EVAL_HOST_LEN = 2 ** 31 - 1           # a list longer than this is ranked and scored on the host: none is, since long lists are sorted on the device and the host wins at no swept length up to 131 072 documents (measured: DESIGN.md 19.4); a test patches it to keep that path reached
 
 
 # ---- what a scorer object holds, resolved per list id ---------------------------------------------------------------------
@@ -291,7 +291,7 @@ def score_lists(scorer, samples, flat_scores, want_pos=False):
     """scorer.score(ranked list) of every list of samples, all lists in one _native.eval_lists call: flat_scores [n_docs] holds the
     model's scores, list after list.  Returns (f64 value per list, int32 position of every document in its list's ranking or None).
     What the scorer object holds is resolved per list id (held_judgments: idealGains for NDCG, relDocCount for MAP; k, ERRScorer.MAX)
-    and the ideal DCGs the call computed are written back into idealGains (keep_ideals).  A list whose scores hold a NaN, or one longer than EVAL_HOST_LEN, takes the per-list host path
+    and the ideal DCGs the call computed are written back into idealGains (keep_ideals).  A list whose scores hold a NaN, or one longer than EVAL_HOST_LEN (none, as the constant stands), takes the per-list host path
     (stable_desc_order + scorer.score) in its place."""
     from .learning import RankList, stable_desc_order
     sc = np.ascontiguousarray(flat_scores, dtype=np.float64)

@@ -15,10 +15,13 @@ One JSON line per measurement.
       Both write an -idv file; the tool stops if the two differ by a byte.  The ranked lists are built in memory from the synthetic arrays
       and handed to the flow in place of the LETOR reader (the same objects for both; parsing a file is not what differs between them).
       Best of --repeat-flow runs each, after one warm-up run of the batch path.
-  "sweep": one list of growing length, eval_lists (NDCG@10) against the host's stable_desc_order + scorer.score, to place
-      metric.EVAL_HOST_LEN.  One block ranks one list, so inside a file's call a long list costs its kernel_ms while the other lists
-      run beside it, and on the host path it costs host_ms: crossover is the first length from which host_ms stays below kernel_ms.
-      (call_ms of a lone list carries the call's fixed cost, uploads and copies of about 0.15 ms, which a file pays once.)
+  "sweep": one list of growing length, eval_lists (NDCG@10) against the host's stable_desc_order + scorer.score, to place kEvSort
+      (rl_eval_dev.h) and metric.EVAL_HOST_LEN.  ranked_in names the length class that ran (rl_debug_eval_path).  The sweep of a build
+      of the parent commit (--build parent) is the counting row: kEvSort is the smallest swept length from which this build's
+      kernel_ms stays at or below that row.  crossover is the first length from which host_ms stays below kernel_ms + 0.12 ms (the
+      call's share of a lone list); without one, no list needs the host path.
+  "map_split": at the longest swept length, kernel_ms of DCG@1 (the ranking and one label) and of MAP (the ranking and the whole
+      list's serial chain on one lane): their difference is the chain.
 Clocks are whatever the device runs at: nothing here assumes a frequency."""
 import argparse
 import json
@@ -112,11 +115,35 @@ def run_shape(name, a, tmp):
                           batch_ms=round(batch_ms, 2), ratio=round(lists_ms / batch_ms, 2), idv_bytes=len(idv[True]), idv_equal=True)), flush=True)
 
 
+CALL_SHARE_MS = 0.12                  # a lone list's call beyond its kernels: what the device row adds when EVAL_HOST_LEN is placed
+
+
+def sweep_lengths(a):
+    """--sweep, and both neighbours of the in-LDS sort class's edge where the library has one (a parent build has none)"""
+    lens = {int(v) for v in a.sweep.split(",")}
+    if hasattr(N.lib(), "rl_debug_eval_classes"):
+        lens |= {N.eval_classes()["sort_lds"] - 1, N.eval_classes()["sort_lds"] + 1}
+    return sorted(lens)
+
+
+def map_split(n, repeat):
+    """where a long list's time goes: DCG@1 walks one ranked label, MAP the whole list on one lane, and both rank alike"""
+    rng = np.random.default_rng(8)
+    sc, lab, qoff = rng.standard_normal(n).round(2), rng.integers(0, 5, n).astype(np.float32), np.array([0, n], np.int32)
+    ms = {}
+    for m, k in (("DCG", 1), ("MAP", 0)):
+        N.eval_lists(sc, lab, qoff, m, k)
+        ms[m] = min((N.eval_lists(sc, lab, qoff, m, k), N.eval_kernel_ms())[1] for _ in range(repeat))
+    print(json.dumps(dict(what="map_split", length=n, rank_ms=round(ms["DCG"], 4), map_ms=round(ms["MAP"], 4),
+                          chain_ms=round(ms["MAP"] - ms["DCG"], 4))), flush=True)
+
+
 def sweep(a):
     rng = np.random.default_rng(7)
     scorer = M.NDCGScorer(10)
     crossover, rows = None, []
-    for n in [int(v) for v in a.sweep.split(",")]:
+    has_path = hasattr(N.lib(), "rl_debug_eval_path")
+    for n in sweep_lengths(a):
         sc = rng.standard_normal(n).round(2)                                # ties included
         lab = rng.integers(0, 5, n).astype(np.float32)
         rl = RankList([DataPoint.from_parsed(float(l), "1", "", np.zeros(1, np.float32)) for l in lab])
@@ -132,13 +159,16 @@ def sweep(a):
         if np.float64(got[0][0]).view(np.int64) != np.float64(want).view(np.int64):
             raise SystemExit("sweep: kernel and host disagree at length %d" % n)
         rows.append((n, min(kms), host_ms))
-        print(json.dumps(dict(what="sweep", length=n, call_ms=round(call_ms, 4), kernel_ms=round(min(kms), 4), host_ms=round(host_ms, 4))), flush=True)
+        ran = [c for c, v in N.eval_path().items() if v] if has_path else ["count"]
+        print(json.dumps(dict(what="sweep", build=a.build, length=n, ranked_in=ran[0], call_ms=round(call_ms, 4), kernel_ms=round(min(kms), 4),
+                              host_ms=round(host_ms, 4))), flush=True)
     for n, kernel_ms, host_ms in reversed(rows):
-        if host_ms >= kernel_ms:
+        if host_ms >= kernel_ms + CALL_SHARE_MS:
             break
         crossover = n
-    print(json.dumps(dict(what="sweep_summary", eval_host_len=M.EVAL_HOST_LEN,
+    print(json.dumps(dict(what="sweep_summary", build=a.build, eval_host_len=M.EVAL_HOST_LEN, call_share_ms=CALL_SHARE_MS,
                           crossover=crossover if crossover is not None else "none up to the longest length")), flush=True)
+    map_split(rows[-1][0], a.repeat)
 
 
 def main():
@@ -147,7 +177,9 @@ def main():
     ap.add_argument("--metric", default="NDCG@10", help="the flows' test metric")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--repeat-flow", type=int, default=2)
-    ap.add_argument("--sweep", default="256,1024,1536,2048,3072,4096,6144,6145,8192,16384,32768,65536")
+    ap.add_argument("--sweep", default="256,512,768,1024,1536,2048,3072,4096,6144,6145,8192,16384,32768,65536,131072")
+    ap.add_argument("--build", default="tree", help="a name for the library under test, copied into every sweep line (the counting row "
+                    "of DESIGN.md 19.4 is this tool's sweep run from a build of the parent commit)")
     ap.add_argument("--hbm-tbs", type=float, default=8.0, help="HBM peak in TB/s the byte floor is taken against (MI355X datasheet: 8)")
     a = ap.parse_args()
     import logging
