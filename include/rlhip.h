@@ -1097,6 +1097,51 @@ enum { RL_MODEL_PATH_INTERACT = 8 };
 int  rl_debug_interact_times(double *walk_ms, double *shap_ms);
 int  rl_debug_interact_passes(int32_t *passes);
 
+/* ---- interventional TreeSHAP of a tree model against background rows, one pass over a file ---------------------------
+ * What shap.TreeExplainer(model, data) computes by default: the contributions explain a row's score RELATIVE TO A REFERENCE SET, the
+ * background rows BG [n_background][bg_stride], B = n_background <= 16 384.  No cover is needed or read.  The WALK (v <= thr goes left;
+ * anything else, a NaN included, goes right), the row rule v = (f < stride) ? row[f] : 0 -- for the documents under row_stride, for the
+ * background under bg_stride --, W = (double)w_t, the slots (columns[0 .. C-1], rest = C, bias = C + 1, columns == NULL), the ELEMENTS
+ * e = 1 .. d of a leaf (the distinct features of its root-to-leaf path in order of first appearance, each with its slot and its
+ * conditions) and the limit of 32 distinct features on a path are those of the sections above.
+ * MEANING: for a document x, a background row z, a tree t and a set S of feature ids, v_S is (double)out of the leaf of t reached by the
+ * hybrid row that has x's value for f in S and z's value otherwise.  phi_i(x; z, t) is feature i's Shapley value in the game S -> v_S over
+ * the features the tree splits on.  The contribution of i is (1/B) sum over z, sum over t of W phi_i; the bias is (1/B) sum over z, sum
+ * over t of W (double)out of z's leaf in t.  A row's slots sum to rl_model_predict_leaf_sums' value up to f64 rounding.
+ * COMPUTED FORM.  For a (row, leaf) with elements e = 1 .. d: bit e of xm is set iff the row's own decision is the path's direction at
+ * every split of element e; zm is the same for a background row; full = 2^d - 1.  A background row MEETS the leaf iff (xm | zm) == full;
+ * then a = popcount(xm & ~zm), b = popcount(~xm & zm).  TABLE: T[p][q] = 1.0 / (double)(p C(p+q, p)) for 1 <= p, 0 <= q, p + q <= 32; the
+ * denominator is an exact integer, the quotient one rounded f64 division.  acc[0 .. C] = +0.0; for every tree in order and every leaf
+ * in the pre-order of the model text:
+ *     s_e = +0.0, touched_e = 0 for all e
+ *     for z = 0 .. B-1 in order, if z meets the leaf and a + b > 0, for every e:
+ *         bit e in xm & ~zm:   s_e = s_e + T[a][b];  touched_e = 1
+ *         bit e in ~xm & zm:   s_e = s_e - T[b][a];  touched_e = 1
+ *     for e = 1 .. d in order, if touched_e:   acc[slot_e] = acc[slot_e] + ((s_e * (double)out_leaf) * W)
+ * and after the last tree every slot 0 .. C is acc / (double)B.  (Every s_e is a chain of its own over z ascending, so the order among
+ * the elements inside one z changes no bit.)  BIAS, made once per call and written with the same bits to every row: per tree m_t is the
+ * f64 chain from +0.0 over z ascending of (double)out at z's leaf; bias = bias + m_t * W in tree order from +0.0; at the end
+ * bias / (double)B.  Every operation rounded, no FMA.  A single-leaf tree adds to bias only; a document equal to a background row
+ * contributes nothing through that row; a requested id the model never splits on gets +0.0, and rest is exactly +0.0 under columns == NULL.
+ * X, BG, columns and out are HOST pointers.  The background's masks zm[leaf][z] are made once per call and chunk of trees: the trees
+ * go in chunks, in order, whose masks and leaf indices -- 4 bytes per (leaf, background row), the rows of the buffer padded to a multiple
+ * of four, and 4 per (tree, background row) -- stay within scratch_bytes (0 = 256 MiB), one tree at least; the documents go in chunks
+ * as rl_model_predict_contribs', within scratch_bytes again.  Between tree chunks a slot's chain travels through out, so the result does
+ * not depend on either chunking, nor on the grid, the block width or the number of column passes (rl_debug_interv_passes).
+ * RL_ERR_INVALID: the cases of rl_model_predict_contribs, the message naming this entry point; a null BG; n_background < 1;
+ * bg_stride < 1.  RL_ERR_UNSUPPORTED, before the device is touched: more than 2^31 rows per call; n_background > 16 384; a path of more
+ * than 32 distinct features, the message naming tree, leaf and node.  Never RL_ERR_STATE: a model without covers is served.  n_docs == 0
+ * is legal and launches nothing.  rl_model_debug_path reports RL_MODEL_PATH_INTERV afterwards. */
+int  rl_model_predict_shap_background(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const float *BG,
+                                      int32_t n_background, int32_t bg_stride, const int32_t *columns, int32_t n_columns,
+                                      int64_t scratch_bytes, double *out);
+enum { RL_MODEL_PATH_INTERV = 9 };
+/* debug (tools/interv_bench.py): ms between device events around the k_interv_masks and k_interv_bias launches, and around the
+ * k_model_interv launches (with the copies that carry a chain from one tree chunk to the next), of this thread's last
+ * rl_model_predict_shap_background call, summed over the chunks; and the column passes of that call */
+int  rl_debug_interv_times(double *mask_ms, double *walk_ms);
+int  rl_debug_interv_passes(int32_t *passes);
+
 /* ---- partial dependence and ICE curves of a tree model, one pass over a file -------------------------------------------
  * How the score moves as one feature moves.  columns[0 .. C-1] are feature ids, each >= 0, in any order, repeats allowed; grid_off
  * [C + 1] is a CSR offset array, grid_off[0] == 0, strictly increasing; grid [grid_off[C]] holds f32 grid values.  CELL j, grid_off[c] <=

@@ -152,6 +152,7 @@ ABI_SYMBOLS = [
     "rl_refit_model_text", "rl_debug_refit_stats",
     "rl_model_predict_partial", "rl_debug_partial_times",
     "rl_model_predict_interactions", "rl_debug_interact_times", "rl_debug_interact_passes",
+    "rl_model_predict_shap_background", "rl_debug_interv_times", "rl_debug_interv_passes",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -333,6 +334,10 @@ def lib():
         L.rl_model_predict_interactions.argtypes = [vp, vp, i64, i32, vp, i32, i64, vp]
         L.rl_debug_interact_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_debug_interact_passes.argtypes = [C.POINTER(i32)]
+    if hasattr(L, "rl_model_predict_shap_background"):  # (A/B builds of older sources have path-dependent TreeSHAP only)
+        L.rl_model_predict_shap_background.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, i32, i64, vp]
+        L.rl_debug_interv_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.rl_debug_interv_passes.argtypes = [C.POINTER(i32)]
     _lib = L
     return L
 
@@ -749,6 +754,7 @@ MODEL_PATH_COVER, MODEL_PATH_CONTRIBS = 4, 5      # rl_model_cover (k_model_cove
 MODEL_PATH_SHAP = 6                               # rl_model_predict_shap (k_model_shap)
 MODEL_PATH_PARTIAL = 7                            # rl_model_predict_partial (k_model_partial_scores, k_partial_reduce)
 MODEL_PATH_INTERACT = 8                           # rl_model_predict_interactions (k_model_shap, k_model_interact, k_interact_finish)
+MODEL_PATH_INTERV = 9                             # rl_model_predict_shap_background (k_interv_masks, k_interv_bias, k_model_interv)
 PARTIAL_BATCH = 16                                # RL_PARTIAL_BATCH (rlhip.h): cells of one column k_model_partial_scores takes per document at a time
 PARTIAL_SUM_BLOCK = 256                           # RL_PARTIAL_SUM_BLOCK (rlhip.h): the documents of one partial sum, part of the definition
 
@@ -954,7 +960,21 @@ class Model:
             raise RankLibError("rlhip: this librlhip.so has no interaction values (rl_model_predict_interactions)")
         return self._predict_slots("rl_model_predict_interactions", rows, columns, scratch_bytes, square=True)
 
-    def _predict_slots(self, entry, rows, columns, scratch_bytes, square=False):
+    def predict_shap_background(self, rows, background, columns=None, scratch_bytes=0):
+        """rl_model_predict_shap_background: predict_contribs' layout with interventional TreeSHAP values, what
+        shap.TreeExplainer(model, data) computes: per background row the Shapley values of the game in which a feature is either the
+        document's or the background row's, averaged over the background [n_background][bg_stride] (16 384 rows at most).  The bias is
+        the background's mean f64 leaf sum, so a row's other columns say how it differs from that reference set.  Needs no cover()."""
+        if not hasattr(lib(), "rl_model_predict_shap_background"):
+            raise RankLibError("rlhip: this librlhip.so has no interventional contributions (rl_model_predict_shap_background)")
+        bg = np.ascontiguousarray(background, dtype=np.float32)
+        if bg.ndim != 2:
+            raise RankLibError("rlhip: feature contributions take background rows [n_background][bg_stride]")
+        bbuf = bg if bg.size else np.zeros(1, np.float32)                      # (no rows: still a pointer that is not null)
+        return self._predict_slots("rl_model_predict_shap_background", rows, columns, scratch_bytes,
+                                   background=(bbuf.ctypes.data, bg.shape[0], bg.shape[1]))
+
+    def _predict_slots(self, entry, rows, columns, scratch_bytes, square=False, background=()):
         L, rows, buf = self._contrib_rows(rows)
         if columns is None:
             ids, cols, nc = [int(f) for f in self.features()], None, 0
@@ -967,8 +987,8 @@ class Model:
                 cols = np.zeros(1, np.int32)          # (an empty list is refused by the library, by name: it must not arrive as NULL)
         out = np.zeros((rows.shape[0],) + (len(ids) + 2,) * (2 if square else 1), np.float64)
         obuf = out if out.size else np.zeros(1, np.float64)
-        check(getattr(L, entry)(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], None if cols is None else cols.ctypes.data, nc,
-                                int(scratch_bytes), obuf.ctypes.data))
+        check(getattr(L, entry)(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], *background, None if cols is None else cols.ctypes.data,
+                                nc, int(scratch_bytes), obuf.ctypes.data))
         return out, ids
 
     def leaf_sums(self, rows):
@@ -1502,6 +1522,20 @@ def interact_passes():
     """rl_debug_interact_passes: the column passes k_model_interact took in this thread's last predict_interactions call"""
     p = C.c_int32(0)
     check(lib().rl_debug_interact_passes(C.byref(p)))
+    return p.value
+
+
+def interv_times():
+    """rl_debug_interv_times: (mask ms, walk ms) of this thread's last predict_shap_background call, between device events"""
+    k, w = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_interv_times(C.byref(k), C.byref(w)))
+    return k.value, w.value
+
+
+def interv_passes():
+    """rl_debug_interv_passes: the column passes of this thread's last predict_shap_background call"""
+    p = C.c_int32(0)
+    check(lib().rl_debug_interv_passes(C.byref(p)))
     return p.value
 
 

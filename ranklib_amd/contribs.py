@@ -19,6 +19,13 @@ rounding of Ensemble.eval's chain -- not its bits.
                          by the ids (pairs with `rest` are printed, not written).  Every sum over the documents is one serial f64 chain
                          in file order, carried from chunk to chunk, so it does not depend on the chunking; each is divided once.
                          Per-document matrices: LambdaMART.interactions.
+  -interventional        interventional TreeSHAP (what shap.TreeExplainer(model, data) gives) in place of Saabas' path
+                         attribution: the documents of the -background files are the REFERENCE SET the scores are explained against, not
+                         a source of node counts (none are made).  The same files and the same local-accuracy line; `bias` is the
+                         reference set's mean f64 leaf sum.  Not together with -exact or -interactions.
+  -nbg n                 the reference set holds at most n documents (default 100): all of the background if it has no more, else n
+                         drawn without replacement by a seeded generator, in file order
+  -bgseed s              that generator's seed (default 1)
   -norm, -missingZero, -device   as in ranklib_amd.evaluator: the files are prepared by the code its -load -test uses
   -out tsv               one line per document: qid <TAB> index in its list <TAB> the model's score (Float.toString) and then
                          fid:value ... rest:value bias:value, the values as Double.toString
@@ -91,11 +98,12 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
         print("Usage: -load model -background file [-background file ...] -test file [-feature file] [-norm sum|zscore|linear] [-missingZero] "
-              "[-device d] [-out tsv] [-summary tsv] [-exact] [-interactions tsv]")
+              "[-device d] [-out tsv] [-summary tsv] [-exact] [-interactions tsv] [-interventional] [-nbg n] [-bgseed s]")
         return 0
     models, backgrounds, testFiles = [], [], []
     featureFile, outFile, summaryFile, pairFile = "", "", "", ""
-    exact = False
+    exact = interventional = False
+    nbg, bgseed = 100, 1
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
     Evaluator.qrelFile = ""
@@ -112,6 +120,9 @@ def main(argv=None):
         elif a == "-interactions":
             pairFile = nxt()
             exact = True
+        elif a == "-interventional": interventional = True
+        elif a == "-nbg": nbg = int(nxt())
+        elif a == "-bgseed": bgseed = int(nxt())
         elif not common_flag(a, nxt, reader_only=True):     # no -gmax, -qrel, -hr here, and -device is LambdaMART's alone
             cur.unknown()
     if len(models) != 1:
@@ -120,18 +131,26 @@ def main(argv=None):
         raise RankLibError("ranklib_amd.contribs needs a -background file: the model text holds no node counts")
     if len(testFiles) != 1:
         raise RankLibError("ranklib_amd.contribs needs a -test file, exactly one (got %d)" % len(testFiles))
+    if interventional and exact:
+        raise RankLibError("ranklib_amd.contribs takes -interventional or -exact / -interactions, not both")
     ranker = RankerFactory().loadRankerFromFile(models[0])
     if not isinstance(ranker, LambdaMART):
         ranker.contributions([], None)                      # the refusal, naming the model type
     features = [int(f) for f in FeatureManager.readFeature(featureFile)] if featureFile else None
     e = Evaluator(RankerType.LAMBDAMART, "ERR@10", "ERR@10")
-    for k, f in enumerate(backgrounds):
-        ranker.countCover(e.readTestFile(ranker, f), accumulate=k > 0)
+    ref = None
+    if interventional:
+        ref = ranker.referenceRows([rl for f in backgrounds for rl in e.readTestFile(ranker, f)], nbg, bgseed)
+    else:
+        for k, f in enumerate(backgrounds):
+            ranker.countCover(e.readTestFile(ranker, f), accumulate=k > 0)
     test = e.readTestFile(ranker, testFiles[0])
     cols = None if features is None else features
     ids = [int(f) for f in ranker._model.features()] if cols is None else cols
     parts, scores, worst = [], [], 0.0
     predict = ranker._model.predict_shap if exact else ranker._model.predict_contribs
+    if interventional:
+        predict = lambda rows, cols: ranker._model.predict_shap_background(rows, ref, cols)      # noqa: E731
     S = len(ids) + 2
     pair_abs, pair_sum = np.zeros((S - 1, S - 1)), np.zeros((S - 1, S - 1))
     gap_row = gap_sym = gap_all = 0.0
@@ -166,7 +185,9 @@ def main(argv=None):
         parts, scores = [predict(np.zeros((0, 1), np.float32), cols)[0]], [np.zeros(0, np.float32)]
     matrix, scores = np.concatenate(parts), np.concatenate(scores)
     n_docs = matrix.shape[0]
-    logger.info("%d documents, %d features, background of %d rows", n_docs, len(ids), ranker._model.cover_rows())
+    logger.info("%d documents, %d features, background of %d rows", n_docs, len(ids), len(ref) if interventional else ranker._model.cover_rows())
+    if interventional:
+        logger.info("Interventional Shapley values against the background rows (-nbg %d -bgseed %d)", nbg, bgseed)
     if exact:
         logger.info("Exact Shapley values (path-dependent TreeSHAP)")
     logger.info("Largest |sum of contributions - f64 sum of weighted leaf outputs|: %s", java_double_str(worst))

@@ -88,7 +88,8 @@ inline int shap_check_paths(const std::string &w, const std::vector<HostTree> &t
 
 // appends the tables of one tree: per leaf the distinct features of its path in order of first appearance, each with its slot
 // (slot [n_nodes] as contrib_node_slots made it), z -- the f64 product, in root-to-leaf order, of c[child on the path] / (a + b) over the
-// path's splits on the feature, a = b = 1 where a + b == 0 -- and those splits' conditions
+// path's splits on the feature, a = b = 1 where a + b == 0 -- and those splits' conditions.  cover may be null (rl_interv_host.h: the
+// interventional walk needs the elements and their conditions only); every split then counts as one the background never reached.
 inline void shap_tree_paths(const HostTree &t, const uint64_t *cover, const int32_t *slot, ShapPaths &p)
 {
     if (p.leaf0.empty()) p.leaf0.push_back(0);
@@ -102,7 +103,7 @@ inline void shap_tree_paths(const HostTree &t, const uint64_t *cover, const int3
         els.clear(); cds.clear();
         for (const auto &s : steps) {
             const int32_t nd = s.first, f = t.feature[(size_t)nd];
-            uint64_t a = cover[t.left[(size_t)nd]], b = cover[t.right[(size_t)nd]];
+            uint64_t a = cover ? cover[t.left[(size_t)nd]] : 0, b = cover ? cover[t.right[(size_t)nd]] : 0;     // (no cover: z is not used)
             if (a + b == 0) a = b = 1;
             const double r = (double)(s.second ? a : b) / (double)(a + b);
             size_t e = 0;

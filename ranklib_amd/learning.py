@@ -305,7 +305,7 @@ class Ranker:
         raise RankLibError("rlhip: contributions needs a LambdaMART or MART model: a %s model has no trees%s" % (
             self.name(), " of one ensemble: a forest is several ensembles averaged" if self.name() == "Random Forests" else ""))
 
-    def contributions(self, samples, background, features=None, exact=False):
+    def contributions(self, samples, background, features=None, exact=False, interventional=False, nBackground=100, backgroundSeed=1):
         self.countCover(background)
 
     def interactions(self, samples, background, features=None):
@@ -703,7 +703,20 @@ class LambdaMART(Ranker):
         for rows in self._rowChunks(background):
             self._model.cover(rows, accumulate=True)
 
-    def contributions(self, samples, background, features=None, exact=False):
+    def referenceRows(self, background, nBackground=100, backgroundSeed=1):
+        """the reference set of contributions(interventional=True): the documents of `background` as rows, all of them if there are at
+        most nBackground, else nBackground of them drawn without replacement by numpy.random.default_rng(backgroundSeed), in file order"""
+        dps = [dp for rl in (background or []) for dp in rl.rl]
+        if not dps:
+            raise RankLibError("rlhip: interventional contributions need a background with at least one document")
+        if int(nBackground) < 1:
+            raise RankLibError("rlhip: nBackground must be >= 1 (got %d)" % int(nBackground))
+        if len(dps) > int(nBackground):
+            keep = np.sort(np.random.default_rng(int(backgroundSeed)).choice(len(dps), int(nBackground), replace=False))
+            dps = [dps[int(i)] for i in keep]
+        return self._rows(dps)
+
+    def contributions(self, samples, background, features=None, exact=False, interventional=False, nBackground=100, backgroundSeed=1):
         """Which features put a document where it is: (f64 [documents of samples in file order][C + 2], the C feature ids).  Column c
         holds what feature ids[c] contributes to every document's score, column C what the features not asked for contribute, column
         C + 1 the bias -- Saabas path attribution over node values averaged with the covers of `background` (None: the counts of earlier
@@ -711,12 +724,21 @@ class LambdaMART(Ranker):
         outputs: the model's score up to the float rounding of Ensemble.eval's chain, not its bits.  One _native.Model.predict_contribs
         call per chunk of whole lists whose rows stay under EVAL_ROW_BYTES.  exact: the Shapley values themselves, path-dependent
         TreeSHAP (_native.Model.predict_shap), in the same layout: consistent where Saabas' attribution depends on which
-        feature sits higher in a tree, at about two orders of magnitude more work."""
-        if background is not None:
-            self.countCover(background)
+        feature sits higher in a tree, at about two orders of magnitude more work.  interventional: the Shapley values against a
+        reference set instead (_native.Model.predict_shap_background; what shap.TreeExplainer(model, data) gives): the
+        rows of referenceRows(background, nBackground, backgroundSeed); no covers are counted or used, the bias is the reference set's
+        mean f64 leaf sum and the other columns say how a document differs from it."""
+        if interventional and exact:
+            raise RankLibError("rlhip: contributions takes exact or interventional, not both")
         cols = None if features is None else [int(f) for f in features]
         ids = [int(f) for f in self._model.features()] if cols is None else cols
-        predict = self._model.predict_shap if exact else self._model.predict_contribs
+        if interventional:
+            ref = self.referenceRows(background, nBackground, backgroundSeed)
+            predict = lambda rows, cols: self._model.predict_shap_background(rows, ref, cols)      # noqa: E731
+        else:
+            if background is not None:
+                self.countCover(background)
+            predict = self._model.predict_shap if exact else self._model.predict_contribs
         parts = [predict(rows, cols)[0] for rows in self._rowChunks(samples)]
         if not parts:                                        # no document: the library still checks the columns and that covers exist
             parts = [predict(np.zeros((0, 1), np.float32), cols)[0]]
