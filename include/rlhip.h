@@ -1181,6 +1181,40 @@ int  rl_model_predict_partial(rl_model *m, const float *X, int64_t n_docs, int32
  * rl_model_predict_partial call, summed over its chunks */
 int  rl_debug_partial_times(double *walk_ms, double *reduce_ms);
 
+/* ---- two-feature partial dependence of a tree model, one pass over a file ----------------------------------------------
+ * How the score moves as TWO features move: the surface behind a pair that interacts.  pairs [n_pairs][2] holds per pair p the columns
+ * a = pairs[2p] and b = pairs[2p+1], both >= 0 and a != b; pairs may repeat and may come in either order.  grid_off [2 n_pairs + 1] is a
+ * CSR offset array, grid_off[0] == 0, strictly increasing: slice 2p of grid is a's grid (ga values), slice 2p+1 is b's (gb values), each
+ * strictly ascending under < as above (no NaN, no -0.0 beside 0.0, +-Infinity ordinary).  The cells of pair p are row-major: CELL
+ * cell_off[p] + u * gb + v, cell_off the running sum of ga * gb, is column a set to grid_a[u] AND column b set to grid_b[v].
+ * The ICE score of document i in a cell is Ensemble.eval's float chain, as defined above, on row i taken as padded with zeros to any
+ * width with both columns then set: bit for bit what the matrix materialised on the host gives through rl_model_predict.  out_base
+ * [n_docs] (may be NULL), out_mean [cells], out_shift2 [cells] and out_ice [cells][n_docs] (may be NULL) have the meaning they have in
+ * rl_model_predict_partial, and the two sums per cell take THE SAME FIXED ORDER (RL_PARTIAL_SUM_BLOCK): they depend on n_docs alone, not
+ * on tiles, chunks or the launch grid.
+ * The kernel takes tiles of up to RL_PARTIAL2_TILE_A x RL_PARTIAL2_TILE_B cells of one pair per document at a time and descends every
+ * tree that tests a or b once per tile, carrying the rectangle of cells that reach a node; the cost of a tree is bounded by its leaves,
+ * not by the grid.  Chunks hold whole tiles whose device scratch -- 4 bytes per document and cell, plus the base -- stays within
+ * scratch_bytes (0 = 256 MiB), at least one cell.  X, pairs, grid_off, grid and the outputs are HOST pointers.
+ * RL_ERR_INVALID, the message naming the argument, all checked before the model: null X, pairs, grid_off, grid, out_mean or out_shift2;
+ * n_docs < 1; row_stride < 1; n_pairs < 1; a negative column or a == b ("pairs[p] = (a, b) ..."); grid_off[0] != 0, an empty or
+ * descending grid_off; a grid value that is NaN or not greater than its predecessor ("grid[slice][g] = ..."); scratch_bytes < 0.  Then
+ * a null model and a model without trees.  RL_ERR_UNSUPPORTED: more than 2^31 documents or cells per call.
+ * rl_model_debug_path reports RL_MODEL_PATH_PARTIAL2 afterwards: one kernel serves packed and unpacked models, trees of any size. */
+#ifndef RL_PARTIAL2_TILE_A
+#define RL_PARTIAL2_TILE_A 8
+#endif
+#ifndef RL_PARTIAL2_TILE_B
+#define RL_PARTIAL2_TILE_B 8
+#endif
+enum { RL_MODEL_PATH_PARTIAL2 = 10 };
+int  rl_model_predict_partial2(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *pairs, int32_t n_pairs,
+                               const int32_t *grid_off, const float *grid, int64_t scratch_bytes, float *out_base, double *out_mean,
+                               double *out_shift2, float *out_ice);
+/* debug (tools/partial2_bench.py): ms between device events around the descending and around the reducing launches of this thread's
+ * last rl_model_predict_partial2 call, summed over its chunks */
+int  rl_debug_partial2_times(double *walk_ms, double *reduce_ms);
+
 #ifdef __cplusplus
 }
 #endif

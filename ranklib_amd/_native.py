@@ -151,6 +151,7 @@ ABI_SYMBOLS = [
     "rl_adopt_model_text",
     "rl_refit_model_text", "rl_debug_refit_stats",
     "rl_model_predict_partial", "rl_debug_partial_times",
+    "rl_model_predict_partial2", "rl_debug_partial2_times",
     "rl_model_predict_interactions", "rl_debug_interact_times", "rl_debug_interact_passes",
     "rl_model_predict_shap_background", "rl_debug_interv_times", "rl_debug_interv_passes",
 ]
@@ -330,6 +331,9 @@ def lib():
     if hasattr(L, "rl_model_predict_partial"):  # (A/B builds of older sources have no partial dependence)
         L.rl_model_predict_partial.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp]
         L.rl_debug_partial_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_predict_partial2"):
+        L.rl_model_predict_partial2.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp]
+        L.rl_debug_partial2_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     if hasattr(L, "rl_model_predict_interactions"):  # (A/B builds of older sources have no interaction values)
         L.rl_model_predict_interactions.argtypes = [vp, vp, i64, i32, vp, i32, i64, vp]
         L.rl_debug_interact_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
@@ -755,6 +759,8 @@ MODEL_PATH_SHAP = 6                               # rl_model_predict_shap (k_mod
 MODEL_PATH_PARTIAL = 7                            # rl_model_predict_partial (k_model_partial_scores, k_partial_reduce)
 MODEL_PATH_INTERACT = 8                           # rl_model_predict_interactions (k_model_shap, k_model_interact, k_interact_finish)
 MODEL_PATH_INTERV = 9                             # rl_model_predict_shap_background (k_interv_masks, k_interv_bias, k_model_interv)
+MODEL_PATH_PARTIAL2 = 10                          # rl_model_predict_partial2 (k_model_partial2_scores, k_partial_reduce)
+PARTIAL2_TILE_A = PARTIAL2_TILE_B = 8             # RL_PARTIAL2_TILE_A / _B (rlhip.h): the cells of one pair k_model_partial2_scores takes per document at a time
 PARTIAL_BATCH = 16                                # RL_PARTIAL_BATCH (rlhip.h): cells of one column k_model_partial_scores takes per document at a time
 PARTIAL_SUM_BLOCK = 256                           # RL_PARTIAL_SUM_BLOCK (rlhip.h): the documents of one partial sum, part of the definition
 
@@ -1025,6 +1031,33 @@ class Model:
         check(L.rl_model_predict_partial(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], cbuf.ctypes.data, int(cols.size), off.ctypes.data,
                                          grid.ctypes.data, int(scratch_bytes), base.ctypes.data, mean.ctypes.data, shift2.ctypes.data,
                                          out.ctypes.data if ice and out.size else None))
+        return base[:rows.shape[0]], mean[:cells], shift2[:cells], out
+
+    def predict_partial2(self, rows, pairs, grids, ice=False, scratch_bytes=0):
+        """rl_model_predict_partial2: two-feature partial dependence.  pairs: [n_pairs][2] columns (a, b), a != b; grids:
+        per pair (grid_a, grid_b), each strictly ascending.  The cells of pair p are row-major, cell_off[p] + u * len(grid_b) + v.
+        Returns (f32 base [n_docs], f64 mean [cells], f64 shift2 [cells], f32 ice [cells][n_docs] or None) with predict_partial's
+        meaning: a cell holds the scores of rows, padded with zeros to any width, with a set to grid_a[u] and b to grid_b[v]."""
+        L = lib()
+        if not hasattr(L, "rl_model_predict_partial2"):
+            raise RankLibError("rlhip: this librlhip.so has no two-feature partial dependence (rl_model_predict_partial2)")
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        prs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2) if len(pairs) else np.zeros((0, 2), np.int32)
+        gs = [np.ascontiguousarray(g, dtype=np.float32) for pair in grids for g in pair]
+        if rows.ndim != 2 or len(gs) != 2 * len(prs) or any(len(pair) != 2 for pair in grids) or any(g.ndim != 1 for g in gs):
+            raise RankLibError("rlhip: two-feature partial dependence takes rows [n_docs][row_stride], pairs [n_pairs][2] and one (grid_a, grid_b) of 1-d grids per pair")
+        off = np.zeros(len(gs) + 1, np.int32)
+        np.cumsum([g.size for g in gs], out=off[1:])
+        grid = np.concatenate(gs + [np.zeros(1, np.float32)])      # (never an empty buffer: the library names what is wrong)
+        cells = sum(gs[2 * p].size * gs[2 * p + 1].size for p in range(len(prs)))
+        base = np.zeros(max(1, rows.shape[0]), np.float32)
+        mean, shift2 = np.zeros(max(1, cells), np.float64), np.zeros(max(1, cells), np.float64)
+        out = np.zeros((cells, rows.shape[0]), np.float32) if ice else None
+        buf = rows if rows.size else np.zeros(1, np.float32)
+        pbuf = prs if prs.size else np.zeros(2, np.int32)
+        check(L.rl_model_predict_partial2(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], pbuf.ctypes.data, len(prs), off.ctypes.data,
+                                          grid.ctypes.data, int(scratch_bytes), base.ctypes.data, mean.ctypes.data, shift2.ctypes.data,
+                                          out.ctypes.data if ice and out.size else None))
         return base[:rows.shape[0]], mean[:cells], shift2[:cells], out
 
     def path(self):
@@ -1543,6 +1576,13 @@ def partial_times():
     """rl_debug_partial_times: (walk ms, reduce ms) of this thread's last predict_partial call, between device events"""
     w, r = C.c_double(0.0), C.c_double(0.0)
     check(lib().rl_debug_partial_times(C.byref(w), C.byref(r)))
+    return w.value, r.value
+
+
+def partial2_times():
+    """rl_debug_partial2_times: (walk ms, reduce ms) of this thread's last predict_partial2 call, between device events"""
+    w, r = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_partial2_times(C.byref(w), C.byref(r)))
     return w.value, r.value
 
 

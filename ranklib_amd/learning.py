@@ -364,6 +364,40 @@ class Ranker:
             curves.append(sc)
         return P.summarize(feats, grids, base, mean, shift2, curves if ice else None)
 
+    # rlhip: two-feature partial dependence: how the score moves as two features move together
+    def _askedPairs(self, pairs):
+        prs = [(int(a), int(b)) for a, b in pairs]
+        if not prs:
+            raise RankLibError("rlhip: partialDependence2 has no pair to vary")
+        for a, b in prs:
+            if a < 1 or b < 1:
+                raise RankLibError("rlhip: partialDependence2 takes feature ids >= 1 (got %d %d)" % (a, b))
+            if a == b:
+                raise RankLibError("rlhip: partialDependence2 takes pairs of two different features (got %d %d)" % (a, b))
+        return prs
+
+    def partialDependence2(self, samples, pairs, grid=10, ice=False):
+        """partial.Partial2 of pairs [(a, b), ...] on samples: per pair the two grids partial.grid_for gives and per (value of a, value
+        of b) cell the mean score of the documents with both features set, its difference from the base mean, the rms move of a
+        document, and Friedman and Popescu's h2 of the pair on the grid; with ice the per-document scores of every cell too.  This is
+        the generic path, for every ranker: per cell a copy with both features substituted goes through evalLists, and the sums take
+        the fixed order of include/rlhip.h (partial.fixed_order_sums)."""
+        from . import partial as P
+        prs = self._askedPairs(pairs)
+        if not sum(rl.size() for rl in samples):
+            raise RankLibError("rlhip: partialDependence2 needs at least one document")
+        grids = [(P.grid_for(self, samples, a, grid), P.grid_for(self, samples, b, grid)) for a, b in prs]
+        base, _ = self.evalLists(samples)
+        mean, shift2, surfaces = [], [], []
+        for (a, b), (ga, gb) in zip(prs, grids):
+            sc = np.stack([self.evalLists(substituted_lists(substituted_lists(samples, a, va), b, vb))[0] for va in ga for vb in gb])
+            sums = [P.fixed_order_sums(s, base) for s in sc]
+            mean.append(np.array([s1 for s1, _ in sums], np.float64) / float(len(base)))
+            shift2.append(np.array([s2 for _, s2 in sums], np.float64) / float(len(base)))
+            surfaces.append(sc)
+        one = self.partialDependence(samples, features=sorted({f for pr in prs for f in pr}), grid=grid)
+        return P.summarize2(prs, grids, base, mean, shift2, one, surfaces if ice else None)
+
     def save(self, modelFile):        # :106-122
         d = modelFile.rsplit("/", 1)[0] if "/" in modelFile else None
         if d:
@@ -685,6 +719,23 @@ class LambdaMART(Ranker):
         off = np.concatenate([[0], np.cumsum([len(g) for g in grids])]).astype(np.int64)
         cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(feats))]      # noqa: E731
         return P.summarize(feats, grids, base.astype(np.float64), cut(mean), cut(shift2), cut(sc.astype(np.float64)) if ice else None)
+
+    # --- two-feature partial dependence in one pass (rlhip) --------------------------------------
+    def partialDependence2(self, samples, pairs, grid=10, ice=False):
+        """Ranker.partialDependence2, bit for bit, without a substituted copy per cell: every (pair, value of a, value of b) cell and
+        the base are descended and summed by ONE _native.Model.predict_partial2 call, the one-feature curves behind h2 by one
+        predict_partial call."""
+        from . import partial as P
+        prs = self._askedPairs(pairs)
+        dps = [dp for rl in samples for dp in rl.rl]
+        if not dps:
+            raise RankLibError("rlhip: partialDependence2 needs at least one document")
+        grids = [(P.grid_for(self, samples, a, grid), P.grid_for(self, samples, b, grid)) for a, b in prs]
+        base, mean, shift2, sc = self._model.predict_partial2(self._rows(dps), prs, grids, ice=ice)
+        off = np.concatenate([[0], np.cumsum([len(ga) * len(gb) for ga, gb in grids])]).astype(np.int64)
+        cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(prs))]      # noqa: E731
+        one = self.partialDependence(samples, features=sorted({f for pr in prs for f in pr}), grid=grid)
+        return P.summarize2(prs, grids, base.astype(np.float64), cut(mean), cut(shift2), one, cut(sc.astype(np.float64)) if ice else None)
 
     # --- per-document feature contributions (rlhip, DESIGN.md 26) ----------------------------------------------
     def _rowChunks(self, samples):
