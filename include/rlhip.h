@@ -221,6 +221,31 @@ int rl_refit_model_text(rl_trainer *t, const char *text, float decay, int32_t *s
  * than 640 features, or RLHIP_REFIT_DIRECT), leaves that kept their old output because no document reached them. */
 int rl_debug_refit_stats(const rl_trainer *t, int64_t *out);
 
+/* DART, dropout boosting (Rashmi & Gilad-Bachrach).  After rl_create, before rl_init; rate_drop == 0 switches it off again.
+ * Round m (0-based) works on trees 0 .. m-1 with float weights w_i (every tree's first weight is set by the round that grew it):
+ *   1. draw, on the host: tree i < m is a candidate when (feature_key(root_hash(seed ^ 0x44415254, m), i) >> 11) * 2^-53 < (double)rate_drop,
+ *      the hashes being the feature sampling's (oracle: ro_root_hash, ro_feature_key).  Of more than max_drop candidates the max_drop with the
+ *      smallest keys stay, ties to the smaller index; max_drop <= 0: no cap.  D = the kept set ascending, k = |D|.  k == 0 (always in round 0):
+ *      the round is a plain round with w_m = learning_rate.
+ *   2. weights (XGBoost's "tree" normalisation): f = (float)((double)k / ((double)k + (double)lr)), w_m = (float)((double)lr / ((double)k + (double)lr)),
+ *      w_i' = (float)((double)w_i * (double)f) for i in D.
+ *   3. per document in f64, o_i the float output of tree i on it, a rounding after every product and sum:
+ *      s' = s, s' -= (double)w_i * (double)o_i for i in D ascending;  r = 0, r += (double)w_i' * (double)o_i for i in D ascending;  base = s' + r.
+ *      The validation scores become base by the same rule.
+ *   4. the training lists are ranked on s', lambda / w (MART: residuals) come from s', the tree is grown and its leaves evaluated as ever.
+ *   5. modelScores = base, then += (double)w_m * (double)output; the stored weights of D become w_i'; ranking and both metrics as ever.
+ * RL_ARR_SCORE / RL_ARR_VALID_SCORE are therefore a chain of their own, not the from-scratch chain over the final weights (that one is rl_predict's).
+ * With DART on rl_boost_round never sets *stop, rl_finish keeps every tree (a prefix of the ensemble is not a model that ever existed),
+ * rl_best_validation still reports the best round.  rl_adopt_model_text and rl_refit_model_text are RL_ERR_UNSUPPORTED on such a trainer.
+ * RL_ERR_INVALID: a null handle, a rate_drop that is NaN, negative or above 1.  RL_ERR_STATE: after rl_init.  rl_init of a DART trainer is
+ * RL_ERR_UNSUPPORTED when it is sharded, with RL_FLAG_SERIAL_CHAIN, RLHIP_SCORE_STREAM=0 or more than 1024 leaves (no leaf per document is
+ * kept), or when the leaf history -- 2 bytes per tree and document of both data sets -- does not fit free device memory (the message states the bytes). */
+int rl_set_dart(rl_trainer *t, float rate_drop, int32_t max_drop, uint64_t seed);
+/* the weights of the kept trees (learning_rate each without DART), as the model text holds them; *n = their number, out may be NULL */
+int rl_get_tree_weights(const rl_trainer *t, float *out, int32_t cap, int32_t *n);
+/* the set D a round that has been enqueued dropped, ascending; *n = k, ids may be NULL.  RL_ERR_STATE without DART, RL_ERR_INVALID: round out of range */
+int rl_dart_dropped(const rl_trainer *t, int32_t round, int32_t *ids, int32_t cap, int32_t *n);
+
 /* Enqueue n rounds without any host synchronisation (no validation set allowed: early stopping needs
  * the host).  rl_sync waits for them; trees and per-round metrics are then available through
  * rl_get_tree / rl_get_round_metrics. */
@@ -448,7 +473,7 @@ int rl_hist_features(const rl_trainer *t, int32_t *n, int32_t *columns, int32_t 
 int rl_quant_exponent(const rl_trainer *t, int32_t *e);   /* q = rint(lambda * 2^e) in the last round */
 int rl_get_array(rl_trainer *t, int32_t which, void *out, int64_t cap_bytes);
 
-enum { RL_KERNEL_HIST_ROOT = 0, RL_KERNEL_HIST_NODE = 1, RL_KERNEL_LAMBDA = 2, RL_KERNEL_COUNT_ = 3 };
+enum { RL_KERNEL_HIST_ROOT = 0, RL_KERNEL_HIST_NODE = 1, RL_KERNEL_LAMBDA = 2, RL_KERNEL_DART_DROP = 3 /* k_dart_drop on both data sets */, RL_KERNEL_COUNT_ = 4 };
 /* With RL_FLAG_TIMING: accumulated HIP-event time (ms), launch count and algorithmic bytes of a kernel
  * since the last rl_reset_timing. */
 int rl_get_timing(rl_trainer *t, int32_t kernel, double *total_ms, int64_t *launches, double *alg_bytes);

@@ -116,7 +116,7 @@ ARM = dict(HIST_ROOT=0, HIST_CHILD=12, RANK_TINY=24, RANK_MIXED=25, RANK_WAVE_LO
            QUANTIZE=39, XPLAN_HOST=40, XPLAN_DEVICE=41, STEPS_ENQUEUED=42, SET_STEP_AHEAD=43, SET_DIST_AHEAD=44, CHILD_GRID_X=45, CHILD_GRID_Y=46, CHILD_LDS=47,
            SET_P8=48, SET_DM_ROOT=49, SET_DM_DIV=50, SET_SUB_CHILD=51, SET_HIST_NT=52, SET_ANY_RUNS=53, SET_CROWS=54, SET_TIE_ON=55, SET_NODE_DIV=56,
            SET_NODE_MIN=57, SET_BALANCE=58, SET_BALANCE_TARGET=59, SET_BALANCE_MIN=60, SET_BALANCE_CAP=61, SET_NODE_CHUNK=62, SET_MAX_CHUNKS=63, REPLAY_TILED=64, REPLAY_DIRECT=65, COUNT_=66)
-KERNEL = dict(HIST_ROOT=0, HIST_NODE=1, LAMBDA=2)
+KERNEL = dict(HIST_ROOT=0, HIST_NODE=1, LAMBDA=2, DART_DROP=3)
 
 # every symbol include/rlhip.h declares (tests/test_abi.py checks the .so exports all of them)
 ABI_SYMBOLS = [
@@ -154,6 +154,7 @@ ABI_SYMBOLS = [
     "rl_model_predict_partial2", "rl_debug_partial2_times",
     "rl_model_predict_interactions", "rl_debug_interact_times", "rl_debug_interact_passes",
     "rl_model_predict_shap_background", "rl_debug_interv_times", "rl_debug_interv_passes",
+    "rl_set_dart", "rl_get_tree_weights", "rl_dart_dropped",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -325,6 +326,10 @@ def lib():
         L.rl_debug_shap_passes.argtypes = [C.POINTER(i32)]
     if hasattr(L, "rl_adopt_model_text"):     # (A/B builds of older sources cannot resume)
         L.rl_adopt_model_text.argtypes = [vp, C.c_char_p, i64, C.POINTER(i32)]
+    if hasattr(L, "rl_set_dart"):             # (A/B builds of older sources have no DART)
+        L.rl_set_dart.argtypes = [vp, C.c_float, i32, C.c_uint64]
+        L.rl_get_tree_weights.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        L.rl_dart_dropped.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
     if hasattr(L, "rl_refit_model_text"):     # (A/B builds of older sources cannot refit)
         L.rl_refit_model_text.argtypes = [vp, C.c_char_p, C.c_float, C.POINTER(i32)]
         L.rl_debug_refit_stats.argtypes = [vp, C.POINTER(i64)]
@@ -640,6 +645,29 @@ class Trainer:
         stop = C.c_int32(0)
         check(lib().rl_refit_model_text(self.h, None if text is None else text.encode("ascii"), float(decay), C.byref(stop)))
         return bool(stop.value)
+
+    def set_dart(self, rate_drop, max_drop=0, seed=0):
+        """DART: every round drops each earlier tree with probability rate_drop (at most max_drop of them, <= 0: no cap) before its
+        lambdas are taken, and rescales them and the new tree afterwards; before init().  rate_drop 0 switches it off again"""
+        if not hasattr(lib(), "rl_set_dart"):
+            raise RankLibError("this librlhip.so has no rl_set_dart: it cannot train with DART")
+        check(lib().rl_set_dart(self.h, float(rate_drop), int(max_drop), int(seed)))
+
+    def tree_weights(self):
+        """the float weight of every kept tree (learning_rate each without DART)"""
+        n = C.c_int32(0)
+        check(lib().rl_get_tree_weights(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.float32)
+        check(lib().rl_get_tree_weights(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def dart_dropped(self, r):
+        """the trees round r dropped, ascending"""
+        n = C.c_int32(0)
+        check(lib().rl_dart_dropped(self.h, r, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        check(lib().rl_dart_dropped(self.h, r, out.ctypes.data, n.value, C.byref(n)))
+        return out
 
     def refit_stats(self):
         """rl_debug_refit_stats: (routing launches through the LDS tile, routing launches from global memory, leaves that kept their old output)"""

@@ -705,6 +705,9 @@ static int init_round_state(rl_trainer *t, InitWork &w)
     RL_HIP(t->pool.alloc(&t->ens.n_nodes, (size_t)t->p.n_trees));
     RL_HIP(hipMemset(t->ens.n_nodes, 0, t->p.n_trees * sizeof(int32_t)));
     RL_HIP(t->pool.alloc(&t->d_mean, (size_t)2));
+    t->h_tree_w.assign((size_t)t->p.n_trees, t->p.learning_rate);
+    RL_HIP(t->pool.alloc(&t->d_tree_w, (size_t)t->p.n_trees));
+    RL_HIP(hipMemcpy(t->d_tree_w, t->h_tree_w.data(), t->h_tree_w.size() * sizeof(float), hipMemcpyHostToDevice));
     return RL_OK;
 }
 
@@ -815,6 +818,50 @@ static int init_lambda_state(rl_trainer *t)
     RL_HIP(hipDeviceSynchronize());
     int rc = launch_rank(t, d, c.scores, d.d_ndcg, true);      // ranking of the all-zero start scores (file order)
     if (rc) return rc;
+    return RL_OK;
+}
+
+// ---- DART (rl_set_dart, rl_dart.inc): what it cannot be combined with, the leaf history, the argument table and its pinned ring ----
+static const char *const kDartNoLeaves = "DART needs the leaf of every document from the leaf sums' gather: not with RL_FLAG_SERIAL_CHAIN, RLHIP_SCORE_STREAM=0 or more than 1024 leaves";
+
+// at the top of rl_init: the combinations and the size that are known before anything is built
+static int dart_precheck(rl_trainer *t)
+{
+    DartState &da = t->dart;
+    if (!da.on) return RL_OK;
+    if (t->dist) return fail(RL_ERR_UNSUPPORTED, "DART with a sharded trainer: the leaf history is not built for shards");
+    if ((t->p.flags & RL_FLAG_SERIAL_CHAIN) || !t->knobs.score_stream || t->p.n_leaves > 1024) return fail(RL_ERR_UNSUPPORTED, kDartNoLeaves);
+    const size_t T = (size_t)t->p.n_trees, N = (size_t)t->tr.N, Nv = t->has_valid ? (size_t)t->va.N : 0;
+    da.stride_tr = (N + 127) / 128 * 128; da.stride_va = (Nv + 3) & ~(size_t)3;       // (Ctx::Npad; rows of a multiple of four entries: k_dart_drop's 8-byte loads)
+    const size_t need = 2 * T * (da.stride_tr + da.stride_va) + N * sizeof(double) + 3 * T * sizeof(int32_t);
+    size_t free_b = 0, total_b = 0;
+    RL_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (need > free_b)
+        return fail(RL_ERR_UNSUPPORTED, "DART: the leaf history of " + std::to_string(T) + " trees needs " + std::to_string(need) + " bytes of device memory, " +
+                                        std::to_string(free_b) + " are free");
+    return RL_OK;
+}
+
+static int init_dart(rl_trainer *t)
+{
+    DartState &da = t->dart;
+    if (!da.on) return RL_OK;
+    const Ctx &c = t->ctx;
+    if (!round_streams_scores(t)) return fail(RL_ERR_UNSUPPORTED, kDartNoLeaves);       // (-leaf -1: the leaf budget is known now)
+    const size_t T = (size_t)t->p.n_trees, Nv = t->has_valid ? (size_t)t->va.N : 0;
+    RL_HIP(t->pool.alloc(&da.hist_tr, T * da.stride_tr)); RL_HIP(hipMemset(da.hist_tr, 0, T * da.stride_tr * sizeof(uint16_t)));
+    if (Nv) { RL_HIP(t->pool.alloc(&da.hist_va, T * da.stride_va)); RL_HIP(hipMemset(da.hist_va, 0, T * da.stride_va * sizeof(uint16_t))); }
+    RL_HIP(t->pool.alloc(&da.d_base, (size_t)c.N));
+    RL_HIP(t->pool.alloc(&da.d_args, 3 * T));
+    for (int i = 0; i < DartState::kSlots; i++) {
+        RL_HIP(hipHostMalloc((void **)&da.h_args[i], 3 * T * sizeof(int32_t), hipHostMallocDefault));
+        RL_HIP(hipEventCreateWithFlags(&da.ev[i], hipEventDisableTiming));
+        da.used[i] = false;
+    }
+    da.chunk = dart_chunk_trees(c.MAXN, t->knobs.dart_chunk);
+    da.dropped.clear();
+    RL_HIP(hipFuncSetAttribute((const void *)k_dart_drop<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDartLdsBytes));
+    RL_HIP(hipFuncSetAttribute((const void *)k_dart_drop<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDartLdsBytes));
     return RL_OK;
 }
 

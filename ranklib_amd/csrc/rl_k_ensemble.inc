@@ -50,10 +50,10 @@ __global__ __launch_bounds__(kThreads) void k_valid_update(const EnsTree e, int 
     }
 }
 
-// Ensemble.eval (Ensemble.java:110-116): float s; s += tree.eval(dp) * weight   for trees 0..nt-1.
+// Ensemble.eval (Ensemble.java:110-116): float s; s += tree.eval(dp) * weight   for trees 0..nt-1, wt[t] the weight of tree t.
 // rows: row-major [n][stride]; column of feature index f is colmap ? colmap[f] : f.
 __global__ __launch_bounds__(kThreads) void k_ensemble_eval(const EnsTree e, int MAXN, int nt, const float *X, int64_t n,
-                                                             int stride, float w, float *out, double *out_d)
+                                                             int stride, const float *wt, float *out, double *out_d)
 {
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
         const float *row = X + (size_t)i * stride;
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void k_ensemble_eval(const EnsTree e, int
                 const float v = (fc < stride) ? row[fc] : 0.f;
                 nd = (v <= e.thr[o + nd]) ? e.left[o + nd] : e.right[o + nd];
             }
-            s = (float)((double)s + (double)e.out[o + nd] * (double)w);
+            s = (float)((double)s + (double)e.out[o + nd] * (double)wt[t]);
         }
         if (out) out[i] = s;
         if (out_d) out_d[i] = (double)s;

@@ -129,6 +129,7 @@ static int check_adoptable(rl_trainer *t, const std::string &w, const char *text
     if (t->finished) return fail(RL_ERR_STATE, w + "rl_finish has been called");
     if (t->round != 0) return fail(RL_ERR_STATE, w + "a model is " + (refit ? "refitted" : "adopted") + " before the first round (this trainer has " + std::to_string(t->round) + ")");
     if (t->dist) return fail(RL_ERR_UNSUPPORTED, w + "a sharded trainer cannot " + (refit ? "refit a model (the routing is not built for shards)" : "adopt a model (the replay is not built for shards)"));
+    if (t->dart.on) return fail(RL_ERR_UNSUPPORTED, w + "a DART trainer cannot " + (refit ? "refit" : "adopt") + " a model (no leaf history exists for trees it did not grow)");
     std::string err;
     if (!model_from_text(text, trees, err)) return fail(RL_ERR_INVALID, w + "Error in Emsemble(xmlRepresentation): " + err);
     {   // one <ensemble>: the parser stops behind the first

@@ -37,6 +37,71 @@ static int round_plan(const rl_trainer *t, RoundPlan &pl)
     return RL_OK;
 }
 
+// ---- DART (rl_dart.inc), in front of the lambdas: the round's draw, its argument table, the dropped trees out of both score arrays, the ranking of s' ----
+// (DART off: nothing is launched.  A round that drops nothing -- round 0 always -- launches nothing here either: it is a plain round with w_m = learning_rate)
+static int enqueue_dart_drop(rl_trainer *t)
+{
+    DartState &da = t->dart;
+    if (!da.on) return RL_OK;
+    Ctx &c = t->ctx;
+    hipStream_t s = t->stream;
+    const int m = t->round;
+    const float lr = t->p.learning_rate;
+    std::vector<int32_t> D;
+    const unsigned long long h = root_hash(da.seed ^ kDartSeedTag, m);
+    dart_draw([&](int32_t i) { return (uint64_t)feature_key(h, i); }, m, da.rate, da.max_drop, D);
+    const int k = (int)D.size();
+    da.w_m = dart_new_weight(k, lr);
+    da.cur = DartArgs{da.d_args, (const float *)(da.d_args + k), (const float *)(da.d_args + 2 * k), k};
+    da.dropped.resize((size_t)m + 1);
+    da.dropped[(size_t)m] = D;
+    if (k == 0) return RL_OK;
+    const int slot = m % DartState::kSlots;
+    if (da.used[slot]) RL_HIP(hipEventSynchronize(da.ev[slot]));       // the copy out of this slot, DartState::kSlots rounds ago
+    const float f = dart_factor(k, lr);
+    int32_t *ha = da.h_args[slot];
+    for (int j = 0; j < k; j++) {
+        const float w_old = t->h_tree_w[(size_t)D[j]], w_new = dart_scaled(w_old, f);
+        ha[j] = D[j]; memcpy(ha + k + j, &w_old, 4); memcpy(ha + 2 * k + j, &w_new, 4);
+        t->h_tree_w[(size_t)D[j]] = w_new;
+    }
+    RL_HIP(hipMemcpyAsync(da.d_args, ha, (size_t)3 * k * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    RL_HIP(hipEventRecord(da.ev[slot], s));
+    da.used[slot] = true;
+    const int chunk = std::min(da.chunk, k);       // (a round that drops few trees asks for the LDS it uses: more resident blocks)
+    const size_t lds = (size_t)2 * chunk * dart_lds_stride(c.MAXN) * sizeof(float);
+    {
+        ScopedTiming tm(t, RL_KERNEL_DART_DROP, (double)c.N * (2.0 * k + 24.0) + (t->has_valid ? (double)t->va.N * (2.0 * k + 16.0) : 0.0));
+        hipLaunchKernelGGL(k_dart_drop<true>, dim3((unsigned)((c.N + kDartTile - 1) / kDartTile)), dim3(kDartLanes), lds, s, (const uint16_t *)da.hist_tr, da.stride_tr,
+                           (const float *)t->ens.out, c.MAXN, da.cur, chunk, c.N, c.scores, da.d_base);
+        if (t->has_valid)
+            hipLaunchKernelGGL(k_dart_drop<false>, dim3((unsigned)((t->va.N + kDartTile - 1) / kDartTile)), dim3(kDartLanes), lds, s, (const uint16_t *)da.hist_va, da.stride_va,
+                               (const float *)t->ens.out, c.MAXN, da.cur, chunk, (int)t->va.N, t->va.d_scores, (double *)nullptr);
+    }
+    RL_HIP(hipGetLastError());
+    // the lambdas rank on s'.  The ranking writes d_ndcg (values nobody reads): the previous round's metric mean on the side stream may still read it
+    if (!t->has_valid && t->side_pending) RL_HIP(hipStreamWaitEvent(s, t->ev_metric, 0));
+    return c.mart ? RL_OK : launch_rank(t, t->tr, c.scores, t->tr.d_ndcg, true);       // (MART's residuals need no ranking)
+}
+
+// ---- DART, in front of the score update: s' + r back into the scores, the round's w_m for the score kernels, the weights, the new tree's history row ----
+// (the validation rows' row is written by k_valid_update_rec, enqueue_scores_and_metrics)
+static int enqueue_dart_restore(rl_trainer *t)
+{
+    DartState &da = t->dart;
+    if (!da.on) return RL_OK;
+    Ctx &c = t->ctx;
+    hipStream_t s = t->stream;
+    const int m = t->round;
+    if (da.cur.k > 0) hipLaunchKernelGGL(k_copy_f64, dim3(std::max(1, std::min(2048, (c.N + kThreads - 1) / kThreads))), dim3(kThreads), 0, s, (const double *)da.d_base, c.scores, c.N);
+    c.lr = da.w_m;                  // k_score_stream and the validation update add (double)w_m * (double)output
+    t->h_tree_w[(size_t)m] = da.w_m;
+    hipLaunchKernelGGL(k_dart_weights, dim3(1), dim3(kThreads), 0, s, t->d_tree_w, da.cur, m, da.w_m);
+    hipLaunchKernelGGL(k_dart_record, dim3(std::max(1, std::min(2048, (c.N + kThreads - 1) / kThreads))), dim3(kThreads), 0, s, c, da.hist_tr + (size_t)m * da.stride_tr);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
 // ---- lambdas (MART: residuals) and the blocks' max |lambda|; n_max: blocks that reported theirs (folded by k_max_reduce) ----
 static int enqueue_lambdas(rl_trainer *t, int &n_max)
 {
@@ -432,7 +497,10 @@ static int enqueue_scores_and_metrics(rl_trainer *t, bool stream_scores, bool ex
         enqueue_metric_mean(t, gq, t->Qglobal, c.round_metric + 2 * (size_t)m);
     } else enqueue_metric_mean(t, t->tr.d_ndcg, t->tr.Q, c.round_metric + 2 * (size_t)m);
     if (t->has_valid) {   // :228-237
-        hipLaunchKernelGGL(k_valid_update, dim3(std::min<int64_t>(4096, (t->va.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+        if (t->dart.on)       // the same walk, which also leaves every validation row's node in the tree's history row (rl_dart.inc)
+            hipLaunchKernelGGL(k_valid_update_rec, dim3(std::min<int64_t>(4096, (t->va.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                               t->ens, c.MAXN, m, (const float *)t->va.d_X, (int)t->va.N, t->F, c.lr, t->va.d_scores, t->dart.hist_va + (size_t)m * t->dart.stride_va);
+        else hipLaunchKernelGGL(k_valid_update,dim3(std::min<int64_t>(4096, (t->va.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
                            t->ens, c.MAXN, m, (const float *)t->va.d_X, (int)t->va.N, t->F, c.lr, t->va.d_scores);
         rc = launch_rank(t, t->va, t->va.d_scores, t->va.d_ndcg, false);
         if (rc != RL_OK) return rc;
@@ -469,6 +537,7 @@ static int enqueue_round(rl_trainer *t)
     if (rc) return rc;
     int n_max = 0;
     bool root_quant_fused = false;
+    if ((rc = enqueue_dart_drop(t)) != RL_OK) return rc;
     if ((rc = enqueue_lambdas(t, n_max)) != RL_OK) return rc;
     if ((rc = enqueue_max_and_quant(t, n_max, root_quant_fused)) != RL_OK) return rc;
     for (;;) {      // one pass per growth of the tree
@@ -486,6 +555,7 @@ static int enqueue_round(rl_trainer *t)
         if (!other_cut || !(c.tie_on & 2)) break;
         c.tie_on = 1; t->tie_regrown++;
     }
+    if ((rc = enqueue_dart_restore(t)) != RL_OK) return rc;
     return enqueue_scores_and_metrics(t, stream_scores);
 }
 

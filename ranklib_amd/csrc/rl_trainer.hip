@@ -33,6 +33,8 @@
 #include "rl_tie.inc"
 #include "rl_membench.inc"
 #include "rl_dist.inc"
+#include "rl_dart_host.h"
+#include "rl_dart.inc"
 #include "rl_model.h"
 
 namespace rl {
@@ -140,6 +142,9 @@ struct rl_trainer {
     double *d_qsend = nullptr, *d_qgath = nullptr, *d_qcat = nullptr; int32_t *d_allQ = nullptr;
     // the same for the validation set (sharded by query like the training set)
     int32_t vQglobal = 0, vQmax = 0; double *d_vqsend = nullptr, *d_vqgath = nullptr, *d_vqcat = nullptr; int32_t *d_vallQ = nullptr;
+    // a weight per tree: learning_rate in every slot unless DART (rl_dart.inc) rescales them; the host's copy is what rl_get_tree_weights and the model text read
+    float *d_tree_w = nullptr; std::vector<float> h_tree_w;
+    DartState dart;
 };
 
 namespace rl {
@@ -309,7 +314,7 @@ static int fetch_tree(const rl_trainer *tc, int i, HostTree &out)
 {
     rl_trainer *t = const_cast<rl_trainer *>(tc);
     if ((int)t->trees.size() <= i) t->trees.resize((size_t)i + 1);
-    if (t->trees[i].n_nodes > 0) { out = t->trees[i]; return RL_OK; }
+    if (t->trees[i].n_nodes > 0) { out = t->trees[i]; out.weight = t->h_tree_w[i]; return RL_OK; }       // (DART: a later round may have rescaled the tree)
     const int MAXN = t->ctx.MAXN;
     int32_t nn = 0;
     RL_HIP(hipMemcpy(&nn, t->ens.n_nodes + i, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -326,7 +331,7 @@ static int fetch_tree(const rl_trainer *tc, int i, HostTree &out)
     RL_HIP(hipMemcpy(ou.data(), t->ens.out + o, nn * sizeof(float), hipMemcpyDeviceToHost));
     RL_HIP(hipMemcpy(dv.data(), t->ens.deviance + o, nn * sizeof(double), hipMemcpyDeviceToHost));
     HostTree h;
-    h.weight = t->p.learning_rate;
+    h.weight = t->h_tree_w[i];
     // creation order -> pre-order (root, left subtree, right subtree)
     std::vector<int> stack{0};
     std::vector<int> order, newid(nn, -1);
@@ -397,6 +402,36 @@ int rl_set_external_judgments(rl_trainer *t, int32_t validation, const double *i
     std::string err;
     const int rc = (validation ? t->va : t->tr).set_external(ideal_dcg, rel_doc_count, err);
     return rc ? fail(rc, err) : RL_OK;
+}
+
+int rl_set_dart(rl_trainer *t, float rate_drop, int32_t max_drop, uint64_t seed)
+{
+    if (check_trainer(t)) return RL_ERR_INVALID;
+    if (!(rate_drop >= 0.0f && rate_drop <= 1.0f)) return fail(RL_ERR_INVALID, "rl_set_dart: rate_drop must be in [0, 1]");
+    if (t->inited) return fail(RL_ERR_STATE, "rl_set_dart must be called before rl_init");
+    t->dart.on = rate_drop > 0.0f;
+    t->dart.rate = rate_drop; t->dart.max_drop = max_drop; t->dart.seed = seed;
+    return RL_OK;
+}
+
+int rl_get_tree_weights(const rl_trainer *t, float *out, int32_t cap, int32_t *n)
+{
+    if (check_trainer(t)) return RL_ERR_INVALID;
+    if (!t->inited) return fail(RL_ERR_STATE, "rl_init has not been called");
+    if (n) *n = t->n_kept;
+    if (out) for (int32_t i = 0; i < t->n_kept && i < cap; i++) out[i] = t->h_tree_w[i];
+    return RL_OK;
+}
+
+int rl_dart_dropped(const rl_trainer *t, int32_t round, int32_t *ids, int32_t cap, int32_t *n)
+{
+    if (check_trainer(t)) return RL_ERR_INVALID;
+    if (!t->dart.on) return fail(RL_ERR_STATE, "rl_dart_dropped: DART is off (rl_set_dart)");
+    if (round < 0 || round >= t->round) return fail(RL_ERR_INVALID, "rl_dart_dropped: round out of range");
+    const std::vector<int32_t> &d = t->dart.dropped[(size_t)round];
+    if (n) *n = (int32_t)d.size();
+    if (ids) for (int32_t i = 0; i < (int32_t)d.size() && i < cap; i++) ids[i] = d[i];
+    return RL_OK;
 }
 
 int rl_set_err_max(double max_gain)
@@ -506,6 +541,7 @@ void rl_destroy(rl_trainer *t)
     if (t->h_xmail) (void)hipHostFree(t->h_xmail);
     if (t->tie_buf) (void)hipFree(t->tie_buf);
     if (t->tie_pin) (void)hipHostFree(t->tie_pin);
+    for (int i = 0; i < DartState::kSlots; i++) { if (t->dart.h_args[i]) (void)hipHostFree(t->dart.h_args[i]); if (t->dart.ev[i]) (void)hipEventDestroy(t->dart.ev[i]); }
     for (void *q : t->pinned) (void)hipHostFree(q);
     delete t;
 }
@@ -576,6 +612,8 @@ int rl_init(rl_trainer *t)
         return fail(RL_ERR_STATE, "rl_set_rows has not delivered every row yet");
     RL_HIP(hipSetDevice(t->p.device));
     RL_HIP(hipDeviceSynchronize());      // uploads of rl_set_* went through the null stream; t->stream is non-blocking
+    int rcd = dart_precheck(t);          // (what DART cannot be combined with is known before anything is built)
+    if (rcd) return rcd;
     InitWork w;
     int rc = init_shape(t, w);
     if (!rc) rc = init_threshold_tables(t, w);
@@ -588,6 +626,7 @@ int rl_init(rl_trainer *t)
     if (!rc) rc = init_round_state(t, w);
     if (!rc) rc = init_dist_state(t, w);
     if (!rc) rc = init_lambda_state(t);
+    if (!rc) rc = init_dart(t);
     if (rc) return rc;
     RL_HIP(hipDeviceSynchronize());
     t->inited = true;
@@ -613,7 +652,7 @@ int rl_boost_round(rl_trainer *t, rl_tree *out, float *train_metric, float *vali
         const double score = vm;                                     // LambdaMART.java:237-243
         if (score > t->best_score) { t->best_score = score; t->best_round = t->round - 1; }
     }
-    if (stop) *stop = (m - t->best_round > t->p.early_stop_rounds) ? 1 : 0;      // :248
+    if (stop) *stop = (!t->dart.on && m - t->best_round > t->p.early_stop_rounds) ? 1 : 0;      // :248 (DART: a prefix of the ensemble is not a model that ever existed)
     if (out) return rl_get_tree(t, m, out);
     return RL_OK;
 }
@@ -643,7 +682,7 @@ static int final_score(rl_trainer *t, DataSet &d, double *out)
     double *d_sc = nullptr;
     RL_HIP(t->pool.alloc(&d_sc, (size_t)d.N));
     hipLaunchKernelGGL(k_ensemble_eval, dim3((unsigned)std::min<int64_t>(8192, (d.N + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, t->ens,
-                       t->ctx.MAXN, t->n_kept, (const float *)d.d_X, d.N, t->F, t->p.learning_rate, (float *)nullptr, d_sc);
+                       t->ctx.MAXN, t->n_kept, (const float *)d.d_X, d.N, t->F, (const float *)t->d_tree_w, (float *)nullptr, d_sc);
     int rc = launch_rank(t, d, d_sc, d.d_ndcg, false);
     if (rc) return rc;
     if (t->dist) {
@@ -667,7 +706,7 @@ int rl_finish(rl_trainer *t, double *train_score, double *valid_score)
     RL_HIP(hipSetDevice(t->p.device));
     int rc = sync_rounds(t);
     if (rc) return rc;
-    if ((int64_t)t->n_kept > (int64_t)t->best_round + 1) t->n_kept = t->best_round + 1;      // LambdaMART.java:254-256
+    if (!t->dart.on && (int64_t)t->n_kept > (int64_t)t->best_round + 1) t->n_kept = t->best_round + 1;      // LambdaMART.java:254-256 (DART keeps every tree)
     double ts = 0, vs = 0;
     rc = final_score(t, t->tr, &ts);                                                          // :259
     if (rc) return rc;
@@ -748,7 +787,7 @@ int rl_predict(rl_trainer *t, const float *X, int64_t n_docs, float *out)
     RL_HIP(hipMalloc((void **)&dO, (size_t)n_docs * sizeof(float)));
     RL_HIP(hipMemcpyAsync(dX, X, (size_t)n_docs * t->F * sizeof(float), hipMemcpyHostToDevice, t->stream));
     hipLaunchKernelGGL(k_ensemble_eval, dim3((unsigned)std::min<int64_t>(8192, (n_docs + kThreads - 1) / kThreads)), dim3(kThreads), 0, t->stream,
-                       t->ens, t->ctx.MAXN, t->n_kept, (const float *)dX, n_docs, t->F, t->p.learning_rate, dO, (double *)nullptr);
+                       t->ens, t->ctx.MAXN, t->n_kept, (const float *)dX, n_docs, t->F, (const float *)t->d_tree_w, dO, (double *)nullptr);
     RL_HIP(hipGetLastError());
     RL_HIP(hipStreamSynchronize(t->stream));
     RL_HIP(hipMemcpy(out, dO, (size_t)n_docs * sizeof(float), hipMemcpyDeviceToHost));

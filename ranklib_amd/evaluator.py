@@ -45,7 +45,7 @@ import numpy as np
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, RESUME_NOT_BAGS, REFIT_NOT_BAGS, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, RESUME_NOT_BAGS, REFIT_NOT_BAGS, DART_NOT_BAGS, java_double_str, java_round,
                        stable_desc_order)
 from .metric import DCGScorer, ERRScorer, MetricScorerFactory, score_lists
 
@@ -471,13 +471,14 @@ def main(argv=None):
     finally:      # -resume / -checkpoint / -refit belong to this command line only: a later LambdaMART of the process starts from nothing again
         LambdaMART.resumeFrom, LambdaMART.checkpointFile, LambdaMART.checkpointEvery = None, None, 100
         LambdaMART.refitFrom, LambdaMART.refitDecay = None, 0.0
+        LambdaMART.dartRate, LambdaMART.dartMaxDrop, LambdaMART.dartSeed = 0.0, 50, 0
 
 
 def _main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-fastleaf] [-resume model] [-checkpoint file [-every n]] [-refit model [-decay x]] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-dart rate [-maxdrop n] [-dartseed s]] [-fastleaf] [-resume model] [-checkpoint file [-every n]] [-refit model [-decay x]] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
               "(-load also reads RankNet, LambdaRank and ListNet models; several -load: the models of a -kcv run, model i for fold i of the file, "
               "or for the i-th -test file) | -test f [-idv out] | -test f -score s | -rank f -indri out (no model: the file's own order, or the order of the numbers in s) | "
@@ -493,7 +494,10 @@ def _main(argv=None):
               "every n-th round (default 100), complete or not at all | "
               "-refit model [-decay x] is an rlhip extension of a -train -ranker 6|0 run: the model's trees keep their features and thresholds and get "
               "new leaf values from the training file, stored as x * old + (1 - x) * new (x in [0, 1), default 0: the new values alone); -tree stays "
-              "the total: equal to the model's tree count the run only refits, larger it trains further behind the refit trees")
+              "the total: equal to the model's tree count the run only refits, larger it trains further behind the refit trees | "
+              "-dart rate [-maxdrop n] [-dartseed s] is an rlhip extension of a -train -ranker 6|0 run: dropout boosting, every round leaves each earlier "
+              "tree out with probability rate (in (0, 1]; at most n of them, default 50, 0: no limit; s seeds the draw, default 0) before it fits its "
+              "tree, then rescales them and the new tree; no early stopping, no roll-back; the saved model is ordinary model text with a weight per tree")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
     testFiles, savedModelFiles = [], []
@@ -506,6 +510,8 @@ def _main(argv=None):
     LambdaMART.refitFrom, LambdaMART.refitDecay = None, 0.0                                             # -refit, -decay (rlhip extensions)
     resumeFile, everyGiven = "", False
     refitFile, decayGiven = "", None
+    LambdaMART.dartRate, LambdaMART.dartMaxDrop, LambdaMART.dartSeed = 0.0, 50, 0                        # -dart, -maxdrop, -dartseed (rlhip extensions)
+    dartGiven = maxdropGiven = dartseedGiven = False
     rankerType = 4                                          # the reference's default is Coordinate Ascent (:83)
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)
     ttSplit = tvSplit = 0.0
@@ -552,6 +558,15 @@ def _main(argv=None):
             RFRanker.rType = RankerType(rt)
         elif a == "-seed": RFRanker.seed = FeatureHistogram.seed = CoorAscent.seed = int(nxt())     # rlhip extension: the Java draws are unseeded
         elif a == "-fastleaf": LambdaMART.fastLeaf = True   # rlhip extension: RL_FLAG_FAST_LEAF for -ranker 6 / 0 / 8 (leaf values within tolerance, not bit for bit)
+        elif a == "-dart":                                  # rlhip extension: DART, dropout boosting
+            LambdaMART.dartRate = float(nxt())
+            dartGiven = True
+        elif a == "-maxdrop":
+            LambdaMART.dartMaxDrop = int(nxt())
+            maxdropGiven = True
+        elif a == "-dartseed":
+            LambdaMART.dartSeed = int(nxt())
+            dartseedGiven = True
         elif a == "-resume": resumeFile = nxt()             # rlhip extension: the saved model whose trees are this run's first rounds
         elif a == "-refit": refitFile = nxt()               # rlhip extension: the saved model whose trees get new leaf values from this run's data
         elif a == "-decay": decayGiven = float(nxt())       # rlhip extension: the share of the old leaf value a refit keeps
@@ -595,6 +610,23 @@ def _main(argv=None):
             cur.unknown()                                   # :369-371 (incl. the documented -silent)
     if not testMetric:
         testMetric = trainMetric                            # :379-381
+    if dartGiven or maxdropGiven or dartseedGiven:
+        if not dartGiven:
+            raise RankLibError("rlhip: %s belongs to -dart rate" % ("-maxdrop n" if maxdropGiven else "-dartseed s"))
+        if not (0.0 < LambdaMART.dartRate <= 1.0):                         # (NaN fails both comparisons)
+            raise RankLibError("rlhip: -dart must be in (0, 1] (got %s): the probability that a round leaves an earlier tree out" % LambdaMART.dartRate)
+        if LambdaMART.dartMaxDrop < 0:
+            raise RankLibError("rlhip: -maxdrop must be >= 0 (got %d; 0: no limit)" % LambdaMART.dartMaxDrop)
+        if not 0 <= LambdaMART.dartSeed < 2 ** 64:
+            raise RankLibError("rlhip: -dartseed must be an unsigned 64-bit number (got %d)" % LambdaMART.dartSeed)
+        if not trainFile:
+            raise RankLibError("rlhip: -dart is a way to train: it needs -train")
+        if rankerType == 8:
+            raise RankLibError(DART_NOT_BAGS)
+        if rankerType not in (0, 6):
+            raise RankLibError("rlhip: -dart is built for the tree trainers, -ranker 6 (LambdaMART) and -ranker 0 (MART), not for -ranker %d" % rankerType)
+        if resumeFile or refitFile:
+            raise RankLibError("rlhip: -dart together with %s: a DART run keeps the leaf of every document in every tree it grew, a saved model has none" % ("-resume" if resumeFile else "-refit"))
     if refitFile or decayGiven is not None:
         if not refitFile:
             raise RankLibError("rlhip: -decay x belongs to -refit model")

@@ -493,6 +493,8 @@ RESUME_NOT_BAGS = ("rlhip: -resume / -checkpoint continue one LambdaMART (-ranke
                    "(-ranker 8) are trainers of their own and are not built for it")
 REFIT_NOT_BAGS = ("rlhip: -refit recomputes the leaf values of one LambdaMART (-ranker 6) or MART (-ranker 0) model; the bags of Random Forests "
                   "(-ranker 8) are trainers of their own and are not built for it")
+DART_NOT_BAGS = ("rlhip: -dart trains one LambdaMART (-ranker 6) or MART (-ranker 0) model with dropout; the bags of Random Forests "
+                 "(-ranker 8) are trainers of their own and are not built for it")
 
 
 class LambdaMART(Ranker):
@@ -519,6 +521,11 @@ class LambdaMART(Ranker):
     # TOTAL: equal to the model's tree count the run only refits, larger it trains further behind the refit trees
     refitFrom = None
     refitDecay = 0.0
+    # -dart / -maxdrop / -dartseed: dropout boosting.  Every round leaves each earlier tree out with probability dartRate (at most
+    # dartMaxDrop of them, 0: no limit; dartSeed seeds the draw) before its lambdas are taken, and rescales them and the new tree afterwards.  0: off
+    dartRate = 0.0
+    dartMaxDrop = 50
+    dartSeed = 0
     _RANKER = "LAMBDAMART"
 
     def __init__(self, samples=None, features=None, scorer=None):
@@ -543,6 +550,12 @@ class LambdaMART(Ranker):
                       device=cls.device, metric=metric, ranker=self._RANKER, flags=N.RL_FLAG_FAST_LEAF if cls.fastLeaf else 0,
                       feature_sampling_rate=FeatureHistogram.samplingRate, seed=FeatureHistogram.seed)
         feed_trainer(self, t, metric, lambda lists: train if lists is self.samples else flatten(lists, self.features), feature_ids=self.features)
+        if cls.dartRate > 0:
+            if cls.resumeFrom is not None or cls.refitFrom is not None:
+                raise RankLibError("rlhip: dartRate together with resumeFrom / refitFrom: a DART run keeps the leaf of every document in every tree it grew, a saved model has none")
+            t.set_dart(cls.dartRate, cls.dartMaxDrop, cls.dartSeed)
+            logger.info("DART: drop rate %s, at most %s trees a round, seed %d; early stopping and the roll-back to the best validation round are off",
+                        cls.dartRate, cls.dartMaxDrop if cls.dartMaxDrop > 0 else "all", cls.dartSeed)
         t.init()
         self._resumed, self._resume_stop = 0, False
         if cls.resumeFrom is not None:
@@ -984,6 +997,8 @@ class RFRanker(Ranker):
             raise RankLibError(RESUME_NOT_BAGS)
         if LambdaMART.refitFrom is not None:
             raise RankLibError(REFIT_NOT_BAGS)
+        if LambdaMART.dartRate > 0:
+            raise RankLibError(DART_NOT_BAGS)
         self.ensembles = [None] * cls.nBag
         LambdaMART.nTrees = cls.nTrees
         LambdaMART.nTreeLeaves = cls.nTreeLeaves
