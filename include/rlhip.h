@@ -246,6 +246,33 @@ int rl_get_tree_weights(const rl_trainer *t, float *out, int32_t cap, int32_t *n
 /* the set D a round that has been enqueued dropped, ascending; *n = k, ids may be NULL.  RL_ERR_STATE without DART, RL_ERR_INVALID: round out of range */
 int rl_dart_dropped(const rl_trainer *t, int32_t round, int32_t *ids, int32_t cap, int32_t *n);
 
+/* The ranking objective of an RL_RANKER_LAMBDAMART trainer.  After rl_create, before rl_init.
+ * RL_OBJECTIVE_LAMBDA: RankLib's pairwise lambda with the train metric's swap change, the default.
+ * RL_OBJECTIVE_XENDCG: the cross-entropy NDCG loss (Bruch, "An Alternative Cross Entropy Loss for Learning-to-Rank"; LightGBM's rank_xendcg), listwise,
+ * O(n) a list, no ranked order.  The train metric keeps deciding the per-round train / validation metric and early stopping; it no longer enters lambda.
+ * Round m is 0-based.  A list has documents j = 0 .. n-1 in file order, s_j the document's f64 model score, l_j its float label, i_j its index in the
+ * training set.  Every operation is IEEE f64 with one rounding and no contraction, exp is fdlibm's e_exp (as everywhere in the library), every sum a
+ * serial chain from 0.0 in ascending j:
+ *   n <= 1:        lambda = 0, w = 0
+ *   gamma_j      = (feature_key(root_hash(seed ^ 0x58454E44, m), i_j) >> 11) * 2^-53, the hashes of the feature sampling (oracle: ro_root_hash, ro_feature_key)
+ *   target:        phi_j = ldexp(1.0, (int)l_j) - gamma_j;  P = sum phi_j;  inv = 1.0 / P      (P > 0 always: no epsilon)
+ *   softmax:       M = max_j s_j;  e_j = exp(s_j - M);  S = sum e_j;  rho_j = e_j / S
+ *   guard:         d_j = max(1.0 - rho_j, 2^-52)      (ours, not LightGBM's: a list that one score dominates has rho_j == 1.0)
+ *   first order:   a_j = rho_j - phi_j * inv;  b_j = a_j / d_j;  B = sum b_j
+ *   second order:  c_j = rho_j * (B - b_j);  g_j = c_j / d_j;  G = sum g_j
+ *   third order:   h_j = rho_j * (G - g_j)
+ *   outputs:       lambda_j = -((a_j + c_j) + h_j);  w_j = rho_j * (1.0 - rho_j), the unguarded difference
+ * Leaf values stay RankLib's: the float running sums s1 / s2, 0 when s2 == 0, or the RL_FLAG_FAST_LEAF reduction.  Flags, feature sampling, DART,
+ * rl_adopt_model_text and rl_refit_model_text compose with it.
+ * RL_ERR_INVALID: a null handle, an unknown objective, an RL_RANKER_MART trainer.  RL_ERR_STATE: after rl_init.  rl_init of an XE-NDCG trainer is
+ * RL_ERR_UNSUPPORTED when it is sharded (gamma is keyed by the global document index) or holds a label above 30 (the message states the label). */
+enum { RL_OBJECTIVE_LAMBDA = 0, RL_OBJECTIVE_XENDCG = 1 };
+int rl_set_objective(rl_trainer *t, int32_t objective, uint64_t seed);
+/* k_lambda_xe on caller-given host arrays, without a trainer: lambda[i], w[i] of round `round` for the lists qoff[0 .. n_queries] over scores / labels,
+ * document i's index being i.  tile: documents of a tile, 0 = the default (values above it are the default too).  On the current device. */
+int rl_debug_xe_lambdas(const double *scores, const float *labels, const int32_t *qoff, int32_t n_queries, uint64_t seed, int32_t round, int32_t tile,
+                        double *lambda, double *w);
+
 /* Enqueue n rounds without any host synchronisation (no validation set allowed: early stopping needs
  * the host).  rl_sync waits for them; trees and per-round metrics are then available through
  * rl_get_tree / rl_get_round_metrics. */

@@ -117,6 +117,7 @@ ARM = dict(HIST_ROOT=0, HIST_CHILD=12, RANK_TINY=24, RANK_MIXED=25, RANK_WAVE_LO
            SET_P8=48, SET_DM_ROOT=49, SET_DM_DIV=50, SET_SUB_CHILD=51, SET_HIST_NT=52, SET_ANY_RUNS=53, SET_CROWS=54, SET_TIE_ON=55, SET_NODE_DIV=56,
            SET_NODE_MIN=57, SET_BALANCE=58, SET_BALANCE_TARGET=59, SET_BALANCE_MIN=60, SET_BALANCE_CAP=61, SET_NODE_CHUNK=62, SET_MAX_CHUNKS=63, REPLAY_TILED=64, REPLAY_DIRECT=65, COUNT_=66)
 KERNEL = dict(HIST_ROOT=0, HIST_NODE=1, LAMBDA=2, DART_DROP=3)
+OBJECTIVE = {"lambda": 0, "xendcg": 1}
 
 # every symbol include/rlhip.h declares (tests/test_abi.py checks the .so exports all of them)
 ABI_SYMBOLS = [
@@ -155,6 +156,7 @@ ABI_SYMBOLS = [
     "rl_model_predict_interactions", "rl_debug_interact_times", "rl_debug_interact_passes",
     "rl_model_predict_shap_background", "rl_debug_interv_times", "rl_debug_interv_passes",
     "rl_set_dart", "rl_get_tree_weights", "rl_dart_dropped",
+    "rl_set_objective", "rl_debug_xe_lambdas",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -330,6 +332,9 @@ def lib():
         L.rl_set_dart.argtypes = [vp, C.c_float, i32, C.c_uint64]
         L.rl_get_tree_weights.argtypes = [vp, vp, i32, C.POINTER(i32)]
         L.rl_dart_dropped.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
+    if hasattr(L, "rl_set_objective"):        # (A/B builds of older sources have one objective)
+        L.rl_set_objective.argtypes = [vp, i32, C.c_uint64]
+        L.rl_debug_xe_lambdas.argtypes = [vp, vp, vp, i32, C.c_uint64, i32, i32, vp, vp]
     if hasattr(L, "rl_refit_model_text"):     # (A/B builds of older sources cannot refit)
         L.rl_refit_model_text.argtypes = [vp, C.c_char_p, C.c_float, C.POINTER(i32)]
         L.rl_debug_refit_stats.argtypes = [vp, C.POINTER(i64)]
@@ -474,6 +479,16 @@ def debug_fast_sum(x, seg_start=None, device=0):
     out32 = np.zeros(len(seg) - 1, np.float32)
     check(lib().rl_debug_fast_sum(device, x.ctypes.data, len(x), seg.ctypes.data, len(seg) - 1, out64.ctypes.data, out32.ctypes.data))
     return out64, out32
+
+
+def debug_xe_lambdas(scores, labels, qoff, seed=0, round=0, tile=0):
+    """k_lambda_xe (rl_xe.inc) on host arrays, document i's index being i; returns (lambda, w), float64"""
+    s = np.ascontiguousarray(scores, np.float64)
+    lab = np.ascontiguousarray(labels, np.float32)
+    q = np.ascontiguousarray(qoff, np.int32)
+    lam, w = np.zeros(len(s), np.float64), np.zeros(len(s), np.float64)
+    check(lib().rl_debug_xe_lambdas(s.ctypes.data, lab.ctypes.data, q.ctypes.data, len(q) - 1, int(seed), int(round), int(tile), lam.ctypes.data, w.ctypes.data))
+    return lam, w
 
 
 def set_err_max(max_gain):
@@ -652,6 +667,13 @@ class Trainer:
         if not hasattr(lib(), "rl_set_dart"):
             raise RankLibError("this librlhip.so has no rl_set_dart: it cannot train with DART")
         check(lib().rl_set_dart(self.h, float(rate_drop), int(max_drop), int(seed)))
+
+    def set_objective(self, objective, seed=0):
+        """the ranking objective: "lambda" (RankLib's pairwise lambda, the default) or "xendcg" (the listwise cross-entropy NDCG loss,
+        seed keys its gamma draws); before init()"""
+        if not hasattr(lib(), "rl_set_objective"):
+            raise RankLibError("this librlhip.so has no rl_set_objective: it trains on the pairwise lambda only")
+        check(lib().rl_set_objective(self.h, OBJECTIVE[objective] if isinstance(objective, str) else int(objective), int(seed)))
 
     def tree_weights(self):
         """the float weight of every kept tree (learning_rate each without DART)"""

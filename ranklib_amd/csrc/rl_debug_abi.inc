@@ -106,6 +106,32 @@ int rl_debug_fast_sum(int32_t device, const double *x, int64_t n, const int64_t 
     return RL_OK;
 }
 
+int rl_debug_xe_lambdas(const double *scores, const float *labels, const int32_t *qoff, int32_t n_queries, uint64_t seed, int32_t round, int32_t tile,
+                        double *lambda, double *w)
+{
+    if (!scores || !labels || !qoff || !lambda || !w || n_queries < 1 || round < 0 || tile < 0) return fail(RL_ERR_INVALID, "bad argument");
+    const int64_t n = qoff[n_queries];
+    if (n < 1 || n > 2147483647 / 2) return fail(RL_ERR_INVALID, "bad argument");
+    std::string err;
+    const int rcl = check_lists("rl_debug_xe_lambdas", labels, n, qoff, n_queries, err);
+    if (rcl) return fail(rcl, err);
+    for (int64_t i = 0; i < n; i++) if (labels[i] > (float)kXeMaxLabel) return fail(RL_ERR_UNSUPPORTED, "rl_debug_xe_lambdas: relevance label above " + std::to_string(kXeMaxLabel));
+    std::vector<XeBlock> blocks;
+    xe_pack(qoff, n_queries, xe_tile(tile), blocks);
+    DevPool pool;
+    double *d_s = nullptr, *d_max = nullptr; float *d_l = nullptr; int32_t *d_q = nullptr; XeBlock *d_b = nullptr; double2 *d_lw = nullptr;
+    RL_HIP(pool.upload(&d_s, scores, (size_t)n)); RL_HIP(pool.upload(&d_l, labels, (size_t)n)); RL_HIP(pool.upload(&d_q, qoff, (size_t)n_queries + 1));
+    RL_HIP(pool.upload(&d_b, (const XeBlock *)blocks.data(), blocks.size()));
+    RL_HIP(pool.alloc(&d_lw, (size_t)n)); RL_HIP(pool.alloc(&d_max, blocks.size()));
+    launch_lambda_xe(nullptr, d_s, d_l, d_q, d_b, (int)blocks.size(), xe_tile(tile), seed, round, d_lw, d_max);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipDeviceSynchronize());
+    std::vector<double2> lw((size_t)n);
+    RL_HIP(hipMemcpy(lw.data(), d_lw, (size_t)n * sizeof(double2), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; i++) { lambda[i] = lw[(size_t)i].x; w[i] = lw[(size_t)i].y; }
+    return RL_OK;
+}
+
 int rl_debug_membench(int32_t device, int32_t mode, int64_t bytes, int32_t stride, int32_t iters, double *avg_ms, double *alg_bytes)
 {
     if (!avg_ms || bytes < 4096 || iters < 1 || mode < 0 || mode > 9 || (mode == 3 && stride < 1)) return fail(RL_ERR_INVALID, "bad argument");

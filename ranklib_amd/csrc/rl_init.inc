@@ -808,7 +808,8 @@ static int init_lambda_state(rl_trainer *t)
         if ((size_t)N * c.k * sizeof(double2) > ((size_t)16 << 30)) return fail(RL_ERR_UNSUPPORTED, "this metric cutoff needs more than 16 GiB of pair terms");
         RL_HIP(t->pool.alloc(&t->d_T, (size_t)N * c.k));
     }
-    RL_HIP(t->pool.alloc(&t->d_wmax, (size_t)std::max(std::max(d.Q, (N + kThreads - 1) / kThreads), 2048) + 1));
+    t->wmax_cap = (size_t)std::max(std::max(d.Q, (N + kThreads - 1) / kThreads), 2048) + 1;
+    RL_HIP(t->pool.alloc(&t->d_wmax, t->wmax_cap));
     if (c.metric == RL_METRIC_MAP) RL_HIP(t->pool.alloc(&d.d_aux_i, (size_t)N));
     if (c.metric == RL_METRIC_RR) RL_HIP(t->pool.alloc(&d.d_aux_i, (size_t)2 * d.Q));      // firstRank, secondRank of every list (written by the rank kernels)
     if (c.metric == RL_METRIC_ERR) {     // R[] / np[]: the rank kernels only ever write the top min(k, n) positions of a list, the rest stays 0
@@ -862,6 +863,32 @@ static int init_dart(rl_trainer *t)
     da.dropped.clear();
     RL_HIP(hipFuncSetAttribute((const void *)k_dart_drop<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDartLdsBytes));
     RL_HIP(hipFuncSetAttribute((const void *)k_dart_drop<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kDartLdsBytes));
+    return RL_OK;
+}
+
+// ---- XE-NDCG (rl_set_objective, rl_xe.inc): what it cannot be combined with, then the block table of k_lambda_xe ----
+// at the top of rl_init: gamma is keyed by the document's index in the whole training set, phi is built from the label's exponent
+static int xe_precheck(rl_trainer *t)
+{
+    if (!t->xe.on) return RL_OK;
+    if (t->dist) return fail(RL_ERR_UNSUPPORTED, "XE-NDCG with a sharded trainer: gamma is keyed by the global document index, a shard knows its own");
+    for (int64_t i = 0; i < t->tr.N; i++)
+        if (t->tr.labels[(size_t)i] > (float)kXeMaxLabel)
+            return fail(RL_ERR_UNSUPPORTED, "XE-NDCG: relevance label " + std::to_string((int)t->tr.labels[(size_t)i]) + " of document " + std::to_string(i) +
+                                            " is above " + std::to_string(kXeMaxLabel) + " (phi = 2^label)");
+    return RL_OK;
+}
+
+static int init_xe(rl_trainer *t)
+{
+    XeState &x = t->xe;
+    if (!x.on) return RL_OK;
+    x.tile = xe_tile(t->knobs.xe_tile);
+    std::vector<XeBlock> blocks;
+    xe_pack(t->tr.qoff.data(), t->tr.Q, x.tile, blocks);
+    x.n_blocks = (int32_t)blocks.size();
+    if ((size_t)x.n_blocks > t->wmax_cap) return fail(RL_ERR_UNSUPPORTED, "XE-NDCG: " + std::to_string(x.n_blocks) + " blocks, room for the max |lambda| of " + std::to_string(t->wmax_cap));
+    RL_HIP(t->pool.upload(&x.d_blocks, (const XeBlock *)blocks.data(), blocks.size()));
     return RL_OK;
 }
 

@@ -36,7 +36,7 @@ struct Knobs {
     // -- growth step: chunks, grids, kernel choice
     Opt node_div, balance_target, balance_min, balance_cap, fin_split, hist_nt, hist_grid, trace_tree;
     // (the initialisers are the defaults of read(): a trainer that rl_create did not make -- rl_debug_float_chain's -- runs the default paths)
-    int node_min = 256, sub_child = 16, p8 = 1, dm_div = 1, csc_dens = 3, crows = -1, step_ahead = 1, dist_ahead = 1, piece_force = 0, lam_side = 1, tiny_min = 4096, dart_chunk = 0;
+    int node_min = 256, sub_child = 16, p8 = 1, dm_div = 1, csc_dens = 3, crows = -1, step_ahead = 1, dist_ahead = 1, piece_force = 0, lam_side = 1, tiny_min = 4096, dart_chunk = 0, xe_tile = 0;
     size_t hist_ldspad = 0, tie_walk_max = 24576, tie_slack = (size_t)64 << 20;
     double dist_timeout_s = 300.0;
     bool balance = true, skip_last = true, step2 = true, sel2_wide = true, fused_quant = true, score_stream = true, dm_root = false, lam_compact = false;
@@ -83,6 +83,8 @@ struct Knobs {
         refit_direct = present("RLHIP_REFIT_DIRECT");                                           // k_refit_route reads the rows from global memory instead of an LDS tile (cross-check, tools/refit_bench.py)
         // -- DART (rl_dart.inc)
         dart_chunk = std::max(0, value("RLHIP_DART_CHUNK", 0));                                 // dropped trees whose output tables k_dart_drop stages per chunk (default, and at most: what fits half its LDS); the tests force 1 and 2
+        // -- XE-NDCG (rl_xe.inc)
+        xe_tile = std::max(0, value("RLHIP_XE_TILE", 0));                                       // documents of a tile of k_lambda_xe (default, and at most: the build constant kXeTile); the tests force 64
         // -- lazy Java-order tie-break (rl_tie.inc, rl_tie_host.inc)
         tie_off = present("RLHIP_TIE_OFF");                                                     // keep the first candidate of an exact tie
         tie_no_xdefer = present("RLHIP_TIE_NO_XDEFER");                                         // stall on ties over several features instead of deferring them

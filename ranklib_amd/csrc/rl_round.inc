@@ -81,7 +81,7 @@ static int enqueue_dart_drop(rl_trainer *t)
     RL_HIP(hipGetLastError());
     // the lambdas rank on s'.  The ranking writes d_ndcg (values nobody reads): the previous round's metric mean on the side stream may still read it
     if (!t->has_valid && t->side_pending) RL_HIP(hipStreamWaitEvent(s, t->ev_metric, 0));
-    return c.mart ? RL_OK : launch_rank(t, t->tr, c.scores, t->tr.d_ndcg, true);       // (MART's residuals need no ranking)
+    return (c.mart || t->xe.on) ? RL_OK : launch_rank(t, t->tr, c.scores, t->tr.d_ndcg, true);       // (MART's residuals and XE-NDCG need no ranking)
 }
 
 // ---- DART, in front of the score update: s' + r back into the scores, the round's w_m for the score kernels, the weights, the new tree's history row ----
@@ -116,6 +116,11 @@ static int enqueue_lambdas(rl_trainer *t, int &n_max)
         n_max = std::min(2048, (c.N + kThreads - 1) / kThreads);
         t->arms[RL_ARM_LAM_MART]++;
         hipLaunchKernelGGL(k_mart_residual, dim3(n_max), dim3(kThreads), 0, s, c.labels, (const double *)c.scores, c.lw, c.N, t->d_wmax);
+    } else if (t->xe.on) {   // XE-NDCG (rl_xe.inc): listwise, O(n) a list, from the scores in file order -- no ranked order, no metric in lambda
+        // (counted under no RL_ARM_LAM_* arm: the arm table is full, as for P / RR below)
+        ScopedTiming tm(t, RL_KERNEL_LAMBDA, (double)c.N * 28.0);
+        n_max = t->xe.n_blocks;
+        launch_lambda_xe(s, c.scores, c.labels, c.qoff, t->xe.d_blocks, n_max, t->xe.tile, t->xe.seed, m, c.lw, t->d_wmax);
     } else {   // K1 lambdas: pair terms in parallel, then ordered accumulation (ranked order comes from the previous
         // round's k_rank_* / from rl_init for round 0)
         ScopedTiming tm(t, RL_KERNEL_LAMBDA, (double)c.N * 28.0);

@@ -35,6 +35,8 @@
 #include "rl_dist.inc"
 #include "rl_dart_host.h"
 #include "rl_dart.inc"
+#include "rl_xe_host.h"
+#include "rl_xe.inc"
 #include "rl_model.h"
 
 namespace rl {
@@ -119,7 +121,7 @@ struct rl_trainer {
     int32_t *d_seg_buf = nullptr;
     double2 *d_fast_part = nullptr, *d_fast_sums = nullptr; int64_t fast_slots = 0;      // RL_FLAG_FAST_LEAF (rl_fast_leaf.inc): tile partials [fast_slots], R of every leaf [MAXN + 1]
     double2 *d_T = nullptr;                  // pair terms of the lambda computation [N][k]
-    double *d_wmax = nullptr;                // per-block max |lambda| of the lambda launches
+    double *d_wmax = nullptr; size_t wmax_cap = 0;      // per-block max |lambda| of the lambda launches, and the blocks it has room for
     float *d_vmetric = nullptr;
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending[RL_KERNEL_COUNT_];
@@ -145,6 +147,7 @@ struct rl_trainer {
     // a weight per tree: learning_rate in every slot unless DART (rl_dart.inc) rescales them; the host's copy is what rl_get_tree_weights and the model text read
     float *d_tree_w = nullptr; std::vector<float> h_tree_w;
     DartState dart;
+    XeState xe;                              // the XE-NDCG objective (rl_set_objective, rl_xe.inc)
 };
 
 namespace rl {
@@ -414,6 +417,17 @@ int rl_set_dart(rl_trainer *t, float rate_drop, int32_t max_drop, uint64_t seed)
     return RL_OK;
 }
 
+int rl_set_objective(rl_trainer *t, int32_t objective, uint64_t seed)
+{
+    if (check_trainer(t)) return RL_ERR_INVALID;
+    if (objective != RL_OBJECTIVE_LAMBDA && objective != RL_OBJECTIVE_XENDCG) return fail(RL_ERR_INVALID, "rl_set_objective: unknown objective " + std::to_string(objective));
+    if (t->p.ranker != RL_RANKER_LAMBDAMART) return fail(RL_ERR_INVALID, "rl_set_objective: MART fits residuals, it has no ranking objective to choose");
+    if (t->inited) return fail(RL_ERR_STATE, "rl_set_objective must be called before rl_init");
+    t->xe.on = objective == RL_OBJECTIVE_XENDCG;
+    t->xe.seed = seed;
+    return RL_OK;
+}
+
 int rl_get_tree_weights(const rl_trainer *t, float *out, int32_t cap, int32_t *n)
 {
     if (check_trainer(t)) return RL_ERR_INVALID;
@@ -613,6 +627,7 @@ int rl_init(rl_trainer *t)
     RL_HIP(hipSetDevice(t->p.device));
     RL_HIP(hipDeviceSynchronize());      // uploads of rl_set_* went through the null stream; t->stream is non-blocking
     int rcd = dart_precheck(t);          // (what DART cannot be combined with is known before anything is built)
+    if (!rcd) rcd = xe_precheck(t);
     if (rcd) return rcd;
     InitWork w;
     int rc = init_shape(t, w);
@@ -627,6 +642,7 @@ int rl_init(rl_trainer *t)
     if (!rc) rc = init_dist_state(t, w);
     if (!rc) rc = init_lambda_state(t);
     if (!rc) rc = init_dart(t);
+    if (!rc) rc = init_xe(t);
     if (rc) return rc;
     RL_HIP(hipDeviceSynchronize());
     t->inited = true;

@@ -45,7 +45,7 @@ import numpy as np
 from ._native import RankLibError
 from . import normalizer
 from .features import FeatureManager
-from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, RESUME_NOT_BAGS, REFIT_NOT_BAGS, DART_NOT_BAGS, java_double_str, java_round,
+from .learning import (AdaRank, CoorAscent, RankBoost, LinearRegRank, RankNet, LambdaRank, ListNet, Neuron, DataPoint, FeatureHistogram, LambdaMART, RankerFactory, RankerTrainer, RankerType, RankList, RFRanker, RESUME_NOT_BAGS, REFIT_NOT_BAGS, DART_NOT_BAGS, XE_NOT_BAGS, java_double_str, java_round,
                        stable_desc_order)
 from .metric import DCGScorer, ERRScorer, MetricScorerFactory, score_lists
 
@@ -472,13 +472,14 @@ def main(argv=None):
         LambdaMART.resumeFrom, LambdaMART.checkpointFile, LambdaMART.checkpointEvery = None, None, 100
         LambdaMART.refitFrom, LambdaMART.refitDecay = None, 0.0
         LambdaMART.dartRate, LambdaMART.dartMaxDrop, LambdaMART.dartSeed = 0.0, 50, 0
+        LambdaMART.objective, LambdaMART.xeSeed = "lambda", 0
 
 
 def _main(argv=None):
     args = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not args:
-        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-dart rate [-maxdrop n] [-dartseed s]] [-fastleaf] [-resume model] [-checkpoint file [-every n]] [-refit model [-decay x]] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
+        print("Usage: -train <file> -ranker 4|3|2|9|6|0|8 [-r n -i n -tolerance t -reg slack] [-round n -noeq -max n] [-round n -tc n (RankBoost)] [-L2 reg (Linear Regression)] [-bag n -srate f -frate f -rtype 0|6 -seed n] [-objective lambda|xendcg [-xeseed s]] [-dart rate [-maxdrop n] [-dartseed s]] [-fastleaf] [-resume model] [-checkpoint file [-every n]] [-refit model [-decay x]] [-metric2t NDCG@k|DCG@k|MAP|ERR@k|P@k|RR@k] [-tree n] [-leaf n] [-shrinkage f] [-tc n] [-mls n] [-estop n] "
               "[-validate f] [-test f] [-feature f] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-save model] | -load model [-test f [-idv out]] [-rank f -indri out] [-rank f -score out] "
               "(-load also reads RankNet, LambdaRank and ListNet models; several -load: the models of a -kcv run, model i for fold i of the file, "
               "or for the i-th -test file) | -test f [-idv out] | -test f -score s | -rank f -indri out (no model: the file's own order, or the order of the numbers in s) | "
@@ -497,7 +498,10 @@ def _main(argv=None):
               "the total: equal to the model's tree count the run only refits, larger it trains further behind the refit trees | "
               "-dart rate [-maxdrop n] [-dartseed s] is an rlhip extension of a -train -ranker 6|0 run: dropout boosting, every round leaves each earlier "
               "tree out with probability rate (in (0, 1]; at most n of them, default 50, 0: no limit; s seeds the draw, default 0) before it fits its "
-              "tree, then rescales them and the new tree; no early stopping, no roll-back; the saved model is ordinary model text with a weight per tree")
+              "tree, then rescales them and the new tree; no early stopping, no roll-back; the saved model is ordinary model text with a weight per tree | "
+              "-objective lambda|xendcg [-xeseed s] is an rlhip extension of a -train -ranker 6 run: xendcg fits every tree to the listwise cross-entropy "
+              "NDCG loss (XE-NDCG, O(n) a list) instead of RankLib's pairwise lambda; s seeds its draws, default 0; -metric2t still decides the printed "
+              "metrics and early stopping; the saved model is ordinary model text")
         return 0
     trainFile = validationFile = testFile = featureDescriptionFile = savedModelFile = rankFile = indriRankingFile = scoreFile = modelFile = prpFile = ""
     testFiles, savedModelFiles = [], []
@@ -512,6 +516,8 @@ def _main(argv=None):
     refitFile, decayGiven = "", None
     LambdaMART.dartRate, LambdaMART.dartMaxDrop, LambdaMART.dartSeed = 0.0, 50, 0                        # -dart, -maxdrop, -dartseed (rlhip extensions)
     dartGiven = maxdropGiven = dartseedGiven = False
+    LambdaMART.objective, LambdaMART.xeSeed = "lambda", 0                                               # -objective, -xeseed (rlhip extensions)
+    objectiveGiven = xeseedGiven = False
     rankerType = 4                                          # the reference's default is Coordinate Ascent (:83)
     trainMetric, testMetric = "ERR@10", ""                  # the reference's default train metric (:84)
     ttSplit = tvSplit = 0.0
@@ -567,7 +573,13 @@ def _main(argv=None):
         elif a == "-dartseed":
             LambdaMART.dartSeed = int(nxt())
             dartseedGiven = True
-        elif a == "-resume": resumeFile = nxt()             # rlhip extension: the saved model whose trees are this run's first rounds
+        elif a == "-objective":                             # rlhip extension: what a LambdaMART tree is fitted to
+            LambdaMART.objective = nxt()
+            objectiveGiven = True
+        elif a == "-xeseed":
+            LambdaMART.xeSeed = int(nxt())
+            xeseedGiven = True
+        elif a == "-resume": resumeFile = nxt()            # rlhip extension: the saved model whose trees are this run's first rounds
         elif a == "-refit": refitFile = nxt()               # rlhip extension: the saved model whose trees get new leaf values from this run's data
         elif a == "-decay": decayGiven = float(nxt())       # rlhip extension: the share of the old leaf value a refit keeps
         elif a == "-checkpoint": LambdaMART.checkpointFile = nxt()      # rlhip extension: all trees so far, after every -every n-th round
@@ -627,6 +639,19 @@ def _main(argv=None):
             raise RankLibError("rlhip: -dart is built for the tree trainers, -ranker 6 (LambdaMART) and -ranker 0 (MART), not for -ranker %d" % rankerType)
         if resumeFile or refitFile:
             raise RankLibError("rlhip: -dart together with %s: a DART run keeps the leaf of every document in every tree it grew, a saved model has none" % ("-resume" if resumeFile else "-refit"))
+    if objectiveGiven or xeseedGiven:
+        if LambdaMART.objective not in ("lambda", "xendcg"):
+            raise RankLibError("rlhip: -objective must be lambda or xendcg (got %s)" % LambdaMART.objective)
+        if xeseedGiven and LambdaMART.objective != "xendcg":
+            raise RankLibError("rlhip: -xeseed s belongs to -objective xendcg")
+        if not 0 <= LambdaMART.xeSeed < 2 ** 64:
+            raise RankLibError("rlhip: -xeseed must be an unsigned 64-bit number (got %d)" % LambdaMART.xeSeed)
+        if not trainFile:
+            raise RankLibError("rlhip: -objective is a way to train: it needs -train")
+        if rankerType == 8:
+            raise RankLibError(XE_NOT_BAGS)
+        if rankerType != 6:
+            raise RankLibError("rlhip: -objective chooses the ranking objective of -ranker 6 (LambdaMART), not of -ranker %d" % rankerType)
     if refitFile or decayGiven is not None:
         if not refitFile:
             raise RankLibError("rlhip: -decay x belongs to -refit model")

@@ -495,6 +495,8 @@ REFIT_NOT_BAGS = ("rlhip: -refit recomputes the leaf values of one LambdaMART (-
                   "(-ranker 8) are trainers of their own and are not built for it")
 DART_NOT_BAGS = ("rlhip: -dart trains one LambdaMART (-ranker 6) or MART (-ranker 0) model with dropout; the bags of Random Forests "
                  "(-ranker 8) are trainers of their own and are not built for it")
+XE_NOT_BAGS = ("rlhip: -objective xendcg trains one LambdaMART (-ranker 6) model on the XE-NDCG loss; the bags of Random Forests "
+               "(-ranker 8) are trainers of their own and are not built for it")
 
 
 class LambdaMART(Ranker):
@@ -526,6 +528,10 @@ class LambdaMART(Ranker):
     dartRate = 0.0
     dartMaxDrop = 50
     dartSeed = 0
+    # -objective / -xeseed: what a tree is fitted to.  "lambda": RankLib's pairwise lambda with the train metric's swap change; "xendcg":
+    # the listwise cross-entropy NDCG loss (LambdaMART only), whose gamma draws xeSeed keys.  The train metric still decides the printed metrics and early stopping
+    objective = "lambda"
+    xeSeed = 0
     _RANKER = "LAMBDAMART"
 
     def __init__(self, samples=None, features=None, scorer=None):
@@ -556,6 +562,13 @@ class LambdaMART(Ranker):
             t.set_dart(cls.dartRate, cls.dartMaxDrop, cls.dartSeed)
             logger.info("DART: drop rate %s, at most %s trees a round, seed %d; early stopping and the roll-back to the best validation round are off",
                         cls.dartRate, cls.dartMaxDrop if cls.dartMaxDrop > 0 else "all", cls.dartSeed)
+        if cls.objective != "lambda":
+            if cls.objective != "xendcg":
+                raise RankLibError("rlhip: objective must be \"lambda\" or \"xendcg\" (got %r)" % (cls.objective,))
+            if self._RANKER != "LAMBDAMART":
+                raise RankLibError("rlhip: objective xendcg is a ranking objective of LambdaMART; MART fits residuals")
+            t.set_objective("xendcg", cls.xeSeed)
+            logger.info("Objective: XE-NDCG (listwise cross entropy), seed %d; %s decides the printed metrics and early stopping only", cls.xeSeed, self.scorer.name())
         t.init()
         self._resumed, self._resume_stop = 0, False
         if cls.resumeFrom is not None:
@@ -999,6 +1012,8 @@ class RFRanker(Ranker):
             raise RankLibError(REFIT_NOT_BAGS)
         if LambdaMART.dartRate > 0:
             raise RankLibError(DART_NOT_BAGS)
+        if LambdaMART.objective != "lambda":
+            raise RankLibError(XE_NOT_BAGS)
         self.ensembles = [None] * cls.nBag
         LambdaMART.nTrees = cls.nTrees
         LambdaMART.nTreeLeaves = cls.nTreeLeaves
