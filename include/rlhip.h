@@ -1267,6 +1267,32 @@ int  rl_model_predict_partial2(rl_model *m, const float *X, int64_t n_docs, int3
  * last rl_model_predict_partial2 call, summed over its chunks */
 int  rl_debug_partial2_times(double *walk_ms, double *reduce_ms);
 
+/* ---- the leaf every document reaches in every tree, one pass over a file -----------------------------------------------
+ * pred_leaf of XGBoost and LightGBM, apply() of scikit-learn: the leaf embedding behind "GBDT + linear model" pipelines and leaf-level
+ * diagnostics.  LEAF NUMBERS: the leaves of tree t are numbered 0 .. L_t - 1 in Split.leaves() order, left first and depth first: the
+ * order of the nodes with feature == -1 in rl_tree's pre-order, the order rl_refit_model_text's step 3 uses.  leaf(d, t) is the number
+ * of the leaf row d reaches in tree t under the library's one walk rule: value <= threshold goes left, a column the row does not have
+ * reads 0, and feature id 0, NaN thresholds, +-0.0 and subnormals behave exactly as in rl_model_predict.  Tree weights play no part.
+ * rl_model_leaf_counts: *n = the number of trees; leaves [cap] (may be NULL) receives L_t of the first cap trees.
+ * rl_model_predict_leaves: the trees [first_tree, first_tree + n_trees) of the model, n_trees == 0 meaning "through the last tree";
+ * out[d * n_trees + j] (RL_LEAVES_BY_ROW) or out[j * n_docs + d] (RL_LEAVES_BY_TREE) = leaf(d, first_tree + j), n_trees the window's
+ * count.  X and out are HOST pointers; the index d * n_trees + j is 64 bits wide.  The rows go through the device in chunks whose
+ * buffers -- the rows and 2 n_trees bytes of output per row -- stay within 256 MiB, and a chunk's output is copied back before the next
+ * chunk is walked; the result does not depend on the chunking.  A model the tiled packing takes is walked by k_model_leaves_tiled, any
+ * other (and every model under RLHIP_EVAL_GENERIC) by k_model_leaves: rl_model_debug_path reports RL_MODEL_PATH_TILED / _GENERIC
+ * afterwards.  The two kernels give the same integers.  The model's first call makes the kernels' tables and keeps them on the handle,
+ * unguarded: as stated at the top, a handle is used by one thread at a time.
+ * RL_ERR_INVALID, the message naming the cause, before the device is touched: a null model / X / out, n_docs < 0, row_stride < 1, an
+ * unknown layout, a model without trees, first_tree outside the model, n_trees negative or reaching beyond the last tree.
+ * RL_ERR_UNSUPPORTED: more than 2^31 documents per call; a tree of the window with more than 65 536 leaves. */
+enum { RL_LEAVES_BY_ROW = 0, RL_LEAVES_BY_TREE = 1 };
+int  rl_model_leaf_counts(const rl_model *m, int32_t *leaves, int32_t cap, int32_t *n);
+int  rl_model_predict_leaves(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, int32_t first_tree, int32_t n_trees,
+                             int32_t layout, uint16_t *out);
+/* debug (tools/leaves_bench.py): ms between device events around the kernel launches of this thread's last rl_model_predict_leaves
+ * call, summed over its chunks */
+int  rl_debug_leaves_times(double *walk_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,7 @@ ABI_SYMBOLS = [
     "rl_model_predict_shap_background", "rl_debug_interv_times", "rl_debug_interv_passes",
     "rl_set_dart", "rl_get_tree_weights", "rl_dart_dropped",
     "rl_set_objective", "rl_debug_xe_lambdas",
+    "rl_model_leaf_counts", "rl_model_predict_leaves", "rl_debug_leaves_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -352,6 +353,10 @@ def lib():
         L.rl_model_predict_shap_background.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, i32, i64, vp]
         L.rl_debug_interv_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rl_debug_interv_passes.argtypes = [C.POINTER(i32)]
+    if hasattr(L, "rl_model_predict_leaves"):  # (A/B builds of older sources have no leaf indices)
+        L.rl_model_leaf_counts.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        L.rl_model_predict_leaves.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp]
+        L.rl_debug_leaves_times.argtypes = [C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -1110,6 +1115,31 @@ class Model:
                                           out.ctypes.data if ice and out.size else None))
         return base[:rows.shape[0]], mean[:cells], shift2[:cells], out
 
+    def leaf_counts(self):
+        """rl_model_leaf_counts: int32 [trees], the leaves of every tree"""
+        L, n = lib(), C.c_int32(0)
+        if not hasattr(L, "rl_model_predict_leaves"):
+            raise RankLibError("rlhip: this librlhip.so has no leaf indices (rl_model_predict_leaves)")
+        check(L.rl_model_leaf_counts(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), np.int32)
+        check(L.rl_model_leaf_counts(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
+
+    def predict_leaves(self, rows, first_tree=0, n_trees=None, by_tree=False):
+        """rl_model_predict_leaves: uint16 [n_docs][n_trees] (by_tree: [n_trees][n_docs]), the number of the leaf every row reaches in
+        the trees [first_tree, first_tree + n_trees) (n_trees None: through the last tree); a tree's leaves are numbered in pre-order,
+        left first.  rows as in predict_rows."""
+        L, rows, buf = self._contrib_rows(rows)
+        if not hasattr(L, "rl_model_predict_leaves"):
+            raise RankLibError("rlhip: this librlhip.so has no leaf indices (rl_model_predict_leaves)")
+        ask = 0 if n_trees is None else int(n_trees)                  # (0: through the last tree, as the library reads it)
+        nt = ask if ask > 0 else max(0, self.num_trees() - int(first_tree))
+        out = np.zeros((max(nt, 0), rows.shape[0]) if by_tree else (rows.shape[0], max(nt, 0)), np.uint16)
+        obuf = out if out.size else np.zeros(1, np.uint16)          # (a window the library refuses is refused before anything is written)
+        check(L.rl_model_predict_leaves(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], int(first_tree), ask, 1 if by_tree else 0,
+                                        obuf.ctypes.data))
+        return out
+
     def path(self):
         """MODEL_PATH_* of the last predict call: which kernel it took"""
         p = C.c_int32(0)
@@ -1634,6 +1664,13 @@ def partial2_times():
     w, r = C.c_double(0), C.c_double(0)
     check(lib().rl_debug_partial2_times(C.byref(w), C.byref(r)))
     return w.value, r.value
+
+
+def leaves_times():
+    """rl_debug_leaves_times: walk ms of this thread's last predict_leaves call, between device events, summed over its chunks"""
+    w = C.c_double(0)
+    check(lib().rl_debug_leaves_times(C.byref(w)))
+    return w.value
 
 
 def permuted_times():

@@ -22,6 +22,11 @@ struct rl_model {
     std::vector<double> value;
     int64_t cover_rows = 0;
     void *d_cover_nodes = nullptr;          // the trees as k_model_cover stages them (made by the first rl_model_cover call)
+    // leaf indices (rl_leaves.inc), made by the first rl_model_predict_leaves call
+    bool leaves_ready = false;
+    unsigned long long *d_leaf_pack = nullptr;   // eval_pack's nodes with a leaf's number in its value bits, for k_model_leaves_tiled (null: the packing refuses the model)
+    uint16_t *d_leaf_no = nullptr;          // [trees][maxn] node -> leaf number, for k_model_leaves
+    std::vector<int> leaf_depth;            // the trees' depths: a window of trees is dealt to the walkers per call
 };
 
 namespace rl {
@@ -166,8 +171,9 @@ __global__ __launch_bounds__(kEvalThreads) void k_model_eval_tiled(const unsigne
                     // The walker's trees come deepest first.  All eight chains walk for as many steps as the walker's (kEvalPh1 + 1)-th tree has levels, then the
                     // kEvalPh1 deepest for as many as the (kEvalPh2 + 1)-th has, ... : a chain that has reached its leaf in every lane stops costing instructions
                     // (in ONE loop to the deepest tree's depth the shallow chains idled on their leaves, at the cost of their instructions).
+                    // (rl_leaves.inc's leaves_walk_tile holds a copy of this walk, RL_LEAVES_PHASE: a change here is made there too)
                     int step = 0;
-#define RL_EVAL_PHASE(NCH, UNTIL)                                                                                                          \
+#define RL_EVAL_PHASE(NCH, UNTIL)                                                                                                         \
                     for (; step < (UNTIL); step++) {                                                                                       \
                         float x[NCH];                                                                                                      \
                         _Pragma("unroll") for (int u = 0; u < NCH; u++) x[u] = *(const float *)(sXb + ((unsigned)(v[u] >> 32) & 0xffffu)); \

@@ -398,6 +398,11 @@ class Ranker:
         one = self.partialDependence(samples, features=sorted({f for pr in prs for f in pr}), grid=grid)
         return P.summarize2(prs, grids, base, mean, shift2, one, surfaces if ice else None)
 
+    # rlhip: the leaf every document reaches in every tree: one ensemble of trees has them
+    def leaves(self, samples, firstTree=0, nTrees=None, byTree=False):
+        raise RankLibError(LEAVES_NOT_BAGS if self.name() == "Random Forests" else
+                           "rlhip: leaves needs a LambdaMART or MART model: a %s model has no trees" % self.name())
+
     def save(self, modelFile):        # :106-122
         d = modelFile.rsplit("/", 1)[0] if "/" in modelFile else None
         if d:
@@ -495,6 +500,8 @@ REFIT_NOT_BAGS = ("rlhip: -refit recomputes the leaf values of one LambdaMART (-
                   "(-ranker 8) are trainers of their own and are not built for it")
 DART_NOT_BAGS = ("rlhip: -dart trains one LambdaMART (-ranker 6) or MART (-ranker 0) model with dropout; the bags of Random Forests "
                  "(-ranker 8) are trainers of their own and are not built for it")
+LEAVES_NOT_BAGS = ("rlhip: leaves numbers the leaves of one LambdaMART (-ranker 6) or MART (-ranker 0) model; the bags of Random Forests "
+                   "(-ranker 8) are ensembles of their own and are not built for it")
 XE_NOT_BAGS = ("rlhip: -objective xendcg trains one LambdaMART (-ranker 6) model on the XE-NDCG loss; the bags of Random Forests "
                "(-ranker 8) are trainers of their own and are not built for it")
 
@@ -762,6 +769,23 @@ class LambdaMART(Ranker):
         cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(prs))]      # noqa: E731
         one = self.partialDependence(samples, features=sorted({f for pr in prs for f in pr}), grid=grid)
         return P.summarize2(prs, grids, base.astype(np.float64), cut(mean), cut(shift2), one, cut(sc.astype(np.float64)) if ice else None)
+
+    # --- leaf indices in one pass (rlhip) --------------------------------------------------------
+    def leafCounts(self):
+        """the leaves of every tree of the model, int32 [trees]"""
+        return self._model.leaf_counts()
+
+    def leaves(self, samples, firstTree=0, nTrees=None, byTree=False):
+        """uint16 [n_docs][n_trees] (byTree: [n_trees][n_docs]): the number of the leaf every document reaches in the trees [firstTree,
+        firstTree + nTrees) of the model (nTrees None: through the last), a tree's leaves numbered in Split.leaves() order.  samples:
+        RankLists, whose documents go through _native.Model.predict_leaves in chunks of whole lists whose rows stay under
+        EVAL_ROW_BYTES, or an array of rows [n_docs][row_stride] as predict_rows takes them, which is one call."""
+        if isinstance(samples, np.ndarray):
+            return self._model.predict_leaves(samples, firstTree, nTrees, byTree)
+        parts = [self._model.predict_leaves(rows, firstTree, nTrees, byTree) for rows in self._rowChunks(samples)]
+        if not parts:
+            return self._model.predict_leaves(np.zeros((0, 1), np.float32), firstTree, nTrees, byTree)
+        return np.concatenate(parts, axis=1 if byTree else 0)
 
     # --- per-document feature contributions (rlhip, DESIGN.md 26) ----------------------------------------------
     def _rowChunks(self, samples):
