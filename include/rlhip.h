@@ -1293,6 +1293,50 @@ int  rl_model_predict_leaves(rl_model *m, const float *X, int64_t n_docs, int32_
  * call, summed over its chunks */
 int  rl_debug_leaves_times(double *walk_ms);
 
+/* ---- accumulated local effects (ALE) of a tree model, one pass over a file ----------------------------------------------
+ * How the score moves as one feature moves, measured only where the data is (Apley and Zhu): a document is moved between the two edges
+ * of the interval its own value lies in, never to a value far from its own, so correlated columns produce no rows that cannot occur.
+ * columns[0 .. C-1] are feature ids, each >= 0, in any order, repeats allowed; edge_off [C + 1] is a CSR offset array, edge_off[0] == 0;
+ * edges [edge_off[C]] holds f32 values.  The edges of one column are strictly ascending under <: no NaN, no equal values, not -0.0
+ * beside 0.0; +-Infinity are ordinary values.  A column with E_c edges z_0 < ... < z_K has K = E_c - 1 INTERVALS, 1 <= K <=
+ * RL_ALE_MAX_INTERVALS.  CELL (c, k), k = 1 .. K, sits at edge_off[c] - c + k - 1 in the per-cell outputs: edge_off[C] - C cells in all.
+ * OWN VALUE AND INTERVAL: document i's own value v in column c is row[columns[c]], or 0 where columns[c] >= row_stride (the rows are
+ * TAKEN AS PADDED WITH ZEROS TO ANY WIDTH, as in partial dependence).  Where z_0 <= v <= z_K its interval is k = 1 + #{j in 1 .. K-1 :
+ * z_j < v}: v == z_0 falls in interval 1 and v == z_j in interval j.  Otherwise -- v below z_0, above z_K, or NaN -- k = 0: the
+ * document is OUTSIDE and joins no sum.
+ * THE TWO SCORES: lo and hi are Ensemble.eval's float chain (learning/tree/Ensemble.java:110-116, s = (float)((double)s + (double)out *
+ * (double)w), s_0 = 0.0f; v <= thr goes left) on row i with column columns[c] set to z_{k-1} and to z_k; for an outside document both
+ * are its unsubstituted score.  Bit for bit what the two matrices materialised on the host give through rl_model_predict.
+ * PER CELL a count n_k (int64) and S_k, the sum of d = (double)hi - (double)lo over the cell's documents, in ONE FIXED ORDER: with
+ * RL_PARTIAL_SUM_BLOCK = 256, partial p is the serial f64 chain, starting from +0.0, over those documents of [256 p, 256 p + 256) that
+ * lie in the cell, in document order; the total is the serial chain over all partials in order, starting from +0.0.  Every operation
+ * is rounded, no FMA; NaN and Infinity propagate as IEEE gives them.  (A partial without a document of the cell is +0.0 and changes no
+ * total.)  The local effect of the interval is S_k / n_k, the ALE curve their running sum along the feature, centred: the callers'
+ * arithmetic (ranklib_amd/partial.py), a few f64 operations per cell.
+ * out_count [cells] and out_sum [cells]; out_lo, out_hi f32 [C][n_docs] and out_interval int32 [C][n_docs] may each be NULL: then
+ * nothing of that size crosses the bus.  out_base [n_docs] (may be NULL) is the unsubstituted scores; it costs one scoring pass more.
+ * X, columns, edge_off, edges and the outputs are HOST pointers; rows and tables are uploaded once per call.  The columns are processed
+ * in chunks whose device scratch -- 12 bytes per document and column, plus the base -- stays within scratch_bytes (0 = 256 MiB); a
+ * chunk holds at least one column.  The result does not depend on the chunking.  Inside a chunk the kernel takes up to RL_ALE_BATCH
+ * columns per document at a time.
+ * RL_ERR_INVALID, the message naming the argument, all checked before the model so that a machine without a device reaches them: null
+ * X, columns, edge_off, edges, out_count or out_sum; n_docs < 1; row_stride < 1; n_columns < 1; a negative column; edge_off[0] != 0; a
+ * column with fewer than 2 or more than 256 edges ("edge_off[c+1] - edge_off[c] = ..."); an edge that is NaN or not greater than its
+ * predecessor ("edges[c][j] = ..."); scratch_bytes < 0.  Then a null model and a model without trees.  RL_ERR_UNSUPPORTED: more than
+ * 2^31 documents per call.
+ * rl_model_debug_path reports RL_MODEL_PATH_ALE afterwards: one kernel serves packed and unpacked models. */
+#ifndef RL_ALE_BATCH
+#define RL_ALE_BATCH 16
+#endif
+#define RL_ALE_MAX_INTERVALS 255
+enum { RL_MODEL_PATH_ALE = 11 };
+int  rl_model_predict_ale(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *columns, int32_t n_columns,
+                          const int32_t *edge_off, const float *edges, int64_t scratch_bytes, float *out_base, int64_t *out_count,
+                          double *out_sum, float *out_lo, float *out_hi, int32_t *out_interval);
+/* debug (tools/ale_bench.py): ms between device events around the walking and around the reducing launches of this thread's last
+ * rl_model_predict_ale call, summed over its chunks */
+int  rl_debug_ale_times(double *walk_ms, double *reduce_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,7 @@ ABI_SYMBOLS = [
     "rl_set_dart", "rl_get_tree_weights", "rl_dart_dropped",
     "rl_set_objective", "rl_debug_xe_lambdas",
     "rl_model_leaf_counts", "rl_model_predict_leaves", "rl_debug_leaves_times",
+    "rl_model_predict_ale", "rl_debug_ale_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -357,6 +358,9 @@ def lib():
         L.rl_model_leaf_counts.argtypes = [vp, vp, i32, C.POINTER(i32)]
         L.rl_model_predict_leaves.argtypes = [vp, vp, i64, i32, i32, i32, i32, vp]
         L.rl_debug_leaves_times.argtypes = [C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_predict_ale"):  # (A/B builds of older sources have no accumulated local effects)
+        L.rl_model_predict_ale.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
+        L.rl_debug_ale_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -818,6 +822,9 @@ MODEL_PATH_PARTIAL2 = 10                          # rl_model_predict_partial2 (k
 PARTIAL2_TILE_A = PARTIAL2_TILE_B = 8             # RL_PARTIAL2_TILE_A / _B (rlhip.h): the cells of one pair k_model_partial2_scores takes per document at a time
 PARTIAL_BATCH = 16                                # RL_PARTIAL_BATCH (rlhip.h): cells of one column k_model_partial_scores takes per document at a time
 PARTIAL_SUM_BLOCK = 256                           # RL_PARTIAL_SUM_BLOCK (rlhip.h): the documents of one partial sum, part of the definition
+MODEL_PATH_ALE = 11                               # rl_model_predict_ale (k_model_ale_scores, k_ale_reduce)
+ALE_BATCH = 16                                    # RL_ALE_BATCH (rlhip.h): columns k_model_ale_scores takes per document at a time
+ALE_MAX_INTERVALS = 255                           # RL_ALE_MAX_INTERVALS (rlhip.h): intervals of one column at most
 
 
 class Model:
@@ -1114,6 +1121,37 @@ class Model:
                                           grid.ctypes.data, int(scratch_bytes), base.ctypes.data, mean.ctypes.data, shift2.ctypes.data,
                                           out.ctypes.data if ice and out.size else None))
         return base[:rows.shape[0]], mean[:cells], shift2[:cells], out
+
+    def predict_ale(self, rows, columns, edges, local=False, base=False, scratch_bytes=0):
+        """rl_model_predict_ale: accumulated local effects.  edges: one array of f32 interval edges per entry of columns,
+        each strictly ascending, 2 .. 256 of them; cell (c, k), k = 1 .. K_c, is interval k of column c, the cells laid end to end.
+        Returns (int64 count [cells], f64 sum [cells], lo, hi, interval, base): count and sum of d = (double)hi - (double)lo over the
+        documents whose own value lies in the interval, in the fixed order of include/rlhip.h; with local the f32 lo and hi
+        [n_columns][n_docs] -- the scores of rows, padded with zeros to any width, with the column set to the lower and the upper edge
+        of the document's interval -- and the int32 interval [n_columns][n_docs] (0: outside the edges), else None; with base the f32
+        unsubstituted scores [n_docs], else None.  rows as in predict_rows."""
+        L = lib()
+        if not hasattr(L, "rl_model_predict_ale"):
+            raise RankLibError("rlhip: this librlhip.so has no accumulated local effects (rl_model_predict_ale)")
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        cols = np.ascontiguousarray(columns, dtype=np.int32)
+        es = [np.ascontiguousarray(e, dtype=np.float32) for e in edges]
+        if rows.ndim != 2 or cols.ndim != 1 or len(es) != cols.size or any(e.ndim != 1 for e in es):
+            raise RankLibError("rlhip: accumulated local effects take rows [n_docs][row_stride], columns [n_columns] and one 1-d array of edges per column")
+        off = np.zeros(cols.size + 1, np.int32)
+        np.cumsum([e.size for e in es], out=off[1:])
+        flat = np.concatenate(es + [np.zeros(1, np.float32)])      # (never an empty buffer: the library names what is wrong)
+        cells = max(0, int(off[-1]) - int(cols.size))
+        count, total = np.zeros(max(1, cells), np.int64), np.zeros(max(1, cells), np.float64)
+        shape = (int(cols.size), rows.shape[0])
+        lo, hi, iv = (np.zeros(shape, np.float32), np.zeros(shape, np.float32), np.zeros(shape, np.int32)) if local else (None, None, None)
+        bs = np.zeros(max(1, rows.shape[0]), np.float32) if base else None
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None      # noqa: E731
+        buf = rows if rows.size else np.zeros(1, np.float32)
+        cbuf = cols if cols.size else np.zeros(1, np.int32)
+        check(L.rl_model_predict_ale(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], cbuf.ctypes.data, int(cols.size), off.ctypes.data,
+                                     flat.ctypes.data, int(scratch_bytes), ptr(bs), count.ctypes.data, total.ctypes.data, ptr(lo), ptr(hi), ptr(iv)))
+        return count[:cells], total[:cells], lo, hi, iv, None if bs is None else bs[:rows.shape[0]]
 
     def leaf_counts(self):
         """rl_model_leaf_counts: int32 [trees], the leaves of every tree"""
@@ -1663,6 +1701,13 @@ def partial2_times():
     """rl_debug_partial2_times: (walk ms, reduce ms) of this thread's last predict_partial2 call, between device events"""
     w, r = C.c_double(0), C.c_double(0)
     check(lib().rl_debug_partial2_times(C.byref(w), C.byref(r)))
+    return w.value, r.value
+
+
+def ale_times():
+    """rl_debug_ale_times: (walk ms, reduce ms) of this thread's last predict_ale call, between device events"""
+    w, r = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_ale_times(C.byref(w), C.byref(r)))
     return w.value, r.value
 
 

@@ -398,6 +398,34 @@ class Ranker:
         one = self.partialDependence(samples, features=sorted({f for pr in prs for f in pr}), grid=grid)
         return P.summarize2(prs, grids, base, mean, shift2, one, surfaces if ice else None)
 
+    # rlhip: accumulated local effects: how the score moves as one feature moves, measured where the data is
+    def _aleEdges(self, samples, features, intervals):
+        from . import partial as P
+        feats = self._askedFeatures(features, "accumulatedEffects", "vary")
+        dps = [dp for rl in samples for dp in rl.rl]
+        if not dps:
+            raise RankLibError("rlhip: accumulatedEffects needs at least one document")
+        return dps, P.ale_edges(samples, feats, intervals)
+
+    def accumulatedEffects(self, samples, features=None, intervals=20, local=False):
+        """partial.Ale of features (None: the model's own, ascending) on samples: per feature the edges partial.ale_edges gives
+        (intervals + 1 order statistics of its values) and per edge the centred ALE curve, the local effect of the interval ending
+        there and its documents; with local every document's interval and its two scores too.  A document's own value (unknown or
+        missing: 0) picks its interval, and the document is scored with the feature at the interval's lower and at its upper edge; a
+        document outside the edges keeps its value.  This is the generic path, for every ranker: two substituted copies of the
+        documents per feature go through evalLists, and the sums take the fixed order of include/rlhip.h (partial.ale_cell_sums)."""
+        from . import partial as P
+        dps, (feats, edges) = self._aleEdges(samples, features, intervals)
+        counts, totals, los, his, ivs = [], [], [], [], []
+        for f, z in zip(feats, edges):
+            own = np.array([dp.fVals[f] if f < len(dp.fVals) else 0.0 for dp in dps], np.float32)
+            iv = P.ale_intervals(np.where(np.isnan(own), np.float32(0), own), z)
+            lo = self.evalLists(substituted_each(samples, f, z[np.maximum(iv, 1) - 1], iv > 0))[0]
+            hi = self.evalLists(substituted_each(samples, f, z[np.maximum(iv, 1)], iv > 0))[0]
+            n, s = P.ale_cell_sums(lo, hi, iv, len(z) - 1)
+            counts.append(n); totals.append(s); los.append(lo); his.append(hi); ivs.append(iv)
+        return P.summarize_ale(feats, edges, counts, totals, *((los, his, ivs) if local else ()))
+
     # rlhip: the leaf every document reaches in every tree (DESIGN.md 38): one ensemble of trees has them
     def leaves(self, samples, firstTree=0, nTrees=None, byTree=False):
         raise RankLibError(LEAVES_NOT_BAGS if self.name() == "Random Forests" else
@@ -478,6 +506,24 @@ def substituted_lists(samples, fid, value):
             fv[:len(dp.fVals)] = dp.fVals
             fv[fid] = value
             pts.append(DataPoint.from_parsed(dp.label, dp.id, dp.description, fv))
+        out.append(RankList(pts))
+    return out
+
+
+def substituted_each(samples, fid, values, where):
+    """samples with feature fid of document i (file order) set to values[i] where where[i], the document itself elsewhere: new lists,
+    everything else shared.  A document too short for the feature is widened with the unknown value (NaN, which reads as 0)."""
+    out, i = [], 0
+    for rl in samples:
+        pts = []
+        for dp in rl.rl:
+            if where[i]:
+                fv = np.full(max(len(dp.fVals), fid + 1), np.nan, np.float32)
+                fv[:len(dp.fVals)] = dp.fVals
+                fv[fid] = values[i]
+                dp = DataPoint.from_parsed(dp.label, dp.id, dp.description, fv)
+            pts.append(dp)
+            i += 1
         out.append(RankList(pts))
     return out
 
@@ -769,6 +815,20 @@ class LambdaMART(Ranker):
         cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(prs))]      # noqa: E731
         one = self.partialDependence(samples, features=sorted({f for pr in prs for f in pr}), grid=grid)
         return P.summarize2(prs, grids, base.astype(np.float64), cut(mean), cut(shift2), one, cut(sc.astype(np.float64)) if ice else None)
+
+    # --- accumulated local effects in one pass (rlhip) -------------------------------------------
+    def accumulatedEffects(self, samples, features=None, intervals=20, local=False):
+        """Ranker.accumulatedEffects, bit for bit, without a substituted copy per feature: every document is walked at the two edges
+        of its own interval in every feature, and the differences are counted and summed per interval, by ONE
+        _native.Model.predict_ale call (a sum does not split over calls)."""
+        from . import partial as P
+        dps, (feats, edges) = self._aleEdges(samples, features, intervals)
+        if not feats:
+            return P.summarize_ale([], [], [], [], *(([], [], []) if local else ()))
+        count, total, lo, hi, iv, _ = self._model.predict_ale(self._rows(dps), feats, edges, local=local)
+        off = np.concatenate([[0], np.cumsum([len(z) - 1 for z in edges])]).astype(np.int64)
+        cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(feats))]      # noqa: E731
+        return P.summarize_ale(feats, edges, cut(count), cut(total), *((list(lo.astype(np.float64)), list(hi.astype(np.float64)), list(iv)) if local else ()))
 
     # --- leaf indices in one pass (rlhip, DESIGN.md 38) --------------------------------------------------------
     def leafCounts(self):

@@ -19,6 +19,18 @@ rl_model_predict_partial); every other model scores one substituted copy per cel
   -out2 tsv              one line per cell: a <TAB> b <TAB> value_a <TAB> value_b <TAB> mean <TAB> centred mean <TAB> rms shift, sorted by
                          ascending pair and values, and one further line per pair: a <TAB> b <TAB> h2 <TAB> its value
   -ice2 file             one line per cell: a <TAB> b <TAB> value_a <TAB> value_b <TAB> the score of every document in file order
+  -ale tsv               accumulated local effects: one line per edge: feature <TAB> edge <TAB> ale <TAB> local effect of
+                         the interval ending there <TAB> count.  For a LambdaMART / MART model in one GPU pass (rl_model_predict_ale).
+                         It may stand without -out: then only the accumulated local effects are computed
+  -intervals n           the intervals of a feature, 1 .. 255: n + 1 order statistics of its distinct values in the file are the edges
+                         (default 20); a feature with fewer than two distinct values has no interval and is left out
+  -local file            one line per feature and document: feature <TAB> document <TAB> interval <TAB> lo <TAB> hi
+
+Accumulated local effects answer the same question as partial dependence without leaving the data: a document is moved only between
+the two edges of the interval its own value lies in (0: it lies outside the edges and is not moved), lo and hi are its scores at the
+lower and the upper edge, the local effect of an interval is the mean of hi - lo over its documents, the curve is the running sum of the
+local effects from 0 at the first edge, centred as ALEPlot does it: minus sum n_k (ale(z_{k-1}) + ale(z_k)) / 2 / sum n_k.  Where the
+features are correlated -- LETOR's are -- partial dependence averages the model over rows that cannot occur; this does not.
 
 Lines are sorted by ascending feature, then ascending value; the numbers are printed as Double.toString.  The sums behind a mean take
 one fixed order (include/rlhip.h): partial p is the serial f64 chain over the documents [256 p, 256 p + 256), the total the serial chain
@@ -39,7 +51,7 @@ import sys
 
 import numpy as np
 
-from ._native import PARTIAL_SUM_BLOCK, RankLibError
+from ._native import ALE_MAX_INTERVALS, PARTIAL_SUM_BLOCK, RankLibError
 
 logger = logging.getLogger("ranklib_amd")
 
@@ -70,6 +82,96 @@ def fixed_order_sums(scores, base):
             p = np.cumsum(m, axis=1)[:, -1]
             out.append(float(np.cumsum(np.concatenate([[0.0], p]))[-1]))
     return out[0], out[1]
+
+
+Ale = collections.namedtuple("Ale", "features edges ale effect count centre lo hi interval")
+Ale.__doc__ = """features [F], ascending (a feature without two distinct values in the file is left out); per feature c: edges[c] f32
+[K_c + 1], ale[c] f64 [K_c + 1] the centred curve at the edges, effect[c] f64 [K_c + 1] the local effect of the interval ending at the
+edge (0 at the first), count[c] int64 [K_c + 1] its documents (0 at the first), centre[c] what was subtracted; lo, hi, interval: None, or
+per feature f64 [n_docs], f64 [n_docs] and int32 [n_docs] (0: the document is outside the edges)"""
+
+
+def ale_intervals(values, edges):
+    """int32 [n]: the interval of every own value (f32) under the strictly ascending edges z_0 < ... < z_K -- 1 + #{j in 1 .. K-1 :
+    z_j < v} where z_0 <= v <= z_K, else 0 (below, above, NaN)"""
+    v, z = np.asarray(values, np.float32), np.asarray(edges, np.float32)
+    with np.errstate(invalid="ignore"):
+        inside = (z[0] <= v) & (v <= z[-1])
+    return np.where(inside, 1 + np.searchsorted(z[1:-1], np.where(inside, v, z[0]), side="left"), 0).astype(np.int32)
+
+
+def ale_cell_sums(lo, hi, interval, K):
+    """(int64 count [K], f64 S [K]) of one column in the fixed order of include/rlhip.h: lo and hi f64 [n_docs], interval int32 [n_docs].
+    A NumPy statement of it: a document of another cell stands as +0.0, which changes no chain that started from +0.0 (such a chain
+    is never -0.0); cumsum is a serial chain, a row of the padded matrix one partial."""
+    iv = np.asarray(interval)
+    with np.errstate(all="ignore"):
+        d = np.asarray(hi, np.float64) - np.asarray(lo, np.float64)
+    parts = -(-len(d) // PARTIAL_SUM_BLOCK)
+    count, total = np.zeros(K, np.int64), np.zeros(K, np.float64)
+    for k in range(1, K + 1):
+        member = iv == k
+        count[k - 1] = int(member.sum())
+        pad = np.zeros(parts * PARTIAL_SUM_BLOCK, np.float64)
+        pad[:len(d)] = np.where(member, d, 0.0)
+        m = np.zeros((parts, PARTIAL_SUM_BLOCK + 1), np.float64)
+        m[:, 1:] = pad.reshape(parts, PARTIAL_SUM_BLOCK)
+        with np.errstate(all="ignore"):
+            total[k - 1] = _serial(np.cumsum(m, axis=1)[:, -1])
+    return count, total
+
+
+def ale_curve(count, total):
+    """(ale f64 [K + 1] centred, effect f64 [K + 1], centre) of one column's cells: effect_k = S_k / n_k (0 where n_k == 0, and at the
+    first edge), the curve their serial chain from 0 at z_0, centred as ALEPlot does it: minus the serial chain of n_k (ale(z_{k-1}) +
+    ale(z_k)) / 2 over k, divided by the sum of the n_k (0 where no document is inside)"""
+    n = np.asarray(count, np.int64)
+    with np.errstate(all="ignore"):
+        effect = np.concatenate([[0.0], np.where(n > 0, np.asarray(total, np.float64) / np.maximum(n, 1), 0.0)])
+        curve = np.cumsum(effect)
+        inside = int(n.sum())
+        centre = _serial(n.astype(np.float64) * ((curve[:-1] + curve[1:]) / 2.0)) / float(inside) if inside else 0.0
+        return curve - centre, effect, centre
+
+
+def summarize_ale(features, edges, counts, totals, lo=None, hi=None, interval=None):
+    """Ale of per-cell results: per feature count int64 [K_c] and total f64 [K_c]"""
+    curves = [ale_curve(n, s) for n, s in zip(counts, totals)]
+    return Ale([int(f) for f in features], [np.asarray(e, np.float32) for e in edges], [c[0] for c in curves], [c[1] for c in curves],
+               [np.concatenate([[0], np.asarray(n, np.int64)]) for n in counts], [c[2] for c in curves], lo, hi, interval)
+
+
+def ale_edges(samples, features, intervals):
+    """(the features that have an interval, their edges): order_statistics(values, intervals + 1) of the feature's values in samples; a
+    feature with fewer than two distinct values there has no interval, is logged and left out"""
+    n = int(intervals)
+    if not 1 <= n <= ALE_MAX_INTERVALS:
+        raise RankLibError("rlhip: -intervals must be 1 .. %d (got %d)" % (ALE_MAX_INTERVALS, n))
+    kept, edges = [], []
+    for f in features:
+        z = order_statistics([dp.fVals[f] if f < len(dp.fVals) else np.nan for rl in samples for dp in rl.rl], n + 1)
+        if len(z) < 2:
+            logger.info("Feature %d has fewer than two distinct values in the file: no interval, left out", f)
+            continue
+        kept.append(f)
+        edges.append(z)
+    return kept, edges
+
+
+def ale_lines(result):
+    """the -ale lines: ascending feature, then ascending edge"""
+    from .learning import java_double_str
+    d = lambda x: java_double_str(float(x))      # noqa: E731
+    return ["%d\t%s\t%s\t%s\t%d" % (f, d(z), d(result.ale[c][k]), d(result.effect[c][k]), int(result.count[c][k]))
+            for c, f in enumerate(result.features) for k, z in enumerate(result.edges[c])]
+
+
+def local_lines(result):
+    """the -local lines: feature <TAB> document (from 0, file order) <TAB> interval <TAB> lo <TAB> hi"""
+    from .learning import java_double_str
+    d = lambda x: java_double_str(float(x))      # noqa: E731
+    return ["%d\t%d\t%d\t%s\t%s" % (f, i, int(result.interval[c][i]), d(result.lo[c][i]), d(result.hi[c][i]))
+            for c, f in enumerate(result.features) for i in range(len(result.interval[c]))]
 
 
 def model_thresholds(ranker, feature):
@@ -237,10 +339,12 @@ def main(argv=None):
     if not args:
         print("Usage: -load model -test file [-feature file] [-grid n|thresholds] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-missingZero] "
               "[-hr] [-device d] [-out tsv] [-ice file] [-pairs file [-grid2 n|thresholds] [-out2 tsv] [-ice2 file]]")
+        print("       accumulated local effects: [-ale tsv [-intervals n] [-local file]]")
         return 0
     models, testFiles = [], []
     grid, featureFile, outFile, iceFile = "20", "", "", ""
     grid2, pairsFile, out2File, ice2File = "10", "", "", ""
+    aleFile, intervals, localFile = "", "", ""
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
     Evaluator.qrelFile = ""
@@ -257,6 +361,9 @@ def main(argv=None):
         elif a == "-grid2": grid2 = nxt()
         elif a == "-out2": out2File = nxt()
         elif a == "-ice2": ice2File = nxt()
+        elif a == "-ale": aleFile = nxt()
+        elif a == "-intervals": intervals = nxt()
+        elif a == "-local": localFile = nxt()
         elif not common_flag(a, nxt):
             cur.unknown()
     if len(models) != 1:
@@ -265,12 +372,31 @@ def main(argv=None):
         raise RankLibError("ranklib_amd.partial takes exactly one -test file (got %d)" % len(testFiles))
     if (out2File or ice2File) and not pairsFile:
         raise RankLibError("-out2 and -ice2 need -pairs file")
+    if (intervals or localFile) and not aleFile:
+        raise RankLibError("-intervals and -local need -ale tsv")
+    if intervals and not (intervals.isdigit() and 1 <= int(intervals) <= ALE_MAX_INTERVALS):
+        raise RankLibError("-intervals takes a count 1 .. %d (got %s)" % (ALE_MAX_INTERVALS, intervals))
     grid = _grid_arg("-grid", grid)
     pairs = read_pairs(pairsFile) if pairsFile else None
     ranker = RankerFactory().loadRankerFromFile(models[0])
     features = [int(f) for f in FeatureManager.readFeature(featureFile)] if featureFile else None
     e = Evaluator(RankerType.LAMBDAMART, "ERR@10", "ERR@10")
     test = e.readTestFile(ranker, testFiles[0])
+    if aleFile:
+        ale = ranker.accumulatedEffects(test, features=features, intervals=int(intervals or 20), local=bool(localFile))
+        lines = ale_lines(ale)
+        logger.info("feature\tedge\tale\tlocal effect\tcount\t(%s)", testFiles[0])
+        for ln in lines:
+            logger.info(ln)
+        with open(aleFile, "w", encoding="ascii") as out:
+            out.write("".join(ln + "\n" for ln in lines))
+        logger.info("Accumulated local effects saved to: %s", aleFile)
+        if localFile:
+            with open(localFile, "w", encoding="ascii") as out:
+                out.write("".join(ln + "\n" for ln in local_lines(ale)))
+            logger.info("Local effects saved to: %s", localFile)
+        if not (outFile or iceFile or pairsFile):
+            return 0
     res = ranker.partialDependence(test, features=features, grid=grid, ice=bool(iceFile))
     lines = table_lines(res)
     logger.info("feature\tvalue\tmean\tcentred mean\trms shift\t(%s, base mean %s)", testFiles[0], res.base_mean)
