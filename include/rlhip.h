@@ -1337,6 +1337,55 @@ int  rl_model_predict_ale(rl_model *m, const float *X, int64_t n_docs, int32_t r
  * rl_model_predict_ale call, summed over its chunks */
 int  rl_debug_ale_times(double *walk_ms, double *reduce_ms);
 
+/* ---- second-order accumulated local effects of a tree model, one pass over a file ---------------------------------------
+ * How the score moves as TWO features move together beyond what either does alone, measured only where the data is (Apley and Zhu's
+ * second-order ALE): a document is moved between the four corners of the cell its own two values lie in.  pairs [n_pairs][2] holds per
+ * pair p the columns a = pairs[2p] and b = pairs[2p+1], both >= 0 and a != b; pairs may repeat and may come in either order.  edge_off
+ * [2 n_pairs + 1] is a CSR offset array, edge_off[0] == 0: slice 2p of edges holds a's edges za_0 < ... < za_Ka, slice 2p+1 b's edges
+ * zb_0 < ... < zb_Kb, each under rl_model_predict_ale's rules (strictly ascending under <, no NaN, not -0.0 beside 0.0, +-Infinity
+ * ordinary values).  1 <= Ka, Kb <= RL_ALE_MAX_INTERVALS and Ka * Kb <= RL_ALE2_MAX_CELLS.  The cells of pair p are row-major: CELL
+ * (p, k, l), k = 1 .. Ka, l = 1 .. Kb, sits at cell_off[p] + (k - 1) * Kb + (l - 1) in the per-cell outputs, cell_off the running sum of
+ * Ka * Kb.
+ * OWN INTERVALS: k from column a and l from column b, each exactly by rl_model_predict_ale's rule: the own value is row[column], or 0
+ * where the column is >= row_stride; a value on z_0 falls in interval 1, a value on z_j in interval j; below z_0, above z_K or NaN gives
+ * 0.  A document with k == 0 or l == 0 is OUTSIDE: its cell is -1, it joins no sum, and all four of its scores are its unsubstituted
+ * score.
+ * THE FOUR SCORES of an inside document: s[ua][ub], ua, ub in {0, 1}, is Ensemble.eval's float chain (as defined for
+ * rl_model_predict_ale) on row i, taken as padded with zeros to any width, with column a set to za_{k-1+ua} and column b to
+ * zb_{l-1+ub}: bit for bit what the four matrices materialised on the host give through rl_model_predict.  THE SECOND DIFFERENCE is
+ * d = ((double)s[1][1] - (double)s[0][1]) - ((double)s[1][0] - (double)s[0][0]), every operation rounded, no FMA.
+ * PER CELL a count n_kl (int64) and S_kl, the sum of d over the cell's documents, in ONE FIXED ORDER that depends on n_docs alone, of
+ * three levels: partial p is the serial f64 chain, starting from +0.0, over those documents of [256 p, 256 p + 256) that lie in the
+ * cell, in document order (RL_PARTIAL_SUM_BLOCK); super-partial q is the serial chain from +0.0 over the partials p in [64 q, 64 q +
+ * 64), in order (RL_ALE2_SUM_SUPER: a super-block is 16 384 documents); the total is the serial chain from +0.0 over the
+ * super-partials, in order.  Up to 16 384 documents this is the two-level order of rl_model_predict_ale.  RL_ALE2_SUM_SUPER is part
+ * of the result, not a knob.  The accumulation over the cells, the removal of the two main effects and the centring are the callers'
+ * arithmetic (ranklib_amd/partial.py, summarize_ale2).
+ * out_count [cells] and out_sum [cells]; out_corner f32 [n_pairs][4][n_docs], slot 2 * ua + ub; out_cell int32 [n_pairs][n_docs], a
+ * document's (k - 1) * Kb + (l - 1) within its pair, or -1; out_base f32 [n_docs], the unsubstituted scores, one scoring pass more.  The
+ * last three may each be NULL: then nothing of that size crosses the bus.  X, pairs, edge_off, edges and the outputs are HOST pointers.
+ * The pairs are processed in chunks whose device scratch -- 12 bytes per document and pair, 28 where out_corner is asked for, plus the
+ * base -- stays within scratch_bytes (0 = 256 MiB); a chunk holds at least one pair.  The result does not depend on the chunking.
+ * Inside a chunk the kernel takes up to RL_ALE2_BATCH pairs per document at a time.
+ * RL_ERR_INVALID, the message naming the argument, all checked before the model so that a machine without a device reaches them: null
+ * X, pairs, edge_off, edges, out_count or out_sum; n_docs < 1; row_stride < 1; n_pairs < 1; a negative column or a == b ("pairs[p] =
+ * (a, b) ..."); edge_off[0] != 0; a slice with fewer than 2 or more than 256 edges; an edge that is NaN or not greater than its
+ * predecessor ("edges[slice][j] = ..."); a pair with more than RL_ALE2_MAX_CELLS cells; scratch_bytes < 0.  Then a null model and a
+ * model without trees.  RL_ERR_UNSUPPORTED: more than 2^31 documents or cells, or 2^30 pairs, per call.
+ * rl_model_debug_path reports RL_MODEL_PATH_ALE2 afterwards: one kernel serves packed and unpacked models. */
+#ifndef RL_ALE2_BATCH
+#define RL_ALE2_BATCH 4
+#endif
+#define RL_ALE2_MAX_CELLS 4096
+#define RL_ALE2_SUM_SUPER 64
+enum { RL_MODEL_PATH_ALE2 = 12 };
+int  rl_model_predict_ale2(rl_model *m, const float *X, int64_t n_docs, int32_t row_stride, const int32_t *pairs, int32_t n_pairs,
+                           const int32_t *edge_off, const float *edges, int64_t scratch_bytes, float *out_base, int64_t *out_count,
+                           double *out_sum, float *out_corner, int32_t *out_cell);
+/* debug (tools/ale2_bench.py): ms between device events around the walking and around the reducing launches of this thread's last
+ * rl_model_predict_ale2 call, summed over its chunks */
+int  rl_debug_ale2_times(double *walk_ms, double *reduce_ms);
+
 #ifdef __cplusplus
 }
 #endif

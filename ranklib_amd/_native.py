@@ -159,6 +159,7 @@ ABI_SYMBOLS = [
     "rl_set_objective", "rl_debug_xe_lambdas",
     "rl_model_leaf_counts", "rl_model_predict_leaves", "rl_debug_leaves_times",
     "rl_model_predict_ale", "rl_debug_ale_times",
+    "rl_model_predict_ale2", "rl_debug_ale2_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -361,6 +362,9 @@ def lib():
     if hasattr(L, "rl_model_predict_ale"):  # (A/B builds of older sources have no accumulated local effects)
         L.rl_model_predict_ale.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp]
         L.rl_debug_ale_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_predict_ale2"):  # (A/B builds of older sources have no second-order accumulated local effects)
+        L.rl_model_predict_ale2.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp]
+        L.rl_debug_ale2_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -825,6 +829,10 @@ PARTIAL_SUM_BLOCK = 256                           # RL_PARTIAL_SUM_BLOCK (rlhip.
 MODEL_PATH_ALE = 11                               # rl_model_predict_ale (k_model_ale_scores, k_ale_reduce)
 ALE_BATCH = 16                                    # RL_ALE_BATCH (rlhip.h): columns k_model_ale_scores takes per document at a time
 ALE_MAX_INTERVALS = 255                           # RL_ALE_MAX_INTERVALS (rlhip.h): intervals of one column at most
+MODEL_PATH_ALE2 = 12                              # rl_model_predict_ale2 (k_model_ale2_scores, k_ale2_reduce, k_ale2_finish)
+ALE2_BATCH = 4                                    # RL_ALE2_BATCH (rlhip.h): pairs k_model_ale2_scores takes per document at a time
+ALE2_MAX_CELLS = 4096                             # RL_ALE2_MAX_CELLS (rlhip.h): cells of one pair at most
+ALE2_SUM_SUPER = 64                               # RL_ALE2_SUM_SUPER (rlhip.h): partials of PARTIAL_SUM_BLOCK documents in a super-partial
 
 
 class Model:
@@ -1152,6 +1160,38 @@ class Model:
         check(L.rl_model_predict_ale(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], cbuf.ctypes.data, int(cols.size), off.ctypes.data,
                                      flat.ctypes.data, int(scratch_bytes), ptr(bs), count.ctypes.data, total.ctypes.data, ptr(lo), ptr(hi), ptr(iv)))
         return count[:cells], total[:cells], lo, hi, iv, None if bs is None else bs[:rows.shape[0]]
+
+    def predict_ale2(self, rows, pairs, edges, local=False, base=False, scratch_bytes=0):
+        """rl_model_predict_ale2: second-order accumulated local effects (DESIGN.md 40).  pairs: [n_pairs][2] columns (a, b), a != b;
+        edges: per pair (edges_a, edges_b), each strictly ascending, 2 .. 256 of them, Ka * Kb <= ALE2_MAX_CELLS.  The cells of pair p
+        are row-major, cell_off[p] + (k - 1) * Kb + (l - 1).  Returns (int64 count [cells], f64 sum [cells], corner, cell, base): count
+        and sum of the second difference d over the documents whose own two values lie in the cell, in the fixed order of
+        include/rlhip.h; with local the f32 corner [n_pairs][4][n_docs] -- slot 2 * ua + ub: the scores of rows, padded with zeros to
+        any width, with a at the lower (ua = 0) or upper edge of the document's interval and b alike -- and the int32 cell
+        [n_pairs][n_docs] within the pair (-1: outside the edges of either axis), else None; with base the f32 unsubstituted scores
+        [n_docs], else None.  rows as in predict_rows."""
+        L = lib()
+        if not hasattr(L, "rl_model_predict_ale2"):
+            raise RankLibError("rlhip: this librlhip.so has no second-order accumulated local effects (rl_model_predict_ale2)")
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        prs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2) if len(pairs) else np.zeros((0, 2), np.int32)
+        es = [np.ascontiguousarray(e, dtype=np.float32) for pair in edges for e in pair]
+        if rows.ndim != 2 or len(es) != 2 * len(prs) or any(len(pair) != 2 for pair in edges) or any(e.ndim != 1 for e in es):
+            raise RankLibError("rlhip: second-order accumulated local effects take rows [n_docs][row_stride], pairs [n_pairs][2] and one (edges_a, edges_b) of 1-d arrays per pair")
+        off = np.zeros(len(es) + 1, np.int32)
+        np.cumsum([e.size for e in es], out=off[1:])
+        flat = np.concatenate(es + [np.zeros(1, np.float32)])      # (never an empty buffer: the library names what is wrong)
+        cells = sum(max(0, es[2 * p].size - 1) * max(0, es[2 * p + 1].size - 1) for p in range(len(prs)))
+        count, total = np.zeros(max(1, cells), np.int64), np.zeros(max(1, cells), np.float64)
+        n = rows.shape[0]
+        corner, cell = (np.zeros((len(prs), 4, n), np.float32), np.zeros((len(prs), n), np.int32)) if local else (None, None)
+        bs = np.zeros(max(1, n), np.float32) if base else None
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None      # noqa: E731
+        buf = rows if rows.size else np.zeros(1, np.float32)
+        pbuf = prs if prs.size else np.zeros(2, np.int32)
+        check(L.rl_model_predict_ale2(self.h, buf.ctypes.data, n, rows.shape[1], pbuf.ctypes.data, len(prs), off.ctypes.data, flat.ctypes.data,
+                                      int(scratch_bytes), ptr(bs), count.ctypes.data, total.ctypes.data, ptr(corner), ptr(cell)))
+        return count[:cells], total[:cells], corner, cell, None if bs is None else bs[:n]
 
     def leaf_counts(self):
         """rl_model_leaf_counts: int32 [trees], the leaves of every tree"""
@@ -1708,6 +1748,13 @@ def ale_times():
     """rl_debug_ale_times: (walk ms, reduce ms) of this thread's last predict_ale call, between device events"""
     w, r = C.c_double(0), C.c_double(0)
     check(lib().rl_debug_ale_times(C.byref(w), C.byref(r)))
+    return w.value, r.value
+
+
+def ale2_times():
+    """rl_debug_ale2_times: (walk ms, reduce ms) of this thread's last predict_ale2 call, between device events"""
+    w, r = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_ale2_times(C.byref(w), C.byref(r)))
     return w.value, r.value
 
 

@@ -1073,6 +1073,7 @@ int rl_reset_timing(rl_trainer *t)
 #include "rl_partial.inc"    // partial dependence and ICE curves: k_model_partial_scores walks every (column, grid value) cell, k_partial_reduce sums them in one fixed order
 #include "rl_partial2.inc"   // two-feature partial dependence: k_model_partial2_scores descends every tree once per tile of (value of a, value of b) cells with an index rectangle, k_partial_reduce sums
 #include "rl_ale.inc"        // accumulated local effects: k_model_ale_scores walks every document at the two edges of its own interval per column, k_ale_reduce counts and sums per interval in one fixed order
+#include "rl_ale2.inc"       // second-order accumulated local effects: k_model_ale2_scores walks every document at the four corners of its own cell per pair, k_ale2_reduce and k_ale2_finish count and sum per cell in one fixed order
 #include "rl_model_rows.inc" // RowStream: a file's rows through a model kernel chunk by chunk, the host loop of the four entry points below
 #include "rl_contrib.inc"    // contributions of the features to a document's score: k_model_cover counts a background file, k_model_contribs walks the paths
 #include "rl_shap.inc"       // the same as exact TreeSHAP values: k_model_shap runs every row through the recurrence of every leaf

@@ -426,6 +426,37 @@ class Ranker:
             counts.append(n); totals.append(s); los.append(lo); his.append(hi); ivs.append(iv)
         return P.summarize_ale(feats, edges, counts, totals, *((los, his, ivs) if local else ()))
 
+    # rlhip: second-order accumulated local effects: what two features do together, measured where the data is
+    def _ale2Edges(self, samples, pairs, intervals):
+        from . import partial as P
+        prs = self._askedPairs(pairs)
+        dps = [dp for rl in samples for dp in rl.rl]
+        if not dps:
+            raise RankLibError("rlhip: accumulatedEffects2 needs at least one document")
+        return dps, P.ale2_edges(samples, prs, intervals)
+
+    def accumulatedEffects2(self, samples, pairs, intervals=10, local=False):
+        """partial.Ale2 of pairs [(a, b), ...] on samples: per pair the edges partial.ale2_edges gives (intervals + 1 order statistics
+        of either feature's values) and per pair of edges the centred second-order ALE surface, per cell its local effect and its
+        documents; with local every document's cell and its four scores too.  A document's own values (unknown or missing: 0) pick
+        its cell, and the document is scored with the two features at the cell's four corners; a document outside the edges of
+        either axis keeps its values.  This is the generic path, for every ranker: four substituted copies of the documents per pair
+        go through evalLists, and the sums take the fixed order of include/rlhip.h (partial.ale2_cell_sums)."""
+        from . import partial as P
+        dps, (prs, edges) = self._ale2Edges(samples, pairs, intervals)
+        counts, totals, corners, cells = [], [], [], []
+        for (a, b), (za, zb) in zip(prs, edges):
+            own = lambda f: np.array([dp.fVals[f] if f < len(dp.fVals) else 0.0 for dp in dps], np.float32)      # noqa: E731
+            k, l = (P.ale_intervals(np.where(np.isnan(v), np.float32(0), v), z) for v, z in ((own(a), za), (own(b), zb)))
+            inside = (k > 0) & (l > 0)
+            cell = np.where(inside, (k - 1) * (len(zb) - 1) + (l - 1), -1).astype(np.int32)
+            sc = [self.evalLists(substituted_each(substituted_each(samples, a, za[np.maximum(k, 1) - 1 + ua], inside), b,
+                                                  zb[np.maximum(l, 1) - 1 + ub], inside))[0] for ua in (0, 1) for ub in (0, 1)]
+            with np.errstate(all="ignore"):
+                n, s = P.ale2_cell_sums((sc[3] - sc[1]) - (sc[2] - sc[0]), cell, (len(za) - 1) * (len(zb) - 1))
+            counts.append(n); totals.append(s); corners.append(np.stack(sc)); cells.append(cell)
+        return P.summarize_ale2(prs, edges, counts, totals, *((corners, cells) if local else ()))
+
     # rlhip: the leaf every document reaches in every tree (DESIGN.md 38): one ensemble of trees has them
     def leaves(self, samples, firstTree=0, nTrees=None, byTree=False):
         raise RankLibError(LEAVES_NOT_BAGS if self.name() == "Random Forests" else
@@ -829,6 +860,20 @@ class LambdaMART(Ranker):
         off = np.concatenate([[0], np.cumsum([len(z) - 1 for z in edges])]).astype(np.int64)
         cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(feats))]      # noqa: E731
         return P.summarize_ale(feats, edges, cut(count), cut(total), *((list(lo.astype(np.float64)), list(hi.astype(np.float64)), list(iv)) if local else ()))
+
+    # --- second-order accumulated local effects in one pass (rlhip) ------------------------------
+    def accumulatedEffects2(self, samples, pairs, intervals=10, local=False):
+        """Ranker.accumulatedEffects2, bit for bit, without the four substituted copies per pair: every document is walked at the
+        four corners of its own cell in every pair, and the second differences are counted and summed per cell, by ONE
+        _native.Model.predict_ale2 call (a sum does not split over calls)."""
+        from . import partial as P
+        dps, (prs, edges) = self._ale2Edges(samples, pairs, intervals)
+        if not prs:
+            return P.summarize_ale2([], [], [], [], *(([], []) if local else ()))
+        count, total, corner, cell, _ = self._model.predict_ale2(self._rows(dps), prs, edges, local=local)
+        off = np.concatenate([[0], np.cumsum([(len(za) - 1) * (len(zb) - 1) for za, zb in edges])]).astype(np.int64)
+        cut = lambda a: [a[int(off[c]):int(off[c + 1])] for c in range(len(prs))]      # noqa: E731
+        return P.summarize_ale2(prs, edges, cut(count), cut(total), *((list(corner.astype(np.float64)), list(cell)) if local else ()))
 
     # --- leaf indices in one pass (rlhip, DESIGN.md 38) --------------------------------------------------------
     def leafCounts(self):

@@ -25,12 +25,27 @@ rl_model_predict_partial); every other model scores one substituted copy per cel
   -intervals n           the intervals of a feature, 1 .. 255: n + 1 order statistics of its distinct values in the file are the edges
                          (default 20); a feature with fewer than two distinct values has no interval and is left out
   -local file            one line per feature and document: feature <TAB> document <TAB> interval <TAB> lo <TAB> hi
+  -ale2 tsv              second-order accumulated local effects of the pairs of -pairs: one line per pair of edges:
+                         a <TAB> b <TAB> edge_a <TAB> edge_b <TAB> ale <TAB> local effect of the cell ending there <TAB> count.  A count
+                         of 0 away from the first edges is an empty cell: the surface there is an extrapolation.  For a LambdaMART /
+                         MART model in one GPU pass (rl_model_predict_ale2).  It may stand without -out and -out2
+  -intervals2 n          the intervals of either axis of a pair, 1 .. 64 (default 10), edges as -intervals; a pair with a feature of
+                         fewer than two distinct values is left out
+  -local2 file           one line per pair and document: a <TAB> b <TAB> document <TAB> cell <TAB> s00 <TAB> s01 <TAB> s10 <TAB> s11
 
 Accumulated local effects answer the same question as partial dependence without leaving the data: a document is moved only between
 the two edges of the interval its own value lies in (0: it lies outside the edges and is not moved), lo and hi are its scores at the
 lower and the upper edge, the local effect of an interval is the mean of hi - lo over its documents, the curve is the running sum of the
 local effects from 0 at the first edge, centred as ALEPlot does it: minus sum n_k (ale(z_{k-1}) + ale(z_k)) / 2 / sum n_k.  Where the
 features are correlated -- LETOR's are -- partial dependence averages the model over rows that cannot occur; this does not.
+
+The second-order effect of a pair is what the two features do together beyond what either does alone.  A document is moved between the
+four corners of the cell its own two values lie in (cell -1: it lies outside the edges of either axis and is not moved); s00 .. s11
+are its scores there (first digit a, second b; 0 the lower edge), d = (s11 - s01) - (s10 - s00), the local effect of a cell is the mean
+of d over its documents (0 in an empty cell).  The surface is ALEPlot's: the double running sum of the local effects over both axes
+from a zero first row and column; minus its own two main effects -- per interval of a the count-weighted mean over the cells of that
+row of the surface's step across the interval, averaged over the cell's two b edges, accumulated along a; b alike --; minus the
+count-weighted mean over all cells of the mean of the cell's four corners.
 
 Lines are sorted by ascending feature, then ascending value; the numbers are printed as Double.toString.  The sums behind a mean take
 one fixed order (include/rlhip.h): partial p is the serial f64 chain over the documents [256 p, 256 p + 256), the total the serial chain
@@ -51,7 +66,7 @@ import sys
 
 import numpy as np
 
-from ._native import ALE_MAX_INTERVALS, PARTIAL_SUM_BLOCK, RankLibError
+from ._native import ALE2_MAX_CELLS, ALE2_SUM_SUPER, ALE_MAX_INTERVALS, PARTIAL_SUM_BLOCK, RankLibError
 
 logger = logging.getLogger("ranklib_amd")
 
@@ -156,6 +171,97 @@ def ale_edges(samples, features, intervals):
         kept.append(f)
         edges.append(z)
     return kept, edges
+
+
+Ale2 = collections.namedtuple("Ale2", "pairs edges ale effect count centre corner cell")
+Ale2.__doc__ = """pairs [(a, b)] as asked (a pair with a feature of fewer than two distinct values in the file is left out); per pair p:
+edges[p] = (f32 [Ka + 1], f32 [Kb + 1]), ale[p] f64 [Ka + 1][Kb + 1] the centred second-order surface at the edges, effect[p] f64
+[Ka][Kb] the local effect of every cell (0 where it is empty), count[p] int64 [Ka][Kb], centre[p] what was subtracted last; corner,
+cell: None, or per pair f64 [4][n_docs] (slot 2 ua + ub) and int32 [n_docs] ((k - 1) Kb + l - 1; -1: outside)"""
+ALE2_MAX_INTERVALS = int(ALE2_MAX_CELLS ** 0.5)               # of either axis, where both take the same count
+
+
+def ale2_cell_sums(d, cell, cells):
+    """(int64 count [cells], f64 S [cells]) of one pair in the three-level fixed order of include/rlhip.h: d f64 [n_docs], cell int32
+    [n_docs] (-1: outside).  A NumPy statement of it, as ale_cell_sums: a row of the padded matrix is one partial, a row of the padded
+    partials one super-partial, every chain starts from +0.0 and a +0.0 term changes none."""
+    d, cell = np.asarray(d, np.float64), np.asarray(cell)
+    parts = -(-len(d) // PARTIAL_SUM_BLOCK)
+    supers = -(-parts // ALE2_SUM_SUPER)
+    count, total = np.zeros(cells, np.int64), np.zeros(cells, np.float64)
+    for c in np.unique(cell[cell >= 0]):
+        member = cell == c
+        count[c] = int(member.sum())
+        pad = np.zeros(supers * ALE2_SUM_SUPER * PARTIAL_SUM_BLOCK, np.float64)
+        pad[:len(d)] = np.where(member, d, 0.0)
+        with np.errstate(all="ignore"):
+            for width in (PARTIAL_SUM_BLOCK, ALE2_SUM_SUPER):
+                m = np.zeros((len(pad) // width, width + 1), np.float64)
+                m[:, 1:] = pad.reshape(-1, width)
+                pad = np.cumsum(m, axis=1)[:, -1]
+            total[c] = _serial(pad)
+    return count, total
+
+
+def ale2_surface(count, total):
+    """(ale f64 [Ka + 1][Kb + 1] centred, effect f64 [Ka][Kb], centre) of one pair's cells, count and total [Ka][Kb]: ALEPlot's rule, the
+    module's text.  cumsum along a, then along b; the sums over a row, a column and all cells are NumPy's."""
+    n = np.asarray(count, np.int64)
+    b = n.astype(np.float64)
+    with np.errstate(all="ignore"):
+        effect = np.where(n > 0, np.asarray(total, np.float64) / np.maximum(n, 1), 0.0)
+        acc = np.zeros((n.shape[0] + 1, n.shape[1] + 1), np.float64)
+        acc[1:, 1:] = np.cumsum(np.cumsum(effect, axis=0), axis=1)
+        da, db = acc[1:, :] - acc[:-1, :], acc[:, 1:] - acc[:, :-1]
+        rows, cols = b.sum(axis=1), b.sum(axis=0)
+        ma = np.where(rows > 0, (b * ((da[:, :-1] + da[:, 1:]) / 2.0)).sum(axis=1) / np.maximum(rows, 1.0), 0.0)
+        mb = np.where(cols > 0, (b * ((db[:-1, :] + db[1:, :]) / 2.0)).sum(axis=0) / np.maximum(cols, 1.0), 0.0)
+        surf = acc - np.concatenate([[0.0], np.cumsum(ma)])[:, None] - np.concatenate([[0.0], np.cumsum(mb)])[None, :]
+        inside = float(b.sum())
+        four = (surf[:-1, :-1] + surf[:-1, 1:] + surf[1:, :-1] + surf[1:, 1:]) / 4.0
+        centre = float((b * four).sum()) / inside if inside else 0.0
+        return surf - centre, effect, centre
+
+
+def summarize_ale2(pairs, edges, counts, totals, corner=None, cell=None):
+    """Ale2 of per-cell results: per pair count int64 [Ka * Kb] and total f64 [Ka * Kb], row-major"""
+    edges = [(np.asarray(za, np.float32), np.asarray(zb, np.float32)) for za, zb in edges]
+    shape = [(len(za) - 1, len(zb) - 1) for za, zb in edges]
+    counts = [np.asarray(n, np.int64).reshape(sh) for n, sh in zip(counts, shape)]
+    surfs = [ale2_surface(n, np.asarray(s, np.float64).reshape(sh)) for n, s, sh in zip(counts, totals, shape)]
+    return Ale2([(int(a), int(b)) for a, b in pairs], edges, [s[0] for s in surfs], [s[1] for s in surfs], counts, [s[2] for s in surfs], corner, cell)
+
+
+def ale2_edges(samples, pairs, intervals):
+    """(the pairs both of whose features have an interval, their (edges_a, edges_b)): ale_edges per feature; the other pairs are left out"""
+    n = int(intervals)
+    if not 1 <= n <= ALE2_MAX_INTERVALS:
+        raise RankLibError("rlhip: -intervals2 must be 1 .. %d (got %d)" % (ALE2_MAX_INTERVALS, n))
+    feats, zs = ale_edges(samples, sorted({f for pr in pairs for f in pr}), n)
+    z = dict(zip(feats, zs))
+    kept = [(a, b) for a, b in pairs if a in z and b in z]
+    return kept, [(z[a], z[b]) for a, b in kept]
+
+
+def ale2_lines(result):
+    """the -ale2 lines: ascending pair, then ascending edges; a pair asked twice is written once"""
+    from .learning import java_double_str
+    d = lambda x: java_double_str(float(x))      # noqa: E731
+    first = {pr: p for p, pr in reversed(list(enumerate(result.pairs)))}
+    out = []
+    for (a, b), p in sorted(first.items()):
+        za, zb = result.edges[p]
+        out += ["%d\t%d\t%s\t%s\t%s\t%s\t%d" % (a, b, d(za[k]), d(zb[l]), d(result.ale[p][k, l]), d(result.effect[p][k - 1, l - 1] if k and l else 0.0),
+                                                int(result.count[p][k - 1, l - 1]) if k and l else 0) for k in range(len(za)) for l in range(len(zb))]
+    return out
+
+
+def local2_lines(result):
+    """the -local2 lines: a <TAB> b <TAB> document (from 0, file order) <TAB> cell <TAB> s00 <TAB> s01 <TAB> s10 <TAB> s11"""
+    from .learning import java_double_str
+    d = lambda x: java_double_str(float(x))      # noqa: E731
+    return ["%d\t%d\t%d\t%d\t%s" % (a, b, i, int(result.cell[p][i]), "\t".join(d(result.corner[p][c][i]) for c in range(4)))
+            for p, (a, b) in enumerate(result.pairs) for i in range(len(result.cell[p]))]
 
 
 def ale_lines(result):
@@ -340,11 +446,13 @@ def main(argv=None):
         print("Usage: -load model -test file [-feature file] [-grid n|thresholds] [-norm sum|zscore|linear] [-qrel f] [-gmax g] [-missingZero] "
               "[-hr] [-device d] [-out tsv] [-ice file] [-pairs file [-grid2 n|thresholds] [-out2 tsv] [-ice2 file]]")
         print("       accumulated local effects: [-ale tsv [-intervals n] [-local file]]")
+        print("       second-order accumulated local effects of the pairs: [-ale2 tsv [-intervals2 n] [-local2 file]]")
         return 0
     models, testFiles = [], []
     grid, featureFile, outFile, iceFile = "20", "", "", ""
     grid2, pairsFile, out2File, ice2File = "10", "", "", ""
     aleFile, intervals, localFile = "", "", ""
+    ale2File, intervals2, local2File = "", "", ""
     Evaluator.mustHaveRelDoc = False
     Evaluator.normalize = False
     Evaluator.qrelFile = ""
@@ -364,6 +472,9 @@ def main(argv=None):
         elif a == "-ale": aleFile = nxt()
         elif a == "-intervals": intervals = nxt()
         elif a == "-local": localFile = nxt()
+        elif a == "-ale2": ale2File = nxt()
+        elif a == "-intervals2": intervals2 = nxt()
+        elif a == "-local2": local2File = nxt()
         elif not common_flag(a, nxt):
             cur.unknown()
     if len(models) != 1:
@@ -376,6 +487,12 @@ def main(argv=None):
         raise RankLibError("-intervals and -local need -ale tsv")
     if intervals and not (intervals.isdigit() and 1 <= int(intervals) <= ALE_MAX_INTERVALS):
         raise RankLibError("-intervals takes a count 1 .. %d (got %s)" % (ALE_MAX_INTERVALS, intervals))
+    if (intervals2 or local2File) and not ale2File:
+        raise RankLibError("-intervals2 and -local2 need -ale2 tsv")
+    if ale2File and not pairsFile:
+        raise RankLibError("-ale2 needs -pairs file")
+    if intervals2 and not (intervals2.isdigit() and 1 <= int(intervals2) <= ALE2_MAX_INTERVALS):
+        raise RankLibError("-intervals2 takes a count 1 .. %d (got %s)" % (ALE2_MAX_INTERVALS, intervals2))
     grid = _grid_arg("-grid", grid)
     pairs = read_pairs(pairsFile) if pairsFile else None
     ranker = RankerFactory().loadRankerFromFile(models[0])
@@ -396,6 +513,21 @@ def main(argv=None):
                 out.write("".join(ln + "\n" for ln in local_lines(ale)))
             logger.info("Local effects saved to: %s", localFile)
         if not (outFile or iceFile or pairsFile):
+            return 0
+    if ale2File:
+        ale2 = ranker.accumulatedEffects2(test, pairs, intervals=int(intervals2 or 10), local=bool(local2File))
+        lines = ale2_lines(ale2)
+        logger.info("a\tb\tedge a\tedge b\tale\tlocal effect\tcount\t(%s)", testFiles[0])
+        for ln in lines:
+            logger.info(ln)
+        with open(ale2File, "w", encoding="ascii") as out:
+            out.write("".join(ln + "\n" for ln in lines))
+        logger.info("Second-order accumulated local effects saved to: %s", ale2File)
+        if local2File:
+            with open(local2File, "w", encoding="ascii") as out:
+                out.write("".join(ln + "\n" for ln in local2_lines(ale2)))
+            logger.info("Local second-order effects saved to: %s", local2File)
+        if not (outFile or iceFile or out2File or ice2File):
             return 0
     res = ranker.partialDependence(test, features=features, grid=grid, ice=bool(iceFile))
     lines = table_lines(res)
