@@ -1386,6 +1386,38 @@ int  rl_model_predict_ale2(rl_model *m, const float *X, int64_t n_docs, int32_t 
  * rl_model_predict_ale2 call, summed over its chunks */
 int  rl_debug_ale2_times(double *walk_ms, double *reduce_ms);
 
+/* ---- nearest neighbours in leaf space, one pass over two files -----------------------------------------------------------
+ * "Which reference documents does the model treat like this one?": the proximity of random-forest practice, the supervised kernel of a
+ * GBDT.  LEAF NUMBERS: leaf(d, t) is exactly rl_model_predict_leaves' leaf number, for the trees [first_tree, first_tree + n_trees) of
+ * the model, n_trees == 0 meaning "through the last tree".  SHARED COUNT: shared(q, r) = the number of trees of the window in which query
+ * row q (of Xq [nq][row_stride]) and reference row r (of Xr [nr][row_stride]) reach the same leaf; tree weights play no part; 0 <= shared
+ * <= n_trees.  ORDER OF REFERENCES: for a query the references are ordered by shared descending, then by reference index ascending -- a
+ * total order, so the first k are unique whatever the order of evaluation.
+ * out_index int32 [nq][k] and out_shared int32 [nq][k]: the first k eligible references of every query in that order and their counts;
+ * slots beyond the number of eligible references hold index -1 and count 0.  Every reference is eligible, except that with
+ * RL_NEAR_SKIP_SAME_INDEX reference r == q is not: the flag for calls whose query set IS the reference set.  out_matrix (may be NULL)
+ * uint16 [nq][nr], every shared(q, r), the ineligible included: for small sets (clustering, tests).  When it is NULL nothing of that
+ * size exists anywhere; when it is given, 2 bytes per (query of a chunk, reference of a band) come on top of the scratch below.
+ * All pointers are HOST pointers.  Both sets are walked on the device into leaf-number buffers that never cross the bus, and matched
+ * there.  The rows and leaf numbers on the device -- 4 row_stride + 2 (n_trees rounded up to 4) bytes a row -- stay within scratch_bytes
+ * (0 = 256 MiB): a quarter for a chunk of queries, the rest for a band of references, a chunk of at least 64 and a band of at least 128
+ * rows.  Every chunk meets every band (the bands are walked again for every chunk).  THE RESULT DOES NOT DEPEND on tiles, splits, bands
+ * or chunks.
+ * RL_ERR_INVALID, the message naming the argument, all checked before the model so that a machine without a device reaches them: null
+ * Xq, Xr, out_index or out_shared; nq < 1; nr < 1; row_stride < 1; k outside [1, RL_NEAR_MAX_K]; unknown flag bits; scratch_bytes < 0;
+ * first_tree or n_trees negative.  Then a null model, a model without trees, a window outside the model (rl_model_predict_leaves' words).
+ * RL_ERR_UNSUPPORTED: more than 2^31 rows on either side; a window of more than 65 535 trees; a tree of the window with more than
+ * 65 536 leaves.  rl_model_debug_path reports RL_MODEL_PATH_NEIGHBOURS afterwards, whichever kernel walked. */
+enum { RL_MODEL_PATH_NEIGHBOURS = 13 };
+enum { RL_NEAR_SKIP_SAME_INDEX = 1 };
+#define RL_NEAR_MAX_K 64
+int  rl_model_predict_neighbours(rl_model *m, const float *Xq, int64_t nq, const float *Xr, int64_t nr, int32_t row_stride,
+                                 int32_t first_tree, int32_t n_trees, int32_t k, int32_t flags, int64_t scratch_bytes,
+                                 int32_t *out_index, int32_t *out_shared, uint16_t *out_matrix);
+/* debug (tools/near_bench.py): ms between device events around the walks and around the matching and merging launches of this thread's
+ * last rl_model_predict_neighbours call, summed over its chunks and bands */
+int  rl_debug_neighbours_times(double *walk_ms, double *match_ms);
+
 #ifdef __cplusplus
 }
 #endif

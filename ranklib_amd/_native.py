@@ -160,6 +160,7 @@ ABI_SYMBOLS = [
     "rl_model_leaf_counts", "rl_model_predict_leaves", "rl_debug_leaves_times",
     "rl_model_predict_ale", "rl_debug_ale_times",
     "rl_model_predict_ale2", "rl_debug_ale2_times",
+    "rl_model_predict_neighbours", "rl_debug_neighbours_times",
 ]
 
 HOST_ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32)
@@ -365,6 +366,9 @@ def lib():
     if hasattr(L, "rl_model_predict_ale2"):  # (A/B builds of older sources have no second-order accumulated local effects)
         L.rl_model_predict_ale2.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp]
         L.rl_debug_ale2_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "rl_model_predict_neighbours"):  # (A/B builds of older sources have no neighbours in leaf space)
+        L.rl_model_predict_neighbours.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i64, vp, vp, vp]
+        L.rl_debug_neighbours_times.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -833,6 +837,12 @@ MODEL_PATH_ALE2 = 12                              # rl_model_predict_ale2 (k_mod
 ALE2_BATCH = 4                                    # RL_ALE2_BATCH (rlhip.h): pairs k_model_ale2_scores takes per document at a time
 ALE2_MAX_CELLS = 4096                             # RL_ALE2_MAX_CELLS (rlhip.h): cells of one pair at most
 ALE2_SUM_SUPER = 64                               # RL_ALE2_SUM_SUPER (rlhip.h): partials of PARTIAL_SUM_BLOCK documents in a super-partial
+MODEL_PATH_NEIGHBOURS = 13                        # rl_model_predict_neighbours (the leaves' walk, k_near_match, k_near_merge)
+NEAR_MAX_K = 64                                   # RL_NEAR_MAX_K (rlhip.h)
+NEAR_SKIP_SAME_INDEX = 1                          # RL_NEAR_SKIP_SAME_INDEX (rlhip.h)
+# k_near_match's shape (rl_near_host.h): queries of a block, references of one step of its sweep, trees staged at a time, and the blocks
+# a launch aims at: a band of r reference tiles under q query tiles is cut into about min(63, r, ceil(NEAR_BLOCKS / q)) splits
+NEAR_QUERY_TILE, NEAR_REF_TILE, NEAR_TREE_CHUNK, NEAR_BLOCKS = 64, 128, 64, 1024
 
 
 class Model:
@@ -1217,6 +1227,30 @@ class Model:
         check(L.rl_model_predict_leaves(self.h, buf.ctypes.data, rows.shape[0], rows.shape[1], int(first_tree), ask, 1 if by_tree else 0,
                                         obuf.ctypes.data))
         return out
+
+    def predict_neighbours(self, queries, reference, k, first_tree=0, n_trees=None, skip_same=False, matrix=False, scratch_bytes=0):
+        """rl_model_predict_neighbours: (index int32 [nq][k], shared int32 [nq][k]) -- per query row the k reference rows that reach the
+        same leaf in the most trees of [first_tree, first_tree + n_trees) (n_trees None: through the last tree), ordered by shared
+        descending, then index ascending; slots without an eligible reference hold -1 and 0.  skip_same: reference
+        r == q is not eligible (the query set is the reference set).  matrix: a third result, uint16 [nq][nr], every shared count.
+        queries and reference as in predict_rows, of one width."""
+        L = lib()
+        if not hasattr(L, "rl_model_predict_neighbours"):
+            raise RankLibError("rlhip: this librlhip.so has no neighbours in leaf space (rl_model_predict_neighbours)")
+        q, r = np.ascontiguousarray(queries, dtype=np.float32), np.ascontiguousarray(reference, dtype=np.float32)
+        if q.ndim != 2 or r.ndim != 2:
+            raise RankLibError("rlhip: neighbours take queries [nq][row_stride] and reference [nr][row_stride]")
+        qbuf, rbuf = (a if a.size else np.zeros(1, np.float32) for a in (q, r))      # (no rows: still a pointer that is not null)
+        if q.shape[1] != r.shape[1]:
+            raise RankLibError("rlhip: queries and reference rows must have one width (got %d and %d)" % (q.shape[1], r.shape[1]))
+        kk = max(1, min(int(k), NEAR_MAX_K))                         # (a k the library refuses is refused before anything is written)
+        nq, nr = q.shape[0], r.shape[0]
+        index, shared = np.zeros((max(1, nq), kk), np.int32), np.zeros((max(1, nq), kk), np.int32)      # (never an empty buffer: the library names what is wrong)
+        mat = np.zeros((max(1, nq), max(1, nr)), np.uint16) if matrix else None
+        check(L.rl_model_predict_neighbours(self.h, qbuf.ctypes.data, nq, rbuf.ctypes.data, nr, q.shape[1], int(first_tree),
+                                            0 if n_trees is None else int(n_trees), int(k), NEAR_SKIP_SAME_INDEX if skip_same else 0,
+                                            int(scratch_bytes), index.ctypes.data, shared.ctypes.data, None if mat is None else mat.ctypes.data))
+        return (index[:nq], shared[:nq], mat[:nq, :nr]) if matrix else (index[:nq], shared[:nq])
 
     def path(self):
         """MODEL_PATH_* of the last predict call: which kernel it took"""
@@ -1763,6 +1797,13 @@ def leaves_times():
     w = C.c_double(0)
     check(lib().rl_debug_leaves_times(C.byref(w)))
     return w.value
+
+
+def debug_neighbours_times():
+    """rl_debug_neighbours_times: (walk ms, match ms) of this thread's last predict_neighbours call, between device events"""
+    w, r = C.c_double(0), C.c_double(0)
+    check(lib().rl_debug_neighbours_times(C.byref(w), C.byref(r)))
+    return w.value, r.value
 
 
 def permuted_times():

@@ -234,6 +234,56 @@ static int leaves_prepare(rl_model *m)
     return RL_OK;
 }
 
+// The walk of a window of trees into DEVICE memory: what rl_model_predict_leaves launches per chunk, and what rl_near.inc launches into
+// the leaf-number buffers its match reads.  open() makes the model's tables (leaves_prepare), picks the kernel and deals the window;
+// launch() enqueues one walk of nr rows dX [nr][row_stride] on the null stream: out [n_trees][ld] by tree, ld >= nr, or [nr][ld] by row,
+// ld >= n_trees -- the writer takes its 64-bit stores where ld is a multiple of 4.
+struct LeavesWalk {
+    rl_model *m = nullptr;
+    bool tiled = false;
+    int cols = 0, row_stride = 0, first_tree = 0, n_trees = 0;
+    size_t lds = 0;
+    int64_t tree_tiles = 0;
+    unsigned char *d_perm = nullptr, *d_meta = nullptr;
+
+    int open(rl_model *model, DevPool &pool, const std::string &w, int32_t stride, int32_t first, int32_t nt)
+    {
+        m = model; row_stride = stride; first_tree = first; n_trees = nt;
+        tree_tiles = ((int64_t)nt + kEvalTreeTile - 1) / kEvalTreeTile;
+        const int rc = leaves_prepare(m);
+        if (rc) return rc;
+        cols = (int)std::min<int64_t>(INT32_MAX, std::max<int64_t>(row_stride, (int64_t)m->maxcol + 1));
+        lds = leaves_tiled_lds(cols, m->maxn);
+        tiled = m->d_leaf_pack && lds <= kEvalLdsBudget && !m->knobs.generic;
+        if (!tiled && tree_tiles > 65535) return fail(RL_ERR_UNSUPPORTED, w + "more than 65535 tiles of trees per call of the generic kernel");
+        if (tiled) {                                                           // the window as tiles of its own
+            std::vector<unsigned char> perm, meta;
+            leaves_deal_window(m->leaf_depth.data() + first_tree, n_trees, m->knobs.deal, m->knobs.phased, perm, meta);
+            RL_HIP(pool.upload(&d_perm, perm.data(), perm.size()));
+            RL_HIP(pool.upload(&d_meta, meta.data(), meta.size()));
+        }
+        return RL_OK;
+    }
+
+    int launch(bool by_tree, const float *dX, int64_t nr, uint16_t *dO, int64_t ld) const
+    {
+        const int64_t tiles = (nr + kEvalDocs - 1) / kEvalDocs;
+        if (tiled) {
+            const unsigned long long *nodes = m->d_leaf_pack + (size_t)first_tree * m->maxn;
+            auto k = by_tree ? k_model_leaves_tiled<true> : k_model_leaves_tiled<false>;
+            hipLaunchKernelGGL(k, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256)), dim3(kEvalThreads), lds, 0, nodes, m->maxn, (int)n_trees,
+                               dX, nr, row_stride, cols, dO, ld, (const unsigned char *)d_perm, (const unsigned char *)d_meta);
+        } else {
+            // (document tiles x tree tiles): a long window fills the chip even with few documents
+            auto k = by_tree ? k_model_leaves<true> : k_model_leaves<false>;
+            hipLaunchKernelGGL(k, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256), (unsigned)tree_tiles), dim3(kThreads), 0, 0, m->ens,
+                               (const uint16_t *)m->d_leaf_no, m->maxn, (int)first_tree, (int)n_trees, dX, nr, row_stride, dO, ld);
+        }
+        RL_HIP(hipGetLastError());
+        return RL_OK;
+    }
+};
+
 }  // namespace rl
 
 extern "C" {
@@ -258,46 +308,21 @@ int rl_model_predict_leaves(rl_model *m, const float *X, int64_t n_docs, int32_t
         if (leaves_count(m->trees[t]) > kLeavesMax)
             return fail(RL_ERR_UNSUPPORTED, w + "tree " + std::to_string(t) + " has " + std::to_string(leaves_count(m->trees[t])) +
                                                 " leaves: a leaf number is 16 bits, 65536 leaves at most");
-    const int64_t tree_tiles = ((int64_t)n_trees + kEvalTreeTile - 1) / kEvalTreeTile;
     g_lv_walk_ms = 0.0;
     if (n_docs == 0) return RL_OK;
     RL_HIP(hipSetDevice(m->device));
-    if ((rc = leaves_prepare(m))) return rc;
     const bool by_tree = layout == RL_LEAVES_BY_TREE;
-    const int cols = (int)std::min<int64_t>(INT32_MAX, std::max<int64_t>(row_stride, (int64_t)m->maxcol + 1));
-    const size_t lds = leaves_tiled_lds(cols, m->maxn);
-    const bool tiled = m->d_leaf_pack && lds <= kEvalLdsBudget && !m->knobs.generic;
-    if (!tiled && tree_tiles > 65535) return fail(RL_ERR_UNSUPPORTED, w + "more than 65535 tiles of trees per call of the generic kernel");
     RowStream rows;
     uint16_t *dO = nullptr;
-    unsigned char *d_perm = nullptr, *d_meta = nullptr;
     if ((rc = rows.open(n_docs, row_stride, 0, (int64_t)row_stride * 4 + 2 * (int64_t)n_trees))) return rc;
     // A chunk that is not the whole call holds whole document tiles: its BY_TREE rows are then even (the writer's 32-bit stores) and every
     // tile's part of a row is a whole 128-byte line.  Only the call's last chunk can have an odd length.
     if (rows.chunk < n_docs && rows.chunk >= kEvalDocs) rows.chunk -= rows.chunk % kEvalDocs;
     RL_HIP(rows.pool.alloc(&dO, (size_t)rows.chunk * n_trees));
-    if (tiled) {                                                               // the window as tiles of its own
-        std::vector<unsigned char> perm, meta;
-        leaves_deal_window(m->leaf_depth.data() + first_tree, n_trees, m->knobs.deal, m->knobs.phased, perm, meta);
-        RL_HIP(rows.pool.upload(&d_perm, perm.data(), perm.size()));
-        RL_HIP(rows.pool.upload(&d_meta, meta.data(), meta.size()));
-    }
-    auto walk = [&](int64_t nr) -> int {
-        const int64_t tiles = (nr + kEvalDocs - 1) / kEvalDocs, ld = by_tree ? nr : (int64_t)n_trees;
-        if (tiled) {
-            const unsigned long long *nodes = m->d_leaf_pack + (size_t)first_tree * m->maxn;
-            auto k = by_tree ? k_model_leaves_tiled<true> : k_model_leaves_tiled<false>;
-            hipLaunchKernelGGL(k, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256)), dim3(kEvalThreads), lds, 0, nodes, m->maxn, (int)n_trees,
-                               (const float *)rows.dX, nr, row_stride, cols, dO, ld, (const unsigned char *)d_perm, (const unsigned char *)d_meta);
-        } else {
-            // (document tiles x tree tiles): a long window fills the chip even with few documents
-            auto k = by_tree ? k_model_leaves<true> : k_model_leaves<false>;
-            hipLaunchKernelGGL(k, dim3((unsigned)std::min<int64_t>(tiles, 256 * 256), (unsigned)tree_tiles), dim3(kThreads), 0, 0, m->ens,
-                               (const uint16_t *)m->d_leaf_no, m->maxn, (int)first_tree, (int)n_trees, (const float *)rows.dX, nr, row_stride, dO, ld);
-        }
-        RL_HIP(hipGetLastError());
-        return RL_OK;
-    };
+    LeavesWalk lw;
+    if ((rc = lw.open(m, rows.pool, w, row_stride, first_tree, n_trees))) return rc;
+    const bool tiled = lw.tiled;
+    auto walk = [&](int64_t nr) -> int { return lw.launch(by_tree, rows.dX, nr, dO, by_tree ? nr : (int64_t)n_trees); };
     if (!by_tree) {                                                            // a chunk's rows are one contiguous piece of out
         rc = rows.run(X, n_docs, row_stride, walk, (const uint16_t *)dO, out, (int64_t)n_trees);
         g_lv_walk_ms = rows.ms;

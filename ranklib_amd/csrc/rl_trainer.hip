@@ -1080,5 +1080,6 @@ int rl_reset_timing(rl_trainer *t)
 #include "rl_interact.inc"   // SHAP interaction values: k_model_interact runs that recurrence once per conditioned element, k_interact_finish makes the diagonal
 #include "rl_interv.inc"     // interventional TreeSHAP against background rows: k_interv_masks makes the background's masks, k_model_interv meets every (row, background row, leaf)
 #include "rl_leaves.inc"     // leaf indices (pred_leaf): k_model_leaves_tiled walks as the scorer does and a writer wavefront transposes the leaf numbers out, k_model_leaves for unpacked models
+#include "rl_near.inc"       // neighbours in leaf space: both sets walked into device leaf numbers, k_near_match counts shared leaves in register tiles and keeps every query's best k, k_near_merge merges splits and bands
 #include "rl_resume.inc"     // resume: rl_adopt_model_text replays a saved model's trees as this trainer's first rounds (k_replay_scores)
 #include "rl_refit.inc"      // refit: rl_refit_model_text keeps those trees' structure and recomputes their leaf values on this trainer's data (k_refit_route)

@@ -462,6 +462,11 @@ class Ranker:
         raise RankLibError(LEAVES_NOT_BAGS if self.name() == "Random Forests" else
                            "rlhip: leaves needs a LambdaMART or MART model: a %s model has no trees" % self.name())
 
+    # rlhip: the reference documents that share the most leaves with a document: as leaves, one ensemble of trees
+    def neighbours(self, samples, reference, k=10, firstTree=0, nTrees=None, skipSame=False):
+        raise RankLibError(NEIGHBOURS_NOT_BAGS if self.name() == "Random Forests" else
+                           "rlhip: neighbours needs a LambdaMART or MART model: a %s model has no trees" % self.name())
+
     def save(self, modelFile):        # :106-122
         d = modelFile.rsplit("/", 1)[0] if "/" in modelFile else None
         if d:
@@ -579,6 +584,8 @@ DART_NOT_BAGS = ("rlhip: -dart trains one LambdaMART (-ranker 6) or MART (-ranke
                  "(-ranker 8) are trainers of their own and are not built for it")
 LEAVES_NOT_BAGS = ("rlhip: leaves numbers the leaves of one LambdaMART (-ranker 6) or MART (-ranker 0) model; the bags of Random Forests "
                    "(-ranker 8) are ensembles of their own and are not built for it")
+NEIGHBOURS_NOT_BAGS = ("rlhip: neighbours counts the shared leaves of one LambdaMART (-ranker 6) or MART (-ranker 0) model; the bags of Random "
+                       "Forests (-ranker 8) are ensembles of their own and are not built for it")
 XE_NOT_BAGS = ("rlhip: -objective xendcg trains one LambdaMART (-ranker 6) model on the XE-NDCG loss; the bags of Random Forests "
                "(-ranker 8) are trainers of their own and are not built for it")
 
@@ -891,6 +898,17 @@ class LambdaMART(Ranker):
         if not parts:
             return self._model.predict_leaves(np.zeros((0, 1), np.float32), firstTree, nTrees, byTree)
         return np.concatenate(parts, axis=1 if byTree else 0)
+
+    # --- neighbours in leaf space in one pass (rlhip) --------------------------------------------
+    def neighbours(self, samples, reference, k=10, firstTree=0, nTrees=None, skipSame=False):
+        """(index int32 [n_docs][k], shared int32 [n_docs][k]): per document of samples the k documents of reference that reach the same
+        leaf in the most trees of [firstTree, firstTree + nTrees) (nTrees None: through the last), ordered by shared trees descending,
+        then by their place in reference ascending; -1 and 0 where reference has no further document.  skipSame: the document at a
+        document's own place is left out (samples is reference).  samples, reference: RankLists, or arrays of rows [n_docs][row_stride]
+        as predict_rows takes them.  ONE _native.Model.predict_neighbours call: the library cuts both sets into chunks itself."""
+        rows = lambda s: s if isinstance(s, np.ndarray) else self._rows([dp for rl in s for dp in rl.rl])      # noqa: E731
+        q = rows(samples)
+        return self._model.predict_neighbours(q, q if reference is samples else rows(reference), k, firstTree, nTrees, skipSame)
 
     # --- per-document feature contributions (rlhip, DESIGN.md 26) ----------------------------------------------
     def _rowChunks(self, samples):
